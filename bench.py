@@ -21,9 +21,19 @@ seed and index) and fills its shard of the global operand array with the values 
 (he355_fill_uniform_at), so the job computes the same global batch at every world size.
 
 Timing: W untimed warm-up steps, barrier + synchronize, K timed steps, barrier + synchronize, MAX over ranks; `value` =
-results of all ranks / that time.  Inputs and keys are resident in HBM before the timed region.  Rank 0 at N=1 also times the
-oracle (CPU port, `cpu_baseline`) on a bounded sample; every rank pushes a small sample of ITS shard through the checker and
-compares bit for bit (`parity`): a mismatch on any rank makes the run exit non-zero.
+results of all ranks / that time.  Inputs and keys are resident in HBM before the timed region.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (--dump-outputs), print the
+line.  --full adds everything else, each in untimed work of its own after the timed steps: at N > 1 without --scaling the second
+scaling (a `weak` block beside the strong `value`); the shader clock probe, package power and the single-stream dominant-kernel
+timing under `roofline`; the oracle (CPU port, `cpu_baseline`) timed by rank 0 at N=1 on a bounded sample; every rank pushing a
+small sample of ITS shard through the checker, bit for bit (`parity`: a mismatch on any rank makes the run exit non-zero); the
+collective check and per-rank devices at N > 1; a checksum of the first results.
+
+  --dump-outputs DIR           after the timed steps, write what the last timed step computed as DIR/result.npy (DIR/result_rank<r>.npy
+                               at N > 1): a fixed, seeded sample of the step's result ciphertexts, every u64 residue word exactly as
+                               two float64 numbers (high and low 32 bits); see dump_outputs().  Inputs and keys come from fixed seeds,
+                               so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -423,11 +433,54 @@ def self_launch(n_gpus: int) -> int:
 
 def scalings_of(args, world):
     """The scalings one invocation times, primary first.  N = 1: one run (both scalings are the same job).  N > 1 without --scaling: BOTH --
-    `value` answers north_star's strong question (the GLOBAL batch is --batch, 1024 for the headline, at every N: ">= 6x at 8 GPUs"), and a
-    `weak` block beside it times --batch results PER GPU (the 1-GPU load on every GPU).  --scaling weak|strong times that one only."""
+    `value` answers north_star's strong question (the GLOBAL batch is --batch, 1024 for the headline, at every N: ">= 6x at 8 GPUs"), and
+    with --full a `weak` block beside it times --batch results PER GPU (the 1-GPU load on every GPU).  --scaling weak|strong times that one only."""
     if args.scaling:
         return [args.scaling]
-    return ["weak"] if world == 1 else ["strong", "weak"]
+    if world == 1:
+        return ["weak"]
+    return ["strong", "weak"] if args.full else ["strong"]
+
+
+DUMP_SEED = 20251016
+DUMP_RESULTS = 8            # result ciphertexts in the sample (the first and the last of the step always among them)
+DUMP_VALUES = 6_000_000     # float64 numbers written in all: 48 MB
+
+
+def dump_sample(n, polys, N, seed=DUMP_SEED, results=DUMP_RESULTS, values=DUMP_VALUES):
+    """(result indices, coefficient positions or None for all) of the fixed sample --dump-outputs writes: `results` of the step's n
+    results drawn by a seeded generator, the first and the last always among them, sorted; when their `polys` residue polynomials
+    of N coefficients, two float64 numbers per word, exceed `values`, a seeded sorted subset of the coefficient positions, the same
+    in every polynomial.  A function of its arguments only."""
+    rng = np.random.default_rng(seed)
+    ends = sorted({0, n - 1})
+    inner = rng.choice(np.arange(1, n - 1), size=min(results, n) - len(ends), replace=False) if n > 2 else np.zeros(0, dtype=np.int64)
+    idx = np.array(sorted(ends + [int(i) for i in inner]), dtype=np.int64)
+    m = values // (2 * len(idx) * polys)
+    cols = None if m >= N else np.sort(rng.choice(N, size=max(1, m), replace=False))
+    return idx, cols
+
+
+def dump_outputs(wl, out_dir, rank, world):
+    """--dump-outputs: the results the last timed step left in HBM, downloaded after the timed region.  One file, DIR/result.npy
+    (DIR/result_rank<r>.npy at N > 1, this rank's shard), float64 of shape (results, ciphertext size, residues, coefficients, 2): the
+    result ciphertexts and coefficient positions of dump_sample(), every u64 residue word as [..., 0] = its high 32 bits and
+    [..., 1] = its low 32 bits (both exact in float64; a word itself is not: residues reach 2^60).  Returns what the line says of it."""
+    buf, per = wl.result_slab()
+    words = per[0] * per[1] * wl.N
+    idx, cols = dump_sample(wl.n, per[0] * per[1], wl.N)
+    rows = []
+    for i in idx:
+        r = buf.download_range(int(i) * words, per + (wl.N,))
+        rows.append(r if cols is None else r[..., cols])
+    w = np.stack(rows)
+    out = np.stack([(w >> np.uint64(32)).astype(np.float64), (w & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+    os.makedirs(out_dir, exist_ok=True)
+    name = "result" if world == 1 else f"result_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), out)
+    return {"dir": out_dir, "files": [name + ".npy"], "shape": list(out.shape), "results": [int(i) for i in idx],
+            "coefficients": "all" if cols is None else f"{len(cols)} of {wl.N} (seed {DUMP_SEED})",
+            "layout": "float64 (results, ciphertext size, residues, coefficients, 2): [..., 0] = high 32 bits, [..., 1] = low 32 bits of each u64 residue"}
 
 
 def dry_run(args, rank, world, dist, torch) -> int:
@@ -525,9 +578,14 @@ def main():
     ap.add_argument("--b1", type=int, default=0, help="operand-1 batch of the HEBench outer product (results = batch x b1; operand 1 is replicated on every rank); 0: the "
                                                       "configuration's own (1).  `--config eltwise_mul --batch 16 --b1 16` is the 16 x 16 shape of configs[1] (SURVEY.md 8d cfg2)")
     ap.add_argument("--chunk", type=int, default=0, help="ops per kernel sequence (0: library default)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="results in the CPU-baseline sample (-1: the configuration's own, 0: skip)")
-    ap.add_argument("--cpu-passes", type=int, default=5, help="timed passes of the CPU baseline (median reported)")
-    ap.add_argument("--parity-sample", type=int, default=-1, help="results every rank checks against the oracle (-1: the configuration's own, 0: skip)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure, after the timed steps: the second scaling at N > 1, clock probe, "
+                                                        "power, dominant kernel, CPU baseline, parity sample, collective check, checksum (off: a plain run is "
+                                                        "set-up, warm-up, timed steps, --dump-outputs and the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed, seeded sample of what the last timed step computed to DIR/result.npy "
+                                                                        "(float64, every u64 residue as its high and low 32 bits; see dump_outputs())")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: results in the CPU-baseline sample (-1: the configuration's own, 0: skip)")
+    ap.add_argument("--cpu-passes", type=int, default=5, help="with --full: timed passes of the CPU baseline (median reported)")
+    ap.add_argument("--parity-sample", type=int, default=-1, help="with --full: results every rank checks against the oracle (-1: the configuration's own, 0: skip)")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / sharding only: the ranks meet (gloo), every rank computes its shard of "
                                                            "the global batch, rank 0 prints them; no GPU is touched (what the CPU test of the N>1 path runs)")
     ap.add_argument("--profile-mode", action="store_true", help="only warm-up + timed steps on the GPU (no CPU baseline, no parity sample, no extra "
@@ -536,8 +594,11 @@ def main():
                     help="take the N > 1 branch at --gpus 1 too (also HE355_BENCH_FORCE_DIST=1): the one rank is started under torch.distributed.run, initialises the "
                          "collective backend (nccl = RCCL) on its device, and the line carries `collective` -- what a 1-GPU box can check of the multi-GPU path")
     args = ap.parse_args()
-    if args.profile_mode:
+    if not args.full and (args.cpu_sample > 0 or args.parity_sample > 0):
+        ap.error("--cpu-sample / --parity-sample are checks of --full: add --full")
+    if args.profile_mode or not args.full:
         args.cpu_sample, args.parity_sample = 0, 0
+    extras = args.full and not args.profile_mode  # the untimed probes after the timed steps
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))  # plain `python bench.py --gpus N`: this process becomes the launcher
@@ -639,6 +700,7 @@ def main():
     wl, n = run["wl"], run["wl"].n
     scaling_kind, global_b0, elapsed, gpu_ms, per_rank_ms, total_results, value = (run[k] for k in ("scaling", "global_b0", "elapsed", "gpu_ms", "per_rank_ms",
                                                                                                 "total_results", "value"))
+    dumped = dump_outputs(wl, args.dump_outputs, rank, world) if args.dump_outputs and n > 0 else None
     # what a reader of the N > 1 line needs to see that the ranks really met over the collective backend and which card each one drove:
     # an all-reduce of one 1 per rank (must equal the world size), every rank's own time and its device's PCI bus id
     props = torch.cuda.get_device_properties(device)
@@ -646,7 +708,7 @@ def main():
            if hasattr(props, "pci_bus_id") else None)
     collective = None
     per_rank_device = [{"rank": 0, "local_device": device, "pci_bus_id": bus, "name": props.name}]
-    if use_dist:
+    if use_dist and args.full:
         ones = torch.ones(1, dtype=torch.float64, device=tdev)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         objs = [None] * world
@@ -659,7 +721,7 @@ def main():
     # ---- shader clock held under this load: one extra untimed step (same schedule as the timed ones) with a one-wave probe beside it that
     # samples s_memtime against the 100 MHz counter for ~80 % of a step (he355_clock_probe_begin; MI355X_MICROARCH.md "DVFS give-back") ----
     clock = None
-    if n > 0 and not args.profile_mode:
+    if n > 0 and extras:
         step_us = elapsed / args.steps * 1e6
         ctx.clock_probe_begin(max(200, int(step_us * 0.8)))
         wl.step()
@@ -671,12 +733,12 @@ def main():
     # ---- package power and core clock under this load: an extra untimed run of ~1.5 s while a host thread reads the device's hwmon files
     # (power1_input = PPT in microwatts, power1_cap, freq1_input = sclk) every 20 ms -- sysfs reads, no subprocess; rank 0 at N = 1 only ----
     power = None
-    if n > 0 and not args.profile_mode and rank == 0 and world == 1:
+    if n > 0 and extras and rank == 0 and world == 1:
         power = sample_power(torch.cuda.get_device_properties(device), lambda k: ([wl.step() for _ in range(k)], ctx.sync()), elapsed / args.steps)
 
     # ---- dominant kernel, single stream: one extra untimed step with the two-stream schedule off, HIP events around each launch ----
     k3 = None
-    if args.config in ("mul_relin_rescale", "mul_relin", "dot") and n > 0 and not args.profile_mode:
+    if args.config in ("mul_relin_rescale", "mul_relin", "dot") and n > 0 and extras:
         ctx.set_dual_stream(False)
         ctx.timer_begin()
         wl.step()
@@ -743,12 +805,12 @@ def main():
             times, want = wl.checker(ho, o, rows_checked, threads, 1)
             got = wl.result_rows(rows_checked * W.b1)
             parity = bool(np.array_equal(got, want))
-    if n > 0:
+    if n > 0 and args.full:
         checksum = hashlib.sha256(np.ascontiguousarray(wl.result_rows(min(n, 4))).tobytes()).hexdigest()[:16]
 
     # every rank's verdict reaches rank 0
     flags = [1 if parity is None else int(parity), rows_checked * W.b1]
-    if use_dist:
+    if use_dist and args.full:
         t = torch.tensor(flags, dtype=torch.int64, device=tdev)
         gathered = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(gathered, t)
@@ -857,6 +919,8 @@ def main():
                        "per_rank": [{"rank": r, "ok": bool(p[0]), "results_checked": p[1]} for r, p in enumerate(per_rank)],
                        "against": "oracle (CPU restatement) on the first rows of each rank's shard, bit for bit"},
             "results_checksum_rank0": checksum,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if use_dist:

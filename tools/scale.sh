@@ -13,10 +13,10 @@ for n in $COUNTS; do
   for mode in weak strong; do
     PORT=$((PORT + 1))
     if [ "$n" = 1 ]; then
-      python3 bench.py --gpus 1 --steps 5 --warmup 1 --scaling $mode --batch 1024 --cpu-sample 0 >> "$OUT"
+      python3 bench.py --gpus 1 --steps 5 --warmup 1 --scaling $mode --batch 1024 --cpu-sample 0 --full >> "$OUT"
     else
       python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $n --steps 5 --warmup 1 \
-        --scaling $mode --batch 1024 --cpu-sample 0 >> "$OUT"
+        --scaling $mode --batch 1024 --cpu-sample 0 --full >> "$OUT"
     fi
     tail -1 "$OUT" | python3 -c "import json,sys; j=json.loads(sys.stdin.readline()); print('$n GPU(s) $mode:', j['value'], 'ops/s', j['ms_per_step'], 'ms/step', 'allreduce_of_ones', (j.get('collective') or {}).get('allreduce_of_ones'), 'per_rank_ms', j.get('per_rank_ms'))"
   done
