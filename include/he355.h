@@ -273,7 +273,7 @@ int he355_set_latency_max(he355_ctx *ctx, uint64_t n);
  * HE355_LEVEL_WALK=0), or node by node (0: one sequence per node; what CKKS batches within the latency shape always take).  Results are
  * bit-identical either way. */
 int he355_set_level_walk(he355_ctx *ctx, int on);
-/* Rings that fit one CU's LDS (N <= 8192, at most 8 data primes): key switches over at most n ciphertexts per kernel sequence run as TWO
+/* Rings that fit one CU's LDS (N <= 8192, at most 6 data primes: L <= 6): key switches over at most n ciphertexts per kernel sequence run as TWO
  * launches of one-polynomial workgroups whose transforms never leave LDS (csrc/he355_kernels_lds.hip; the reference's descriptors default
  * to N = 8192: src/benchmarks/ckks/seal_ckks_dot_product_benchmark.cpp:53-60).  Default: the library's rule (one and a half rounds of the chip for the first kernel's grid: 64 ciphertexts at {60, 40, 60}); a call (or
  * HE355_LDS_MAX) replaces it by n; 0: never; UINT64_MAX: the rule again.  Results are bit-identical either way. */

@@ -6,6 +6,8 @@
 
 #include <array>
 #include <algorithm>
+#include <cerrno>
+#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -118,6 +120,20 @@ __global__ void k_key_quotients(const u64 *key, u64 *keyq, u64 n_dk, int logN, c
 
 } // namespace
 
+// A count from the environment (HE355_CHUNK, HE355_LATENCY_MAX, HE355_LDS_MAX): false when the variable is unset, empty or not a decimal
+// number -- the library's own rule then applies
+static bool env_u64(const char *name, u64 &v)
+{
+    const char *s = std::getenv(name);
+    if (!s || *s < '0' || *s > '9') return false;
+    char *end = nullptr;
+    errno = 0;
+    const unsigned long long x = std::strtoull(s, &end, 10);
+    if (*end || errno) return false;
+    v = (u64)x;
+    return true;
+}
+
 // 64 bits from the operating system's entropy source (the context's own encryptions of zero; the bridge's client seeds likewise)
 static u64 os_seed()
 {
@@ -227,10 +243,10 @@ public:
         env_.u64_fold = P.u64_fold;
         const char *ds = std::getenv("HE355_DUAL_STREAM");
         if (ds) dual_stream_ = ds[0] != '0';
-        const char *lm = std::getenv("HE355_LATENCY_MAX");
-        if (lm) set_latency_max((u64)std::max(0, std::atoi(lm)));
-        const char *ch = std::getenv("HE355_CHUNK");
-        if (ch && std::atoi(ch) > 0) chunk_ = (size_t)std::atoi(ch);
+        u64 v = 0;
+        if (env_u64("HE355_LATENCY_MAX", v)) set_latency_max(v);
+        if (env_u64("HE355_LDS_MAX", v)) set_lds_max(v);
+        if (env_u64("HE355_CHUNK", v) && v > 0) chunk_ = (size_t)v;
     }
     ~DeviceContext()
     {
@@ -504,18 +520,19 @@ public:
             c = (c + 1) / 2;
         }
     }
-    void reserve_arena(int which, size_t need)
+    void reserve_arena(int which, size_t need) { which ? grow(scratch2_, scratch2_bytes_, need) : grow(scratch_, scratch_bytes_, need); }
+    // the context's grow-on-demand device buffers: at least `bytes` afterwards.  Both streams are drained before the old buffer goes (no
+    // steady-state call grows one: test_steady_state_operate_does_not_allocate).
+    void grow(u64 *&buf, size_t &buf_bytes, size_t bytes)
     {
-        u64 *&arena = which ? scratch2_ : scratch_;
-        size_t &arena_bytes = which ? scratch2_bytes_ : scratch_bytes_;
-        if (need <= arena_bytes) return;
+        if (bytes <= buf_bytes) return;
         HIPCHECK(hipStreamSynchronize(stream_));
         HIPCHECK(hipStreamSynchronize(stream2_));
-        pool_.raw_free(arena);
-        arena = nullptr;
-        arena_bytes = 0;
-        dmalloc(arena, need);
-        arena_bytes = need;
+        pool_.raw_free(buf);
+        buf = nullptr;
+        buf_bytes = 0;
+        dmalloc(buf, bytes);
+        buf_bytes = bytes;
     }
     Scratch scratch(size_t c, int L, int which = 0)
     {
@@ -538,24 +555,6 @@ public:
         return s;
     }
 
-    // K2, K3, mod-down; result added into B.c01.  with_tail: also start the rescale (tail of prime L-1)
-    // rescale_out != null (size-2 result wanted at level L-1): when the fused path applies, the rescale is finished here too
-    // and the function returns true (the caller skips rescale_tail).
-    // operands of a ct x ct multiply whose c0, c1 k_k1 did not write (tensor_in_k3): the fused k_k3 computes them where it adds them in
-    struct TensorOperands {
-        const u64 *a = nullptr, *b = nullptr;
-        Indexer ix{};
-        u64 op_offset = 0;
-        // rotations (a, b null): polynomial 1 of the ciphertext k_k1 prepares is zero (1) or the addend's (2, c1_src = the addend rows of
-        // this chunk) and is taken from there by the fused k_k3 instead of being written into c01 by k_k1
-        int c1_mode = 0;
-        const u64 *c1_src = nullptr;
-        // c1_mode 4: the rotation's input and its permutation (K3Fuse::gsrc): k_k3 gathers the permuted c0 and c1 itself
-        const u64 *gsrc = nullptr;
-        const uint32_t *gperm = nullptr;
-        u64 gsrc_op_offset = 0;
-    };
-    // true when key_switch_tail will take a fused path for this batch, i.e. when k_k3's epilogue is where c0, c1 are consumed
     // The fused mod-down runs the special prime's tiles as a launch of their own, ahead of the data primes' (their epilogue needs its
     // result): n1 rows x nc / 8 op-groups of blocks.  With a handful of ciphertexts at a small ring that launch is a few dozen blocks
     // on 256 CUs -- as long as the data primes' launch and nearly idle -- and the unfused sequence (every prime's tiles in ONE launch,
@@ -577,103 +576,7 @@ public:
         if (n % 8 || !k3_can_fuse(e) || !fuse_pays(e, n, L) || (u64)chunk_ < n) return false; // (a launch holds whole groups, and takes the fused path)
         return (((u64)L << e.logn1) * (n / 8)) >= 512;                                      // blocks of the data-prime launch
     }
-    bool tensor_in_k3(const KernelEnv &env_, int L, u64 nc, const KsBuffers &B) const
-    {
-        return !latency_shape_env(env_, nc) && k3_can_fuse(env_) && fuse_pays(env_, nc, L) && B.c01_item_stride == 2 * (size_t)L * P.N;
-    }
-    // groups (grouped rotations, fused path only): per-group keys; g_off: index of the chunk's first op in the grouped batch
-    bool key_switch_tail(const KernelEnv &env_, int L, u64 nc, const Scratch &S, const KsBuffers &B, const u64 *key, bool with_tail,
-                         hipEvent_t after_k2 = nullptr, u64 *rescale_out = nullptr, const TensorOperands *ten = nullptr, const KsGroups *groups = nullptr,
-                         u64 g_off = 0)
-    {
-        if (groups && (rescale_out || with_tail || !(k3_can_fuse(env_) && B.c01_item_stride == 2 * (size_t)L * P.N)))
-            throw std::logic_error("key_switch_tail: grouped keys are for plain rotations into a ciphertext slab");
-        const bool lat = !groups && latency_shape_env(env_, nc); // (a grouped launch always takes the throughput shape)
-        auto with_operands = [&](K3Fuse f) {
-            if (ten) { f.ta = ten->a; f.tb = ten->b; f.tix = ten->ix; f.t_op_offset = ten->op_offset; f.c1_mode = ten->c1_mode; f.c1_src = ten->c1_src; f.gsrc = ten->gsrc; f.gperm = ten->gperm; f.gsrc_op_offset = ten->gsrc_op_offset; }
-            return f;
-        };
-        const size_t N = P.N, LN = (size_t)L * N;
-        const int SP = (int)P.K - 1;
-        if (lat) {
-            ++paths_.ks_latency;
-            // Few ciphertexts (HEBench's Latency category is batch 1: ckks eltwise .cpp:138-141): the throughput shape would leave one
-            // wave walking all digits of a tile and one lane walking all targets of a column while the chip idles.  Same kernels,
-            // unfused, with the serial loops dealt to more blocks: targets of a column over kLatTargets blocks (k_k2n, k_floor_colsn),
-            // digits of a tile over kLatSplit (u64 engine: kLatSplitU64) single-wave blocks whose partial sums k_k3_combine adds (k_k3).
-            launch_k2(env_, L, nc, B, nullptr, 0, kLatTargets);
-            if (after_k2) HIPCHECK(hipEventRecord(after_k2, env_.stream));
-            u64 *part = latency_partials((size_t)std::max(kLatSplit, kLatSplitU64) * nc * 2 * (L + 1) * N, env_.stream == stream2_ ? 1 : 0);
-            launch_k3(env_, L, nc, B, key, K3_ALL, nullptr, kLatSplit, part, kLatSplitU64);
-            launch_k3_combine(env_, L, nc, B, kLatSplit, part, kLatSplitU64);
-            launch_floor_cols(env_, SP, L, nc * 2, B.tpr, B.e, 0, 0, nullptr, 0, kLatTargets);
-            return key_switch_floor_rows(env_, L, nc, S, B, with_tail);
-        }
-        launch_k2(env_, L, nc, B);
-        if (after_k2) HIPCHECK(hipEventRecord(after_k2, env_.stream));
-        if (k3_can_fuse(env_) && B.c01_item_stride == 2 * LN && fuse_pays(env_, nc, L)) {
-            // special prime first, its correction through the column pass, then the data primes with the mod-down finished
-            // inside K3 (the sums never go to HBM)
-            ++paths_.ks_fused;
-            if (groups && groups->sum_out) ++paths_.level_sum_launches_in_k3;
-            launch_k3(env_, L, nc, B, key, K3_SPECIAL_ONLY, nullptr, 1, nullptr, 0, groups, g_off);
-            if (rescale_out && L >= 2) {
-                // Mod-down + rescale with ONE column pass and ONE row transform per target: only the prime the rescale divides out needs
-                // the mod-down correction by itself (its tiles run first, mod-down only); for every other prime the two corrections are
-                // combined in coefficient form, delta2 + P^-1 * delta1, inside one k_floor_colsn launch that reads both sources (the
-                // special prime's sums and the divided-out prime's tail) -- 16 column passes per polynomial instead of 31, and the
-                // mod-down correction slab is neither written for those primes nor read back.
-                launch_floor_cols(env_, SP, 1, nc * 2, B.tpr, B.e, /*tgt_first*/ L - 1, /*dst_ntgt*/ L);
-                const K3Fuse last = with_operands(K3Fuse{B.e, B.c01, B.c01_item_stride, L - 1, L, nullptr, nullptr});
-                launch_k3(env_, L, nc, B, key, K3_DATA_ONLY, &last);
-                launch_rows_inv_select(env_, L - 1, nc * 2, B.c01 + (size_t)(L - 1) * N, (u64)LN, S.rlr);
-                launch_floor_cols(env_, L - 1, L - 1, nc * 2, S.rlr, S.f, 0, L - 1, /*src2*/ B.tpr, SP);
-                const K3Fuse rest = with_operands(K3Fuse{B.e, B.c01, B.c01_item_stride, 0, L - 1, S.f, rescale_out});
-                launch_k3(env_, L, nc, B, key, K3_DATA_ONLY, &rest);
-                return true;
-            }
-            launch_floor_cols(env_, SP, L, nc * 2, B.tpr, B.e);
-            const K3Fuse fuse = with_operands(K3Fuse{B.e, B.c01, B.c01_item_stride, 0, L, nullptr, nullptr});
-            launch_k3(env_, L, nc, B, key, K3_DATA_ONLY, &fuse, 1, nullptr, 0, groups, g_off);
-            if (with_tail) launch_rows_inv_select(env_, L - 1, nc * 2, B.c01 + (size_t)(L - 1) * N, (u64)LN, S.rlr);
-            return false;
-        }
-        if (ten) throw std::logic_error("key_switch_tail: c0, c1 were left to a fused k_k3 that is not running");
-        ++paths_.ks_unfused;
-        launch_k3(env_, L, nc, B, key, K3_ALL, nullptr, 1, nullptr, 0, groups, g_off);
-        launch_floor_cols(env_, SP, L, nc * 2, B.tpr, B.e);
-        return key_switch_floor_rows(env_, L, nc, S, B, with_tail);
-    }
-    // the row half of the unfused mod-down: c01 += (t - NTT(e)) * P^-1, optionally starting the rescale (tail of prime L-1)
-    bool key_switch_floor_rows(const KernelEnv &env_, int L, u64 nc, const Scratch &S, const KsBuffers &B, bool with_tail)
-    {
-        const size_t LN = (size_t)L * P.N;
-        const int SP = (int)P.K - 1;
-        FloorRowsArgs fr;
-        fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
-        fr.cols = B.e;
-        fr.tsrc = B.t; fr.tsrc_op_stride = 2 * LN; fr.tsrc_poly_stride = LN;
-        fr.addend = B.c01; fr.add_op_stride = B.c01_item_stride; fr.add_poly_stride = LN;
-        fr.out = B.c01; fr.out_op_stride = B.c01_item_stride; fr.out_poly_stride = LN;
-        fr.tail_prime = with_tail ? L - 1 : -1;
-        fr.tail = S.rlr;
-        launch_floor_rows(env_, nc, fr);
-        return false;
-    }
-    void rescale_tail(const KernelEnv &env_, int L, int size, u64 nc, const Scratch &S, const u64 *src, u64 src_op_stride, u64 *out)
-    {
-        const size_t N = P.N, LN = (size_t)L * N, L1N = (size_t)(L - 1) * N;
-        launch_floor_cols(env_, L - 1, L - 1, nc * size, S.rlr, S.f, 0, 0, nullptr, 0, latency_shape(nc) ? kLatTargets : 1);
-        FloorRowsArgs fr;
-        fr.src_prime = L - 1; fr.n_tgt = L - 1; fr.n_src = size;
-        fr.cols = S.f;
-        fr.tsrc = src; fr.tsrc_op_stride = src_op_stride; fr.tsrc_poly_stride = LN;
-        fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
-        fr.out = out; fr.out_op_stride = (u64)size * L1N; fr.out_poly_stride = L1N;
-        fr.tail_prime = -1; fr.tail = nullptr;
-        launch_floor_rows(env_, nc, fr);
-    }
-    // latency shape of the key switch (key_switch_tail): batches of at most lat_max_ ciphertexts, CKKS pipeline
+    // latency shape of the key switch: batches of at most lat_limit() ciphertexts, CKKS pipeline
     // digit groups per fp64-engine tile (480 tiles x 4 single-wave blocks fill the chip once at batch 1), per u64-engine tile (64 tiles, rows
     // 2.5x as long), blocks per column for the targets of k_k2n / k_floor_colsn
     static constexpr int kLatTargets = 8;
@@ -685,10 +588,9 @@ public:
     // coefficients per residue on (profiles/r05_latency_boundary.txt: N = 2^15 crosses between 4 and 5 ciphertexts at depth 6 and 16, 2^14
     // between 6 and 8, 2^13 at 12), so the default limit is 2^17 / N ciphertexts, at most 12; he355_set_latency_max replaces it.
     u64 lat_limit() const { return lat_auto_ ? std::min<u64>(12, std::max<u64>(1, ((u64)1 << 17) / P.N)) : lat_max_; }
-    bool latency_shape(u64 nc) const { return P.scheme == kSchemeCKKS && nc <= lat_limit() && P.K >= 2; }
-    // ... for a given kernel environment (a BFV context runs its rotation chains in the NTT domain on the CKKS pipeline: ntt_env)
-    bool latency_shape_env(const KernelEnv &e, u64 nc) const { return e.scheme == kSchemeCKKS && nc <= lat_limit() && P.K >= 2; }
-    // Ring-in-LDS shape (he355_kernels_lds.hip): N <= 8192, NTT-domain pipeline, batches up to lds_limit() -- two
+    // ... for a kernel environment (a BFV context runs its rotation chains in the NTT domain on the CKKS pipeline: ntt_env)
+    bool latency_shape(const KernelEnv &e, u64 nc) const { return e.scheme == kSchemeCKKS && nc <= lat_limit() && P.K >= 2; }
+    // Ring-in-LDS shape (he355_kernels_lds.hip): N <= 8192, L <= 6, NTT-domain pipeline, batches up to lds_limit() -- two
     // launches of L^2 + 2L one-polynomial workgroups per ciphertext instead of six launches through HBM.  Where the throughput shape's
     // better use of the chip overtakes it was measured (profiles/r06_lds_shape.txt); he355_set_lds_max / HE355_LDS_MAX replace the rule.
     // The rule: while k_lds_digits' grid, (L + 1) L blocks per ciphertext, runs in at most one and a half rounds of the chip -- 256 CUs, one
@@ -702,34 +604,252 @@ public:
         const u64 blocks = (u64)384 << (3 - std::min(3, e.logn1));
         return std::max<u64>(1, blocks / ((u64)(L + 1) * (u64)L));
     }
+    // (also the test of he355_rescale's two-launch form)
     bool lds_shape(const KernelEnv &e, int L, u64 nc) const { return e.scheme == kSchemeCKKS && ks_lds_supported(e, L) && nc <= lds_limit(e, L); }
-    // scratch of the shape: the arena behind c01 (k_lds_digits' partial products; (2L + 2) L N words per ciphertext fit there for L <= 8)
-    u64 *lds_part(const Scratch &S, int L, u64 nc) const
+    // scratch of the shape: the arena behind c01 holds k_lds_digits' partial products, (2L + 4) L N words per ciphertext, for every L <= 6
+    u64 *lds_part(const Scratch &S, int L) const
     {
         const size_t need = (size_t)ks_lds_part_words(env_, L), have = scratch_words_per_op(L) - 2 * (size_t)L * P.N;
         if (need > have) throw std::logic_error("ring-in-LDS key switch: the arena is too small for the partial products");
-        (void)nc;
         return S.ks.c2n;
+    }
+
+    // What a key switch switches.  key_switch_batch alone turns it into k_k1's flags, K3Fuse's operand fields and LdsKsOperands.
+    enum class KsKind {
+        Product, // a * b of two size-2 ciphertexts: a, b [.][2][L][N], result r takes a[idx_a(ix, r)], b[idx_b(ix, r)] (he355_multiply_relin)
+        Size3,   // a [n][3][L][N]: c2 switched, added into (c0, c1) (he355_relinearize)
+        Galois,  // a [n][2][L][N] under element elt (table: its NTT-domain permutation or coefficient-form gather), out = addend + galois(a)
+        Grouped, // a [.][2][L][N] in groups of groups.group_size ciphertexts, per-group elements and keys (he355_rotate_sum, rotate_each)
+    };
+    struct KsSource {
+        KsKind kind;
+        const u64 *a = nullptr, *b = nullptr;
+        Indexer ix{};
+        const u64 *addend = nullptr; // Galois, optional [n][2][L][N]: may be `out` (the wave that reads a row of it writes that row, afterwards)
+        uint32_t elt = 0;
+        const uint32_t *table = nullptr;
+        const u64 *key = nullptr;    // the relinearization key or the Galois key (grouped: the groups' keys)
+        KsGroups groups{};
+        bool coeff = false;          // a BFV context's coefficient-form ciphertexts (else the NTT-domain pipeline)
+    };
+    enum class KsShape { Lds, Latency, Fused, Unfused, BfvCoeff };
+    // The shape of one chunk's key switch: the whole rule.  The first row that holds:
+    //   BfvCoeff | e.scheme is BFV: coefficient-form ciphertexts of a BFV context (the BFV kernels; no he355_path_stats counter)
+    //   Lds      | not grouped, out_apart, lds_shape(e, L, nc): CKKS / NTT-domain pipeline, ks_lds_supported(e, L), nc <= lds_limit(e, L)
+    //   Latency  | not grouped, latency_shape(e, nc)
+    //   Fused    | k3_can_fuse(e), fuse_pays(e, nc, L)  (and c01 a slab [nc][2][L][N] of its own: key_switch_batch always lays it out so)
+    //   Unfused  | otherwise
+    // out_apart: `out` shares no word with a product's operands or a size-3 input (a rotation may add into `out`: always apart).  k_k3 forms
+    // c0, c1 itself (K3Fuse operands, k_k1 does not write them) exactly when the shape is Fused and out_apart.
+    KsShape ks_shape(const KernelEnv &e, int L, u64 nc, KsKind kind, bool out_apart) const
+    {
+        if (e.scheme != kSchemeCKKS) return KsShape::BfvCoeff;
+        if (kind != KsKind::Grouped && out_apart && lds_shape(e, L, nc)) return KsShape::Lds;
+        if (kind != KsKind::Grouped && latency_shape(e, nc)) return KsShape::Latency;
+        return k3_can_fuse(e) && fuse_pays(e, nc, L) ? KsShape::Fused : KsShape::Unfused;
     }
     // the kernel environment of a batch on stream `which`
     // ntt: the NTT-domain (CKKS) pipeline whatever the context's scheme (ntt_env)
-    KernelEnv batch_env(u64 /*nc*/, int which = 0, bool ntt = false) const
+    KernelEnv batch_env(int which = 0, bool ntt = false) const
     {
         KernelEnv env = env_;
         env.stream = which ? stream2_ : stream_;
         if (ntt) env.scheme = kSchemeCKKS;
         return env;
     }
+    // The chunk loop of every batched op: `chunk` ciphertexts per step (chunk_ops(n, L, may_dual), or fewer), each with the scratch arena of
+    // its stream.  With may_dual and a batch that is cut, the chunks alternate between the two streams, each with its own arena: the
+    // ALU-bound key-product kernel of one chunk overlaps the HBM-bound multiply / digit-lift / floor kernels of the other.  The second
+    // stream starts half a pipeline late: f(off, nc, which, scratch, fork) records `fork` (chunk 0 only, else null) once chunk 0's launches
+    // are issued (the HBM shapes: after its K1 + K2) and stream2_ waits for it before its first chunk; from then on one stream's ALU-bound
+    // kernels (K3, floor column pass) run beside the other's HBM-bound ones instead of beside their own kind (starting both streams
+    // together measured slower: HISTORY.md).
+    template <class F> void for_each_chunk(u64 n, int L, size_t chunk, bool may_dual, F &&f)
+    {
+        const bool dual = may_dual && n > chunk;
+        u64 ci = 0;
+        for (u64 off = 0; off < n; off += chunk, ++ci) {
+            const int which = dual ? (int)(ci & 1) : 0;
+            const bool fork = dual && ci == 0;
+            f(off, std::min<u64>(chunk, n - off), which, scratch(std::min<u64>(chunk, n), L, which), fork ? ev_fork_ : nullptr);
+            if (fork) HIPCHECK(hipStreamWaitEvent(stream2_, ev_fork_, 0));
+        }
+        if (dual) {
+            HIPCHECK(hipEventRecord(ev_join_, stream2_));
+            HIPCHECK(hipStreamWaitEvent(stream_, ev_join_, 0));
+        }
+    }
+    // One key-switch batch: n ciphertexts described by `src` into `out` ([n][2][L][N]; rescale: [n][2][L-1][N]), chunk by chunk, each chunk
+    // in the shape ks_shape picks and counted in he355_path_stats.  Returns true when a grouped source's level sum (KsGroups::sum_out) was
+    // formed in k_k3; false where the chunks cannot hold whole groups on the fused path (the caller then sums the groups itself).
+    bool key_switch_batch(int L, u64 n, const KsSource &src, bool rescale, u64 *out, bool may_dual)
+    {
+        const size_t N = P.N, LN = (size_t)L * N, out_per = 2 * (size_t)(rescale ? L - 1 : L) * N;
+        const bool product = src.kind == KsKind::Product, grouped = src.kind == KsKind::Grouped;
+        const bool galois = grouped || src.kind == KsKind::Galois;
+        // A level sum is a read-modify-write of groups.sum_out WITHOUT atomics.  It is exact because (1) the launch shape gives one wave sole
+        // ownership of a (ciphertext, polynomial, tile, row) of the sum across all groups of the launch (launch_k3 checks the whole-group
+        // shape), and (2) every chunk of the level is queued on ONE stream, in order: grouped chunks never alternate over stream2_, and
+        // grouped launches never take the four-wave or dual shapes.
+        if (grouped && (rescale || may_dual || !k3_can_fuse(batch_env(0, true))))
+            throw std::logic_error("grouped key switches: plain rotations on the fused pipeline, all chunks on one stream");
+        // k_k3 (fused) and the ring-in-LDS kernels read the operand rows while they write results: only when `out` is a slab of its own
+        bool out_apart = true;
+        if (product && n) {
+            const Indexer &ix = src.ix;
+            const u64 a_lo = idx_a(ix, 0), a_hi = idx_a(ix, n - 1), b_lo = ix.b_base, b_hi = ix.pairwise ? ix.b_base + n - 1 : ix.b_base + std::min<u64>(n, ix.b1) - 1;
+            out_apart = !ranges_overlap(out, n * out_per, src.a + a_lo * 2 * LN, (size_t)(a_hi - a_lo + 1) * 2 * LN) &&
+                        !ranges_overlap(out, n * out_per, src.b + b_lo * 2 * LN, (size_t)(b_hi - b_lo + 1) * 2 * LN);
+        } else if (src.kind == KsKind::Size3) {
+            out_apart = !ranges_overlap(out, n * out_per, src.a, n * 3 * LN);
+        }
+        size_t chunk = chunk_ops(n, L, may_dual);
+        KsGroups groups = src.groups;
+        if (groups.sum_out) { // chunks of whole groups, each on the fused path (fuse_pays grows with the chunk), or no level sum in k_k3
+            if (chunk < groups.group_size || !fuse_pays(batch_env(0, true), groups.group_size, L)) groups.sum_out = nullptr;
+            else chunk -= chunk % groups.group_size;
+        }
+        for_each_chunk(n, L, chunk, may_dual, [&](u64 off, u64 nc, int which, Scratch S, hipEvent_t fork) {
+            const KernelEnv env = batch_env(which, !src.coeff);
+            KsBuffers &B = S.ks;
+            if (!rescale) { B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN; }
+            u64 *ro = rescale ? out + off * out_per : nullptr;
+            const KsShape shape = ks_shape(env, L, nc, src.kind, out_apart);
+            if (shape == KsShape::BfvCoeff) {
+                const u64 *a = src.a + off * (galois ? 2 : 3) * LN;
+                if (galois) {
+                    launch_bfv_galois(env, L, nc, a, src.table, B.c01, B.c01_item_stride, B.c2n, src.addend ? src.addend + off * 2 * LN : nullptr);
+                    bfv_key_switch(env, L, nc, S, B, src.key, B.c2n, LN);
+                } else { // out = (c0, c1) of each size-3 ciphertext (read where they lie by the last kernel) + the key-switched c2
+                    bfv_key_switch(env, L, nc, S, B, src.key, a + 2 * LN, 3 * LN, a, 3 * LN);
+                }
+            } else if (shape == KsShape::Lds) {
+                // a ring that fits LDS: the tensor product / permutation, key switch and the add in two launches (the operands are read where they lie)
+                ++paths_.ks_lds;
+                LdsKsOperands o;
+                if (product) {
+                    o.mode = LDSKS_MUL; o.a = src.a; o.b = src.b; o.ix = src.ix; o.op_offset = off;
+                } else if (galois) {
+                    o.mode = LDSKS_GALOIS; o.a = src.a; o.op_offset = off; o.perm = src.table;
+                    const std::array<unsigned char, 32> &rows = perm_rows_.at(src.elt);
+                    std::copy(rows.begin(), rows.end(), o.perm_src_row);
+                    o.add = src.addend ? src.addend + off * 2 * LN : nullptr; o.add_op_stride = 2 * LN;
+                } else {
+                    o.mode = LDSKS_PLAIN;
+                    o.tgt = src.a + off * 3 * LN + 2 * LN; o.tgt_op_stride = 3 * LN;
+                    o.add = src.a + off * 3 * LN; o.add_op_stride = 3 * LN;
+                }
+                launch_ks_lds(env, L, nc, o, src.key, lds_part(S, L), B.c01, B.c01_item_stride);
+                if (rescale) launch_rescale_lds(env, L, 2, nc, B.c01, 2 * LN, ro);
+            } else {
+                const bool fused = shape == KsShape::Fused;
+                if (groups.sum_out && !fused) throw std::logic_error("level sum: the fused key switch only");
+                ++(fused ? paths_.ks_fused : shape == KsShape::Latency ? paths_.ks_latency : paths_.ks_unfused);
+                if (fused && groups.sum_out) ++paths_.level_sum_launches_in_k3;
+                // c0, c1 of the ciphertext the switched key part is added into: written by k_k1, or (in_k3) formed by k_k3 where it adds them
+                // in -- k_k1 is HBM-bound and then reads and writes less, k_k3 is not and reads the operand rows instead of c01
+                const bool in_k3 = fused && out_apart;
+                K3Fuse ops{};
+                if (in_k3 && product) {
+                    ops.ta = src.a; ops.tb = src.b; ops.tix = src.ix; ops.t_op_offset = off;
+                } else if (in_k3 && galois) {
+                    // polynomial 1 is zero (4) or the addend's (5), and the epilogue gathers the permuted c0 from the input itself (grouped: the
+                    // op's group names its source block; g_op_offset carries the chunk offset) -- k_k1 writes two rows instead of three
+                    ops.c1_mode = src.addend ? 5 : 4;
+                    ops.c1_src = src.addend ? src.addend + off * 2 * LN : nullptr;
+                    ops.gsrc = src.a; ops.gperm = src.table; ops.gsrc_op_offset = grouped ? 0 : off;
+                } else if (in_k3) { // c0, c1 and the NTT-form c2 read from the size-3 input where it lies (k_k1 only sends c2 through the inverse row pass)
+                    ops.c1_mode = 3; ops.c1_src = src.a + off * 3 * LN;
+                }
+                const K1Mode mode = product ? K1_MUL : galois ? K1_GALOIS : K1_CT3;
+                launch_k1(env, L, mode, nc, off, src.a, src.b, src.ix, src.table, B, src.addend, in_k3 && product, in_k3 && !product,
+                          grouped ? &groups : nullptr, in_k3 && galois);
+                key_switch_tail(env, L, nc, S, shape, in_k3 && product ? relin_scaled() : src.key, ops, grouped ? &groups : nullptr, off, ro, fork);
+                return;
+            }
+            if (fork) HIPCHECK(hipEventRecord(fork, env.stream));
+        });
+        HIPCHECK(hipGetLastError());
+        return groups.sum_out != nullptr;
+    }
+    // An HBM-shape key switch after k_k1: K2, K3 and the mod-down into S.ks.c01, then (rescale_out) the rescale into rescale_out.
+    // ops: K3Fuse's operand fields (k_k3 forms c0, c1); groups: per-group keys, op 0 of the chunk is op g_off of the grouped batch;
+    // fork: recorded on the chunk's stream after K2
+    void key_switch_tail(const KernelEnv &env, int L, u64 nc, const Scratch &S, KsShape shape, const u64 *key, const K3Fuse &ops,
+                         const KsGroups *groups, u64 g_off, u64 *rescale_out, hipEvent_t fork)
+    {
+        const KsBuffers &B = S.ks;
+        const size_t N = P.N, LN = (size_t)L * N;
+        const int SP = (int)P.K - 1;
+        const bool lat = shape == KsShape::Latency;
+        launch_k2(env, L, nc, B, nullptr, 0, lat ? kLatTargets : 1);
+        if (fork) HIPCHECK(hipEventRecord(fork, env.stream));
+        if (lat) {
+            // Few ciphertexts (HEBench's Latency category is batch 1: ckks eltwise .cpp:138-141): the throughput shape would leave one
+            // wave walking all digits of a tile and one lane walking all targets of a column while the chip idles.  Same kernels,
+            // unfused, with the serial loops dealt to more blocks: targets of a column over kLatTargets blocks (k_k2n, k_floor_colsn),
+            // digits of a tile over kLatSplit (u64 engine: kLatSplitU64) single-wave blocks whose partial sums k_k3_combine adds (k_k3).
+            u64 *part = latency_partials((size_t)std::max(kLatSplit, kLatSplitU64) * nc * 2 * (L + 1) * N, env.stream == stream2_ ? 1 : 0);
+            launch_k3(env, L, nc, B, key, K3_ALL, nullptr, kLatSplit, part, kLatSplitU64);
+            launch_k3_combine(env, L, nc, B, kLatSplit, part, kLatSplitU64);
+            launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e, 0, 0, nullptr, 0, kLatTargets);
+        } else if (shape == KsShape::Unfused) {
+            launch_k3(env, L, nc, B, key, K3_ALL, nullptr, 1, nullptr, 0, groups, g_off);
+            launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e);
+        } else {
+            // fused: special prime first, its correction through the column pass, then the data primes with the mod-down finished
+            // inside K3 (the sums never go to HBM)
+            launch_k3(env, L, nc, B, key, K3_SPECIAL_ONLY, nullptr, 1, nullptr, 0, groups, g_off);
+            K3Fuse f = ops;
+            f.cols = B.e; f.c01 = B.c01; f.c01_item_stride = B.c01_item_stride; f.cols2 = nullptr; f.out = nullptr;
+            if (rescale_out) {
+                // Mod-down + rescale with ONE column pass and ONE row transform per target: only the prime the rescale divides out needs
+                // the mod-down correction by itself (its tiles run first, mod-down only); for every other prime the two corrections are
+                // combined in coefficient form, delta2 + P^-1 * delta1, inside one k_floor_colsn launch that reads both sources (the
+                // special prime's sums and the divided-out prime's tail) -- 16 column passes per polynomial instead of 31, and the
+                // mod-down correction slab is neither written for those primes nor read back.
+                launch_floor_cols(env, SP, 1, nc * 2, B.tpr, B.e, /*tgt_first*/ L - 1, /*dst_ntgt*/ L);
+                f.tt_lo = L - 1; f.tt_hi = L;
+                launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
+                launch_rows_inv_select(env, L - 1, nc * 2, B.c01 + (size_t)(L - 1) * N, (u64)LN, S.rlr);
+                launch_floor_cols(env, L - 1, L - 1, nc * 2, S.rlr, S.f, 0, L - 1, /*src2*/ B.tpr, SP);
+                f.tt_lo = 0; f.tt_hi = L - 1; f.cols2 = S.f; f.out = rescale_out;
+                launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
+                return;
+            }
+            launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e);
+            f.tt_lo = 0; f.tt_hi = L;
+            launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f, 1, nullptr, 0, groups, g_off);
+            return;
+        }
+        // the row half of the unfused mod-down: c01 += (t - NTT(e)) * P^-1, starting the rescale (tail of prime L-1) where one follows
+        FloorRowsArgs fr;
+        fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
+        fr.cols = B.e;
+        fr.tsrc = B.t; fr.tsrc_op_stride = 2 * LN; fr.tsrc_poly_stride = LN;
+        fr.addend = B.c01; fr.add_op_stride = B.c01_item_stride; fr.add_poly_stride = LN;
+        fr.out = B.c01; fr.out_op_stride = B.c01_item_stride; fr.out_poly_stride = LN;
+        fr.tail_prime = rescale_out ? L - 1 : -1;
+        fr.tail = S.rlr;
+        launch_floor_rows(env, nc, fr);
+        if (rescale_out) rescale_tail(env, L, 2, nc, S, B.c01, 2 * LN, rescale_out);
+    }
+    void rescale_tail(const KernelEnv &env, int L, int size, u64 nc, const Scratch &S, const u64 *src, u64 src_op_stride, u64 *out)
+    {
+        const size_t N = P.N, LN = (size_t)L * N, L1N = (size_t)(L - 1) * N;
+        launch_floor_cols(env, L - 1, L - 1, nc * size, S.rlr, S.f, 0, 0, nullptr, 0, latency_shape(env, nc) ? kLatTargets : 1);
+        FloorRowsArgs fr;
+        fr.src_prime = L - 1; fr.n_tgt = L - 1; fr.n_src = size;
+        fr.cols = S.f;
+        fr.tsrc = src; fr.tsrc_op_stride = src_op_stride; fr.tsrc_poly_stride = LN;
+        fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
+        fr.out = out; fr.out_op_stride = (u64)size * L1N; fr.out_poly_stride = L1N;
+        fr.tail_prime = -1; fr.tail = nullptr;
+        launch_floor_rows(env, nc, fr);
+    }
     u64 *latency_partials(size_t elems, int which) // one buffer per stream: chunks of the two streams are in flight together
     {
-        if (elems * 8 > lat_part_bytes_[which]) {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            HIPCHECK(hipStreamSynchronize(stream2_));
-            pool_.raw_free(lat_part_[which]);
-            lat_part_[which] = nullptr; lat_part_bytes_[which] = 0;
-            dmalloc(lat_part_[which], elems * 8);
-            lat_part_bytes_[which] = elems * 8;
-        }
+        grow(lat_part_[which], lat_part_bytes_[which], elems * 8);
         return lat_part_[which];
     }
     void require_keyswitch() const
@@ -745,62 +865,9 @@ public:
         if (P.scheme != kSchemeCKKS) throw std::invalid_argument("he355_multiply_relin implements the CKKS pipeline");
         if (!d_relin_) throw std::invalid_argument("relinearization key not set");
         if (rescale && L < 2) throw std::invalid_argument("cannot rescale at the last level");
-        const size_t N = P.N, LN = (size_t)L * N;
-        // Alternate chunks between two streams, each with its own scratch arena: the ALU-bound key-product kernel
-        // of one chunk overlaps the HBM-bound multiply / digit-lift / floor kernels of the other.
-        const size_t chunk = chunk_ops(n, L, dual_stream_); // this call's chunk size
-        const bool dual = dual_stream_ && n > chunk;
-        // The second stream starts half a pipeline late (after the first chunk's K1+K2 on the first stream): from then on
-        // one stream's ALU-bound kernels (K3, floor column pass) run beside the other's HBM-bound ones (K1, K2, floor row pass)
-        // instead of beside their own kind.
-        // (starting both streams together measured slower: HISTORY.md)
-        if (dual) {
-            (void)scratch(std::min<u64>(chunk, n), L, 0);
-            (void)scratch(std::min<u64>(chunk, n), L, 1);
-        }
-        // k_k3 reads the operand rows while it writes results: only when `out` is a slab of its own (it always was meant to be)
-        bool out_overlaps_operands = false;
-        if (n) {
-            auto overlap = [](const u64 *p, size_t np, const u64 *q, size_t nq) { return p < q + nq && q < p + np; };
-            const size_t out_words = n * 2 * (size_t)(rescale ? L - 1 : L) * N;
-            const u64 a_lo = idx_a(ix, 0), a_hi = idx_a(ix, n - 1), b_lo = ix.pairwise ? ix.b_base : ix.b_base, b_hi = ix.pairwise ? ix.b_base + n - 1 : ix.b_base + std::min<u64>(n, ix.b1) - 1;
-            out_overlaps_operands = overlap(out, out_words, a + a_lo * 2 * LN, (size_t)(a_hi - a_lo + 1) * 2 * LN) ||
-                                    overlap(out, out_words, b + b_lo * 2 * LN, (size_t)(b_hi - b_lo + 1) * 2 * LN);
-        }
-        u64 ci = 0;
-        for (u64 off = 0; off < n; off += chunk, ++ci) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            const int which = dual ? (int)(ci & 1) : 0;
-            const KernelEnv env = batch_env(nc, which);
-            Scratch S = scratch(std::min<u64>(chunk, n), L, which);
-            KsBuffers B = S.ks;
-            if (!rescale) { B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN; }
-            if (lds_shape(env, L, nc) && !out_overlaps_operands) {
-                // a ring that fits LDS: tensor product, key switch and the add in two launches (the operands are read where they lie)
-                ++paths_.ks_lds;
-                LdsKsOperands src;
-                src.mode = LDSKS_MUL; src.a = a; src.b = b; src.ix = ix; src.op_offset = off;
-                launch_ks_lds(env, L, nc, src, d_relin_, lds_part(S, L, nc), B.c01, B.c01_item_stride);
-                if (rescale) launch_rescale_lds(env, L, 2, nc, B.c01, 2 * LN, out + off * 2 * (size_t)(L - 1) * N);
-                continue;
-            }
-            // c0, c1 of the tensor product: written by k_k1, or (fused key switch) computed by k_k3 where it adds them in -- k_k1 is
-            // HBM-bound and then reads half and writes a third of what it did, k_k3 is not and reads the operand rows instead of c01
-            const bool in_k3 = tensor_in_k3(env, L, nc, B) && !out_overlaps_operands;
-            TensorOperands ten;
-            ten.a = a; ten.b = b; ten.ix = ix; ten.op_offset = off;
-            launch_k1(env, L, K1_MUL, nc, off, a, b, ix, nullptr, B, nullptr, in_k3);
-            const bool fork_here = dual && ci == 0;
-            u64 *ro = rescale ? out + off * 2 * (size_t)(L - 1) * N : nullptr;
-            const bool done = key_switch_tail(env, L, nc, S, B, in_k3 ? relin_scaled() : d_relin_, rescale, fork_here ? ev_fork_ : nullptr, ro, in_k3 ? &ten : nullptr);
-            if (fork_here) HIPCHECK(hipStreamWaitEvent(stream2_, ev_fork_, 0));
-            if (rescale && !done) rescale_tail(env, L, 2, nc, S, B.c01, 2 * LN, ro);
-        }
-        if (dual) {
-            HIPCHECK(hipEventRecord(ev_join_, stream2_));
-            HIPCHECK(hipStreamWaitEvent(stream_, ev_join_, 0));
-        }
-        HIPCHECK(hipGetLastError());
+        KsSource src{KsKind::Product};
+        src.a = a; src.b = b; src.ix = ix; src.key = d_relin_;
+        key_switch_batch(L, n, src, rescale, out, dual_stream_);
     }
     void relinearize(int L, u64 n, const u64 *ct3, u64 *out, bool rescale = false)
     {
@@ -808,56 +875,13 @@ public:
         check_level(L);
         require_keyswitch();
         if (!d_relin_) throw std::invalid_argument("relinearization key not set");
-        const size_t N = P.N, LN = (size_t)L * N;
-        if (P.scheme == kSchemeBFV) {
-            if (rescale) throw std::invalid_argument("rescale is a CKKS operation");
-            if (ranges_overlap(out, n * 2 * LN, ct3, n * 3 * LN)) throw std::invalid_argument("relinearize: `out` overlaps the size-3 input");
-            const size_t chunk = chunk_ops(n, L, false); // this call's chunk size
-            for (u64 off = 0; off < n; off += chunk) {
-                const u64 nc = std::min<u64>(chunk, n - off);
-                Scratch S = scratch(std::min<u64>(chunk, n), L); // arena sized for the batch actually processed
-                KsBuffers B = S.ks;
-                B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN;
-                const u64 *src = ct3 + off * 3 * LN;
-                // out = (c0, c1) of each size-3 ciphertext (read where they lie by the last kernel) + the key-switched c2
-                bfv_key_switch(L, nc, S, B, d_relin_, src + 2 * LN, 3 * LN, src, 3 * LN);
-            }
-            HIPCHECK(hipGetLastError());
-            return;
-        }
+        const bool bfv = P.scheme == kSchemeBFV;
+        if (bfv && rescale) throw std::invalid_argument("rescale is a CKKS operation");
+        if (bfv && ranges_overlap(out, n * 2 * (size_t)L * P.N, ct3, n * 3 * (size_t)L * P.N)) throw std::invalid_argument("relinearize: `out` overlaps the size-3 input");
         if (rescale && L < 2) throw std::invalid_argument("cannot rescale at the last level");
-        Indexer ix{};
-        const size_t chunk = chunk_ops(n, L, false); // this call's chunk size
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            Scratch S = scratch(std::min<u64>(chunk, n), L); // arena sized for the batch actually processed
-            KsBuffers B = S.ks;
-            if (!rescale) { B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN; }
-            const KernelEnv env = batch_env(nc);
-            // on the fused path k_k3 reads c0, c1 and the NTT-form c2 from the size-3 input where it lies (k_k1 copies nothing: it only
-            // sends c2 through the inverse row pass); `out` must then be a slab of its own
-            auto overlap = [](const u64 *p, size_t np, const u64 *q, size_t nq) { return p < q + nq && q < p + np; };
-            const bool out_apart = !overlap(out, n * 2 * (size_t)(rescale ? L - 1 : L) * N, ct3, n * 3 * LN);
-            if (lds_shape(env, L, nc) && out_apart) {
-                ++paths_.ks_lds;
-                LdsKsOperands src;
-                src.mode = LDSKS_PLAIN;
-                src.tgt = ct3 + off * 3 * LN + 2 * LN; src.tgt_op_stride = 3 * LN;
-                src.add = ct3 + off * 3 * LN; src.add_op_stride = 3 * LN;
-                launch_ks_lds(env, L, nc, src, d_relin_, lds_part(S, L, nc), B.c01, B.c01_item_stride);
-                if (rescale) launch_rescale_lds(env, L, 2, nc, B.c01, 2 * LN, out + off * 2 * (size_t)(L - 1) * N);
-                continue;
-            }
-            const bool in_k3 = tensor_in_k3(env, L, nc, B) && out_apart;
-            TensorOperands ten;
-            ten.c1_mode = 3;
-            ten.c1_src = ct3 + off * 3 * LN;
-            launch_k1(env, L, K1_CT3, nc, off, ct3, nullptr, ix, nullptr, B, nullptr, false, in_k3);
-            u64 *ro = rescale ? out + off * 2 * (size_t)(L - 1) * N : nullptr;
-            const bool done = key_switch_tail(env, L, nc, S, B, d_relin_, rescale, nullptr, ro, in_k3 ? &ten : nullptr);
-            if (rescale && !done) rescale_tail(env, L, 2, nc, S, B.c01, 2 * LN, ro);
-        }
-        HIPCHECK(hipGetLastError());
+        KsSource src{KsKind::Size3};
+        src.a = ct3; src.key = d_relin_; src.coeff = bfv;
+        key_switch_batch(L, n, src, rescale, out, false);
     }
     void plain_op(int L, int size, u64 n, const u64 *ct, const u64 *pt, Indexer ix, u64 *out, int mode)
     {
@@ -904,19 +928,19 @@ public:
         if (P.scheme != kSchemeCKKS) throw std::invalid_argument("he355_rescale is a CKKS operation");
         if (L < 2) throw std::invalid_argument("cannot rescale at the last level");
         if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
-        const size_t N = P.N, LN = (size_t)L * N;
-        const size_t chunk = chunk_ops(n, L, false); // this call's chunk size
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            Scratch S = scratch(std::min<u64>(chunk, n), L); // arena sized for the batch actually processed
+        const size_t N = P.N, LN = (size_t)L * N, L1N = (size_t)(L - 1) * N;
+        const bool apart = !ranges_overlap(in, n * size * LN, out, n * size * L1N); // (the two-launch form's blocks of an op read all of its input)
+        for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int which, const Scratch &S, hipEvent_t) {
+            const KernelEnv env = batch_env(which);
             const u64 *src = in + off * size * LN;
-            if (lds_shape(env_, L, nc) && !ranges_overlap(in, n * size * LN, out, n * size * (size_t)(L - 1) * N)) { // (the blocks of an op read all of its input)
-                launch_rescale_lds(env_, L, size, nc, src, (u64)size * LN, out + off * size * (size_t)(L - 1) * N);
-                continue;
+            u64 *dst = out + off * size * L1N;
+            if (apart && lds_shape(env, L, nc)) {
+                launch_rescale_lds(env, L, size, nc, src, (u64)size * LN, dst);
+                return;
             }
-            launch_rows_inv_select(env_, L - 1, nc * size, src + (size_t)(L - 1) * N, LN, S.rlr);
-            rescale_tail(env_, L, size, nc, S, src, (u64)size * LN, out + off * size * (size_t)(L - 1) * N);
-        }
+            launch_rows_inv_select(env, L - 1, nc * size, src + (size_t)(L - 1) * N, LN, S.rlr);
+            rescale_tail(env, L, size, nc, S, src, (u64)size * LN, dst);
+        });
         HIPCHECK(hipGetLastError());
     }
     // `addend` (optional, [n][2][L][N]; may alias `out`, never `in`): out = addend + galois(in) -- the add_inplace that follows
@@ -933,56 +957,11 @@ public:
         if (!key) throw std::invalid_argument("Galois key not present");
         // every kernel of the pipeline reads `in` while later ones already write `out`: any overlap (not just in == out) corrupts the input
         if (ranges_overlap(in, n * 2 * (size_t)L * P.N, out, n * 2 * (size_t)L * P.N)) throw std::invalid_argument("apply_galois cannot run in place: `out` overlaps `in`");
-        if (P.scheme == kSchemeBFV && !ntt_form) {
-            const uint32_t *gt = gather(elt);
-            const size_t LN = (size_t)L * P.N;
-            const size_t chunk = chunk_ops(n, L, false); // this call's chunk size
-            for (u64 off = 0; off < n; off += chunk) {
-                const u64 nc = std::min<u64>(chunk, n - off);
-                Scratch S = scratch(std::min<u64>(chunk, n), L); // arena sized for the batch actually processed
-                KsBuffers B = S.ks;
-                B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN;
-                launch_bfv_galois(env_, L, nc, in + off * 2 * LN, gt, B.c01, B.c01_item_stride, B.c2n, addend ? addend + off * 2 * LN : nullptr);
-                bfv_key_switch(L, nc, S, B, key, B.c2n, LN);
-            }
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        const uint32_t *pm = perm(elt);
-        const size_t N = P.N, LN = (size_t)L * N;
-        Indexer ix{};
-        const size_t chunk = chunk_ops(n, L, false); // this call's chunk size
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            Scratch S = scratch(std::min<u64>(chunk, n), L); // arena sized for the batch actually processed
-            KsBuffers B = S.ks;
-            B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN;
-            const KernelEnv env = batch_env(nc, 0, true);
-            if (lds_shape(env, L, nc)) {
-                // a ring that fits LDS: permutation, key switch and the add in two launches (an addend may be `out`: the wave that reads a row
-                // of it is the one that writes that row of the result, afterwards)
-                ++paths_.ks_lds;
-                LdsKsOperands src;
-                src.mode = LDSKS_GALOIS; src.a = in; src.op_offset = off; src.perm = pm;
-                const std::array<unsigned char, 32> &rows = perm_rows_.at(elt);
-                std::copy(rows.begin(), rows.end(), src.perm_src_row);
-                src.add = addend ? addend + off * 2 * LN : nullptr; src.add_op_stride = 2 * LN;
-                launch_ks_lds(env, L, nc, src, key, lds_part(S, L, nc), B.c01, B.c01_item_stride);
-                continue;
-            }
-            // polynomial 1 of the rotated ciphertext is zero (or the addend's): on the fused path k_k1 does not write it and k_k3 takes it
-            // from where it is (the addend may be `out`: the wave that reads a row is the one that writes it, afterwards)
-            const bool c1_in_k3 = tensor_in_k3(env, L, nc, B);
-            TensorOperands ten;
-            // (4 / 5: k_k3's epilogue gathers the permuted c0 from `in` itself -- and adds the addend's polynomial 0 to it -- so k_k1 writes two
-            // rows instead of three and reads neither c0 nor the addend)
-            ten.c1_mode = addend ? 5 : 4;
-            ten.c1_src = addend ? addend + off * 2 * LN : nullptr;
-            ten.gsrc = in; ten.gperm = pm; ten.gsrc_op_offset = off;
-            launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, ix, pm, B, addend, false, c1_in_k3, nullptr, c1_in_k3);
-            key_switch_tail(env, L, nc, S, B, key, false, nullptr, nullptr, c1_in_k3 ? &ten : nullptr);
-        }
-        HIPCHECK(hipGetLastError());
+        KsSource src{KsKind::Galois};
+        src.a = in; src.addend = addend; src.elt = elt; src.key = key;
+        src.coeff = P.scheme == kSchemeBFV && !ntt_form;
+        src.table = src.coeff ? gather(elt) : perm(elt);
+        key_switch_batch(L, n, src, false, out, false);
     }
     // Evaluator::rotate_internal: use the key of the step if present, otherwise the NAF decomposition
     void rotate(int L, u64 n, const u64 *in, int step, u64 *out, const u64 *addend = nullptr, bool ntt_form = false)
@@ -1017,13 +996,7 @@ public:
             if ((size_t)(s < 0 ? -s : s) != P.N / 2) steps.push_back(s); // a term of N/2 is no rotation
         if (steps.empty()) { plain_copy(); return; }
         if (addend == out && steps.size() > 1) throw std::invalid_argument("rotate_add through several Galois steps cannot add in place");
-        if (steps.size() > 1 && bytes > rot_tmp_bytes_) {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            pool_.raw_free(rot_tmp_);
-            rot_tmp_ = nullptr; rot_tmp_bytes_ = 0;
-            dmalloc(rot_tmp_, bytes);
-            rot_tmp_bytes_ = bytes;
-        }
+        if (steps.size() > 1) grow(rot_tmp_, rot_tmp_bytes_, bytes);
         // ping-pong between out and the temporary so that the last rotation lands in out
         const u64 *cur = in;
         const size_t m = steps.size();
@@ -1148,39 +1121,14 @@ public:
         e.scheme = kSchemeCKKS;
         return e;
     }
-    // NTT-form ciphertexts: out[g * gs + c] = apply_galois(in[src_block[g] * gs + c], element / key of group g), c < gs, g < G
-    // groups.sum_out (level_sum_pays): k_k3 adds every group's ciphertext into the sum itself; chunks are then whole groups
+    // NTT-form ciphertexts: out[g * gs + c] = apply_galois(in[src_block[g] * gs + c], element / key of group g), c < gs = groups.group_size,
+    // g < n / gs groups.  groups.sum_out (level_sum_pays): k_k3 adds every group's ciphertext into the sum itself; chunks are then whole groups
     // (returns false where it could not: the scratch arenas hold less than one group per launch -- the caller then sums the groups itself)
-    bool apply_galois_grouped(int L, u64 G, u64 gs, const u64 *in, KsGroups groups, u64 *out)
+    bool apply_galois_grouped(int L, u64 n, const u64 *in, const KsGroups &groups, u64 *out)
     {
-        const KernelEnv env = ntt_env();
-        const size_t N = P.N, LN = (size_t)L * N;
-        const u64 n = G * gs;
-        Indexer ix{};
-        size_t chunk = chunk_ops(n, L, false);
-        if (groups.sum_out) {
-            if (chunk < gs || !fuse_pays(env, gs, L)) groups.sum_out = nullptr;
-            else chunk -= chunk % gs;
-        }
-        // A level sum is a read-modify-write of groups.sum_out WITHOUT atomics.  It is exact because (1) the launch shape gives one wave sole
-        // ownership of a (ciphertext, polynomial, tile, row) of the sum across all groups of the launch (launch_k3 checks the whole-group
-        // shape), and (2) every chunk of the level is queued on this ONE stream, in order: never alternate these chunks over stream2_ the way
-        // multiply_relin does, and never give grouped launches the four-wave or dual shapes.
-        if (groups.sum_out && env.stream != stream_) throw std::logic_error("level sum: the chunks of a level must stay on one stream");
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            Scratch S = scratch(std::min<u64>(chunk, n), L);
-            KsBuffers B = S.ks;
-            B.c01 = out + off * 2 * LN; B.c01_item_stride = 2 * LN;
-            TensorOperands ten;
-            ten.c1_mode = 4; // polynomial 1 of the rotated ciphertext is zero: the fused k_k3 starts it from there, and gathers the permuted c0 from `in` ...
-            ten.gsrc = in; ten.gsrc_op_offset = 0; // (grouped: the op's group names its source block; g_op_offset carries the chunk offset)
-            const bool fused = fuse_pays(env, nc, L); // ... (small grids take the unfused sequence: k_k1 writes the zero polynomial, k_floor_rows adds into it)
-            if (groups.sum_out && !fused) throw std::logic_error("level sum: the fused key switch only"); // (fuse_pays grows with the chunk)
-            launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, ix, nullptr, B, nullptr, false, fused, &groups, fused);
-            key_switch_tail(env, L, nc, S, B, nullptr, false, nullptr, nullptr, fused ? &ten : nullptr, &groups, off);
-        }
-        return groups.sum_out != nullptr;
+        KsSource src{KsKind::Grouped};
+        src.a = in; src.groups = groups;
+        return key_switch_batch(L, n, src, false, out, false);
     }
     u64 rotate_sum(int L, u64 n, const u64 *in, const int *steps, u64 n_steps, u64 *out)
     {
@@ -1203,7 +1151,7 @@ public:
         }
         // node by node where that is the better shape: no fused path; CKKS batches so small that even the widest level stays within the
         // latency shape (digit-split k_k3: he355_set_latency_max) -- a BFV context has no latency shape, its levels always go grouped
-        if (!bfs_on || trie.size() == 1 || !k3_can_fuse(nenv) || (P.scheme == kSchemeCKKS && latency_shape(n * widest)) || n > 0xFFFFFFFFull / trie.size())
+        if (!bfs_on || trie.size() == 1 || !k3_can_fuse(nenv) || latency_shape(env_, n * widest) || n > 0xFFFFFFFFull / trie.size())
             return rotate_sum_by_node(L, n, in, trie, depth, out);
         require_keyswitch();
         const bool bfv = P.scheme == kSchemeBFV;
@@ -1258,7 +1206,7 @@ public:
             Held cur{pool_};
             cur.reset(static_cast<u64 *>(pool_.alloc(G * bytes)));
             if (in_k3) { gt.g.sum_out = out; gt.g.count = gt.d_mult; }
-            if (apply_galois_grouped(L, G, n, src, gt.g, cur.p)) ++paths_.level_sums_in_k3;
+            if (apply_galois_grouped(L, G * n, src, gt.g, cur.p)) ++paths_.level_sums_in_k3;
             else { ++paths_.level_sums_by_kernel; launch_sum_groups(env_, L, n, (u32)G, cur.p, gt.d_mult, out); }
             held.reset(cur.p);
             cur.p = nullptr;
@@ -1286,13 +1234,7 @@ public:
         // one ciphertext slab per trie level (a node's ciphertext lives until its last child is done; a leaf needs one only when
         // several steps end there)
         const size_t levels = depth;
-        if (levels * bytes > rot_tmp_bytes_) {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            pool_.raw_free(rot_tmp_);
-            rot_tmp_ = nullptr; rot_tmp_bytes_ = 0;
-            dmalloc(rot_tmp_, levels * bytes);
-            rot_tmp_bytes_ = levels * bytes;
-        }
+        grow(rot_tmp_, rot_tmp_bytes_, levels * bytes);
         u64 switches = 0;
         // depth-first: (node, level of the node = number of terms applied)
         std::vector<std::pair<int, size_t>> stack;
@@ -1335,20 +1277,14 @@ public:
         HIPCHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, stream_));
         if (!depth) return;
         require_keyswitch();
-        if (2 * bytes > rot_tmp_bytes_) {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            pool_.raw_free(rot_tmp_);
-            rot_tmp_ = nullptr; rot_tmp_bytes_ = 0;
-            dmalloc(rot_tmp_, 2 * bytes);
-            rot_tmp_bytes_ = 2 * bytes;
-        }
+        grow(rot_tmp_, rot_tmp_bytes_, 2 * bytes);
         u64 *ga = rot_tmp_, *gb = rot_tmp_ + n * per;
         for (size_t t = 0; t < depth; ++t) {
             std::map<uint32_t, std::vector<uint32_t>> groups; // Galois element -> ciphertexts whose t-th term it is
             u64 m_all = 0;
             for (u64 i = 0; i < n; ++i)
                 if (t < terms[i].size()) { groups[P.galois_elt_from_step(terms[i][t])].push_back((uint32_t)i); ++m_all; }
-            if (P.scheme == kSchemeCKKS && level_walk_ && k3_can_fuse(env_) && !latency_shape(m_all) && groups.size() > 1) {
+            if (P.scheme == kSchemeCKKS && level_walk_ && k3_can_fuse(env_) && !latency_shape(env_, m_all) && groups.size() > 1) {
                 // ONE grouped key-switch sequence for every ciphertext that has a t-th term (groups of one op, each with its own Galois
                 // element and key, ordered by element so that neighbouring waves share key rows): the ciphertexts are read where they lie
                 // in `out` (KsGroups::src_block), the results land compactly in gb and are scattered back.  A loop over the elements
@@ -1366,7 +1302,7 @@ public:
                         order.push_back(i);
                     }
                 const GroupTables gt = upload_groups(perms, keys, src_block, mult, 1);
-                apply_galois_grouped(L, m_all, 1, out, gt.g, gb);
+                apply_galois_grouped(L, m_all, out, gt.g, gb);
                 launch_move_cts(env_, out, gb, order.data(), m_all, per, true);
                 continue;
             }
@@ -1408,7 +1344,7 @@ public:
             // latency shape (1 ciphertext at N = 2^14: 2.02 -> 1.59 ms) -- and in the throughput regime (1024 ciphertexts at N = 2^14:
             // 44.1 -> 38.9 ms); in between (64-80 ciphertexts at N <= 2^14) the BFV kernels' launches fill the chip better: 1.47 -> 1.77 ms.
             const int n_steps = rot + (count > half ? 1 : 0);
-            const bool ntt_chain = level_walk_ && n_steps >= 2 && k3_can_fuse(ntt_env()) && (n <= lat_limit() || n * P.N >= ((u64)1 << 23));
+            const bool ntt_chain = level_walk_ && n_steps >= 2 && k3_can_fuse(ntt_env()) && (latency_shape(ntt_env(), n) || n * P.N >= ((u64)1 << 23));
             PolyView pv{};
             pv.base = inout; pv.polys_per_item = 2 * L; pv.item_stride = 2 * (u64)L * P.N;
             for (int p2 = 0; p2 < 2 * L; ++p2) pv.prime_of[p2] = (unsigned char)(p2 % L);
@@ -1507,11 +1443,7 @@ public:
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)bytes > 0.9 * (double)(free_b + bfv_bytes_ + pool_.cached_bytes())) return false;
         try {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            pool_.raw_free(bfv_scratch_);
-            bfv_scratch_ = nullptr; bfv_bytes_ = 0;
-            dmalloc(bfv_scratch_, bytes);
-            bfv_bytes_ = bytes;
+            grow(bfv_scratch_, bfv_bytes_, bytes);
             return true;
         } catch (const OutOfDeviceMemory &) {
             return false;
@@ -1610,13 +1542,13 @@ public:
         HIPCHECK(hipGetLastError());
     }
     // key switching for BFV: the target is in coefficient form; result added into c01 (coefficient form)
-    void bfv_key_switch(int L, u64 nc, const Scratch &S, const KsBuffers &B, const u64 *key, const u64 *target, u64 target_op_stride,
-                        const u64 *add01 = nullptr, u64 add01_item_stride = 0)
+    void bfv_key_switch(const KernelEnv &env, int L, u64 nc, const Scratch &S, const KsBuffers &B, const u64 *key, const u64 *target,
+                        u64 target_op_stride, const u64 *add01 = nullptr, u64 add01_item_stride = 0)
     {
-        launch_k2(env_, L, nc, B, target, target_op_stride);
-        launch_k3(env_, L, nc, B, key);
-        launch_bfv_tail_sp(env_, nc * 2, B.tpr, S.rlr);
-        launch_bfv_tail_fin(env_, L, nc, B.t, S.rlr, B.c01, B.c01_item_stride, add01, add01_item_stride);
+        launch_k2(env, L, nc, B, target, target_op_stride);
+        launch_k3(env, L, nc, B, key);
+        launch_bfv_tail_sp(env, nc * 2, B.tpr, S.rlr);
+        launch_bfv_tail_fin(env, L, nc, B.t, S.rlr, B.c01, B.c01_item_stride, add01, add01_item_stride);
     }
     // ---- client side on the device -----------------------------------------------------
     void set_public_key(const u64 *h_pk) // [2][K][N], NTT form
@@ -1635,13 +1567,7 @@ public:
     }
     u64 *client_scratch(size_t elems)
     {
-        if (elems > client_scratch_elems_) {
-            HIPCHECK(hipStreamSynchronize(stream_));
-            pool_.raw_free(client_scratch_);
-            client_scratch_ = nullptr;
-            dmalloc(client_scratch_, elems * 8);
-            client_scratch_elems_ = elems;
-        }
+        grow(client_scratch_, client_scratch_bytes_, elems * 8);
         return client_scratch_;
     }
     static PolyView poly_view(u64 *base, int polys_per_item, size_t N, int period)
@@ -1982,7 +1908,7 @@ private:
     u64 *d_pk_ = nullptr, *d_sk_ = nullptr;
     u64 zero_seed_ = os_seed(), zero_index_ = 0;
     u64 *client_scratch_ = nullptr;
-    size_t client_scratch_elems_ = 0;
+    size_t client_scratch_bytes_ = 0;
     std::map<int, CrtTablesDev> crt_;
     std::map<uint32_t, u64 *> d_galois_;
     std::map<uint32_t, uint32_t *> d_perm_;
@@ -1997,8 +1923,8 @@ private:
     size_t rot_tmp_bytes_ = 0;
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
     he355_path_stats_t paths_{};
-    bool lds_auto_ = !getenv("HE355_LDS_MAX");
-    u64 lds_max_ = getenv("HE355_LDS_MAX") ? (u64)std::max(0, std::atoi(getenv("HE355_LDS_MAX"))) : 0;
+    bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
+    u64 lds_max_ = 0;
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
     unsigned char *d_groups_ = nullptr; // group tables of the grouped key switches (upload_groups)
     size_t groups_bytes_ = 0, groups_next_ = 0;

@@ -748,7 +748,7 @@ def test_lds_shape_equals_the_other_shapes_and_the_oracle(pair, be, n):
     want_rl = [o.relinearize(c3[r], rk) for r in range(n)]
     want_rot = [o.apply_galois(a[r], e1, gk1) for r in range(n)]
     want_rot_add = [o.add(want_rl[r], o.apply_galois(a[r], e3, gk3)) for r in range(n)]
-    fits = N <= 8192 and L <= 8
+    fits = N <= 8192 and L <= 6  # ks_lds_supported: the partial products, (2L + 4) L N words per ciphertext, fit the arena up to L = 6
     try:
         for lds in (64, 0):
             g.set_lds_max(lds)
@@ -800,6 +800,44 @@ def test_lds_shape_equals_the_other_shapes_and_the_oracle(pair, be, n):
                 assert st["ks_lds"] == 0, st
     finally:
         g.set_lds_max(None)
+
+
+def test_lds_chunks_on_two_streams_wait_for_earlier_work(be, oracle):
+    """A multiply -> relinearize (-> rescale) batch cut into ring-in-LDS chunks that alternate between the two streams, its operand
+    produced by asynchronous he355_add calls queued just before it: the second stream must wait for that work before its first chunk,
+    whatever shape chunk 0 took.  Every result equals the oracle's; the path counters prove every chunk took the ring-in-LDS shape."""
+    g, o = make_pair(be, oracle, "n2048_f64")
+    rng = np.random.default_rng(20261016)
+    try:
+        L, N, n, chunk, adds = g.L, g.N, 12, 4, 4
+        g.set_lds_max(None)  # the library's own rule (128 ciphertexts at this ring), whatever the environment says
+        g.set_dual_stream(True)
+        g.set_chunk(chunk)  # three chunks: 0 and 2 on the first stream, 1 on the second
+        rk = o.random_kswitch_key(rng)
+        g.set_relin_key(rk)
+        a0, d, b = rand_cts(o, rng, n, L), rand_cts(o, rng, n, L), rand_cts(o, rng, 1, L)
+        dd, db = g.to_device(d), g.to_device(b)
+        want = []
+        for r in range(n):
+            ar = a0[r]
+            for _ in range(adds):
+                ar = o.add(ar, d[r])
+            want.append(o.relinearize(o.multiply_ntt(ar, b[0]), rk))
+        g.path_stats(reset=True)
+        for rescale in (False, True):
+            da = g.to_device(a0)
+            for _ in range(adds):  # a += d, queued on the first stream and not waited for
+                g.add(L, 2, n, da, dd, be.Context.pairwise(), da)
+            Lo = L - 1 if rescale else L
+            out = g.alloc(n * 2 * Lo * N)
+            g.multiply_relin(L, n, da, db, be.Context.outer(0, n, 0, 1), out, rescale=rescale)
+            got = out.download((n, 2, Lo, N))
+            for r in range(n):
+                assert np.array_equal(got[r], o.rescale(want[r]) if rescale else want[r]), (rescale, r)
+        st = g.path_stats()
+        assert st["ks_lds"] == 2 * (n // chunk) and st["ks_fused"] == st["ks_unfused"] == st["ks_latency"] == 0, st
+    finally:
+        g.close()
 
 
 @pytest.mark.parametrize("N,bits,expect_lds", [
