@@ -93,9 +93,7 @@ public:
     // batched encoders / decoders: one device call per operand when a GPU is present (same bits as the host encoders)
     std::vector<Plain> encodeBatch(const std::vector<std::vector<double>> &rows);
     std::vector<Plain> encodeBatch(const std::vector<std::vector<std::int64_t>> &rows);
-    std::vector<std::vector<double>> decodeBatchCKKS(const std::vector<Plain> &plains);
-    std::vector<std::vector<std::int64_t>> decodeBatchBFV(const std::vector<Plain> &plains);
-    // ... writing / downloading only the slots a workload's decode() reads: `ranges` = {first slot, count} (at most 4), the result is flat,
+    // decoders that write / download only the slots a workload's decode() reads: `ranges` = {first slot, count} (at most 4), the result is flat,
     // [plains.size()][sum of counts] (ckks eltwise .cpp:214-226 copies the first n slots of a result; bfv row .cpp:339-369 the first dim3 of
     // both batching rows).  The values land in a page-locked buffer the context owns and are copied out of it once.
     typedef std::vector<std::pair<std::uint64_t, std::uint64_t>> SlotRanges;

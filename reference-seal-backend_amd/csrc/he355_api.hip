@@ -284,20 +284,13 @@ public:
     // ---- device memory (device_pool.h): slabs handed to callers come from the pool, the context's own tables / keys / arenas
     // are raw allocations; both are counted
     template <class T> void dmalloc(T *&p, size_t bytes) { p = static_cast<T *>(pool_.raw_malloc(bytes)); }
-    // HE355_POOL=0: every he355_malloc / he355_free is a hipMalloc / drain + hipFree again (the pre-pool behaviour, kept for A/B timing:
-    // tools/bench_bridge.py, profiles/r04_bridge_phases.jsonl)
     void *pool_alloc(size_t bytes)
     {
         use();
-        return pool_on_ ? pool_.alloc(bytes) : pool_.raw_malloc(bytes ? bytes : 8);
+        return pool_.alloc(bytes);
     }
     void pool_free(void *p)
     {
-        if (!pool_on_) { // HE355_POOL=0: every block is a raw allocation, freed as before the pool existed
-            sync();
-            pool_.raw_free(p);
-            return;
-        }
         switch (pool_.release(p)) {
         case DevicePool::kReleased: return;
         case DevicePool::kCached: throw std::invalid_argument("he355_free: this block was freed already");
@@ -558,10 +551,9 @@ public:
     // The fused mod-down runs the special prime's tiles as a launch of their own, ahead of the data primes' (their epilogue needs its
     // result): n1 rows x nc / 8 op-groups of blocks.  With a handful of ciphertexts at a small ring that launch is a few dozen blocks
     // on 256 CUs -- as long as the data primes' launch and nearly idle -- and the unfused sequence (every prime's tiles in ONE launch,
-    // then the two floor kernels) is the shorter chain: fused from 128 such blocks up (HE355_K3_FUSE=all: always).
+    // then the two floor kernels) is the shorter chain: fused from 128 such blocks up.
     bool fuse_pays(const KernelEnv &e, u64 nc, int L) const
     {
-        if (k3_fuse_policy() == 2) return true;
         // ... or from 1536 (tile, op-group) units of the data primes' launch up: at L = 16 that launch is 16 times the special prime's, and what
         // the fused epilogue saves (the sums' trip through HBM, k_floor_rows) outweighs the idle launch ahead of it from 17 ciphertexts on at
         // N = 2^15 instead of 25 (batch 20 / 24 of the headline shape: 1.64 -> 1.45 / 1.79 -> 1.52 ms, DotProduct -9 %; profiles/r05_latency_boundary.txt)
@@ -1366,9 +1358,6 @@ public:
         if (count > slots) count = slots;
         int rotations = 64 - __builtin_clzll(count);
         if (((u64)1 << (rotations - 1)) == count) --rotations;
-        Indexer ix{};
-        ix.pairwise = 1;
-        (void)ix;
         u64 *cur = inout, *nxt = tmp;
         for (int i = 0; i < rotations; ++i) {
             rotate(L, n, cur, 1 << i, nxt, cur); // rotate_vector + add_inplace in one pipeline
@@ -1469,7 +1458,6 @@ public:
         // the terms of a matrix product) each is extended to Bsk and transformed ONCE (steps (1)-(3) per operand instead of per result:
         // SEAL's multiply recomputes them for every pair, the values are the same), and a result costs its dyadic tensor, three inverse
         // transforms and steps (6)-(8).
-        const bool hoist_on = (behz_fuse_mask() & 2) != 0;
         const u64 gsz = std::min<u64>(ix.gs, n), G = ix.gs >= n ? 1 : (n + ix.gs - 1) / ix.gs;
         src.I = (gsz + ix.b1 - 1) / ix.b1; src.J = std::min<u64>(ix.b1, gsz); src.na = G * src.I;
         const u64 n_cts = src.na + G * src.J;
@@ -1479,7 +1467,7 @@ public:
             if (ranges_overlap(out, (size_t)n * 3 * L * N, a, a_cts * 2 * L * N) || ranges_overlap(out, (size_t)n * 3 * L * N, b, b_cts * 2 * L * N))
                 throw std::invalid_argument("he355_bfv_multiply: `out` overlaps an operand");
         }
-        bool lists = hoist_on && (G == 1 || (n % ix.gs == 0 && ix.gs % ix.b1 == 0)) && n_cts <= n; // at least two times fewer extensions than the 2 n of the per-pair path
+        bool lists = (G == 1 || (n % ix.gs == 0 && ix.gs % ix.b1 == 0)) && n_cts <= n; // at least two times fewer extensions than the 2 n of the per-pair path
         size_t c = std::min<size_t>(chunk_, (size_t)n);
         if (lists) {
             while (!reserve_bfv_scratch((e_words + per_res * c) * 8) && c > 1) c = (c + 1) / 2;
@@ -1934,7 +1922,6 @@ private:
     std::map<uint32_t, uint32_t *> d_gather_;
     size_t chunk_ = 1024;
     DevicePool pool_;
-    const bool pool_on_ = !(getenv("HE355_POOL") && getenv("HE355_POOL")[0] == '0');
 };
 
 } // namespace he355

@@ -114,29 +114,8 @@ struct K3Fuse {
     const uint32_t *gperm = nullptr;
     u64 gsrc_op_offset = 0;
 };
-// HE355_K3_FUSE: "0" = the unfused sequence everywhere (k_floor_rows finishes the mod-down); unset / "1" = fused where it pays, with the
-// small-grid rules (both engines in one launch, four-wave u64-engine blocks, unfused below a minimum of special-prime blocks); "all" =
-// fused for every throughput-shape batch and none of the small-grid rules (the schedule before those rules existed).  The thresholds
-// are constants (profiles/r04_dual_engine_latency.txt: swept on one box).
-inline int k3_fuse_policy()
-{
-    static const int v = [] {
-        const char *e = std::getenv("HE355_K3_FUSE");
-        if (!e) return 1;
-        if (e[0] == '0') return 0;
-        if (e[0] == 'a' || e[0] == 'A') return 2;
-        return 1;
-    }();
-    return v;
-}
-inline bool k3_can_fuse(const KernelEnv &env) { return k3_fuse_policy() != 0 && env.scheme == 2 && env.K >= 2; }
-// HE355_BEHZ_FUSE=<mask>: bit 0 = extension / floor fused with the column passes, bit 1 = operands shared by several results extended and
-// transformed once (he355_api.hip: bfv_multiply3); default 3.
-inline int behz_fuse_mask()
-{
-    static const int v = [] { const char *e = std::getenv("HE355_BEHZ_FUSE"); return e ? std::atoi(e) & 3 : 3; }();
-    return v;
-}
+// The fused mod-down (CKKS only); whether it pays for a batch is fuse_pays' rule (he355_api.hip).
+inline bool k3_can_fuse(const KernelEnv &env) { return env.scheme == 2 && env.K >= 2; }
 // floor step, row half: out[(op,k,i)] = (tsrc[(op,k,i)] - NTT(dst_cols[(op,k,i)])) * s^-1 (+ addend) mod q_i.
 // Strides are in u64 elements.  If tail_prime >= 0 the rows of that prime additionally go through the
 // inverse row pass into tail[(op,k)] (next floor step's source).

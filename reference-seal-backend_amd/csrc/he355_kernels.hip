@@ -737,10 +737,7 @@ template <int LOGN1> __device__ __forceinline__ bool fits_48(double m0, double q
 // Per-target constants come through the constant address space (scalar loads): a vector load of a PrimeDev field would put an
 // s_waitcnt vmcnt(0) -- i.e. the full HBM write latency of the previous target's stores -- in front of every target.
 // butterflies of a column-pass stage issued together (interleaved dependent chains, ArF64::mulmod_vv_g)
-#ifndef HE355_K2_G
-#define HE355_K2_G 2
-#endif
-constexpr int kK2G = HE355_K2_G;
+constexpr int kK2G = 2;
 // every n_groups-th set bit of mask, starting with the g-th (latency shape: the targets of a column are dealt to n_groups blocks)
 __device__ __forceinline__ u64 split_mask(u64 mask, int g, int n_groups)
 {
@@ -939,15 +936,9 @@ __device__ __forceinline__ void k2n_targets_u64(const K2Args &A, const PrimeDev 
 // WIDE: the launch's digits are 60-bit (integers throughout); else below 2^52 (doubles).  Two instantiations instead of one kernel with
 // both paths: each gets its own register allocation (one kernel at 168 registers spilled 102 through the wide path's live ranges and
 // cost 14.9 ms; at 256 it took 12.4; the pair takes 11.0 + 1.0).  Two or three waves per SIMD make no difference to the narrow
-// instantiation any more (11.04 / 11.18 ms): K2N_WAVES = 2 leaves it without spills.
-#ifndef K2N_WAVES
-#define K2N_WAVES 2
-#endif
-#ifndef K2N_WAVES_WIDE
-#define K2N_WAVES_WIDE 2
-#endif
+// instantiation any more (11.04 / 11.18 ms): two leave it without spills.
 template <int LOGN1, bool WIDE>
-__global__ void __launch_bounds__(kBlock, WIDE ? K2N_WAVES_WIDE : K2N_WAVES) k_k2n(K2Args A, const PrimeDev *primes)
+__global__ void __launch_bounds__(kBlock, 2) k_k2n(K2Args A, const PrimeDev *primes)
 {
 #define K2N_BID_X blockIdx.x
 #include "k2n_body.inc"
@@ -1864,18 +1855,9 @@ __global__ void __launch_bounds__(kBlock) k_bfv_tail_sp(const u64 *tpr, u64 *rp,
 // k_bfv_tail_fin is memory-bound and latency-hidden by occupancy alone: at 101 registers five waves fit a SIMD, and the 6144 waves of
 // BASELINE configs[4]'s calls (64 ciphertexts x 2 x 3 polynomials) ran as one full round plus a fifth of one.  Held to six waves per SIMD
 // (80 registers, 32 spilled) the call is one round: 109 -> 95 us, the matrix product 67.1 -> 65.3 ms.
-#ifndef HE355_TAILFIN_WAVES
-#define HE355_TAILFIN_WAVES 6
-#endif
 template <int LOGN1>
-__global__ void
-#if HE355_TAILFIN_WAVES
-__launch_bounds__(kBlock, HE355_TAILFIN_WAVES)
-#else
-__launch_bounds__(kBlock)
-#endif
-k_bfv_tail_fin(const u64 *t, const u64 *rp, u64 *c01, u64 c01_item_stride, const u64 *add01, u64 add01_item_stride, const PrimeDev *primes,
-                                                         const FloorConst *fcs, int L, int K)
+__global__ void __launch_bounds__(kBlock, 6) k_bfv_tail_fin(const u64 *t, const u64 *rp, u64 *c01, u64 c01_item_stride, const u64 *add01,
+                                                            u64 add01_item_stride, const PrimeDev *primes, const FloorConst *fcs, int L, int K)
 {
     constexpr int N1 = 1 << LOGN1;
     constexpr u64 N = (u64)N1 << kRowLog;
@@ -2039,19 +2021,12 @@ void launch_mul3(const KernelEnv &env, int L, u64 n_results, const u64 *a, const
     hipLaunchKernelGGL(k_mul3, dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, a, b, out, ix, env.primes, L, logN, n_results);
 }
 
-// Latency shape: the two engines' launches of a stage as one kernel (k_k1_dual, k_k2n_dual, k_k3_dual, k_floor_rows_dual); HE355_DUAL_ENGINE=0: one
-// launch per engine as in the throughput shape.
-static bool dual_engine_launches()
-{
-    static const bool off = getenv("HE355_DUAL_ENGINE") && getenv("HE355_DUAL_ENGINE")[0] == '0';
-    return !off;
-}
-// ... also for small grids of the throughput shape: up to this many blocks for both engines together (profiles/r04_dual_engine_latency.txt)
+// The two engines' launches of a stage as one kernel (k_k1_dual, k_k2n_dual, k_k3_dual, k_floor_rows_dual) in the latency shape, and
+// for small grids of the throughput shape: up to this many blocks for both engines together (profiles/r04_dual_engine_latency.txt)
 // (round 5: per kernel.  k_k3's shared launch pays up to a few thousand blocks since the fold form of the u64 engine brought its blocks
 // close to the fp64 engine's in length; the others -- whose dual kernels are the latency shape's, behind a function boundary -- keep
 // the 1024 they were swept at.  profiles/r05_dual_threshold_sweep.txt)
-static unsigned dual_max_blocks_k3() { return k3_fuse_policy() == 2 ? 0u : 4096u; }
-static unsigned dual_max_blocks() { return k3_fuse_policy() == 2 ? 0u : 1024u; }
+constexpr unsigned kDualMaxBlocksK3 = 4096, kDualMaxBlocks = 1024;
 void launch_k1(const KernelEnv &env, int L, K1Mode mode, u64 n_ops, u64 op_offset, const u64 *a, const u64 *b, Indexer ix, const uint32_t *perm,
                const KsBuffers &buf, const u64 *addend, bool no_c01, bool no_c1, const KsGroups *groups, bool no_c0n)
 {
@@ -2078,8 +2053,8 @@ void launch_k1(const KernelEnv &env, int L, K1Mode mode, u64 n_ops, u64 op_offse
     }
     // (k_k1 proper -- the throughput shape -- maps a block onto one (residue, row) tile and four consecutive ops: its own grid below)
     const hipStream_t st = env.stream;
-    if (gp[0] && gp[1] && (n_ops <= 8 || gp[0] + gp[1] <= dual_max_blocks()) && mode != K1_MUL_C2 && !(mode == K1_MUL && no_c01) &&
-        dual_engine_launches()) { // latency shape / small grids: one launch for both engines
+    if (gp[0] && gp[1] && (n_ops <= 8 || gp[0] + gp[1] <= kDualMaxBlocks) && mode != K1_MUL_C2 && !(mode == K1_MUL && no_c01)) {
+        // latency shape / small grids: one launch for both engines
         const dim3 grid(gp[0] + gp[1]);
         if (mode == K1_MUL) hipLaunchKernelGGL((k_k1_dual<K1_MUL>), grid, dim3(kBlock), 0, st, AP[0], AP[1], gp[0], env.primes);
         else if (mode == K1_CT3) hipLaunchKernelGGL((k_k1_dual<K1_CT3>), grid, dim3(kBlock), 0, st, AP[0], AP[1], gp[0], env.primes);
@@ -2139,9 +2114,9 @@ void launch_k2(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
         AK[wide] = A;
         gk[wide] = (unsigned)(n_ops * A.n_dig * 4);
     }
-    if (gk[0] && gk[1] && dual_engine_launches()) { // latency shape or a small grid: both digit kinds in one launch (k_k2n_dual)
+    if (gk[0] && gk[1]) { // latency shape or a small grid: both digit kinds in one launch (k_k2n_dual)
         const int ts = target_split(gk[0] + gk[1]);
-        if (tsplit > 1 || (gk[0] + gk[1]) * (unsigned)ts <= dual_max_blocks()) {
+        if (tsplit > 1 || (gk[0] + gk[1]) * (unsigned)ts <= kDualMaxBlocks) {
             AK[0].tsplit = AK[1].tsplit = ts;
             const dim3 gd(gk[0] + gk[1], (unsigned)ts);
 #define HE355_K2D(L1) case L1: hipLaunchKernelGGL((k_k2n_dual<L1>), gd, dim3(kBlock), 0, env.stream, AK[0], AK[1], gk[0], env.primes); break;
@@ -2249,8 +2224,7 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
         }
         // u64-engine tiles of a small grid (at most half the CUs busy with 8-wave blocks): FOUR waves per block -- one per SIMD, each at
         // the full issue rate instead of half of it, and twice the blocks; the serial digit loop of a tile is what such a launch lasts
-        const unsigned four_max = k3_fuse_policy() == 2 ? 0u : 128u;
-        if (pass == 1 && waves == 8 && g <= four_max && !level_sum) {
+        if (pass == 1 && waves == 8 && g <= 128 && !level_sum) {
             size_grid(4);
             // (a CU holds ONE block of either shape -- the LDS arrays -- so the four-wave blocks must still fit one round together with the
             // fp64-engine blocks they may share the launch with)
@@ -2264,13 +2238,13 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
     }
     const hipStream_t st3 = env.stream;
     const bool tensor = fuse && fuse->ta;
-    if (n_pend == 2 && pend[0].waves == 1 && dual_engine_launches()) { // latency shape
+    if (n_pend == 2 && pend[0].waves == 1) { // latency shape
         const unsigned ny = (unsigned)std::max(pend[0].A.n_split, pend[1].A.n_split);
         hipLaunchKernelGGL(k_k3_dual, dim3(pend[0].g + pend[1].g, ny), dim3(64), 0, st3, pend[0].A, pend[1].A, pend[1].g, env.primes);
         return;
     }
     // throughput shape, small grids (up to two blocks per CU for both engines together): both engines in one launch
-    if (n_pend == 2 && pend[0].waves == 8 && pend[0].g + pend[1].g <= dual_max_blocks_k3() && dual_engine_launches()) {
+    if (n_pend == 2 && pend[0].waves == 8 && pend[0].g + pend[1].g <= kDualMaxBlocksK3) {
         const dim3 gd(pend[0].g + pend[1].g);
 #define HE355_K3D8(F, T, G)                                                                                                                     \
     do {                                                                                                                                        \
@@ -2369,7 +2343,7 @@ void launch_floor_rows(const KernelEnv &env, u64 n_ops, const FloorRowsArgs &arg
     // per block: up to 8 jobs per wave, fewer when that would leave CUs without blocks
     u32 jpb = 8 * kWaves;
     while (jpb > (u32)kWaves && (((u64)args.n_tgt << env.logn1) * ((n_jobs + jpb - 1) / jpb) < 256u * 8 || jpb / 2 >= n_jobs)) jpb >>= 1;
-    if (args.tail_prime < 0 && dual_engine_launches()) { // no tail prime; latency shape or small grids: both engines in one launch
+    if (args.tail_prime < 0) { // no tail prime; latency shape or small grids: both engines in one launch
         FloorRowsDev AE[2];
         unsigned ge[2] = {0, 0};
         for (int e = 0; e < 2; ++e) {
@@ -2381,7 +2355,7 @@ void launch_floor_rows(const KernelEnv &env, u64 n_ops, const FloorRowsArgs &arg
                 if ((prime_f64[i] != 0) == (e == 0)) A.i_list[A.n_i++] = (unsigned char)i;
             ge[e] = (unsigned)((((u64)A.n_i) << env.logn1) * ((n_jobs + jpb - 1) / jpb));
         }
-        if (ge[0] && ge[1] && (n_ops <= 8 || ge[0] + ge[1] <= dual_max_blocks())) {
+        if (ge[0] && ge[1] && (n_ops <= 8 || ge[0] + ge[1] <= kDualMaxBlocks)) {
             hipLaunchKernelGGL(k_floor_rows_dual, dim3(ge[0] + ge[1]), dim3(kBlock), 0, env.stream, AE[0], AE[1], ge[0], env.primes);
             return;
         }
@@ -2424,7 +2398,7 @@ void launch_behz_extend(const KernelEnv &env, const BehzDev &bz, const BehzSrc &
 }
 bool behz_cols_fusable(const KernelEnv &env, const BehzDev &bz)
 {
-    return (behz_fuse_mask() & 1) && bz.L <= 4 && bz.nB <= 6 && env.logn1 >= 1 && env.logn1 <= 4;
+    return bz.L <= 4 && bz.nB <= 6 && env.logn1 >= 1 && env.logn1 <= 4;
 }
 void launch_behz_extend_cols(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
 {
@@ -2485,7 +2459,7 @@ void launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops,
         }
         ge[pass] = (unsigned)((n_ops * A.n_r) << env.logn1);
     }
-    if (ge[0] && ge[1] && ge[0] + ge[1] <= dual_max_blocks() && dual_engine_launches()) {
+    if (ge[0] && ge[1] && ge[0] + ge[1] <= kDualMaxBlocks) {
         hipLaunchKernelGGL(k_behz_rows_tensor_dual, dim3(ge[0] + ge[1]), dim3(kBlock), 0, env.stream, AE[0], AE[1], ge[0], env.primes);
         return;
     }
@@ -2513,7 +2487,7 @@ void launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzS
         jobs[pass] = ((n_ops * A.n_r) << env.logn1) * 3;
     }
     const unsigned g0 = grid_for(jobs[0], kWaves), g1 = grid_for(jobs[1], kWaves);
-    if (jobs[0] && jobs[1] && g0 + g1 <= dual_max_blocks() && dual_engine_launches()) {
+    if (jobs[0] && jobs[1] && g0 + g1 <= kDualMaxBlocks) {
         hipLaunchKernelGGL(k_behz_tensor_inv_dual, dim3(g0 + g1), dim3(kBlock), 0, env.stream, AE[0], AE[1], jobs[0], jobs[1], g0, env.primes);
         return;
     }

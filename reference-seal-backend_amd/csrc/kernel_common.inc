@@ -7,18 +7,12 @@ constexpr int kWaves = 4;
 
 // Each wave exchanges data only inside its own LDS region: LDS instructions of one wave execute in
 // order, so a wavefront-scope release/acquire pair (compiler ordering only) is all the hand-off needs.
-// Every wave of a block still runs the same number of phases (invalid jobs are clamped, not skipped), so
-// building with -DHE355_BLOCK_SYNC (workgroup barriers instead, debug aid) stays legal.
-#if defined(HE355_BLOCK_SYNC)
-#define HE_WAVE_SYNC() __syncthreads()
-#else
 #define HE_WAVE_SYNC()                                             \
     do {                                                           \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     \
         __builtin_amdgcn_wave_barrier();                           \
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     \
     } while (0)
-#endif
 
 // Twiddle tables are reached through pointers stored in PrimeDev (HBM), which the compiler would treat as
 // generic (flat_load + full s_waitcnt per access).  They are always global memory: say so.
@@ -80,10 +74,7 @@ __device__ __forceinline__ void store_rowC(u64 *row, int lane, const u64 v[kRowE
 
 // Key products issued together in the fused fp64 k_k3 (2 polynomials x kMacG / 2 elements): interleaved chains, at two waves per
 // SIMD a serial chain issues at 3/4 of the pipe's rate.
-#ifndef HE355_MAC_G
-#define HE355_MAC_G 4
-#endif
-constexpr int kMacG = HE355_MAC_G;
+constexpr int kMacG = 4;
 
 // ---- LDS-DMA: one 8 KiB row, HBM -> this wave's LDS staging buffer, no VGPRs, asynchronous -------------
 // Each global_load_lds_dwordx4 moves 64 x 16 B; the LDS image is the row in natural element order.

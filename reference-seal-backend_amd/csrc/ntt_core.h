@@ -188,10 +188,7 @@ template <class TW> HE_HD void gather_C(const TW &tw, int lane, Tw16 w[kTwC])
 // stages 0..3 on layout A (register bit 3-s' is the butterfly bit); twiddles are lane-uniform
 // One radix-2 stage over the 16 registers of U rows: butterflies (r, r | 1<<BIT) with twiddle index widx(r), issued
 // in groups of kBflyGroup independent butterflies (Ar::bfly_fwd_g).
-#ifndef HE355_BFLY_GROUP
-#define HE355_BFLY_GROUP 2
-#endif
-constexpr int kBflyGroup = HE355_BFLY_GROUP;
+constexpr int kBflyGroup = 2;
 template <int U, int BIT, bool LAZY, bool SW = false, class Ar, class WIdx> HE_HD void row_fwd_stage_x(const Ar &ar, typename Ar::T (*x)[kRowE], const Tw16 *w, WIdx widx)
 {
     constexpr int kTotal = 8 * U, G = kBflyGroup < kTotal ? kBflyGroup : kTotal;

@@ -409,8 +409,6 @@ def test_steady_state_operate_does_not_allocate(backend, which):
     destroyed in between, as the harness's measurement loop does -- perform no hipMalloc and no hipFree at all (he355_alloc_stats,
     process totals), and every he355_malloc inside them is served from a free list."""
     from hebench_harness import Handle, ParameterIndexer
-    if os.environ.get("HE355_POOL", "1")[:1] == "0":
-        pytest.skip("HE355_POOL=0 selects the pre-pool allocation behaviour on purpose")
     be = importlib.import_module("reference-seal-backend_amd")
     hb, operands = _steady_state_case(backend, which)
     L = backend.L
@@ -439,8 +437,6 @@ def test_steady_state_operate_does_not_allocate(backend, which):
 def test_pool_reuses_and_trims():
     """he355_malloc / he355_free: a freed block of the same size class is handed out again without a HIP call; he355_pool_trim gives the
     cached blocks back to the device; a block keeps its contents' independence (two live blocks never alias)."""
-    if os.environ.get("HE355_POOL", "1")[:1] == "0":
-        pytest.skip("HE355_POOL=0 selects the pre-pool allocation behaviour on purpose")
     be = importlib.import_module("reference-seal-backend_amd")
     g = be.Context(be.SCHEME_CKKS, 4096, bit_sizes=[60, 45, 60], sec128=False, device=0)
     a = g.alloc(1 << 16)
@@ -467,8 +463,6 @@ def test_pool_reuses_and_trims():
 def test_double_free_and_foreign_pointers_are_rejected():
     """he355_free of a block that already sits on the pool's free list, or that another context allocated, is an argument error -- it
     must not be hipFree'd while the list still holds it (the next allocation of that class would receive freed memory)."""
-    if os.environ.get("HE355_POOL", "1")[:1] == "0":
-        pytest.skip("HE355_POOL=0 selects the pre-pool allocation behaviour on purpose")
     be = importlib.import_module("reference-seal-backend_amd")
     g = be.Context(be.SCHEME_CKKS, 4096, bit_sizes=[60, 45, 60], sec128=False, device=0)
     g2 = be.Context(be.SCHEME_CKKS, 4096, bit_sizes=[60, 45, 60], sec128=False, device=0)

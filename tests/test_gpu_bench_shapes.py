@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 # The path-counter assertions describe the LIBRARY'S OWN choice of shape: under a run-time setting that pins another one (tools/test_matrix.sh
 # runs this module under all of them) only the bits are held to the oracle.
-_SHAPE_ENV = ("HE355_K3_FUSE", "HE355_CHUNK", "HE355_LATENCY_MAX", "HE355_LEVEL_WALK", "HE355_LDS_MAX", "HE355_DUAL_ENGINE", "HE355_FORCE_U64")
+_SHAPE_ENV = ("HE355_CHUNK", "HE355_LATENCY_MAX", "HE355_LEVEL_WALK", "HE355_LDS_MAX", "HE355_FORCE_U64")
 DEFAULT_SHAPES = not any(os.environ.get(k) for k in _SHAPE_ENV)
 
 
@@ -138,3 +138,79 @@ def test_bfv_matmul_bench_shape_level_sums_inside_the_key_switch(be, oracle):
         assert np.array_equal(wl.result.download((64, 2, wl.L, wl.N)), full), "k_sum_groups and the in-kernel level sum disagree"
     finally:
         ctx.close()
+
+
+# Shapes where the library's own rule gives each arithmetic engine a launch of its own instead of the both-engines kernels:
+# (N, key-level bits, batch, engine of each prime, shape that must be taken)
+ONE_ENGINE_SHAPES = {
+    # every prime on the u64 engine (fold form), latency shape: k_k1 / k_k2n / k_k3 of that engine alone
+    "latency_u64_engine_only": (16384, [60, 60, 60], 2, [False, False, False], "ks_latency"),
+    # throughput shape, a digit grid too large for k_k2n_dual (256 x 3 digits x 4 > 1024 blocks): k_k2n per digit kind
+    "wide_digit_grid": (4096, [60, 45, 45, 60], 256, [False, True, True, False], "ks_fused"),
+}
+
+
+@pytest.mark.parametrize("case", list(ONE_ENGINE_SHAPES))
+def test_multiply_relin_rescale_one_launch_per_engine(be, oracle, case):
+    N, bits, n, fp64, shape = ONE_ENGINE_SHAPES[case]
+    g = be.Context(be.SCHEME_CKKS, N, bit_sizes=bits, sec128=False, device=0)
+    try:
+        o = oracle.Context(oracle.SCHEME_CKKS, N, bit_sizes=bits, sec128=False)
+        assert g.moduli == o.moduli
+        rng = np.random.default_rng(n)
+        L = g.L
+        rk = o.random_kswitch_key(rng)
+        g.set_relin_key(rk)
+        a = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
+        b = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
+        out = g.alloc(n * 2 * (L - 1) * N)
+        g.path_stats(reset=True)
+        g.multiply_relin(L, n, g.to_device(a), g.to_device(b), be.Context.pairwise(), out, rescale=True)
+        g.sync()
+        st = g.path_stats()
+        got = out.download((n, 2, L - 1, N))
+        for r in range(n):
+            assert np.array_equal(got[r], o.rescale(o.relinearize(o.multiply_ntt(a[r], b[r]), rk))), r
+        if DEFAULT_SHAPES:
+            assert g.fp64 == fp64
+            assert st[shape] >= 1 and all(st[k] == 0 for k in ("ks_fused", "ks_unfused", "ks_latency", "ks_lds") if k != shape), st
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("bits,fp64", [([60, 60, 60], [False, False, False]), ([45, 45, 60], [True, True, False])],
+                         ids=["data_primes_u64_engine", "data_primes_fp64_engine"])
+def test_rotate_sum_level_sums_in_one_engine_launch(be, oracle, bits, fp64):
+    """he355_rotate_sum of 128 ciphertexts at N = 2^14, L = 2: every trie level is one grouped key switch whose level sum is formed inside
+    the fused k_k3 ((L << logn1) * n / 8 = 512 blocks: level_sum_pays), and with every data prime on one engine the data-prime launch is
+    that engine's grouped fused k_k3 alone.  Every result == the oracle's loop of independent rotations + add_inplace."""
+    N, n, steps = 16384, 128, [1, 2, 3]  # 3 = 4 - 1: a NAF term under the 1-term node, a trie of two levels
+    g = be.Context(be.SCHEME_CKKS, N, bit_sizes=bits, sec128=False, device=0)
+    try:
+        o = oracle.Context(oracle.SCHEME_CKKS, N, bit_sizes=bits, sec128=False)
+        assert g.moduli == o.moduli
+        rng = np.random.default_rng(128)
+        L = g.L
+        keys = {}
+        for k in range(3):
+            for s in (1 << k, -(1 << k)):
+                e = o.galois_elt(s)
+                keys[e] = o.random_kswitch_key(rng)
+                g.set_galois_key(e, keys[e])
+        a = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
+        out = g.alloc(n * 2 * L * N)
+        g.path_stats(reset=True)
+        g.rotate_sum(L, n, g.to_device(a), steps, out)
+        g.sync()
+        st = g.path_stats()
+        got = out.download((n, 2, L, N))
+        for r in range(n):
+            want = a[r].copy()
+            for s in steps:
+                want = o.add(want, o.rotate(a[r], s, keys))
+            assert np.array_equal(got[r], want), r
+        if DEFAULT_SHAPES:
+            assert g.fp64 == fp64
+            assert st["level_sums_in_k3"] > 0 and st["level_sums_by_kernel"] == 0, st
+    finally:
+        g.close()

@@ -303,29 +303,6 @@ def test_galois_rotate_accumulate(pair, be):
         g.rotate(L, 3, da, 8, out)  # power-of-two step without a key: "Galois key not present"
 
 
-def test_block_sync_debug_mode_agrees(be, oracle):
-    """The wavefront-scope LDS hand-off and the workgroup-barrier variant give identical results."""
-    os.environ["HE355_BLOCK_SYNC"] = "1"
-    try:
-        g, o = make_pair(be, oracle, "n2048_f64")
-    finally:
-        os.environ.pop("HE355_BLOCK_SYNC", None)
-    rng = np.random.default_rng(77)
-    L = g.L
-    rk = o.random_kswitch_key(rng)
-    g.set_relin_key(rk)
-    a, b = rand_cts(o, rng, 3, L), rand_cts(o, rng, 3, L)
-    out = g.alloc(3 * 2 * (L - 1) * g.N)
-    g.multiply_relin(L, 3, g.to_device(a), g.to_device(b), be.Context.pairwise(), out, rescale=True)
-    got = out.download((3, 2, L - 1, g.N))
-    for r in range(3):
-        assert np.array_equal(got[r], o.rescale(o.relinearize(o.multiply_ntt(a[r], b[r]), rk)))
-    g.close()
-    # restore the default mode for later contexts
-    g2, _ = make_pair(be, oracle, "n1024_mixed")
-    g2.close()
-
-
 # ---------------------------------------------------------------------------------------------------------
 # BASELINE.json full sizes
 # ---------------------------------------------------------------------------------------------------------

@@ -13,7 +13,6 @@ the same shape (what bench.py and tools/latency_probe.py time), where operate() 
 the cleartext ground truth the way the harness does.
 
 Usage (GPU box):  python tools/bench_bridge.py [--sizes default|bench|both] [--only SUBSTR] [--reps 20] [--out FILE]
-                  HE355_POOL=0 python tools/bench_bridge.py ...      # the pre-pool behaviour (hipMalloc / drain + hipFree per call)
 One JSON object per line."""
 import argparse
 import ctypes as C
@@ -293,14 +292,13 @@ def main():
         raise SystemExit("bench_bridge.py needs an MI355X (no CPU fallback)")
     os.environ.setdefault("HE355_SEED", "1234")
     backend = Backend(be.LIB_PATH)
-    pool = "off (HE355_POOL=0)" if os.environ.get("HE355_POOL", "1")[:1] == "0" else "on"
     fout = open(a.out, "a") if a.out else None
     for i, case in enumerate(cases(backend, a.sizes)):
         if a.only and a.only.lower() not in (case.name() + " " + case.label).lower():
             continue
         reps = a.reps if (case.category == LATENCY or a.exact_reps) else max(3, a.reps // 4)
         r = run_case(backend, case, reps)
-        rec = dict(descriptor=case.name(), sizes=case.label, params=dict(case.params), sample_counts=list(case.counts), pool=pool, **r)
+        rec = dict(descriptor=case.name(), sizes=case.label, params=dict(case.params), sample_counts=list(case.counts), **r)
         if not a.no_direct:
             d = direct(case, reps)
             rec.update(d if d else dict(direct_ms=None))
