@@ -171,6 +171,26 @@ int he355_add_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t 
  * the last residues of every polynomial are dropped; in [n_polys][L][N] -> out [n_polys][L_to][N] (n_polys = n * size for
  * ciphertexts, n for plaintexts) */
 int he355_mod_switch_drop(he355_ctx *ctx, int L, int L_to, uint64_t n_polys, const uint64_t *d_in, uint64_t *d_out);
+/* ---- BFV level operations (BFV contexts only, else HE355_E_INVALID_ARGS; every L in 1..L_top).  Ciphertexts [n][size][L][N] in
+ * coefficient form, size 1..3; plaintexts [.][N] coefficients mod t: what he355_bfv_encode writes and he355_encrypt reads.  Operands by
+ * the Indexer rule of he355_multiply_plain: ciphertext a_base + r / b1, plaintext b_base + r % b1, or pairwise.
+ * [UPSTREAM-UNVERIFIED] (SEAL is not part of this tree): the published SEAL v3.7.2 algorithms, SURVEY.md Appendix A.
+ *   he355_bfv_mod_switch     Evaluator::mod_switch_to_next_inplace / mod_switch_to_inplace for BFV: L - L_to successive
+ *                            RNSTool::divide_and_round_q_last_inplace steps, each dropping the current last prime with rounding, in ONE launch
+ *                            (a polynomial is read once at L and written once at L_to residues).  -> [n][size][L_to][N]; 1 <= L_to <= L <= 16;
+ *                            L_to == L copies.  d_out may not overlap d_in.
+ *   he355_bfv_add_plain      Evaluator::add_plain_inplace / sub_plain_inplace (multiply_add/sub_plain_with_scaling_variant at the ciphertext's
+ *   he355_bfv_sub_plain      level): c0 +- Delta_L(m), Delta_L(m) = floor((q_L m + floor((t + 1) / 2)) / t) mod q_i, q_L the product of the first
+ *                            L primes; the other polynomials are copied.  d_out == d_ct is allowed exactly when every ciphertext serves one
+ *                            result (pairwise, or b1 == 1); any other overlap is refused.
+ *   he355_bfv_multiply_plain Evaluator::multiply_plain_inplace (multiply_plain_normal): every polynomial times lift(m) in Z_q_i[X]/(X^N + 1),
+ *                            lift(m) = m below floor((t + 1) / 2), else m - t; canonical residues, coefficient form.  Each distinct plaintext
+ *                            of the call is lifted and transformed once.  SEAL's optional "transparent ciphertext" exception is NOT reproduced:
+ *                            a zero plaintext gives a zero ciphertext.  d_out may not overlap an operand. */
+int he355_bfv_mod_switch(he355_ctx *ctx, int L, int L_to, int size, uint64_t n, const uint64_t *d_in, uint64_t *d_out);
+int he355_bfv_add_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
+int he355_bfv_sub_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
+int he355_bfv_multiply_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
 /* out = in[0] + ... + in[n-1] (one ciphertext): the add_inplace accumulation of collapseCKKS, src/engine/seal_context.cpp:401 */
 int he355_sum(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint64_t *d_out);
 /* CKKS: out(i,j) = sum_k multiply(a(i,k), b(k,j)), size-3 results [rows*cols][3][L][N]; ciphertext (i,k) of a is at index

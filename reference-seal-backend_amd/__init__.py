@@ -112,6 +112,10 @@ def lib():
             "he355_multiply_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_add_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_mod_switch_drop": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_mod_switch": (i32, [vp, i32, i32, i32, u64, vp, vp]),
+            "he355_bfv_add_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
+            "he355_bfv_sub_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
+            "he355_bfv_multiply_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -155,7 +159,7 @@ C_ABI_SYMBOLS = [
     "he355_fill_uniform", "he355_fill_uniform_at", "he355_set_dual_stream", "he355_set_relin_key", "he355_set_galois_key", "he355_set_relin_key_synthetic",
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
-    "he355_mod_switch_drop", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -355,6 +359,19 @@ class Context:
 
     def mod_switch_drop(self, L, L_to, n_polys, inp, out):
         _check(lib().he355_mod_switch_drop(self.h, L, L_to, n_polys, inp.ptr, out.ptr))
+
+    def bfv_mod_switch(self, L, L_to, size, n, inp, out):
+        """BFV mod_switch_to: [n][size][L][N] -> [n][size][L_to][N] (L - L_to divide-and-round steps, one launch)"""
+        _check(lib().he355_bfv_mod_switch(self.h, L, L_to, size, n, inp.ptr, out.ptr))
+
+    def bfv_add_plain(self, L, size, n, ct, pt, ix, out, sub=False):
+        """BFV add_plain / sub_plain: out = ct +- (Delta_L(pt), 0, ..); pt [.][N] coefficients mod t (bfv_encode's output)"""
+        f = lib().he355_bfv_sub_plain if sub else lib().he355_bfv_add_plain
+        _check(f(self.h, L, size, n, ct.ptr, pt.ptr, ix, out.ptr))
+
+    def bfv_multiply_plain(self, L, size, n, ct, pt, ix, out):
+        """BFV multiply_plain: every polynomial times the centred lift of pt, negacyclic; coefficient form in and out"""
+        _check(lib().he355_bfv_multiply_plain(self.h, L, size, n, ct.ptr, pt.ptr, ix, out.ptr))
 
     def sum(self, L, size, n, inp, out):
         _check(lib().he355_sum(self.h, L, size, n, inp.ptr, out.ptr))

@@ -1579,15 +1579,6 @@ public:
         // per ciphertext: u K, e 2K, z 2K (BFV), tail 2, cols 2L polys
         u64 *base = client_scratch(cmax * (K + 2 * K + 2 * K + 2 + 2 * L) * N);
         u64 *u = base, *e = u + cmax * K * N, *z = e + cmax * 2 * K * N, *tpr = z + cmax * 2 * K * N, *cols = tpr + cmax * 2 * N;
-        u64 qdivt[kMaxPrimes] = {0}, q_mod_t = 1; // L <= K <= kMaxPrimes (constructor)
-        if (!ckks) {
-            const u64 t = P.plain_modulus;
-            for (size_t i = 0; i < L; ++i) q_mod_t = (u64)(((u128)q_mod_t * (P.primes[i].q % t)) % t);
-            for (size_t i = 0; i < L; ++i) {
-                const u64 qi = P.primes[i].q, tinv = Params::invmod(t % qi, qi), neg = (q_mod_t % qi) ? qi - q_mod_t % qi : 0;
-                qdivt[i] = (u64)(((u128)neg * tinv) % qi); // floor(q/t) mod q_i = -(q mod t) * t^-1
-            }
-        }
         for (u64 off = 0; off < n; off += cmax) {
             const u64 c = std::min<u64>(cmax, n - off);
             u64 *o = out + off * 2 * L * N;
@@ -1622,9 +1613,103 @@ public:
                 launch_addsub(env_, (int)K, 2, c, z, e, pw, z, false);
                 if (K > 1) launch_divround_last_coeff(env_, c * 2, z, o);
                 else HIPCHECK(hipMemcpyAsync(o, z, c * 2 * N * 8, hipMemcpyDeviceToDevice, stream_));
-                if (plain) launch_bfv_add_scaled_plain(env_, (int)L, c, o, plain + off * N, P.plain_modulus, q_mod_t, qdivt);
+                if (plain) launch_bfv_addsub_plain(env_, (int)L, 2, c, o, plain + off * N, pw, o, bfv_delta((int)L), false); // c0 += Delta(plain), in place
             }
         }
+        HIPCHECK(hipGetLastError());
+    }
+    // ---- BFV level operations (he355_kernels_bfv_level.hip) ---------------------------------------------------------------
+    // the constants of Delta_L, cached per level as crt_tables(L) caches its own (host side: they travel as a kernel argument)
+    const BfvDeltaConst &bfv_delta(int L)
+    {
+        auto it = bfv_delta_.find(L);
+        if (it != bfv_delta_.end()) return it->second;
+        return bfv_delta_[L] = bfv_delta_const(env_.prime_q, L, P.plain_modulus);
+    }
+    // q_j^-1 mod q_i, floor(q_j / 2) mod q_i for i < j < Ltop: one device table for every (L, L_to), built on first use
+    const BfvDropConst *bfv_drop_table_dev()
+    {
+        if (d_bfv_drop_) return d_bfv_drop_;
+        const std::vector<BfvDropConst> tab = bfv_drop_table(env_.prime_q, (int)P.Ltop, P.u64_fold);
+        dmalloc(d_bfv_drop_, tab.size() * sizeof(BfvDropConst));
+        owned_.push_back(d_bfv_drop_);
+        HIPCHECK(hipMemcpy(d_bfv_drop_, tab.data(), tab.size() * sizeof(BfvDropConst), hipMemcpyHostToDevice));
+        return d_bfv_drop_;
+    }
+    void require_bfv(const char *what) const
+    {
+        if (P.scheme != kSchemeBFV) throw std::invalid_argument(std::string(what) + " needs a BFV context");
+    }
+    // the ciphertexts / plaintexts a batch of n results reads: [lo, hi] of the indexer's operand 0 / operand 1
+    static void indexer_span(const Indexer &ix, u64 n, u64 &a_lo, u64 &a_n, u64 &b_lo, u64 &b_n)
+    {
+        a_lo = idx_a(ix, 0); a_n = idx_a(ix, n - 1) - a_lo + 1;
+        b_lo = ix.b_base; b_n = ix.pairwise ? n : std::min<u64>(n, ix.b1);
+    }
+    // Evaluator::mod_switch_to (BFV): [n][size][L][N] -> [n][size][L_to][N], L - L_to divide-and-round steps in one launch
+    void bfv_mod_switch(int L, int L_to, int size, u64 n, const u64 *in, u64 *out)
+    {
+        use();
+        check_level(L);
+        require_bfv("he355_bfv_mod_switch");
+        if (L_to < 1 || L_to > L) throw std::invalid_argument("target level out of range");
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        if (L > kBfvLevelMaxL) throw std::invalid_argument("BFV modulus switching supports up to 16 data primes");
+        const size_t N = P.N, n_polys = (size_t)n * size;
+        if (ranges_overlap(in, n_polys * L * N, out, n_polys * L_to * N)) throw std::invalid_argument("he355_bfv_mod_switch: `out` overlaps `in`");
+        if (!n) return;
+        if (L_to == L) {
+            HIPCHECK(hipMemcpyAsync(out, in, n_polys * L * N * 8, hipMemcpyDeviceToDevice, stream_));
+            return;
+        }
+        launch_bfv_mod_switch(env_, bfv_drop_table_dev(), (int)P.Ltop, L, L_to, n_polys, in, out);
+        HIPCHECK(hipGetLastError());
+    }
+    // Evaluator::add_plain / sub_plain (BFV): out = ct +- (Delta_L(plain), 0, ..); plain [.][N] mod t
+    void bfv_addsub_plain(int L, int size, u64 n, const u64 *ct, const u64 *plain, Indexer ix, u64 *out, bool sub)
+    {
+        use();
+        check_level(L);
+        require_bfv(sub ? "he355_bfv_sub_plain" : "he355_bfv_add_plain");
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        if (!n) return;
+        const size_t N = P.N, ctn = (size_t)size * L * N;
+        u64 a_lo, a_n, b_lo, b_n;
+        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
+        // in place exactly where every ciphertext serves one result (pairwise, or one plaintext per ciphertext): result r then reads what it writes
+        const bool in_place = out == ct + a_lo * ctn && (ix.pairwise || ix.b1 == 1);
+        if (!in_place && ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn)) throw std::invalid_argument("he355_bfv_add_plain / sub_plain: `out` overlaps the ciphertexts (in place only when each serves one result)");
+        if (ranges_overlap(out, n * ctn, plain + b_lo * N, b_n * N)) throw std::invalid_argument("he355_bfv_add_plain / sub_plain: `out` overlaps the plaintexts");
+        launch_bfv_addsub_plain(env_, L, size, n, ct, plain, ix, out, bfv_delta(L), sub);
+        HIPCHECK(hipGetLastError());
+    }
+    // Evaluator::multiply_plain (BFV, multiply_plain_normal): every polynomial times the centred lift of the plaintext, negacyclic.
+    // Each distinct plaintext of the call is lifted and transformed once under the L primes (on stream_, ahead of the chunk loop: the
+    // fork event chunk 0 records orders the second stream behind it, and behind whatever produced the operands); a chunk is three
+    // launches -- forward column pass ct -> out, the fused row kernel in place on out, inverse column pass.
+    void bfv_multiply_plain(int L, int size, u64 n, const u64 *ct, const u64 *plain, Indexer ix, u64 *out)
+    {
+        use();
+        check_level(L);
+        require_bfv("he355_bfv_multiply_plain");
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        if (!n) return;
+        const size_t N = P.N, LN = (size_t)L * N, ctn = (size_t)size * LN;
+        u64 a_lo, a_n, b_lo, b_n;
+        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
+        if (ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn) || ranges_overlap(out, n * ctn, plain + b_lo * N, b_n * N))
+            throw std::invalid_argument("he355_bfv_multiply_plain: `out` overlaps an operand");
+        if (!reserve_bfv_scratch(b_n * LN * 8)) throw OutOfDeviceMemory("HIP error: out of device memory: the prepared plaintexts of he355_bfv_multiply_plain do not fit");
+        u64 *prep = bfv_scratch_;
+        launch_bfv_lift_plain(env_, L, b_n, plain + b_lo * N, prep, P.plain_modulus);
+        launch_ntt_forward(env_, poly_view(prep, L, N, L), (u32)b_n);
+        for_each_chunk(n, L, chunk_ops(n, L, true), true, [&](u64 off, u64 nc, int which, const Scratch &, hipEvent_t fork) {
+            const KernelEnv env = batch_env(which);
+            launch_bfv_mp_cols_fwd(env, L, size, nc, off, ct, ix, out);
+            launch_bfv_mp_rows(env, L, size, nc, off, ct, prep, ix, out);
+            launch_cols_inv(env, poly_view(out + off * ctn, size * L, N, L), (u32)nc);
+            if (fork) HIPCHECK(hipEventRecord(fork, env.stream));
+        });
         HIPCHECK(hipGetLastError());
     }
     const CrtTablesDev &crt_tables(int L)
@@ -1898,6 +1983,8 @@ private:
     u64 *client_scratch_ = nullptr;
     size_t client_scratch_bytes_ = 0;
     std::map<int, CrtTablesDev> crt_;
+    std::map<int, BfvDeltaConst> bfv_delta_; // Delta_L constants per level (bfv_level_core.h)
+    BfvDropConst *d_bfv_drop_ = nullptr;     // [Ltop][Ltop] drop-chain constants (owned_)
     std::map<uint32_t, u64 *> d_galois_;
     std::map<uint32_t, uint32_t *> d_perm_;
     u64 *scratch_ = nullptr, *scratch2_ = nullptr;
@@ -2208,6 +2295,28 @@ int he355_multiply_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64
 int he355_add_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
 {
     return guarded([&] { dev(c).plain_op(L, size, n, ct, pt, to_ix(ix), out, 1); });
+}
+// BFV level operations: the scheme is the context's (host side), so a CKKS context is refused before any device is asked for
+static void need_bfv(const he355_ctx *c, const char *what)
+{
+    if (!c) throw std::invalid_argument("null context");
+    if (c->params->scheme != kSchemeBFV) throw std::invalid_argument(std::string(what) + " needs a BFV context");
+}
+int he355_bfv_mod_switch(he355_ctx *c, int L, int L_to, int size, uint64_t n, const uint64_t *in, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_mod_switch"); dev(c).bfv_mod_switch(L, L_to, size, n, in, out); });
+}
+int he355_bfv_add_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_add_plain"); dev(c).bfv_addsub_plain(L, size, n, ct, pt, to_ix(ix), out, false); });
+}
+int he355_bfv_sub_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_sub_plain"); dev(c).bfv_addsub_plain(L, size, n, ct, pt, to_ix(ix), out, true); });
+}
+int he355_bfv_multiply_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain"); dev(c).bfv_multiply_plain(L, size, n, ct, pt, to_ix(ix), out); });
 }
 int he355_mod_switch_drop(he355_ctx *c, int L, int L_to, uint64_t n_polys, const uint64_t *in, uint64_t *out)
 {

@@ -8,6 +8,7 @@
 
 #include "device_types.h"
 #include "behz_core.h"
+#include "bfv_level_core.h"
 
 namespace he355 {
 
@@ -219,7 +220,11 @@ HE355_FWD(launch_rows_inv_select)
 HE355_FWD(launch_enc_sample)
 HE355_FWD(launch_enc_mul_pk)
 HE355_FWD(launch_divround_last_coeff)
-HE355_FWD(launch_bfv_add_scaled_plain)
+HE355_FWD(launch_bfv_mod_switch)
+HE355_FWD(launch_bfv_addsub_plain)
+HE355_FWD(launch_bfv_lift_plain)
+HE355_FWD(launch_bfv_mp_cols_fwd)
+HE355_FWD(launch_bfv_mp_rows)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

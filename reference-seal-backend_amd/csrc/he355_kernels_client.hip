@@ -89,27 +89,6 @@ __global__ void __launch_bounds__(kBlock) k_divround_last_coeff(const u64 *z, u6
         out[((poly * L + i) << logN) + n] = mulmod(submod(z[((poly * K + i) << logN) + n], delta, Pi.q), f.inv, make_modu(Pi)) /* any prime: Barrett */;
     }
 }
-// BFV: c0 += round(q*m/t) (util/scalingvariant.cpp multiply_add_plain_with_scaling_variant); plain [n][N] mod t.
-struct ScaleVariantConst {
-    u64 t, q_mod_t, thr;
-    u64 qdivt[kMaxPrimes]; // floor(q/t) mod q_i
-};
-__global__ void __launch_bounds__(kBlock) k_bfv_add_scaled_plain(u64 *ct, const u64 *plain, const PrimeDev *primes, ScaleVariantConst sv, int L, int logN,
-                                                                 u64 n_cts)
-{
-    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
-    const u64 r = gid >> logN, n = gid & (((u64)1 << logN) - 1);
-    if (r >= n_cts) return;
-    const u64 m = plain[(r << logN) + n];
-    const u64 fix = (u64)(((u128)m * sv.q_mod_t + sv.thr) / sv.t);
-    for (int i = 0; i < L; ++i) {
-        const PrimeDev &Pi = primes[i];
-        const ModU64 mod = make_modu(Pi);
-        const u64 v = addmod(barrett128((u128)m * sv.qdivt[i], mod), barrett64(fix, mod), Pi.q);
-        u64 *c = ct + ((r * 2 * L + i) << logN) + n;
-        *c = addmod(*c, v, Pi.q);
-    }
-}
 // Decryptor dot_product_ct_sk_array: out[r][i] = c0 + c1 s + c2 s^2 ... (Horner in s), NTT form; ct [n][size][L][N], sk [K][N].
 __global__ void __launch_bounds__(kBlock) k_dot_sk(const u64 *ct, const u64 *sk, u64 *out, const PrimeDev *primes, int L, int size, int logN, u64 n_cts)
 {
@@ -361,16 +340,6 @@ void launch_divround_last_coeff(const KernelEnv &env, u64 n_polys, const u64 *z,
     const int logN = env.logn1 + kRowLog;
     hipLaunchKernelGGL(k_divround_last_coeff, dim3(grid_for(n_polys << logN, kBlock)), dim3(kBlock), 0, env.stream, z, out, env.primes, env.floor_consts, env.K,
                        logN, n_polys);
-}
-void launch_bfv_add_scaled_plain(const KernelEnv &env, int L, u64 n_cts, u64 *ct, const u64 *plain, u64 t, u64 q_mod_t, const u64 *qdivt)
-{
-    if (!n_cts) return;
-    const int logN = env.logn1 + kRowLog;
-    ScaleVariantConst sv;
-    sv.t = t; sv.q_mod_t = q_mod_t; sv.thr = (t + 1) >> 1;
-    if (L > kMaxPrimes) throw std::invalid_argument("too many data primes");
-    for (int i = 0; i < kMaxPrimes; ++i) sv.qdivt[i] = i < L ? qdivt[i] : 0;
-    hipLaunchKernelGGL(k_bfv_add_scaled_plain, dim3(grid_for(n_cts << logN, kBlock)), dim3(kBlock), 0, env.stream, ct, plain, env.primes, sv, L, logN, n_cts);
 }
 void launch_dot_sk(const KernelEnv &env, int L, int size, u64 n_cts, const u64 *ct, const u64 *sk, u64 *out)
 {

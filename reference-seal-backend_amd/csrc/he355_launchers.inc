@@ -87,7 +87,6 @@ void launch_enc_sample(const KernelEnv &env, u64 n_cts, u64 seed, u64 first_inde
 void launch_enc_mul_pk(const KernelEnv &env, u64 n_cts, const u64 *u, const u64 *pk, u64 *z, bool add_in);
 // coefficient-form divide-and-round by the special prime: z [n_polys][K][N] -> out [n_polys][K-1][N]
 void launch_divround_last_coeff(const KernelEnv &env, u64 n_polys, const u64 *z, u64 *out);
-void launch_bfv_add_scaled_plain(const KernelEnv &env, int L, u64 n_cts, u64 *ct, const u64 *plain, u64 t, u64 q_mod_t, const u64 *qdivt);
 void launch_dot_sk(const KernelEnv &env, int L, int size, u64 n_cts, const u64 *ct, const u64 *sk, u64 *out);
 void launch_bfv_scale_round(const KernelEnv &env, u64 n_cts, const u64 *phase, u64 *plain, const CrtTablesDev &c);
 // values [n][count] -> plain [n][Ltop][N] coefficient form (zbuf: [n][N] complex scratch; *err |= 1 if a coefficient overflows)
@@ -108,3 +107,17 @@ u64 ks_lds_part_words(const KernelEnv &env, int L);
 void launch_ks_lds(const KernelEnv &env, int L, u64 n_ops, const LdsKsOperands &src, const u64 *key, u64 *part, u64 *out, u64 out_op_stride);
 // CKKS rescale in the same shape: src [size][L][N] per op -> out [n_ops][size][L - 1][N], one launch
 void launch_rescale_lds(const KernelEnv &env, int L, int size, u64 n_ops, const u64 *src, u64 src_op_stride, u64 *out);
+// ---- BFV level operations on coefficient-form ciphertexts (he355_kernels_bfv_level.hip; arithmetic: bfv_level_core.h) -------------------
+// Evaluator::mod_switch_to for BFV: in [n_polys][L][N] -> out [n_polys][L_to][N], the L - L_to divide-and-round steps in one launch.
+// tab: device copy of bfv_drop_table, entry [j * stride + i].  L <= kBfvLevelMaxL.
+void launch_bfv_mod_switch(const KernelEnv &env, const BfvDropConst *tab, int stride, int L, int L_to, u64 n_polys, const u64 *in, u64 *out);
+// out[r] = ct[ia(r)] +- (Delta_L(plain[ib(r)]), 0, ..); plain [.][N] mod t.  out may be ct where every ciphertext serves one result
+// (he355_encrypt: the plaintext term at the top level, pairwise, in place)
+void launch_bfv_addsub_plain(const KernelEnv &env, int L, int size, u64 n_results, const u64 *ct, const u64 *plain, Indexer ix, u64 *out, const BfvDeltaConst &dc,
+                             bool sub);
+// multiply_plain: plain [n_plain][N] mod t -> dst [n_plain][L][N] centred lift (coefficient form; launch_ntt_forward then prepares it);
+// forward column pass ct[ia(r)] -> out[r] (nothing when N = 1024); forward row pass x prepared plaintext row, inverse row pass, in place
+// on out (N = 1024: ct -> out) -- launch_cols_inv finishes.  r = op_offset .. op_offset + n_ops - 1; ct, prep, out: the batch's pointers
+void launch_bfv_lift_plain(const KernelEnv &env, int L, u64 n_plain, const u64 *plain, u64 *dst, u64 t);
+void launch_bfv_mp_cols_fwd(const KernelEnv &env, int L, int size, u64 n_ops, u64 op_offset, const u64 *ct, Indexer ix, u64 *out);
+void launch_bfv_mp_rows(const KernelEnv &env, int L, int size, u64 n_ops, u64 op_offset, const u64 *ct, const u64 *prep, Indexer ix, u64 *out);
