@@ -191,6 +191,17 @@ int he355_bfv_mod_switch(he355_ctx *ctx, int L, int L_to, int size, uint64_t n, 
 int he355_bfv_add_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_sub_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_multiply_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
+/* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
+ * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
+ * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).
+ * d_budget [n] int32 (device): max(0, bits(q_L) - noise_bits - 1)
+ * d_noise_bits [n] int32 (device) or NULL: significant bits of the norm below, BEFORE the clamp.
+ * Per ciphertext, q_L the product of the first L primes: phase = c0 + c1 s (+ c2 s^2) per prime (coefficient form), every residue times
+ * t mod q_i, CRT-composed to x in [0, q_L), |x| = q_L - x where x >= (q_L + 1) / 2 else x, norm = the largest |x| over the N coefficients,
+ * noise_bits = bit length of norm (0 for 0).  Exact integers: no tolerance.  Queued on the context's stream like he355_decrypt (no
+ * he355_sync needed after an asynchronous producer; outputs valid after he355_sync / he355_download).  n == 0 touches nothing.
+ * [UPSTREAM-UNVERIFIED] as the level operations above: SEAL v3.7.2 decryptor.cpp, invariant_noise_budget. */
+int he355_bfv_noise_budget(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits);
 /* out = in[0] + ... + in[n-1] (one ciphertext): the add_inplace accumulation of collapseCKKS, src/engine/seal_context.cpp:401 */
 int he355_sum(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint64_t *d_out);
 /* CKKS: out(i,j) = sum_k multiply(a(i,k), b(k,j)), size-3 results [rows*cols][3][L][N]; ciphertext (i,k) of a is at index

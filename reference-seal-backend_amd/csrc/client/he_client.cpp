@@ -3,7 +3,9 @@
 #include "ckks_codec.h"
 #include "multiword.h"
 #include "sampler.h"
+#include "../bfv_noise_core.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -476,6 +478,36 @@ std::vector<u64> Client::decrypt(const u64 *ct, size_t size, size_t L) const
         plain[n] = m % t;
     }
     return plain;
+}
+
+int Client::invariant_noise_budget(const u64 *ct, size_t size, size_t L, int *noise_bits) const
+{
+    if (P.scheme != kSchemeBFV) throw std::invalid_argument("the invariant noise budget needs a BFV context");
+    if (size < 2 || size > 3) throw std::invalid_argument("ciphertext size must be 2 or 3");
+    if (L < 1 || L > P.Ltop || L > (size_t)kBfvNoiseMaxL) throw std::invalid_argument("level out of range (1 to 16 data primes)");
+    const size_t N = P.N;
+    // the key-dependent part of the phase, (c_{size-1} s + .. + c_1) s, back in coefficient form; c0 is added per coefficient below
+    std::vector<u64> part(L * N), tmp(N), q(L);
+    std::vector<PrimeDev> pd(L);
+    for (size_t i = 0; i < L; ++i) {
+        const PrimeTables &pt = P.primes[i];
+        u64 *o = part.data() + i * N;
+        for (size_t k = size; k-- > 1;) {
+            std::memcpy(tmp.data(), ct + (k * L + i) * N, N * 8);
+            host_ntt_forward(pt, N, tmp.data());
+            for (size_t n = 0; n < N; ++n) o[n] = mulm(k == size - 1 ? tmp[n] : addmod(o[n], tmp[n], pt.q), sk_[i * N + n], pt.mod);
+        }
+        host_ntt_inverse(pt, N, o);
+        std::memset(&pd[i], 0, sizeof(PrimeDev));
+        pd[i].q = pt.q; pd[i].cr0 = pt.mod.cr0; pd[i].cr1 = pt.mod.cr1;
+        q[i] = pt.q;
+    }
+    const BfvNoiseHostTables T = bfv_noise_host_tables(q.data(), (int)L, P.plain_modulus);
+    const BfvNoiseView v = T.view();
+    int bits = 0;
+    for (size_t n = 0; n < N; ++n) bits = std::max(bits, bfv_noise_bits_host((int)L, part.data() + n, ct + n, N, pd.data(), T.c, v));
+    if (noise_bits) *noise_bits = bits;
+    return bfv_noise_budget_of(T.c.q_bits, bits);
 }
 
 } // namespace client

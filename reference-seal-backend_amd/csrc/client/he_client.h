@@ -64,6 +64,10 @@ public:
     // ---- decryption of a size-`size` ciphertext at level L (size 3 allowed: the reference decrypts
     //      un-relinearized products, ckks eltwise .cpp:342-344). CKKS: [L][N] NTT plaintext; BFV: [N] mod t ----
     std::vector<u64> decrypt(const u64 *ct, size_t size, size_t L) const;
+    // ---- Decryptor::invariant_noise_budget of a BFV ciphertext at level L (size 2 or 3, L <= 16): bits of noise budget left,
+    //      max(0, bits(q_L) - noise_bits - 1); noise_bits (optional): bit length of the invariant noise norm before the clamp.
+    //      The per-coefficient arithmetic is bfv_noise_core.h, the text the device kernel compiles ----
+    int invariant_noise_budget(const u64 *ct, size_t size, size_t L, int *noise_bits = nullptr) const;
 
 private:
     void sample_ternary(std::vector<u64> &out, size_t nmod);

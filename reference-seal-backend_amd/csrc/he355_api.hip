@@ -1774,6 +1774,53 @@ public:
         }
         HIPCHECK(hipGetLastError());
     }
+    // Decryptor::invariant_noise_budget of n size-`size` BFV ciphertexts at level L: budget [n] int32, noise_bits [n] int32 or null.
+    // Per chunk: polynomials 1 .. size-1 into scratch, forward transform, Horner with the NTT-form secret key (without the constant term),
+    // inverse transform, then k_bfv_noise_bits adds c0 in coefficient form -- one forward transform and one slab copy less per ciphertext
+    // than decrypt() spends on the same phase -- and gathers the per-ciphertext maximum in `budget`, which k_bfv_noise_finish turns into
+    // the budget in place.  Everything on stream_, like decrypt().
+    const BfvNoiseConst &bfv_noise(int L)
+    {
+        auto it = bfv_noise_.find(L);
+        if (it != bfv_noise_.end()) return it->second;
+        return bfv_noise_[L] = bfv_noise_const(env_.prime_q, L, P.plain_modulus);
+    }
+    // Ciphertexts per chunk: 2^21 coefficients' worth (64 at N = 32768, as decrypt(); 256 at N = 8192), at most 1024 -- 64 ciphertexts of a
+    // small ring are one wave per SIMD for k_bfv_noise_bits, which then waits on its own dependent instructions (profiles/bfv_noise.txt) --
+    // and never more than the batch chunk (he355_set_chunk), so a test can cut a small batch.
+    u64 noise_chunk(u64 n) const
+    {
+        const u64 by_ring = std::min<u64>(1024, std::max<u64>(64, ((u64)1 << 21) / P.N));
+        return std::max<u64>(1, std::min<u64>(n, std::min<u64>(by_ring, chunk_)));
+    }
+    void bfv_noise_budget(int L, int size, u64 n, const u64 *ct, int32_t *budget, int32_t *noise_bits)
+    {
+        use();
+        require_bfv("he355_bfv_noise_budget");
+        check_level(L);
+        if (L > kBfvNoiseMaxL) throw std::invalid_argument("the BFV noise budget supports up to 16 data primes");
+        if (size < 2 || size > 3) throw std::invalid_argument("ciphertext size must be 2 or 3");
+        if (!d_sk_) throw std::invalid_argument("secret key not set");
+        if (!n) return;
+        if (!ct || !budget) throw std::invalid_argument("he355_bfv_noise_budget: null ciphertexts or null budget output");
+        const size_t N = P.N, LN = (size_t)L * N;
+        const CrtTablesDev &crt = crt_tables(L);
+        const BfvNoiseConst &nc = bfv_noise(L);
+        const u64 cmax = noise_chunk(n);
+        u64 *tmp = client_scratch(cmax * (size_t)size * LN), *part = tmp + cmax * (size_t)(size - 1) * LN;
+        HIPCHECK(hipMemsetAsync(budget, 0, n * sizeof(int32_t), stream_));
+        for (u64 off = 0; off < n; off += cmax) {
+            const u64 c = std::min<u64>(cmax, n - off);
+            const u64 *src = ct + off * size * LN;
+            launch_bfv_noise_take(env_, L, size, c, src, tmp);
+            launch_ntt_forward(env_, poly_view(tmp, (size - 1) * L, N, L), (u32)c);
+            launch_bfv_noise_dot_sk(env_, L, size, c, tmp, d_sk_, part);
+            launch_ntt_inverse(env_, poly_view(part, L, N, L), (u32)c);
+            launch_bfv_noise_bits(env_, size, c, part, src, budget + off, crt, nc);
+        }
+        launch_bfv_noise_finish(env_, n, budget, noise_bits, nc.q_bits);
+        HIPCHECK(hipGetLastError());
+    }
     // ---- encoders (CKKSEncoder / BatchEncoder) -------------------------------------------------------------------
     const EncTablesDev &enc_tables()
     {
@@ -1984,6 +2031,7 @@ private:
     size_t client_scratch_bytes_ = 0;
     std::map<int, CrtTablesDev> crt_;
     std::map<int, BfvDeltaConst> bfv_delta_; // Delta_L constants per level (bfv_level_core.h)
+    std::map<int, BfvNoiseConst> bfv_noise_; // t-folded CRT constants and bits(q_L) per level (bfv_noise_core.h)
     BfvDropConst *d_bfv_drop_ = nullptr;     // [Ltop][Ltop] drop-chain constants (owned_)
     std::map<uint32_t, u64 *> d_galois_;
     std::map<uint32_t, uint32_t *> d_perm_;
@@ -2317,6 +2365,10 @@ int he355_bfv_sub_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_
 int he355_bfv_multiply_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
 {
     return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain"); dev(c).bfv_multiply_plain(L, size, n, ct, pt, to_ix(ix), out); });
+}
+int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_noise_budget"); dev(c).bfv_noise_budget(L, size, n, d_ct, d_budget, d_noise_bits); });
 }
 int he355_mod_switch_drop(he355_ctx *c, int L, int L_to, uint64_t n_polys, const uint64_t *in, uint64_t *out)
 {

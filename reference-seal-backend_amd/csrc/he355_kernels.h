@@ -9,6 +9,7 @@
 #include "device_types.h"
 #include "behz_core.h"
 #include "bfv_level_core.h"
+#include "bfv_noise_core.h"
 
 namespace he355 {
 
@@ -225,6 +226,10 @@ HE355_FWD(launch_bfv_addsub_plain)
 HE355_FWD(launch_bfv_lift_plain)
 HE355_FWD(launch_bfv_mp_cols_fwd)
 HE355_FWD(launch_bfv_mp_rows)
+HE355_FWD(launch_bfv_noise_take)
+HE355_FWD(launch_bfv_noise_dot_sk)
+HE355_FWD(launch_bfv_noise_bits)
+HE355_FWD(launch_bfv_noise_finish)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -121,3 +121,12 @@ void launch_bfv_addsub_plain(const KernelEnv &env, int L, int size, u64 n_result
 void launch_bfv_lift_plain(const KernelEnv &env, int L, u64 n_plain, const u64 *plain, u64 *dst, u64 t);
 void launch_bfv_mp_cols_fwd(const KernelEnv &env, int L, int size, u64 n_ops, u64 op_offset, const u64 *ct, Indexer ix, u64 *out);
 void launch_bfv_mp_rows(const KernelEnv &env, int L, int size, u64 n_ops, u64 op_offset, const u64 *ct, const u64 *prep, Indexer ix, u64 *out);
+// ---- BFV invariant noise budget (he355_kernels_bfv_noise.hip; arithmetic: bfv_noise_core.h) ----------------------------------------------
+// ct [n_cts][size][L][N] -> tmp [n_cts][size - 1][L][N]: polynomials 1 .. size-1, the ones the phase needs transformed
+void launch_bfv_noise_take(const KernelEnv &env, int L, int size, u64 n_cts, const u64 *ct, u64 *tmp);
+// tmp in NTT form -> out [n_cts][L][N] = (c_{size-1} s + .. + c_1) s, NTT form
+void launch_bfv_noise_dot_sk(const KernelEnv &env, int L, int size, u64 n_cts, const u64 *tmp, const u64 *sk, u64 *out);
+// bits[r] = max(bits[r], bit length of the largest centred coefficient of t (part[r] + ct[r][0]) mod q_L); part [n_cts][L][N] coefficient form
+void launch_bfv_noise_bits(const KernelEnv &env, int size, u64 n_cts, const u64 *part, const u64 *ct, int *bits, const CrtTablesDev &crt, const BfvNoiseConst &c);
+// in place: budget[r] = max(0, q_bits - budget[r] - 1); noise_bits[r] (if given) = the value that came in
+void launch_bfv_noise_finish(const KernelEnv &env, u64 n_cts, int *budget, int *noise_bits, int q_bits);

@@ -1,0 +1,103 @@
+// sim_bfv_noise.cpp -- TEST-ONLY.  Runs the product's per-coefficient noise-budget arithmetic (csrc/bfv_noise_core.h: the very function
+// the HIP kernel k_bfv_noise_bits<W> compiles) on the CPU, on the tables the product builds (bfv_noise_const, bfv_noise_host_tables), and
+// the host client's whole chain (Client::invariant_noise_budget), so that tests/test_bfv_noise_core_cpu.py can hold both to Python
+// integers without a GPU.  Compiled once per form of the u64 engine into tests/csim_bfv_noise/_build; the product never contains it.
+#include <cstring>
+#include <map>
+#include <stdexcept>
+#include <vector>
+
+#include "../../reference-seal-backend_amd/csrc/bfv_noise_core.h"
+#include "../../reference-seal-backend_amd/csrc/client/he_client.h"
+#include "../../reference-seal-backend_amd/csrc/he_params.h"
+
+using namespace he355;
+
+namespace {
+struct NoiseSim {
+    Params *p = nullptr;
+    client::Client *cl = nullptr;
+    std::vector<PrimeDev> pd; // the data primes: what bfv_noise_bits reads of them
+    std::vector<u64> q;
+    std::map<int, BfvNoiseHostTables> tab;
+    const BfvNoiseHostTables &tables(int L)
+    {
+        auto it = tab.find(L);
+        if (it == tab.end()) it = tab.emplace(L, bfv_noise_host_tables(q.data(), L, p->plain_modulus)).first;
+        return it->second;
+    }
+};
+} // namespace
+
+extern "C" {
+
+// the form this library was compiled for: 0 Shoup quotients, 1 fold reduction
+int sim_bfvn_form(void) { return HE355_U64_FOLD; }
+
+// null when the parameters are refused, or when this library's form is not the one a context of these primes runs (as sim_bfvl_create)
+void *sim_bfvn_create(size_t N, const int *bits, size_t n_bits, int plain_bits, uint64_t seed)
+{
+    try {
+        NoiseSim *s = new NoiseSim();
+        s->p = Params::create(kSchemeBFV, N, std::vector<int>(bits, bits + n_bits), plain_bits, false, HE355_U64_FOLD != 0);
+        if ((HE355_U64_FOLD != 0) != s->p->u64_fold) {
+            delete s->p;
+            delete s;
+            return nullptr;
+        }
+        for (size_t i = 0; i < s->p->Ltop; ++i) {
+            PrimeDev d;
+            std::memset(&d, 0, sizeof(d));
+            d.q = s->p->primes[i].q; d.cr0 = s->p->primes[i].mod.cr0; d.cr1 = s->p->primes[i].mod.cr1;
+            s->pd.push_back(d);
+            s->q.push_back(d.q);
+        }
+        s->cl = new client::Client(*s->p, seed);
+        return s;
+    } catch (const std::exception &) {
+        return nullptr;
+    }
+}
+void sim_bfvn_destroy(void *h)
+{
+    NoiseSim *s = static_cast<NoiseSim *>(h);
+    if (s) { delete s->cl; delete s->p; delete s; }
+}
+size_t sim_bfvn_levels(void *h) { return static_cast<NoiseSim *>(h)->p->Ltop; }
+uint64_t sim_bfvn_q(void *h, size_t i) { return static_cast<NoiseSim *>(h)->q[i]; }
+uint64_t sim_bfvn_t(void *h) { return static_cast<NoiseSim *>(h)->p->plain_modulus; }
+// bit length of q_L as the product computes it (what the finishing kernel is handed)
+int sim_bfvn_qbits(void *h, int L)
+{
+    NoiseSim *s = static_cast<NoiseSim *>(h);
+    if (L < 1 || L > (int)s->p->Ltop || L > kBfvNoiseMaxL) return -1;
+    return s->tables(L).c.q_bits;
+}
+// n coefficients: a, b [n][L] canonical residues (b may be null) -> bits [n] = bfv_noise_bits<L + 2>(a + b), budget [n] from them
+int sim_bfvn_bits(void *h, int L, const uint64_t *a, const uint64_t *b, int *bits, int *budget, size_t n)
+{
+    NoiseSim *s = static_cast<NoiseSim *>(h);
+    if (L < 1 || L > (int)s->p->Ltop || L > kBfvNoiseMaxL) return 1;
+    const BfvNoiseHostTables &T = s->tables(L);
+    const BfvNoiseView v = T.view();
+    for (size_t c = 0; c < n; ++c) {
+        bits[c] = bfv_noise_bits_host(L, a + c * L, b ? b + c * L : nullptr, 1, s->pd.data(), T.c, v);
+        budget[c] = bfv_noise_budget_of(T.c.q_bits, bits[c]);
+    }
+    return 0;
+}
+// the host client of this context: its keys (SEAL layouts, for the oracle to evaluate with) and its noise budget
+void sim_bfvn_secret_key(void *h, uint64_t *out) { auto &v = static_cast<NoiseSim *>(h)->cl->secret_key(); std::memcpy(out, v.data(), v.size() * 8); }
+void sim_bfvn_public_key(void *h, uint64_t *out) { auto &v = static_cast<NoiseSim *>(h)->cl->public_key(); std::memcpy(out, v.data(), v.size() * 8); }
+void sim_bfvn_relin_key(void *h, uint64_t *out) { auto v = static_cast<NoiseSim *>(h)->cl->make_relin_key(); std::memcpy(out, v.data(), v.size() * 8); }
+void sim_bfvn_galois_key(void *h, uint32_t elt, uint64_t *out) { auto v = static_cast<NoiseSim *>(h)->cl->make_galois_key(elt); std::memcpy(out, v.data(), v.size() * 8); }
+// budget (>= 0), or -1 when the client refuses the arguments
+int sim_bfvn_client_budget(void *h, const uint64_t *ct, size_t size, size_t L, int *noise_bits)
+{
+    try {
+        return static_cast<NoiseSim *>(h)->cl->invariant_noise_budget(ct, size, L, noise_bits);
+    } catch (const std::exception &) {
+        return -1;
+    }
+}
+}
