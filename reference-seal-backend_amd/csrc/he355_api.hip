@@ -800,11 +800,23 @@ public:
                 // combined in coefficient form, delta2 + P^-1 * delta1, inside one k_floor_colsn launch that reads both sources (the
                 // special prime's sums and the divided-out prime's tail) -- 16 column passes per polynomial instead of 31, and the
                 // mod-down correction slab is neither written for those primes nor read back.
-                launch_floor_cols(env, SP, 1, nc * 2, B.tpr, B.e, /*tgt_first*/ L - 1, /*dst_ntgt*/ L);
+                // A ct x ct multiply with operand-formed sums (ops.ta: the key residues carry P^-1, c0 and c1 are inside the sums) needs
+                // no correction slab at all: the rescale wants the divided-out prime's mod-down result in coefficient form only, and
+                // iNTT(sums') - P^-1 * delta1 is that residue, so its tiles go from the sums straight through the inverse row pass (raw_tail)
+                // and the merged k_floor_colsn launch takes P^-1 * delta1 off once per column (sub2) -- 15 column passes, no
+                // k_rows_inv_select, and the prime-(L-1) block of B.e is neither written nor read.
+                const bool raw = ops.ta != nullptr;
                 f.tt_lo = L - 1; f.tt_hi = L;
-                launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
-                launch_rows_inv_select(env, L - 1, nc * 2, B.c01 + (size_t)(L - 1) * N, (u64)LN, S.rlr);
-                launch_floor_cols(env, L - 1, L - 1, nc * 2, S.rlr, S.f, 0, L - 1, /*src2*/ B.tpr, SP);
+                if (raw) {
+                    f.raw_tail = S.rlr;
+                    launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
+                    f.raw_tail = nullptr;
+                } else {
+                    launch_floor_cols(env, SP, 1, nc * 2, B.tpr, B.e, /*tgt_first*/ L - 1, /*dst_ntgt*/ L);
+                    launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
+                    launch_rows_inv_select(env, L - 1, nc * 2, B.c01 + (size_t)(L - 1) * N, (u64)LN, S.rlr);
+                }
+                launch_floor_cols(env, L - 1, L - 1, nc * 2, S.rlr, S.f, 0, L - 1, /*src2*/ B.tpr, SP, 1, /*sub2*/ raw);
                 f.tt_lo = 0; f.tt_hi = L - 1; f.cols2 = S.f; f.out = rescale_out;
                 launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f);
                 return;

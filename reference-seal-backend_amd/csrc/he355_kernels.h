@@ -92,6 +92,11 @@ struct K3Fuse {
     // delta2 + P^-1 * delta1; out [n_ops][2][L-1][N].  Null: mod-down only (correction from cols).
     const u64 *cols2;
     u64 *out;
+    // ct x ct multiply + rescale, the tiles of the divided-out prime L-1 (tt_lo = L-1, tt_hi = L; needs ta / tb): no correction rows and no
+    // floor step -- the operand-formed sums (c0, c1 and the key products, scaled by P^-1) go through the inverse row pass and leave as raw
+    // rows in raw_tail [n_ops*2][N], the source of launch_floor_cols(prime L-1 -> L-1 targets, src2 = the special prime's sums, sub2),
+    // which takes the mod-down correction off in coefficient form.  cols, c01 are not read.  Null: the floor step(s) above.
+    u64 *raw_tail = nullptr;
     // ct x ct multiply (he355_multiply_relin): the addend of the floor step -- c0 = a0 b0, c1 = a0 b1 + a1 b0 -- is computed here from the
     // operand rows instead of being written by k_k1 and read back (k_k1 is HBM-bound, this kernel is not).  Null: the addend is read
     // from c01.  ta / tb: the operand slabs [.][2][L][N], tix / t_op_offset: result r = t_op_offset + op multiplies a[ia(r)] by b[ib(r)].

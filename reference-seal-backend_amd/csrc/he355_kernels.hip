@@ -994,8 +994,9 @@ struct K3Args {
 // registers — the wave transforms the matching rows of the special-prime correction (forward row pass, same tile twiddles)
 // and writes (T - NTT(delta)) * P^-1 + c01 straight into c01.  Needs the special prime's sums first: the caller launches the
 // special-prime tiles, the inverse transform and k_floor_colsn before the data-prime tiles.
-// TENSOR (FUSE only): the launch belongs to a ct x ct multiply whose c0, c1 this kernel computes from the operand rows (K3Args::ta); an
-// instantiation of its own, so that the other users of the fused kernel keep their register allocation.
+// TENSOR: the launch belongs to a ct x ct multiply whose c0, c1 this kernel computes from the operand rows (K3Args::ta); an
+// instantiation of its own, so that the other users of the fused kernel keep their register allocation.  TENSOR without FUSE is the
+// rescale's divided-out prime (K3Fuse::raw_tail): the same sums and digit loop, then the inverse row pass instead of the floor step.
 // WAVES: 8 (throughput shape: one block per CU, two waves per SIMD, each wave on its own op; LDS: 8 x 8.5 KiB exchange + 8 x 8 KiB
 // DMA landing + the tile's twiddles) or 1 (latency shape: one wave per block, the digits of a tile dealt to n_split blocks).
 // GROUPED: every group of ops has its own key (he355_rotate_sum: all nodes of a trie level in one launch); ops of a group are consecutive,
@@ -1155,23 +1156,36 @@ struct FloorColsArgs {
     // neither written for these targets nor read back
     const u64 *src2;
     int src2_prime;
+    // MERGE, optional: `src` holds the sums of prime src_prime with the earlier correction still in them (k_k3's raw_tail rows: sums scaled
+    // by src2^-1, no floor step taken), so the earlier floor step's result under this prime is finished here, once per column and in
+    // coefficient form, c' = x - src2^-1 * delta1 mod q_src, before anything reads it
+    int sub2;
     u64 f64_mask; // bit i: key prime i belongs to the fp64 engine
     int tsplit;   // latency shape: the targets of a column are dealt to tsplit blocks (blockIdx.y)
 };
 
 // canonical coefficients + floor(s/2) of one column of a source residue after its inverse row pass
-template <int LOGN1>
-__device__ __forceinline__ void floor_source_column(const PrimeDev &Ps, const u64 *src, int col, u64 c[1 << LOGN1])
+// SUB (fp64-engine source, LOGN1 > 0): sub[a], an integer double below q_s in magnitude, is taken off each coefficient on the way -- in
+// the engine's lazy range, ahead of the one canonicalisation, which then takes floor(s/2) with it too
+template <int LOGN1, bool SUB = false>
+__device__ __forceinline__ void floor_source_column(const PrimeDev &Ps, const u64 *src, int col, u64 c[1 << LOGN1], const double *sub = nullptr)
 {
     constexpr int N1 = 1 << LOGN1;
+    static_assert(!SUB || LOGN1 > 0, "the correction rides the fp64 column pass");
     if (LOGN1 == 0) {
         c[0] = src[col];
-    } else if (Ps.f64) {
+    } else if (SUB || Ps.f64) {
         const ArF64 ar = make_ar(Ps, (ArF64 *)nullptr);
         double x[N1];
 #pragma unroll
         for (int a = 0; a < N1; ++a) x[a] = ar.from_raw(src[(a << kRowLog) + col]);
         col_inv<ArF64, LOGN1>(ar, x, ctw(Ps.inv), Ps.inv_w0_scaled);
+        if constexpr (SUB) { // x centred (the last stage's products), |sub| < q, floor(s/2) < q: far inside to_canon's 2^52
+            const double half = u52_to_f64(Ps.q >> 1);
+#pragma unroll
+            for (int a = 0; a < N1; ++a) c[a] = ar.to_canon(x[a] - sub[a] + half);
+            return;
+        }
 #pragma unroll
         for (int a = 0; a < N1; ++a) c[a] = ar.to_canon(x[a]);
     } else {
@@ -1307,12 +1321,41 @@ __global__ void __launch_bounds__(kBlock, 2) k_floor_colsn(FloorColsArgs A, cons
         ctab[i] = k;
     }
     u64 c[N1];
-    floor_source_column<LOGN1>(Ps, A.src + poly * N, col, c);
     if constexpr (MERGE) {
         u64 c2[N1];
         floor_source_column<LOGN1>(primes[A.src2_prime], A.src2 + poly * N, col, c2);
 #pragma unroll
         for (int a = 0; a < N1; ++a) park[a][threadIdx.x] = c2[a]; // each thread reads back only what it wrote itself
+        if (A.sub2) {
+            // source 1 still lacks the earlier correction under its own prime: c' = x - src2^-1 * delta1 mod q_src, once per column,
+            // delta1 = [source 2]_{q_src} - floor(src2 / 2)
+            const FloorConst fs = A.fc[A.src2_prime * A.K + A.src_prime];
+            bool done = false;
+            if constexpr (LOGN1 > 0) {
+                if (Ps.f64) { // in the engine's doubles, folded into the column's one canonicalisation
+                    const ArF64 ar = make_ar(Ps, (ArF64 *)nullptr);
+                    const double pow32 = Ps.pow32, half2 = (double)fs.half_mod;
+                    double d[N1];
+#pragma unroll
+                    for (int a = 0; a < N1; ++a) d[a] = ar.mulmod_c(lift_wide(ar, c2[a], pow32) - half2, fs.inv_d, fs.inv_i);
+                    floor_source_column<LOGN1, true>(Ps, A.src + poly * N, col, c, d);
+                    done = true;
+                }
+            }
+            if (!done) { // integers (any prime, either form of the u64 engine)
+                floor_source_column<LOGN1>(Ps, A.src + poly * N, col, c);
+                const ModU64 ms = make_modu(Ps);
+#pragma unroll
+                for (int a = 0; a < N1; ++a) {
+                    const u64 d1 = submod(qs2 > qs ? barrett64(c2[a], ms) : c2[a], fs.half_mod, qs);
+                    c[a] = submod(c[a], mulmod(d1, fs.inv, ms), qs);
+                }
+            }
+        } else {
+            floor_source_column<LOGN1>(Ps, A.src + poly * N, col, c);
+        }
+    } else {
+        floor_source_column<LOGN1>(Ps, A.src + poly * N, col, c);
     }
     __syncthreads(); // the constants table
     u64 tgt = ((A.tgt_first + A.n_tgt >= 64 ? ~(u64)0 : (((u64)1 << (A.tgt_first + A.n_tgt)) - 1))) & ~(((u64)1 << A.tgt_first) - 1);
@@ -2163,6 +2206,10 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
         if (A.c1_mode == 5 && !A.c1_src) throw std::runtime_error("gathered rotation with addend: the addend rows are needed");
         A.ta = fuse ? fuse->ta : nullptr; A.tb = fuse ? fuse->tb : nullptr; A.tix = fuse ? fuse->tix : Indexer{}; A.t_op_offset = fuse ? fuse->t_op_offset : 0;
         if (fuse && fuse->cols2 && fuse->tt_hi > L - 1) throw std::runtime_error("fused rescale: only primes below the one divided out");
+        if (fuse && fuse->raw_tail) { // the rescale's divided-out prime: operand-formed sums, inverse row pass, raw rows (no floor step)
+            if (!fuse->ta || fuse->tt_hi != fuse->tt_lo + 1 || groups) throw std::runtime_error("raw tail: one prime of a ct x ct multiply");
+            A.tpr = fuse->raw_tail;
+        }
         A.fc = env.floor_consts;
         A.n_split = n_split > 1 ? (pass == 0 ? n_split : n_split_u64) : 1; A.part = split_part;
         A.n_tt = 0;
@@ -2237,7 +2284,7 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
         ++n_pend;
     }
     const hipStream_t st3 = env.stream;
-    const bool tensor = fuse && fuse->ta;
+    const bool tensor = fuse && fuse->ta, raw_tail = fuse && fuse->raw_tail; // (raw_tail: one prime, so one engine and no dual launch)
     if (n_pend == 2 && pend[0].waves == 1) { // latency shape
         const unsigned ny = (unsigned)std::max(pend[0].A.n_split, pend[1].A.n_split);
         hipLaunchKernelGGL(k_k3_dual, dim3(pend[0].g + pend[1].g, ny), dim3(64), 0, st3, pend[0].A, pend[1].A, pend[1].g, env.primes);
@@ -2281,6 +2328,7 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
         } else if (pend[i].waves == 4) { // (u64 engine, small grid)
             if (groups && fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
             else if (groups) hipLaunchKernelGGL((k_k3<ArU64, 4, false, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
+            else if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 4, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
             else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 4, true, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
             else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
             else hipLaunchKernelGGL((k_k3<ArU64, 4>), dim3(g), dim3(256), 0, st3, A, env.primes);
@@ -2290,11 +2338,13 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
             else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
             else hipLaunchKernelGGL((k_k3<ArU64, 8, false, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
         } else if (f64) {
-            if (tensor) hipLaunchKernelGGL((k_k3<ArF64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            if (raw_tail) hipLaunchKernelGGL((k_k3<ArF64, 8, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            else if (tensor) hipLaunchKernelGGL((k_k3<ArF64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
             else if (fuse) hipLaunchKernelGGL((k_k3<ArF64, 8, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
             else hipLaunchKernelGGL((k_k3<ArF64, 8>), dim3(g), dim3(512), 0, st3, A, env.primes);
         } else {
-            if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 8, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
             else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
             else hipLaunchKernelGGL((k_k3<ArU64, 8>), dim3(g), dim3(512), 0, st3, A, env.primes);
         }
@@ -2315,13 +2365,14 @@ void launch_k3_combine(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &
 }
 
 void launch_floor_cols(const KernelEnv &env, int src_prime, int n_tgt, u64 n_polys, const u64 *src, u64 *dst, int tgt_first, int dst_ntgt, const u64 *src2,
-                       int src2_prime, int tsplit)
+                       int src2_prime, int tsplit, bool sub2)
 {
+    if (sub2 && !src2) throw std::runtime_error("floor column pass: the earlier correction comes from the merged source");
     if (!n_polys || n_tgt <= 0) return;
     FloorColsArgs A;
     A.src = src; A.dst = dst; A.src_prime = src_prime; A.n_tgt = n_tgt; A.K = env.K; A.fc = env.floor_consts;
     A.tgt_first = tgt_first; A.dst_ntgt = dst_ntgt > 0 ? dst_ntgt : n_tgt;
-    A.src2 = src2; A.src2_prime = src2_prime;
+    A.src2 = src2; A.src2_prime = src2_prime; A.sub2 = sub2;
     A.tsplit = tsplit > 1 ? tsplit : 1;
     const dim3 g((unsigned)(n_polys * 4), (unsigned)A.tsplit);
     A.f64_mask = 0;

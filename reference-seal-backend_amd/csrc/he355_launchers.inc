@@ -43,8 +43,10 @@ void launch_k3_combine(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &
 // (r mod q_i - floor(s/2) mod q_i) for i in [tgt_first, tgt_first + n_tgt) -> forward column pass -> dst [n_ops*n_src][dst_ntgt][N]
 // src2 (optional): the SOURCE of an earlier floor step ([n_polys][N] after its inverse row pass, prime src2_prime): its correction is
 // folded in before the column pass, delta2 + src2^-1 * delta1 (mod-down + rescale share one column pass and one row transform)
+// sub2 (with src2): src still lacks the earlier correction under its own prime (K3Fuse::raw_tail rows); x - src2^-1 * delta1 mod q_src is
+// formed first, once per column
 void launch_floor_cols(const KernelEnv &env, int src_prime, int n_tgt, u64 n_polys, const u64 *src, u64 *dst, int tgt_first = 0, int dst_ntgt = 0,
-                       const u64 *src2 = nullptr, int src2_prime = 0, int tsplit = 1);
+                       const u64 *src2 = nullptr, int src2_prime = 0, int tsplit = 1, bool sub2 = false);
 void launch_floor_rows(const KernelEnv &env, u64 n_ops, const FloorRowsArgs &args);
 // ---- BFV -------------------------------------------------------------------------------------------------
 // (BehzDev, kBehzMaxL / kBehzMaxB and the per-coefficient BEHZ arithmetic: behz_core.h -- host-compilable, the lane simulator runs it on the CPU)

@@ -3,7 +3,9 @@
 // register allocation of the headline's instantiations is the product's bottleneck and a __device__ function boundary changed it,
 // 48.5 -> 49.0 ms per step) and once per engine in k_k3_dual, the latency shape's both-engines-in-one-launch kernel.
 // In scope at the point of inclusion: Ar, WAVES, FUSE, TENSOR, GROUPED, A (K3Args), primes; macros K3_BID_X, K3_BID_Y, K3_LDS_DECL.
-    static_assert(!TENSOR || FUSE, "the operand rows enter through the fused epilogue's sums");
+    // TENSOR without FUSE is the rescale's divided-out prime (launch_k3, K3Fuse::raw_tail): the sums start from the operand rows and take the
+    // fused instantiation's digit loop, but no correction rows and no floor step follow -- the sums leave through the inverse row pass of
+    // the unfused epilogue, raw rows into A.tpr (k_floor_colsn<., true> subtracts the mod-down correction in coefficient form)
     static_assert(!GROUPED || !TENSOR, "grouped keys are for rotations");
     constexpr int kWaves = WAVES, kBlock = WAVES * 64; // this kernel's own block shape (shadows the file-wide one)
     typedef typename Ar::T T;
@@ -165,7 +167,7 @@
                 mac_digit(x, tt);
             }
         }
-        if constexpr (FUSE) {
+        if constexpr (FUSE || TENSOR) {
             // One digit per wave, mod-down (and rescale) finished here.  The correction rows ride the same pipeline as the digit
             // rows: rows [0, nd) are digits (transform + key MAC), rows nd, nd+1 the special-prime correction of polynomial
             // 0 / 1 (transform, then (sums - x) * P^-1 + c01), rows nd+2, nd+3 the rescale correction (transform, then
@@ -184,7 +186,7 @@
             };
             const FloorConst fc = A.fc[(A.K - 1) * A.K + t];
             const FloorConst fc2 = A.fc[(resc ? A.L - 1 : 0) * A.K + t];
-            if (nd == 0) dma_row_to_lds(row_ptr(0), stage[wave], lane); // no digit row was primed above
+            if (FUSE && nd == 0) dma_row_to_lds(row_ptr(0), stage[wave], lane); // no digit row was primed above
             // digit rows: transform + key MAC (the last one prefetches the first correction row)
             for (int i = 0; i < nd; ++i) {
                 T x[1][kRowE];
@@ -200,7 +202,7 @@
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // staging buffer drained into registers
                 // next row, behind this step's math: a digit row (packed for this engine) or the first correction row (64-bit words)
                 if (i + 1 < nd) dma_row_to_lds<kDigitPieces>(row_ptr(i + 1), stage[wave], lane);
-                else dma_row_to_lds(row_ptr(i + 1), stage[wave], lane);
+                else if constexpr (FUSE) dma_row_to_lds(row_ptr(i + 1), stage[wave], lane);
                 if constexpr (!Ar::kKeyQuotient) {
                     // both key rows of the digit are requested before the second exchange (the hook runs after phase B's math): they
                     // land behind the exchange and phase C instead of in front of the multiply-accumulate, which used to wait out
@@ -232,7 +234,7 @@
             acc_flush();
             // correction rows: transform + floor step(s)
 #pragma unroll 1
-            for (int i = nd; i < n_rows; ++i) {
+            for (int i = nd; FUSE && i < n_rows; ++i) {
                 T x[1][kRowE];
                 u64 v[kRowE], av[kRowE];
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -329,8 +331,9 @@
                     if (valid) store_rowC(A.out2 + (op * 2 + k) * L1N + (u64)tt * N + rowoff, lane, v);
                 }
             }
-        } else {
-            for (int i = i_begin; i < i_end; ++i) {
+        }
+        if constexpr (!FUSE) {
+            for (int i = i_begin; !TENSOR && i < i_end; ++i) {
                 T x[1][kRowE];
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this step's row has landed in the staging buffer
                 if constexpr (kPacked) {
@@ -350,14 +353,31 @@
             // Epilogue: canonical sums, NTT form, layout C.  Data primes -> t; special prime -> tp.  Where the next step is the
             // inverse transform of these very rows (the special prime always; every prime for BFV, whose key switch returns to
             // coefficient form) the wave runs the inverse row pass right here and writes the raw rows (special prime -> tpr).
-            const bool inv_here = tt == A.L || !A.ckks;
+            const bool inv_here = TENSOR || tt == A.L || !A.ckks;
             const bool last = A.logn1 == 0;
+            // (the raw-tail form: polynomial 1's canonical sums wait in the wave's landing buffer -- no row is on its way into it any more, and
+            // each lane reads back only what it wrote -- so that the first inverse pass does not run with 32 more live registers than the
+            // digit loop was allocated for)
+            if constexpr (TENSOR) {
+#pragma unroll
+                for (int r = 0; r < kRowE; ++r) stage[wave][(r << 6) | lane] = ar.acc_canon(acc1[r]);
+            }
 #pragma unroll 1
             for (int k = 0; k < 2; ++k) {
                 u64 v[kRowE];
-                const Acc *acc = k == 0 ? acc0 : acc1;
+                if constexpr (TENSOR) {
+                    if (k == 0) {
 #pragma unroll
-                for (int r = 0; r < kRowE; ++r) v[r] = ar.acc_canon(acc[r]);
+                        for (int r = 0; r < kRowE; ++r) v[r] = ar.acc_canon(acc0[r]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < kRowE; ++r) v[r] = stage[wave][(r << 6) | lane];
+                    }
+                } else {
+                    const Acc *acc = k == 0 ? acc0 : acc1;
+#pragma unroll
+                    for (int r = 0; r < kRowE; ++r) v[r] = ar.acc_canon(acc[r]);
+                }
                 if (split > 1) { // a partial sum: k_k3_combine finishes the tile
                     if (valid) store_rowC(A.part + (((u64)grp * A.n_ops * 2 + op * 2 + k) * (A.L + 1) + tt) * N + rowoff, lane, v);
                     continue;
@@ -372,7 +392,7 @@
                 wave_rows_inv(ar, P, last, n1 + a_row, lane, lds[wave], x);
 #pragma unroll
                 for (int r = 0; r < kRowE; ++r) v[r] = last ? ar.to_canon(x[r]) : ar.to_raw(x[r]);
-                u64 *dst = tt < A.L ? A.t + ((op * 2 + k) * A.L + tt) * N + rowoff : A.tpr + (op * 2 + k) * N + rowoff;
+                u64 *dst = tt < A.L && !TENSOR ? A.t + ((op * 2 + k) * A.L + tt) * N + rowoff : A.tpr + (op * 2 + k) * N + rowoff;
                 if (valid) store_rowA(dst, lane, v);
             }
         }
