@@ -145,6 +145,7 @@ int he355_set_relin_key_synthetic(he355_ctx *ctx, uint64_t seed);               
 int he355_set_galois_key_synthetic(he355_ctx *ctx, uint32_t galois_elt, uint64_t seed);
 
 /* ---- batched evaluator ops on device slabs; L = residues at the operands' level ---- */
+/* he355_add / he355_sub add residues whatever they stand for: also the add_inplace / sub_inplace of NTT-form BFV ciphertexts (below) */
 int he355_add(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_a, const uint64_t *d_b, he355_indexer ix, uint64_t *d_out);
 int he355_sub(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_a, const uint64_t *d_b, he355_indexer ix, uint64_t *d_out);
 /* CKKS multiply: [.][2][L][N] x [.][2][L][N] -> [n][3][L][N] */
@@ -191,6 +192,41 @@ int he355_bfv_mod_switch(he355_ctx *ctx, int L, int L_to, int size, uint64_t n, 
 int he355_bfv_add_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_sub_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_multiply_plain(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain, he355_indexer ix, uint64_t *d_out);
+/* ---- NTT-form BFV operands (BFV contexts only, else HE355_E_INVALID_ARGS, decided on the host before any device is asked for; every L in
+ * 1..L_top; polynomial (k, i) of a ciphertext at level L is under prime i < L of the key chain).  SEAL's BFV evaluator has a second mode
+ * for sums of plaintext products -- a plaintext matrix times an encrypted vector, a PIR database scan, a plain-weight linear layer: every
+ * operand is transformed once, every term is a dyadic product and an addition, the result is transformed back once.
+ * THE FORM OF A SLAB IS THE CALLER'S CONTRACT, as it is for CKKS: the library keeps raw slabs and does not track which form one is in.
+ * The transforms use the bit order he355_ntt_forward uses.
+ * [UPSTREAM-UNVERIFIED] as the level operations above (SEAL v3.7.2 evaluator.cpp):
+ *   he355_bfv_transform_to_ntt    Evaluator::transform_to_ntt_inplace(Ciphertext &): [n][size][L][N], size 1..3, coefficient form -> NTT form.
+ *   he355_bfv_transform_from_ntt  Evaluator::transform_from_ntt_inplace: the way back.  For both, d_out == d_in is allowed (in place); any
+ *                                 other overlap is refused; n == 0 touches nothing.
+ *   he355_bfv_plain_to_ntt        Evaluator::transform_to_ntt_inplace(Plaintext &, parms_id): d_plain [n][N] coefficients mod t -> d_out
+ *                                 [n][L][N]: the centred lift he355_bfv_multiply_plain multiplies by (m below floor((t + 1) / 2), else m - t,
+ *                                 reduced per prime), transformed under primes 0 .. L-1.  d_out may not overlap d_plain.
+ *   he355_bfv_multiply_plain_ntt  Evaluator::multiply_plain on NTT-form operands (multiply_plain_ntt): every polynomial times the NTT-form
+ *                                 plaintext, canonical residues; operands by the Indexer rule of he355_bfv_multiply_plain.  d_out == d_ct is
+ *                                 allowed exactly when every ciphertext serves one result (pairwise, or b1 == 1), as in he355_bfv_add_plain;
+ *                                 any other overlap is refused.  (he355_multiply_plain stays the CKKS entry and refuses BFV contexts.)
+ *   he355_bfv_multiply_plain_accumulate
+ *                                 out(i, j) = sum_{k < inner} ct(i, k) (.) pt(k, j), size-`size` results [rows * cols][size][L][N]: ciphertext
+ *                                 (i, k) at index i * ct_stride_i + k * ct_stride_k, plaintext (k, j) at k * pt_stride_k + j * pt_stride_j (the
+ *                                 addressing of he355_multiply_accumulate); size 1..3, inner 1..2^31-1; rows * cols == 0 returns without a
+ *                                 launch; d_out may not overlap an operand.  One launch: the products are summed unreduced in 128 bits and
+ *                                 reduced once per run (csrc/bfv_mac_core.h); the result is the canonical residue of the sum, bit-identical
+ *                                 to the term-by-term multiply_plain + add_inplace loop.
+ *   add_inplace / sub_inplace     he355_add / he355_sub: they are form-agnostic and serve NTT-form BFV ciphertexts as they are.
+ * NOT for NTT-form BFV ciphertexts, as in SEAL 3.7.2 (which refuses them in multiply, relinearize, the rotations, mod_switch, add_plain and
+ * decrypt): he355_bfv_multiply, he355_relinearize, he355_rotate / he355_apply_galois and their kin, he355_bfv_mod_switch,
+ * he355_bfv_add_plain / sub_plain, he355_bfv_multiply_plain, he355_decrypt, he355_bfv_noise_budget.  Transform back first: the library
+ * cannot check it and would compute garbage. */
+int he355_bfv_transform_to_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint64_t *d_out);
+int he355_bfv_transform_from_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint64_t *d_out);
+int he355_bfv_plain_to_ntt(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain, uint64_t *d_out);
+int he355_bfv_multiply_plain_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain_ntt, he355_indexer ix, uint64_t *d_out);
+int he355_bfv_multiply_plain_accumulate(he355_ctx *ctx, int L, int size, uint64_t rows, uint64_t cols, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_i,
+                                        uint64_t ct_stride_k, const uint64_t *d_plain_ntt, uint64_t pt_stride_k, uint64_t pt_stride_j, uint64_t *d_out);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

@@ -117,6 +117,11 @@ def lib():
             "he355_bfv_sub_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_bfv_multiply_plain": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_bfv_noise_budget": (i32, [vp, i32, i32, u64, vp, vp, vp]),
+            "he355_bfv_transform_to_ntt": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_transform_from_ntt": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_plain_to_ntt": (i32, [vp, i32, u64, vp, vp]),
+            "he355_bfv_multiply_plain_ntt": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
+            "he355_bfv_multiply_plain_accumulate": (i32, [vp, i32, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -160,7 +165,8 @@ C_ABI_SYMBOLS = [
     "he355_fill_uniform", "he355_fill_uniform_at", "he355_set_dual_stream", "he355_set_relin_key", "he355_set_galois_key", "he355_set_relin_key_synthetic",
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
-    "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -373,6 +379,27 @@ class Context:
     def bfv_multiply_plain(self, L, size, n, ct, pt, ix, out):
         """BFV multiply_plain: every polynomial times the centred lift of pt, negacyclic; coefficient form in and out"""
         _check(lib().he355_bfv_multiply_plain(self.h, L, size, n, ct.ptr, pt.ptr, ix, out.ptr))
+
+    def bfv_transform_to_ntt(self, L, size, n, inp, out):
+        """BFV transform_to_ntt_inplace of ciphertexts [n][size][L][N]; out may be inp (in place).  The form of a slab is the caller's contract"""
+        _check(lib().he355_bfv_transform_to_ntt(self.h, L, size, n, inp.ptr, out.ptr))
+
+    def bfv_transform_from_ntt(self, L, size, n, inp, out):
+        """BFV transform_from_ntt_inplace: NTT form -> coefficient form; out may be inp"""
+        _check(lib().he355_bfv_transform_from_ntt(self.h, L, size, n, inp.ptr, out.ptr))
+
+    def bfv_plain_to_ntt(self, L, n, pt, out):
+        """pt [n][N] coefficients mod t (bfv_encode's output) -> out [n][L][N]: centred lift, NTT form under primes 0 .. L-1"""
+        _check(lib().he355_bfv_plain_to_ntt(self.h, L, n, pt.ptr, out.ptr))
+
+    def bfv_multiply_plain_ntt(self, L, size, n, ct, pt_ntt, ix, out):
+        """BFV multiply_plain on NTT-form operands: every polynomial times the NTT-form plaintext (bfv_plain_to_ntt's output)"""
+        _check(lib().he355_bfv_multiply_plain_ntt(self.h, L, size, n, ct.ptr, pt_ntt.ptr, ix, out.ptr))
+
+    def bfv_multiply_plain_accumulate(self, L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt_ntt, pt_stride_k, pt_stride_j, out):
+        """out(i, j) = sum_k ct(i, k) (.) pt(k, j) over NTT-form operands, [rows * cols][size][L][N]: one launch, bit-identical to the loop"""
+        _check(lib().he355_bfv_multiply_plain_accumulate(self.h, L, size, rows, cols, inner, ct.ptr, ct_stride_i, ct_stride_k, pt_ntt.ptr,
+                                                         pt_stride_k, pt_stride_j, out.ptr))
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

@@ -1724,6 +1724,78 @@ public:
         });
         HIPCHECK(hipGetLastError());
     }
+    // ---- NTT-form BFV operands (he355_kernels_bfv_ntt.hip) -------------------------------------------------------------------
+    // Evaluator::transform_to_ntt_inplace / transform_from_ntt_inplace of ciphertexts: [n][size][L][N], polynomial (k, i) under prime i.
+    // In place, or apart (copied, then transformed where it lands).  The library does not track which form a slab is in.
+    void bfv_transform(int L, int size, u64 n, const u64 *in, u64 *out, bool inverse)
+    {
+        const char *what = inverse ? "he355_bfv_transform_from_ntt" : "he355_bfv_transform_to_ntt";
+        use();
+        check_level(L);
+        require_bfv(what);
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        const size_t N = P.N, words = (size_t)n * size * L * N;
+        if (out != in && ranges_overlap(in, words, out, words)) throw std::invalid_argument(std::string(what) + ": `out` overlaps `in` (in place: the same pointer)");
+        if (n * size > 0xffffffffull) throw std::invalid_argument(std::string(what) + ": too many polynomials for one call");
+        if (!n) return;
+        if (out != in) HIPCHECK(hipMemcpyAsync(out, in, words * 8, hipMemcpyDeviceToDevice, stream_));
+        const PolyView v = poly_view(out, L, N, L);
+        if (inverse) launch_ntt_inverse(env_, v, (u32)(n * size));
+        else launch_ntt_forward(env_, v, (u32)(n * size));
+        HIPCHECK(hipGetLastError());
+    }
+    // Evaluator::transform_to_ntt_inplace(Plaintext, parms_id): plain [n][N] mod t -> out [n][L][N], the centred lift he355_bfv_multiply_plain
+    // multiplies by, transformed under primes 0 .. L-1
+    void bfv_plain_to_ntt(int L, u64 n, const u64 *plain, u64 *out)
+    {
+        use();
+        check_level(L);
+        require_bfv("he355_bfv_plain_to_ntt");
+        const size_t N = P.N;
+        if (ranges_overlap(out, (size_t)n * L * N, plain, (size_t)n * N)) throw std::invalid_argument("he355_bfv_plain_to_ntt: `out` overlaps the plaintexts");
+        if (n > 0xffffffffull) throw std::invalid_argument("he355_bfv_plain_to_ntt: too many plaintexts for one call");
+        if (!n) return;
+        launch_bfv_lift_plain(env_, L, n, plain, out, P.plain_modulus);
+        launch_ntt_forward(env_, poly_view(out, L, N, L), (u32)n);
+        HIPCHECK(hipGetLastError());
+    }
+    // Evaluator::multiply_plain on NTT-form operands (multiply_plain_ntt): every polynomial times the NTT-form plaintext, k_plain_op's product
+    void bfv_multiply_plain_ntt(int L, int size, u64 n, const u64 *ct, const u64 *pt, Indexer ix, u64 *out)
+    {
+        use();
+        check_level(L);
+        require_bfv("he355_bfv_multiply_plain_ntt");
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        if (!n) return;
+        const size_t LN = (size_t)L * P.N, ctn = (size_t)size * LN;
+        u64 a_lo, a_n, b_lo, b_n;
+        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
+        // in place exactly where every ciphertext serves one result: result r then reads the words it writes (as he355_bfv_add_plain)
+        const bool in_place = out == ct + a_lo * ctn && (ix.pairwise || ix.b1 == 1);
+        if (!in_place && ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn)) throw std::invalid_argument("he355_bfv_multiply_plain_ntt: `out` overlaps the ciphertexts (in place only when each serves one result)");
+        if (ranges_overlap(out, n * ctn, pt + b_lo * LN, b_n * LN)) throw std::invalid_argument("he355_bfv_multiply_plain_ntt: `out` overlaps the plaintexts");
+        launch_plain_op(env_, L, size, n, ct, pt, ix, out, 0);
+        HIPCHECK(hipGetLastError());
+    }
+    // out(i, j) = sum_k ct(i, k) (.) pt(k, j): the multiply_plain / add_inplace loop of a plaintext matrix x encrypted vector, one launch on
+    // the context's stream (nothing to fork: no scratch, no second stream)
+    void bfv_multiply_plain_accumulate(int L, int size, u64 rows, u64 cols, u64 inner, const u64 *ct, u64 ct_stride_i, u64 ct_stride_k, const u64 *pt,
+                                       u64 pt_stride_k, u64 pt_stride_j, u64 *out)
+    {
+        use();
+        check_level(L);
+        require_bfv("he355_bfv_multiply_plain_accumulate");
+        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        if (inner < 1 || inner > 0x7fffffff) throw std::invalid_argument("inner dimension out of range");
+        const u64 n = rows * cols;
+        if (!n) return;
+        const size_t LN = (size_t)L * P.N, ctn = (size_t)size * LN;
+        const size_t n_ct = (size_t)((inner - 1) * ct_stride_k + (rows - 1) * ct_stride_i + 1), n_pt = (size_t)((inner - 1) * pt_stride_k + (cols - 1) * pt_stride_j + 1);
+        if (ranges_overlap(out, n * ctn, ct, n_ct * ctn) || ranges_overlap(out, n * ctn, pt, n_pt * LN))
+            throw std::invalid_argument("he355_bfv_multiply_plain_accumulate: `out` overlaps an operand");
+        launch_bfv_plain_mac(env_, L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
+        HIPCHECK(hipGetLastError());
+    }
     const CrtTablesDev &crt_tables(int L)
     {
         auto it = crt_.find(L);
@@ -2377,6 +2449,30 @@ int he355_bfv_sub_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_
 int he355_bfv_multiply_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
 {
     return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain"); dev(c).bfv_multiply_plain(L, size, n, ct, pt, to_ix(ix), out); });
+}
+int he355_bfv_transform_to_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_transform_to_ntt"); dev(c).bfv_transform(L, size, n, in, out, false); });
+}
+int he355_bfv_transform_from_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_transform_from_ntt"); dev(c).bfv_transform(L, size, n, in, out, true); });
+}
+int he355_bfv_plain_to_ntt(he355_ctx *c, int L, uint64_t n, const uint64_t *plain, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_plain_to_ntt"); dev(c).bfv_plain_to_ntt(L, n, plain, out); });
+}
+int he355_bfv_multiply_plain_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
+{
+    return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain_ntt"); dev(c).bfv_multiply_plain_ntt(L, size, n, ct, pt, to_ix(ix), out); });
+}
+int he355_bfv_multiply_plain_accumulate(he355_ctx *c, int L, int size, uint64_t rows, uint64_t cols, uint64_t inner, const uint64_t *ct, uint64_t ct_stride_i,
+                                        uint64_t ct_stride_k, const uint64_t *pt, uint64_t pt_stride_k, uint64_t pt_stride_j, uint64_t *out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_multiply_plain_accumulate");
+        dev(c).bfv_multiply_plain_accumulate(L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
+    });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)
 {

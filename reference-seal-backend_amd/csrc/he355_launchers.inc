@@ -132,3 +132,8 @@ void launch_bfv_noise_dot_sk(const KernelEnv &env, int L, int size, u64 n_cts, c
 void launch_bfv_noise_bits(const KernelEnv &env, int size, u64 n_cts, const u64 *part, const u64 *ct, int *bits, const CrtTablesDev &crt, const BfvNoiseConst &c);
 // in place: budget[r] = max(0, q_bits - budget[r] - 1); noise_bits[r] (if given) = the value that came in
 void launch_bfv_noise_finish(const KernelEnv &env, u64 n_cts, int *budget, int *noise_bits, int q_bits);
+// ---- NTT-form BFV plaintext inner product (he355_kernels_bfv_ntt.hip; arithmetic: bfv_mac_core.h) ---------------------------------------------
+// out(i, j) = sum_k ct(i, k) (.) pt(k, j), canonical residues: ct [.][size][L][N] and pt [.][L][N] in NTT form, ciphertext (i, k) at index
+// i * ct_stride_i + k * ct_stride_k, plaintext (k, j) at k * pt_stride_k + j * pt_stride_j; out [rows * cols][size][L][N].  One launch.
+void launch_bfv_plain_mac(const KernelEnv &env, int L, int size, u64 rows, u64 cols, u64 inner, const u64 *ct, u64 ct_stride_i, u64 ct_stride_k, const u64 *pt,
+                          u64 pt_stride_k, u64 pt_stride_j, u64 *out);
