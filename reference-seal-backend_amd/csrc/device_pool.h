@@ -184,4 +184,11 @@ private:
     Stats st_;
 };
 
+// A grow-on-demand device buffer of a context: one raw block of its pool and the block's size.  DeviceContext::reserve grows it (the
+// context's streams are drained before the old block goes) and DeviceContext::try_reserve asks first whether the device can hold it.
+struct Arena {
+    uint64_t *p = nullptr;
+    size_t bytes = 0;
+};
+
 } // namespace he355

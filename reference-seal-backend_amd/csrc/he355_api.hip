@@ -168,6 +168,20 @@ public:
         if (e != hipSuccess || count <= 0) throw DeviceError("no HIP device available (the MI355X backend has no CPU fallback)");
         if (device < 0 || device >= count) throw DeviceError("invalid device ordinal");
         HIPCHECK(hipSetDevice(device));
+        // a throw from here on (out of memory on a table) must give back the streams, events and tables made so far: the destructor of a
+        // half-built object never runs, so the same teardown is called by hand
+        try {
+            init();
+        } catch (...) {
+            teardown();
+            throw;
+        }
+    }
+    ~DeviceContext() { teardown(); }
+
+private:
+    void init()
+    {
         HIPCHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         HIPCHECK(hipStreamCreateWithFlags(&stream2_, hipStreamNonBlocking));
         HIPCHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
@@ -183,13 +197,7 @@ public:
         std::vector<PrimeDev> pd(n_all);
         for (size_t i = 0; i < n_all; ++i) {
             const PrimeTables &pt = i < K ? P.primes[i] : i < K + P.aux.size() ? P.aux[i - K] : plain_tables_;
-            Tw16 *dfwd = nullptr, *dinv = nullptr;
-            dmalloc(dfwd, N * sizeof(Tw16));
-            owned_.push_back(dfwd);
-            dmalloc(dinv, N * sizeof(Tw16));
-            owned_.push_back(dinv);
-            HIPCHECK(hipMemcpy(dfwd, pt.fwd.data(), N * sizeof(Tw16), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(dinv, pt.inv.data(), N * sizeof(Tw16), hipMemcpyHostToDevice));
+            Tw16 *dfwd = upload_owned(pt.fwd.data(), N), *dinv = upload_owned(pt.inv.data(), N);
             PrimeDev &d = pd[i];
             const ArU64 au = pt.aru();
             const ArF64 af = pt.arf();
@@ -217,8 +225,7 @@ public:
                 if (!(m * 1.0000001 < 140737488355328.0)) continue;
                 (direct ? pd[j].k2_direct : pd[j].k2_lift) |= (u64)1 << t;
             }
-        dmalloc(d_primes_, n_all * sizeof(PrimeDev));
-        HIPCHECK(hipMemcpy(d_primes_, pd.data(), n_all * sizeof(PrimeDev), hipMemcpyHostToDevice));
+        d_primes_ = upload_owned(pd.data(), n_all);
         std::vector<FloorConst> fc(K * K);
         for (size_t s = 0; s < K; ++s)
             for (size_t i = 0; i < K; ++i) {
@@ -234,8 +241,7 @@ public:
                 f.half_mod = (qs >> 1) % qi;
                 f.src_mod = qs % qi;
             }
-        dmalloc(d_floor_, K * K * sizeof(FloorConst));
-        HIPCHECK(hipMemcpy(d_floor_, fc.data(), K * K * sizeof(FloorConst), hipMemcpyHostToDevice));
+        d_floor_ = upload_owned(fc.data(), K * K);
         env_.primes = d_primes_;
         env_.floor_consts = d_floor_;
         env_.N = (int)N; env_.logn1 = P.logn1; env_.K = (int)K; env_.Ltop = (int)P.Ltop; env_.scheme = P.scheme;
@@ -248,42 +254,38 @@ public:
         if (env_u64("HE355_LDS_MAX", v)) set_lds_max(v);
         if (env_u64("HE355_CHUNK", v) && v > 0) chunk_ = (size_t)v;
     }
-    ~DeviceContext()
+    // drain, free the tables, the keys and the arenas, destroy the pool, then the events and streams (whatever of them exists)
+    void teardown()
     {
         (void)hipSetDevice(device_);
-        (void)hipStreamSynchronize(stream_);
+        for (hipStream_t s : {stream_, stream2_, probe_stream_})
+            if (s) (void)hipStreamSynchronize(s);
         for (void *p : owned_) pool_.raw_free(p);
-        pool_.raw_free(d_primes_);
-        pool_.raw_free(d_floor_);
         pool_.raw_free(d_relin_);
         pool_.raw_free(d_relin_scaled_);
-        pool_.raw_free(d_clock_);
         for (auto &kv : d_galois_) pool_.raw_free(kv.second);
-        for (auto &kv : d_perm_) pool_.raw_free(kv.second);
-        (void)hipStreamSynchronize(stream2_);
-        pool_.raw_free(scratch_);
-        pool_.raw_free(scratch2_);
-        pool_.raw_free(rot_tmp_);
-        pool_.raw_free(d_groups_);
-        pool_.raw_free(lat_part_[0]);
-        pool_.raw_free(lat_part_[1]);
-        pool_.raw_free(bfv_scratch_);
-        pool_.raw_free(client_scratch_);
-        for (auto &kv : d_gather_) pool_.raw_free(kv.second);
+        for (Arena &a : arena_) pool_.raw_free(a.p);
         pool_.destroy();
-        (void)hipEventDestroy(ev_fork_);
-        (void)hipEventDestroy(ev_join_);
-        (void)hipStreamDestroy(stream2_);
-        if (probe_stream_) { (void)hipStreamSynchronize(probe_stream_); (void)hipStreamDestroy(probe_stream_); }
-        (void)hipEventDestroy(ev0_);
-        (void)hipEventDestroy(ev1_);
-        (void)hipStreamDestroy(stream_);
+        for (hipEvent_t e : {ev_fork_, ev_join_, ev0_, ev1_})
+            if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {stream2_, probe_stream_, stream_})
+            if (s) (void)hipStreamDestroy(s);
     }
 
+public:
     void use() { HIPCHECK(hipSetDevice(device_)); }
     // ---- device memory (device_pool.h): slabs handed to callers come from the pool, the context's own tables / keys / arenas
     // are raw allocations; both are counted
     template <class T> void dmalloc(T *&p, size_t bytes) { p = static_cast<T *>(pool_.raw_malloc(bytes)); }
+    // a device table the context owns until it goes (owned_): `count` elements, copied from `h` (null: left as allocated)
+    template <class T> T *upload_owned(const T *h, size_t count)
+    {
+        T *d = nullptr;
+        dmalloc(d, count * sizeof(T));
+        owned_.push_back(d);
+        if (h) HIPCHECK(hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice));
+        return d;
+    }
     void *pool_alloc(size_t bytes)
     {
         use();
@@ -405,10 +407,7 @@ public:
         auto it = d_perm_.find(elt);
         if (it != d_perm_.end()) return it->second;
         const std::vector<uint32_t> h = P.galois_perm_ntt(elt);
-        uint32_t *d = nullptr;
-        dmalloc(d, P.N * 4);
-        HIPCHECK(hipMemcpy(d, h.data(), P.N * 4, hipMemcpyHostToDevice));
-        d_perm_[elt] = d;
+        const uint32_t *d = d_perm_[elt] = upload_owned(h.data(), P.N);
         std::array<unsigned char, 32> rows{};
         for (size_t a = 0; a < ((size_t)1 << P.logn1) && a < rows.size(); ++a) rows[a] = (unsigned char)(h[a << kRowLog] >> kRowLog);
         perm_rows_[elt] = rows; // the one source row of every row of the permuted polynomial (the ring-in-LDS kernels take it with their arguments)
@@ -420,11 +419,7 @@ public:
         auto it = d_gather_.find(elt);
         if (it != d_gather_.end()) return it->second;
         const std::vector<uint32_t> h = P.galois_gather_coeff(elt);
-        uint32_t *d = nullptr;
-        dmalloc(d, P.N * 4);
-        HIPCHECK(hipMemcpy(d, h.data(), P.N * 4, hipMemcpyHostToDevice));
-        d_gather_[elt] = d;
-        return d;
+        return d_gather_[elt] = upload_owned(h.data(), P.N);
     }
 
     void set_dual_stream(bool on) { dual_stream_ = on; }
@@ -449,6 +444,10 @@ public:
     void check_level(int L) const
     {
         if (L < 1 || (size_t)L > P.Ltop) throw std::invalid_argument("level out of range");
+    }
+    static void check_size(int size, int lo, int hi) // "ciphertext size must be 1..3" / "... 2 or 3"
+    {
+        if (size < lo || size > hi) throw std::invalid_argument("ciphertext size must be " + std::to_string(lo) + (hi == lo + 1 ? " or " : "..") + std::to_string(hi));
     }
     void addsub(int L, int size, u64 n, const u64 *a, const u64 *b, Indexer ix, u64 *out, bool sub)
     {
@@ -477,64 +476,70 @@ public:
         const size_t N = P.N, LN = (size_t)L * N;
         return 2 * LN + LN + LN + (size_t)(L + 1) * LN + 2 * LN + 2 * N + 2 * N + 2 * LN + 3 * N + 3 * LN;
     }
-    // Ciphertexts per chunk for a batch of n at level L: chunk_ (default 1024, HE355_CHUNK / he355_set_chunk), halved until the scratch
-    // arena(s) it needs -- two when the batch is cut and the chunks alternate between the streams -- are RESERVED: each arena is checked by
-    // itself (growing one frees only that one), against 0.9 of the memory that is free now plus what this context can give back (the
-    // arena being replaced, the pool's cached blocks); a hipMalloc that fails all the same (another context or process took the memory
-    // between the query and the call) halves the chunk again instead of failing the operation.  On return scratch(c, L, which) does not
-    // allocate.
-    size_t chunk_ops(u64 n, int L, bool may_dual)
+    // ---- the context's grow-on-demand device buffers (Arena, device_pool.h), one per use: which buffer serves which call is fixed
+    enum { kScratch0, kScratch1, // key-switch scratch, one per stream (scratch())
+           kLat0, kLat1,         // partial sums of the digit-split K3 (latency shape), one per stream: chunks of the two are in flight together
+           kRotTmp,              // intermediate ciphertexts of rotation chains (rotate, rotate_sum_by_node, rotate_each)
+           kBfv,                 // the BFV multiply's operands and products; he355_bfv_multiply_plain's prepared plaintexts
+           kClient,              // encrypt / decrypt / encode / decode / noise budget / key generation
+           kGroups,              // the ring of group tables of the grouped key switches (upload_groups)
+           kArenas };
+    // at least `bytes` afterwards; contents are not kept.  Both streams are drained before the old block goes (no steady-state call grows
+    // one: test_steady_state_operate_does_not_allocate).
+    u64 *reserve(Arena &a, size_t bytes)
     {
-        size_t c = std::min<u64>(chunk_, n ? n : 1);
-        const size_t per_op = scratch_words_per_op(L) * 8;
-        for (;;) {
-            const int arenas = (may_dual && n > c) ? 2 : 1;
-            const size_t need = per_op * c;
-            size_t grow = 0, reclaim = pool_.cached_bytes();
-            for (int a = 0; a < arenas; ++a) {
-                const size_t have = a ? scratch2_bytes_ : scratch_bytes_;
-                if (need > have) { grow += need; reclaim += have; }
-            }
-            bool fits = grow == 0;
-            if (!fits) {
-                size_t free_b = 0, total_b = 0;
-                fits = hipMemGetInfo(&free_b, &total_b) != hipSuccess || (double)grow <= 0.9 * (double)(free_b + reclaim);
-            }
-            if (fits) {
-                try {
-                    for (int a = 0; a < arenas; ++a) reserve_arena(a, need);
-                    return c;
-                } catch (const OutOfDeviceMemory &) {
-                    if (c == 1) throw;
-                }
-            } else if (c == 1) {
-                throw OutOfDeviceMemory("HIP error: out of device memory: the key-switch scratch of one ciphertext (" + std::to_string(per_op) + " bytes) does not fit");
-            }
-            c = (c + 1) / 2;
-        }
-    }
-    void reserve_arena(int which, size_t need) { which ? grow(scratch2_, scratch2_bytes_, need) : grow(scratch_, scratch_bytes_, need); }
-    // the context's grow-on-demand device buffers: at least `bytes` afterwards.  Both streams are drained before the old buffer goes (no
-    // steady-state call grows one: test_steady_state_operate_does_not_allocate).
-    void grow(u64 *&buf, size_t &buf_bytes, size_t bytes)
-    {
-        if (bytes <= buf_bytes) return;
+        if (bytes <= a.bytes) return a.p;
         HIPCHECK(hipStreamSynchronize(stream_));
         HIPCHECK(hipStreamSynchronize(stream2_));
-        pool_.raw_free(buf);
-        buf = nullptr;
-        buf_bytes = 0;
-        dmalloc(buf, bytes);
-        buf_bytes = bytes;
+        pool_.raw_free(a.p);
+        a = Arena{};
+        dmalloc(a.p, bytes);
+        a.bytes = bytes;
+        return a.p;
+    }
+    // The one fit rule: the `count` arenas from `first` on hold `need` bytes each afterwards, or false -- not enough device memory.  What has
+    // to grow is checked against 0.9 of the memory that is free now plus what this context can give back (the arenas being replaced, the
+    // pool's cached blocks); a hipMalloc that fails all the same (another context or process took the memory between the query and the
+    // call) is a "no" as well, not an error -- unless the caller has nothing smaller left to ask for (last_resort: the allocator's own error goes up).
+    bool try_reserve(Arena *first, int count, size_t need, bool last_resort = false)
+    {
+        size_t grow = 0, reclaim = pool_.cached_bytes();
+        for (Arena *a = first; a != first + count; ++a)
+            if (need > a->bytes) { grow += need; reclaim += a->bytes; }
+        size_t free_b = 0, total_b = 0;
+        if (grow && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)grow > 0.9 * (double)(free_b + reclaim)) return false;
+        try {
+            for (Arena *a = first; a != first + count; ++a) reserve(*a, need);
+            return true;
+        } catch (const OutOfDeviceMemory &) {
+            if (last_resort) throw;
+            return false;
+        }
+    }
+    // the one halving loop: c, halved until fits(c) says yes; 0 when not even one fits
+    template <class F> static size_t halve_until_fit(size_t c, F &&fits)
+    {
+        for (;; c = (c + 1) / 2) {
+            if (fits(c)) return c;
+            if (c == 1) return 0;
+        }
+    }
+    // Ciphertexts per chunk for a batch of n at level L: chunk_ (default 1024, HE355_CHUNK / he355_set_chunk), halved until the scratch
+    // arena(s) it needs -- two when the batch is cut and the chunks alternate between the streams -- are RESERVED (try_reserve: growing one
+    // arena frees only that one).  On return scratch(c, L, which) does not allocate.
+    size_t chunk_ops(u64 n, int L, bool may_dual)
+    {
+        const size_t per_op = scratch_words_per_op(L) * 8;
+        const size_t c = halve_until_fit(std::min<u64>(chunk_, n ? n : 1), [&](size_t k) { return try_reserve(&arena_[kScratch0], (may_dual && n > k) ? 2 : 1, per_op * k, k == 1); });
+        if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the key-switch scratch of one ciphertext (" + std::to_string(per_op) + " bytes) does not fit");
+        return c;
     }
     Scratch scratch(size_t c, int L, int which = 0)
     {
         const size_t N = P.N, LN = (size_t)L * N;
         const size_t per_op = scratch_words_per_op(L);
-        reserve_arena(which, per_op * c * 8);
-        u64 *arena = which ? scratch2_ : scratch_;
         Scratch s;
-        u64 *p = arena;
+        u64 *p = reserve(arena_[kScratch0 + which], per_op * c * 8);
         s.ks.c01 = p; p += c * 2 * LN; s.ks.c01_item_stride = 2 * LN;
         s.ks.c2n = p; p += c * LN;
         s.ks.c2r = p; p += c * LN;
@@ -688,10 +693,9 @@ public:
         // k_k3 (fused) and the ring-in-LDS kernels read the operand rows while they write results: only when `out` is a slab of its own
         bool out_apart = true;
         if (product && n) {
-            const Indexer &ix = src.ix;
-            const u64 a_lo = idx_a(ix, 0), a_hi = idx_a(ix, n - 1), b_lo = ix.b_base, b_hi = ix.pairwise ? ix.b_base + n - 1 : ix.b_base + std::min<u64>(n, ix.b1) - 1;
-            out_apart = !ranges_overlap(out, n * out_per, src.a + a_lo * 2 * LN, (size_t)(a_hi - a_lo + 1) * 2 * LN) &&
-                        !ranges_overlap(out, n * out_per, src.b + b_lo * 2 * LN, (size_t)(b_hi - b_lo + 1) * 2 * LN);
+            u64 a_lo, a_n, b_lo, b_n;
+            indexer_span(src.ix, n, a_lo, a_n, b_lo, b_n);
+            out_apart = !ranges_overlap(out, n * out_per, src.a + a_lo * 2 * LN, (size_t)a_n * 2 * LN) && !ranges_overlap(out, n * out_per, src.b + b_lo * 2 * LN, (size_t)b_n * 2 * LN);
         } else if (src.kind == KsKind::Size3) {
             out_apart = !ranges_overlap(out, n * out_per, src.a, n * 3 * LN);
         }
@@ -781,7 +785,7 @@ public:
             // wave walking all digits of a tile and one lane walking all targets of a column while the chip idles.  Same kernels,
             // unfused, with the serial loops dealt to more blocks: targets of a column over kLatTargets blocks (k_k2n, k_floor_colsn),
             // digits of a tile over kLatSplit (u64 engine: kLatSplitU64) single-wave blocks whose partial sums k_k3_combine adds (k_k3).
-            u64 *part = latency_partials((size_t)std::max(kLatSplit, kLatSplitU64) * nc * 2 * (L + 1) * N, env.stream == stream2_ ? 1 : 0);
+            u64 *part = reserve(arena_[kLat0 + (env.stream == stream2_ ? 1 : 0)], (size_t)std::max(kLatSplit, kLatSplitU64) * nc * 2 * (L + 1) * N * 8);
             launch_k3(env, L, nc, B, key, K3_ALL, nullptr, kLatSplit, part, kLatSplitU64);
             launch_k3_combine(env, L, nc, B, kLatSplit, part, kLatSplitU64);
             launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e, 0, 0, nullptr, 0, kLatTargets);
@@ -851,11 +855,6 @@ public:
         fr.tail_prime = -1; fr.tail = nullptr;
         launch_floor_rows(env, nc, fr);
     }
-    u64 *latency_partials(size_t elems, int which) // one buffer per stream: chunks of the two streams are in flight together
-    {
-        grow(lat_part_[which], lat_part_bytes_[which], elems * 8);
-        return lat_part_[which];
-    }
     void require_keyswitch() const
     {
         if (P.K < 2) throw std::invalid_argument("encryption parameters do not support key switching");
@@ -892,7 +891,7 @@ public:
         use();
         check_level(L);
         if (P.scheme != kSchemeCKKS) throw std::invalid_argument("plaintext operands are NTT-form CKKS plaintexts");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         launch_plain_op(env_, L, size, n, ct, pt, ix, out, mode);
         HIPCHECK(hipGetLastError());
     }
@@ -909,7 +908,7 @@ public:
     {
         use();
         check_level(L);
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (n < 1) throw std::invalid_argument("nothing to sum");
         launch_sum_cts(env_, L, size, n, in, out);
         HIPCHECK(hipGetLastError());
@@ -931,7 +930,7 @@ public:
         check_level(L);
         if (P.scheme != kSchemeCKKS) throw std::invalid_argument("he355_rescale is a CKKS operation");
         if (L < 2) throw std::invalid_argument("cannot rescale at the last level");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         const size_t N = P.N, LN = (size_t)L * N, L1N = (size_t)(L - 1) * N;
         const bool apart = !ranges_overlap(in, n * size * LN, out, n * size * L1N); // (the two-launch form's blocks of an op read all of its input)
         for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int which, const Scratch &S, hipEvent_t) {
@@ -1000,12 +999,12 @@ public:
             if ((size_t)(s < 0 ? -s : s) != P.N / 2) steps.push_back(s); // a term of N/2 is no rotation
         if (steps.empty()) { plain_copy(); return; }
         if (addend == out && steps.size() > 1) throw std::invalid_argument("rotate_add through several Galois steps cannot add in place");
-        if (steps.size() > 1) grow(rot_tmp_, rot_tmp_bytes_, bytes);
+        u64 *rot_tmp = steps.size() > 1 ? reserve(arena_[kRotTmp], bytes) : nullptr;
         // ping-pong between out and the temporary so that the last rotation lands in out
         const u64 *cur = in;
         const size_t m = steps.size();
         for (size_t t = 0; t < m; ++t) {
-            u64 *dst = ((m - 1 - t) % 2 == 0) ? out : rot_tmp_;
+            u64 *dst = ((m - 1 - t) % 2 == 0) ? out : rot_tmp;
             const uint32_t e = P.galois_elt_from_step(steps[t]);
             if (!e || !galois_key(e)) throw std::invalid_argument("Galois key not present");
             apply_galois(L, n, cur, e, dst, t + 1 == m ? addend : nullptr, ntt_form); // the addend joins the last step only
@@ -1092,17 +1091,13 @@ public:
         // launched with it may still be running; when the ring wraps (or has to grow) the stream is drained first.  The copy itself is
         // synchronous (complete on return, whatever the runtime does with pageable memory), and everything that reads the region is
         // launched afterwards.
-        if (bytes > groups_bytes_ || groups_next_ + bytes > groups_bytes_) {
+        Arena &ring = arena_[kGroups];
+        if (bytes > ring.bytes || groups_next_ + bytes > ring.bytes) {
             HIPCHECK(hipStreamSynchronize(stream_));
-            if (bytes > groups_bytes_ / 4) {
-                pool_.raw_free(d_groups_);
-                d_groups_ = nullptr; groups_bytes_ = 0;
-                dmalloc(d_groups_, std::max<size_t>(bytes * 8, (size_t)64 << 10));
-                groups_bytes_ = std::max<size_t>(bytes * 8, (size_t)64 << 10);
-            }
+            if (bytes > ring.bytes / 4) reserve(ring, std::max<size_t>(bytes * 8, (size_t)64 << 10)); // (eight uploads' worth: always more than it held; reserve drains both streams)
             groups_next_ = 0;
         }
-        unsigned char *d_tab = d_groups_ + groups_next_;
+        unsigned char *d_tab = reinterpret_cast<unsigned char *>(ring.p) + groups_next_;
         groups_next_ += bytes;
         std::vector<unsigned char> h(bytes, 0);
         std::memcpy(h.data(), perms.data(), G * 8);
@@ -1238,7 +1233,7 @@ public:
         // one ciphertext slab per trie level (a node's ciphertext lives until its last child is done; a leaf needs one only when
         // several steps end there)
         const size_t levels = depth;
-        grow(rot_tmp_, rot_tmp_bytes_, levels * bytes);
+        u64 *rot_tmp = reserve(arena_[kRotTmp], levels * bytes);
         u64 switches = 0;
         // depth-first: (node, level of the node = number of terms applied)
         std::vector<std::pair<int, size_t>> stack;
@@ -1247,12 +1242,12 @@ public:
             const auto [id, lvl] = stack.back();
             stack.pop_back();
             const RotNode &nd = trie[(size_t)id];
-            const u64 *src = lvl == 1 ? in : rot_tmp_ + (lvl - 2) * n * per;
+            const u64 *src = lvl == 1 ? in : rot_tmp + (lvl - 2) * n * per;
             const uint32_t e = nd.elt;
             if (nd.kids.empty() && nd.ends == 1) {
                 apply_galois(L, n, src, e, out, out); // a leaf: the add_inplace rides the Galois step (sum += rotate(parent))
             } else {
-                u64 *mine = rot_tmp_ + (lvl - 1) * n * per;
+                u64 *mine = rot_tmp + (lvl - 1) * n * per;
                 apply_galois(L, n, src, e, mine);
                 for (u64 r = 0; r < nd.ends; ++r) addsub(L, 2, n, out, mine, ixp, out, false);
                 for (auto it = nd.kids.rbegin(); it != nd.kids.rend(); ++it) stack.push_back({*it, lvl + 1});
@@ -1281,8 +1276,7 @@ public:
         HIPCHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, stream_));
         if (!depth) return;
         require_keyswitch();
-        grow(rot_tmp_, rot_tmp_bytes_, 2 * bytes);
-        u64 *ga = rot_tmp_, *gb = rot_tmp_ + n * per;
+        u64 *ga = reserve(arena_[kRotTmp], 2 * bytes), *gb = ga + n * per;
         for (size_t t = 0; t < depth; ++t) {
             std::map<uint32_t, std::vector<uint32_t>> groups; // Galois element -> ciphertexts whose t-th term it is
             u64 m_all = 0;
@@ -1379,21 +1373,21 @@ public:
     }
 
     // ---- BFV ------------------------------------------------------------------------------------------
+    // the per-level caches (behz_, crt_, bfv_delta_, bfv_noise_): the entry of level L, built on first use
+    template <class T, class F> static const T &per_level(std::map<int, T> &cache, int L, F &&build)
+    {
+        auto it = cache.find(L);
+        if (it == cache.end()) it = cache.emplace(L, build()).first;
+        return it->second;
+    }
     const BehzDev &behz(int L)
     {
-        auto it = behz_.find(L);
-        if (it != behz_.end()) return it->second;
-        const BehzHost H = P.behz_host(L); // the folded constants (he_params.cpp), as two flat arrays
-        u64 *d = nullptr;
-        dmalloc(d, H.words.size() * 8);
-        owned_.push_back(d);
-        HIPCHECK(hipMemcpy(d, H.words.data(), H.words.size() * 8, hipMemcpyHostToDevice));
-        double *ddev = nullptr;
-        dmalloc(ddev, H.doubles.size() * 8);
-        owned_.push_back(ddev);
-        HIPCHECK(hipMemcpy(ddev, H.doubles.data(), H.doubles.size() * 8, hipMemcpyHostToDevice));
-        const BehzDev Z = H.view(d, ddev, P.K);
-        return behz_[L] = Z;
+        return per_level(behz_, L, [&] {
+            const BehzHost H = P.behz_host(L); // the folded constants (he_params.cpp), as two flat arrays
+            u64 *d = upload_owned(H.words.data(), H.words.size());
+            double *ddev = upload_owned(H.doubles.data(), H.doubles.size());
+            return H.view(d, ddev, P.K);
+        });
     }
     // out(i, j) = sum_k relinearize(multiply(a(i, k), b(k, j))): the multiply / relinearize_inplace / add_inplace loop of the BFV
     // CipherBatchAxis matrix product (bfv cipherbatchaxis .cpp:398-410) with the inner index as part of the batch -- one multiply and
@@ -1437,17 +1431,27 @@ public:
     }
     // Evaluator::bfv_multiply (BEHZ), size 2 x 2 -> 3, coefficient form
     void bfv_multiply(int L, u64 n, const u64 *a, const u64 *b, Indexer ix, u64 *out) { bfv_multiply3(L, n, a, b, to_ix3(ix), out); }
-    // the BFV multiply's scratch arena holds at least `bytes` afterwards, or false (not enough device memory: the caller halves its chunk)
-    bool reserve_bfv_scratch(size_t bytes)
+    // The two halves of the BEHZ multiply that its two paths share (vq / vb: the views of a polynomial set under q and under Bsk).
+    // Extension to Bsk and the forward column passes of n_items operands (two polynomials each) into xq / xb: one kernel where the fused shape applies
+    void behz_extend_fwd_cols(const BehzDev &Z, const BehzSrc &src, bool fuse_cols, u64 n_items, u64 *xq, u64 *xb, PolyView vq, PolyView vb)
     {
-        if (bytes <= bfv_bytes_) return true;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)bytes > 0.9 * (double)(free_b + bfv_bytes_ + pool_.cached_bytes())) return false;
-        try {
-            grow(bfv_scratch_, bfv_bytes_, bytes);
-            return true;
-        } catch (const OutOfDeviceMemory &) {
-            return false;
+        if (fuse_cols) {
+            launch_behz_extend_cols(env_, Z, src, n_items, xq, xb);
+        } else {
+            launch_behz_extend(env_, Z, src, n_items, xq, xb);
+            vq.base = xq; launch_cols_fwd(env_, vq, (u32)(n_items * 2));
+            vb.base = xb; launch_cols_fwd(env_, vb, (u32)(n_items * 2));
+        }
+    }
+    // the inverse column passes of nc products (three polynomials each) and steps (6)-(8) into `out`: again one kernel where it applies
+    void behz_inv_cols_floor(const BehzDev &Z, bool fuse_cols, u64 nc, u64 *dq, u64 *ds, u64 *out, PolyView vq, PolyView vb)
+    {
+        if (fuse_cols) {
+            launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out);
+        } else {
+            vq.base = dq; launch_cols_inv(env_, vq, (u32)(nc * 3));
+            vb.base = ds; launch_cols_inv(env_, vb, (u32)(nc * 3));
+            launch_behz_floor_sk(env_, Z, nc, dq, ds, out);
         }
     }
     void bfv_multiply3(int L, u64 n, const u64 *a, const u64 *b, Indexer3 ix, u64 *out)
@@ -1480,64 +1484,40 @@ public:
                 throw std::invalid_argument("he355_bfv_multiply: `out` overlaps an operand");
         }
         bool lists = (G == 1 || (n % ix.gs == 0 && ix.gs % ix.b1 == 0)) && n_cts <= n; // at least two times fewer extensions than the 2 n of the per-pair path
+        Arena &arena = arena_[kBfv];
         size_t c = std::min<size_t>(chunk_, (size_t)n);
         if (lists) {
-            while (!reserve_bfv_scratch((e_words + per_res * c) * 8) && c > 1) c = (c + 1) / 2;
-            lists = (e_words + per_res * c) * 8 <= bfv_bytes_; // else: the operand set does not fit beside one result -- per-pair path below
+            const size_t cl = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, (e_words + per_res * k) * 8); });
+            lists = cl != 0; // else: the operand set does not fit beside one result -- per-pair path below, from one result per chunk
+            c = lists ? cl : 1;
         }
         if (lists) {
             src.lists = 1;
-            u64 *eq = bfv_scratch_, *eb = eq + (size_t)n_cts * 2 * L * N, *dq = eb + (size_t)n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
-            if (fuse_cols) {
-                launch_behz_extend_cols(env_, Z, src, n_cts, eq, eb);
-            } else {
-                launch_behz_extend(env_, Z, src, n_cts, eq, eb);
-                vq.base = eq; launch_cols_fwd(env_, vq, (u32)(n_cts * 2));
-                vb.base = eb; launch_cols_fwd(env_, vb, (u32)(n_cts * 2));
-            }
+            u64 *eq = arena.p, *eb = eq + (size_t)n_cts * 2 * L * N, *dq = eb + (size_t)n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
+            behz_extend_fwd_cols(Z, src, fuse_cols, n_cts, eq, eb, vq, vb);
             vq.base = eq; launch_rows_fwd(env_, vq, (u32)(n_cts * 2));
             vb.base = eb; launch_rows_fwd(env_, vb, (u32)(n_cts * 2));
             for (u64 off = 0; off < n; off += c) {
                 const u64 nc = std::min<u64>(c, n - off);
                 launch_behz_tensor_inv(env_, Z, src, nc, off, eq, eb, dq, ds);
-                if (fuse_cols) {
-                    launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out + off * 3 * (size_t)L * N);
-                } else {
-                    vq.base = dq; launch_cols_inv(env_, vq, (u32)(nc * 3));
-                    vb.base = ds; launch_cols_inv(env_, vb, (u32)(nc * 3));
-                    launch_behz_floor_sk(env_, Z, nc, dq, ds, out + off * 3 * (size_t)L * N);
-                }
+                behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
             }
             HIPCHECK(hipGetLastError());
             return;
         }
         const size_t per_op = (4 * L + 4 * S) * N + per_res;
-        while (!reserve_bfv_scratch(per_op * c * 8)) { // as chunk_ops: halved until the arena is reserved
-            if (c == 1) throw OutOfDeviceMemory("HIP error: out of device memory: the BFV multiply scratch of one ciphertext does not fit");
-            c = (c + 1) / 2;
-        }
-        u64 *xq = bfv_scratch_, *xb = xq + c * 4 * L * N, *dq = xb + c * 4 * S * N, *ds = dq + c * 3 * L * N;
+        c = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, per_op * k * 8); });
+        if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the BFV multiply scratch of one ciphertext does not fit");
+        u64 *xq = arena.p, *xb = xq + c * 4 * L * N, *dq = xb + c * 4 * S * N, *ds = dq + c * 3 * L * N;
         for (u64 off = 0; off < n; off += c) {
             const u64 nc = std::min<u64>(c, n - off);
-            // extension to Bsk and forward column passes (one kernel where the fused shape applies), then per (op, residue, row) ONE
-            // kernel for the forward row pass of the four polynomials, the dyadic tensor and the inverse row pass of the three
-            // products (k_behz_rows_tensor), then the inverse column passes and steps (6)-(8) (again one kernel where it applies)
+            // extension to Bsk and forward column passes, then per (op, residue, row) ONE kernel for the forward row pass of the four
+            // polynomials, the dyadic tensor and the inverse row pass of the three products (k_behz_rows_tensor), then the inverse column
+            // passes and steps (6)-(8)
             src.op_offset = off;
-            if (fuse_cols) {
-                launch_behz_extend_cols(env_, Z, src, nc * 2, xq, xb);
-            } else {
-                launch_behz_extend(env_, Z, src, nc * 2, xq, xb);
-                vq.base = xq; launch_cols_fwd(env_, vq, (u32)(nc * 4));
-                vb.base = xb; launch_cols_fwd(env_, vb, (u32)(nc * 4));
-            }
+            behz_extend_fwd_cols(Z, src, fuse_cols, nc * 2, xq, xb, vq, vb);
             launch_behz_rows_tensor(env_, Z, nc, xq, xb, dq, ds);
-            if (fuse_cols) {
-                launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out + off * 3 * (size_t)L * N);
-            } else {
-                vq.base = dq; launch_cols_inv(env_, vq, (u32)(nc * 3));
-                vb.base = ds; launch_cols_inv(env_, vb, (u32)(nc * 3));
-                launch_behz_floor_sk(env_, Z, nc, dq, ds, out + off * 3 * (size_t)L * N);
-            }
+            behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
         }
         HIPCHECK(hipGetLastError());
     }
@@ -1555,21 +1535,17 @@ public:
     {
         use();
         const size_t bytes = 2 * P.K * P.N * 8;
-        if (!d_pk_) { dmalloc(d_pk_, bytes); owned_.push_back(d_pk_); }
-        HIPCHECK(hipMemcpy(d_pk_, h_pk, bytes, hipMemcpyHostToDevice));
+        if (!d_pk_) d_pk_ = upload_owned(h_pk, 2 * P.K * P.N);
+        else HIPCHECK(hipMemcpy(d_pk_, h_pk, bytes, hipMemcpyHostToDevice));
     }
     void set_secret_key(const u64 *h_sk) // [K][N], NTT form
     {
         use();
         const size_t bytes = P.K * P.N * 8;
-        if (!d_sk_) { dmalloc(d_sk_, bytes); owned_.push_back(d_sk_); }
-        HIPCHECK(hipMemcpy(d_sk_, h_sk, bytes, hipMemcpyHostToDevice));
+        if (!d_sk_) d_sk_ = upload_owned(h_sk, P.K * P.N);
+        else HIPCHECK(hipMemcpy(d_sk_, h_sk, bytes, hipMemcpyHostToDevice));
     }
-    u64 *client_scratch(size_t elems)
-    {
-        grow(client_scratch_, client_scratch_bytes_, elems * 8);
-        return client_scratch_;
-    }
+    u64 *client_scratch(size_t elems) { return reserve(arena_[kClient], elems * 8); }
     static PolyView poly_view(u64 *base, int polys_per_item, size_t N, int period)
     {
         if (polys_per_item > 64) throw std::invalid_argument("too many polynomials per item");
@@ -1632,25 +1608,13 @@ public:
     }
     // ---- BFV level operations (he355_kernels_bfv_level.hip) ---------------------------------------------------------------
     // the constants of Delta_L, cached per level as crt_tables(L) caches its own (host side: they travel as a kernel argument)
-    const BfvDeltaConst &bfv_delta(int L)
-    {
-        auto it = bfv_delta_.find(L);
-        if (it != bfv_delta_.end()) return it->second;
-        return bfv_delta_[L] = bfv_delta_const(env_.prime_q, L, P.plain_modulus);
-    }
+    const BfvDeltaConst &bfv_delta(int L) { return per_level(bfv_delta_, L, [&] { return bfv_delta_const(env_.prime_q, L, P.plain_modulus); }); }
     // q_j^-1 mod q_i, floor(q_j / 2) mod q_i for i < j < Ltop: one device table for every (L, L_to), built on first use
     const BfvDropConst *bfv_drop_table_dev()
     {
         if (d_bfv_drop_) return d_bfv_drop_;
         const std::vector<BfvDropConst> tab = bfv_drop_table(env_.prime_q, (int)P.Ltop, P.u64_fold);
-        dmalloc(d_bfv_drop_, tab.size() * sizeof(BfvDropConst));
-        owned_.push_back(d_bfv_drop_);
-        HIPCHECK(hipMemcpy(d_bfv_drop_, tab.data(), tab.size() * sizeof(BfvDropConst), hipMemcpyHostToDevice));
-        return d_bfv_drop_;
-    }
-    void require_bfv(const char *what) const
-    {
-        if (P.scheme != kSchemeBFV) throw std::invalid_argument(std::string(what) + " needs a BFV context");
+        return d_bfv_drop_ = upload_owned(tab.data(), tab.size());
     }
     // the ciphertexts / plaintexts a batch of n results reads: [lo, hi] of the indexer's operand 0 / operand 1
     static void indexer_span(const Indexer &ix, u64 n, u64 &a_lo, u64 &a_n, u64 &b_lo, u64 &b_n)
@@ -1663,9 +1627,8 @@ public:
     {
         use();
         check_level(L);
-        require_bfv("he355_bfv_mod_switch");
         if (L_to < 1 || L_to > L) throw std::invalid_argument("target level out of range");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (L > kBfvLevelMaxL) throw std::invalid_argument("BFV modulus switching supports up to 16 data primes");
         const size_t N = P.N, n_polys = (size_t)n * size;
         if (ranges_overlap(in, n_polys * L * N, out, n_polys * L_to * N)) throw std::invalid_argument("he355_bfv_mod_switch: `out` overlaps `in`");
@@ -1682,8 +1645,7 @@ public:
     {
         use();
         check_level(L);
-        require_bfv(sub ? "he355_bfv_sub_plain" : "he355_bfv_add_plain");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (!n) return;
         const size_t N = P.N, ctn = (size_t)size * L * N;
         u64 a_lo, a_n, b_lo, b_n;
@@ -1703,16 +1665,15 @@ public:
     {
         use();
         check_level(L);
-        require_bfv("he355_bfv_multiply_plain");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (!n) return;
         const size_t N = P.N, LN = (size_t)L * N, ctn = (size_t)size * LN;
         u64 a_lo, a_n, b_lo, b_n;
         indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
         if (ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn) || ranges_overlap(out, n * ctn, plain + b_lo * N, b_n * N))
             throw std::invalid_argument("he355_bfv_multiply_plain: `out` overlaps an operand");
-        if (!reserve_bfv_scratch(b_n * LN * 8)) throw OutOfDeviceMemory("HIP error: out of device memory: the prepared plaintexts of he355_bfv_multiply_plain do not fit");
-        u64 *prep = bfv_scratch_;
+        if (!try_reserve(&arena_[kBfv], 1, b_n * LN * 8)) throw OutOfDeviceMemory("HIP error: out of device memory: the prepared plaintexts of he355_bfv_multiply_plain do not fit");
+        u64 *prep = arena_[kBfv].p;
         launch_bfv_lift_plain(env_, L, b_n, plain + b_lo * N, prep, P.plain_modulus);
         launch_ntt_forward(env_, poly_view(prep, L, N, L), (u32)b_n);
         for_each_chunk(n, L, chunk_ops(n, L, true), true, [&](u64 off, u64 nc, int which, const Scratch &, hipEvent_t fork) {
@@ -1732,8 +1693,7 @@ public:
         const char *what = inverse ? "he355_bfv_transform_from_ntt" : "he355_bfv_transform_to_ntt";
         use();
         check_level(L);
-        require_bfv(what);
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         const size_t N = P.N, words = (size_t)n * size * L * N;
         if (out != in && ranges_overlap(in, words, out, words)) throw std::invalid_argument(std::string(what) + ": `out` overlaps `in` (in place: the same pointer)");
         if (n * size > 0xffffffffull) throw std::invalid_argument(std::string(what) + ": too many polynomials for one call");
@@ -1750,7 +1710,6 @@ public:
     {
         use();
         check_level(L);
-        require_bfv("he355_bfv_plain_to_ntt");
         const size_t N = P.N;
         if (ranges_overlap(out, (size_t)n * L * N, plain, (size_t)n * N)) throw std::invalid_argument("he355_bfv_plain_to_ntt: `out` overlaps the plaintexts");
         if (n > 0xffffffffull) throw std::invalid_argument("he355_bfv_plain_to_ntt: too many plaintexts for one call");
@@ -1764,8 +1723,7 @@ public:
     {
         use();
         check_level(L);
-        require_bfv("he355_bfv_multiply_plain_ntt");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (!n) return;
         const size_t LN = (size_t)L * P.N, ctn = (size_t)size * LN;
         u64 a_lo, a_n, b_lo, b_n;
@@ -1784,8 +1742,7 @@ public:
     {
         use();
         check_level(L);
-        require_bfv("he355_bfv_multiply_plain_accumulate");
-        if (size < 1 || size > 3) throw std::invalid_argument("ciphertext size must be 1..3");
+        check_size(size, 1, 3);
         if (inner < 1 || inner > 0x7fffffff) throw std::invalid_argument("inner dimension out of range");
         const u64 n = rows * cols;
         if (!n) return;
@@ -1798,37 +1755,33 @@ public:
     }
     const CrtTablesDev &crt_tables(int L)
     {
-        auto it = crt_.find(L);
-        if (it != crt_.end()) return it->second;
-        const int words = L + 2;
-        std::vector<u64> Q(words, 0), halfQ(words, 0), punct((size_t)L * words, 0), inv(L);
-        Q[0] = 1;
-        for (int i = 0; i < L; ++i) client::mw_mul_small(Q.data(), words, P.primes[i].q);
-        for (int i = 0; i < words; ++i) halfQ[i] = (Q[i] >> 1) | (i + 1 < words ? Q[i + 1] << 63 : 0);
-        for (int i = 0; i < L; ++i) {
-            u64 *p = punct.data() + (size_t)i * words;
-            p[0] = 1;
-            u64 pm = 1;
-            const u64 qi = P.primes[i].q;
-            for (int k = 0; k < L; ++k)
-                if (k != i) {
-                    client::mw_mul_small(p, words, P.primes[k].q);
-                    pm = (u64)(((u128)pm * (P.primes[k].q % qi)) % qi);
-                }
-            inv[i] = Params::invmod(pm, qi);
-        }
-        u64 *d = nullptr;
-        const size_t tot = (size_t)words * 2 + (size_t)L * words + L;
-        dmalloc(d, tot * 8);
-        owned_.push_back(d);
-        HIPCHECK(hipMemcpy(d, Q.data(), words * 8, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(d + words, halfQ.data(), words * 8, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(d + 2 * words, punct.data(), punct.size() * 8, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(d + 2 * words + punct.size(), inv.data(), L * 8, hipMemcpyHostToDevice));
-        CrtTablesDev t;
-        t.L = L; t.words = words; t.Q = d; t.halfQ = d + words; t.punct = d + 2 * words; t.inv = d + 2 * words + punct.size();
-        t.Qd = client::mw_to_double(Q.data(), words); t.t = P.plain_modulus;
-        return crt_[L] = t;
+        return per_level(crt_, L, [&] {
+            // one block: Q | floor(Q / 2) | the L punctured products (`words` words each) | their inverses mod q_i
+            const int words = L + 2;
+            const size_t o_half = words, o_punct = 2 * (size_t)words, o_inv = o_punct + (size_t)L * words;
+            std::vector<u64> h(o_inv + L, 0);
+            u64 *Q = h.data(), *halfQ = Q + o_half;
+            Q[0] = 1;
+            for (int i = 0; i < L; ++i) client::mw_mul_small(Q, words, P.primes[i].q);
+            for (int i = 0; i < words; ++i) halfQ[i] = (Q[i] >> 1) | (i + 1 < words ? Q[i + 1] << 63 : 0);
+            for (int i = 0; i < L; ++i) {
+                u64 *p = h.data() + o_punct + (size_t)i * words;
+                p[0] = 1;
+                u64 pm = 1;
+                const u64 qi = P.primes[i].q;
+                for (int k = 0; k < L; ++k)
+                    if (k != i) {
+                        client::mw_mul_small(p, words, P.primes[k].q);
+                        pm = (u64)(((u128)pm * (P.primes[k].q % qi)) % qi);
+                    }
+                h[o_inv + i] = Params::invmod(pm, qi);
+            }
+            const u64 *d = upload_owned(h.data(), h.size());
+            CrtTablesDev t;
+            t.L = L; t.words = words; t.Q = d; t.halfQ = d + o_half; t.punct = d + o_punct; t.inv = d + o_inv;
+            t.Qd = client::mw_to_double(Q, words); t.t = P.plain_modulus;
+            return t;
+        });
     }
     // Decryptor::decrypt of n size-`size` ciphertexts at level L: CKKS -> [n][L][N] NTT-form plaintext (the phase);
     // BFV -> [n][N] coefficients mod t
@@ -1837,7 +1790,7 @@ public:
         use();
         check_level(L);
         if (!d_sk_) throw std::invalid_argument("secret key not set");
-        if (size < 2 || size > 3) throw std::invalid_argument("ciphertext size must be 2 or 3");
+        check_size(size, 2, 3);
         const size_t N = P.N;
         if (P.scheme == kSchemeCKKS) {
             launch_dot_sk(env_, L, size, n, ct, d_sk_, out);
@@ -1863,12 +1816,7 @@ public:
     // inverse transform, then k_bfv_noise_bits adds c0 in coefficient form -- one forward transform and one slab copy less per ciphertext
     // than decrypt() spends on the same phase -- and gathers the per-ciphertext maximum in `budget`, which k_bfv_noise_finish turns into
     // the budget in place.  Everything on stream_, like decrypt().
-    const BfvNoiseConst &bfv_noise(int L)
-    {
-        auto it = bfv_noise_.find(L);
-        if (it != bfv_noise_.end()) return it->second;
-        return bfv_noise_[L] = bfv_noise_const(env_.prime_q, L, P.plain_modulus);
-    }
+    const BfvNoiseConst &bfv_noise(int L) { return per_level(bfv_noise_, L, [&] { return bfv_noise_const(env_.prime_q, L, P.plain_modulus); }); }
     // Ciphertexts per chunk: 2^21 coefficients' worth (64 at N = 32768, as decrypt(); 256 at N = 8192), at most 1024 -- 64 ciphertexts of a
     // small ring are one wave per SIMD for k_bfv_noise_bits, which then waits on its own dependent instructions (profiles/bfv_noise.txt) --
     // and never more than the batch chunk (he355_set_chunk), so a test can cut a small batch.
@@ -1880,10 +1828,9 @@ public:
     void bfv_noise_budget(int L, int size, u64 n, const u64 *ct, int32_t *budget, int32_t *noise_bits)
     {
         use();
-        require_bfv("he355_bfv_noise_budget");
         check_level(L);
         if (L > kBfvNoiseMaxL) throw std::invalid_argument("the BFV noise budget supports up to 16 data primes");
-        if (size < 2 || size > 3) throw std::invalid_argument("ciphertext size must be 2 or 3");
+        check_size(size, 2, 3);
         if (!d_sk_) throw std::invalid_argument("secret key not set");
         if (!n) return;
         if (!ct || !budget) throw std::invalid_argument("he355_bfv_noise_budget: null ciphertexts or null budget output");
@@ -1911,22 +1858,15 @@ public:
         if (enc_.slot_index) return enc_;
         std::vector<uint32_t> si;
         client::build_slot_index(P.N, si);
-        uint32_t *dsi = nullptr;
-        dmalloc(dsi, P.N * 4);
-        owned_.push_back(dsi);
-        HIPCHECK(hipMemcpy(dsi, si.data(), P.N * 4, hipMemcpyHostToDevice));
-        enc_.slot_index = dsi;
+        enc_.slot_index = upload_owned(si.data(), P.N);
         if (P.scheme == kSchemeCKKS) {
             std::vector<client::Cplx> W, Z;
             client::build_ckks_tables(P.N, W, Z);
-            client::Cplx *dw = nullptr;
-            dmalloc(dw, 2 * P.N * sizeof(client::Cplx));
-            owned_.push_back(dw);
-            HIPCHECK(hipMemcpy(dw, W.data(), P.N * sizeof(client::Cplx), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(dw + P.N, Z.data(), P.N * sizeof(client::Cplx), hipMemcpyHostToDevice));
+            W.insert(W.end(), Z.begin(), Z.begin() + P.N); // one block: W | Z
+            const client::Cplx *dw = upload_owned(W.data(), 2 * P.N);
             enc_.W = dw; enc_.Z = dw + P.N;
         }
-        if (!d_err_) { dmalloc(d_err_, sizeof(int)); owned_.push_back(d_err_); }
+        if (!d_err_) d_err_ = upload_owned<int>(nullptr, 1);
         return enc_;
     }
     // CKKSEncoder::encode: values [n][count] (count <= N/2) at `scale` -> [n][Ltop][N] NTT-form plaintexts
@@ -2072,7 +2012,7 @@ public:
         use();
         if (duration_us == 0 || duration_us > 10000000) throw std::invalid_argument("clock probe duration must be in (0, 10 s]");
         if (!probe_stream_) HIPCHECK(hipStreamCreateWithFlags(&probe_stream_, hipStreamNonBlocking));
-        if (!d_clock_) dmalloc(d_clock_, 2 * sizeof(u64));
+        if (!d_clock_) d_clock_ = upload_owned<u64>(nullptr, 2);
         HIPCHECK(hipMemsetAsync(d_clock_, 0, 2 * sizeof(u64), probe_stream_));
         hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, probe_stream_, duration_us * 100, d_clock_);
         HIPCHECK(hipGetLastError());
@@ -2096,8 +2036,6 @@ private:
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     KernelEnv env_{};
     PrimeDev *d_primes_ = nullptr;
-    u64 *lat_part_[2] = {nullptr, nullptr}; // partial sums of the digit-split K3 (latency shape), one per stream
-    size_t lat_part_bytes_[2] = {0, 0};
     u64 lat_max_ = 0;              // largest batch that takes the latency shape once set (HE355_LATENCY_MAX; 0: never) ...
     bool lat_auto_ = true;         // ... until then lat_limit()'s rule
     FloorConst *d_floor_ = nullptr;
@@ -2111,34 +2049,25 @@ private:
     int *d_err_ = nullptr;
     u64 *d_pk_ = nullptr, *d_sk_ = nullptr;
     u64 zero_seed_ = os_seed(), zero_index_ = 0;
-    u64 *client_scratch_ = nullptr;
-    size_t client_scratch_bytes_ = 0;
     std::map<int, CrtTablesDev> crt_;
     std::map<int, BfvDeltaConst> bfv_delta_; // Delta_L constants per level (bfv_level_core.h)
     std::map<int, BfvNoiseConst> bfv_noise_; // t-folded CRT constants and bits(q_L) per level (bfv_noise_core.h)
     BfvDropConst *d_bfv_drop_ = nullptr;     // [Ltop][Ltop] drop-chain constants (owned_)
     std::map<uint32_t, u64 *> d_galois_;
-    std::map<uint32_t, uint32_t *> d_perm_;
-    u64 *scratch_ = nullptr, *scratch2_ = nullptr;
-    size_t scratch_bytes_ = 0, scratch2_bytes_ = 0;
+    std::map<uint32_t, const uint32_t *> d_perm_, d_gather_; // NTT-domain permutations / coefficient-form gathers per Galois element (owned_)
+    Arena arena_[kArenas];
     hipStream_t stream2_ = nullptr;
     hipStream_t probe_stream_ = nullptr; // clock_probe_begin's own stream
-    u64 *d_clock_ = nullptr;
+    u64 *d_clock_ = nullptr; // (owned_)
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     bool dual_stream_ = true;
-    u64 *rot_tmp_ = nullptr;
-    size_t rot_tmp_bytes_ = 0;
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
     he355_path_stats_t paths_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
     u64 lds_max_ = 0;
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
-    unsigned char *d_groups_ = nullptr; // group tables of the grouped key switches (upload_groups)
-    size_t groups_bytes_ = 0, groups_next_ = 0;
-    u64 *bfv_scratch_ = nullptr;
-    size_t bfv_bytes_ = 0;
+    size_t groups_next_ = 0; // upload_groups: the next free byte of the kGroups ring
     std::map<int, BehzDev> behz_;
-    std::map<uint32_t, uint32_t *> d_gather_;
     size_t chunk_ = 1024;
     DevicePool pool_;
 };

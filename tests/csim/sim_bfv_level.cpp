@@ -1,7 +1,7 @@
 // sim_bfv_level.cpp -- TEST-ONLY.  Runs the product's per-coefficient BFV level arithmetic (csrc/bfv_level_core.h: the very functions the
 // HIP kernels k_bfv_mod_switch, k_bfv_addsub_plain and k_bfv_lift_plain compile) on the CPU, on the tables the product uploads
 // (bfv_drop_table, bfv_delta_const), so that tests/test_bfv_level_core_cpu.py can hold them to Python integers without a GPU.
-// Compiled once per form of the u64 engine into tests/csim_bfv/_build; the product never contains it.
+// Compiled once per form of the u64 engine into tests/csim/_build; the product never contains it.
 #include <cstring>
 #include <map>
 #include <stdexcept>

@@ -2,7 +2,7 @@
 // (csrc/bfv_mac_core.h: the very functions the HIP kernel k_bfv_plain_mac compiles -- the 128-bit multiply-add, the run-length rule, the
 // reduction -- and the loop that cuts a sum into runs) on the CPU, with the Barrett constants the product builds (Params), so that
 // tests/test_bfv_mac_core_cpu.py can hold it to Python integers without a GPU.  The arithmetic does not depend on the form of the u64
-// engine: one library.  Built into tests/csim_bfv_mac/_build; the product never contains it.
+// engine: the tests load the Shoup library.  Built into tests/csim/_build; the product never contains it.
 #include <stdexcept>
 #include <vector>
 

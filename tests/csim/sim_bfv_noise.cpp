@@ -1,7 +1,7 @@
 // sim_bfv_noise.cpp -- TEST-ONLY.  Runs the product's per-coefficient noise-budget arithmetic (csrc/bfv_noise_core.h: the very function
 // the HIP kernel k_bfv_noise_bits<W> compiles) on the CPU, on the tables the product builds (bfv_noise_const, bfv_noise_host_tables), and
 // the host client's whole chain (Client::invariant_noise_budget), so that tests/test_bfv_noise_core_cpu.py can hold both to Python
-// integers without a GPU.  Compiled once per form of the u64 engine into tests/csim_bfv_noise/_build; the product never contains it.
+// integers without a GPU.  Compiled once per form of the u64 engine into tests/csim/_build; the product never contains it.
 #include <cstring>
 #include <map>
 #include <stdexcept>

@@ -9,14 +9,13 @@ compile -- on the constants the product uploads, Params::behz_host) against exac
   behz_base_suffices) are inside the tested range.
 No GPU, no oracle: the expected values are Python integers."""
 import ctypes as C
-import os
 import random
-import subprocess
 from fractions import Fraction
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import csim_lib
+
 PARAMS = [
     (8192, [60, 40, 60], 20),              # <4, 6> instantiation, L = 2 = nB
     (8192, [60, 40, 40, 60], 20),
@@ -30,8 +29,7 @@ PARAMS = [
 
 @pytest.fixture(scope="module")
 def sim():
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim"), "-s"], check=True)
-    L = C.CDLL(os.path.join(HERE, "csim", "_build", "libcsim.so"))
+    L = csim_lib.load()
     u64p = C.POINTER(C.c_uint64)
     L.sim_behz_create.restype = C.c_void_p
     L.sim_behz_create.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int]

@@ -1,4 +1,4 @@
-"""The product's per-coefficient BFV level arithmetic on the CPU (tests/csim_bfv/sim_bfv_level.cpp runs csrc/bfv_level_core.h -- the
+"""The product's per-coefficient BFV level arithmetic on the CPU (tests/csim/sim_bfv_level.cpp runs csrc/bfv_level_core.h -- the
 functions the HIP kernels k_bfv_mod_switch, k_bfv_addsub_plain and k_bfv_lift_plain compile -- on the tables the product uploads)
 against Python integers and the oracle, in both forms of the u64 engine:
 
@@ -13,10 +13,11 @@ import ctypes as C
 import importlib
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
+
+import csim_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -29,16 +30,14 @@ CHAINS = [
     (1024, [60, 40, 45, 50, 55, 60, 40, 45, 50, 55, 60, 40, 45, 50, 55, 59, 60], 20, False),  # 16 data primes, both engines, any order
     (1024, [60, 40, 60, 46, 60, 40, 60, 44, 60, 40, 60, 46, 60, 42, 60, 40, 60], 20, True),   # 16 data primes a fold context holds
 ]
-FORMS = ["libcsim_bfv.so", "libcsim_bfv_fold.so"]
 
 
 @pytest.fixture(scope="module")
 def sims():
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim_bfv"), "-s"], check=True)
     out = []
     u64p = C.POINTER(C.c_uint64)
-    for name in FORMS:
-        L = C.CDLL(os.path.join(HERE, "csim_bfv", "_build", name))
+    for fold in (False, True):
+        L = csim_lib.load(fold)
         L.sim_bfvl_create.restype = C.c_void_p
         L.sim_bfvl_create.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int]
         L.sim_bfvl_destroy.argtypes = [C.c_void_p]

@@ -1,4 +1,4 @@
-"""The arithmetic of the NTT-form BFV plaintext inner product on the CPU (tests/csim_bfv_mac/sim_bfv_mac.cpp runs csrc/bfv_mac_core.h --
+"""The arithmetic of the NTT-form BFV plaintext inner product on the CPU (tests/csim/sim_bfv_mac.cpp runs csrc/bfv_mac_core.h --
 the 128-bit multiply-add, the run-length rule, the reduction and the loop that cuts a sum into runs, the functions the HIP kernel
 k_bfv_plain_mac compiles -- with the Barrett constants the product builds) against Python integers:
 
@@ -13,10 +13,11 @@ import ctypes as C
 import importlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import csim_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -34,8 +35,7 @@ u64p = C.POINTER(C.c_uint64)
 
 @pytest.fixture(scope="module")
 def sim():
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim_bfv_mac"), "-s"], check=True)
-    L = C.CDLL(os.path.join(HERE, "csim_bfv_mac", "_build", "libcsim_bfv_mac.so"))
+    L = csim_lib.load()  # (the Shoup library: the arithmetic does not depend on the form)
     L.sim_bfvmac_create.restype = C.c_void_p
     L.sim_bfvmac_create.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int]
     L.sim_bfvmac_destroy.argtypes = [C.c_void_p]

@@ -1,5 +1,5 @@
 """The product's BFV invariant noise budget on the CPU, exact against Python integers (tests/bfv_noise_model.py), in both forms of the u64
-engine (tests/csim_bfv_noise/sim_bfv_noise.cpp compiles csrc/bfv_noise_core.h -- the function the HIP kernel k_bfv_noise_bits<W>
+engine (tests/csim/sim_bfv_noise.cpp compiles csrc/bfv_noise_core.h -- the function the HIP kernel k_bfv_noise_bits<W>
 compiles -- and the host client):
 
 * bfv_noise_bits<W> for every level of five chains (W = 3..18): uniform residues, and engineered coefficients whose composed value is
@@ -12,12 +12,12 @@ import ctypes as C
 import importlib
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import bfv_noise_model as model
+import csim_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -37,17 +37,15 @@ CLIENT_CHAINS = [
     (8192, [60, 40, 40, 60], 20, True),
     (1024, CHAINS[3][1], 20, False),
 ]
-FORMS = ["libcsim_bfv_noise.so", "libcsim_bfv_noise_fold.so"]
 IDS = lambda v: "-".join(map(str, v)) if isinstance(v, list) else str(v)
 
 
 @pytest.fixture(scope="module")
 def sims():
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim_bfv_noise"), "-s"], check=True)
     out = []
     vp, u64p, i32p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)
-    for name in FORMS:
-        L = C.CDLL(os.path.join(HERE, "csim_bfv_noise", "_build", name))
+    for fold in (False, True):
+        L = csim_lib.load(fold)
         L.sim_bfvn_create.restype = vp
         L.sim_bfvn_create.argtypes = [C.c_size_t, i32p, C.c_size_t, C.c_int, C.c_uint64]
         L.sim_bfvn_destroy.argtypes = [vp]

@@ -1,19 +1,16 @@
 """Client-side host code of the product (keys, encoders, encrypt/decrypt) cross-checked with the oracle on the CPU:
 keys and ciphertexts are SEAL-layout arrays, so each side must be able to consume the other's."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import csim_lib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim"), "-s"], check=True)
-    L = C.CDLL(os.path.join(HERE, "csim", "_build", "libcsim.so"))
+    L = csim_lib.load()
     vp, u64p = C.c_void_p, C.POINTER(C.c_uint64)
     L.sim_params_create.restype = vp
     L.sim_params_create.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.c_int]

@@ -9,75 +9,18 @@
 * semantic    : Dec(mod_switch_to(L')(Enc(x) (.) p + r)) = x p + r mod t slot-wise at every level, with real keys, by the oracle's decryption
                 and by he355_decrypt + he355_bfv_decode;
 * no raw hipMalloc in a second call."""
-import importlib
-
 import numpy as np
 import pytest
 
+from bfv_gpu_helpers import ALL, SENT, be, lift, pair, plains, rand_cts, refused  # noqa: F401 (be: the fixture)
+
 pytestmark = pytest.mark.gpu
-
-CONFIGS = {
-    # the CONFIGS of tests/test_gpu_parity_bfv.py
-    "n1024": (1024, [50, 40, 50], 20),
-    "n4096_d3": (4096, [60, 40, 40, 60], 20),
-    "n8192_default": (8192, [60, 40, 60], 20),
-    "n32768_d3": (32768, [60, 40, 40, 60], 20),
-}
-
-
-def random_chain(seed):
-    """the draw of test_gpu_parity_bfv.py::test_bfv_random_parameter_chains"""
-    rng = np.random.default_rng(5000 + seed)
-    N = int(rng.choice([1024, 2048, 4096]))
-    K = int(rng.integers(2, 6))
-    bits = [int(b) for b in rng.integers(35, 61, K)]
-    return N, bits, int(rng.integers(16, 23))
-
-
-ALL = dict(CONFIGS)
-for _s in (0, 3, 4):
-    ALL[f"random{_s}"] = random_chain(_s)
-
-
-@pytest.fixture(scope="module")
-def be():
-    mod = importlib.import_module("reference-seal-backend_amd")
-    if mod.device_count() < 1:
-        pytest.fail("no HIP device")
-    return mod
-
-
-def pair(be, oracle, name):
-    N, bits, pb = ALL[name]
-    g = be.Context(be.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False, device=0)
-    o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False)
-    assert g.moduli == o.moduli and g.t == o.t
-    return g, o, N
-
-
-def rand_cts(o, rng, n, L, size=2):
-    return np.stack([o.random_poly(rng, L, size) for _ in range(n)])
 
 
 def switch_to(o, ct, L_to):
     while ct.shape[1] > L_to:
         ct = o.mod_switch_coeff(ct)
     return ct
-
-
-def plains(o, rng, n, N):
-    """n plaintexts mod t: a monomial, zero, -X^k, then full-range ones"""
-    t = o.t
-    m = rng.integers(0, t, (n, N), dtype=np.uint64)
-    if n > 0:
-        m[0] = 0
-        m[0, 5] = 1
-    if n > 1:
-        m[1] = 0
-    if n > 3:
-        m[3] = 0
-        m[3, N - 1] = t - 1
-    return m
 
 
 def delta(o, m, L):
@@ -98,12 +41,6 @@ def addsub(o, a, b, sub):
     for i in range(a.shape[1]):
         out[:, i] = ((a[:, i].astype(object) - b[:, i].astype(object)) % o.moduli[i]).astype(np.uint64)
     return out
-
-
-def lift(o, m, L):
-    t = o.t
-    c = np.where(m < np.uint64((t + 1) // 2), m.astype(object), m.astype(object) - t)
-    return [(c % q).astype(np.uint64) for q in o.moduli[:L]]
 
 
 def mul_plain_transform(o, ct, m):
@@ -133,18 +70,9 @@ def schoolbook(c, lm, q, js):
     return out
 
 
-def refused(be, f):
-    with pytest.raises(be.HE355Error) as ei:
-        f()
-    assert ei.value.code == be.E_INVALID_ARGS, ei.value
-
-
-SENT = np.uint64(0x5E17155E17155E17)
-
-
 @pytest.mark.parametrize("name", list(ALL))
 def test_mod_switch_every_level_pair(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(11)
     Ltop = g.L
     for L in range(1, Ltop + 1):
@@ -187,7 +115,7 @@ def test_mod_switch_every_level_pair(be, oracle, name):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_add_sub_plain(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(12)
     for L in range(1, g.L + 1):
         for size in (2, 3):
@@ -235,7 +163,7 @@ def test_add_sub_plain(be, oracle, name):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_multiply_plain(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(13)
     g.set_dual_stream(True)
     for L in range(1, g.L + 1):
@@ -290,7 +218,7 @@ def test_multiply_plain(be, oracle, name):
 def test_async_producer_then_each_op(be, oracle, name):
     """The operand is still being written by he355_add (asynchronous, first stream) when each op is issued; the batch is cut in chunks of 3
     that alternate over both streams, so the second stream has to be ordered behind the producer."""
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(14)
     L, size, n = g.L, 2, 8
     g.set_dual_stream(True)
@@ -366,7 +294,7 @@ def test_semantic_multiply_add_switch_decrypt(be, oracle, N, bits):
 
 
 def test_second_call_makes_no_raw_allocation(be, oracle):
-    g, o, N = pair(be, oracle, "n8192_default")
+    g, o, N, *_ = pair(be, oracle, "n8192_default")
     rng = np.random.default_rng(15)
     L, n = g.L, 8
     g.set_chunk(3)

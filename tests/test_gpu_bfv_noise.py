@@ -9,12 +9,13 @@ d_noise_bits, no tolerance:
 * a ciphertext squared until its budget is 0;
 * ordering behind an asynchronous producer, d_noise_bits = NULL, n = 0, every argument error, no raw hipMalloc in a second call."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
+import bfv_gpu_helpers as helpers
 import bfv_noise_model as model
+from bfv_gpu_helpers import be, refused  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,51 +26,9 @@ def chunk_of(N):
     return min(1024, max(64, (1 << 21) // N))
 
 
-CONFIGS = {
-    # the CONFIGS of tests/test_gpu_bfv_levels.py
-    "n1024": (1024, [50, 40, 50], 20),            # the Shoup form of the u64 engine (50-bit primes are not 2^60 - c)
-    "n4096_d3": (4096, [60, 40, 40, 60], 20),     # the fold form
-    "n8192_default": (8192, [60, 40, 60], 20),
-    "n32768_d3": (32768, [60, 40, 40, 60], 20),
-}
-
-
-def random_chain(seed):
-    """the draw of test_gpu_parity_bfv.py::test_bfv_random_parameter_chains"""
-    rng = np.random.default_rng(5000 + seed)
-    N = int(rng.choice([1024, 2048, 4096]))
-    K = int(rng.integers(2, 6))
-    bits = [int(b) for b in rng.integers(35, 61, K)]
-    return N, bits, int(rng.integers(16, 23))
-
-
-ALL = dict(CONFIGS)
-for _s in (0, 3, 4):
-    ALL[f"random{_s}"] = random_chain(_s)
+ALL = dict(helpers.ALL)
 # 16 data primes, both engines, any order (the first chain of 17 in tests/test_bfv_level_core_cpu.py)
 ALL["n1024_16primes"] = (1024, [60, 40, 45, 50, 55, 60, 40, 45, 50, 55, 60, 40, 45, 50, 55, 59, 60], 20)
-
-
-@pytest.fixture(scope="module")
-def be():
-    mod = importlib.import_module("reference-seal-backend_amd")
-    if mod.device_count() < 1:
-        pytest.fail("no HIP device")
-    return mod
-
-
-def pair(be, oracle, name, keys=True):
-    N, bits, pb = ALL[name]
-    g = be.Context(be.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False, device=0)
-    o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False)
-    assert g.moduli == o.moduli and g.t == o.t
-    sk = pk = None
-    if keys:
-        sk = o.keygen_secret(21)
-        pk = o.keygen_public(sk, 22)
-        g.set_secret_key(sk)
-        g.set_public_key(pk)
-    return g, o, N, sk, pk
 
 
 def want_of(o, cts, sk):
@@ -90,17 +49,10 @@ def check(g, o, sk, L, size, dbuf, host, tag):
     return wb, wn
 
 
-def refused(be, f):
-    with pytest.raises(be.HE355Error) as ei:
-        f()
-    assert ei.value.code == be.E_INVALID_ARGS, ei.value
-    assert len(str(ei.value)) > len("he355 error 1: "), "a message goes with the code"
-
-
 @pytest.mark.parametrize("name", list(ALL))
 def test_uniform_random_ciphertexts(be, oracle, name):
     """a uniform phase: every word of the composition is exercised, the budget is 0"""
-    g, o, N, sk, _ = pair(be, oracle, name)
+    g, o, N, sk, _ = helpers.pair(be, oracle, ALL[name], keys=True)
     rng = np.random.default_rng(31)
     big = chunk_of(N) + 6
     for L in range(1, g.L + 1):
@@ -131,7 +83,7 @@ def test_uniform_random_ciphertexts(be, oracle, name):
 def test_engineered_edge_values(be, oracle, name):
     """c1 = 0, so the phase is c0: one coefficient of c0 holds the residues of x t^-1 mod q_L for an edge value x, the rest are zero; one
     edge per ciphertext, so neighbours of a batch have norms from 0 bits to bits(q_L) - 1 and a leak across ciphertexts would show"""
-    g, o, N, sk, _ = pair(be, oracle, name)
+    g, o, N, sk, _ = helpers.pair(be, oracle, ALL[name], keys=True)
     t = o.t
     for L in range(1, g.L + 1):
         qs = o.moduli[:L]
@@ -171,7 +123,7 @@ def slots_of(g, L, size, n, dbuf, N):
 
 @pytest.mark.parametrize("name", ["n1024", "n4096_d3", "n8192_default", "n1024_16primes"])
 def test_device_pipeline_real_keys(be, oracle, name):
-    g, o, N, sk, pk = pair(be, oracle, name)
+    g, o, N, sk, pk = helpers.pair(be, oracle, ALL[name], keys=True)
     t, L = o.t, g.L
     codec = oracle.BatchCodec(N, t)
     rng = np.random.default_rng(41)
@@ -231,7 +183,7 @@ def test_device_pipeline_real_keys(be, oracle, name):
 
 @pytest.mark.parametrize("name", ["n4096_d3", "n1024"])
 def test_squared_until_no_budget(be, oracle, name):
-    g, o, N, sk, pk = pair(be, oracle, name)
+    g, o, N, sk, pk = helpers.pair(be, oracle, ALL[name], keys=True)
     t, L = o.t, g.L
     codec = oracle.BatchCodec(N, t)
     rng = np.random.default_rng(43)
@@ -256,7 +208,7 @@ def test_squared_until_no_budget(be, oracle, name):
 @pytest.mark.parametrize("name", ["n8192_default", "n1024"])
 def test_budget_right_behind_an_asynchronous_multiply(be, oracle, name):
     """he355_bfv_multiply returns with its kernels queued (the batch cut in chunks of 3 over both streams); the budget is asked at once"""
-    g, o, N, sk, pk = pair(be, oracle, name)
+    g, o, N, sk, pk = helpers.pair(be, oracle, ALL[name], keys=True)
     t, L, n = o.t, g.L, 8
     codec = oracle.BatchCodec(N, t)
     rng = np.random.default_rng(44)
@@ -280,7 +232,7 @@ def test_budget_right_behind_an_asynchronous_multiply(be, oracle, name):
 
 
 def test_arguments(be, oracle):
-    g, o, N, sk, pk = pair(be, oracle, "n4096_d3", keys=False)
+    g, o, N, sk, pk = helpers.pair(be, oracle, "n4096_d3")
     L, n = g.L, 3
     rng = np.random.default_rng(45)
     cts = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
@@ -326,7 +278,7 @@ def test_arguments(be, oracle):
 
 
 def test_second_call_makes_no_raw_allocation(be, oracle):
-    g, o, N, sk, pk = pair(be, oracle, "n8192_default")
+    g, o, N, sk, pk = helpers.pair(be, oracle, "n8192_default", keys=True)
     rng = np.random.default_rng(46)
     L, n = g.L, chunk_of(N) + 6
     base = np.stack([o.random_poly(rng, L, 3) for _ in range(4)])

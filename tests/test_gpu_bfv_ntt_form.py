@@ -16,24 +16,15 @@ transforms and Python integers, on the CONFIGS and the three random chains of te
 * refusals    : overlaps, inner == 0, size 0 or 4, L out of range: HE355_E_INVALID_ARGS and the outputs untouched;
 * no raw hipMalloc / hipFree in a second call."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 
-from test_gpu_bfv_levels import ALL, SENT, lift, pair, plains, rand_cts, refused
+from bfv_gpu_helpers import ALL, SENT, be, lift, pair, plains, rand_cts, refused  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (1, 1, 7), (3, 2, 5), (1, 5, 16), (5, 1, 16)]
-
-
-@pytest.fixture(scope="module")
-def be():
-    mod = importlib.import_module("reference-seal-backend_amd")
-    if mod.device_count() < 1:
-        pytest.fail("no HIP device")
-    return mod
 
 
 class At:
@@ -98,7 +89,7 @@ def edged_cts(o, rng, n, L, size):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_transforms(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(21)
     for L in range(1, g.L + 1):
         for size in (1, 2, 3):
@@ -141,7 +132,7 @@ def test_transforms(be, oracle, name):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_plain_to_ntt(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(22)
     pls = plains(o, rng, 6, N)
     pls[2, :6] = [0, 1, o.t // 2, (o.t + 1) // 2, o.t - 1, 2]
@@ -175,7 +166,7 @@ def pointwise(o, ct, pt):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_multiply_plain_ntt(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(23)
     for L in range(1, g.L + 1):
         for size in (1, 2, 3):
@@ -222,7 +213,7 @@ def test_multiply_plain_ntt(be, oracle, name):
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_ntt_form_pipeline_equals_coefficient_form_multiply_plain(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(24)
     for L in range(1, g.L + 1):
         for size in (2, 3):
@@ -291,7 +282,7 @@ def run_accumulate(be, g, o, L, size, rows, cols, inner, strides, ctn_vals, ptn_
 
 @pytest.mark.parametrize("name", list(ALL))
 def test_multiply_plain_accumulate(be, oracle, name):
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(25)
     for L in range(1, g.L + 1):
         for size in (1, 2, 3):
@@ -379,7 +370,7 @@ def test_semantic_plain_matrix_times_encrypted_vector(be, oracle, N, bits):
 def test_async_producer_then_each_call(be, oracle, name):
     """The operand is still being written by he355_add (asynchronous, first stream) when each new call is issued, with small chunks and the
     dual stream on: whatever stream a call uses has to be ordered behind the producer."""
-    g, o, N = pair(be, oracle, name)
+    g, o, N, *_ = pair(be, oracle, name)
     rng = np.random.default_rng(27)
     L, size, n = g.L, 2, 8
     g.set_dual_stream(True)
@@ -432,7 +423,7 @@ def test_async_producer_then_each_call(be, oracle, name):
 
 
 def test_accumulate_refusals_leave_the_output_untouched(be, oracle):
-    g, o, N = pair(be, oracle, "n4096_d3")
+    g, o, N, *_ = pair(be, oracle, "n4096_d3")
     rng = np.random.default_rng(28)
     L, size = g.L, 2
     per = size * L * N
@@ -461,7 +452,7 @@ def test_accumulate_refusals_leave_the_output_untouched(be, oracle):
 
 
 def test_second_call_makes_no_raw_allocation(be, oracle):
-    g, o, N = pair(be, oracle, "n8192_default")
+    g, o, N, *_ = pair(be, oracle, "n8192_default")
     rng = np.random.default_rng(29)
     L, n = g.L, 8
     g.set_chunk(3)

@@ -177,11 +177,8 @@ def test_encrypt_zero_and_accumulate_count_zero(case, be):
 @pytest.fixture(scope="module")
 def sim():
     import ctypes as C
-    import os
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    subprocess.run(["make", "-C", os.path.join(here, "csim"), "-s"], check=True)
-    L = C.CDLL(os.path.join(here, "csim", "_build", "libcsim.so"))
+    import csim_lib
+    L = csim_lib.load()
     vp, u64p = C.c_void_p, C.POINTER(C.c_uint64)
     L.sim_params_create.restype = vp
     L.sim_params_create.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.c_int]

@@ -3,19 +3,17 @@ index maps, LDS exchange layouts, twiddle addressing, and the fp64 engine's magn
 compared bit-for-bit with the oracle.  No GPU needed."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import csim_lib
 
 
 # both builds of the u64 engine (csrc/modarith.h): Shoup quotients, and the fold reduction for primes 2^60 - c
 @pytest.fixture(scope="module", params=["shoup", "fold"])
 def sim(request):
-    subprocess.run(["make", "-C", os.path.join(HERE, "csim"), "-s"], check=True)
-    L = C.CDLL(os.path.join(HERE, "csim", "_build", "libcsim.so" if request.param == "shoup" else "libcsim_fold.so"))
+    L = csim_lib.load(fold=request.param == "fold")
     L.sim_u64_fold_build.restype = C.c_int
     assert L.sim_u64_fold_build() == (request.param == "fold")
     u64p = C.POINTER(C.c_uint64)
