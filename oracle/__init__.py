@@ -280,6 +280,12 @@ class Context:
         lib().ho_add(self.h, L, size, _p(a), _p(b), _p(out))
         return out
 
+    def sub(self, a, b):
+        size, L, _ = a.shape
+        out = np.empty_like(a)
+        lib().ho_sub(self.h, L, size, _p(np.ascontiguousarray(a)), _p(np.ascontiguousarray(b)), _p(out))
+        return out
+
     def multiply_ntt(self, a, b):
         L = a.shape[1]
         out = np.empty((3, L, self.N), dtype=np.uint64)

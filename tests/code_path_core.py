@@ -1,7 +1,8 @@
 """Compact core of the GPU parity suite, run as a CHILD PROCESS by tests/test_gpu_code_paths.py once per kernel-selecting setting
 (the HE355_* switches are read when a context is created, some once per process): NTT round trip, multiply -> relinearize ->
-rescale (n = 5), a rotation that takes the NAF path, BFV multiply + relinearize, one he355_rotate_sum level walk and one DotProduct
-through the API-Bridge C ABI -- each compared bit for bit with the oracle (the bridge result with cleartext).  Exit code 0 = all equal.
+rescale (n = 5), a rotation that takes the NAF path, BFV multiply + relinearize, one he355_rotate_sum level walk, one DotProduct
+through the API-Bridge C ABI, and last relinearize and rotate at the extreme operands of tests/edge_operands.py (all q - 1 ciphertexts,
+all q - 1 and identity keys) -- each compared bit for bit with the oracle (the bridge result with cleartext).  Exit code 0 = all equal.
 usage: python tests/code_path_core.py            (environment = the setting under test)"""
 import importlib
 import os
@@ -114,6 +115,35 @@ def main():
     bk.destroy(hb)
     bk.close()
     done.append("bridge_dot")
+    # ---- the CKKS ring again, its own context (the switches are read when a context is created) ----
+    g = be.Context(be.SCHEME_CKKS, N, bit_sizes=bits, sec128=False, device=0)
+    # structured operands (tests/edge_operands.py): relinearize and rotate ciphertexts that are all q - 1 (NTT form: the constant -1) or
+    # whose every digit coefficient is q_j - 1, between uniform neighbours, under keys that are all q_t - 1 or the identity on the first /
+    # last digit -- the latter also against the closed form floor((d + floor(P/2)) / P) in Python integers
+    import edge_operands as eo
+    c3e = eo.batch(o, ["qm1", None, "qm1_coeff", None, "qm1"], L, 3, rng)
+    c3e[4, 2] = eo.planted_digit(o, L, L - 1, rng)
+    ae = np.ascontiguousarray(c3e[:, 1:])
+    d3e, dae = g.to_device(c3e), g.to_device(ae)
+    e1 = o.galois_elt(1)
+    for kind, j0 in (("qm1", 0), ("identity", 0), ("identity", L - 1)):
+        ke = eo.key(o, kind, rng, j0)
+        g.set_relin_key(ke)
+        g.set_galois_key(e1, ke)
+        refs = [o] + ([eo.IdentityOps(o, j0)] if kind == "identity" else [])
+        oe = g.alloc(n * 2 * L * N)
+        g.relinearize(L, n, d3e, oe)
+        got = oe.download((n, 2, L, N))
+        for ref in refs:
+            for r in range(n):
+                assert np.array_equal(got[r], ref.relinearize(c3e[r], ke)), ("edge relinearize", kind, j0, r)
+        g.rotate(L, n, dae, 1, oe)
+        got = oe.download((n, 2, L, N))
+        for ref in refs:
+            for r in range(n):
+                assert np.array_equal(got[r], ref.apply_galois(ae[r], e1, ke)), ("edge rotate", kind, j0, r)
+    g.close()
+    done.append("edge_operands")
     print("code paths ok:", " ".join(done))
 
 

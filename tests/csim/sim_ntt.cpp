@@ -244,7 +244,57 @@ template <int LOGN1> static int col_extreme(const ArU64 &ar, const PrimeTables &
         if (x[a] >= 4 * pt.q || ar.to_canon(x[a]) != ar.to_canon(y[a])) return 1;
     return 0;
 }
+// the fp64 engine's forward column pass as the digit lift runs it on its direct path (col_fwd_w: the digit's coefficients enter as they are,
+// twiddles as bare doubles, PrimeDev::colw): the largest |x| the pass leaves
+template <int LOGN1> static double col_w_maxmag(const ArF64 &ar, const PrimeTables &pt, const u64 *col)
+{
+    constexpr int N1 = 1 << LOGN1;
+    double cw[N1 < 2 ? 2 : N1], in[N1], x[N1] = {}, m = 0;
+    for (int k = 0; k < N1; ++k) { cw[k] = ArF64::tw_w(pt.fwd[k]); in[k] = (double)col[k]; }
+    col_fwd_w<LOGN1, false>(ar, [&](int a) { return in[a]; }, x, cw, 0.0);
+    for (int a = 0; a < N1; ++a) m = std::max(m, std::fabs(x[a]));
+    return m;
+}
+static double col_w_maxmag_any(const Params &P, size_t t, const u64 *col)
+{
+    const PrimeTables &pt = P.primes[t];
+    if (!pt.f64) return -1.0;
+    const ArF64 ar = pt.arf();
+    switch (P.logn1) {
+    case 1: return col_w_maxmag<1>(ar, pt, col);
+    case 2: return col_w_maxmag<2>(ar, pt, col);
+    case 3: return col_w_maxmag<3>(ar, pt, col);
+    case 4: return col_w_maxmag<4>(ar, pt, col);
+    case 5: return col_w_maxmag<5>(ar, pt, col);
+    default: return -1.0;
+    }
+}
 extern "C" {
+int sim_logn1(void *p) { return ((Params *)p)->logn1; }
+// max |x| after the direct-path forward column pass of fp64-engine target prime t on one column of N1 digit coefficients (-1: not an
+// fp64-engine prime, or a ring without a column pass)
+double sim_col_fwd_maxmag(void *p, size_t t, const uint64_t *col) { return col_w_maxmag_any(*(Params *)p, t, col); }
+// the same over `count` columns of uniform coefficients below qj (splitmix64 from seed): the largest magnitude seen
+double sim_col_fwd_maxmag_uniform(void *p, size_t t, uint64_t qj, size_t count, uint64_t seed)
+{
+    const Params &P = *(Params *)p;
+    const int n1 = 1 << P.logn1;
+    std::vector<u64> col(n1);
+    double m = -1.0;
+    u64 s = seed;
+    for (size_t c = 0; c < count; ++c) {
+        for (int a = 0; a < n1; ++a) {
+            s += 0x9E3779B97F4A7C15ull;
+            u64 z = s;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            col[a] = (u64)(((u128)z * qj) >> 64);
+        }
+        m = std::max(m, col_w_maxmag_any(P, t, col.data()));
+    }
+    return m;
+}
 void *sim_params_create(int scheme, size_t N, const int *bits, size_t n, int plain_bits, int sec128)
 {
     try {

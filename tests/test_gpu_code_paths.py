@@ -1,5 +1,5 @@
 """The code-path matrix where the driver runs it (`pytest -m gpu`): the compact core of tests/code_path_core.py -- NTT round trip,
-multiply -> relinearize -> rescale, a NAF rotation, BFV multiply + relinearize, one he355_rotate_sum level walk, one DotProduct through
+multiply -> relinearize -> rescale, a NAF rotation, relinearize and rotate at extreme operands and keys, BFV multiply + relinearize, one he355_rotate_sum level walk, one DotProduct through
 the API-Bridge C ABI, every result held to the oracle bit for bit -- re-run under each setting that selects kernels or schedules.
 Each setting runs in a fresh child process started BEFORE anything here touches the GPU for it (the switches are read at context
 creation, some once per process); the whole module takes under a minute.  tools/test_matrix.sh runs the FULL suite under the same
@@ -37,4 +37,4 @@ def test_core_under_setting(name):
     env.update(SETTINGS[name])
     r = subprocess.run([sys.executable, os.path.join(HERE, "code_path_core.py")], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"{name} ({SETTINGS[name]}):\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    assert "code paths ok: ntt mul_relin_rescale rotate_naf bfv_multiply_relin rotate_sum bridge_dot" in r.stdout
+    assert "code paths ok: ntt mul_relin_rescale rotate_naf bfv_multiply_relin rotate_sum bridge_dot edge_operands" in r.stdout

@@ -4,7 +4,9 @@ fp64-/u64-engine primes, forced-u64 contexts), levels, batch sizes on both sides
 ragged tails; CKKS multiply -> relinearize (-> rescale), relinearize of size-3 ciphertexts, rotations and rotate_add; BFV (30 % of the
 cases) BEHZ multiply, relinearize and a row or column rotation; and for both schemes the rotation chains of round 4 -- he355_rotate_sum
 (NAF-prefix trie, walked node by node or level by level with grouped key switches, now and then at a batch that sums the level inside k_k3), he355_rotate_each, he355_accumulate -- every result
-compared bit for bit.  usage: tools/fuzz_parity.py <seconds> [seed]   (prints one line per case; exit 1 on the first mismatch)"""
+compared bit for bit.  About 30 % of the cases draw their ciphertexts and key-switch keys from the structured families of
+tests/edge_operands.py (all q - 1, half, alternating, impulses, planted floor edges; keys all q - 1, zero or the identity on one digit)
+instead of uniform ones, the family named in the case line.  usage: tools/fuzz_parity.py <seconds> [seed]   (prints one line per case; exit 1 on the first mismatch)"""
 import importlib
 import os
 import sys
@@ -14,16 +16,46 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import edge_operands as eo  # noqa: E402  (test infrastructure)
 
 
-def chains(be, g, o, rng, L, n, a, da):
+class Draw:
+    """the operands of one case: uniform, or (p = 0.3) a ciphertext family at the even batch positions between uniform neighbours and a
+    key kind for every key-switch key of the case"""
+
+    def __init__(self, o, rng, L, coeff_form=False):
+        self.o, self.rng, self.cf = o, rng, coeff_form
+        self.fam = self.kind = None
+        if rng.random() < 0.3:
+            self.fam = str(rng.choice(eo.CT_FAMILIES))
+            self.kind = str(rng.choice(["uniform", "qm1", "identity", "identity", "zero"]))
+            self.j0 = int(rng.integers(0, L))
+
+    def cts(self, n, L, size=2):
+        if self.fam is None:
+            return np.stack([self.o.random_poly(self.rng, L, size) for _ in range(n)])
+        return eo.batch(self.o, eo.mixed(n, [self.fam]), L, size, self.rng, coeff_form=self.cf)
+
+    def key(self):
+        if self.kind in (None, "uniform"):
+            return self.o.random_kswitch_key(self.rng)
+        return eo.key(self.o, self.kind, self.rng, self.j0)
+
+    def __str__(self):
+        if self.fam is None:
+            return ""
+        return f" family={self.fam} key={self.kind}{self.j0 if self.kind == 'identity' else ''}"
+
+
+def chains(be, g, o, rng, L, n, a, da, draw):
     """rotate_sum / rotate_each / accumulate against the oracle's rotate_internal restatement; returns (ok, what)"""
     N = g.N
     keys = {}
     for k in range(5):  # +-1 .. +-16: every NAF term of a step in [-15, 15]
         for st in (1 << k, -(1 << k)):
             e = o.galois_elt(st)
-            keys[e] = o.random_kswitch_key(rng)
+            keys[e] = draw.key()
             g.set_galois_key(e, keys[e])
     walk = bool(rng.random() < 0.7)
     g.set_level_walk(walk)
@@ -101,8 +133,8 @@ def main():
             assert g.moduli == o.moduli and g.t == o.t
             L, n = g.L, int(rng.choice([1, 2, 3, 5, 9]))
             g.set_chunk(int(rng.choice([2, 4, 256])))
-            a = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
-            b = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
+            draw = Draw(o, rng, L, coeff_form=True)
+            a, b = draw.cts(n, L), draw.cts(n, L)
             da, db = g.to_device(a), g.to_device(b)
             c3 = g.alloc(n * 3 * L * N)
             g.bfv_multiply(L, n, da, db, be.Context.pairwise(), c3)
@@ -118,7 +150,7 @@ def main():
                 shape += f"+outer{nres}"
                 co.free()
             if ok:
-                rk = o.random_kswitch_key(rng)
+                rk = draw.key()
                 g.set_relin_key(rk)
                 out = g.alloc(n * 2 * L * N)
                 g.relinearize(L, n, c3, out)
@@ -144,7 +176,7 @@ def main():
                 outm.free()
             if ok:
                 elt = 2 * N - 1 if rng.random() < 0.3 else g.galois_elt(int(rng.choice([1, 2, -1, 4])))
-                gk = o.random_kswitch_key(rng)
+                gk = draw.key()
                 g.set_galois_key(elt, gk)
                 rot = g.alloc(n * 2 * L * N)
                 g.apply_galois(L, n, da, elt, rot)
@@ -153,8 +185,8 @@ def main():
             extra = []
             if ok and g.K >= 2:
                 g.set_latency_max(int(rng.choice([0, 8])))
-                ok, extra = chains(be, g, o, rng, L, n, a, da)
-            print(f"case {case}: BFV N={N} bits={bits} t_bits={pb}{' seal-base' if seal_base else ''} L={L} n={n} multiply[{shape}]+relin+galois+{'+'.join(extra)} {'ok' if ok else 'MISMATCH'}", flush=True)
+                ok, extra = chains(be, g, o, rng, L, n, a, da, draw)
+            print(f"case {case}: BFV N={N} bits={bits} t_bits={pb}{' seal-base' if seal_base else ''} L={L} n={n}{draw} multiply[{shape}]+relin+galois+{'+'.join(extra)} {'ok' if ok else 'MISMATCH'}", flush=True)
             g.close()
             if not ok:
                 return 1
@@ -182,10 +214,10 @@ def main():
         n = int(rng.choice([1, 2, 3, 5, 8, 9, 13]))
         g.set_chunk(int(rng.choice([2, 4, 32, 256])))
         g.set_latency_max(int(rng.choice([0, 4, 8])))
-        rk = o.random_kswitch_key(rng)
+        draw = Draw(o, rng, L)
+        rk = draw.key()
         g.set_relin_key(rk)
-        a = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
-        b = np.stack([o.random_poly(rng, L, 2) for _ in range(n)])
+        a, b = draw.cts(n, L), draw.cts(n, L)
         da, db = g.to_device(a), g.to_device(b)
         what = []
         # multiply -> relinearize (-> rescale): pairwise, or HEBench's outer product (result r = i * b1 + x) with operand bases > 0
@@ -215,7 +247,7 @@ def main():
         # relinearize of size-3 ciphertexts
         if ok:
             m = min(n, 3)
-            ct3 = np.stack([o.random_poly(rng, L, 3) for _ in range(m)])
+            ct3 = draw.cts(m, L, 3)
             o3 = g.alloc(m * 2 * L * N)
             g.relinearize(L, m, g.to_device(ct3), o3)
             g3 = o3.download((m, 2, L, N))
@@ -225,7 +257,7 @@ def main():
         if ok:
             step = int(rng.choice([1, -1, 2, 4, -8, 16]))
             e = o.galois_elt(step)
-            gk = o.random_kswitch_key(rng)
+            gk = draw.key()
             g.set_galois_key(e, gk)
             orot = g.alloc(n * 2 * L * N)
             g.rotate(L, n, da, step, orot)
@@ -239,9 +271,9 @@ def main():
                 ok = all(np.array_equal(gr[r], o.add(b[r], wr[r])) for r in range(n))
                 what.append("rot_add")
         if ok and rng.random() < 0.6:
-            ok, extra = chains(be, g, o, rng, L, n, a, da)
+            ok, extra = chains(be, g, o, rng, L, n, a, da, draw)
             what += extra
-        print(f"case {case}: N={N} bits={bits} force_u64={int(force)} L={L} n={n} {'+'.join(what)} {'ok' if ok else 'MISMATCH'}", flush=True)
+        print(f"case {case}: N={N} bits={bits} force_u64={int(force)} L={L} n={n}{draw} {'+'.join(what)} {'ok' if ok else 'MISMATCH'}", flush=True)
         g.close()
         if not ok:
             return 1
