@@ -32,4 +32,15 @@ void simc_sample(uint64_t seed, uint64_t stream, size_t count, int kind, int32_t
     for (size_t n = 0; n < count; ++n) out[n] = kind == 0 ? client::sample_ternary_at(seed, stream, n) : client::sample_cbd_at(seed, stream, n);
 }
 void simc_decrypt(void *c, const uint64_t *ct, size_t size, size_t L, uint64_t *out) { auto v = ((Client *)c)->decrypt(ct, size, L); std::memcpy(out, v.data(), v.size() * 8); }
+// decrypt under a given secret key [K][N] (NTT form) instead of the client's own: tests/client_operands.py's constant keys give the phase
+// of a ciphertext a closed form.  The client's key is put back before returning.
+void simc_decrypt_with_key(void *c, const uint64_t *sk, const uint64_t *ct, size_t size, size_t L, uint64_t *out)
+{
+    auto &own = const_cast<std::vector<uint64_t> &>(((Client *)c)->secret_key());
+    const std::vector<uint64_t> saved = own;
+    std::memcpy(own.data(), sk, own.size() * 8);
+    auto v = ((Client *)c)->decrypt(ct, size, L);
+    own = saved;
+    std::memcpy(out, v.data(), v.size() * 8);
+}
 }
