@@ -227,6 +227,35 @@ int he355_bfv_plain_to_ntt(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_
 int he355_bfv_multiply_plain_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain_ntt, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_multiply_plain_accumulate(he355_ctx *ctx, int L, int size, uint64_t rows, uint64_t cols, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_i,
                                         uint64_t ct_stride_k, const uint64_t *d_plain_ntt, uint64_t pt_stride_k, uint64_t pt_stride_j, uint64_t *d_out);
+/* ---- monomial multiply and oblivious query expansion (BFV contexts only, else HE355_E_INVALID_ARGS, decided on the host before any device
+ * is asked for; coefficient form; every L in 1..L_top).  he355_bfv_multiply_plain_accumulate scans a database with one ciphertext per
+ * index of a dimension -- Enc(1) at the wanted index, Enc(0) elsewhere; instead of encrypting and uploading all of them a client sends
+ * ONE ciphertext of sum_k m_k X^k and the server expands it obliviously (Angel, Chen, Laine, Setty, "PIR with compressed queries and
+ * amortized query processing", Alg. 3): each level takes one Galois substitution and one multiplication by a monomial.
+ *   he355_bfv_multiply_monomial   out = in X^exponent in Z_q_i[X]/(X^N + 1) for every polynomial of [n][size][L][N], size 1..3, exponent in
+ *                                 [0, 2N) (X^N = -1); canonical residues: the negative of 0 is 0.  By definition bit-identical to
+ *                                 he355_bfv_multiply_plain with the plaintext X^e (coefficient 1) for e < N and with coefficient t - 1 at
+ *                                 e - N for e >= N; one streaming launch, no transform.  d_out may not overlap d_in; n == 0 touches nothing.
+ *                                 [UPSTREAM-UNVERIFIED] as the level operations above: SEAL's multiply_plain mono path
+ *                                 (util::negacyclic_shift_poly_coeffmod).
+ *   he355_bfv_expand_galois_elts  the Galois elements he355_bfv_expand needs for `count` children: e_j = N / 2^j + 1, j < d = ceil(log2 count),
+ *                                 written to out (at most cap entries); returns d, 0 for a CKKS context or a count outside 1..N.  Their keys
+ *                                 come from he355_keygen_galois / he355_set_galois_key (any odd element is accepted there).
+ *   he355_bfv_expand              d_in [n][2][L][N], n queries -> d_out [count][n][2][L][N], 1 <= count <= N, CHILD-MAJOR: child k of query r is
+ *                                 ciphertext k n + r, the addressing of he355_bfv_multiply_plain_accumulate with ct_stride_i = 1,
+ *                                 ct_stride_k = n (transform the children with he355_bfv_transform_to_ntt first).  The definition, every + and -
+ *                                 being he355_add / he355_sub on canonical residues: for j = 0 .. d-1, s = 2^j, and every node k < 2^j holding c:
+ *                                     g = he355_apply_galois(c, e_j);  child k = c + g;  child k + s = X^(-s) (c - g), only when k + s < count.
+ *                                 A query costs 2^d - 1 key switches, one batched key switch per level over the nodes of all queries.  If the
+ *                                 query's plaintext is sum_i m_i X^i mod t, child k decrypts to 2^d sum_{i = k mod 2^d} m_i X^(i - k) mod t: for a
+ *                                 query supported on i < 2^d the constant 2^d m_k (the client folds 2^-d mod t into the query; t is odd).
+ *                                 Refused before the first launch, so that nothing is half-written: a count of 0 or above N, a bad L, a
+ *                                 missing Galois key (the message names the element), d_out overlapping d_in.  n == 0 touches nothing;
+ *                                 count == 1 copies.  Scratch: one pool block of 2^(d-1) n ciphertexts (a second identical call allocates
+ *                                 nothing).  NOT for NTT-form ciphertexts: as in SEAL, transform after the expansion. */
+int he355_bfv_multiply_monomial(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint32_t exponent, uint64_t *d_out);
+uint64_t he355_bfv_expand_galois_elts(const he355_ctx *ctx, uint64_t count, uint32_t *out, uint64_t cap);
+int he355_bfv_expand(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, uint64_t count, uint64_t *d_out);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

@@ -122,6 +122,9 @@ def lib():
             "he355_bfv_plain_to_ntt": (i32, [vp, i32, u64, vp, vp]),
             "he355_bfv_multiply_plain_ntt": (i32, [vp, i32, i32, u64, vp, vp, Indexer, vp]),
             "he355_bfv_multiply_plain_accumulate": (i32, [vp, i32, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
+            "he355_bfv_multiply_monomial": (i32, [vp, i32, i32, u64, vp, u32, vp]),
+            "he355_bfv_expand_galois_elts": (u64, [vp, u64, C.POINTER(u32), u64]),
+            "he355_bfv_expand": (i32, [vp, i32, u64, vp, u64, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -166,7 +169,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -400,6 +403,20 @@ class Context:
         """out(i, j) = sum_k ct(i, k) (.) pt(k, j) over NTT-form operands, [rows * cols][size][L][N]: one launch, bit-identical to the loop"""
         _check(lib().he355_bfv_multiply_plain_accumulate(self.h, L, size, rows, cols, inner, ct.ptr, ct_stride_i, ct_stride_k, pt_ntt.ptr,
                                                          pt_stride_k, pt_stride_j, out.ptr))
+
+    def bfv_multiply_monomial(self, L, size, n, inp, exponent, out):
+        """out = inp * X^exponent in Z_q[X]/(X^N + 1) for every polynomial of [n][size][L][N]; exponent in [0, 2N), coefficient form"""
+        _check(lib().he355_bfv_multiply_monomial(self.h, L, size, n, inp.ptr, exponent, out.ptr))
+
+    def bfv_expand_galois_elts(self, count: int) -> list[int]:
+        """the Galois elements bfv_expand needs for `count` children: N / 2^j + 1, j < ceil(log2 count) (host-side; no device needed)"""
+        buf = (C.c_uint32 * 32)()
+        d = lib().he355_bfv_expand_galois_elts(self.h, count, buf, 32)
+        return [int(x) for x in buf[:d]]
+
+    def bfv_expand(self, L, n, inp, count, out):
+        """oblivious query expansion: inp [n][2][L][N] -> out [count][n][2][L][N], child k of query r at index k * n + r"""
+        _check(lib().he355_bfv_expand(self.h, L, n, inp.ptr, count, out.ptr))
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

@@ -946,8 +946,9 @@ public:
         });
         HIPCHECK(hipGetLastError());
     }
-    // `addend` (optional, [n][2][L][N]; may alias `out`, never `in`): out = addend + galois(in) -- the add_inplace that follows
-    // a rotation in accumulateCKKS/BFV and in the row-major MatMult is folded into the first kernel of the rotation.
+    // `addend` (optional, [n][2][L][N]; may alias `out`): out = addend + galois(in) -- the add_inplace that follows
+    // a rotation in accumulateCKKS/BFV and in the row-major MatMult is folded into the first kernel of the rotation.  No kernel writes
+    // the addend unless it is `out`, so it may also be `in` itself (out = in + galois(in): bfv_expand's even children).
     // ntt_form (BFV contexts): the ciphertexts are held in NTT form (a rotation chain that was transformed on the way in runs on the fused
     // NTT-domain pipeline: accumulate, rotate_sum)
     void apply_galois(int L, u64 n, const u64 *in, uint32_t elt, u64 *out, const u64 *addend = nullptr, bool ntt_form = false)
@@ -1753,6 +1754,77 @@ public:
         launch_bfv_plain_mac(env_, L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
         HIPCHECK(hipGetLastError());
     }
+    // ---- monomial multiply and oblivious query expansion (he355_kernels_bfv_expand.hip) -------------------------------------------
+    // The argument checks that need no device: the C ABI makes them before it asks for one.
+    static void check_monomial_args(const Params &p, int L, int size, u32 e)
+    {
+        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_multiply_monomial: level out of range");
+        check_size(size, 1, 3);
+        if (e >= 2 * p.N) throw std::invalid_argument("he355_bfv_multiply_monomial: the exponent must be below 2N (X^N = -1)");
+    }
+    static void check_expand_args(const Params &p, int L, u64 count)
+    {
+        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_expand: level out of range");
+        if (count < 1 || count > p.N) throw std::invalid_argument("he355_bfv_expand: count must be in 1..N");
+    }
+    // levels of the expansion tree of `count` children, ceil(log2 count); level j uses the Galois element N / 2^j + 1
+    static int expand_depth(u64 count)
+    {
+        int d = 0;
+        while (((u64)1 << d) < count) ++d;
+        return d;
+    }
+    // out = in X^e for every polynomial of [n][size][L][N], coefficient form: one launch
+    void bfv_multiply_monomial(int L, int size, u64 n, const u64 *in, u32 e, u64 *out)
+    {
+        use();
+        check_monomial_args(P, L, size, e);
+        const size_t words = (size_t)n * size * L * P.N;
+        if (ranges_overlap(in, words, out, words)) throw std::invalid_argument("he355_bfv_multiply_monomial: `out` overlaps `in`");
+        launch_bfv_shift(env_, L, n * size * L, in, nullptr, e, out);
+        HIPCHECK(hipGetLastError());
+    }
+    // Oblivious expansion (Angel et al., "PIR with compressed queries", Alg. 3): in [n][2][L][N] -> out [count][n][2][L][N], child k of query r
+    // at index k n + r.  Level j (s = 2^j) turns the s n nodes it reads, node k of query r at k n + r, into 2 s n: ONE batched key switch
+    // with the node itself as the addend leaves the even children c + g where the nodes' indices are (k_bfv_galois forms c0 + sigma(c0) and
+    // passes c1 through, k_bfv_tail_fin adds the switched part; the addend is only read, so it may be the input), and one k_bfv_shift
+    // launch writes the odd children X^(-s) (2c - even) behind them, at (k + s) n + r -- the last level only those below `count`.  The
+    // levels alternate between `out` and one pool block of 2^(d-1) n ciphertexts (what level d - 2 writes), the parity chosen so that
+    // level d - 1 lands in `out`; everything runs on the context's stream.  Every refusal comes before the first launch.
+    void bfv_expand(int L, u64 n, const u64 *in, u64 count, u64 *out)
+    {
+        use();
+        check_expand_args(P, L, count);
+        const int d = expand_depth(count);
+        const size_t N = P.N, ctn = 2 * (size_t)L * N;
+        if (d) require_keyswitch();
+        for (int j = 0; j < d; ++j) {
+            const uint32_t elt = (uint32_t)(N >> j) + 1;
+            if (!galois_key(elt)) throw std::invalid_argument("he355_bfv_expand: Galois key of element " + std::to_string(elt) + " not present");
+        }
+        if (ranges_overlap(in, n * ctn, out, count * n * ctn)) throw std::invalid_argument("he355_bfv_expand: `out` overlaps `in`");
+        if (!n) return;
+        if (!d) {
+            HIPCHECK(hipMemcpyAsync(out, in, n * ctn * 8, hipMemcpyDeviceToDevice, stream_));
+            return;
+        }
+        u64 *tmp = d > 1 ? static_cast<u64 *>(pool_alloc(((size_t)n << (d - 1)) * ctn * 8)) : nullptr;
+        try {
+            const u64 *cur = in;
+            for (int j = 0; j < d; ++j) {
+                const u64 s = (u64)1 << j, odd = std::min<u64>(s, count - s); // (count - s < s at the last level only)
+                u64 *dst = (d - 1 - j) % 2 == 0 ? out : tmp;
+                apply_galois(L, s * n, cur, (uint32_t)(N >> j) + 1, dst, cur);
+                launch_bfv_shift(env_, L, odd * n * 2 * L, cur, dst, (u32)(2 * N - s), dst + s * n * ctn);
+                cur = dst;
+            }
+            HIPCHECK(hipGetLastError());
+        } catch (...) {
+            if (tmp) pool_free(tmp);
+            throw;
+        }
+        if (tmp) pool_free(tmp);
+    }
     const CrtTablesDev &crt_tables(int L)
     {
         return per_level(crt_, L, [&] {
@@ -2401,6 +2473,29 @@ int he355_bfv_multiply_plain_accumulate(he355_ctx *c, int L, int size, uint64_t 
     return guarded([&] {
         need_bfv(c, "he355_bfv_multiply_plain_accumulate");
         dev(c).bfv_multiply_plain_accumulate(L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
+    });
+}
+int he355_bfv_multiply_monomial(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint32_t exponent, uint64_t *out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_multiply_monomial");
+        DeviceContext::check_monomial_args(*c->params, L, size, exponent);
+        dev(c).bfv_multiply_monomial(L, size, n, in, exponent, out);
+    });
+}
+uint64_t he355_bfv_expand_galois_elts(const he355_ctx *c, uint64_t count, uint32_t *out, uint64_t cap)
+{
+    if (!c || c->params->scheme != kSchemeBFV || count < 1 || count > c->params->N) return 0;
+    const int d = DeviceContext::expand_depth(count);
+    for (int j = 0; j < d && (uint64_t)j < cap; ++j) out[j] = (uint32_t)(c->params->N >> j) + 1;
+    return (uint64_t)d;
+}
+int he355_bfv_expand(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint64_t count, uint64_t *out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_expand");
+        DeviceContext::check_expand_args(*c->params, L, count);
+        dev(c).bfv_expand(L, n, in, count, out);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

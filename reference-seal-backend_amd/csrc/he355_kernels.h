@@ -236,6 +236,7 @@ HE355_FWD(launch_bfv_noise_dot_sk)
 HE355_FWD(launch_bfv_noise_bits)
 HE355_FWD(launch_bfv_noise_finish)
 HE355_FWD(launch_bfv_plain_mac)
+HE355_FWD(launch_bfv_shift)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -137,3 +137,8 @@ void launch_bfv_noise_finish(const KernelEnv &env, u64 n_cts, int *budget, int *
 // i * ct_stride_i + k * ct_stride_k, plaintext (k, j) at k * pt_stride_k + j * pt_stride_j; out [rows * cols][size][L][N].  One launch.
 void launch_bfv_plain_mac(const KernelEnv &env, int L, int size, u64 rows, u64 cols, u64 inner, const u64 *ct, u64 ct_stride_i, u64 ct_stride_k, const u64 *pt,
                           u64 pt_stride_k, u64 pt_stride_j, u64 *out);
+// ---- BFV monomial multiply and the odd children of he355_bfv_expand (he355_kernels_bfv_expand.hip; arithmetic: bfv_expand_core.h) -----------
+// out[p] = x[p] X^e in Z_q[X]/(X^N + 1), e in [0, 2N), for n_polys residue polynomials [.][L][N] in coefficient form (polynomial p under
+// prime p % L): x = in, or (even != null) 2 in - even -- the odd child X^(-s) (c - g) of the expansion from the node c and its even child
+// c + g.  out may overlap neither operand.  One launch.
+void launch_bfv_shift(const KernelEnv &env, int L, u64 n_polys, const u64 *in, const u64 *even, u32 e, u64 *out);
