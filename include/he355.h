@@ -256,6 +256,35 @@ int he355_bfv_multiply_plain_accumulate(he355_ctx *ctx, int L, int size, uint64_
 int he355_bfv_multiply_monomial(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint32_t exponent, uint64_t *d_out);
 uint64_t he355_bfv_expand_galois_elts(const he355_ctx *ctx, uint64_t count, uint32_t *out, uint64_t cap);
 int he355_bfv_expand(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, uint64_t count, uint64_t *d_out);
+/* ---- ciphertext decomposition for recursive (two-dimensional) PIR (BFV contexts only, coefficient-form ciphertexts, every L in 1..L_top).
+ * A database seen as n1 x n2 needs n1 + n2 expanded children instead of n1 n2 (Angel, Chen, Laine, Setty, "Handling larger databases"): scan
+ * the first dimension, CUT each of the n2 resulting ciphertexts into plaintexts, scan those with the second dimension's children; the client
+ * decrypts, glues the plaintexts back into a ciphertext and decrypts once more.  The cut and its inverse are these calls.
+ * [UPSTREAM-UNVERIFIED] as the level operations above; the definition is this library's own:
+ *     w = bitlen(t) - 1 (2^w <= t: every w-bit value is a plaintext coefficient), b_i = bitlen(q_i), D_i = ceil(b_i / w),
+ *     off_i = sum_{i' < i} D_i', D(L) = off_L, F = size D(L);
+ *     digit g < D_i of a canonical residue x under prime i is (x >> (g w)) & (2^w - 1) (every shift below 64);
+ *     polynomial k, prime i, digit g of ciphertext r is plaintext r F + k D(L) + off_i + g, coefficient e of it the digit of coefficient e.
+ *   he355_bfv_digit_count    returns D(L) and writes D_0 .. D_(L-1) (at most cap entries); 0 for a CKKS context or a bad level.  Host only.
+ *   he355_bfv_decompose      d_ct [n][size][L][N] -> d_plain [n][F][N] coefficients mod t, the layout he355_bfv_plain_to_ntt and he355_encrypt
+ *                            read; size 1..3; one streaming launch, every ciphertext word read once.
+ *   he355_bfv_decompose_ntt  d_ct [n][size][L][N] -> d_plain_ntt [n][F][L_out][N].  By definition bit-identical to he355_bfv_decompose followed
+ *                            by he355_bfv_plain_to_ntt(L_out, n F, ..): the centred lift of each digit (below floor((t + 1) / 2) as is, else
+ *                            minus t) under primes 0 .. L_out-1, transformed in he355_ntt_forward's bit order.  L and L_out are independent:
+ *                            switch the first scan's result down with he355_bfv_mod_switch so that F is small, then scan again at the level
+ *                            of the fresh children.  The output is the pt(k, j) operand of he355_bfv_multiply_plain_accumulate as it lies:
+ *                            entry k = r, column j = f, pt_stride_k = F, pt_stride_j = 1.  For N >= 2048 the digits are cut and lifted
+ *                            inside the forward column pass (neither intermediate slab exists); N = 1024 runs the two calls (one pool block).
+ *   he355_bfv_compose        the inverse, d_plain [n][F][N] -> d_ct [n][size][L][N], for the client after he355_decrypt of the second scan:
+ *                            residue = sum_g (digit_g masked) 2^(g w), digits below the top one masked to w bits, the top one to
+ *                            b_i - (D_i - 1) w bits, so the sum is below 2^b_i < 2 q_i and one conditional subtraction gives a canonical
+ *                            residue whatever the input.  On he355_bfv_decompose's own output it is the identity.
+ * Refused with HE355_E_INVALID_ARGS on the host, before any device is asked for: a CKKS context, a bad L or L_out, size outside 1..3, t < 2,
+ * n F above 2^32 - 1, any overlap of output and input.  n == 0 touches nothing.  Everything is queued on the context's stream. */
+uint64_t he355_bfv_digit_count(const he355_ctx *ctx, int L, uint32_t *per_prime, uint64_t cap);
+int he355_bfv_decompose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_plain);
+int he355_bfv_decompose_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, int L_out, uint64_t *d_plain_ntt);
+int he355_bfv_compose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_plain, uint64_t *d_ct);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

@@ -125,6 +125,10 @@ def lib():
             "he355_bfv_multiply_monomial": (i32, [vp, i32, i32, u64, vp, u32, vp]),
             "he355_bfv_expand_galois_elts": (u64, [vp, u64, C.POINTER(u32), u64]),
             "he355_bfv_expand": (i32, [vp, i32, u64, vp, u64, vp]),
+            "he355_bfv_digit_count": (u64, [vp, i32, C.POINTER(u32), u64]),
+            "he355_bfv_decompose": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_decompose_ntt": (i32, [vp, i32, i32, u64, vp, i32, vp]),
+            "he355_bfv_compose": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -169,7 +173,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -417,6 +421,27 @@ class Context:
     def bfv_expand(self, L, n, inp, count, out):
         """oblivious query expansion: inp [n][2][L][N] -> out [count][n][2][L][N], child k of query r at index k * n + r"""
         _check(lib().he355_bfv_expand(self.h, L, n, inp.ptr, count, out.ptr))
+
+    def bfv_digit_count(self, L: int) -> tuple[int, list[int]]:
+        """(D(L), [D_0 .. D_(L-1)]): how many plaintexts bfv_decompose cuts one residue polynomial into under each prime of level L, digits
+        of bitlen(t) - 1 bits; a ciphertext of `size` polynomials becomes size * D(L) plaintexts.  (0, []) for a CKKS context or a bad level
+        (host-side; no device needed)"""
+        buf = (C.c_uint32 * 64)()
+        total = int(lib().he355_bfv_digit_count(self.h, L, buf, 64))
+        return total, [int(x) for x in buf[:L]] if total else []
+
+    def bfv_decompose(self, L, size, n, ct, plain):
+        """ct [n][size][L][N] coefficient form -> plain [n][F][N] mod t, F = size * D(L): polynomial k, prime i, digit g at k D(L) + off_i + g"""
+        _check(lib().he355_bfv_decompose(self.h, L, size, n, ct.ptr, plain.ptr))
+
+    def bfv_decompose_ntt(self, L, size, n, ct, L_out, plain_ntt):
+        """ct [n][size][L][N] -> plain_ntt [n][F][L_out][N]: bfv_decompose followed by bfv_plain_to_ntt(L_out, n * F), fused; the pt operand of
+        bfv_multiply_plain_accumulate with pt_stride_k = F, pt_stride_j = 1"""
+        _check(lib().he355_bfv_decompose_ntt(self.h, L, size, n, ct.ptr, L_out, plain_ntt.ptr))
+
+    def bfv_compose(self, L, size, n, plain, ct):
+        """the inverse of bfv_decompose: plain [n][F][N] -> ct [n][size][L][N], canonical residues whatever the digits"""
+        _check(lib().he355_bfv_compose(self.h, L, size, n, plain.ptr, ct.ptr))
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

@@ -1825,6 +1825,68 @@ public:
         }
         if (tmp) pool_free(tmp);
     }
+    // ---- ciphertext decomposition for recursive (two-dimensional) PIR (he355_kernels_bfv_digits.hip) ---------------------------------
+    // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the digit table of level L.
+    // `ct` [n][size][L][N], `plain` [n][F][N] (L_out == 0) or [n][F][L_out][N]: the two may not overlap, whichever is written.
+    static BfvDigitTab check_digit_args(const Params &p, const char *what, int L, int size, u64 n, const u64 *ct, const u64 *plain, int L_out = 0)
+    {
+        const std::string w(what);
+        if (L < 1 || (size_t)L > p.Ltop || L_out < 0 || (size_t)L_out > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+        check_size(size, 1, 3);
+        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+        u64 q[kMaxPrimes];
+        for (int i = 0; i < L; ++i) q[i] = p.primes[i].q;
+        const BfvDigitTab tab = bfv_digit_table(q, L, p.plain_modulus);
+        const u64 F = (u64)size * tab.total;
+        if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many plaintexts for one call (n F must be below 2^32)");
+        if (ranges_overlap(ct, (size_t)n * size * L * p.N, plain, (size_t)n * F * (L_out ? L_out : 1) * p.N))
+            throw std::invalid_argument(w + ": the plaintexts overlap the ciphertexts");
+        return tab;
+    }
+    // [n][size][L][N] -> [n][F][N] coefficients mod t: one streaming launch
+    void bfv_decompose(int L, int size, u64 n, const u64 *ct, u64 *plain)
+    {
+        use();
+        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_decompose", L, size, n, ct, plain);
+        launch_bfv_digits(env_, tab, L, size, n, ct, plain);
+        HIPCHECK(hipGetLastError());
+    }
+    // the inverse: [n][F][N] -> [n][size][L][N], canonical whatever the digits are
+    void bfv_compose(int L, int size, u64 n, const u64 *plain, u64 *ct)
+    {
+        use();
+        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_compose", L, size, n, ct, plain);
+        launch_bfv_undigits(env_, tab, L, size, n, plain, ct);
+        HIPCHECK(hipGetLastError());
+    }
+    // [n][size][L][N] -> [n][F][L_out][N], by definition bfv_decompose + bfv_plain_to_ntt(L_out, n F).  N >= 2048: the fused column pass
+    // reads the ciphertext, cuts, lifts and writes out(f, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is
+    // routed to the composition, its [n][F][N] slab a pool block (a second identical call allocates nothing).
+    void bfv_decompose_ntt(int L, int size, u64 n, const u64 *ct, int L_out, u64 *out)
+    {
+        use();
+        if (L_out < 1) throw std::invalid_argument("he355_bfv_decompose_ntt: level out of range");
+        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_decompose_ntt", L, size, n, ct, out, L_out);
+        const size_t N = P.N, F = (size_t)size * tab.total;
+        if (!n) return;
+        if (env_.logn1 == 0) {
+            u64 *tmp = static_cast<u64 *>(pool_alloc((size_t)n * F * N * 8));
+            try {
+                launch_bfv_digits(env_, tab, L, size, n, ct, tmp);
+                launch_bfv_lift_plain(env_, L_out, n * F, tmp, out, P.plain_modulus);
+                launch_ntt_forward(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
+                HIPCHECK(hipGetLastError());
+            } catch (...) {
+                pool_free(tmp);
+                throw;
+            }
+            pool_free(tmp);
+            return;
+        }
+        launch_bfv_digits_cols_fwd(env_, tab, L, size, n, ct, L_out, P.plain_modulus, out);
+        launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
+        HIPCHECK(hipGetLastError());
+    }
     const CrtTablesDev &crt_tables(int L)
     {
         return per_level(crt_, L, [&] {
@@ -2496,6 +2558,40 @@ int he355_bfv_expand(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint64
         need_bfv(c, "he355_bfv_expand");
         DeviceContext::check_expand_args(*c->params, L, count);
         dev(c).bfv_expand(L, n, in, count, out);
+    });
+}
+uint64_t he355_bfv_digit_count(const he355_ctx *c, int L, uint32_t *per_prime, uint64_t cap)
+{
+    if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || c->params->plain_modulus < 2) return 0;
+    u64 q[kMaxPrimes];
+    for (int i = 0; i < L; ++i) q[i] = c->params->primes[i].q;
+    const BfvDigitTab tab = bfv_digit_table(q, L, c->params->plain_modulus);
+    for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
+    return tab.total;
+}
+int he355_bfv_decompose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, uint64_t *plain)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_decompose");
+        DeviceContext::check_digit_args(*c->params, "he355_bfv_decompose", L, size, n, ct, plain);
+        dev(c).bfv_decompose(L, size, n, ct, plain);
+    });
+}
+int he355_bfv_decompose_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, int L_out, uint64_t *plain_ntt)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_decompose_ntt");
+        if (L_out < 1) throw std::invalid_argument("he355_bfv_decompose_ntt: level out of range");
+        DeviceContext::check_digit_args(*c->params, "he355_bfv_decompose_ntt", L, size, n, ct, plain_ntt, L_out);
+        dev(c).bfv_decompose_ntt(L, size, n, ct, L_out, plain_ntt);
+    });
+}
+int he355_bfv_compose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *plain, uint64_t *ct)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_compose");
+        DeviceContext::check_digit_args(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
+        dev(c).bfv_compose(L, size, n, plain, ct);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

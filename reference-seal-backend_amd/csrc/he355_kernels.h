@@ -10,6 +10,7 @@
 #include "behz_core.h"
 #include "bfv_level_core.h"
 #include "bfv_noise_core.h"
+#include "bfv_digits_core.h"
 
 namespace he355 {
 
@@ -237,6 +238,9 @@ HE355_FWD(launch_bfv_noise_bits)
 HE355_FWD(launch_bfv_noise_finish)
 HE355_FWD(launch_bfv_plain_mac)
 HE355_FWD(launch_bfv_shift)
+HE355_FWD(launch_bfv_digits)
+HE355_FWD(launch_bfv_undigits)
+HE355_FWD(launch_bfv_digits_cols_fwd)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -142,3 +142,12 @@ void launch_bfv_plain_mac(const KernelEnv &env, int L, int size, u64 rows, u64 c
 // prime p % L): x = in, or (even != null) 2 in - even -- the odd child X^(-s) (c - g) of the expansion from the node c and its even child
 // c + g.  out may overlap neither operand.  One launch.
 void launch_bfv_shift(const KernelEnv &env, int L, u64 n_polys, const u64 *in, const u64 *even, u32 e, u64 *out);
+// ---- BFV ciphertext decomposition for recursive PIR (he355_kernels_bfv_digits.hip; arithmetic: bfv_digits_core.h) ---------------------------
+// ct [n][size][L][N] coefficient form <-> plain [n][F][N] mod t, F = size D(L): digit g of polynomial k under prime i is plaintext
+// k D(L) + off_i + g (`tab`: bfv_digit_table of the level).  One launch each; the two slabs may not overlap.
+void launch_bfv_digits(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *ct, u64 *plain);
+void launch_bfv_undigits(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *plain, u64 *ct);
+// The forward column pass of the digits' transforms, out of place: ct -> out [n][F][L_out][N], the centred lift of digit plaintext f under
+// prime i' < L_out after the column pass (raw of prime i'), what launch_bfv_lift_plain + launch_cols_fwd would have left there;
+// launch_rows_fwd finishes it in place.  N >= 2048 only (N = 1024 has no column pass).
+void launch_bfv_digits_cols_fwd(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *ct, int L_out, u64 t, u64 *out);
