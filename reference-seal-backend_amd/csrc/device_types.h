@@ -16,7 +16,9 @@ struct PrimeDev {
     const Tw16 *inv;      // N entries
     Tw16 inv_w0_scaled;
     int f64;              // 1: ArF64 engine owns this prime
-    int pad_;
+    // k_k3's floor steps, this prime as the TARGET (fp64 engine): the most accumulated terms for which they may read the double sums and
+    // the correction row as they are (modarith.h: floor_direct_terms; 0: never) -- beyond it both are re-centred first
+    u32 acc_terms;
     // k_k2n, this prime as the DIGIT prime j: how the digit's column enters the forward column pass of fp64-engine target prime t
     // (bit t).  k2_direct: as it is (q_j < 2^52, q_j <= 2 q_t) and the 48-bit row format holds the result; k2_lift: after a
     // re-centring (q_j > 2 q_t) or an integer reduction (q_j >= 2^52), result fits too; neither bit: the general path.

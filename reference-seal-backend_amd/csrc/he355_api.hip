@@ -205,7 +205,8 @@ private:
             d.ninv = au.ninv; d.ninv_q = au.ninv_q;
             d.qd = af.q; d.qinv = af.qinv; d.ninv_d = af.ninv; d.ninv_i = af.ninv_i;
             d.fwd = dfwd; d.inv = dinv; d.inv_w0_scaled = pt.inv_w0_scaled;
-            d.f64 = pt.f64 ? 1 : 0; d.pad_ = 0;
+            d.f64 = pt.f64 ? 1 : 0;
+            d.acc_terms = pt.f64 ? floor_direct_terms(pt.q) : 0;
             for (size_t k = 0; k < 64; ++k) d.colw[k] = 0.0;
             if (pt.f64)
                 for (size_t k = 0; k < 32 && k < N; ++k) { d.colw[k] = ArF64::tw_w(pt.fwd[k]); d.colw[32 + k] = ArF64::tw_w(pt.inv[k]); }

@@ -484,10 +484,7 @@ __device__ __forceinline__ void k1_job(const K1Args &A, const PrimeDev &P, u64 o
             load_rowC(pa + P1, lane, a1);
             load_rowC(pb + P1, lane, b1);
 #pragma unroll
-            for (int r2 = 0; r2 < kRowE; ++r2) {
-                v2[r2] = ar.dy_out(ar.dy_mul(ar.dy_in(a1[r2]), ar.dy_in(b1[r2])));
-                x[r2] = ar.from_canon(v2[r2]);
-            }
+            for (int r2 = 0; r2 < kRowE; ++r2) x[r2] = ar.dy_mul(ar.dy_in(a1[r2]), ar.dy_in(b1[r2])); // the product as it is (fp64 engine: centred lazy, |x| < q): nothing here reads the canonical integer
             // (no c2n row either: the fused k_k3 of a ct x ct multiply forms a1 b1 itself, from the rows it reads for c0, c1)
         } else {
         load_rowC(pa, lane, a0); load_rowC(pa + P1, lane, a1);

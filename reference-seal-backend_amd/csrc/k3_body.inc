@@ -156,7 +156,7 @@
                 load_rowC(A.tb + (idx_b(A.tix, tr) * 2 + 1) * LNt + (u64)tt * N + rowoff, lane, b1);
                 T x[kRowE];
 #pragma unroll
-                for (int r = 0; r < kRowE; ++r) x[r] = ar.from_canon(ar.dy_out(ar.dy_mul(ar.dy_in(a1[r]), ar.dy_in(b1[r])))); // as the c2n row would read
+                for (int r = 0; r < kRowE; ++r) x[r] = ar.dy_mul(ar.dy_in(a1[r]), ar.dy_in(b1[r])); // the product as it is (fp64 engine: centred lazy, |x| < q; the key product takes any |x k| < 2^100)
                 mac_digit(x, tt);
             } else {
                 T x[kRowE];
@@ -232,6 +232,15 @@
                 }
             }
             acc_flush();
+            // fp64 engine: the floor steps read the double sums as they are (no canonical integer in between).  Where this prime's bound
+            // does not hold for the launch's number of terms (at most L digits and the two operand products; modarith.h,
+            // floor_direct_terms) sums and correction row are re-centred first -- one wave-uniform branch per row.
+            // (Read here, behind the digit loop: one more value live across it costs the rotation instantiations spilled registers.)
+            // kAccForms: the plain rotation / size-3 instantiation <FUSE, !TENSOR, !GROUPED> keeps the canonical forms -- with the accumulator
+            // forms its allocation changes (34 -> 58 spilled registers on the fp64 engine, one reload inside the digit step, whose
+            // s_waitcnt also waits for the prefetched row: DotProduct 38.9 -> 41.1 ms per step), the other instantiations' improves.
+            constexpr bool kAccForms = TENSOR || GROUPED;
+            const bool direct = kAccForms && Ar::kAccDirect && floor_direct(P.acc_terms, (u32)A.L + 2);
             // correction rows: transform + floor step(s)
 #pragma unroll 1
             for (int i = nd; FUSE && i < n_rows; ++i) {
@@ -294,19 +303,31 @@
                     wave_rows_fwd_n(ar, twr, lane, lds[wave], x);
                 }
                 const Acc *acc = k == 0 ? acc0 : acc1;
+                if (kAccForms && Ar::kAccDirect && !direct) { // beyond the direct forms' bound: sums (not read again after this row) and row re-centred
+                    if (k == 0) {
+#pragma unroll
+                        for (int r = 0; r < kRowE; ++r) ar.floor_prep(acc0[r], x[0][r]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < kRowE; ++r) ar.floor_prep(acc1[r], x[0][r]);
+                    }
+                }
                 if constexpr (TENSOR) { // sums formed with scaled key residues, addend inside them
                     if (!resc) {
 #pragma unroll
-                        for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin_s(ar.acc_canon(acc[r]), x[0][r], fc.inv, fc.inv_shoup, fc.inv_d, fc.inv_i);
+                        for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin_s_acc(acc[r], x[0][r], fc.inv, fc.inv_shoup, fc.inv_d, fc.inv_i);
                         if (valid) store_rowC(c01_row, lane, v);
                     } else {
 #pragma unroll
-                        for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin2_s(ar.acc_canon(acc[r]), x[0][r], fc2);
+                        for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin2_s_acc(acc[r], x[0][r], fc2);
                         if (valid) store_rowC(A.out2 + (op * 2 + k) * L1N + (u64)tt * N + rowoff, lane, v);
                     }
                 } else if (!resc) {
 #pragma unroll
-                    for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin(ar.acc_canon(acc[r]), x[0][r], fc.inv, fc.inv_shoup, fc.inv_d, fc.inv_i, av[r]);
+                    for (int r = 0; r < kRowE; ++r) {
+                        if constexpr (kAccForms) v[r] = ar.floor_fin_acc(acc[r], x[0][r], fc.inv, fc.inv_shoup, fc.inv_d, fc.inv_i, av[r]);
+                        else v[r] = ar.floor_fin(ar.acc_canon(acc[r]), x[0][r], fc.inv, fc.inv_shoup, fc.inv_d, fc.inv_i, av[r]);
+                    }
                     if constexpr (GROUPED) {
                         if (into_sum) {
                             if (valid) store_rowC(sum_row, lane, v);
@@ -327,7 +348,10 @@
                     } else if (valid) store_rowC(c01_row, lane, v);
                 } else {
 #pragma unroll
-                    for (int r = 0; r < kRowE; ++r) v[r] = ar.floor_fin2(ar.acc_canon(acc[r]), x[0][r], fc, fc2, av[r]);
+                    for (int r = 0; r < kRowE; ++r) {
+                        if constexpr (kAccForms) v[r] = ar.floor_fin2_acc(acc[r], x[0][r], fc, fc2, av[r]);
+                        else v[r] = ar.floor_fin2(ar.acc_canon(acc[r]), x[0][r], fc, fc2, av[r]);
+                    }
                     if (valid) store_rowC(A.out2 + (op * 2 + k) * L1N + (u64)tt * N + rowoff, lane, v);
                 }
             }
@@ -355,40 +379,42 @@
             // coefficient form) the wave runs the inverse row pass right here and writes the raw rows (special prime -> tpr).
             const bool inv_here = TENSOR || tt == A.L || !A.ckks;
             const bool last = A.logn1 == 0;
-            // (the raw-tail form: polynomial 1's canonical sums wait in the wave's landing buffer -- no row is on its way into it any more, and
+            // (the raw-tail form: polynomial 1's sums wait in the wave's landing buffer -- no row is on its way into it any more, and
             // each lane reads back only what it wrote -- so that the first inverse pass does not run with 32 more live registers than the
-            // digit loop was allocated for)
+            // digit loop was allocated for.  The sums go into the inverse pass in the engine's cheapest form its first stage accepts
+            // (acc_to_inv: the fp64 engine re-centres, no canonical integer in between); a TENSOR launch is never split and always
+            // inverts here.)
             if constexpr (TENSOR) {
 #pragma unroll
-                for (int r = 0; r < kRowE; ++r) stage[wave][(r << 6) | lane] = ar.acc_canon(acc1[r]);
+                for (int r = 0; r < kRowE; ++r) stage[wave][(r << 6) | lane] = ar.acc_park(acc1[r]);
             }
 #pragma unroll 1
             for (int k = 0; k < 2; ++k) {
                 u64 v[kRowE];
+                T x[kRowE];
                 if constexpr (TENSOR) {
                     if (k == 0) {
 #pragma unroll
-                        for (int r = 0; r < kRowE; ++r) v[r] = ar.acc_canon(acc0[r]);
+                        for (int r = 0; r < kRowE; ++r) x[r] = ar.acc_to_inv(acc0[r]);
                     } else {
 #pragma unroll
-                        for (int r = 0; r < kRowE; ++r) v[r] = stage[wave][(r << 6) | lane];
+                        for (int r = 0; r < kRowE; ++r) x[r] = ar.acc_unpark(stage[wave][(r << 6) | lane]);
                     }
                 } else {
                     const Acc *acc = k == 0 ? acc0 : acc1;
 #pragma unroll
                     for (int r = 0; r < kRowE; ++r) v[r] = ar.acc_canon(acc[r]);
-                }
-                if (split > 1) { // a partial sum: k_k3_combine finishes the tile
-                    if (valid) store_rowC(A.part + (((u64)grp * A.n_ops * 2 + op * 2 + k) * (A.L + 1) + tt) * N + rowoff, lane, v);
-                    continue;
-                }
-                if (!inv_here) {
-                    if (valid) store_rowC(A.t + ((op * 2 + k) * A.L + tt) * N + rowoff, lane, v);
-                    continue;
-                }
-                T x[kRowE];
+                    if (split > 1) { // a partial sum: k_k3_combine finishes the tile
+                        if (valid) store_rowC(A.part + (((u64)grp * A.n_ops * 2 + op * 2 + k) * (A.L + 1) + tt) * N + rowoff, lane, v);
+                        continue;
+                    }
+                    if (!inv_here) {
+                        if (valid) store_rowC(A.t + ((op * 2 + k) * A.L + tt) * N + rowoff, lane, v);
+                        continue;
+                    }
 #pragma unroll
-                for (int r = 0; r < kRowE; ++r) x[r] = ar.from_canon(v[r]);
+                    for (int r = 0; r < kRowE; ++r) x[r] = ar.from_canon(v[r]);
+                }
                 wave_rows_inv(ar, P, last, n1 + a_row, lane, lds[wave], x);
 #pragma unroll
                 for (int r = 0; r < kRowE; ++r) v[r] = last ? ar.to_canon(x[r]) : ar.to_raw(x[r]);

@@ -271,6 +271,24 @@ struct ArU64 {
     // and the addend is inside it): t - x * inv, and (t - x) * inv2.  t canonical, x lazy < 4q.
     HE_HD u64 floor_fin_s(u64 t, T x, u64 inv, u64 inv_shoup, double, double) const { return submod(t, mul_pre(x, inv, inv_shoup, q), q); }
     template <class FC> HE_HD u64 floor_fin2_s(u64 t, T x, const FC &f2) const { return mul_pre(t + 2 * two_q - x, f2.inv, f2.inv_shoup, q); }
+    // The same four steps from the accumulator itself (k_k3's epilogue).  This engine's sums are integers already: acc_canon, then the
+    // forms above (ArF64 has a shorter way from its double, and a range to keep for it: floor_prep).
+    static constexpr bool kAccDirect = false;
+    HE_HD void floor_prep(Acc &, T &) const {}
+    HE_HD u64 floor_fin_acc(Acc acc, T x, u64 inv, u64 inv_shoup, double inv_d, double inv_i, u64 addend) const
+    {
+        return floor_fin(acc_canon(acc), x, inv, inv_shoup, inv_d, inv_i, addend);
+    }
+    template <class FC> HE_HD u64 floor_fin2_acc(Acc acc, T x, const FC &f1, const FC &f2, u64 addend) const { return floor_fin2(acc_canon(acc), x, f1, f2, addend); }
+    HE_HD u64 floor_fin_s_acc(Acc acc, T x, u64 inv, u64 inv_shoup, double inv_d, double inv_i) const
+    {
+        return floor_fin_s(acc_canon(acc), x, inv, inv_shoup, inv_d, inv_i);
+    }
+    template <class FC> HE_HD u64 floor_fin2_s_acc(Acc acc, T x, const FC &f2) const { return floor_fin2_s(acc_canon(acc), x, f2); }
+    // a finished sum as the input of the inverse row pass, directly or parked as a 64-bit word in between (k_k3's raw tail)
+    HE_HD T acc_to_inv(Acc acc) const { return from_canon(acc_canon(acc)); }
+    HE_HD u64 acc_park(Acc acc) const { return acc_canon(acc); }
+    HE_HD T acc_unpark(u64 w) const { return from_canon(w); }
     HE_HD T from_canon(u64 x) const { return x; }
     HE_HD T from_raw(u64 bits) const { return bits; }
     HE_HD u64 to_raw(T x) const { return x; }
@@ -526,6 +544,60 @@ struct ArF64 {
     // ... and for sums formed with key residues scaled by s^-1 (see ArU64): t - x * inv, (t - x) * inv2; |x| < q, so both stay inside canon2's range
     HE_HD u64 floor_fin_s(u64 t, T x, u64, u64, double inv_d, double inv_i) const { return to_canon2(u52_to_f64(t) - mulmod_c(x, inv_d, inv_i)); }
     template <class FC> HE_HD u64 floor_fin2_s(u64 t, T x, const FC &f2) const { return to_canon2(mulmod_c(u52_to_f64(t) - x, f2.inv_d, f2.inv_i)); }
+    // ---- the same four steps from the accumulator itself (k_k3's epilogue) -------------------------------------------------------
+    // The forms above take the sum as a canonical integer, so a caller holding it as a double pays acc_canon (13 instructions) and
+    // u52_to_f64 (2) for a value that goes straight back into a double product.  Everything is exact mod q and the result is
+    // canonicalised once at the end, so the product can take the lazy sum as it is -- if it is small enough:
+    //   mulmod_c(y, w, fl(w/q)), 0 <= w < q: the quotient estimate fl(y fl(w/q)) is within |y| 2^-52 of y w / q (two roundings of
+    //   2^-53 each and their product: |y| (2^-52 + 2^-106)), rint adds 1/2, so |result| <= q (1/2 + |y| 2^-52 (1 + 2^-54)); |y| <= 2^50
+    //   gives |result| <= 3q/4 + q 2^-56, far below q, and ONE conditional addition canonicalises it (canon_neg) where canon2's range
+    //   (|.| < 2q) takes three.  (mulmod_c's own comment states the looser |y| 2^-51, which is all its other callers need.)
+    // Every form is exact for integers |acc| <= 2^49 (kFloorAccMax) and |x| <= 2^49 (kFloorXMax):
+    //   floor_fin_acc    y = acc - x, |y| <= 2^50; result + addend within [-3q/4 - 1, 7q/4 + 1]: two fix-ups (canon_1)
+    //   floor_fin2_acc   m1 = mulmod_c(acc, inv1) in (-3q/4, 3q/4); y = m1 + addend - x, |y| < 2^49 + 2q < 2^50; result in (-3q/4, 3q/4):
+    //                    one fix-up
+    //   floor_fin_s_acc  m = mulmod_c(x, inv) in (-3q/4, 3q/4); acc - m is an integer below 2^50 and NOT small: renorm (its quotient
+    //                    estimate is within (2^50 / q) 2^-52 = 1 / (4q) of exact) leaves |r| <= q/2 + 1; one fix-up
+    //   floor_fin2_s_acc y = acc - x; result in (-3q/4, 3q/4): one fix-up
+    // Whether a launch's sums and correction rows stay inside that range is decided on the host from the prime and the number of
+    // accumulated terms (floor_direct_terms below, PrimeDev::acc_terms; wave-uniform in the kernel).  Where they may not, the caller
+    // runs floor_prep over both first: renorm, exact for any integer below 2^52 (as acc_canon's own range), leaves |.| <= q/2 + 1, far
+    // inside the forms' range, at 3 instructions each against the 15 of the canonical round trip.
+    static constexpr bool kAccDirect = true;
+    HE_HD void floor_prep(Acc &acc, T &x) const
+    {
+        acc = renorm(acc);
+        x = renorm(x);
+    }
+    // integer -q < x < q -> [0, q)
+    HE_HD T canon_neg(T x) const { return x < 0.0 ? x + q : x; }
+    // integer -q < x < 2q -> [0, q)
+    HE_HD T canon_1(T x) const
+    {
+        if (x < 0.0) x += q;
+        if (x >= q) x -= q;
+        return x;
+    }
+    HE_HD u64 floor_fin_acc(Acc acc, T x, u64, u64, double inv_d, double inv_i, u64 addend) const
+    {
+        return f64_to_u52(canon_1(mulmod_c(acc - x, inv_d, inv_i) + u52_to_f64(addend)));
+    }
+    template <class FC> HE_HD u64 floor_fin2_acc(Acc acc, T x, const FC &f1, const FC &f2, u64 addend) const
+    {
+        const double m1 = mulmod_c(acc, f1.inv_d, f1.inv_i);
+        return f64_to_u52(canon_neg(mulmod_c(m1 + u52_to_f64(addend) - x, f2.inv_d, f2.inv_i)));
+    }
+    HE_HD u64 floor_fin_s_acc(Acc acc, T x, u64, u64, double inv_d, double inv_i) const
+    {
+        return f64_to_u52(canon_neg(renorm(acc - mulmod_c(x, inv_d, inv_i))));
+    }
+    template <class FC> HE_HD u64 floor_fin2_s_acc(Acc acc, T x, const FC &f2) const { return f64_to_u52(canon_neg(mulmod_c(acc - x, f2.inv_d, f2.inv_i))); }
+    // A finished sum as the input of the inverse row pass (k_k3's raw tail): re-centred, |x| <= q/2 + 1 for any |acc| < 2^52 (three
+    // instructions) -- inside [0, q)'s magnitude, which is what bfly_inv's first stage was sized for -- and parked, where it has to wait,
+    // as the double's own bits.
+    HE_HD T acc_to_inv(Acc acc) const { return renorm(acc); }
+    HE_HD u64 acc_park(Acc acc) const { return to_raw(renorm(acc)); }
+    HE_HD T acc_unpark(u64 w) const { return from_raw(w); }
     HE_HD static double tw_w(const Tw16 &t)
     {
         union { u64 u; double d; } c;
@@ -600,5 +672,41 @@ struct ArF64 {
     HE_HD T renorm(T x) const { return __builtin_fma(-__builtin_rint(x * qinv), q, x); }
     static constexpr bool kNeedsRenormInv = true;
 };
+
+// ---- which launches may take ArF64's direct floor forms (host side; PrimeDev::acc_terms) ----------------------------------------
+// The forms are exact for |acc| <= kFloorAccMax and |x| <= kFloorXMax.  Both magnitudes follow from the prime and the number of
+// accumulated terms, by the growth rule of the fp64 butterfly the kernels already size their 48-bit rows with (fits_48):
+// a stage takes |.| <= m to m + q (1/2 + m 2^-51).
+//   x:   a correction row enters the forward column pass below 4q (a centred or canonical residue of the source prime, re-centred when
+//        the source is wider than 2q, plus at most one centred product of the merged second correction) and runs at most 5 column and
+//        10 row stages.
+//   acc: every term is a mulmod_vv product x * key, key canonical, |product| <= q (1/2 + |x| 2^-51).  The widest x is a digit row:
+//        below 2^47 out of its 48-bit packed form, then 10 row stages.  (The operand products a0 b0 ... and the own digit have
+//        |x| < q.)  `terms` products of that size are the bound of the sum.
+// The library admits fp64-engine primes up to 2^47 and chains up to kMaxPrimes: a 45-bit prime takes 24 terms (L <= 22 with the two
+// operand products of a ct x ct multiply), a 40-bit prime any chain, a 46- or 47-bit prime none (its correction rows alone can pass
+// 2^49) -- those launches re-centre sums and rows first (ArF64::floor_prep).
+constexpr double kFloorAccMax = 562949953421312.0, kFloorXMax = 562949953421312.0; // 2^49
+HE_HD double f64_stage_growth(double m, double q, int stages)
+{
+    for (int s = 0; s < stages; ++s) m += q * (0.5 + m * 4.440892098500626e-16); // 2^-51
+    return m;
+}
+// the bound of one accumulated term under prime q, and the largest number of terms the direct forms accept (0: never)
+HE_HD double floor_term_bound(u64 q)
+{
+    const double qd = (double)q;
+    return qd * (0.5 + f64_stage_growth(140737488355328.0, qd, 10) * 4.440892098500626e-16);
+}
+HE_HD u32 floor_direct_terms(u64 q)
+{
+    const double qd = (double)q;
+    if (q >> 47) return 0; // not an fp64-engine prime
+    if (!(f64_stage_growth(4.0 * qd, qd, 15) <= kFloorXMax)) return 0;
+    const double t = kFloorAccMax / floor_term_bound(q);
+    return t >= 4294967295.0 ? 0xFFFFFFFFu : (u32)t; // (truncation: terms * bound <= 2^49 for every terms <= the result)
+}
+// what the kernel evaluates per tile: `terms` sums under a target prime whose PrimeDev carries acc_terms
+HE_HD bool floor_direct(u32 acc_terms, u32 terms) { return terms <= acc_terms; }
 
 } // namespace he355
