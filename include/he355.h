@@ -285,6 +285,38 @@ uint64_t he355_bfv_digit_count(const he355_ctx *ctx, int L, uint32_t *per_prime,
 int he355_bfv_decompose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_plain);
 int he355_bfv_decompose_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, int L_out, uint64_t *d_plain_ntt);
 int he355_bfv_compose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_plain, uint64_t *d_ct);
+/* ---- a PIR database from packed bytes (BFV contexts only).  The scan, the expansion and the cut above take the database as an [n][L][N]
+ * slab of NTT-form plaintexts; what a user holds is bytes.  These calls are the device path between the two, and the client's way back
+ * after he355_decrypt.  [UPSTREAM-UNVERIFIED] as the decomposition; the definition is this library's own:
+ *     w = bitlen(t) - 1, the digit width of he355_bfv_decompose (2^w <= t: every w-bit value is a plaintext coefficient);
+ *     a plaintext holds B bytes, 1 <= B <= Bmax = floor(N w / 8); the bytes of plaintext j are buf[j stride, j stride + B), read as ONE
+ *     little-endian integer v_j; coefficient e < N of plaintext j is (v_j >> (e w)) & (2^w - 1), which is 0 once e w >= 8 B; the last non-zero
+ *     field is zero-extended and never borrows from bytes at or beyond j stride + B;
+ *     the inverse masks every coefficient to w bits, ORs it in at bit e w and keeps the low 8 B bits.
+ * How records are laid into the B bytes (whole records per plaintext, padding up to stride) is the caller's business.
+ *   he355_bfv_bytes_per_plain   returns Bmax and writes w (field_bits may be null); 0 for a CKKS context.  Host only.
+ *   he355_bfv_unpack_bytes      d_bytes -> d_plain [n][N] coefficients mod t, the layout he355_encrypt and he355_bfv_plain_to_ntt read.
+ *                               d_bytes may be ANY byte address inside a device allocation and stride_bytes any value >= bytes_per_plain: a
+ *                               contiguous byte array with stride = B is a database as it lies.  The kernel reads only aligned 8-byte words
+ *                               that contain at least one valid byte of the plaintext it is working on.  d_plain must be 16-byte
+ *                               aligned (a lane stores two coefficients at once).
+ *   he355_bfv_unpack_bytes_ntt  d_bytes -> d_plain_ntt [n][L_out][N].  By definition bit-identical to he355_bfv_unpack_bytes followed by
+ *                               he355_bfv_plain_to_ntt(L_out, n, ..); the output is the pt(k, j) operand of
+ *                               he355_bfv_multiply_plain_accumulate.  For N >= 2048 the fields are cut and lifted inside the forward column
+ *                               pass (neither the coefficient slab nor the lifted slab exists); N = 1024 runs the two calls, 4096
+ *                               plaintexts at a time through one pool block.
+ *   he355_bfv_pack_bytes        the inverse, d_plain [n][N] -> d_bytes, for the client after he355_decrypt.  It writes whole words,
+ *                               ceil(B / 8) per plaintext, the bytes past B in the last word zero; nothing else inside stride is touched.
+ *                               d_bytes must be 8-byte aligned, stride_bytes a multiple of 8 and at least 8 ceil(B / 8) (two plaintexts never
+ *                               share a word).  The input may be any 64-bit words: each is masked to w bits.
+ * Refused with HE355_E_INVALID_ARGS on the host, before any device is asked for, the output untouched: a CKKS context, L_out outside
+ * 1..L_top, B == 0 or B > Bmax, stride < B, (n - 1) stride + B at or above 2^63 (a checked multiply: no address can wrap), a d_plain of
+ * he355_bfv_unpack_bytes that is not 16-byte aligned, pack's alignment rules, n N / 256 above 2^31 - 1 (one launch's grid), any overlap
+ * of output and input.  n == 0 touches nothing.  Everything is queued on the context's stream. */
+uint64_t he355_bfv_bytes_per_plain(const he355_ctx *ctx, uint32_t *field_bits);
+int he355_bfv_unpack_bytes(he355_ctx *ctx, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain);
+int he355_bfv_unpack_bytes_ntt(he355_ctx *ctx, int L_out, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain_ntt);
+int he355_bfv_pack_bytes(he355_ctx *ctx, uint64_t n, const uint64_t *d_plain, uint64_t bytes_per_plain, uint64_t stride_bytes, void *d_bytes);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

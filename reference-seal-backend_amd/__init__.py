@@ -129,6 +129,10 @@ def lib():
             "he355_bfv_decompose": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_bfv_decompose_ntt": (i32, [vp, i32, i32, u64, vp, i32, vp]),
             "he355_bfv_compose": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_bytes_per_plain": (u64, [vp, C.POINTER(u32)]),
+            "he355_bfv_unpack_bytes": (i32, [vp, u64, vp, u64, u64, vp]),
+            "he355_bfv_unpack_bytes_ntt": (i32, [vp, i32, u64, vp, u64, u64, vp]),
+            "he355_bfv_pack_bytes": (i32, [vp, u64, vp, u64, u64, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -173,7 +177,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -442,6 +446,31 @@ class Context:
     def bfv_compose(self, L, size, n, plain, ct):
         """the inverse of bfv_decompose: plain [n][F][N] -> ct [n][size][L][N], canonical residues whatever the digits"""
         _check(lib().he355_bfv_compose(self.h, L, size, n, plain.ptr, ct.ptr))
+
+    def bfv_bytes_per_plain(self) -> tuple[int, int]:
+        """(Bmax, w): the most bytes one plaintext holds, floor(N w / 8), and the field width w = bitlen(t) - 1 of the byte codec; (0, 0)
+        for a CKKS context (host-side; no device needed)"""
+        w = C.c_uint32(0)
+        return int(lib().he355_bfv_bytes_per_plain(self.h, C.byref(w))), int(w.value)
+
+    @staticmethod
+    def _at(buf, byte_offset):
+        return C.c_void_p(buf.ptr.value + int(byte_offset))
+
+    def bfv_unpack_bytes(self, n, buf, byte_offset, stride_bytes, bytes_per_plain, plain):
+        """the B = bytes_per_plain bytes at byte_offset + j * stride_bytes of `buf` (any offset, any stride >= B), read as one little-endian
+        integer -> plain [n][N]: coefficient e its bits [e w, e w + w)"""
+        _check(lib().he355_bfv_unpack_bytes(self.h, n, self._at(buf, byte_offset), stride_bytes, bytes_per_plain, plain.ptr))
+
+    def bfv_unpack_bytes_ntt(self, L_out, n, buf, byte_offset, stride_bytes, bytes_per_plain, plain_ntt):
+        """bytes -> plain_ntt [n][L_out][N]: bfv_unpack_bytes followed by bfv_plain_to_ntt(L_out, n), fused; the pt operand of
+        bfv_multiply_plain_accumulate"""
+        _check(lib().he355_bfv_unpack_bytes_ntt(self.h, L_out, n, self._at(buf, byte_offset), stride_bytes, bytes_per_plain, plain_ntt.ptr))
+
+    def bfv_pack_bytes(self, n, plain, bytes_per_plain, stride_bytes, buf, byte_offset=0):
+        """the inverse of bfv_unpack_bytes: plain [n][N] (each word masked to w bits) -> ceil(B / 8) whole words per plaintext at
+        byte_offset + j * stride_bytes of `buf` (both multiples of 8), the bytes past B in the last word zero"""
+        _check(lib().he355_bfv_pack_bytes(self.h, n, plain.ptr, bytes_per_plain, stride_bytes, self._at(buf, byte_offset)))
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

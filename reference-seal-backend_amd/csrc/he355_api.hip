@@ -1888,6 +1888,83 @@ public:
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
         HIPCHECK(hipGetLastError());
     }
+    // ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; the definition: bfv_bytes_core.h, include/he355.h) ----------------
+    // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the field width w.
+    // `bytes`: plaintext j at bytes + j stride, B bytes; `words`: [n][per] 64-bit words, per = N (coefficients) or L_out N.  pack: the
+    // bytes are the output, whole 8-byte words of it.
+    static constexpr u64 kBytesChunk = 4096; // N = 1024's routed path: plaintexts per pass through its pool block (32 MiB)
+    static int check_bytes_args(const Params &p, const char *what, u64 n, const void *bytes, u64 stride, u64 B, const u64 *words, int L_out, bool pack)
+    {
+        const std::string s(what);
+        if (L_out < 0 || (size_t)L_out > p.Ltop) throw std::invalid_argument(s + ": level out of range");
+        if (p.plain_modulus < 2) throw std::invalid_argument(s + ": the plain modulus must be at least 2");
+        const int w = bfv_bitlen(p.plain_modulus) - 1;
+        if (B < 1 || B > bfv_bytes_max(p.N, w)) throw std::invalid_argument(s + ": bytes_per_plain must be 1 .. floor(N w / 8) (he355_bfv_bytes_per_plain)");
+        if (stride < B) throw std::invalid_argument(s + ": stride_bytes must be at least bytes_per_plain");
+        const u64 tail = pack ? 8 * bfv_bytes_words(B) : B; // the bytes of the last plaintext the call touches
+        // (n - 1) stride + tail stays below 2^63: neither the range below nor a kernel's j * stride can wrap
+        if (n > 1 && n - 1 > (((u64)1 << 63) - tail) / stride) throw std::invalid_argument(s + ": (n - 1) stride_bytes must be below 2^63");
+        if (!pack && !L_out && ((unsigned long long)words & 15)) throw std::invalid_argument(s + ": d_plain must be 16-byte aligned");
+        if (pack && (((unsigned long long)bytes & 7) || (stride & 7) || stride < tail))
+            throw std::invalid_argument(s + ": d_bytes must be 8-byte aligned and stride_bytes a multiple of 8, at least 8 ceil(bytes_per_plain / 8)");
+        if (n > 0x7fffffffull / (p.N / 256)) throw std::invalid_argument(s + ": too many plaintexts for one launch (n N / 256 must be below 2^31)");
+        if (n) {
+            const unsigned long long b0 = (unsigned long long)bytes, b1 = b0 + (n - 1) * stride + tail;
+            const unsigned long long w0 = (unsigned long long)words, w1 = w0 + n * (L_out ? (u64)L_out : 1) * p.N * 8;
+            if (b1 < b0 || w1 < w0) throw std::invalid_argument(s + ": a range wraps the address space");
+            if (b0 < w1 && w0 < b1) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
+        }
+        return w;
+    }
+    // bytes -> [n][N] coefficients mod t: one streaming launch
+    void bfv_unpack_bytes(u64 n, const void *bytes, u64 stride, u64 B, u64 *plain)
+    {
+        use();
+        const int w = check_bytes_args(P, "he355_bfv_unpack_bytes", n, bytes, stride, B, plain, 0, false);
+        launch_bfv_unpack(env_, w, n, bytes, stride, B, plain);
+        HIPCHECK(hipGetLastError());
+    }
+    // the inverse: [n][N] words, each masked to w bits -> ceil(B / 8) whole words per plaintext
+    void bfv_pack_bytes(u64 n, const u64 *plain, u64 B, u64 stride, void *bytes)
+    {
+        use();
+        const int w = check_bytes_args(P, "he355_bfv_pack_bytes", n, bytes, stride, B, plain, 0, true);
+        launch_bfv_pack(env_, w, n, plain, B, stride, bytes);
+        HIPCHECK(hipGetLastError());
+    }
+    // bytes -> [n][L_out][N], by definition bfv_unpack_bytes + bfv_plain_to_ntt(L_out, n).  N >= 2048: the fused column pass reads the bytes,
+    // cuts, lifts and writes out(j, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is routed to the
+    // composition, kBytesChunk plaintexts at a time through one pool block (a database is large; a second identical call allocates nothing).
+    void bfv_unpack_bytes_ntt(int L_out, u64 n, const void *bytes, u64 stride, u64 B, u64 *out)
+    {
+        use();
+        if (L_out < 1) throw std::invalid_argument("he355_bfv_unpack_bytes_ntt: level out of range");
+        const int w = check_bytes_args(P, "he355_bfv_unpack_bytes_ntt", n, bytes, stride, B, out, L_out, false);
+        const size_t N = P.N;
+        if (!n) return;
+        if (env_.logn1 == 0) {
+            const u64 chunk = n < kBytesChunk ? n : kBytesChunk;
+            u64 *tmp = static_cast<u64 *>(pool_alloc((size_t)chunk * N * 8));
+            try {
+                for (u64 j = 0; j < n; j += chunk) {
+                    const u64 c = n - j < chunk ? n - j : chunk;
+                    u64 *dst = out + (size_t)j * L_out * N;
+                    launch_bfv_unpack(env_, w, c, static_cast<const unsigned char *>(bytes) + j * stride, stride, B, tmp);
+                    launch_bfv_lift_plain(env_, L_out, c, tmp, dst, P.plain_modulus);
+                    launch_ntt_forward(env_, poly_view(dst, L_out, N, L_out), (u32)c);
+                }
+                HIPCHECK(hipGetLastError());
+            } catch (...) {
+                pool_free(tmp);
+                throw;
+            }
+            pool_free(tmp);
+            return;
+        }
+        launch_bfv_bytes_cols_fwd(env_, w, n, bytes, stride, B, L_out, P.plain_modulus, out);
+        launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)n);
+        HIPCHECK(hipGetLastError());
+    }
     const CrtTablesDev &crt_tables(int L)
     {
         return per_level(crt_, L, [&] {
@@ -2593,6 +2670,38 @@ int he355_bfv_compose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t 
         need_bfv(c, "he355_bfv_compose");
         DeviceContext::check_digit_args(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
         dev(c).bfv_compose(L, size, n, plain, ct);
+    });
+}
+uint64_t he355_bfv_bytes_per_plain(const he355_ctx *c, uint32_t *field_bits)
+{
+    if (!c || c->params->scheme != kSchemeBFV || c->params->plain_modulus < 2) return 0;
+    const int w = bfv_bitlen(c->params->plain_modulus) - 1;
+    if (field_bits) *field_bits = (uint32_t)w;
+    return bfv_bytes_max(c->params->N, w);
+}
+int he355_bfv_unpack_bytes(he355_ctx *c, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_unpack_bytes");
+        DeviceContext::check_bytes_args(*c->params, "he355_bfv_unpack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, 0, false);
+        dev(c).bfv_unpack_bytes(n, d_bytes, stride_bytes, bytes_per_plain, d_plain);
+    });
+}
+int he355_bfv_unpack_bytes_ntt(he355_ctx *c, int L_out, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain_ntt)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_unpack_bytes_ntt");
+        if (L_out < 1) throw std::invalid_argument("he355_bfv_unpack_bytes_ntt: level out of range");
+        DeviceContext::check_bytes_args(*c->params, "he355_bfv_unpack_bytes_ntt", n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt, L_out, false);
+        dev(c).bfv_unpack_bytes_ntt(L_out, n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt);
+    });
+}
+int he355_bfv_pack_bytes(he355_ctx *c, uint64_t n, const uint64_t *d_plain, uint64_t bytes_per_plain, uint64_t stride_bytes, void *d_bytes)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_pack_bytes");
+        DeviceContext::check_bytes_args(*c->params, "he355_bfv_pack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, 0, true);
+        dev(c).bfv_pack_bytes(n, d_plain, bytes_per_plain, stride_bytes, d_bytes);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

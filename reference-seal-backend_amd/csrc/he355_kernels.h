@@ -11,6 +11,7 @@
 #include "bfv_level_core.h"
 #include "bfv_noise_core.h"
 #include "bfv_digits_core.h"
+#include "bfv_bytes_core.h"
 
 namespace he355 {
 
@@ -241,6 +242,9 @@ HE355_FWD(launch_bfv_shift)
 HE355_FWD(launch_bfv_digits)
 HE355_FWD(launch_bfv_undigits)
 HE355_FWD(launch_bfv_digits_cols_fwd)
+HE355_FWD(launch_bfv_unpack)
+HE355_FWD(launch_bfv_pack)
+HE355_FWD(launch_bfv_bytes_cols_fwd)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -151,3 +151,15 @@ void launch_bfv_undigits(const KernelEnv &env, const BfvDigitTab &tab, int L, in
 // prime i' < L_out after the column pass (raw of prime i'), what launch_bfv_lift_plain + launch_cols_fwd would have left there;
 // launch_rows_fwd finishes it in place.  N >= 2048 only (N = 1024 has no column pass).
 void launch_bfv_digits_cols_fwd(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *ct, int L_out, u64 t, u64 *out);
+// ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; arithmetic: bfv_bytes_core.h) --------------------------------------------
+// Plaintext j is the B bytes at bytes + j stride read as one little-endian integer, coefficient e its bits [e w, e w + w).  `bytes` of
+// launch_bfv_unpack / launch_bfv_bytes_cols_fwd is any byte address and stride any value >= B: only aligned 8-byte words that hold a valid
+// byte of the plaintext at hand are read.  plain [n][N] coefficients mod t.  One launch each; the two sides may not overlap.
+void launch_bfv_unpack(const KernelEnv &env, int w, u64 n, const void *bytes, u64 stride, u64 B, u64 *plain);
+// the inverse: ceil(B / 8) whole words per plaintext, the bytes past B in the last one zero; `bytes` 8-byte aligned, stride a multiple of 8
+// and at least 8 ceil(B / 8); every input word is masked to w bits
+void launch_bfv_pack(const KernelEnv &env, int w, u64 n, const u64 *plain, u64 B, u64 stride, void *bytes);
+// The forward column pass of the plaintexts' transforms, out of place: bytes -> out [n][L_out][N], the centred lift of plaintext j under
+// prime i' < L_out after the column pass (raw of prime i'), what launch_bfv_unpack + launch_bfv_lift_plain + launch_cols_fwd would have left
+// there; launch_rows_fwd finishes it in place.  N >= 2048 only (N = 1024 has no column pass).
+void launch_bfv_bytes_cols_fwd(const KernelEnv &env, int w, u64 n, const void *bytes, u64 stride, u64 B, int L_out, u64 t, u64 *out);
