@@ -285,6 +285,53 @@ uint64_t he355_bfv_digit_count(const he355_ctx *ctx, int L, uint32_t *per_prime,
 int he355_bfv_decompose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_plain);
 int he355_bfv_decompose_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, int L_out, uint64_t *d_plain_ntt);
 int he355_bfv_compose(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_plain, uint64_t *d_ct);
+/* ---- the external product RGSW(m) [.] BFV(mu) -> BFV(m mu) (BFV contexts only, every L in 1..L_top).  The later dimensions of a PIR
+ * (OnionPIR, Spiral) select with it instead of cutting ciphertexts into plaintexts: its noise grows additively, so the reply stays ONE
+ * ciphertext and the client decrypts once.  No special prime is involved.  [UPSTREAM-UNVERIFIED] as the decomposition above; the definition is
+ * this library's own:
+ *     gadget table at level L: digit_bits = v in 1..63 (the caller's choice: noise against work), b_i = bitlen(q_i), E_i = ceil(b_i / v),
+ *     off_i = sum_{i' < i} E_i', E(L) = off_L;
+ *     digit g < E_i of a canonical residue x under prime i is (x >> (g v)) & (2^v - 1) as a NON-NEGATIVE integer (no centred lift: d - t equals
+ *     d mod t only, and the identity below holds mod q);
+ *     gadget element G_(i,g) is 2^(g v) mod q_i under prime i and 0 under every other prime, so for every canonical RNS value
+ *     x == sum_(i,g) digit_(i,g)(x_i) G_(i,g) (mod q_L);
+ *     polynomial k, prime i, digit g of ciphertext r is digit polynomial r size E(L) + k E(L) + off_i + g (he355_bfv_decompose's order);
+ *     an RGSW ciphertext at level L is [2 E(L)][2][L][N] in NTT form, row f = k E(L) + off_i + g: row f of RGSW r is
+ *     he355_encrypt_zero(seed, first_index + r 2 E(L) + f) with its polynomials cut to the first L primes (dropping RNS components of an
+ *     encryption of zero leaves one), plus lift(m) 2^(g v) mod q_i in polynomial k under prime i only -- lift the centred lift of
+ *     he355_bfv_multiply_plain over all N coefficients of m (mod t) -- transformed in he355_ntt_forward's bit order;
+ *     rgsw [.] ct = sum_{f < 2 E(L)} NTT_j(digit_f(ct)) (.) row_f(rgsw) per prime j < L and both polynomials, NTT_j(digit_f) the digit
+ *     polynomial (the same integers under every prime, reduced mod q_j where v >= b_j) transformed under prime j; the sum is the canonical
+ *     residue of the exact integer sum (128-bit unreduced runs, as he355_bfv_multiply_plain_accumulate).
+ * If ct has phase Delta mu + e, the result has phase m (Delta mu + e) + sum_f digit_f e_f.
+ *   he355_bfv_gadget_count          returns E(L) and writes E_0 .. E_(L-1) (at most cap entries); 0 for a CKKS context, a bad L or a bad v.
+ *                                   Host only.
+ *   he355_bfv_gadget_decompose      d_ct [n][size][L][N] coefficient form -> d_digits [n][size E][N], coefficient form; size 1..3; one launch.
+ *   he355_bfv_gadget_decompose_ntt  -> d_digits_ntt [n][size E][L][N].  By definition bit-identical to he355_bfv_gadget_decompose followed by
+ *                                   he355_ntt_forward of every digit polynomial under every prime j < L.  For N >= 2048 a block of the forward
+ *                                   column pass reads each ciphertext word once and walks all of its digits and output primes; N = 1024 writes
+ *                                   the digits under every prime and transforms in place.  No scratch.
+ *   he355_bfv_rgsw_encrypt          d_plain [n][N] mod t -> d_rgsw [n][2E][2][L][N]; needs he355_set_public_key.  At L < L_top the top-level
+ *                                   encryptions of zero live in one pool block.
+ *   he355_bfv_external_product      d_out(r) = sum_{kappa < inner} rgsw(r, kappa) [.] ct(r, kappa), [n][2][L][N], COEFFICIENT form in and out: it
+ *                                   feeds he355_bfv_mod_switch, he355_decrypt or the next external product of a selection tree as it lies.
+ *                                   Ciphertext (r, kappa) ([2][L][N]) at index r ct_stride_r + kappa ct_stride_k of d_ct, RGSW (r, kappa) at
+ *                                   r rg_stride_r + kappa rg_stride_k of d_rgsw; rg_stride_r == 0: all results share one selector row.  By
+ *                                   definition bit-identical to he355_bfv_gadget_decompose_ntt of the inner ciphertexts of each result,
+ *                                   he355_bfv_multiply_plain_accumulate(L, 2, 1, 1, inner 2E, ..) per result with the RGSW rows as the ciphertext
+ *                                   operand and the digits as the plaintext operand, and he355_bfv_transform_from_ntt.  The digit slab is one
+ *                                   pool block, the results split into passes of about 4096 digit polynomials (never fewer than one result).
+ * Refused with HE355_E_INVALID_ARGS on the host, before any launch, the output untouched: a CKKS context, L outside 1..L_top, digit_bits
+ * outside 1..63, size outside 1..3, inner == 0 or inner 2 E(L) above 2^31 - 1, more polynomials than one launch's grid holds, strides that
+ * take an operand past 2^60 words, any overlap of the output with an input (all of these before any device is asked for), and
+ * he355_bfv_rgsw_encrypt without a public key.  n == 0 touches nothing.  Everything is queued on the context's stream; a second identical
+ * call makes no raw allocation. */
+uint64_t he355_bfv_gadget_count(const he355_ctx *ctx, int L, int digit_bits, uint32_t *per_prime, uint64_t cap);
+int he355_bfv_gadget_decompose(he355_ctx *ctx, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits);
+int he355_bfv_gadget_decompose_ntt(he355_ctx *ctx, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits_ntt);
+int he355_bfv_rgsw_encrypt(he355_ctx *ctx, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw);
+int he355_bfv_external_product(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
+                               const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_k, uint64_t *d_out);
 /* ---- a PIR database from packed bytes (BFV contexts only).  The scan, the expansion and the cut above take the database as an [n][L][N]
  * slab of NTT-form plaintexts; what a user holds is bytes.  These calls are the device path between the two, and the client's way back
  * after he355_decrypt.  [UPSTREAM-UNVERIFIED] as the decomposition; the definition is this library's own:

@@ -129,6 +129,11 @@ def lib():
             "he355_bfv_decompose": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_bfv_decompose_ntt": (i32, [vp, i32, i32, u64, vp, i32, vp]),
             "he355_bfv_compose": (i32, [vp, i32, i32, u64, vp, vp]),
+            "he355_bfv_gadget_count": (u64, [vp, i32, i32, C.POINTER(u32), u64]),
+            "he355_bfv_gadget_decompose": (i32, [vp, i32, i32, i32, u64, vp, vp]),
+            "he355_bfv_gadget_decompose_ntt": (i32, [vp, i32, i32, i32, u64, vp, vp]),
+            "he355_bfv_rgsw_encrypt": (i32, [vp, i32, i32, u64, vp, u64, u64, vp]),
+            "he355_bfv_external_product": (i32, [vp, i32, i32, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_bytes_per_plain": (u64, [vp, C.POINTER(u32)]),
             "he355_bfv_unpack_bytes": (i32, [vp, u64, vp, u64, u64, vp]),
             "he355_bfv_unpack_bytes_ntt": (i32, [vp, i32, u64, vp, u64, u64, vp]),
@@ -177,7 +182,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -446,6 +451,34 @@ class Context:
     def bfv_compose(self, L, size, n, plain, ct):
         """the inverse of bfv_decompose: plain [n][F][N] -> ct [n][size][L][N], canonical residues whatever the digits"""
         _check(lib().he355_bfv_compose(self.h, L, size, n, plain.ptr, ct.ptr))
+
+    def bfv_gadget_count(self, L: int, digit_bits: int) -> tuple[int, list[int]]:
+        """(E(L), [E_0 .. E_(L-1)]): the digits of width digit_bits (1..63) a residue under each prime of level L is cut into for the external
+        product; an RGSW ciphertext has 2 E(L) rows.  (0, []) for a CKKS context, a bad level or a bad width (host-side; no device needed)"""
+        buf = (C.c_uint32 * 64)()
+        total = int(lib().he355_bfv_gadget_count(self.h, L, digit_bits, buf, 64))
+        return total, [int(x) for x in buf[:L]] if total else []
+
+    def bfv_gadget_decompose(self, L, digit_bits, size, n, ct, digits):
+        """ct [n][size][L][N] coefficient form -> digits [n][size E][N]: the plain integer digits (no centred lift), polynomial k, prime i,
+        digit g at k E(L) + off_i + g"""
+        _check(lib().he355_bfv_gadget_decompose(self.h, L, digit_bits, size, n, ct.ptr, digits.ptr))
+
+    def bfv_gadget_decompose_ntt(self, L, digit_bits, size, n, ct, digits_ntt):
+        """ct [n][size][L][N] -> digits_ntt [n][size E][L][N]: bfv_gadget_decompose, then ntt_forward of every digit polynomial under every
+        prime of the level (a digit not below q_j reduced first), fused"""
+        _check(lib().he355_bfv_gadget_decompose_ntt(self.h, L, digit_bits, size, n, ct.ptr, digits_ntt.ptr))
+
+    def bfv_rgsw_encrypt(self, L, digit_bits, n, plain, seed, first_index, rgsw):
+        """plain [n][N] mod t -> rgsw [n][2E][2][L][N] NTT form: row f of RGSW r is encrypt_zero(seed, first_index + r 2E + f) cut to L primes
+        plus lift(m) 2^(g v) in polynomial k under prime i (f = k E + off_i + g); needs set_public_key"""
+        _check(lib().he355_bfv_rgsw_encrypt(self.h, L, digit_bits, n, plain.ptr, seed, first_index, rgsw.ptr))
+
+    def bfv_external_product(self, L, digit_bits, n, inner, ct, ct_stride_r, ct_stride_k, rgsw, rg_stride_r, rg_stride_k, out):
+        """out(r) = sum_kappa rgsw(r, kappa) [.] ct(r, kappa), [n][2][L][N], coefficient form in and out; ciphertext (r, kappa) at index
+        r ct_stride_r + kappa ct_stride_k, RGSW (r, kappa) at r rg_stride_r + kappa rg_stride_k (rg_stride_r == 0: one selector row for all)"""
+        _check(lib().he355_bfv_external_product(self.h, L, digit_bits, n, inner, ct.ptr, ct_stride_r, ct_stride_k, rgsw.ptr, rg_stride_r,
+                                                rg_stride_k, out.ptr))
 
     def bfv_bytes_per_plain(self) -> tuple[int, int]:
         """(Bmax, w): the most bytes one plaintext holds, floor(N w / 8), and the field width w = bitlen(t) - 1 of the byte codec; (0, 0)

@@ -1888,6 +1888,151 @@ public:
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
         HIPCHECK(hipGetLastError());
     }
+    // ---- the external product RGSW x ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) ----------
+    // The argument checks that need no device: the C ABI makes them before it asks for one.  Each returns the gadget table of level L.
+    static constexpr u64 kGadgetPassPolys = 4096; // digit polynomials one pass of he355_bfv_external_product holds in its pool block
+    static u64 gadget_poly_blocks(const Params &p, bool cols) { return cols && p.N > 1024 ? 4 : p.N / 512; } // blocks per residue polynomial
+    static BfvDigitTab gadget_table(const Params &p, const std::string &w, int L, int v)
+    {
+        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+        if (!bfv_gadget_width_ok(v)) throw std::invalid_argument(w + ": digit_bits must be 1..63");
+        u64 q[kMaxPrimes];
+        for (int i = 0; i < L; ++i) q[i] = p.primes[i].q;
+        return bfv_gadget_table(q, L, v);
+    }
+    // `ct` [n][size][L][N] -> `digits` [n][size E][N] (ntt false) or [n][size E][L][N]
+    static BfvDigitTab check_gadget_cut_args(const Params &p, const char *what, int L, int v, int size, u64 n, const u64 *ct, const u64 *digits, bool ntt)
+    {
+        const std::string w(what);
+        const BfvDigitTab tab = gadget_table(p, w, L, v);
+        check_size(size, 1, 3);
+        const u64 F = (u64)size * tab.total;
+        if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many digit polynomials for one call (n size E must be below 2^32)");
+        if (n * size * L > 0x7fffffffull / gadget_poly_blocks(p, ntt)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+        if (ranges_overlap(ct, (size_t)n * size * L * p.N, digits, (size_t)n * F * (ntt ? L : 1) * p.N)) throw std::invalid_argument(w + ": the digits overlap the ciphertexts");
+        return tab;
+    }
+    static BfvDigitTab check_rgsw_args(const Params &p, int L, int v, u64 n, const u64 *plain, const u64 *out)
+    {
+        const std::string w("he355_bfv_rgsw_encrypt");
+        const BfvDigitTab tab = gadget_table(p, w, L, v);
+        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+        const u64 per = 2 * (u64)tab.total * 2 * L; // residue polynomials of one RGSW ciphertext
+        if (n > 0x7fffffffull / (per * (p.N / 512))) throw std::invalid_argument(w + ": too many RGSW ciphertexts for one launch");
+        if (ranges_overlap(plain, (size_t)n * p.N, out, (size_t)n * per * p.N)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the plaintexts");
+        return tab;
+    }
+    // the words from the first operand of a batch to the end of the last one it touches, ((n - 1) stride_r + (inner - 1) stride_k + 1) items of
+    // `item_words` each, formed in 128 bits and refused where they cannot lie in one address space
+    static size_t gadget_span_words(const std::string &w, u64 n, u64 inner, u64 stride_r, u64 stride_k, u64 item_words)
+    {
+        const u128 items = (u128)(n - 1) * stride_r + (u128)(inner - 1) * stride_k + 1;
+        if (items > ((u128)1 << 60) || items * item_words > ((u128)1 << 60)) throw std::invalid_argument(w + ": a stride takes the operands past 2^60 words");
+        return (size_t)(items * item_words);
+    }
+    static BfvDigitTab check_external_product_args(const Params &p, int L, int v, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw,
+                                                   u64 rg_stride_r, u64 rg_stride_k, const u64 *out)
+    {
+        const std::string w("he355_bfv_external_product");
+        const BfvDigitTab tab = gadget_table(p, w, L, v);
+        const u64 rows = 2 * (u64)tab.total;
+        if (inner < 1 || inner > 0x7fffffffull / rows) throw std::invalid_argument(w + ": inner must be at least 1 and inner 2 E(L) below 2^31");
+        if (!n) return tab;
+        const u64 terms = inner * rows, pass = bfv_gadget_pass(terms, n, kGadgetPassPolys);
+        if (n > 0x7fffffffull || pass * inner * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, true) || pass * L > 0x7fffffffull / (p.N / 512))
+            throw std::invalid_argument(w + ": too many polynomials for one launch");
+        const size_t ctn = 2 * (size_t)L * p.N;
+        if (ranges_overlap(out, n * ctn, ct, gadget_span_words(w, n, inner, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the ciphertexts");
+        if (ranges_overlap(out, n * ctn, rgsw, gadget_span_words(w, n, inner, rg_stride_r, rg_stride_k, rows * ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the RGSW ciphertexts");
+        return tab;
+    }
+    // [n][size][L][N] -> [n][size E][N], the plain integer digits of width v: he355_bfv_decompose's launch with the width-v table
+    void bfv_gadget_decompose(int L, int v, int size, u64 n, const u64 *ct, u64 *digits)
+    {
+        use();
+        const BfvDigitTab tab = check_gadget_cut_args(P, "he355_bfv_gadget_decompose", L, v, size, n, ct, digits, false);
+        launch_bfv_digits(env_, tab, L, size, n, ct, digits);
+        HIPCHECK(hipGetLastError());
+    }
+    // the cut of ciphertext (a, b) at index a stride_a + b stride_b into NTT-form digit polynomials [(a n_b + b) size E + f][L][N]: N >= 2048 the
+    // fused column pass and the row pass in place, N = 1024 the digits under every prime and the whole transform in place.  No scratch.
+    // ROUTED: a block of the column pass walks all E_i L digit columns of its residue one after the other, so a batch of fewer blocks than
+    // kGadgetColsMinBlocks (one per CU) leaves most of the chip idle and lost to the composition where it was measured (one ciphertext:
+    // profiles/bfv_external_product.txt); such a batch takes N = 1024's path, whose work is spread over the digit polynomials.
+    static constexpr u64 kGadgetColsMinBlocks = 256;
+    void gadget_cut_ntt(const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out)
+    {
+        const u32 items = (u32)(n_a * n_b * size * tab.total);
+        const bool cols = env_.logn1 != 0 && n_a * n_b * size * L * 4 >= kGadgetColsMinBlocks;
+        launch_bfv_gadget_cut(env_, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out, cols);
+        if (cols) launch_rows_fwd(env_, poly_view(out, L, P.N, L), items);
+        else launch_ntt_forward(env_, poly_view(out, L, P.N, L), items);
+    }
+    // [n][size][L][N] -> [n][size E][L][N]: by definition bfv_gadget_decompose, then he355_ntt_forward of every digit polynomial under every prime
+    void bfv_gadget_decompose_ntt(int L, int v, int size, u64 n, const u64 *ct, u64 *out)
+    {
+        use();
+        const BfvDigitTab tab = check_gadget_cut_args(P, "he355_bfv_gadget_decompose_ntt", L, v, size, n, ct, out, true);
+        if (!n) return;
+        gadget_cut_ntt(tab, L, size, n, 1, ct, 1, 0, out);
+        HIPCHECK(hipGetLastError());
+    }
+    // plain [n][N] mod t -> out [n][2E][2][L][N] NTT form: row f of RGSW r is he355_encrypt_zero(seed, first_index + r 2E + f) cut to the first L
+    // primes, plus the planted term.  L == L_top: the zeros are made where the rows lie; below, in one pool block.
+    void bfv_rgsw_encrypt(int L, int v, u64 n, const u64 *plain, u64 seed, u64 first_index, u64 *out)
+    {
+        use();
+        const BfvDigitTab tab = check_rgsw_args(P, L, v, n, plain, out);
+        if (!n) return;
+        if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt: public key not set");
+        const size_t N = P.N, Lt = P.Ltop;
+        const u64 rows = n * 2 * tab.total;
+        u64 *tmp = (size_t)L < Lt ? static_cast<u64 *>(pool_alloc((size_t)rows * 2 * Lt * N * 8)) : nullptr;
+        try {
+            u64 *zero = tmp ? tmp : out;
+            encrypt(rows, nullptr, seed, first_index, zero);
+            launch_bfv_rgsw_plant(env_, tab, L, (int)Lt, n, zero, plain, P.plain_modulus, out);
+            launch_ntt_forward(env_, poly_view(out, L, N, L), (u32)(rows * 2));
+            HIPCHECK(hipGetLastError());
+        } catch (...) {
+            if (tmp) pool_free(tmp);
+            throw;
+        }
+        if (tmp) pool_free(tmp);
+    }
+    // out(r) = sum_kappa rgsw(r, kappa) [.] ct(r, kappa), coefficient form in and out.  By definition bfv_gadget_decompose_ntt of the inner
+    // ciphertexts of each result, he355_bfv_multiply_plain_accumulate(L, 2, 1, 1, inner 2E) with the RGSW rows as the ciphertext operand, and
+    // he355_bfv_transform_from_ntt.  The digit slab of a pass of results (bfv_gadget_pass: about kGadgetPassPolys digit polynomials, at least
+    // one result) is one pool block; a pass is the cut, its row pass and one batched multiply-accumulate; one inverse transform ends the call.
+    void bfv_external_product(int L, int v, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out)
+    {
+        use();
+        const BfvDigitTab tab = check_external_product_args(P, L, v, n, inner, ct, ct_stride_r, ct_stride_k, rgsw, rg_stride_r, rg_stride_k, out);
+        if (!n) return;
+        const size_t N = P.N, LN = (size_t)L * N;
+        const u32 rows = 2 * tab.total;
+        const u64 terms = inner * rows, pass = bfv_gadget_pass(terms, n, kGadgetPassPolys);
+        u64 *slab = static_cast<u64 *>(pool_alloc((size_t)pass * terms * LN * 8));
+        try {
+            for (u64 r0 = 0; r0 < n; r0 += pass) {
+                const u64 c = std::min<u64>(pass, n - r0);
+                gadget_cut_ntt(tab, L, 2, c, inner, ct + r0 * ct_stride_r * 2 * LN, ct_stride_r, ct_stride_k, slab);
+                const u64 *rg = rgsw + r0 * rg_stride_r * rows * 2 * LN;
+                // ROUTED: a call for ONE result whose RGSW rows follow one another is the composition's own inner product, and
+                // k_bfv_plain_mac's 1 x 1 form (two terms' loads in flight) measured 2-17 % ahead of k_bfv_gadget_mac there
+                // (profiles/bfv_external_product.txt).  Only n == 1 was measured, so only n == 1 is routed: a pass that holds one result
+                // of many (inner 2E above 2048, or a ragged last pass) stays with k_bfv_gadget_mac.
+                if (n == 1 && (inner == 1 || rg_stride_k == 1)) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab, 1, 1, out + r0 * 2 * LN);
+                else launch_bfv_gadget_mac(env_, L, c, inner, rows, slab, rg, rg_stride_r, rg_stride_k, out + r0 * 2 * LN);
+            }
+            launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
+            HIPCHECK(hipGetLastError());
+        } catch (...) {
+            pool_free(slab);
+            throw;
+        }
+        pool_free(slab);
+    }
     // ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; the definition: bfv_bytes_core.h, include/he355.h) ----------------
     // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the field width w.
     // `bytes`: plaintext j at bytes + j stride, B bytes; `words`: [n][per] 64-bit words, per = N (coefficients) or L_out N.  pack: the
@@ -2670,6 +2815,48 @@ int he355_bfv_compose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t 
         need_bfv(c, "he355_bfv_compose");
         DeviceContext::check_digit_args(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
         dev(c).bfv_compose(L, size, n, plain, ct);
+    });
+}
+uint64_t he355_bfv_gadget_count(const he355_ctx *c, int L, int digit_bits, uint32_t *per_prime, uint64_t cap)
+{
+    if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || !bfv_gadget_width_ok(digit_bits)) return 0;
+    u64 q[kMaxPrimes];
+    for (int i = 0; i < L; ++i) q[i] = c->params->primes[i].q;
+    const BfvDigitTab tab = bfv_gadget_table(q, L, digit_bits);
+    for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
+    return tab.total;
+}
+int he355_bfv_gadget_decompose(he355_ctx *c, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_gadget_decompose");
+        DeviceContext::check_gadget_cut_args(*c->params, "he355_bfv_gadget_decompose", L, digit_bits, size, n, d_ct, d_digits, false);
+        dev(c).bfv_gadget_decompose(L, digit_bits, size, n, d_ct, d_digits);
+    });
+}
+int he355_bfv_gadget_decompose_ntt(he355_ctx *c, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits_ntt)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_gadget_decompose_ntt");
+        DeviceContext::check_gadget_cut_args(*c->params, "he355_bfv_gadget_decompose_ntt", L, digit_bits, size, n, d_ct, d_digits_ntt, true);
+        dev(c).bfv_gadget_decompose_ntt(L, digit_bits, size, n, d_ct, d_digits_ntt);
+    });
+}
+int he355_bfv_rgsw_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_rgsw_encrypt");
+        DeviceContext::check_rgsw_args(*c->params, L, digit_bits, n, d_plain, d_rgsw);
+        dev(c).bfv_rgsw_encrypt(L, digit_bits, n, d_plain, seed, first_index, d_rgsw);
+    });
+}
+int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
+                               const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_k, uint64_t *d_out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_external_product");
+        DeviceContext::check_external_product_args(*c->params, L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
+        dev(c).bfv_external_product(L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
     });
 }
 uint64_t he355_bfv_bytes_per_plain(const he355_ctx *c, uint32_t *field_bits)

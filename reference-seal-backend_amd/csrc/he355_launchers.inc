@@ -163,3 +163,15 @@ void launch_bfv_pack(const KernelEnv &env, int w, u64 n, const u64 *plain, u64 B
 // prime i' < L_out after the column pass (raw of prime i'), what launch_bfv_unpack + launch_bfv_lift_plain + launch_cols_fwd would have left
 // there; launch_rows_fwd finishes it in place.  N >= 2048 only (N = 1024 has no column pass).
 void launch_bfv_bytes_cols_fwd(const KernelEnv &env, int w, u64 n, const void *bytes, u64 stride, u64 B, int L_out, u64 t, u64 *out);
+// ---- the BFV external product RGSW x ciphertext (he355_kernels_bfv_gadget.hip; arithmetic: bfv_gadget_core.h, bfv_mac_core.h) ----------------
+// The gadget cut in NTT form: ciphertext (a, b), a < n_a, b < n_b, at index a stride_a + b stride_b of `ct` ([size][L][N], coefficient
+// form) -> out [(a n_b + b) size E + f][L][N], digit polynomial f = k E(L) + off_i + g under every prime j < L (`tab`: bfv_gadget_table of the
+// level).  cols (N >= 2048 only): the forward column pass (raw columns; launch_rows_fwd finishes in place).  Else: the digits in coefficient
+// form (launch_ntt_forward follows in place).
+void launch_bfv_gadget_cut(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out, bool cols);
+// out[r] = sum_(kappa < inner) sum_(f < rows) dig[r][kappa][f] (.) row f of RGSW (r, kappa), both polynomials, canonical NTT form: dig
+// [n][inner][rows][L][N], RGSW (r, kappa) at index r rg_stride_r + kappa rg_stride_k of `rgsw`, [rows][2][L][N] each; out [n][2][L][N].
+void launch_bfv_gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out);
+// zero [n 2E][2][L_in][N] encryptions of zero (coefficient form, L_in >= L), plain [n][N] mod t -> out [n 2E][2][L][N]: the first L primes of
+// each row plus lift(m) 2^(g v) mod q_i in polynomial k under prime i of row k E + off_i + g.  In place (out == zero) when L_in == L.
+void launch_bfv_rgsw_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, const u64 *zero, const u64 *plain, u64 t, u64 *out);
