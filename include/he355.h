@@ -332,6 +332,48 @@ int he355_bfv_gadget_decompose_ntt(he355_ctx *ctx, int L, int digit_bits, int si
 int he355_bfv_rgsw_encrypt(he355_ctx *ctx, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw);
 int he355_bfv_external_product(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
                                const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_k, uint64_t *d_out);
+/* ---- RGSW selectors from ONE packed query ciphertext (BFV contexts only, every L in 1..L_top).  An RGSW ciphertext is [2E][2][L][N] words, and a
+ * query of the external-product route carries one per index of a later dimension.  As in OnionPIR and Spiral the client instead packs the
+ * selectors' gadget components into coefficients of a query ciphertext, the server expands it with he355_bfv_expand and turns each group of E
+ * children into an RGSW ciphertext with one external product by RGSW(s), a key the client sends once.  Notation as above: v the digit width, E_i,
+ * off_i, E = E(L), row f = k E + off_i + g, lift the centred lift; a selector is a scalar m in [0, t), the RGSW message the constant polynomial m.
+ * [UPSTREAM-UNVERIFIED] as the external product; the definition is this library's own.
+ *   he355_bfv_selector_encrypt    (client) d_sel [n][n_sel] mod t -> d_out [n][2][L][N], coefficient form.  With d = ceil(log2 count), the d of
+ *                                 he355_bfv_expand(.., count, ..): ciphertext r is he355_encrypt_zero(seed, first_index + r) cut to the first L
+ *                                 primes, and for every selector b < n_sel, prime i < L and digit g < E_i the coefficient
+ *                                 first_slot + b E + off_i + g of polynomial 0 under prime i ONLY receives
+ *                                 lift(m_(r,b)) 2^(g v) (2^d)^(-1) mod q_i; nothing else changes.  After he355_bfv_expand(L, n, .., count, ..) child
+ *                                 first_slot + b E + off_i + g has phase lift(m) G_(i,g) plus noise: row (k = 0, i, g) of RGSW(m) before its
+ *                                 transform.  No Delta is involved.  first_slot and count let the caller he355_add the result onto an
+ *                                 he355_encrypt of the first dimension's one-hot plaintext: first dimension and selectors travel in ONE
+ *                                 ciphertext.  Needs he355_set_public_key.  At L < L_top the top-level encryptions of zero live in one pool block.
+ *   he355_bfv_rgsw_encrypt_secret (client, once per key) d_rgsw [2 E_key][2][L][N], E_key = E(L) at width key_bits.  By definition bit-identical to
+ *                                 he355_bfv_rgsw_encrypt(L, key_bits, 1, d_plain, seed, first_index, ..) with d_plain the secret key's coefficients
+ *                                 mod t: 0, 1, and t - 1 for -1.  The context holds s in NTT form (he355_set_secret_key) and brings it to
+ *                                 coefficients itself; needs both keys.  Publishing an encryption of s under s is the usual CIRCULAR-SECURITY
+ *                                 assumption of these schemes (as for relinearization keys); the library does not weaken or strengthen it.
+ *   he355_bfv_rgsw_from_bfv       (server) d_rgsw [n][n_sel][2E][2][L][N], NTT form.  Slot f < E of selector (r, b) is the coefficient-form
+ *                                 ciphertext at index r ct_stride_r + (b E + f) ct_stride_k of d_ct; after he355_bfv_expand with nq queries:
+ *                                 ct_stride_r = 1, ct_stride_k = nq, d_ct at child first_slot.  By definition bit-identical to: row f (k = 0) of
+ *                                 RGSW (r, b) is he355_bfv_transform_to_ntt of the slot-f ciphertext, row E + f (k = 1) is
+ *                                 he355_bfv_transform_to_ntt of he355_bfv_external_product(L, key_bits, 1, 1, that ciphertext, .., d_key, 0, 1, ..):
+ *                                 RGSW(s) [.] C has phase s phase(C) plus gadget noise, so the k = 1 row carries m G s.  digit_bits (the output's
+ *                                 gadget) and key_bits (the conversion's) are independent; a narrow key_bits buys quiet k = 1 rows once per query.
+ *                                 Fused: the multiply-accumulate leaves its NTT-form sums in the k = 1 rows as they are (the inverse transform
+ *                                 and the transform back are never run), and for N >= 2048 the column pass that cuts the key_bits digits also
+ *                                 emits the slot's own column, so the children are read once for both halves.  N = 1024 and calls whose first
+ *                                 pass is below he355_bfv_gadget_decompose_ntt's 256-block rule stream instead.  The digit slab is one pool block,
+ *                                 split into passes of about 4096 digit polynomials (never less than one slot ciphertext).
+ * Refused with HE355_E_INVALID_ARGS on the host, before any launch, the output untouched: a CKKS context, L outside 1..L_top, digit_bits or
+ * key_bits outside 1..63, n_sel == 0, count outside 1..N, first_slot + n_sel E > count, strides that take an operand past 2^60 words, more
+ * polynomials than one launch's grid holds, any overlap of the output with an input (all of these before any device is asked for), and a
+ * missing public or secret key where one is needed (the message says which).  n == 0 touches nothing.  Everything is queued on the context's
+ * stream; a second identical call makes no raw allocation. */
+int he355_bfv_selector_encrypt(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel,
+                               uint64_t seed, uint64_t first_index, uint64_t *d_out);
+int he355_bfv_rgsw_encrypt_secret(he355_ctx *ctx, int L, int key_bits, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw);
+int he355_bfv_rgsw_from_bfv(he355_ctx *ctx, int L, int digit_bits, int key_bits, uint64_t n, uint64_t n_sel, const uint64_t *d_ct, uint64_t ct_stride_r,
+                            uint64_t ct_stride_k, const uint64_t *d_key, uint64_t *d_rgsw);
 /* ---- a PIR database from packed bytes (BFV contexts only).  The scan, the expansion and the cut above take the database as an [n][L][N]
  * slab of NTT-form plaintexts; what a user holds is bytes.  These calls are the device path between the two, and the client's way back
  * after he355_decrypt.  [UPSTREAM-UNVERIFIED] as the decomposition; the definition is this library's own:

@@ -12,6 +12,11 @@
 //   plant   : row f = k E(L) + off_i + g of RGSW(m) is an encryption of zero plus lift(m) 2^(g v) mod q_i in polynomial k under prime i;
 //             lift is bfv_level_core.h's centred lift, and 2^(g v) <= 2^(b_i - 1) < q_i is canonical as it stands.
 //   order   : polynomial k, prime i, digit g of ciphertext c is digit polynomial c size E(L) + k E(L) + off_i + g (bfv_digit_src's order).
+//   selector: the RGSW selectors a client packs into ONE query ciphertext (he355_bfv_selector_encrypt, he355_bfv_rgsw_from_bfv).  Row
+//             (k = 0, i, g) of RGSW(m), m a scalar, is planted at coefficient first_slot + b E(L) + off_i + g of polynomial 0 under prime i as
+//             lift(m) 2^(g v) (2^d)^(-1) mod q_i: the expansion into 2^d children multiplies by 2^d.  The server's slot ciphertext with running
+//             index c = (r n_sel + b) E + f becomes row (c / E) 2E + f of the RGSW slab [.][2E][2][L][N] (k = 0) and its product with RGSW(s)
+//             row (c / E) 2E + E + f (k = 1).
 #pragma once
 #include "bfv_digits_core.h"
 #include "bfv_level_core.h"
@@ -63,6 +68,14 @@ HE_HD u64 bfv_gadget_first(const BfvDigitTab &tab, int size, u64 p)
     const int i = (int)(p % (u64)tab.L);
     return ck * tab.total + tab.off[i];
 }
+
+// ---- selectors packed into a query ciphertext ---------------------------------------------------------------------------------------
+// host side: (2^d)^(-1) mod q, q odd: ((q + 1) / 2)^d
+inline u64 bfv_selector_inv_pow2(u64 q, int d) { return bfv_level_powmod((q + 1) >> 1, (u64)d, q); }
+// what selector m (mod t) adds at the coefficient of digit g under the digit's own prime: lift(m) 2^(g v) (2^d)^(-1) mod q_i
+HE_HD u64 bfv_selector_value(u64 m, u64 t, int g, int v, u64 inv_pow2, const ModU64 &mi) { return mulmod(bfv_gadget_plant(m, t, g, v, mi), inv_pow2, mi); }
+// slot ciphertext c = (selector) E + f -> its row of the RGSW slab [.][2E][2][L][N]: k = 0 the slot's own transform, k = 1 its product with RGSW(s)
+HE_HD u64 bfv_selector_row(u64 c, u32 E, int k) { return (c / E) * 2 * E + (u64)k * E + c % E; }
 
 // passes of an external product: results per pass so that a pass holds at most about `cap` digit polynomials (terms per result =
 // inner 2 E(L)), never fewer than one result

@@ -2033,6 +2033,134 @@ public:
         }
         pool_free(slab);
     }
+    // ---- RGSW selectors from ONE packed query ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) -------
+    // The argument checks that need no device: the C ABI makes them before it asks for one.
+    // `sel` [n][n_sel] mod t -> `out` [n][2][L][N]; returns the gadget table of level L
+    static BfvDigitTab check_selector_args(const Params &p, int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, const u64 *out)
+    {
+        const std::string w("he355_bfv_selector_encrypt");
+        const BfvDigitTab tab = gadget_table(p, w, L, v);
+        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+        if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
+        if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
+        if ((u128)first_slot + (u128)n_sel * tab.total > count) throw std::invalid_argument(w + ": first_slot + n_sel E(L) must not exceed count");
+        if (n > 0x7fffffffull / (2 * (u64)L * (p.N / 512))) throw std::invalid_argument(w + ": too many ciphertexts for one launch");
+        if (ranges_overlap(sel, (size_t)(n * n_sel), out, (size_t)n * 2 * L * p.N)) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
+        return tab;
+    }
+    static BfvDigitTab check_rgsw_secret_args(const Params &p, int L, int kv)
+    {
+        const std::string w("he355_bfv_rgsw_encrypt_secret");
+        if (L >= 1 && (size_t)L <= p.Ltop && !bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
+        const BfvDigitTab tab = gadget_table(p, w, L, kv);
+        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+        if (2 * (u64)tab.total * 2 * L > 0x7fffffffull / (p.N / 512)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+        return tab;
+    }
+    // slot ciphertexts at r ct_stride_r + (b E + f) ct_stride_k of `ct`, `key` [2 E_key][2][L][N] -> `out` [n][n_sel][2E][2][L][N]; *ktab: the key's table
+    static BfvDigitTab check_from_bfv_args(const Params &p, int L, int v, int kv, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key,
+                                           const u64 *out, BfvDigitTab *ktab = nullptr)
+    {
+        const std::string w("he355_bfv_rgsw_from_bfv");
+        const BfvDigitTab tab = gadget_table(p, w, L, v);
+        if (!bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
+        const BfvDigitTab kt = gadget_table(p, w, L, kv);
+        if (ktab) *ktab = kt;
+        if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
+        if (!n) return tab;
+        const u128 slots = (u128)n * n_sel * tab.total; // slot ciphertexts
+        if (n > 0x7fffffffull || n_sel > 0x7fffffffull || slots > 0x7fffffffull / (2 * (u64)L * 4)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+        const u64 C = (u64)slots, rows = 2 * (u64)kt.total, pass = bfv_gadget_pass(rows, C, kGadgetPassPolys);
+        if (pass * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, false) || pass * rows * L > 0x3fffffffull)
+            throw std::invalid_argument(w + ": too many polynomials for one launch");
+        const size_t ctn = 2 * (size_t)L * p.N, outn = (size_t)C * 2 * ctn;
+        if (ranges_overlap(out, outn, ct, gadget_span_words(w, n, n_sel * tab.total, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_rgsw` overlaps the ciphertexts");
+        if (ranges_overlap(out, outn, key, (size_t)rows * ctn)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the key");
+        return tab;
+    }
+    // sel [n][n_sel] mod t -> out [n][2][L][N], coefficient form: he355_encrypt_zero(seed, first_index + r) cut to the first L primes plus the planted
+    // selectors.  L == L_top: the zeros are made where the ciphertexts lie; below, in one pool block.
+    void bfv_selector_encrypt(int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, u64 seed, u64 first_index, u64 *out)
+    {
+        use();
+        const BfvDigitTab tab = check_selector_args(P, L, v, n, n_sel, first_slot, count, sel, out);
+        if (!n) return;
+        if (!d_pk_) throw std::invalid_argument("he355_bfv_selector_encrypt: public key not set");
+        const size_t N = P.N, Lt = P.Ltop;
+        u64 *tmp = (size_t)L < Lt ? static_cast<u64 *>(pool_alloc((size_t)n * 2 * Lt * N * 8)) : nullptr;
+        try {
+            u64 *zero = tmp ? tmp : out;
+            encrypt(n, nullptr, seed, first_index, zero);
+            launch_bfv_selector_plant(env_, tab, L, (int)Lt, n, n_sel, first_slot, expand_depth(count), zero, sel, P.plain_modulus, out);
+            HIPCHECK(hipGetLastError());
+        } catch (...) {
+            if (tmp) pool_free(tmp);
+            throw;
+        }
+        if (tmp) pool_free(tmp);
+    }
+    // RGSW(s) at (L, key_bits): by definition bfv_rgsw_encrypt of the secret key's coefficients mod t (0, 1, t - 1).  The context holds s in NTT
+    // form: prime 0's residue goes through the inverse transform in one pool block of N words and is mapped there.
+    void bfv_rgsw_encrypt_secret(int L, int kv, u64 seed, u64 first_index, u64 *out)
+    {
+        use();
+        check_rgsw_secret_args(P, L, kv);
+        if (!d_sk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: secret key not set");
+        if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: public key not set");
+        const size_t N = P.N;
+        u64 *s = static_cast<u64 *>(pool_alloc(N * 8));
+        try {
+            HIPCHECK(hipMemcpyAsync(s, d_sk_, N * 8, hipMemcpyDeviceToDevice, stream_));
+            launch_ntt_inverse(env_, poly_view(s, 1, N, 1), 1);
+            launch_bfv_secret_plain(env_, s, P.plain_modulus);
+            HIPCHECK(hipGetLastError());
+            bfv_rgsw_encrypt(L, kv, 1, s, seed, first_index, out);
+        } catch (...) {
+            pool_free(s);
+            throw;
+        }
+        pool_free(s);
+    }
+    // out [n][n_sel][2E][2][L][N], NTT form.  Slot ciphertext c = (r n_sel + b) E + f (coefficient form, read where it lies): row f of RGSW (r, b) is its
+    // forward transform, row E + f the NTT-form sums of its key_bits digits against RGSW(s) -- what he355_bfv_external_product leaves before its
+    // inverse transform, which he355_bfv_transform_to_ntt would only undo.  A pass of slot ciphertexts (bfv_gadget_pass over the key's 2 E_key
+    // terms, one pool block as in bfv_external_product) is the cut, which also emits the slot's own column (gadget_cut_ntt's route, decided once per
+    // call from the first pass: every pass must leave the k = 0 rows in the same state), the digits' row pass and one multiply-accumulate into the
+    // k = 1 rows.  One row pass over the k = 0 rows, in place, ends the call.
+    void bfv_rgsw_from_bfv(int L, int v, int kv, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key, u64 *out)
+    {
+        use();
+        BfvDigitTab ktab;
+        const BfvDigitTab tab = check_from_bfv_args(P, L, v, kv, n, n_sel, ct, ct_stride_r, ct_stride_k, key, out, &ktab);
+        if (!n) return;
+        const size_t N = P.N, LN = (size_t)L * N;
+        const u32 E = tab.total, rows = 2 * ktab.total;
+        const u64 C = n * n_sel * E, pass = bfv_gadget_pass(rows, C, kGadgetPassPolys);
+        const bool cols = env_.logn1 != 0 && std::min<u64>(pass, C) * 2 * L * 4 >= kGadgetColsMinBlocks;
+        u64 *slab = static_cast<u64 *>(pool_alloc((size_t)pass * rows * LN * 8));
+        try {
+            for (u64 c0 = 0; c0 < C; c0 += pass) {
+                const u64 c = std::min<u64>(pass, C - c0);
+                launch_bfv_gadget_cut_own(env_, ktab, L, n_sel * E, c0, c, ct, ct_stride_r, ct_stride_k, slab, out, E, cols);
+                if (cols) launch_rows_fwd(env_, poly_view(slab, L, N, L), (u32)(c * rows));
+                else launch_ntt_forward(env_, poly_view(slab, L, N, L), (u32)(c * rows));
+                launch_bfv_gadget_mac_own(env_, L, c0, c, rows, slab, key, out, E);
+            }
+            // the k = 0 rows: rows f0 .. f0 + R - 1 of every RGSW ciphertext are one item of R 2L polynomials, the items 2E 2L polynomials apart
+            const u32 R = std::max<u32>(1, 64 / (2 * (u32)L));
+            for (u32 f0 = 0; f0 < E; f0 += R) {
+                PolyView pv = poly_view(out + (size_t)f0 * 2 * LN, (int)(std::min<u32>(R, E - f0) * 2 * L), N, L);
+                pv.item_stride = (u64)2 * E * 2 * LN;
+                if (cols) launch_rows_fwd(env_, pv, (u32)(n * n_sel));
+                else launch_ntt_forward(env_, pv, (u32)(n * n_sel));
+            }
+            HIPCHECK(hipGetLastError());
+        } catch (...) {
+            pool_free(slab);
+            throw;
+        }
+        pool_free(slab);
+    }
     // ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; the definition: bfv_bytes_core.h, include/he355.h) ----------------
     // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the field width w.
     // `bytes`: plaintext j at bytes + j stride, B bytes; `words`: [n][per] 64-bit words, per = N (coefficients) or L_out N.  pack: the
@@ -2848,6 +2976,32 @@ int he355_bfv_rgsw_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, cons
         need_bfv(c, "he355_bfv_rgsw_encrypt");
         DeviceContext::check_rgsw_args(*c->params, L, digit_bits, n, d_plain, d_rgsw);
         dev(c).bfv_rgsw_encrypt(L, digit_bits, n, d_plain, seed, first_index, d_rgsw);
+    });
+}
+int he355_bfv_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel, uint64_t seed,
+                               uint64_t first_index, uint64_t *d_out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_selector_encrypt");
+        DeviceContext::check_selector_args(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, d_out);
+        dev(c).bfv_selector_encrypt(L, digit_bits, n, n_sel, first_slot, count, d_sel, seed, first_index, d_out);
+    });
+}
+int he355_bfv_rgsw_encrypt_secret(he355_ctx *c, int L, int key_bits, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_rgsw_encrypt_secret");
+        DeviceContext::check_rgsw_secret_args(*c->params, L, key_bits);
+        dev(c).bfv_rgsw_encrypt_secret(L, key_bits, seed, first_index, d_rgsw);
+    });
+}
+int he355_bfv_rgsw_from_bfv(he355_ctx *c, int L, int digit_bits, int key_bits, uint64_t n, uint64_t n_sel, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
+                            const uint64_t *d_key, uint64_t *d_rgsw)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_rgsw_from_bfv");
+        DeviceContext::check_from_bfv_args(*c->params, L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
+        dev(c).bfv_rgsw_from_bfv(L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
     });
 }
 int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,

@@ -249,6 +249,10 @@ HE355_FWD(launch_bfv_bytes_cols_fwd)
 HE355_FWD(launch_bfv_gadget_cut)
 HE355_FWD(launch_bfv_gadget_mac)
 HE355_FWD(launch_bfv_rgsw_plant)
+HE355_FWD(launch_bfv_gadget_cut_own)
+HE355_FWD(launch_bfv_gadget_mac_own)
+HE355_FWD(launch_bfv_selector_plant)
+HE355_FWD(launch_bfv_secret_plain)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

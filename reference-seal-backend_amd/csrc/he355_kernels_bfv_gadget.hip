@@ -1,5 +1,6 @@
 // he355_kernels_bfv_gadget.hip -- the BFV external product RGSW(m) [.] BFV(mu) -> BFV(m mu): he355_bfv_gadget_decompose_ntt,
-// he355_bfv_rgsw_encrypt, he355_bfv_external_product.  The per-coefficient arithmetic is bfv_gadget_core.h and bfv_mac_core.h
+// he355_bfv_rgsw_encrypt, he355_bfv_external_product; and the selectors a client packs into one query ciphertext:
+// he355_bfv_selector_encrypt, he355_bfv_rgsw_encrypt_secret, he355_bfv_rgsw_from_bfv.  The per-coefficient arithmetic is bfv_gadget_core.h and bfv_mac_core.h
 // (host-compilable: tests/csim/sim_bfv_gadget.cpp runs the same text on the CPU).
 //
 //   k_bfv_gadget_cols_fwd<LOGN1>   N >= 2048: the forward COLUMN pass of every digit polynomial of one ciphertext residue.  A block owns a
@@ -20,6 +21,17 @@
 //   k_bfv_rgsw_plant     streaming; a lane owns two coefficients of one output residue polynomial (row, k', i'): it reads the encryption of
 //                        zero (level L_in >= L, cut to the first L primes) and, where (k', i') is the row's own (k, i), adds
 //                        lift(m) 2^(g v) mod q_i.  In place when L_in == L.  The existing forward transform follows.
+// he355_bfv_rgsw_from_bfv runs the same kernels in their OWN form (a template flag; the plain form compiles what it compiled before):
+//   k_bfv_gadget_cols_fwd<LOGN1, true>  also runs the lane program on the ciphertext words it holds, under the residue's own prime, and stores
+//                        that raw column into row bfv_selector_row(c, E, 0) of the RGSW slab: the k = 0 rows cost no second read of the
+//                        children.  The working column is the one the digits use, so the register count is the plain form's.
+//   k_bfv_gadget_spread<true>           also stores the 16 bytes it loaded into that row, coefficient form.
+//   k_bfv_gadget_mac<true>              one term list per slot ciphertext (inner = 1, all of them against RGSW(s)); the NTT-form sums go
+//                        straight to row bfv_selector_row(c, E, 1).
+//   k_bfv_selector_plant streaming; a lane owns two coefficients of one output residue polynomial (r, k, i) of the query ciphertexts: the
+//                        encryption of zero cut to L primes and, in polynomial 0 at a coefficient that is a slot of a digit of prime i,
+//                        bfv_selector_value of the slot's selector.
+//   k_bfv_secret_plain   the secret key's coefficients under prime 0 (0, 1, q_0 - 1) -> 0, 1, t - 1.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
@@ -48,17 +60,28 @@ struct BfvGadgetCutArgs {
     u64 n_polys; // n_a n_b size L residue polynomials
     int L, size, logN;
     BfvDigitTab tab;
+    // the batch is ciphertexts first .. of the (a, b) order; OWN form (size 2): ciphertext c of that order is also written, transformed as
+    // the digits are, to row bfv_selector_row(c, own_E, 0) of own [.][2 own_E][2][L][N]
+    u64 first;
+    u64 *own;
+    u32 own_E;
 };
 
 // residue polynomial p of the batch -> its words
 __device__ __forceinline__ const u64 *gadget_src(const BfvGadgetCutArgs &A, u64 p)
 {
-    const u64 polys = (u64)A.size * A.L, c = p / polys, rest = p % polys;
+    const u64 polys = (u64)A.size * A.L, c = A.first + p / polys, rest = p % polys;
     const u64 at = (c / A.n_b) * A.stride_a + (c % A.n_b) * A.stride_b;
     return A.in + ((at * polys + rest) << A.logN);
 }
+// OWN form: where residue polynomial p of the batch goes in the RGSW slab
+__device__ __forceinline__ u64 *gadget_own_dst(const BfvGadgetCutArgs &A, u64 p)
+{
+    const u64 polys = 2 * (u64)A.L;
+    return A.own + ((bfv_selector_row(A.first + p / polys, A.own_E, 0) * polys + p % polys) << A.logN);
+}
 
-template <int LOGN1>
+template <int LOGN1, bool OWN>
 __global__ void __launch_bounds__(kBlock) k_bfv_gadget_cols_fwd(BfvGadgetCutArgs A, const PrimeDev *primes)
 {
     constexpr int N1 = 1 << LOGN1;
@@ -70,6 +93,27 @@ __global__ void __launch_bounds__(kBlock) k_bfv_gadget_cols_fwd(BfvGadgetCutArgs
     u64 w[N1];
 #pragma unroll
     for (int a = 0; a < N1; ++a) w[a] = src[(a << kRowLog) + col];
+    if (OWN) { // the ciphertext's own column under its own prime: k_cols_fwd's program on the words already here
+        const PrimeDev &P = primes[i];
+        u64 *dst = gadget_own_dst(A, p);
+        if (P.f64) {
+            const ArF64 ar = make_ar(P, (ArF64 *)nullptr);
+            double x[N1];
+#pragma unroll
+            for (int a = 0; a < N1; ++a) x[a] = ar.from_canon(w[a]);
+            col_fwd<ArF64, LOGN1>(ar, x, ctw(P.fwd));
+#pragma unroll
+            for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = ar.to_raw(x[a]);
+        } else {
+            const ArU64 ar = make_ar(P, (ArU64 *)nullptr);
+            u64 x[N1];
+#pragma unroll
+            for (int a = 0; a < N1; ++a) x[a] = w[a];
+            col_fwd<ArU64, LOGN1>(ar, x, ctw(P.fwd));
+#pragma unroll
+            for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = x[a];
+        }
+    }
     for (int g = 0; g < E; ++g) {
         for (int j = 0; j < A.L; ++j) {
             const PrimeDev &P = primes[j];
@@ -96,6 +140,7 @@ __global__ void __launch_bounds__(kBlock) k_bfv_gadget_cols_fwd(BfvGadgetCutArgs
     }
 }
 
+template <bool OWN>
 __global__ void __launch_bounds__(kBlock) k_bfv_gadget_spread(BfvGadgetCutArgs A, const PrimeDev *primes)
 {
     const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
@@ -104,6 +149,7 @@ __global__ void __launch_bounds__(kBlock) k_bfv_gadget_spread(BfvGadgetCutArgs A
     const int i = (int)(p % (u64)A.L), E = A.tab.D[i], v = A.tab.w;
     const u64 f0 = bfv_gadget_first(A.tab, A.size, p);
     const ulonglong2 x = reinterpret_cast<const ulonglong2 *>(gadget_src(A, p))[e2];
+    if (OWN) reinterpret_cast<ulonglong2 *>(gadget_own_dst(A, p))[e2] = x;
     for (int g = 0; g < E; ++g)
         for (int j = 0; j < A.L; ++j) {
             const ModU64 mj = make_modu(primes[j]);
@@ -120,8 +166,12 @@ struct BfvGadgetMacArgs {
     u32 inner, rows, pairs_blocks; // rows = 2 E(L); pairs_blocks = N / 2 / kBlock
     int L, logN;
     u32 run[kMaxPrimes]; // bfv_mac_run of prime j
+    // OWN form: result r is slot ciphertext first + r, and goes to row bfv_selector_row(first + r, own_E, 1) of out [.][2 own_E][2][L][N]
+    u64 first;
+    u32 own_E;
 };
 
+template <bool OWN>
 __global__ void __launch_bounds__(kBlock) k_bfv_gadget_mac(BfvGadgetMacArgs A, const PrimeDev *primes)
 {
     // block = (residue j, coefficient block, result), the result fastest
@@ -161,7 +211,7 @@ __global__ void __launch_bounds__(kBlock) k_bfv_gadget_mac(BfvGadgetMacArgs A, c
         }
         pd += A.rows * half;
     }
-    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(A.out + r * 2 * LN + (u64)j * N) + e2;
+    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(A.out + (OWN ? bfv_selector_row(A.first + r, A.own_E, 1) : r) * 2 * LN + (u64)j * N) + e2;
     po[0] = make_ulonglong2(bfv_mac_reduce(acc[0][0], m), bfv_mac_reduce(acc[0][1], m));
     po[half] = make_ulonglong2(bfv_mac_reduce(acc[1][0], m), bfv_mac_reduce(acc[1][1], m));
 }
@@ -194,6 +244,52 @@ __global__ void __launch_bounds__(kBlock) k_bfv_rgsw_plant(BfvPlantArgs A, const
     reinterpret_cast<ulonglong2 *>(A.out + (p << A.logN))[e2] = x;
 }
 
+// zero [n][2][L_in][N] (encryptions of zero, coefficient form), sel [n][n_sel] mod t -> out [n][2][L][N]
+struct BfvSelectorArgs {
+    const u64 *zero, *sel;
+    u64 *out;
+    u64 n_polys; // n 2 L output residue polynomials
+    u64 t, n_sel, first_slot;
+    u64 inv_pow2[kMaxPrimes]; // (2^d)^(-1) mod q_i
+    int L, L_in, logN;
+    BfvDigitTab tab;
+};
+
+__global__ void __launch_bounds__(kBlock) k_bfv_selector_plant(BfvSelectorArgs A, const PrimeDev *primes)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (A.logN - 1), e2 = gid & (((u64)1 << (A.logN - 1)) - 1);
+    if (p >= A.n_polys) return;
+    const u64 r = p / (2 * (u64)A.L);
+    const int kk = (int)((p / (u64)A.L) & 1), ii = (int)(p % (u64)A.L);
+    ulonglong2 x = reinterpret_cast<const ulonglong2 *>(A.zero + (((r * 2 + kk) * A.L_in + ii) << A.logN))[e2];
+    const u64 E = A.tab.total, lo = A.first_slot, hi = A.first_slot + A.n_sel * E; // the slots: coefficients lo .. hi - 1
+    if (kk == 0 && 2 * e2 + 1 >= lo && 2 * e2 < hi) {
+        const ModU64 mi = make_modu(primes[ii]);
+        u64 xs[2] = {x.x, x.y};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const u64 e = 2 * e2 + h;
+            if (e < lo || e >= hi) continue;
+            const u64 slot = e - lo, b = slot / E;
+            const u32 d = (u32)(slot % E);
+            if (bfv_digit_prime(A.tab, d) != ii) continue;
+            xs[h] = addmod(xs[h], bfv_selector_value(A.sel[r * A.n_sel + b], A.t, (int)(d - A.tab.off[ii]), A.tab.w, A.inv_pow2[ii], mi), mi.q);
+        }
+        x = make_ulonglong2(xs[0], xs[1]);
+    }
+    reinterpret_cast<ulonglong2 *>(A.out + (p << A.logN))[e2] = x;
+}
+
+// s [N] under prime q0, coefficients 0, 1, q0 - 1 (in place) -> 0, 1, t - 1
+__global__ void __launch_bounds__(kBlock) k_bfv_secret_plain(u64 *s, u64 n, u64 q0, u64 t)
+{
+    const u64 e = (u64)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n) return;
+    const u64 x = s[e];
+    s[e] = x > (q0 >> 1) ? t - (q0 - x) : x;
+}
+
 BfvGadgetCutArgs cut_args(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *in, u64 stride_a, u64 stride_b, u64 *out)
 {
     if (L < 1 || L > kMaxPrimes || tab.L != L || size < 1 || size > 3 || !bfv_gadget_width_ok(tab.w))
@@ -201,6 +297,7 @@ BfvGadgetCutArgs cut_args(const KernelEnv &env, const BfvDigitTab &tab, int L, i
     BfvGadgetCutArgs A{};
     A.in = in; A.out = out; A.n_b = n_b; A.stride_a = stride_a; A.stride_b = stride_b;
     A.n_polys = n_a * n_b * size * L; A.L = L; A.size = size; A.logN = env.logn1 + kRowLog; A.tab = tab;
+    A.first = 0; A.own = nullptr; A.own_E = 0;
     return A;
 }
 unsigned streaming_grid(u64 n_polys, int logN, const char *what)
@@ -210,6 +307,26 @@ unsigned streaming_grid(u64 n_polys, int logN, const char *what)
     return (unsigned)blocks;
 }
 
+template <bool OWN>
+void launch_cut(const KernelEnv &env, const BfvGadgetCutArgs &A, bool cols)
+{
+    if (!cols) {
+        hipLaunchKernelGGL(k_bfv_gadget_spread<OWN>, dim3(streaming_grid(A.n_polys, A.logN, "gadget decomposition")), dim3(kBlock), 0, env.stream, A, env.primes);
+        return;
+    }
+    const u64 blocks = A.n_polys * 4;
+    if (blocks > 0x7fffffffull) throw std::invalid_argument("gadget decomposition: too many polynomials for one launch");
+    const dim3 g((unsigned)blocks), b(kBlock);
+    switch (env.logn1) {
+    case 1: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<1, OWN>), g, b, 0, env.stream, A, env.primes); break;
+    case 2: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<2, OWN>), g, b, 0, env.stream, A, env.primes); break;
+    case 3: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<3, OWN>), g, b, 0, env.stream, A, env.primes); break;
+    case 4: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<4, OWN>), g, b, 0, env.stream, A, env.primes); break;
+    case 5: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<5, OWN>), g, b, 0, env.stream, A, env.primes); break;
+    default: throw std::invalid_argument("ring size out of range");
+    }
+}
+
 } // namespace
 
 void launch_bfv_gadget_cut(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out, bool cols)
@@ -217,24 +334,20 @@ void launch_bfv_gadget_cut(const KernelEnv &env, const BfvDigitTab &tab, int L, 
     if (!n_a || !n_b) return;
     const BfvGadgetCutArgs A = cut_args(env, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out);
     if (env.logn1 == 0 && cols) throw std::invalid_argument("gadget decomposition: N = 1024 has no column pass");
-    if (!cols) {
-        hipLaunchKernelGGL(k_bfv_gadget_spread, dim3(streaming_grid(A.n_polys, A.logN, "gadget decomposition")), dim3(kBlock), 0, env.stream, A, env.primes);
-        return;
-    }
-    const u64 blocks = A.n_polys * 4;
-    if (blocks > 0x7fffffffull) throw std::invalid_argument("gadget decomposition: too many polynomials for one launch");
-    const dim3 g((unsigned)blocks), b(kBlock);
-    switch (env.logn1) {
-    case 1: hipLaunchKernelGGL(k_bfv_gadget_cols_fwd<1>, g, b, 0, env.stream, A, env.primes); break;
-    case 2: hipLaunchKernelGGL(k_bfv_gadget_cols_fwd<2>, g, b, 0, env.stream, A, env.primes); break;
-    case 3: hipLaunchKernelGGL(k_bfv_gadget_cols_fwd<3>, g, b, 0, env.stream, A, env.primes); break;
-    case 4: hipLaunchKernelGGL(k_bfv_gadget_cols_fwd<4>, g, b, 0, env.stream, A, env.primes); break;
-    case 5: hipLaunchKernelGGL(k_bfv_gadget_cols_fwd<5>, g, b, 0, env.stream, A, env.primes); break;
-    default: throw std::invalid_argument("ring size out of range");
-    }
+    launch_cut<false>(env, A, cols);
+}
+void launch_bfv_gadget_cut_own(const KernelEnv &env, const BfvDigitTab &tab, int L, u64 n_b, u64 first, u64 count, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out,
+                               u64 *own, u32 own_E, bool cols)
+{
+    if (!count) return;
+    if (!n_b || !own || !own_E) throw std::invalid_argument("he355_bfv_rgsw_from_bfv: no selectors or no output");
+    BfvGadgetCutArgs A = cut_args(env, tab, L, 2, 1, count, ct, stride_a, stride_b, out); // n_polys of `count` ciphertexts
+    A.n_b = n_b; A.first = first; A.own = own; A.own_E = own_E;
+    if (env.logn1 == 0 && cols) throw std::invalid_argument("he355_bfv_rgsw_from_bfv: N = 1024 has no column pass");
+    launch_cut<true>(env, A, cols);
 }
 static u64 gadget_mac_blocks(const KernelEnv &env, int L, u64 n) { return n * (u64)L * ((((u64)1 << (env.logn1 + kRowLog)) / 2) / kBlock); }
-void launch_bfv_gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out)
+static void gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out, u64 first, u32 own_E)
 {
     if (!n) return;
     if (L < 1 || L > kMaxPrimes || inner < 1 || rows < 2 || inner * rows > 0x7fffffffull)
@@ -249,7 +362,18 @@ void launch_bfv_gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 ro
     }
     const u64 blocks = gadget_mac_blocks(env, L, n);
     if (blocks > 0x7fffffffull) throw std::invalid_argument("he355_bfv_external_product: too many results for one launch");
-    hipLaunchKernelGGL(k_bfv_gadget_mac, dim3((unsigned)blocks), dim3(kBlock), 0, env.stream, A, env.primes);
+    A.first = first; A.own_E = own_E;
+    if (own_E) hipLaunchKernelGGL(k_bfv_gadget_mac<true>, dim3((unsigned)blocks), dim3(kBlock), 0, env.stream, A, env.primes);
+    else hipLaunchKernelGGL(k_bfv_gadget_mac<false>, dim3((unsigned)blocks), dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_bfv_gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out)
+{
+    gadget_mac(env, L, n, inner, rows, dig, rgsw, rg_stride_r, rg_stride_k, out, 0, 0);
+}
+void launch_bfv_gadget_mac_own(const KernelEnv &env, int L, u64 first, u64 count, u32 rows, const u64 *dig, const u64 *key, u64 *out, u32 own_E)
+{
+    if (!own_E) throw std::invalid_argument("he355_bfv_rgsw_from_bfv: no selectors");
+    gadget_mac(env, L, count, 1, rows, dig, key, 0, 1, out, first, own_E);
 }
 void launch_bfv_rgsw_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, const u64 *zero, const u64 *plain, u64 t, u64 *out)
 {
@@ -258,6 +382,23 @@ void launch_bfv_rgsw_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, 
     BfvPlantArgs A{};
     A.zero = zero; A.plain = plain; A.out = out; A.n_polys = n * 2 * tab.total * 2 * L; A.t = t; A.L = L; A.L_in = L_in; A.logN = env.logn1 + kRowLog; A.tab = tab;
     hipLaunchKernelGGL(k_bfv_rgsw_plant, dim3(streaming_grid(A.n_polys, A.logN, "he355_bfv_rgsw_encrypt")), dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_bfv_selector_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, u64 n_sel, u64 first_slot, int d, const u64 *zero, const u64 *sel, u64 t, u64 *out)
+{
+    if (!n) return;
+    if (L < 1 || L > kMaxPrimes || tab.L != L || L_in < L || !bfv_gadget_width_ok(tab.w) || d < 0 || d > env.logn1 + kRowLog ||
+        first_slot + n_sel * tab.total > ((u64)1 << (env.logn1 + kRowLog)))
+        throw std::invalid_argument("he355_bfv_selector_encrypt: level, digit table or slots out of range");
+    BfvSelectorArgs A{};
+    A.zero = zero; A.sel = sel; A.out = out; A.n_polys = n * 2 * L; A.t = t; A.n_sel = n_sel; A.first_slot = first_slot;
+    for (int i = 0; i < L; ++i) A.inv_pow2[i] = bfv_selector_inv_pow2(env.prime_q[i], d);
+    A.L = L; A.L_in = L_in; A.logN = env.logn1 + kRowLog; A.tab = tab;
+    hipLaunchKernelGGL(k_bfv_selector_plant, dim3(streaming_grid(A.n_polys, A.logN, "he355_bfv_selector_encrypt")), dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_bfv_secret_plain(const KernelEnv &env, u64 *s, u64 t)
+{
+    const u64 N = (u64)1 << (env.logn1 + kRowLog);
+    hipLaunchKernelGGL(k_bfv_secret_plain, dim3((unsigned)(N / kBlock)), dim3(kBlock), 0, env.stream, s, N, env.prime_q[0], t);
 }
 
 } // namespace HE355_KNS

@@ -175,3 +175,17 @@ void launch_bfv_gadget_mac(const KernelEnv &env, int L, u64 n, u64 inner, u32 ro
 // zero [n 2E][2][L_in][N] encryptions of zero (coefficient form, L_in >= L), plain [n][N] mod t -> out [n 2E][2][L][N]: the first L primes of
 // each row plus lift(m) 2^(g v) mod q_i in polynomial k under prime i of row k E + off_i + g.  In place (out == zero) when L_in == L.
 void launch_bfv_rgsw_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, const u64 *zero, const u64 *plain, u64 t, u64 *out);
+// ---- RGSW selectors from one packed query ciphertext (he355_kernels_bfv_gadget.hip; arithmetic: bfv_gadget_core.h) -------------------------------
+// launch_bfv_gadget_cut for he355_bfv_rgsw_from_bfv: slot ciphertexts first .. first + count - 1 of the order c = a n_b + b (ciphertext c at
+// index a stride_a + b stride_b of `ct`, [2][L][N]) -> out [count][2 E_key][L][N] (`tab`: the key's table), and ciphertext c itself, transformed as
+// the digits are (cols: its raw column; else coefficient form), into row bfv_selector_row(c, own_E, 0) of own [.][2 own_E][2][L][N].
+void launch_bfv_gadget_cut_own(const KernelEnv &env, const BfvDigitTab &tab, int L, u64 n_b, u64 first, u64 count, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out,
+                               u64 *own, u32 own_E, bool cols);
+// row bfv_selector_row(first + r, own_E, 1) of out = sum_(f < rows) dig[r][f] (.) row f of `key` ([rows][2][L][N]), r < count, canonical NTT form
+void launch_bfv_gadget_mac_own(const KernelEnv &env, int L, u64 first, u64 count, u32 rows, const u64 *dig, const u64 *key, u64 *out, u32 own_E);
+// zero [n][2][L_in][N] encryptions of zero (coefficient form, L_in >= L), sel [n][n_sel] mod t -> out [n][2][L][N]: the first L primes plus
+// bfv_selector_value of selector b, digit (i, g), at coefficient first_slot + b E + off_i + g of polynomial 0 under prime i; d = the expansion's
+// depth.  In place (out == zero) when L_in == L.
+void launch_bfv_selector_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, u64 n_sel, u64 first_slot, int d, const u64 *zero, const u64 *sel, u64 t, u64 *out);
+// s [N]: the secret key's coefficients under prime 0 (0, 1, q_0 - 1), in place -> mod t (0, 1, t - 1)
+void launch_bfv_secret_plain(const KernelEnv &env, u64 *s, u64 t);
