@@ -119,6 +119,21 @@ typedef struct {
     uint64_t reserved;
 } he355_path_stats_t;
 int he355_path_stats(he355_ctx *ctx, he355_path_stats_t *out, int reset);
+/* Which route the context's BFV PIR calls took since he355_device_init (or the last call with reset != 0).  The routes are the library's
+ * (ring size, batch, strides: the ROUTED notes of DESIGN.md) and bit-identical by definition, so a result cannot tell which one ran; tests use
+ * the counters to prove that the route they mean to hold to the oracle is the one that ran (tests/test_gpu_bfv_large_rings.py).  Counted on
+ * the host where the calls branch; no counter is read by a launch.  A "pass" is one trip of he355_bfv_external_product or
+ * he355_bfv_rgsw_from_bfv through its pool block of digit polynomials. */
+typedef struct {
+    uint64_t cut_cols, cut_stream;         /* cuts of he355_bfv_gadget_decompose_ntt and of he355_bfv_external_product's passes: the fused column pass / the streaming cut */
+    uint64_t mac_gadget, mac_plain;        /* he355_bfv_external_product passes by multiply-accumulate kernel: k_bfv_gadget_mac / k_bfv_plain_mac */
+    uint64_t own_cols, own_stream;         /* he355_bfv_rgsw_from_bfv passes by cut: the column pass that also emits the slot's own row / the streaming cut */
+    uint64_t digits_fused, digits_routed;  /* he355_bfv_decompose_ntt calls: the fused column pass / N = 1024's composition */
+    uint64_t bytes_fused, bytes_routed;    /* he355_bfv_unpack_bytes_ntt: fused calls / passes of N = 1024's composition through its pool block */
+    uint64_t passes;                       /* pool-block passes of he355_bfv_external_product and he355_bfv_rgsw_from_bfv */
+    uint64_t reserved[5];
+} he355_bfv_route_stats_t;
+int he355_bfv_route_stats(he355_ctx *ctx, he355_bfv_route_stats_t *out, int reset);
 int he355_upload(he355_ctx *ctx, void *d_dst, const void *h_src, uint64_t bytes);
 int he355_download(he355_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes);
 int he355_copy(he355_ctx *ctx, void *d_dst, const void *d_src, uint64_t bytes); /* device to device, on the context's stream */

@@ -308,6 +308,13 @@ public:
         if (reset) paths_ = he355_path_stats_t{};
         return s;
     }
+    // which route the BFV PIR calls of this context took (he355_bfv_route_stats): counted on the host where the calls branch, read by no launch
+    he355_bfv_route_stats_t bfv_route_stats(bool reset)
+    {
+        const he355_bfv_route_stats_t s = routes_;
+        if (reset) routes_ = he355_bfv_route_stats_t{};
+        return s;
+    }
     size_t pool_trim() { sync(); return pool_.trim(); }
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
@@ -1871,6 +1878,7 @@ public:
         const size_t N = P.N, F = (size_t)size * tab.total;
         if (!n) return;
         if (env_.logn1 == 0) {
+            ++routes_.digits_routed;
             u64 *tmp = static_cast<u64 *>(pool_alloc((size_t)n * F * N * 8));
             try {
                 launch_bfv_digits(env_, tab, L, size, n, ct, tmp);
@@ -1884,6 +1892,7 @@ public:
             pool_free(tmp);
             return;
         }
+        ++routes_.digits_fused;
         launch_bfv_digits_cols_fwd(env_, tab, L, size, n, ct, L_out, P.plain_modulus, out);
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
         HIPCHECK(hipGetLastError());
@@ -1964,6 +1973,7 @@ public:
     {
         const u32 items = (u32)(n_a * n_b * size * tab.total);
         const bool cols = env_.logn1 != 0 && n_a * n_b * size * L * 4 >= kGadgetColsMinBlocks;
+        ++(cols ? routes_.cut_cols : routes_.cut_stream);
         launch_bfv_gadget_cut(env_, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out, cols);
         if (cols) launch_rows_fwd(env_, poly_view(out, L, P.N, L), items);
         else launch_ntt_forward(env_, poly_view(out, L, P.N, L), items);
@@ -2022,7 +2032,10 @@ public:
                 // k_bfv_plain_mac's 1 x 1 form (two terms' loads in flight) measured 2-17 % ahead of k_bfv_gadget_mac there
                 // (profiles/bfv_external_product.txt).  Only n == 1 was measured, so only n == 1 is routed: a pass that holds one result
                 // of many (inner 2E above 2048, or a ragged last pass) stays with k_bfv_gadget_mac.
-                if (n == 1 && (inner == 1 || rg_stride_k == 1)) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab, 1, 1, out + r0 * 2 * LN);
+                const bool plain = n == 1 && (inner == 1 || rg_stride_k == 1);
+                ++routes_.passes;
+                ++(plain ? routes_.mac_plain : routes_.mac_gadget);
+                if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab, 1, 1, out + r0 * 2 * LN);
                 else launch_bfv_gadget_mac(env_, L, c, inner, rows, slab, rg, rg_stride_r, rg_stride_k, out + r0 * 2 * LN);
             }
             launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
@@ -2141,6 +2154,8 @@ public:
         try {
             for (u64 c0 = 0; c0 < C; c0 += pass) {
                 const u64 c = std::min<u64>(pass, C - c0);
+                ++routes_.passes;
+                ++(cols ? routes_.own_cols : routes_.own_stream);
                 launch_bfv_gadget_cut_own(env_, ktab, L, n_sel * E, c0, c, ct, ct_stride_r, ct_stride_k, slab, out, E, cols);
                 if (cols) launch_rows_fwd(env_, poly_view(slab, L, N, L), (u32)(c * rows));
                 else launch_ntt_forward(env_, poly_view(slab, L, N, L), (u32)(c * rows));
@@ -2222,6 +2237,7 @@ public:
                 for (u64 j = 0; j < n; j += chunk) {
                     const u64 c = n - j < chunk ? n - j : chunk;
                     u64 *dst = out + (size_t)j * L_out * N;
+                    ++routes_.bytes_routed;
                     launch_bfv_unpack(env_, w, c, static_cast<const unsigned char *>(bytes) + j * stride, stride, B, tmp);
                     launch_bfv_lift_plain(env_, L_out, c, tmp, dst, P.plain_modulus);
                     launch_ntt_forward(env_, poly_view(dst, L_out, N, L_out), (u32)c);
@@ -2234,6 +2250,7 @@ public:
             pool_free(tmp);
             return;
         }
+        ++routes_.bytes_fused;
         launch_bfv_bytes_cols_fwd(env_, w, n, bytes, stride, B, L_out, P.plain_modulus, out);
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)n);
         HIPCHECK(hipGetLastError());
@@ -2548,6 +2565,7 @@ private:
     bool dual_stream_ = true;
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
     he355_path_stats_t paths_{};
+    he355_bfv_route_stats_t routes_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
     u64 lds_max_ = 0;
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
@@ -2723,6 +2741,13 @@ int he355_path_stats(he355_ctx *c, he355_path_stats_t *out, int reset)
     return guarded([&] {
         if (!out) throw std::invalid_argument("null pointer");
         *out = dev(c).path_stats(reset != 0);
+    });
+}
+int he355_bfv_route_stats(he355_ctx *c, he355_bfv_route_stats_t *out, int reset)
+{
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null pointer");
+        *out = dev(c).bfv_route_stats(reset != 0);
     });
 }
 int he355_pool_trim(he355_ctx *c, uint64_t *released_bytes)

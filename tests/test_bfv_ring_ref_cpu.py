@@ -1,0 +1,179 @@
+"""The device-free references of bfv_ring_ref.py, held to Python integers before test_gpu_bfv_large_rings.py trusts them (no GPU):
+
+* external_product_ref and rgsw_from_bfv_ref (its k = 1 rows after oracle.intt) against the schoolbook negacyclic sum, N = 1024, {50, 40, 50}, at 8
+  output coefficients (0, 1, 511, 512, 1022, 1023 and two random ones), both polynomials, every prime: N products per coefficient and term;
+  the k = 0 rows are oracle.ntt of the slot ciphertext, and every row lies where bfv_selector_ref.row says;
+* decompose_ntt_ref, unpack_bytes_ntt_ref and gadget_ntt_ref against oracle.ntt of digits cut and lifted in Python integers (bfv_gadget_ref.digit /
+  lift, int.from_bytes), whole polynomials of the source words those coefficients belong to; np_lift against bfv_gadget_ref.lift at its edges;
+* the five chains of test_gpu_bfv_large_rings.py build in the oracle, and their engines are what that module means: a 40-bit prime (fp64 engine)
+  beside 60-bit primes of the form 2^60 - c ... (fold form) or 50-bit primes (Shoup form); the plain moduli are the ones its shapes assume."""
+import numpy as np
+import pytest
+
+import bfv_gadget_ref as gad
+import bfv_ring_ref as ring
+import bfv_selector_ref as sel
+
+N, BITS, PB = 1024, [50, 40, 50], 20
+LARGE = {
+    "n8192_fold": (8192, [60, 40, 60], 20),
+    "n16384_fold": (16384, [60, 40, 40, 60], 20),
+    "n32768_fold": (32768, [60, 40, 40, 60], 20),
+    "n8192_shoup": (8192, [50, 40, 50], 20),
+    "n32768_shoup": (32768, [50, 40, 40, 50], 20),
+}
+
+
+@pytest.fixture(scope="module")
+def ctx(oracle):
+    return oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=BITS, plain_bits=PB, sec128=False)
+
+
+def coefficients(rng):
+    return [0, 1, 511, 512, 1022, 1023] + [int(c) for c in rng.choice(np.arange(2, 1022), 2, replace=False)]
+
+
+def edged(o, rng, n, L, size=2):
+    c = np.stack([o.random_poly(rng, L, size) for _ in range(n)])
+    c[0, 0, 0, :] = 0
+    for i, q in enumerate(o.moduli[:L]):
+        c[n - 1, size - 1, i, :] = q - 1
+        c[1 % n, 0, i, 1::2] = 0
+        c[1 % n, 0, i, 0::2] = q - 1
+    return c
+
+
+def uniform_rows(o, rng, T, L):
+    """[T][2][L][N] uniform residues: "RGSW rows" in NTT form (the identity is arithmetic)"""
+    return np.stack([o.random_poly(rng, L, 2) for _ in range(T)])
+
+
+def schoolbook(a, b, j, q):
+    """coefficient j of a b mod (X^N + 1, q): a, b lists of Python integers"""
+    n = len(a)
+    return (sum(a[i] * b[j - i] for i in range(j + 1)) - sum(a[i] * b[n + j - i] for i in range(j + 1, n))) % q
+
+
+def schoolbook_sum(o, rows_ntt, cts, v, coeffs):
+    """{(k, i, j): sum over terms of (row polynomial k under prime i, coefficient form by oracle.intt) times (digit polynomial: Python integers)}"""
+    T = rows_ntt.shape[0]
+    L = cts.shape[2]
+    E, off = gad.table(o.moduli[:L], v)
+    digits = []  # term order: ciphertext kappa, polynomial k', prime i', digit g
+    for ct in cts:
+        for kp in range(2):
+            for ip in range(L):
+                for g in range(E[ip]):
+                    digits.append([gad.digit(int(c), g, v) for c in ct[kp, ip]])
+    assert len(digits) == T
+    out = {}
+    for k in range(2):
+        for i, q in enumerate(o.moduli[:L]):
+            rows = [[int(c) for c in o.intt(i, rows_ntt[f, k, i])] for f in range(T)]
+            for j in coeffs:
+                out[(k, i, j)] = sum(schoolbook(rows[f], [d % q for d in digits[f]], j, q) for f in range(T)) % q
+    return out
+
+
+def test_external_product_ref_is_the_schoolbook_sum(ctx):
+    o, rng = ctx, np.random.default_rng(201)
+    L, v, inner = o.L, 20, 2
+    rows = 2 * gad.table(o.moduli[:L], v)[1][-1]
+    assert (L, rows) == (2, 10)
+    cts = edged(o, rng, inner, L)
+    rg = uniform_rows(o, rng, inner * rows, L)
+    got = ring.external_product_ref(o, cts, rg.reshape(inner, rows, 2, L, N), v)
+    want = schoolbook_sum(o, rg, cts, v, coefficients(rng))
+    assert len(want) == 2 * L * 8
+    for (k, i, j), w in want.items():
+        assert int(got[k, i, j]) == w, (k, i, j)
+
+
+def test_rgsw_from_bfv_ref_is_the_schoolbook_sum_and_the_row_rule(ctx):
+    o, rng = ctx, np.random.default_rng(202)
+    L, v, kv, n_rg = o.L, 45, 20, 2
+    E = gad.table(o.moduli[:L], v)[1][-1]
+    rows = 2 * gad.table(o.moduli[:L], kv)[1][-1]
+    assert (E, rows) == (3, 10)
+    slots = edged(o, rng, n_rg * E, L)
+    key = uniform_rows(o, rng, rows, L)
+    got = ring.rgsw_from_bfv_ref(o, slots, key, v, kv)
+    assert got.shape == (n_rg, 2 * E, 2, L, N)
+    flat = got.reshape(n_rg * 2 * E, 2, L, N)
+    coeffs = coefficients(rng)
+    for c in (0, E - 1, E, n_rg * E - 1):  # the first and last slot of each RGSW ciphertext
+        own, prod = flat[sel.row(c, E, 0)], flat[sel.row(c, E, 1)]
+        for k in range(2):
+            for i in range(L):
+                assert np.array_equal(own[k, i], o.ntt(i, slots[c, k, i])), (c, k, i)
+        want = schoolbook_sum(o, key, slots[c][None], kv, coeffs)
+        back = ring.intt_all(o, prod)
+        for (k, i, j), w in want.items():
+            assert int(back[k, i, j]) == w, (c, k, i, j)
+
+
+def test_np_lift_is_the_centred_lift(ctx):
+    t = ctx.t
+    m = np.array([0, 1, (t + 1) // 2 - 1, (t + 1) // 2, t - 1], dtype=np.uint64)
+    for q in ctx.moduli:
+        assert [int(x) for x in ring.np_lift(m, t, q)] == [gad.lift(int(x), t) % q for x in m]
+
+
+def test_the_cuts_are_ntt_of_python_integer_digits(ctx):
+    o, rng = ctx, np.random.default_rng(203)
+    L, t = o.L, o.t
+    w = t.bit_length() - 1
+    x = edged(o, rng, 3, L, 3)
+    # decompose_ntt_ref: digits of width w, lifted
+    E, off = gad.table(o.moduli[:L], w)
+    for L_out in (L, 1):
+        got = ring.decompose_ntt_ref(o, x, L_out)
+        assert got.shape == (3, 3 * off[-1], L_out, N)
+        for r, k, i in ((0, 0, 0), (1, 0, 1), (2, 2, L - 1), (2, 1, 0)):
+            for g in range(E[i]):
+                d = [gad.digit(int(c), g, w) for c in x[r, k, i]]
+                for ip in range(L_out):
+                    q = o.moduli[ip]
+                    want = o.ntt(ip, np.array([gad.lift(c, t) % q for c in d], dtype=np.uint64))
+                    assert np.array_equal(got[r, k * off[-1] + off[i] + g, ip], want), (L_out, r, k, i, g, ip)
+    # gadget_ntt_ref: plain digits of width v under every prime, reduced where they are not below it (v = 45 against the 40-bit prime)
+    for v in (20, 45):
+        E, off = gad.table(o.moduli[:L], v)
+        got = ring.gadget_ntt_ref(o, x, v)
+        assert got.shape == (3, 3 * off[-1], L, N)
+        for r, k, i in ((0, 0, 0), (1, 0, 1), (2, 2, L - 1)):
+            for g in range(E[i]):
+                d = [gad.digit(int(c), g, v) for c in x[r, k, i]]
+                for ip, q in enumerate(o.moduli[:L]):
+                    want = o.ntt(ip, np.array([c % q for c in d], dtype=np.uint64))
+                    assert np.array_equal(got[r, k * off[-1] + off[i] + g, ip], want), (v, r, k, i, g, ip)
+    # unpack_bytes_ntt_ref: fields of width w of the little-endian integer of the bytes
+    B = N * w // 8
+    data = rng.integers(0, 256, (3, B), dtype=np.uint8)
+    data[0], data[2] = 0, 0xFF
+    for L_out in (L, 1):
+        got = ring.unpack_bytes_ntt_ref(o, data, L_out)
+        for r in range(3):
+            big = int.from_bytes(data[r].tobytes(), "little")
+            f = [(big >> (e * w)) & ((1 << w) - 1) for e in range(N)]
+            for ip in range(L_out):
+                q = o.moduli[ip]
+                assert np.array_equal(got[r, ip], o.ntt(ip, np.array([gad.lift(c, t) % q for c in f], dtype=np.uint64))), (L_out, r, ip)
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_the_large_chains_build_and_their_engines_are_what_is_meant(oracle, name):
+    n, bits, pb = LARGE[name]
+    o = oracle.Context(oracle.SCHEME_BFV, n, bit_sizes=bits, plain_bits=pb, sec128=False)
+    assert o.N == n and o.L == len(bits) - 1 and [q.bit_length() for q in o.moduli] == bits
+    assert o.t == {8192: 1032193, 16384: 786433, 32768: 786433}[n] and o.t.bit_length() == 20
+    data = o.moduli[:o.L]
+    assert any(q < 2 ** 47 for q in data), "a prime of the fp64 engine"
+    assert any(q >= 2 ** 47 for q in data), "a prime of the u64 engine"
+    wide = [q for q in o.moduli if q >= 2 ** 47]  # the form is the context's: the key prime counts
+    if name.endswith("fold"):  # the fold form takes primes 2^60 - c with c < 2^26 only (he_params.h, u64_fold)
+        assert all(0 < 2 ** 60 - q < 2 ** 26 for q in wide)
+    else:
+        assert all(q.bit_length() == 50 for q in wide)
+    # the counts the large-ring shapes are sized by
+    assert gad.table(data, 20)[1][-1] == {2: 5, 3: 7}[o.L]

@@ -13,7 +13,8 @@ bit-exact (np.array_equal, no tolerance):
 * refusals: a CKKS context, L_out outside 1..L_top, B == 0, B > Bmax, stride < B, (n - 1) stride at or above 2^63, an unpack output that is not 16-byte aligned, pack's alignment rules, n too large for one launch's
   grid, every overlap: the code, a message, and the output untouched; n == 0 touches nothing;
 * N = 1024 with n = 4097: the routed path's second pass through its pool block;
-* a second identical he355_bfv_unpack_bytes_ntt makes no raw hipMalloc (the fused path, and N = 1024's pool block);
+* a second identical he355_bfv_unpack_bytes_ntt makes no raw hipMalloc (the fused path, and N = 1024's pool block), and he355_bfv_route_stats
+  says which of the two ran (and counts the two passes of n = 4097);
 * end to end: n4096_d3, real keys, 16 records of Bmax random bytes, unpack_bytes_ntt at L_out = L_top, the query Enc(2^-4 X^i):
   expand(16) -> to_ntt -> bfv_multiply_plain_accumulate (1 x 1 x 16) -> from_ntt -> decrypt -> pack_bytes gives record i byte for byte, for
   two values of i; the noise budget is positive before the decryption."""
@@ -207,7 +208,10 @@ def test_n1024_second_pass_of_the_chunk_loop(be, oracle):
     n, B, L_out, keep = 4097, 9, 1, 3
     src, img, data = byte_slab(g, rng, n, B, B)
     buf = sentinelled(g, n * L_out * N, N)
+    g.bfv_route_stats(reset=True)
     g.bfv_unpack_bytes_ntt(L_out, n, src, BASE, B, B, At(buf, N))
+    routes = {k: c for k, c in g.bfv_route_stats().items() if c}
+    assert routes == {"bytes_routed": 2}, routes
     got = inner(buf, N, "chunks").reshape(n, L_out, N)
     Bmax, w = g.bfv_bytes_per_plain()
     plain, ref = g.to_device(np_fields(data[-keep:], w, N)), g.alloc(keep * L_out * N)
@@ -229,10 +233,13 @@ def test_second_identical_unpack_ntt_makes_no_raw_allocation(be, oracle, chain):
     g.bfv_unpack_bytes_ntt(g.L, n, src, BASE, Bmax, Bmax, out)
     g.sync()
     first = g.alloc_stats()
+    g.bfv_route_stats(reset=True)
     g.bfv_unpack_bytes_ntt(g.L, n, src, BASE, Bmax, Bmax, out)
     g.sync()
     second = g.alloc_stats()
     assert second["raw_mallocs"] == first["raw_mallocs"] and second["raw_frees"] == first["raw_frees"], (first, second)
+    routes = {k: c for k, c in g.bfv_route_stats().items() if c}  # N = 1024 has no column pass: one pass of the composition
+    assert routes == ({"bytes_routed": 1} if N == 1024 else {"bytes_fused": 1}), routes
     assert np.array_equal(out.download((n, g.L, N)), composition(g, g.L, n, src, BASE, Bmax, Bmax, N))
     g.close()
 

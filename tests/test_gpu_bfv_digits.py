@@ -13,7 +13,8 @@ he355_bfv_decompose_ntt, he355_bfv_compose), bit-exact (np.array_equal, no toler
   -> scan over children 0..7 (8 results per query) -> from_ntt -> mod_switch to L = 1 -> decompose_ntt (L = 1 -> L_out = 3) -> scan of
   children 8..15 against the F columns -> from_ntt -> decrypt (F plaintexts per query) -> compose at L = 1 -> decrypt at L = 1 gives
   database entry (i, j) exactly; the noise budget is positive after every stage (printed);
-* a second identical he355_bfv_decompose_ntt makes no raw hipMalloc (the fused path, and N = 1024's pool block)."""
+* a second identical he355_bfv_decompose_ntt makes no raw hipMalloc (the fused path, and N = 1024's pool block), and he355_bfv_route_stats says
+  which of the two ran."""
 import ctypes as C
 
 import numpy as np
@@ -306,9 +307,12 @@ def test_second_identical_decompose_ntt_makes_no_raw_allocation(be, oracle, chai
     g.bfv_decompose_ntt(L, size, n, dx, g.L, out)
     g.sync()
     first = g.alloc_stats()
+    g.bfv_route_stats(reset=True)
     g.bfv_decompose_ntt(L, size, n, dx, g.L, out)
     g.sync()
     second = g.alloc_stats()
     assert second["raw_mallocs"] == first["raw_mallocs"] and second["raw_frees"] == first["raw_frees"], (first, second)
+    routes = {k: c for k, c in g.bfv_route_stats().items() if c}  # N = 1024 has no column pass and takes the composition
+    assert routes == ({"digits_routed": 1} if N == 1024 else {"digits_fused": 1}), routes
     assert np.array_equal(out.download((n, F, g.L, N)), composition(g, L, size, n, dx, g.L, F, N))
     g.close()

@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from bfv_expand_ref import children, expand_levels, np_shift
 from bfv_gpu_helpers import ALL, SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -33,20 +34,6 @@ class At:
 
     def __init__(self, buf, off):
         self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def np_shift(x, e, moduli):
-    """x X^e mod (X^N + 1, q_i) for x [..., L, N] uint64 canonical residues, e in [0, 2N): numpy, the negative of 0 is 0"""
-    N = x.shape[-1]
-    assert 0 <= e < 2 * N
-    r = e % N
-    out = np.roll(x, r, axis=-1)
-    flip = (np.arange(N) < r) ^ (e >= N)  # wrapped past X^N once, and once more for e >= N
-    for i in range(x.shape[-2]):
-        q = np.uint64(moduli[i])
-        v = out[..., i, :]
-        out[..., i, :] = np.where(flip & (v != 0), q - v, v)
-    return out
 
 
 def test_np_shift_is_the_schoolbook_product():
@@ -157,27 +144,6 @@ def test_refusals(be, oracle):
 
 
 # ---- expansion against the definition, run in the oracle -------------------------------------------------------------------------------
-def expand_levels(o, c, d, gks, L):
-    """levels[j] = the 2^j nodes after j levels of the definition, for one query c [2][L][N]"""
-    N = o.N
-    levels = [[c]]
-    for j in range(d):
-        s, e = 1 << j, N // (1 << j) + 1
-        new = [None] * (2 * s)
-        for k, node in enumerate(levels[-1]):
-            gal = o.apply_galois(node, e, gks[e])
-            new[k] = o.add(node, gal)
-            new[k + s] = np_shift(o.sub(node, gal), 2 * N - s, o.moduli)
-        levels.append(new)
-    return levels
-
-
-def children(levels, count):
-    """the `count` children of one query: a cut last level computes the same values, fewer of them"""
-    d = (count - 1).bit_length()
-    return levels[d][:count]
-
-
 def to_level(o, ct, L):
     while ct.shape[1] > L:
         ct = o.mod_switch_coeff(ct)

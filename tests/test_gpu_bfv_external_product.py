@@ -6,7 +6,8 @@ he355_bfv_gadget_decompose_ntt, he355_bfv_rgsw_encrypt, he355_bfv_external_produ
   1..3, n in {1, 3}; uniform rows mixed with all-0, all-(q - 1) and alternating rows; sentinels around the output, the input read back;
 * gadget_decompose_ntt == gadget_decompose, the digits under every prime (reduced where not below it), he355_ntt_forward: the same grid, and
   n size L = 62, 64 and 198 (N >= 2048 runs the column pass from 256 blocks = n size L of 64 on, N = 1024's route below); once more behind
-  an unsynchronised he355_add; a second identical call makes no raw allocation;
+  an unsynchronised he355_add; a second identical call makes no raw allocation; the routes are bit-identical, so the 62 / 64 / 198 cases and the
+  run-boundary cases also assert he355_bfv_route_stats (which cut, which multiply-accumulate kernel, how many passes);
 * rgsw_encrypt == encrypt_zero with the same seed and indices, cut to L, the planted term in numpy, he355_bfv_transform_to_ntt: L in
   {L_top, 1}, messages 0, 1, X^5, -X^(N-1) and full-range;
 * external_product == gadget_decompose_ntt of the inner ciphertexts + he355_bfv_multiply_plain_accumulate(L, 2, 1, 1, inner 2E) with the RGSW
@@ -68,6 +69,11 @@ def inner_of(buf, N, what):
     got = buf.download()
     assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
     return got[N:-N]
+
+
+def routes(g):
+    """the counters of he355_bfv_route_stats that are not zero"""
+    return {k: c for k, c in g.bfv_route_stats().items() if c}
 
 
 def ntt_forward(be, g, buf, n_polys, L):
@@ -138,7 +144,10 @@ def test_gadget_decompose_ntt_equals_the_composition(be, oracle, chain):
         x = edged(o, rng, n, L, size)
         dx = g.to_device(x)
         buf = sentinelled(g, n * F * L * N, N)
+        g.bfv_route_stats(reset=True)
         g.bfv_gadget_decompose_ntt(L, v, size, n, dx, At(buf, N))
+        # both routes give the same bits: the counters say which one ran (N = 1024 has no column pass)
+        assert routes(g) == ({"cut_cols": 1} if N > 1024 and n * size * L >= 64 else {"cut_stream": 1}), (L, size, n, v)
         assert np.array_equal(inner_of(buf, N, (L, size, n)).reshape(n, F, L, N), composition_ntt(be, g, o, L, v, size, n, dx, F, N)), (L, size, n, v)
         dx.free()
         buf.free()
@@ -224,7 +233,7 @@ def ep_composition(g, L, v, n, inner, x, ct_at, rg, rg_stride_r, rows, N):
     return out
 
 
-def ep_case(g, o, rng, L, v, n, inner, shared, child_major, N, what):
+def ep_case(g, o, rng, L, v, n, inner, shared, child_major, N, what, routed=None):
     rows = 2 * g.bfv_gadget_count(L, v)[0]
     per = 2 * L * N
     n_rg = inner if shared else n * inner
@@ -237,7 +246,10 @@ def ep_case(g, o, rng, L, v, n, inner, shared, child_major, N, what):
     gr = 0 if shared else inner
     want = ep_composition(g, L, v, n, inner, x, lambda r, k: r * sr + k * sk, rg, gr, rows, N)
     buf = sentinelled(g, n * per, N)
+    g.bfv_route_stats(reset=True)
     g.bfv_external_product(L, v, n, inner, dx, sr, sk, rg, gr, 1, At(buf, N))
+    if routed is not None:
+        assert routes(g) == routed, (what, routes(g))
     assert np.array_equal(inner_of(buf, N, what).reshape(n, 2, L, N), want), what
     assert np.array_equal(dx.download(x.shape), x), (what, "ciphertexts")
     assert np.array_equal(rg.download(), rg_before), (what, "RGSW")
@@ -288,7 +300,10 @@ def test_external_product_run_boundary(be, oracle, inner, n):
     assert run == 256 and (inner * rows > run) == (inner == 9)
     if n > 1:
         assert 4096 // (inner * rows) < n  # more than one pass through the pool block, the last one ragged
-    ep_case(g, o, np.random.default_rng(87), L, v, n, inner, True, False, N, (inner, n))
+    # 16 results: 15 in the first pass (the column pass), the last one alone (9 ciphertexts: the streaming cut); one result over rows that
+    # follow one another is k_bfv_plain_mac's
+    routed = {"cut_cols": 1, "cut_stream": 1, "mac_gadget": 2, "passes": 2} if n > 1 else {"cut_stream": 1, "mac_plain": 1, "passes": 1}
+    ep_case(g, o, np.random.default_rng(87), L, v, n, inner, True, False, N, (inner, n), routed)
     g.close()
 
 

@@ -11,9 +11,9 @@ he355_bfv_rgsw_from_bfv), bit-exact (np.array_equal, Python integers, no toleran
   arithmetic): L in {L_top, 1}, (digit_bits, key_bits) in {(20, 20), (20, 4), (45, 20), (63, 63)}, (n, n_sel) in {(1, 1), (2, 3)}, unit strides
   and the child-major strides of an expansion (d_ct at a child behind the first ones); on the N >= 2048 chains n n_sel E 2 L = 62, 64 and 66
   (the column pass runs from 256 blocks = 64 on, the streaming route below); on the 2048 chain at L = 1, key_bits = 4 (2 E_key = 30 rows, below
-  the 256-term run of the 60-bit prime) 150 slot ciphertexts, two passes of 136 through the pool block, the last one ragged; on n4096_d3 at
-  L = 3, key_bits = 1 one result sums 2 E_key = 280 terms, above the run (a fold inside one result); sentinels, operands read back; once behind
-  an unsynchronised he355_add; a second identical call makes no raw allocation;
+  the 256-term run of the 60-bit prime) 150 slot ciphertexts, two passes of 136 through the pool block, the last one ragged (the threshold
+  and the two-pass cases also assert he355_bfv_route_stats: which cut ran, in how many passes); on n4096_d3 at L = 3, key_bits = 1 one result
+  sums 2 E_key = 280 terms, above the run (a fold inside one result); sentinels, operands read back; once behind an unsynchronised he355_add; a second identical call makes no raw allocation;
 * meaning, real keys, n4096_d3 at L = 3, digit_bits = key_bits = 20: selectors (0, 1, t - 1) in one query, selector_encrypt -> bfv_expand ->
   rgsw_from_bfv -> external_product on Enc(mu), mu full-range, decrypts to lift(m) mu mod t by Python integers; budgets printed and positive;
 * end to end, ONE ciphertext per query, n4096_d3, L = 3 throughout, the 8 x 8 database and the two queries of test_gpu_bfv_external_product.py:
@@ -170,7 +170,7 @@ def composition(g, L, kv, x, order, key, E, N):
     return ref.np_rows(k0, k1, E)
 
 
-def from_bfv_case(g, o, rng, L, v, kv, n, n_sel, child_major, N, what, producer=False, twice=False):
+def from_bfv_case(g, o, rng, L, v, kv, n, n_sel, child_major, N, what, producer=False, twice=False, routed=None):
     E, rows = g.bfv_gadget_count(L, v)[0], 2 * g.bfv_gadget_count(L, kv)[0]
     per = 2 * L * N
     S = n_sel * E  # slot ciphertexts per query
@@ -197,7 +197,11 @@ def from_bfv_case(g, o, rng, L, v, kv, n, n_sel, child_major, N, what, producer=
     if producer:
         g.sync()
         g.add(L, 2, len(x), da, db, type(g).pairwise(), dx)
+    g.bfv_route_stats(reset=True)
     g.bfv_rgsw_from_bfv(L, v, kv, n, n_sel, At(dx, lead * n * per), sr, sk_, key, At(buf, N))
+    if routed is not None:  # both cuts give the same bits: the counters of he355_bfv_route_stats say which one ran, and in how many passes
+        got_routes = {k: c for k, c in g.bfv_route_stats().items() if c}
+        assert got_routes == routed, (what, got_routes)
     got = inner_of(buf, N, what).reshape(n * n_sel, 2 * E, 2, L, N)
     assert np.array_equal(dx.download(x.shape), x), (what, "ciphertexts")
     assert np.array_equal(key.download(), key_before), (what, "key")
@@ -206,9 +210,12 @@ def from_bfv_case(g, o, rng, L, v, kv, n, n_sel, child_major, N, what, producer=
     if twice:  # a second identical call makes no raw allocation
         g.sync()
         first = g.alloc_stats()
+        g.bfv_route_stats(reset=True)
         g.bfv_rgsw_from_bfv(L, v, kv, n, n_sel, At(dx, lead * n * per), sr, sk_, key, At(buf, N))
         g.sync()
         assert same_allocs(first, g.alloc_stats()), what
+        if routed is not None:
+            assert {k: c for k, c in g.bfv_route_stats().items() if c} == routed, (what, "again")
         assert np.array_equal(inner_of(buf, N, what).reshape(got.shape), want), (what, "again")
     for d in (key, dx, buf):
         d.free()
@@ -237,7 +244,8 @@ def test_rgsw_from_bfv_column_pass_threshold(be, oracle, chain):
     assert E == 1
     for n, n_sel in ((1, 31), (2, 16), (3, 11)):
         assert n * n_sel * E * 2 * L == {31: 62, 32: 64, 33: 66}[n * n_sel]
-        from_bfv_case(g, o, rng, L, v, 20, n, n_sel, n == 2, N, (n, n_sel))
+        routed = {"own_cols" if n * n_sel * E * 2 * L >= 64 else "own_stream": 1, "passes": 1}
+        from_bfv_case(g, o, rng, L, v, 20, n, n_sel, n == 2, N, (n, n_sel), routed=routed)
     g.close()
 
 
@@ -250,7 +258,8 @@ def test_rgsw_from_bfv_two_passes_the_last_one_ragged(be, oracle):
     assert run == 256 > rows
     per_pass, slots = 4096 // rows, n * n_sel * E
     assert per_pass < slots < 2 * per_pass and slots % per_pass  # two passes through the pool block, the last one ragged
-    from_bfv_case(g, o, np.random.default_rng(95), L, v, kv, n, n_sel, True, N, "two passes", twice=True)
+    # the cut is decided once per call, from the first pass: 136 slot ciphertexts are far above the column pass's threshold
+    from_bfv_case(g, o, np.random.default_rng(95), L, v, kv, n, n_sel, True, N, "two passes", twice=True, routed={"own_cols": 2, "passes": 2})
     g.close()
 
 
