@@ -134,6 +134,22 @@ typedef struct {
     uint64_t reserved[5];
 } he355_bfv_route_stats_t;
 int he355_bfv_route_stats(he355_ctx *ctx, he355_bfv_route_stats_t *out, int reset);
+/* Which route the context's BEHZ multiplies (he355_bfv_multiply, he355_bfv_multiply_relin_accumulate) took since he355_device_init (or the
+ * last call with reset != 0): DESIGN.md, "BFV multiply", lists the decisions.  Every route gives the same bits; tests use the counters to
+ * prove which kernels they held to the oracle (tests/test_gpu_bfv_multiply_routes.py, against the restatement in tests/bfv_multiply_plan.py).
+ * Counted on the host where the call branches; no counter is read by a launch. */
+typedef struct {
+    uint64_t calls_lists, calls_pairs;   /* calls by path: every distinct operand extended once / the two operands of every result */
+    uint64_t chunks;                     /* kernel sequences over a chunk of results, both paths */
+    uint64_t cols_fused, cols_unfused;   /* extensions and floor steps (one count each) with the column passes inside / as separate launches */
+    uint64_t cols_exact;                 /* of cols_fused: the instantiations compiled for exactly L = nB = 2, 3, 4 at N = 8192 */
+    uint64_t coef_wide;                  /* of cols_unfused: the <16, 24> coefficient kernels (L > 4 or nB > 6) */
+    uint64_t rows_dual, rows_split;      /* per-pair chunks: k_behz_rows_tensor_dual / one launch per engine */
+    uint64_t inv_dual, inv_split;        /* lists chunks: k_behz_tensor_inv_dual / one launch per engine */
+    uint64_t lds_limit;                  /* not a counter: the dynamic LDS in bytes one block of the fused column kernels may ask for on this device */
+    uint64_t reserved[4];
+} he355_bfv_multiply_stats_t;
+int he355_bfv_multiply_stats(he355_ctx *ctx, he355_bfv_multiply_stats_t *out, int reset);
 int he355_upload(he355_ctx *ctx, void *d_dst, const void *h_src, uint64_t bytes);
 int he355_download(he355_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes);
 int he355_copy(he355_ctx *ctx, void *d_dst, const void *d_src, uint64_t bytes); /* device to device, on the context's stream */

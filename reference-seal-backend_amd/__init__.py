@@ -49,6 +49,11 @@ class BfvRouteStats(C.Structure):
                                            "digits_routed", "bytes_fused", "bytes_routed", "passes")] + [("reserved", C.c_uint64 * 5)]
 
 
+class BfvMultiplyStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("calls_lists", "calls_pairs", "chunks", "cols_fused", "cols_unfused", "cols_exact", "coef_wide",
+                                           "rows_dual", "rows_split", "inv_dual", "inv_split", "lds_limit")] + [("reserved", C.c_uint64 * 4)]
+
+
 def build(force: bool = False) -> str:
     """Compile the backend for gfx950 with hipcc (csrc/Makefile)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -172,6 +177,7 @@ def lib():
             "he355_pool_trim": (i32, [vp, C.POINTER(C.c_uint64)]),
             "he355_path_stats": (i32, [vp, C.POINTER(PathStats), i32]),
             "he355_bfv_route_stats": (i32, [vp, C.POINTER(BfvRouteStats), i32]),
+            "he355_bfv_multiply_stats": (i32, [vp, C.POINTER(BfvMultiplyStats), i32]),
             "he355_bridge_abi": (u64, [C.c_char_p, u64]),
             "he355_bridge_group_load_bytes": (u64, [i32, i32]),
         }
@@ -193,7 +199,7 @@ C_ABI_SYMBOLS = [
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
-    "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
+    "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
 
@@ -647,6 +653,13 @@ class Context:
         st = BfvRouteStats()
         _check(lib().he355_bfv_route_stats(self.h, C.byref(st), int(reset)))
         return {k: int(getattr(st, k)) for k, _ in BfvRouteStats._fields_ if k != "reserved"}
+
+    def bfv_multiply_stats(self, reset: bool = False) -> dict:
+        """which route the BEHZ multiplies took (he355_bfv_multiply_stats): counts of calls, chunks and launches by kind since device_init or
+        the last reset, and `lds_limit`, the dynamic LDS in bytes the device grants one block of the fused column kernels (not a counter)"""
+        st = BfvMultiplyStats()
+        _check(lib().he355_bfv_multiply_stats(self.h, C.byref(st), int(reset)))
+        return {k: int(getattr(st, k)) for k, _ in BfvMultiplyStats._fields_ if k != "reserved"}
 
     def pool_trim(self) -> int:
         b = C.c_uint64()

@@ -1398,6 +1398,16 @@ public:
             return H.view(d, ddev, P.K);
         });
     }
+    // which route the BEHZ multiplies of this context took (he355_bfv_multiply_stats): counted below where bfv_multiply3 branches and from what
+    // the launch_behz_* functions return, read by no launch; lds_limit is the device's answer, not a counter
+    he355_bfv_multiply_stats_t bfv_multiply_stats(bool reset)
+    {
+        use();
+        he355_bfv_multiply_stats_t s = mul_routes_;
+        s.lds_limit = behz_cols_lds_limit(env_);
+        if (reset) mul_routes_ = he355_bfv_multiply_stats_t{};
+        return s;
+    }
     // out(i, j) = sum_k relinearize(multiply(a(i, k), b(k, j))): the multiply / relinearize_inplace / add_inplace loop of the BFV
     // CipherBatchAxis matrix product (bfv cipherbatchaxis .cpp:398-410) with the inner index as part of the batch -- one multiply and
     // one relinearization over rows * cols * k ciphertext pairs, then the sums over k (modular additions: any order, same residues).
@@ -1445,9 +1455,11 @@ public:
     void behz_extend_fwd_cols(const BehzDev &Z, const BehzSrc &src, bool fuse_cols, u64 n_items, u64 *xq, u64 *xb, PolyView vq, PolyView vb)
     {
         if (fuse_cols) {
-            launch_behz_extend_cols(env_, Z, src, n_items, xq, xb);
+            ++mul_routes_.cols_fused;
+            mul_routes_.cols_exact += launch_behz_extend_cols(env_, Z, src, n_items, xq, xb);
         } else {
-            launch_behz_extend(env_, Z, src, n_items, xq, xb);
+            ++mul_routes_.cols_unfused;
+            mul_routes_.coef_wide += launch_behz_extend(env_, Z, src, n_items, xq, xb);
             vq.base = xq; launch_cols_fwd(env_, vq, (u32)(n_items * 2));
             vb.base = xb; launch_cols_fwd(env_, vb, (u32)(n_items * 2));
         }
@@ -1456,11 +1468,13 @@ public:
     void behz_inv_cols_floor(const BehzDev &Z, bool fuse_cols, u64 nc, u64 *dq, u64 *ds, u64 *out, PolyView vq, PolyView vb)
     {
         if (fuse_cols) {
-            launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out);
+            ++mul_routes_.cols_fused;
+            mul_routes_.cols_exact += launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out);
         } else {
+            ++mul_routes_.cols_unfused;
             vq.base = dq; launch_cols_inv(env_, vq, (u32)(nc * 3));
             vb.base = ds; launch_cols_inv(env_, vb, (u32)(nc * 3));
-            launch_behz_floor_sk(env_, Z, nc, dq, ds, out);
+            mul_routes_.coef_wide += launch_behz_floor_sk(env_, Z, nc, dq, ds, out);
         }
     }
     void bfv_multiply3(int L, u64 n, const u64 *a, const u64 *b, Indexer3 ix, u64 *out)
@@ -1502,13 +1516,15 @@ public:
         }
         if (lists) {
             src.lists = 1;
+            ++mul_routes_.calls_lists;
             u64 *eq = arena.p, *eb = eq + (size_t)n_cts * 2 * L * N, *dq = eb + (size_t)n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
             behz_extend_fwd_cols(Z, src, fuse_cols, n_cts, eq, eb, vq, vb);
             vq.base = eq; launch_rows_fwd(env_, vq, (u32)(n_cts * 2));
             vb.base = eb; launch_rows_fwd(env_, vb, (u32)(n_cts * 2));
             for (u64 off = 0; off < n; off += c) {
                 const u64 nc = std::min<u64>(c, n - off);
-                launch_behz_tensor_inv(env_, Z, src, nc, off, eq, eb, dq, ds);
+                ++mul_routes_.chunks;
+                ++(launch_behz_tensor_inv(env_, Z, src, nc, off, eq, eb, dq, ds) ? mul_routes_.inv_dual : mul_routes_.inv_split);
                 behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
             }
             HIPCHECK(hipGetLastError());
@@ -1517,6 +1533,7 @@ public:
         const size_t per_op = (4 * L + 4 * S) * N + per_res;
         c = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, per_op * k * 8); });
         if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the BFV multiply scratch of one ciphertext does not fit");
+        ++mul_routes_.calls_pairs;
         u64 *xq = arena.p, *xb = xq + c * 4 * L * N, *dq = xb + c * 4 * S * N, *ds = dq + c * 3 * L * N;
         for (u64 off = 0; off < n; off += c) {
             const u64 nc = std::min<u64>(c, n - off);
@@ -1525,7 +1542,8 @@ public:
             // passes and steps (6)-(8)
             src.op_offset = off;
             behz_extend_fwd_cols(Z, src, fuse_cols, nc * 2, xq, xb, vq, vb);
-            launch_behz_rows_tensor(env_, Z, nc, xq, xb, dq, ds);
+            ++mul_routes_.chunks;
+            ++(launch_behz_rows_tensor(env_, Z, nc, xq, xb, dq, ds) ? mul_routes_.rows_dual : mul_routes_.rows_split);
             behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
         }
         HIPCHECK(hipGetLastError());
@@ -2566,6 +2584,7 @@ private:
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
     he355_path_stats_t paths_{};
     he355_bfv_route_stats_t routes_{};
+    he355_bfv_multiply_stats_t mul_routes_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
     u64 lds_max_ = 0;
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
@@ -2748,6 +2767,13 @@ int he355_bfv_route_stats(he355_ctx *c, he355_bfv_route_stats_t *out, int reset)
     return guarded([&] {
         if (!out) throw std::invalid_argument("null pointer");
         *out = dev(c).bfv_route_stats(reset != 0);
+    });
+}
+int he355_bfv_multiply_stats(he355_ctx *c, he355_bfv_multiply_stats_t *out, int reset)
+{
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null pointer");
+        *out = dev(c).bfv_multiply_stats(reset != 0);
     });
 }
 int he355_pool_trim(he355_ctx *c, uint64_t *released_bytes)

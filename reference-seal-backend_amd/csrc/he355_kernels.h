@@ -214,6 +214,7 @@ HE355_FWD(launch_floor_cols)
 HE355_FWD(launch_floor_rows)
 HE355_FWD(launch_behz_extend)
 HE355_FWD(behz_cols_fusable)
+HE355_FWD(behz_cols_lds_limit)
 HE355_FWD(launch_behz_extend_cols)
 HE355_FWD(launch_behz_tensor_inv)
 HE355_FWD(launch_rows_fwd)

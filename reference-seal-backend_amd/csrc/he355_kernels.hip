@@ -2434,26 +2434,64 @@ void launch_rows_inv_select(const KernelEnv &env, int prime, u64 n_polys, const 
                        env.logn1);
 }
 
-void launch_behz_extend(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
+bool launch_behz_extend(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
 {
-    if (!n_cts) return;
+    const bool wide = !(bz.L <= 4 && bz.nB <= 6);
+    if (!n_cts) return wide;
     const int logN = env.logn1 + kRowLog;
     const u64 threads = (n_cts * 2) << logN;
-    if (bz.L <= 4 && bz.nB <= 6)
+    if (!wide)
         hipLaunchKernelGGL((k_behz_extend<4, 6>), dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, bz, env.primes, src, xq, xbsk, n_cts * 2, logN);
     else
         hipLaunchKernelGGL((k_behz_extend<kBehzMaxL, kBehzMaxB>), dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, bz, env.primes, src, xq, xbsk, n_cts * 2, logN);
+    return wide;
 }
+// The dynamic LDS one block of the fused column kernels may ask for on the current device, queried once per device (and per build of the
+// device code: a function's attributes belong to the device it was loaded on, he355_kernels_lds.hip).  The LOGN1 = 4 pair is the only one
+// that can pass 64 KiB (up to 4 + 7 residues of 8 KiB = 88 KiB): where the device reports more than 64 KiB per block, both kernels are
+// opted in here to what they can ask for, and a refusal leaves the limit at 64 KiB -- behz_cols_fusable then sends the larger shapes
+// down the unfused route instead of into a launch the runtime would refuse.
+constexpr size_t kBehzColsLdsNoOptIn = 64u << 10, kBehzColsLdsMax4 = (size_t)(4 + 6 + 1) * (64u << 4) * 8;
+size_t behz_cols_lds_limit(const KernelEnv &)
+{
+    static size_t limit_dev[64] = {}; // 0: not asked yet
+    int dev_id = 0;
+    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) dev_id = 63; // (slot 63 is never kept: asked every time)
+    if (limit_dev[dev_id]) return limit_dev[dev_id];
+    int per_block = 0, optin = 0;
+    if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id == 63 ? 0 : dev_id) != hipSuccess || per_block <= 0) {
+        (void)hipGetLastError();
+        per_block = (int)kBehzColsLdsNoOptIn;
+    }
+    if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, dev_id == 63 ? 0 : dev_id) != hipSuccess) {
+        (void)hipGetLastError(); // (a runtime without the attribute: the plain limit stands)
+        optin = 0;
+    }
+    size_t limit = (size_t)std::max(per_block, optin);
+    if (limit > kBehzColsLdsNoOptIn) {
+        const int want = (int)std::min(limit, kBehzColsLdsMax4);
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_behz_extend_cols<4, 4, 6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, want) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_behz_cols_floor_sk<4, 4, 6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, want) != hipSuccess) {
+            (void)hipGetLastError();
+            limit = kBehzColsLdsNoOptIn;
+        }
+    }
+    if (dev_id != 63) limit_dev[dev_id] = limit;
+    return limit;
+}
+size_t behz_cols_lds_bytes(const KernelEnv &env, const BehzDev &bz) { return (size_t)(bz.L + bz.nB + 1) * (64u << env.logn1) * 8; }
+// a pure function of (N, L, nB, the device's limit): tests/bfv_multiply_plan.py restates it
 bool behz_cols_fusable(const KernelEnv &env, const BehzDev &bz)
 {
-    return bz.L <= 4 && bz.nB <= 6 && env.logn1 >= 1 && env.logn1 <= 4;
+    return bz.L <= 4 && bz.nB <= 6 && env.logn1 >= 1 && env.logn1 <= 4 && behz_cols_lds_bytes(env, bz) <= behz_cols_lds_limit(env);
 }
-void launch_behz_extend_cols(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
+bool launch_behz_extend_cols(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
 {
-    if (!n_cts) return;
     if (!behz_cols_fusable(env, bz)) throw std::logic_error("launch_behz_extend_cols: shape not covered by the fused kernel");
+    const bool exact = env.logn1 == 3 && bz.L == bz.nB && bz.L >= 2;
+    if (!n_cts) return exact;
     const dim3 g((unsigned)(n_cts * 2 * 16)), blk(64u << env.logn1);
-    const size_t lds = (size_t)(bz.L + bz.nB + 1) * (64u << env.logn1) * 8;
+    const size_t lds = behz_cols_lds_bytes(env, bz);
 #define HE355_EXT(LOGN1, ML, MB, EXACT) hipLaunchKernelGGL((k_behz_extend_cols<LOGN1, ML, MB, EXACT>), g, blk, lds, env.stream, bz, env.primes, src, xq, xbsk)
     switch (env.logn1) {
     case 1: HE355_EXT(1, 4, 6, false); break;
@@ -2467,13 +2505,15 @@ void launch_behz_extend_cols(const KernelEnv &env, const BehzDev &bz, const Behz
         break;
     }
 #undef HE355_EXT
+    return exact;
 }
-void launch_behz_cols_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *dq, const u64 *ds, u64 *out)
+bool launch_behz_cols_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *dq, const u64 *ds, u64 *out)
 {
-    if (!n_ops) return;
     if (!behz_cols_fusable(env, bz)) throw std::logic_error("launch_behz_cols_floor_sk: shape not covered by the fused kernel");
+    const bool exact = env.logn1 == 3 && bz.L == bz.nB && bz.L >= 2;
+    if (!n_ops) return exact;
     const dim3 g((unsigned)(n_ops * 3 * 16)), blk(64u << env.logn1);
-    const size_t lds = (size_t)(bz.L + bz.nB + 1) * (64u << env.logn1) * 8;
+    const size_t lds = behz_cols_lds_bytes(env, bz);
 #define HE355_FLR(LOGN1, ML, MB, EXACT) hipLaunchKernelGGL((k_behz_cols_floor_sk<LOGN1, ML, MB, EXACT>), g, blk, lds, env.stream, bz, env.primes, dq, ds, out)
     switch (env.logn1) {
     case 1: HE355_FLR(1, 4, 6, false); break;
@@ -2487,10 +2527,11 @@ void launch_behz_cols_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_op
         break;
     }
 #undef HE355_FLR
+    return exact;
 }
-void launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *xq, const u64 *xbsk, u64 *dq, u64 *ds)
+bool launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *xq, const u64 *xbsk, u64 *dq, u64 *ds)
 {
-    if (!n_ops) return;
+    if (!n_ops) return false;
     BehzRowsArgs AE[2];
     unsigned ge[2] = {0, 0};
     const int S = bz.nB + 1;
@@ -2509,15 +2550,16 @@ void launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops,
     }
     if (ge[0] && ge[1] && ge[0] + ge[1] <= kDualMaxBlocks) {
         hipLaunchKernelGGL(k_behz_rows_tensor_dual, dim3(ge[0] + ge[1]), dim3(kBlock), 0, env.stream, AE[0], AE[1], ge[0], env.primes);
-        return;
+        return true;
     }
     if (ge[0]) hipLaunchKernelGGL(k_behz_rows_tensor<ArF64>, dim3(ge[0]), dim3(kBlock), 0, env.stream, AE[0], env.primes);
     if (ge[1]) hipLaunchKernelGGL(k_behz_rows_tensor<ArU64>, dim3(ge[1]), dim3(kBlock), 0, env.stream, AE[1], env.primes);
+    return false;
 }
-void launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_ops, u64 op_offset, const u64 *eq, const u64 *ebsk, u64 *dq,
+bool launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_ops, u64 op_offset, const u64 *eq, const u64 *ebsk, u64 *dq,
                             u64 *ds)
 {
-    if (!n_ops) return;
+    if (!n_ops) return false;
     BehzTensorArgs AE[2];
     u64 jobs[2] = {0, 0};
     const int S = bz.nB + 1;
@@ -2537,10 +2579,11 @@ void launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzS
     const unsigned g0 = grid_for(jobs[0], kWaves), g1 = grid_for(jobs[1], kWaves);
     if (jobs[0] && jobs[1] && g0 + g1 <= kDualMaxBlocks) {
         hipLaunchKernelGGL(k_behz_tensor_inv_dual, dim3(g0 + g1), dim3(kBlock), 0, env.stream, AE[0], AE[1], jobs[0], jobs[1], g0, env.primes);
-        return;
+        return true;
     }
     if (jobs[0]) hipLaunchKernelGGL(k_behz_tensor_inv<ArF64>, dim3(g0), dim3(kBlock), 0, env.stream, AE[0], env.primes, jobs[0]);
     if (jobs[1]) hipLaunchKernelGGL(k_behz_tensor_inv<ArU64>, dim3(g1), dim3(kBlock), 0, env.stream, AE[1], env.primes, jobs[1]);
+    return false;
 }
 void launch_rows_fwd(const KernelEnv &env, const PolyView &v, u32 n_items) // the row half of launch_ntt_forward (raw, or canonical when N = 1024, -> NTT form)
 {
@@ -2574,15 +2617,17 @@ void launch_cols_inv(const KernelEnv &env, const PolyView &v, u32 n_items) // th
     case 5: hipLaunchKernelGGL(k_cols_inv<5>, dim3(g), dim3(kBlock), 0, env.stream, v, env.primes); break;
     }
 }
-void launch_behz_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *dq, const u64 *ds, u64 *out)
+bool launch_behz_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *dq, const u64 *ds, u64 *out)
 {
-    if (!n_ops) return;
+    const bool wide = !(bz.L <= 4 && bz.nB <= 6);
+    if (!n_ops) return wide;
     const int logN = env.logn1 + kRowLog;
     const u64 threads = (n_ops * 3) << logN;
-    if (bz.L <= 4 && bz.nB <= 6)
+    if (!wide)
         hipLaunchKernelGGL((k_behz_floor_sk<4, 6>), dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, bz, env.primes, dq, ds, out, n_ops * 3, logN);
     else
         hipLaunchKernelGGL((k_behz_floor_sk<kBehzMaxL, kBehzMaxB>), dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, bz, env.primes, dq, ds, out, n_ops * 3, logN);
+    return wide;
 }
 void launch_bfv_galois(const KernelEnv &env, int L, u64 n_ops, const u64 *in, const uint32_t *gather, u64 *c01, u64 c01_item_stride, u64 *tgt,
                        const u64 *addend)

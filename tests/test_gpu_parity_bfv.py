@@ -5,6 +5,8 @@ import importlib
 import numpy as np
 import pytest
 
+from bfv_multiply_operands import family_cts
+
 pytestmark = pytest.mark.gpu
 
 CONFIGS = {
@@ -310,11 +312,6 @@ def test_bfv_multiply_rejects_outputs_that_overlap_an_operand(be, oracle):
     g.close()
 
 
-def _residues(o, values, L):
-    """Integer coefficient vector(s) -> residues [.., L, N] under the first L moduli."""
-    return np.stack([np.array([int(v) % q for v in values], dtype=np.uint64) for q in o.moduli[:L]])
-
-
 @pytest.mark.parametrize("base", ["device", "seal"])
 @pytest.mark.parametrize("name,N,bits,pb", [
     ("default_d3", 4096, [60, 40, 40, 60], 20),          # <4, 6> instantiation of the coefficient kernels
@@ -335,21 +332,8 @@ def test_bfv_multiply_is_independent_of_the_auxiliary_base(be, oracle, monkeypat
     o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False)
     assert g.moduli == o.moduli and g.t == o.t
     L = g.L
-    Q = 1
-    for q in o.moduli[:L]:
-        Q *= int(q)
-    h = Q // 2
-    alt = [h if i % 2 == 0 else h + 1 for i in range(N)]          # +Q/2, -Q/2 alternating
-    first_neg = [h + 1] + [h] * (N - 1)                            # coefficient 0: -a_0 b_0 ... all wrapped terms add up
-    polys = {
-        "plus_half": _residues(o, [h] * N, L), "minus_half": _residues(o, [h + 1] * N, L), "alternating": _residues(o, alt, L),
-        "first_negative": _residues(o, first_neg, L), "q_minus_1": _residues(o, [Q - 1] * N, L), "zero": _residues(o, [0] * N, L),
-        "one": _residues(o, [1] * N, L),
-    }
     rng = np.random.default_rng(77)
-    cts = [np.stack([polys[x], polys[y]]) for x, y in [("plus_half", "plus_half"), ("minus_half", "plus_half"), ("alternating", "alternating"),
-                                                         ("first_negative", "minus_half"), ("q_minus_1", "q_minus_1"), ("zero", "one"),
-                                                         ("q_minus_1", "plus_half")]]
+    cts = family_cts(o, L, N)  # bfv_multiply_operands.py: the same seven ciphertexts as before the families moved there
     cts += [o.random_poly(rng, L, 2) for _ in range(2)]
     a = np.stack(cts)
     n = len(cts)
