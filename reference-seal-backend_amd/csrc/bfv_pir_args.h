@@ -1,0 +1,232 @@
+// bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, decomposition, the external
+// product and its selectors, database bytes), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
+// device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands what the check worked out (the digit tables, F,
+// rows, terms, pass, the field width) to DeviceContext as a plan.  What needs the device or its state (keys present, the Galois keys, the
+// key-switch tables) is checked there.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
+// under the address and undefined-behaviour sanitizers.
+#pragma once
+#include <array>
+#include <stdexcept>
+#include <string>
+
+#include "bfv_bytes_core.h"
+#include "bfv_digits_core.h"
+#include "bfv_gadget_core.h"
+#include "he_params.h"
+
+namespace he355 {
+
+// do the u64 ranges [p, p + np) and [q, q + nq) share an element?
+inline bool ranges_overlap(const u64 *p, size_t np, const u64 *q, size_t nq) { return np && nq && p < q + nq && q < p + np; }
+inline void check_size(int size, int lo, int hi) // "ciphertext size must be 1..3" / "... 2 or 3"
+{
+    if (size < lo || size > hi) throw std::invalid_argument("ciphertext size must be " + std::to_string(lo) + (hi == lo + 1 ? " or " : "..") + std::to_string(hi));
+}
+// the first L primes of the chain (1 <= L <= L_top), as the table builders take them
+inline std::array<u64, kMaxPrimes> level_primes(const Params &p, int L)
+{
+    std::array<u64, kMaxPrimes> q{};
+    for (int i = 0; i < L; ++i) q[i] = p.primes[i].q;
+    return q;
+}
+
+// ---- monomial multiply and oblivious query expansion ------------------------------------------------------------------------------
+inline void check_monomial_args(const Params &p, int L, int size, u32 e)
+{
+    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_multiply_monomial: level out of range");
+    check_size(size, 1, 3);
+    if (e >= 2 * p.N) throw std::invalid_argument("he355_bfv_multiply_monomial: the exponent must be below 2N (X^N = -1)");
+}
+// levels of the expansion tree of `count` children, ceil(log2 count); level j uses the Galois element N / 2^j + 1
+inline int expand_depth(u64 count)
+{
+    int d = 0;
+    while (((u64)1 << d) < count) ++d;
+    return d;
+}
+struct BfvExpandPlan {
+    int depth;
+};
+inline BfvExpandPlan plan_expand(const Params &p, int L, u64 count)
+{
+    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_expand: level out of range");
+    if (count < 1 || count > p.N) throw std::invalid_argument("he355_bfv_expand: count must be in 1..N");
+    return {expand_depth(count)};
+}
+
+// ---- ciphertext decomposition for recursive (two-dimensional) PIR, and the gadget cut ----------------------------------------------
+// the digit table of level L and F = size D(L), the polynomials one ciphertext is cut into
+struct BfvDigitPlan {
+    BfvDigitTab tab;
+    u64 F;
+};
+inline BfvDigitTab digit_table(const Params &p, int L) { return bfv_digit_table(level_primes(p, L).data(), L, p.plain_modulus); }
+// `ct` [n][size][L][N], `plain` [n][F][N] (!ntt) or [n][F][L_out][N] (ntt: 1 <= L_out <= L_top): the two may not overlap, whichever is written
+inline BfvDigitPlan plan_digits(const Params &p, const char *what, int L, int size, u64 n, const u64 *ct, const u64 *plain, bool ntt = false, int L_out = 0)
+{
+    const std::string w(what);
+    if (L < 1 || (size_t)L > p.Ltop || L_out < (ntt ? 1 : 0) || (size_t)L_out > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    check_size(size, 1, 3);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    const BfvDigitTab tab = digit_table(p, L);
+    const u64 F = (u64)size * tab.total;
+    if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many plaintexts for one call (n F must be below 2^32)");
+    if (ranges_overlap(ct, (size_t)n * size * L * p.N, plain, (size_t)n * F * (L_out ? L_out : 1) * p.N))
+        throw std::invalid_argument(w + ": the plaintexts overlap the ciphertexts");
+    return {tab, F};
+}
+constexpr u64 kGadgetPassPolys = 4096; // digit polynomials one pass of he355_bfv_external_product holds in its pool block
+inline u64 gadget_poly_blocks(const Params &p, bool cols) { return cols && p.N > 1024 ? 4 : p.N / 512; } // blocks per residue polynomial
+inline BfvDigitTab gadget_table(const Params &p, const std::string &w, int L, int v)
+{
+    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    if (!bfv_gadget_width_ok(v)) throw std::invalid_argument(w + ": digit_bits must be 1..63");
+    return bfv_gadget_table(level_primes(p, L).data(), L, v);
+}
+// `ct` [n][size][L][N] -> `digits` [n][size E][N] (ntt false) or [n][size E][L][N]
+inline BfvDigitPlan plan_gadget_cut(const Params &p, const char *what, int L, int v, int size, u64 n, const u64 *ct, const u64 *digits, bool ntt)
+{
+    const std::string w(what);
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    check_size(size, 1, 3);
+    const u64 F = (u64)size * tab.total;
+    if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many digit polynomials for one call (n size E must be below 2^32)");
+    if (n * size * L > 0x7fffffffull / gadget_poly_blocks(p, ntt)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+    if (ranges_overlap(ct, (size_t)n * size * L * p.N, digits, (size_t)n * F * (ntt ? L : 1) * p.N)) throw std::invalid_argument(w + ": the digits overlap the ciphertexts");
+    return {tab, F};
+}
+
+// ---- the external product RGSW x ciphertext ----------------------------------------------------------------------------------------
+// the gadget table of level L and the rows n 2 E(L) of the batch, each an encryption of zero plus its planted term
+struct BfvRgswPlan {
+    BfvDigitTab tab;
+    u64 rows;
+};
+inline BfvRgswPlan plan_rgsw(const Params &p, int L, int v, u64 n, const u64 *plain, const u64 *out)
+{
+    const std::string w("he355_bfv_rgsw_encrypt");
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    const u64 per = 2 * (u64)tab.total * 2 * L; // residue polynomials of one RGSW ciphertext
+    if (n > 0x7fffffffull / (per * (p.N / 512))) throw std::invalid_argument(w + ": too many RGSW ciphertexts for one launch");
+    if (ranges_overlap(plain, (size_t)n * p.N, out, (size_t)n * per * p.N)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the plaintexts");
+    return {tab, n * 2 * tab.total};
+}
+// the words from the first operand of a batch to the end of the last one it touches, ((n - 1) stride_r + (inner - 1) stride_k + 1) items of
+// `item_words` each, formed in 128 bits and refused where they cannot lie in one address space
+inline size_t gadget_span_words(const std::string &w, u64 n, u64 inner, u64 stride_r, u64 stride_k, u64 item_words)
+{
+    const u128 items = (u128)(n - 1) * stride_r + (u128)(inner - 1) * stride_k + 1;
+    if (items > ((u128)1 << 60) || items * item_words > ((u128)1 << 60)) throw std::invalid_argument(w + ": a stride takes the operands past 2^60 words");
+    return (size_t)(items * item_words);
+}
+// rows = 2 E(L) of one RGSW ciphertext, terms = inner rows digit polynomials per result, pass = results per pass (bfv_gadget_pass; 0 when n is)
+struct BfvExternalPlan {
+    BfvDigitTab tab;
+    u32 rows;
+    u64 terms, pass;
+};
+inline BfvExternalPlan plan_external_product(const Params &p, int L, int v, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r,
+                                             u64 rg_stride_k, const u64 *out)
+{
+    const std::string w("he355_bfv_external_product");
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    const u64 rows = 2 * (u64)tab.total;
+    if (inner < 1 || inner > 0x7fffffffull / rows) throw std::invalid_argument(w + ": inner must be at least 1 and inner 2 E(L) below 2^31");
+    const u64 terms = inner * rows, pass = bfv_gadget_pass(terms, n, kGadgetPassPolys);
+    const BfvExternalPlan plan{tab, (u32)rows, terms, pass};
+    if (!n) return plan;
+    if (n > 0x7fffffffull || pass * inner * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, true) || pass * L > 0x7fffffffull / (p.N / 512))
+        throw std::invalid_argument(w + ": too many polynomials for one launch");
+    const size_t ctn = 2 * (size_t)L * p.N;
+    if (ranges_overlap(out, n * ctn, ct, gadget_span_words(w, n, inner, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the ciphertexts");
+    if (ranges_overlap(out, n * ctn, rgsw, gadget_span_words(w, n, inner, rg_stride_r, rg_stride_k, rows * ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the RGSW ciphertexts");
+    return plan;
+}
+
+// ---- RGSW selectors from ONE packed query ciphertext ---------------------------------------------------------------------------------
+// `sel` [n][n_sel] mod t -> `out` [n][2][L][N]; depth: the levels of the expansion the query is packed for
+struct BfvSelectorPlan {
+    BfvDigitTab tab;
+    int depth;
+};
+inline BfvSelectorPlan plan_selector(const Params &p, int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, const u64 *out)
+{
+    const std::string w("he355_bfv_selector_encrypt");
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
+    if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
+    if ((u128)first_slot + (u128)n_sel * tab.total > count) throw std::invalid_argument(w + ": first_slot + n_sel E(L) must not exceed count");
+    if (n > 0x7fffffffull / (2 * (u64)L * (p.N / 512))) throw std::invalid_argument(w + ": too many ciphertexts for one launch");
+    if (ranges_overlap(sel, (size_t)(n * n_sel), out, (size_t)n * 2 * L * p.N)) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
+    return {tab, expand_depth(count)};
+}
+// the call's own refusals; its RGSW rows are he355_bfv_rgsw_encrypt's (plan_rgsw with n = 1, once the secret's coefficients lie in their block)
+inline void check_rgsw_secret_args(const Params &p, int L, int kv)
+{
+    const std::string w("he355_bfv_rgsw_encrypt_secret");
+    if (L >= 1 && (size_t)L <= p.Ltop && !bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
+    const BfvDigitTab tab = gadget_table(p, w, L, kv);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    if (2 * (u64)tab.total * 2 * L > 0x7fffffffull / (p.N / 512)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+}
+// slot ciphertexts at r ct_stride_r + (b E + f) ct_stride_k of `ct`, `key` [2 E_key][2][L][N] -> `out` [n][n_sel][2E][2][L][N].  tab: the selectors'
+// table, ktab: the key's; rows = 2 E_key terms per slot ciphertext, C = n n_sel E slot ciphertexts, pass of them at a time (both 0 when n is)
+struct BfvFromBfvPlan {
+    BfvDigitTab tab, ktab;
+    u32 rows;
+    u64 C, pass;
+};
+inline BfvFromBfvPlan plan_from_bfv(const Params &p, int L, int v, int kv, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key, const u64 *out)
+{
+    const std::string w("he355_bfv_rgsw_from_bfv");
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    if (!bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
+    const BfvDigitTab kt = gadget_table(p, w, L, kv);
+    const u64 rows = 2 * (u64)kt.total;
+    if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
+    if (!n) return {tab, kt, (u32)rows, 0, 0};
+    const u128 slots = (u128)n * n_sel * tab.total; // slot ciphertexts
+    if (n > 0x7fffffffull || n_sel > 0x7fffffffull || slots > 0x7fffffffull / (2 * (u64)L * 4)) throw std::invalid_argument(w + ": too many polynomials for one launch");
+    const u64 C = (u64)slots, pass = bfv_gadget_pass(rows, C, kGadgetPassPolys);
+    if (pass * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, false) || pass * rows * L > 0x3fffffffull)
+        throw std::invalid_argument(w + ": too many polynomials for one launch");
+    const size_t ctn = 2 * (size_t)L * p.N, outn = (size_t)C * 2 * ctn;
+    if (ranges_overlap(out, outn, ct, gadget_span_words(w, n, n_sel * tab.total, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_rgsw` overlaps the ciphertexts");
+    if (ranges_overlap(out, outn, key, (size_t)rows * ctn)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the key");
+    return {tab, kt, (u32)rows, C, pass};
+}
+
+// ---- a PIR database from packed bytes -------------------------------------------------------------------------------------------------
+constexpr u64 kBytesChunk = 4096; // N = 1024's routed path: plaintexts per pass through its pool block (32 MiB)
+struct BfvBytesPlan {
+    int w; // the field width
+};
+// `bytes`: plaintext j at bytes + j stride, B bytes; `words`: [n][per] 64-bit words, per = N (coefficients) or L_out N (ntt: 1 <= L_out <= L_top).
+// pack: the bytes are the output, whole 8-byte words of it.
+inline BfvBytesPlan plan_bytes(const Params &p, const char *what, u64 n, const void *bytes, u64 stride, u64 B, const u64 *words, bool pack, bool ntt = false, int L_out = 0)
+{
+    const std::string s(what);
+    if (L_out < (ntt ? 1 : 0) || (size_t)L_out > p.Ltop) throw std::invalid_argument(s + ": level out of range");
+    if (p.plain_modulus < 2) throw std::invalid_argument(s + ": the plain modulus must be at least 2");
+    const int w = bfv_bitlen(p.plain_modulus) - 1;
+    if (B < 1 || B > bfv_bytes_max(p.N, w)) throw std::invalid_argument(s + ": bytes_per_plain must be 1 .. floor(N w / 8) (he355_bfv_bytes_per_plain)");
+    if (stride < B) throw std::invalid_argument(s + ": stride_bytes must be at least bytes_per_plain");
+    const u64 tail = pack ? 8 * bfv_bytes_words(B) : B; // the bytes of the last plaintext the call touches
+    // (n - 1) stride + tail stays below 2^63: neither the range below nor a kernel's j * stride can wrap
+    if (n > 1 && n - 1 > (((u64)1 << 63) - tail) / stride) throw std::invalid_argument(s + ": (n - 1) stride_bytes must be below 2^63");
+    if (!pack && !L_out && ((unsigned long long)words & 15)) throw std::invalid_argument(s + ": d_plain must be 16-byte aligned");
+    if (pack && (((unsigned long long)bytes & 7) || (stride & 7) || stride < tail))
+        throw std::invalid_argument(s + ": d_bytes must be 8-byte aligned and stride_bytes a multiple of 8, at least 8 ceil(bytes_per_plain / 8)");
+    if (n > 0x7fffffffull / (p.N / 256)) throw std::invalid_argument(s + ": too many plaintexts for one launch (n N / 256 must be below 2^31)");
+    if (n) {
+        const unsigned long long b0 = (unsigned long long)bytes, b1 = b0 + (n - 1) * stride + tail;
+        const unsigned long long w0 = (unsigned long long)words, w1 = w0 + n * (L_out ? (u64)L_out : 1) * p.N * 8;
+        if (b1 < b0 || w1 < w0) throw std::invalid_argument(s + ": a range wraps the address space");
+        if (b0 < w1 && w0 < b1) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
+    }
+    return {w};
+}
+
+} // namespace he355

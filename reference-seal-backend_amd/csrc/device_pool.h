@@ -25,6 +25,7 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 namespace he355 {
@@ -182,6 +183,30 @@ private:
     std::unordered_map<void *, size_t> live_;
     std::unordered_set<void *> cached_; // the blocks on the free lists (release() tells a second free from a foreign pointer)
     Stats st_;
+};
+
+// A block of a pool for the length of a scope: taken when the holder is made (or none: the default holder is empty) and back on its free
+// list when the holder goes, however the scope is left.  That is a release like any other -- no HIP call, and the kernels queued on the
+// block stay ahead of whatever takes it next (stream order, above).  Move-only.  The block is the pool's own, so release() has nothing to
+// refuse; what it could still throw (the mutex, a list that cannot grow) ends the process in the destructor rather than unwinding twice.
+class PoolBlock {
+public:
+    PoolBlock() = default;
+    PoolBlock(DevicePool &pool, size_t bytes) : pool_(&pool), p_(pool.alloc(bytes)) {}
+    PoolBlock(PoolBlock &&o) noexcept : pool_(o.pool_), p_(o.p_) { o.p_ = nullptr; }
+    PoolBlock &operator=(PoolBlock &&o) noexcept
+    {
+        std::swap(pool_, o.pool_);
+        std::swap(p_, o.p_);
+        return *this;
+    }
+    ~PoolBlock() { if (p_) pool_->release(p_); }
+    uint64_t *get() const { return static_cast<uint64_t *>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    DevicePool *pool_ = nullptr;
+    void *p_ = nullptr;
 };
 
 // A grow-on-demand device buffer of a context: one raw block of its pool and the block's size.  DeviceContext::reserve grows it (the

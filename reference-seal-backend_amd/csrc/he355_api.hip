@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/he355.h"
+#include "bfv_pir_args.h"
 #include "device_pool.h"
 #include "he355_internal.h"
 #include "he355_kernels.h"
@@ -300,6 +301,12 @@ public:
         default: throw std::invalid_argument("he355_free: not a block this context allocated (he355_malloc of another context?)");
         }
     }
+    // a pool block that goes back at the end of the caller's scope (device_pool.h)
+    PoolBlock scoped_block(size_t bytes)
+    {
+        use();
+        return PoolBlock(pool_, bytes);
+    }
     DevicePool::Stats alloc_stats() const { return pool_.stats(); }
     // which shape / schedule the key switches of this context took (he355_path_stats): counted per kernel sequence (one chunk of a batch)
     he355_path_stats_t path_stats(bool reset)
@@ -447,15 +454,21 @@ public:
     }
 
     // ---- per-op sequences ------------------------------------------------------------------------------
-    // do the u64 ranges [p, p + np) and [q, q + nq) share an element?
-    static bool ranges_overlap(const u64 *p, size_t np, const u64 *q, size_t nq) { return np && nq && p < q + nq && q < p + np; }
     void check_level(int L) const
     {
         if (L < 1 || (size_t)L > P.Ltop) throw std::invalid_argument("level out of range");
     }
-    static void check_size(int size, int lo, int hi) // "ciphertext size must be 1..3" / "... 2 or 3"
+    // plain [n][N] mod t -> dst [n][L][N]: the centred lift under primes 0 .. L-1 and its forward transform (he355_bfv_plain_to_ntt's definition)
+    void plain_to_ntt(int L, u64 n, const u64 *src, u64 *dst)
     {
-        if (size < lo || size > hi) throw std::invalid_argument("ciphertext size must be " + std::to_string(lo) + (hi == lo + 1 ? " or " : "..") + std::to_string(hi));
+        launch_bfv_lift_plain(env_, L, n, src, dst, P.plain_modulus);
+        launch_ntt_forward(env_, poly_view(dst, L, P.N, L), (u32)n);
+    }
+    // the forward transform of `items` items of `v`: the row pass alone where a fused kernel has run the column pass (cols), else all of it
+    void forward_rows_or_full(bool cols, const PolyView &v, u32 items)
+    {
+        if (cols) launch_rows_fwd(env_, v, items);
+        else launch_ntt_forward(env_, v, items);
     }
     void addsub(int L, int size, u64 n, const u64 *a, const u64 *b, Indexer ix, u64 *out, bool sub)
     {
@@ -1426,27 +1439,18 @@ public:
         if (ranges_overlap(out, n * 2 * LN, a, a_cts * 2 * LN) || ranges_overlap(out, n * 2 * LN, b, b_cts * 2 * LN))
             throw std::invalid_argument("he355_bfv_multiply_relin_accumulate: `out` overlaps an operand");
         const u64 kc = std::max<u64>(1, std::min<u64>(inner, (u64)4096 / n)); // inner indices per pass: about 4096 products in flight
-        u64 *c3 = static_cast<u64 *>(pool_alloc(n * kc * 3 * LN * 8));
-        u64 *r2 = nullptr;
-        try {
-            r2 = static_cast<u64 *>(pool_alloc(n * kc * 2 * LN * 8));
-            for (u64 k0 = 0; k0 < inner; k0 += kc) {
-                const u64 kn = std::min<u64>(kc, inner - k0);
-                Indexer3 ix{};
-                ix.a_base = k0 * a_stride_k; ix.b_base = k0 * b_stride_k;
-                ix.gs = n; ix.b1 = cols; ix.a_sg = a_stride_k; ix.a_si = a_stride_i; ix.b_sg = b_stride_k; ix.b_sj = b_stride_j;
-                bfv_multiply3(L, n * kn, a, b, ix, c3);
-                relinearize(L, n * kn, c3, r2);
-                launch_sum_cts(env_, L, 2, kn, r2, out, n, k0 != 0);
-            }
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            pool_free(c3);
-            if (r2) pool_free(r2);
-            throw;
+        // (taken c3 then r2, as ever; a scope gives them back in reverse, r2 then c3 -- two size classes, so neither free list sees the order)
+        const PoolBlock c3 = scoped_block(n * kc * 3 * LN * 8), r2 = scoped_block(n * kc * 2 * LN * 8);
+        for (u64 k0 = 0; k0 < inner; k0 += kc) {
+            const u64 kn = std::min<u64>(kc, inner - k0);
+            Indexer3 ix{};
+            ix.a_base = k0 * a_stride_k; ix.b_base = k0 * b_stride_k;
+            ix.gs = n; ix.b1 = cols; ix.a_sg = a_stride_k; ix.a_si = a_stride_i; ix.b_sg = b_stride_k; ix.b_sj = b_stride_j;
+            bfv_multiply3(L, n * kn, a, b, ix, c3.get());
+            relinearize(L, n * kn, c3.get(), r2.get());
+            launch_sum_cts(env_, L, 2, kn, r2.get(), out, n, k0 != 0);
         }
-        pool_free(c3);
-        pool_free(r2);
+        HIPCHECK(hipGetLastError());
     }
     // Evaluator::bfv_multiply (BEHZ), size 2 x 2 -> 3, coefficient form
     void bfv_multiply(int L, u64 n, const u64 *a, const u64 *b, Indexer ix, u64 *out) { bfv_multiply3(L, n, a, b, to_ix3(ix), out); }
@@ -1701,8 +1705,7 @@ public:
             throw std::invalid_argument("he355_bfv_multiply_plain: `out` overlaps an operand");
         if (!try_reserve(&arena_[kBfv], 1, b_n * LN * 8)) throw OutOfDeviceMemory("HIP error: out of device memory: the prepared plaintexts of he355_bfv_multiply_plain do not fit");
         u64 *prep = arena_[kBfv].p;
-        launch_bfv_lift_plain(env_, L, b_n, plain + b_lo * N, prep, P.plain_modulus);
-        launch_ntt_forward(env_, poly_view(prep, L, N, L), (u32)b_n);
+        plain_to_ntt(L, b_n, plain + b_lo * N, prep);
         for_each_chunk(n, L, chunk_ops(n, L, true), true, [&](u64 off, u64 nc, int which, const Scratch &, hipEvent_t fork) {
             const KernelEnv env = batch_env(which);
             launch_bfv_mp_cols_fwd(env, L, size, nc, off, ct, ix, out);
@@ -1741,8 +1744,7 @@ public:
         if (ranges_overlap(out, (size_t)n * L * N, plain, (size_t)n * N)) throw std::invalid_argument("he355_bfv_plain_to_ntt: `out` overlaps the plaintexts");
         if (n > 0xffffffffull) throw std::invalid_argument("he355_bfv_plain_to_ntt: too many plaintexts for one call");
         if (!n) return;
-        launch_bfv_lift_plain(env_, L, n, plain, out, P.plain_modulus);
-        launch_ntt_forward(env_, poly_view(out, L, N, L), (u32)n);
+        plain_to_ntt(L, n, plain, out);
         HIPCHECK(hipGetLastError());
     }
     // Evaluator::multiply_plain on NTT-form operands (multiply_plain_ntt): every polynomial times the NTT-form plaintext, k_plain_op's product
@@ -1781,30 +1783,11 @@ public:
         HIPCHECK(hipGetLastError());
     }
     // ---- monomial multiply and oblivious query expansion (he355_kernels_bfv_expand.hip) -------------------------------------------
-    // The argument checks that need no device: the C ABI makes them before it asks for one.
-    static void check_monomial_args(const Params &p, int L, int size, u32 e)
-    {
-        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_multiply_monomial: level out of range");
-        check_size(size, 1, 3);
-        if (e >= 2 * p.N) throw std::invalid_argument("he355_bfv_multiply_monomial: the exponent must be below 2N (X^N = -1)");
-    }
-    static void check_expand_args(const Params &p, int L, u64 count)
-    {
-        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_expand: level out of range");
-        if (count < 1 || count > p.N) throw std::invalid_argument("he355_bfv_expand: count must be in 1..N");
-    }
-    // levels of the expansion tree of `count` children, ceil(log2 count); level j uses the Galois element N / 2^j + 1
-    static int expand_depth(u64 count)
-    {
-        int d = 0;
-        while (((u64)1 << d) < count) ++d;
-        return d;
-    }
+    // The argument checks that need no device are bfv_pir_args.h's: the C ABI makes them before it asks for one and passes on their plan.
     // out = in X^e for every polynomial of [n][size][L][N], coefficient form: one launch
     void bfv_multiply_monomial(int L, int size, u64 n, const u64 *in, u32 e, u64 *out)
     {
         use();
-        check_monomial_args(P, L, size, e);
         const size_t words = (size_t)n * size * L * P.N;
         if (ranges_overlap(in, words, out, words)) throw std::invalid_argument("he355_bfv_multiply_monomial: `out` overlaps `in`");
         launch_bfv_shift(env_, L, n * size * L, in, nullptr, e, out);
@@ -1817,11 +1800,10 @@ public:
     // launch writes the odd children X^(-s) (2c - even) behind them, at (k + s) n + r -- the last level only those below `count`.  The
     // levels alternate between `out` and one pool block of 2^(d-1) n ciphertexts (what level d - 2 writes), the parity chosen so that
     // level d - 1 lands in `out`; everything runs on the context's stream.  Every refusal comes before the first launch.
-    void bfv_expand(int L, u64 n, const u64 *in, u64 count, u64 *out)
+    void bfv_expand(const BfvExpandPlan &pl, int L, u64 n, const u64 *in, u64 count, u64 *out)
     {
         use();
-        check_expand_args(P, L, count);
-        const int d = expand_depth(count);
+        const int d = pl.depth;
         const size_t N = P.N, ctn = 2 * (size_t)L * N;
         if (d) require_keyswitch();
         for (int j = 0; j < d; ++j) {
@@ -1834,151 +1816,59 @@ public:
             HIPCHECK(hipMemcpyAsync(out, in, n * ctn * 8, hipMemcpyDeviceToDevice, stream_));
             return;
         }
-        u64 *tmp = d > 1 ? static_cast<u64 *>(pool_alloc(((size_t)n << (d - 1)) * ctn * 8)) : nullptr;
-        try {
-            const u64 *cur = in;
-            for (int j = 0; j < d; ++j) {
-                const u64 s = (u64)1 << j, odd = std::min<u64>(s, count - s); // (count - s < s at the last level only)
-                u64 *dst = (d - 1 - j) % 2 == 0 ? out : tmp;
-                apply_galois(L, s * n, cur, (uint32_t)(N >> j) + 1, dst, cur);
-                launch_bfv_shift(env_, L, odd * n * 2 * L, cur, dst, (u32)(2 * N - s), dst + s * n * ctn);
-                cur = dst;
-            }
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            if (tmp) pool_free(tmp);
-            throw;
+        const PoolBlock tmp = d > 1 ? scoped_block(((size_t)n << (d - 1)) * ctn * 8) : PoolBlock();
+        const u64 *cur = in;
+        for (int j = 0; j < d; ++j) {
+            const u64 s = (u64)1 << j, odd = std::min<u64>(s, count - s); // (count - s < s at the last level only)
+            u64 *dst = (d - 1 - j) % 2 == 0 ? out : tmp.get();
+            apply_galois(L, s * n, cur, (uint32_t)(N >> j) + 1, dst, cur);
+            launch_bfv_shift(env_, L, odd * n * 2 * L, cur, dst, (u32)(2 * N - s), dst + s * n * ctn);
+            cur = dst;
         }
-        if (tmp) pool_free(tmp);
+        HIPCHECK(hipGetLastError());
     }
     // ---- ciphertext decomposition for recursive (two-dimensional) PIR (he355_kernels_bfv_digits.hip) ---------------------------------
-    // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the digit table of level L.
-    // `ct` [n][size][L][N], `plain` [n][F][N] (L_out == 0) or [n][F][L_out][N]: the two may not overlap, whichever is written.
-    static BfvDigitTab check_digit_args(const Params &p, const char *what, int L, int size, u64 n, const u64 *ct, const u64 *plain, int L_out = 0)
-    {
-        const std::string w(what);
-        if (L < 1 || (size_t)L > p.Ltop || L_out < 0 || (size_t)L_out > p.Ltop) throw std::invalid_argument(w + ": level out of range");
-        check_size(size, 1, 3);
-        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
-        u64 q[kMaxPrimes];
-        for (int i = 0; i < L; ++i) q[i] = p.primes[i].q;
-        const BfvDigitTab tab = bfv_digit_table(q, L, p.plain_modulus);
-        const u64 F = (u64)size * tab.total;
-        if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many plaintexts for one call (n F must be below 2^32)");
-        if (ranges_overlap(ct, (size_t)n * size * L * p.N, plain, (size_t)n * F * (L_out ? L_out : 1) * p.N))
-            throw std::invalid_argument(w + ": the plaintexts overlap the ciphertexts");
-        return tab;
-    }
     // [n][size][L][N] -> [n][F][N] coefficients mod t: one streaming launch
-    void bfv_decompose(int L, int size, u64 n, const u64 *ct, u64 *plain)
+    void bfv_decompose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *plain)
     {
         use();
-        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_decompose", L, size, n, ct, plain);
-        launch_bfv_digits(env_, tab, L, size, n, ct, plain);
+        launch_bfv_digits(env_, pl.tab, L, size, n, ct, plain);
         HIPCHECK(hipGetLastError());
     }
     // the inverse: [n][F][N] -> [n][size][L][N], canonical whatever the digits are
-    void bfv_compose(int L, int size, u64 n, const u64 *plain, u64 *ct)
+    void bfv_compose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *plain, u64 *ct)
     {
         use();
-        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_compose", L, size, n, ct, plain);
-        launch_bfv_undigits(env_, tab, L, size, n, plain, ct);
+        launch_bfv_undigits(env_, pl.tab, L, size, n, plain, ct);
         HIPCHECK(hipGetLastError());
     }
     // [n][size][L][N] -> [n][F][L_out][N], by definition bfv_decompose + bfv_plain_to_ntt(L_out, n F).  N >= 2048: the fused column pass
     // reads the ciphertext, cuts, lifts and writes out(f, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is
     // routed to the composition, its [n][F][N] slab a pool block (a second identical call allocates nothing).
-    void bfv_decompose_ntt(int L, int size, u64 n, const u64 *ct, int L_out, u64 *out)
+    void bfv_decompose_ntt(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, int L_out, u64 *out)
     {
         use();
-        if (L_out < 1) throw std::invalid_argument("he355_bfv_decompose_ntt: level out of range");
-        const BfvDigitTab tab = check_digit_args(P, "he355_bfv_decompose_ntt", L, size, n, ct, out, L_out);
-        const size_t N = P.N, F = (size_t)size * tab.total;
+        const size_t N = P.N, F = pl.F;
         if (!n) return;
         if (env_.logn1 == 0) {
             ++routes_.digits_routed;
-            u64 *tmp = static_cast<u64 *>(pool_alloc((size_t)n * F * N * 8));
-            try {
-                launch_bfv_digits(env_, tab, L, size, n, ct, tmp);
-                launch_bfv_lift_plain(env_, L_out, n * F, tmp, out, P.plain_modulus);
-                launch_ntt_forward(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
-                HIPCHECK(hipGetLastError());
-            } catch (...) {
-                pool_free(tmp);
-                throw;
-            }
-            pool_free(tmp);
+            const PoolBlock tmp = scoped_block((size_t)n * F * N * 8);
+            launch_bfv_digits(env_, pl.tab, L, size, n, ct, tmp.get());
+            plain_to_ntt(L_out, n * F, tmp.get(), out);
+            HIPCHECK(hipGetLastError());
             return;
         }
         ++routes_.digits_fused;
-        launch_bfv_digits_cols_fwd(env_, tab, L, size, n, ct, L_out, P.plain_modulus, out);
+        launch_bfv_digits_cols_fwd(env_, pl.tab, L, size, n, ct, L_out, P.plain_modulus, out);
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
         HIPCHECK(hipGetLastError());
     }
     // ---- the external product RGSW x ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) ----------
-    // The argument checks that need no device: the C ABI makes them before it asks for one.  Each returns the gadget table of level L.
-    static constexpr u64 kGadgetPassPolys = 4096; // digit polynomials one pass of he355_bfv_external_product holds in its pool block
-    static u64 gadget_poly_blocks(const Params &p, bool cols) { return cols && p.N > 1024 ? 4 : p.N / 512; } // blocks per residue polynomial
-    static BfvDigitTab gadget_table(const Params &p, const std::string &w, int L, int v)
-    {
-        if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
-        if (!bfv_gadget_width_ok(v)) throw std::invalid_argument(w + ": digit_bits must be 1..63");
-        u64 q[kMaxPrimes];
-        for (int i = 0; i < L; ++i) q[i] = p.primes[i].q;
-        return bfv_gadget_table(q, L, v);
-    }
-    // `ct` [n][size][L][N] -> `digits` [n][size E][N] (ntt false) or [n][size E][L][N]
-    static BfvDigitTab check_gadget_cut_args(const Params &p, const char *what, int L, int v, int size, u64 n, const u64 *ct, const u64 *digits, bool ntt)
-    {
-        const std::string w(what);
-        const BfvDigitTab tab = gadget_table(p, w, L, v);
-        check_size(size, 1, 3);
-        const u64 F = (u64)size * tab.total;
-        if (n > 0xffffffffull / F) throw std::invalid_argument(w + ": too many digit polynomials for one call (n size E must be below 2^32)");
-        if (n * size * L > 0x7fffffffull / gadget_poly_blocks(p, ntt)) throw std::invalid_argument(w + ": too many polynomials for one launch");
-        if (ranges_overlap(ct, (size_t)n * size * L * p.N, digits, (size_t)n * F * (ntt ? L : 1) * p.N)) throw std::invalid_argument(w + ": the digits overlap the ciphertexts");
-        return tab;
-    }
-    static BfvDigitTab check_rgsw_args(const Params &p, int L, int v, u64 n, const u64 *plain, const u64 *out)
-    {
-        const std::string w("he355_bfv_rgsw_encrypt");
-        const BfvDigitTab tab = gadget_table(p, w, L, v);
-        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
-        const u64 per = 2 * (u64)tab.total * 2 * L; // residue polynomials of one RGSW ciphertext
-        if (n > 0x7fffffffull / (per * (p.N / 512))) throw std::invalid_argument(w + ": too many RGSW ciphertexts for one launch");
-        if (ranges_overlap(plain, (size_t)n * p.N, out, (size_t)n * per * p.N)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the plaintexts");
-        return tab;
-    }
-    // the words from the first operand of a batch to the end of the last one it touches, ((n - 1) stride_r + (inner - 1) stride_k + 1) items of
-    // `item_words` each, formed in 128 bits and refused where they cannot lie in one address space
-    static size_t gadget_span_words(const std::string &w, u64 n, u64 inner, u64 stride_r, u64 stride_k, u64 item_words)
-    {
-        const u128 items = (u128)(n - 1) * stride_r + (u128)(inner - 1) * stride_k + 1;
-        if (items > ((u128)1 << 60) || items * item_words > ((u128)1 << 60)) throw std::invalid_argument(w + ": a stride takes the operands past 2^60 words");
-        return (size_t)(items * item_words);
-    }
-    static BfvDigitTab check_external_product_args(const Params &p, int L, int v, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw,
-                                                   u64 rg_stride_r, u64 rg_stride_k, const u64 *out)
-    {
-        const std::string w("he355_bfv_external_product");
-        const BfvDigitTab tab = gadget_table(p, w, L, v);
-        const u64 rows = 2 * (u64)tab.total;
-        if (inner < 1 || inner > 0x7fffffffull / rows) throw std::invalid_argument(w + ": inner must be at least 1 and inner 2 E(L) below 2^31");
-        if (!n) return tab;
-        const u64 terms = inner * rows, pass = bfv_gadget_pass(terms, n, kGadgetPassPolys);
-        if (n > 0x7fffffffull || pass * inner * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, true) || pass * L > 0x7fffffffull / (p.N / 512))
-            throw std::invalid_argument(w + ": too many polynomials for one launch");
-        const size_t ctn = 2 * (size_t)L * p.N;
-        if (ranges_overlap(out, n * ctn, ct, gadget_span_words(w, n, inner, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the ciphertexts");
-        if (ranges_overlap(out, n * ctn, rgsw, gadget_span_words(w, n, inner, rg_stride_r, rg_stride_k, rows * ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the RGSW ciphertexts");
-        return tab;
-    }
     // [n][size][L][N] -> [n][size E][N], the plain integer digits of width v: he355_bfv_decompose's launch with the width-v table
-    void bfv_gadget_decompose(int L, int v, int size, u64 n, const u64 *ct, u64 *digits)
+    void bfv_gadget_decompose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *digits)
     {
         use();
-        const BfvDigitTab tab = check_gadget_cut_args(P, "he355_bfv_gadget_decompose", L, v, size, n, ct, digits, false);
-        launch_bfv_digits(env_, tab, L, size, n, ct, digits);
+        launch_bfv_digits(env_, pl.tab, L, size, n, ct, digits);
         HIPCHECK(hipGetLastError());
     }
     // the cut of ciphertext (a, b) at index a stride_a + b stride_b into NTT-form digit polynomials [(a n_b + b) size E + f][L][N]: N >= 2048 the
@@ -1993,164 +1883,95 @@ public:
         const bool cols = env_.logn1 != 0 && n_a * n_b * size * L * 4 >= kGadgetColsMinBlocks;
         ++(cols ? routes_.cut_cols : routes_.cut_stream);
         launch_bfv_gadget_cut(env_, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out, cols);
-        if (cols) launch_rows_fwd(env_, poly_view(out, L, P.N, L), items);
-        else launch_ntt_forward(env_, poly_view(out, L, P.N, L), items);
+        forward_rows_or_full(cols, poly_view(out, L, P.N, L), items);
     }
     // [n][size][L][N] -> [n][size E][L][N]: by definition bfv_gadget_decompose, then he355_ntt_forward of every digit polynomial under every prime
-    void bfv_gadget_decompose_ntt(int L, int v, int size, u64 n, const u64 *ct, u64 *out)
+    void bfv_gadget_decompose_ntt(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *out)
     {
         use();
-        const BfvDigitTab tab = check_gadget_cut_args(P, "he355_bfv_gadget_decompose_ntt", L, v, size, n, ct, out, true);
         if (!n) return;
-        gadget_cut_ntt(tab, L, size, n, 1, ct, 1, 0, out);
+        gadget_cut_ntt(pl.tab, L, size, n, 1, ct, 1, 0, out);
         HIPCHECK(hipGetLastError());
     }
+    // `rows` encryptions of zero, he355_encrypt_zero(seed, first_index + row), for a plant kernel that cuts them to the first L primes: made
+    // in `out` itself at L == L_top (the kernel then works in place, the block returned is empty), below it in the pool block returned
+    PoolBlock zeros_at_level(int L, u64 rows, u64 seed, u64 first_index, u64 *out)
+    {
+        PoolBlock hold = (size_t)L < P.Ltop ? scoped_block((size_t)rows * 2 * P.Ltop * P.N * 8) : PoolBlock();
+        encrypt(rows, nullptr, seed, first_index, hold ? hold.get() : out);
+        return hold;
+    }
     // plain [n][N] mod t -> out [n][2E][2][L][N] NTT form: row f of RGSW r is he355_encrypt_zero(seed, first_index + r 2E + f) cut to the first L
-    // primes, plus the planted term.  L == L_top: the zeros are made where the rows lie; below, in one pool block.
-    void bfv_rgsw_encrypt(int L, int v, u64 n, const u64 *plain, u64 seed, u64 first_index, u64 *out)
+    // primes, plus the planted term.
+    void bfv_rgsw_encrypt(const BfvRgswPlan &pl, int L, u64 n, const u64 *plain, u64 seed, u64 first_index, u64 *out)
     {
         use();
-        const BfvDigitTab tab = check_rgsw_args(P, L, v, n, plain, out);
         if (!n) return;
         if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt: public key not set");
-        const size_t N = P.N, Lt = P.Ltop;
-        const u64 rows = n * 2 * tab.total;
-        u64 *tmp = (size_t)L < Lt ? static_cast<u64 *>(pool_alloc((size_t)rows * 2 * Lt * N * 8)) : nullptr;
-        try {
-            u64 *zero = tmp ? tmp : out;
-            encrypt(rows, nullptr, seed, first_index, zero);
-            launch_bfv_rgsw_plant(env_, tab, L, (int)Lt, n, zero, plain, P.plain_modulus, out);
-            launch_ntt_forward(env_, poly_view(out, L, N, L), (u32)(rows * 2));
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            if (tmp) pool_free(tmp);
-            throw;
-        }
-        if (tmp) pool_free(tmp);
+        const PoolBlock hold = zeros_at_level(L, pl.rows, seed, first_index, out);
+        const u64 *zero = hold ? hold.get() : out;
+        launch_bfv_rgsw_plant(env_, pl.tab, L, (int)P.Ltop, n, zero, plain, P.plain_modulus, out);
+        launch_ntt_forward(env_, poly_view(out, L, P.N, L), (u32)(pl.rows * 2));
+        HIPCHECK(hipGetLastError());
     }
     // out(r) = sum_kappa rgsw(r, kappa) [.] ct(r, kappa), coefficient form in and out.  By definition bfv_gadget_decompose_ntt of the inner
     // ciphertexts of each result, he355_bfv_multiply_plain_accumulate(L, 2, 1, 1, inner 2E) with the RGSW rows as the ciphertext operand, and
     // he355_bfv_transform_from_ntt.  The digit slab of a pass of results (bfv_gadget_pass: about kGadgetPassPolys digit polynomials, at least
     // one result) is one pool block; a pass is the cut, its row pass and one batched multiply-accumulate; one inverse transform ends the call.
-    void bfv_external_product(int L, int v, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_k, u64 *out)
+    void bfv_external_product(const BfvExternalPlan &pl, int L, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r,
+                              u64 rg_stride_k, u64 *out)
     {
         use();
-        const BfvDigitTab tab = check_external_product_args(P, L, v, n, inner, ct, ct_stride_r, ct_stride_k, rgsw, rg_stride_r, rg_stride_k, out);
         if (!n) return;
         const size_t N = P.N, LN = (size_t)L * N;
-        const u32 rows = 2 * tab.total;
-        const u64 terms = inner * rows, pass = bfv_gadget_pass(terms, n, kGadgetPassPolys);
-        u64 *slab = static_cast<u64 *>(pool_alloc((size_t)pass * terms * LN * 8));
-        try {
-            for (u64 r0 = 0; r0 < n; r0 += pass) {
-                const u64 c = std::min<u64>(pass, n - r0);
-                gadget_cut_ntt(tab, L, 2, c, inner, ct + r0 * ct_stride_r * 2 * LN, ct_stride_r, ct_stride_k, slab);
-                const u64 *rg = rgsw + r0 * rg_stride_r * rows * 2 * LN;
-                // ROUTED: a call for ONE result whose RGSW rows follow one another is the composition's own inner product, and
-                // k_bfv_plain_mac's 1 x 1 form (two terms' loads in flight) measured 2-17 % ahead of k_bfv_gadget_mac there
-                // (profiles/bfv_external_product.txt).  Only n == 1 was measured, so only n == 1 is routed: a pass that holds one result
-                // of many (inner 2E above 2048, or a ragged last pass) stays with k_bfv_gadget_mac.
-                const bool plain = n == 1 && (inner == 1 || rg_stride_k == 1);
-                ++routes_.passes;
-                ++(plain ? routes_.mac_plain : routes_.mac_gadget);
-                if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab, 1, 1, out + r0 * 2 * LN);
-                else launch_bfv_gadget_mac(env_, L, c, inner, rows, slab, rg, rg_stride_r, rg_stride_k, out + r0 * 2 * LN);
-            }
-            launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            pool_free(slab);
-            throw;
+        const u32 rows = pl.rows;
+        const u64 terms = pl.terms, pass = pl.pass;
+        const PoolBlock slab = scoped_block((size_t)pass * terms * LN * 8);
+        for (u64 r0 = 0; r0 < n; r0 += pass) {
+            const u64 c = std::min<u64>(pass, n - r0);
+            gadget_cut_ntt(pl.tab, L, 2, c, inner, ct + r0 * ct_stride_r * 2 * LN, ct_stride_r, ct_stride_k, slab.get());
+            const u64 *rg = rgsw + r0 * rg_stride_r * rows * 2 * LN;
+            // ROUTED: a call for ONE result whose RGSW rows follow one another is the composition's own inner product, and
+            // k_bfv_plain_mac's 1 x 1 form (two terms' loads in flight) measured 2-17 % ahead of k_bfv_gadget_mac there
+            // (profiles/bfv_external_product.txt).  Only n == 1 was measured, so only n == 1 is routed: a pass that holds one result
+            // of many (inner 2E above 2048, or a ragged last pass) stays with k_bfv_gadget_mac.
+            const bool plain = n == 1 && (inner == 1 || rg_stride_k == 1);
+            ++routes_.passes;
+            ++(plain ? routes_.mac_plain : routes_.mac_gadget);
+            if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab.get(), 1, 1, out + r0 * 2 * LN);
+            else launch_bfv_gadget_mac(env_, L, c, inner, rows, slab.get(), rg, rg_stride_r, rg_stride_k, out + r0 * 2 * LN);
         }
-        pool_free(slab);
+        launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
+        HIPCHECK(hipGetLastError());
     }
     // ---- RGSW selectors from ONE packed query ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) -------
-    // The argument checks that need no device: the C ABI makes them before it asks for one.
-    // `sel` [n][n_sel] mod t -> `out` [n][2][L][N]; returns the gadget table of level L
-    static BfvDigitTab check_selector_args(const Params &p, int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, const u64 *out)
-    {
-        const std::string w("he355_bfv_selector_encrypt");
-        const BfvDigitTab tab = gadget_table(p, w, L, v);
-        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
-        if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
-        if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
-        if ((u128)first_slot + (u128)n_sel * tab.total > count) throw std::invalid_argument(w + ": first_slot + n_sel E(L) must not exceed count");
-        if (n > 0x7fffffffull / (2 * (u64)L * (p.N / 512))) throw std::invalid_argument(w + ": too many ciphertexts for one launch");
-        if (ranges_overlap(sel, (size_t)(n * n_sel), out, (size_t)n * 2 * L * p.N)) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
-        return tab;
-    }
-    static BfvDigitTab check_rgsw_secret_args(const Params &p, int L, int kv)
-    {
-        const std::string w("he355_bfv_rgsw_encrypt_secret");
-        if (L >= 1 && (size_t)L <= p.Ltop && !bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
-        const BfvDigitTab tab = gadget_table(p, w, L, kv);
-        if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
-        if (2 * (u64)tab.total * 2 * L > 0x7fffffffull / (p.N / 512)) throw std::invalid_argument(w + ": too many polynomials for one launch");
-        return tab;
-    }
-    // slot ciphertexts at r ct_stride_r + (b E + f) ct_stride_k of `ct`, `key` [2 E_key][2][L][N] -> `out` [n][n_sel][2E][2][L][N]; *ktab: the key's table
-    static BfvDigitTab check_from_bfv_args(const Params &p, int L, int v, int kv, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key,
-                                           const u64 *out, BfvDigitTab *ktab = nullptr)
-    {
-        const std::string w("he355_bfv_rgsw_from_bfv");
-        const BfvDigitTab tab = gadget_table(p, w, L, v);
-        if (!bfv_gadget_width_ok(kv)) throw std::invalid_argument(w + ": key_bits must be 1..63");
-        const BfvDigitTab kt = gadget_table(p, w, L, kv);
-        if (ktab) *ktab = kt;
-        if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
-        if (!n) return tab;
-        const u128 slots = (u128)n * n_sel * tab.total; // slot ciphertexts
-        if (n > 0x7fffffffull || n_sel > 0x7fffffffull || slots > 0x7fffffffull / (2 * (u64)L * 4)) throw std::invalid_argument(w + ": too many polynomials for one launch");
-        const u64 C = (u64)slots, rows = 2 * (u64)kt.total, pass = bfv_gadget_pass(rows, C, kGadgetPassPolys);
-        if (pass * 2 * L > 0x7fffffffull / gadget_poly_blocks(p, false) || pass * rows * L > 0x3fffffffull)
-            throw std::invalid_argument(w + ": too many polynomials for one launch");
-        const size_t ctn = 2 * (size_t)L * p.N, outn = (size_t)C * 2 * ctn;
-        if (ranges_overlap(out, outn, ct, gadget_span_words(w, n, n_sel * tab.total, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_rgsw` overlaps the ciphertexts");
-        if (ranges_overlap(out, outn, key, (size_t)rows * ctn)) throw std::invalid_argument(w + ": `d_rgsw` overlaps the key");
-        return tab;
-    }
     // sel [n][n_sel] mod t -> out [n][2][L][N], coefficient form: he355_encrypt_zero(seed, first_index + r) cut to the first L primes plus the planted
-    // selectors.  L == L_top: the zeros are made where the ciphertexts lie; below, in one pool block.
-    void bfv_selector_encrypt(int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, u64 seed, u64 first_index, u64 *out)
+    // selectors.
+    void bfv_selector_encrypt(const BfvSelectorPlan &pl, int L, u64 n, u64 n_sel, u64 first_slot, const u64 *sel, u64 seed, u64 first_index, u64 *out)
     {
         use();
-        const BfvDigitTab tab = check_selector_args(P, L, v, n, n_sel, first_slot, count, sel, out);
         if (!n) return;
         if (!d_pk_) throw std::invalid_argument("he355_bfv_selector_encrypt: public key not set");
-        const size_t N = P.N, Lt = P.Ltop;
-        u64 *tmp = (size_t)L < Lt ? static_cast<u64 *>(pool_alloc((size_t)n * 2 * Lt * N * 8)) : nullptr;
-        try {
-            u64 *zero = tmp ? tmp : out;
-            encrypt(n, nullptr, seed, first_index, zero);
-            launch_bfv_selector_plant(env_, tab, L, (int)Lt, n, n_sel, first_slot, expand_depth(count), zero, sel, P.plain_modulus, out);
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            if (tmp) pool_free(tmp);
-            throw;
-        }
-        if (tmp) pool_free(tmp);
+        const PoolBlock hold = zeros_at_level(L, n, seed, first_index, out);
+        const u64 *zero = hold ? hold.get() : out;
+        launch_bfv_selector_plant(env_, pl.tab, L, (int)P.Ltop, n, n_sel, first_slot, pl.depth, zero, sel, P.plain_modulus, out);
+        HIPCHECK(hipGetLastError());
     }
     // RGSW(s) at (L, key_bits): by definition bfv_rgsw_encrypt of the secret key's coefficients mod t (0, 1, t - 1).  The context holds s in NTT
-    // form: prime 0's residue goes through the inverse transform in one pool block of N words and is mapped there.
+    // form: prime 0's residue goes through the inverse transform in one pool block of N words and is mapped there; the block is held across
+    // the inner call, whose plan (n = 1) is made here, once the plaintext has its address.
     void bfv_rgsw_encrypt_secret(int L, int kv, u64 seed, u64 first_index, u64 *out)
     {
         use();
-        check_rgsw_secret_args(P, L, kv);
         if (!d_sk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: secret key not set");
         if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: public key not set");
         const size_t N = P.N;
-        u64 *s = static_cast<u64 *>(pool_alloc(N * 8));
-        try {
-            HIPCHECK(hipMemcpyAsync(s, d_sk_, N * 8, hipMemcpyDeviceToDevice, stream_));
-            launch_ntt_inverse(env_, poly_view(s, 1, N, 1), 1);
-            launch_bfv_secret_plain(env_, s, P.plain_modulus);
-            HIPCHECK(hipGetLastError());
-            bfv_rgsw_encrypt(L, kv, 1, s, seed, first_index, out);
-        } catch (...) {
-            pool_free(s);
-            throw;
-        }
-        pool_free(s);
+        const PoolBlock s = scoped_block(N * 8);
+        HIPCHECK(hipMemcpyAsync(s.get(), d_sk_, N * 8, hipMemcpyDeviceToDevice, stream_));
+        launch_ntt_inverse(env_, poly_view(s.get(), 1, N, 1), 1);
+        launch_bfv_secret_plain(env_, s.get(), P.plain_modulus);
+        HIPCHECK(hipGetLastError());
+        bfv_rgsw_encrypt(plan_rgsw(P, L, kv, 1, s.get(), out), L, 1, s.get(), seed, first_index, out);
     }
     // out [n][n_sel][2E][2][L][N], NTT form.  Slot ciphertext c = (r n_sel + b) E + f (coefficient form, read where it lies): row f of RGSW (r, b) is its
     // forward transform, row E + f the NTT-form sums of its key_bits digits against RGSW(s) -- what he355_bfv_external_product leaves before its
@@ -2158,118 +1979,69 @@ public:
     // terms, one pool block as in bfv_external_product) is the cut, which also emits the slot's own column (gadget_cut_ntt's route, decided once per
     // call from the first pass: every pass must leave the k = 0 rows in the same state), the digits' row pass and one multiply-accumulate into the
     // k = 1 rows.  One row pass over the k = 0 rows, in place, ends the call.
-    void bfv_rgsw_from_bfv(int L, int v, int kv, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key, u64 *out)
+    void bfv_rgsw_from_bfv(const BfvFromBfvPlan &pl, int L, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key, u64 *out)
     {
         use();
-        BfvDigitTab ktab;
-        const BfvDigitTab tab = check_from_bfv_args(P, L, v, kv, n, n_sel, ct, ct_stride_r, ct_stride_k, key, out, &ktab);
         if (!n) return;
         const size_t N = P.N, LN = (size_t)L * N;
-        const u32 E = tab.total, rows = 2 * ktab.total;
-        const u64 C = n * n_sel * E, pass = bfv_gadget_pass(rows, C, kGadgetPassPolys);
+        const u32 E = pl.tab.total, rows = pl.rows;
+        const u64 C = pl.C, pass = pl.pass;
         const bool cols = env_.logn1 != 0 && std::min<u64>(pass, C) * 2 * L * 4 >= kGadgetColsMinBlocks;
-        u64 *slab = static_cast<u64 *>(pool_alloc((size_t)pass * rows * LN * 8));
-        try {
-            for (u64 c0 = 0; c0 < C; c0 += pass) {
-                const u64 c = std::min<u64>(pass, C - c0);
-                ++routes_.passes;
-                ++(cols ? routes_.own_cols : routes_.own_stream);
-                launch_bfv_gadget_cut_own(env_, ktab, L, n_sel * E, c0, c, ct, ct_stride_r, ct_stride_k, slab, out, E, cols);
-                if (cols) launch_rows_fwd(env_, poly_view(slab, L, N, L), (u32)(c * rows));
-                else launch_ntt_forward(env_, poly_view(slab, L, N, L), (u32)(c * rows));
-                launch_bfv_gadget_mac_own(env_, L, c0, c, rows, slab, key, out, E);
-            }
-            // the k = 0 rows: rows f0 .. f0 + R - 1 of every RGSW ciphertext are one item of R 2L polynomials, the items 2E 2L polynomials apart
-            const u32 R = std::max<u32>(1, 64 / (2 * (u32)L));
-            for (u32 f0 = 0; f0 < E; f0 += R) {
-                PolyView pv = poly_view(out + (size_t)f0 * 2 * LN, (int)(std::min<u32>(R, E - f0) * 2 * L), N, L);
-                pv.item_stride = (u64)2 * E * 2 * LN;
-                if (cols) launch_rows_fwd(env_, pv, (u32)(n * n_sel));
-                else launch_ntt_forward(env_, pv, (u32)(n * n_sel));
-            }
-            HIPCHECK(hipGetLastError());
-        } catch (...) {
-            pool_free(slab);
-            throw;
+        const PoolBlock slab = scoped_block((size_t)pass * rows * LN * 8);
+        for (u64 c0 = 0; c0 < C; c0 += pass) {
+            const u64 c = std::min<u64>(pass, C - c0);
+            ++routes_.passes;
+            ++(cols ? routes_.own_cols : routes_.own_stream);
+            launch_bfv_gadget_cut_own(env_, pl.ktab, L, n_sel * E, c0, c, ct, ct_stride_r, ct_stride_k, slab.get(), out, E, cols);
+            forward_rows_or_full(cols, poly_view(slab.get(), L, N, L), (u32)(c * rows));
+            launch_bfv_gadget_mac_own(env_, L, c0, c, rows, slab.get(), key, out, E);
         }
-        pool_free(slab);
+        // the k = 0 rows: rows f0 .. f0 + R - 1 of every RGSW ciphertext are one item of R 2L polynomials, the items 2E 2L polynomials apart
+        const u32 R = std::max<u32>(1, 64 / (2 * (u32)L));
+        for (u32 f0 = 0; f0 < E; f0 += R) {
+            PolyView pv = poly_view(out + (size_t)f0 * 2 * LN, (int)(std::min<u32>(R, E - f0) * 2 * L), N, L);
+            pv.item_stride = (u64)2 * E * 2 * LN;
+            forward_rows_or_full(cols, pv, (u32)(n * n_sel));
+        }
+        HIPCHECK(hipGetLastError());
     }
     // ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; the definition: bfv_bytes_core.h, include/he355.h) ----------------
-    // The argument checks that need no device: the C ABI makes them before it asks for one.  Returns the field width w.
-    // `bytes`: plaintext j at bytes + j stride, B bytes; `words`: [n][per] 64-bit words, per = N (coefficients) or L_out N.  pack: the
-    // bytes are the output, whole 8-byte words of it.
-    static constexpr u64 kBytesChunk = 4096; // N = 1024's routed path: plaintexts per pass through its pool block (32 MiB)
-    static int check_bytes_args(const Params &p, const char *what, u64 n, const void *bytes, u64 stride, u64 B, const u64 *words, int L_out, bool pack)
-    {
-        const std::string s(what);
-        if (L_out < 0 || (size_t)L_out > p.Ltop) throw std::invalid_argument(s + ": level out of range");
-        if (p.plain_modulus < 2) throw std::invalid_argument(s + ": the plain modulus must be at least 2");
-        const int w = bfv_bitlen(p.plain_modulus) - 1;
-        if (B < 1 || B > bfv_bytes_max(p.N, w)) throw std::invalid_argument(s + ": bytes_per_plain must be 1 .. floor(N w / 8) (he355_bfv_bytes_per_plain)");
-        if (stride < B) throw std::invalid_argument(s + ": stride_bytes must be at least bytes_per_plain");
-        const u64 tail = pack ? 8 * bfv_bytes_words(B) : B; // the bytes of the last plaintext the call touches
-        // (n - 1) stride + tail stays below 2^63: neither the range below nor a kernel's j * stride can wrap
-        if (n > 1 && n - 1 > (((u64)1 << 63) - tail) / stride) throw std::invalid_argument(s + ": (n - 1) stride_bytes must be below 2^63");
-        if (!pack && !L_out && ((unsigned long long)words & 15)) throw std::invalid_argument(s + ": d_plain must be 16-byte aligned");
-        if (pack && (((unsigned long long)bytes & 7) || (stride & 7) || stride < tail))
-            throw std::invalid_argument(s + ": d_bytes must be 8-byte aligned and stride_bytes a multiple of 8, at least 8 ceil(bytes_per_plain / 8)");
-        if (n > 0x7fffffffull / (p.N / 256)) throw std::invalid_argument(s + ": too many plaintexts for one launch (n N / 256 must be below 2^31)");
-        if (n) {
-            const unsigned long long b0 = (unsigned long long)bytes, b1 = b0 + (n - 1) * stride + tail;
-            const unsigned long long w0 = (unsigned long long)words, w1 = w0 + n * (L_out ? (u64)L_out : 1) * p.N * 8;
-            if (b1 < b0 || w1 < w0) throw std::invalid_argument(s + ": a range wraps the address space");
-            if (b0 < w1 && w0 < b1) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
-        }
-        return w;
-    }
     // bytes -> [n][N] coefficients mod t: one streaming launch
-    void bfv_unpack_bytes(u64 n, const void *bytes, u64 stride, u64 B, u64 *plain)
+    void bfv_unpack_bytes(const BfvBytesPlan &pl, u64 n, const void *bytes, u64 stride, u64 B, u64 *plain)
     {
         use();
-        const int w = check_bytes_args(P, "he355_bfv_unpack_bytes", n, bytes, stride, B, plain, 0, false);
-        launch_bfv_unpack(env_, w, n, bytes, stride, B, plain);
+        launch_bfv_unpack(env_, pl.w, n, bytes, stride, B, plain);
         HIPCHECK(hipGetLastError());
     }
     // the inverse: [n][N] words, each masked to w bits -> ceil(B / 8) whole words per plaintext
-    void bfv_pack_bytes(u64 n, const u64 *plain, u64 B, u64 stride, void *bytes)
+    void bfv_pack_bytes(const BfvBytesPlan &pl, u64 n, const u64 *plain, u64 B, u64 stride, void *bytes)
     {
         use();
-        const int w = check_bytes_args(P, "he355_bfv_pack_bytes", n, bytes, stride, B, plain, 0, true);
-        launch_bfv_pack(env_, w, n, plain, B, stride, bytes);
+        launch_bfv_pack(env_, pl.w, n, plain, B, stride, bytes);
         HIPCHECK(hipGetLastError());
     }
     // bytes -> [n][L_out][N], by definition bfv_unpack_bytes + bfv_plain_to_ntt(L_out, n).  N >= 2048: the fused column pass reads the bytes,
     // cuts, lifts and writes out(j, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is routed to the
     // composition, kBytesChunk plaintexts at a time through one pool block (a database is large; a second identical call allocates nothing).
-    void bfv_unpack_bytes_ntt(int L_out, u64 n, const void *bytes, u64 stride, u64 B, u64 *out)
+    void bfv_unpack_bytes_ntt(const BfvBytesPlan &pl, int L_out, u64 n, const void *bytes, u64 stride, u64 B, u64 *out)
     {
         use();
-        if (L_out < 1) throw std::invalid_argument("he355_bfv_unpack_bytes_ntt: level out of range");
-        const int w = check_bytes_args(P, "he355_bfv_unpack_bytes_ntt", n, bytes, stride, B, out, L_out, false);
         const size_t N = P.N;
         if (!n) return;
         if (env_.logn1 == 0) {
             const u64 chunk = n < kBytesChunk ? n : kBytesChunk;
-            u64 *tmp = static_cast<u64 *>(pool_alloc((size_t)chunk * N * 8));
-            try {
-                for (u64 j = 0; j < n; j += chunk) {
-                    const u64 c = n - j < chunk ? n - j : chunk;
-                    u64 *dst = out + (size_t)j * L_out * N;
-                    ++routes_.bytes_routed;
-                    launch_bfv_unpack(env_, w, c, static_cast<const unsigned char *>(bytes) + j * stride, stride, B, tmp);
-                    launch_bfv_lift_plain(env_, L_out, c, tmp, dst, P.plain_modulus);
-                    launch_ntt_forward(env_, poly_view(dst, L_out, N, L_out), (u32)c);
-                }
-                HIPCHECK(hipGetLastError());
-            } catch (...) {
-                pool_free(tmp);
-                throw;
+            const PoolBlock tmp = scoped_block((size_t)chunk * N * 8);
+            for (u64 j = 0; j < n; j += chunk) {
+                const u64 c = n - j < chunk ? n - j : chunk;
+                ++routes_.bytes_routed;
+                launch_bfv_unpack(env_, pl.w, c, static_cast<const unsigned char *>(bytes) + j * stride, stride, B, tmp.get());
+                plain_to_ntt(L_out, c, tmp.get(), out + (size_t)j * L_out * N);
             }
-            pool_free(tmp);
+            HIPCHECK(hipGetLastError());
             return;
         }
         ++routes_.bytes_fused;
-        launch_bfv_bytes_cols_fwd(env_, w, n, bytes, stride, B, L_out, P.plain_modulus, out);
+        launch_bfv_bytes_cols_fwd(env_, pl.w, n, bytes, stride, B, L_out, P.plain_modulus, out);
         launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)n);
         HIPCHECK(hipGetLastError());
     }
@@ -2943,14 +2715,14 @@ int he355_bfv_multiply_monomial(he355_ctx *c, int L, int size, uint64_t n, const
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_multiply_monomial");
-        DeviceContext::check_monomial_args(*c->params, L, size, exponent);
+        check_monomial_args(*c->params, L, size, exponent);
         dev(c).bfv_multiply_monomial(L, size, n, in, exponent, out);
     });
 }
 uint64_t he355_bfv_expand_galois_elts(const he355_ctx *c, uint64_t count, uint32_t *out, uint64_t cap)
 {
     if (!c || c->params->scheme != kSchemeBFV || count < 1 || count > c->params->N) return 0;
-    const int d = DeviceContext::expand_depth(count);
+    const int d = expand_depth(count);
     for (int j = 0; j < d && (uint64_t)j < cap; ++j) out[j] = (uint32_t)(c->params->N >> j) + 1;
     return (uint64_t)d;
 }
@@ -2958,16 +2730,14 @@ int he355_bfv_expand(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint64
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_expand");
-        DeviceContext::check_expand_args(*c->params, L, count);
-        dev(c).bfv_expand(L, n, in, count, out);
+        const BfvExpandPlan pl = plan_expand(*c->params, L, count);
+        dev(c).bfv_expand(pl, L, n, in, count, out);
     });
 }
 uint64_t he355_bfv_digit_count(const he355_ctx *c, int L, uint32_t *per_prime, uint64_t cap)
 {
     if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || c->params->plain_modulus < 2) return 0;
-    u64 q[kMaxPrimes];
-    for (int i = 0; i < L; ++i) q[i] = c->params->primes[i].q;
-    const BfvDigitTab tab = bfv_digit_table(q, L, c->params->plain_modulus);
+    const BfvDigitTab tab = digit_table(*c->params, L);
     for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
     return tab.total;
 }
@@ -2975,33 +2745,30 @@ int he355_bfv_decompose(he355_ctx *c, int L, int size, uint64_t n, const uint64_
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_decompose");
-        DeviceContext::check_digit_args(*c->params, "he355_bfv_decompose", L, size, n, ct, plain);
-        dev(c).bfv_decompose(L, size, n, ct, plain);
+        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_decompose", L, size, n, ct, plain);
+        dev(c).bfv_decompose(pl, L, size, n, ct, plain);
     });
 }
 int he355_bfv_decompose_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, int L_out, uint64_t *plain_ntt)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_decompose_ntt");
-        if (L_out < 1) throw std::invalid_argument("he355_bfv_decompose_ntt: level out of range");
-        DeviceContext::check_digit_args(*c->params, "he355_bfv_decompose_ntt", L, size, n, ct, plain_ntt, L_out);
-        dev(c).bfv_decompose_ntt(L, size, n, ct, L_out, plain_ntt);
+        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_decompose_ntt", L, size, n, ct, plain_ntt, true, L_out);
+        dev(c).bfv_decompose_ntt(pl, L, size, n, ct, L_out, plain_ntt);
     });
 }
 int he355_bfv_compose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *plain, uint64_t *ct)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_compose");
-        DeviceContext::check_digit_args(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
-        dev(c).bfv_compose(L, size, n, plain, ct);
+        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
+        dev(c).bfv_compose(pl, L, size, n, plain, ct);
     });
 }
 uint64_t he355_bfv_gadget_count(const he355_ctx *c, int L, int digit_bits, uint32_t *per_prime, uint64_t cap)
 {
     if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || !bfv_gadget_width_ok(digit_bits)) return 0;
-    u64 q[kMaxPrimes];
-    for (int i = 0; i < L; ++i) q[i] = c->params->primes[i].q;
-    const BfvDigitTab tab = bfv_gadget_table(q, L, digit_bits);
+    const BfvDigitTab tab = bfv_gadget_table(level_primes(*c->params, L).data(), L, digit_bits);
     for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
     return tab.total;
 }
@@ -3009,24 +2776,24 @@ int he355_bfv_gadget_decompose(he355_ctx *c, int L, int digit_bits, int size, ui
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_gadget_decompose");
-        DeviceContext::check_gadget_cut_args(*c->params, "he355_bfv_gadget_decompose", L, digit_bits, size, n, d_ct, d_digits, false);
-        dev(c).bfv_gadget_decompose(L, digit_bits, size, n, d_ct, d_digits);
+        const BfvDigitPlan pl = plan_gadget_cut(*c->params, "he355_bfv_gadget_decompose", L, digit_bits, size, n, d_ct, d_digits, false);
+        dev(c).bfv_gadget_decompose(pl, L, size, n, d_ct, d_digits);
     });
 }
 int he355_bfv_gadget_decompose_ntt(he355_ctx *c, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits_ntt)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_gadget_decompose_ntt");
-        DeviceContext::check_gadget_cut_args(*c->params, "he355_bfv_gadget_decompose_ntt", L, digit_bits, size, n, d_ct, d_digits_ntt, true);
-        dev(c).bfv_gadget_decompose_ntt(L, digit_bits, size, n, d_ct, d_digits_ntt);
+        const BfvDigitPlan pl = plan_gadget_cut(*c->params, "he355_bfv_gadget_decompose_ntt", L, digit_bits, size, n, d_ct, d_digits_ntt, true);
+        dev(c).bfv_gadget_decompose_ntt(pl, L, size, n, d_ct, d_digits_ntt);
     });
 }
 int he355_bfv_rgsw_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_rgsw_encrypt");
-        DeviceContext::check_rgsw_args(*c->params, L, digit_bits, n, d_plain, d_rgsw);
-        dev(c).bfv_rgsw_encrypt(L, digit_bits, n, d_plain, seed, first_index, d_rgsw);
+        const BfvRgswPlan pl = plan_rgsw(*c->params, L, digit_bits, n, d_plain, d_rgsw);
+        dev(c).bfv_rgsw_encrypt(pl, L, n, d_plain, seed, first_index, d_rgsw);
     });
 }
 int he355_bfv_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel, uint64_t seed,
@@ -3034,15 +2801,15 @@ int he355_bfv_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, 
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_selector_encrypt");
-        DeviceContext::check_selector_args(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, d_out);
-        dev(c).bfv_selector_encrypt(L, digit_bits, n, n_sel, first_slot, count, d_sel, seed, first_index, d_out);
+        const BfvSelectorPlan pl = plan_selector(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, d_out);
+        dev(c).bfv_selector_encrypt(pl, L, n, n_sel, first_slot, d_sel, seed, first_index, d_out);
     });
 }
 int he355_bfv_rgsw_encrypt_secret(he355_ctx *c, int L, int key_bits, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_rgsw_encrypt_secret");
-        DeviceContext::check_rgsw_secret_args(*c->params, L, key_bits);
+        check_rgsw_secret_args(*c->params, L, key_bits);
         dev(c).bfv_rgsw_encrypt_secret(L, key_bits, seed, first_index, d_rgsw);
     });
 }
@@ -3051,8 +2818,8 @@ int he355_bfv_rgsw_from_bfv(he355_ctx *c, int L, int digit_bits, int key_bits, u
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_rgsw_from_bfv");
-        DeviceContext::check_from_bfv_args(*c->params, L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
-        dev(c).bfv_rgsw_from_bfv(L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
+        const BfvFromBfvPlan pl = plan_from_bfv(*c->params, L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
+        dev(c).bfv_rgsw_from_bfv(pl, L, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
     });
 }
 int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
@@ -3060,8 +2827,8 @@ int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, 
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_external_product");
-        DeviceContext::check_external_product_args(*c->params, L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
-        dev(c).bfv_external_product(L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
+        const BfvExternalPlan pl = plan_external_product(*c->params, L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
+        dev(c).bfv_external_product(pl, L, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
     });
 }
 uint64_t he355_bfv_bytes_per_plain(const he355_ctx *c, uint32_t *field_bits)
@@ -3075,25 +2842,24 @@ int he355_bfv_unpack_bytes(he355_ctx *c, uint64_t n, const void *d_bytes, uint64
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_unpack_bytes");
-        DeviceContext::check_bytes_args(*c->params, "he355_bfv_unpack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, 0, false);
-        dev(c).bfv_unpack_bytes(n, d_bytes, stride_bytes, bytes_per_plain, d_plain);
+        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_unpack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, false);
+        dev(c).bfv_unpack_bytes(pl, n, d_bytes, stride_bytes, bytes_per_plain, d_plain);
     });
 }
 int he355_bfv_unpack_bytes_ntt(he355_ctx *c, int L_out, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain_ntt)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_unpack_bytes_ntt");
-        if (L_out < 1) throw std::invalid_argument("he355_bfv_unpack_bytes_ntt: level out of range");
-        DeviceContext::check_bytes_args(*c->params, "he355_bfv_unpack_bytes_ntt", n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt, L_out, false);
-        dev(c).bfv_unpack_bytes_ntt(L_out, n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt);
+        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_unpack_bytes_ntt", n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt, false, true, L_out);
+        dev(c).bfv_unpack_bytes_ntt(pl, L_out, n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt);
     });
 }
 int he355_bfv_pack_bytes(he355_ctx *c, uint64_t n, const uint64_t *d_plain, uint64_t bytes_per_plain, uint64_t stride_bytes, void *d_bytes)
 {
     return guarded([&] {
         need_bfv(c, "he355_bfv_pack_bytes");
-        DeviceContext::check_bytes_args(*c->params, "he355_bfv_pack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, 0, true);
-        dev(c).bfv_pack_bytes(n, d_plain, bytes_per_plain, stride_bytes, d_bytes);
+        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_pack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, true);
+        dev(c).bfv_pack_bytes(pl, n, d_plain, bytes_per_plain, stride_bytes, d_bytes);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

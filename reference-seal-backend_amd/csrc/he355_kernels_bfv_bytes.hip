@@ -14,9 +14,12 @@
 //                        is the existing k_rows_fwd, in place.  Neither the [n][N] coefficient slab nor the lifted slab exists.  The four
 //                        blocks of a plaintext are neighbours in the grid and read the same words.  N = 1024 has no column pass: the
 //                        caller runs the two-call composition.
+// Launches: kernel_common.inc's dispatch_logn1 picks the LOGN1 instantiation, streaming_grid / grid_blocks size and bound the grids.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
+#include <string>
+#include <type_traits>
 
 #include "he355_kernels.h"
 #include "bfv_bytes_core.h"
@@ -99,11 +102,7 @@ BfvBytesArgs bytes_args(const KernelEnv &env, int w, u64 n, u64 stride, u64 B)
     A.n = n; A.stride = stride; A.B = B; A.w = w; A.logN = env.logn1 + kRowLog;
     return A;
 }
-unsigned grid_of(u64 blocks)
-{
-    if (blocks > 0x7fffffffull) throw std::invalid_argument("database bytes: too many plaintexts for one launch");
-    return (unsigned)blocks;
-}
+unsigned grid_of(u64 blocks) { return grid_blocks(blocks, "database bytes", "plaintexts"); }
 
 } // namespace
 
@@ -112,8 +111,7 @@ void launch_bfv_unpack(const KernelEnv &env, int w, u64 n, const void *bytes, u6
     if (!n) return;
     BfvBytesArgs A = bytes_args(env, w, n, stride, B);
     A.bytes_in = static_cast<const unsigned char *>(bytes); A.out = plain;
-    // N / 2 is a multiple of kBlock: a block lies inside one plaintext
-    hipLaunchKernelGGL(k_bfv_unpack, dim3(grid_of((n << (A.logN - 1)) / kBlock)), dim3(kBlock), 0, env.stream, A);
+    hipLaunchKernelGGL(k_bfv_unpack, dim3(streaming_grid(n, A.logN, "database bytes", "plaintexts")), dim3(kBlock), 0, env.stream, A);
 }
 void launch_bfv_pack(const KernelEnv &env, int w, u64 n, const u64 *plain, u64 B, u64 stride, void *bytes)
 {
@@ -132,14 +130,7 @@ void launch_bfv_bytes_cols_fwd(const KernelEnv &env, int w, u64 n, const void *b
     BfvBytesArgs A = bytes_args(env, w, n, stride, B);
     A.bytes_in = static_cast<const unsigned char *>(bytes); A.out = out; A.L_out = L_out; A.t = t;
     const dim3 g(grid_of(n * 4)), b(kBlock);
-    switch (env.logn1) {
-    case 1: hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<1>, g, b, 0, env.stream, A, env.primes); break;
-    case 2: hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<2>, g, b, 0, env.stream, A, env.primes); break;
-    case 3: hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<3>, g, b, 0, env.stream, A, env.primes); break;
-    case 4: hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<4>, g, b, 0, env.stream, A, env.primes); break;
-    case 5: hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<5>, g, b, 0, env.stream, A, env.primes); break;
-    default: throw std::invalid_argument("ring size out of range");
-    }
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL(k_bfv_bytes_cols_fwd<decltype(n1)::value>, g, b, 0, env.stream, A, env.primes); });
 }
 
 } // namespace HE355_KNS

@@ -15,9 +15,12 @@
 //                        out(f, i').  The row pass is the existing k_rows_fwd, in place.  Neither the [n][F][N] plaintext slab nor the lifted
 //                        [n][F][L_out][N] slab is written or read back.  The D_i blocks that share a ciphertext residue are neighbours in
 //                        the grid, so the word leaves HBM once.  N = 1024 has no column pass: the caller runs the two-call composition.
+// Launches: kernel_common.inc's dispatch_logn1 picks the LOGN1 instantiation, streaming_grid / grid_blocks size and bound the grids.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
+#include <string>
+#include <type_traits>
 
 #include "he355_kernels.h"
 #include "bfv_digits_core.h"
@@ -119,12 +122,6 @@ BfvDigitsArgs digits_args(const KernelEnv &env, const BfvDigitTab &tab, int L, i
     A.in = in; A.out = out; A.n_polys = n * size * L; A.L = L; A.size = size; A.logN = env.logn1 + kRowLog; A.tab = tab;
     return A;
 }
-unsigned streaming_grid(const BfvDigitsArgs &A)
-{
-    const u64 blocks = (A.n_polys << (A.logN - 1)) / kBlock; // N / 2 is a multiple of kBlock: a block lies inside one polynomial
-    if (blocks > 0x7fffffffull) throw std::invalid_argument("ciphertext decomposition: too many polynomials for one launch");
-    return (unsigned)blocks;
-}
 
 } // namespace
 
@@ -132,13 +129,13 @@ void launch_bfv_digits(const KernelEnv &env, const BfvDigitTab &tab, int L, int 
 {
     if (!n) return;
     const BfvDigitsArgs A = digits_args(env, tab, L, size, n, ct, plain);
-    hipLaunchKernelGGL(k_bfv_digits, dim3(streaming_grid(A)), dim3(kBlock), 0, env.stream, A);
+    hipLaunchKernelGGL(k_bfv_digits, dim3(streaming_grid(A.n_polys, A.logN, "ciphertext decomposition")), dim3(kBlock), 0, env.stream, A);
 }
 void launch_bfv_undigits(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *plain, u64 *ct)
 {
     if (!n) return;
     const BfvDigitsArgs A = digits_args(env, tab, L, size, n, plain, ct);
-    hipLaunchKernelGGL(k_bfv_undigits, dim3(streaming_grid(A)), dim3(kBlock), 0, env.stream, A, env.primes);
+    hipLaunchKernelGGL(k_bfv_undigits, dim3(streaming_grid(A.n_polys, A.logN, "ciphertext decomposition")), dim3(kBlock), 0, env.stream, A, env.primes);
 }
 void launch_bfv_digits_cols_fwd(const KernelEnv &env, const BfvDigitTab &tab, int L, int size, u64 n, const u64 *ct, int L_out, u64 t, u64 *out)
 {
@@ -147,17 +144,8 @@ void launch_bfv_digits_cols_fwd(const KernelEnv &env, const BfvDigitTab &tab, in
     if (L_out < 1 || L_out > kMaxPrimes) throw std::invalid_argument("ciphertext decomposition: output level out of range");
     BfvDigitsArgs A = digits_args(env, tab, L, size, n, ct, out);
     A.L_out = L_out; A.t = t;
-    const u64 blocks = n * size * tab.total * 4;
-    if (blocks > 0x7fffffffull) throw std::invalid_argument("ciphertext decomposition: too many plaintexts for one launch");
-    const dim3 g((unsigned)blocks), b(kBlock);
-    switch (env.logn1) {
-    case 1: hipLaunchKernelGGL(k_bfv_digits_cols_fwd<1>, g, b, 0, env.stream, A, env.primes); break;
-    case 2: hipLaunchKernelGGL(k_bfv_digits_cols_fwd<2>, g, b, 0, env.stream, A, env.primes); break;
-    case 3: hipLaunchKernelGGL(k_bfv_digits_cols_fwd<3>, g, b, 0, env.stream, A, env.primes); break;
-    case 4: hipLaunchKernelGGL(k_bfv_digits_cols_fwd<4>, g, b, 0, env.stream, A, env.primes); break;
-    case 5: hipLaunchKernelGGL(k_bfv_digits_cols_fwd<5>, g, b, 0, env.stream, A, env.primes); break;
-    default: throw std::invalid_argument("ring size out of range");
-    }
+    const dim3 g(grid_blocks(n * size * tab.total * 4, "ciphertext decomposition", "plaintexts")), b(kBlock);
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL(k_bfv_digits_cols_fwd<decltype(n1)::value>, g, b, 0, env.stream, A, env.primes); });
 }
 
 } // namespace HE355_KNS

@@ -32,10 +32,12 @@
 //                        encryption of zero cut to L primes and, in polynomial 0 at a coefficient that is a slot of a digit of prime i,
 //                        bfv_selector_value of the slot's selector.
 //   k_bfv_secret_plain   the secret key's coefficients under prime 0 (0, 1, q_0 - 1) -> 0, 1, t - 1.
+// Launches: kernel_common.inc's dispatch_logn1 picks the LOGN1 instantiation, streaming_grid / grid_blocks size and bound the grids.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "he355_kernels.h"
 #include "bfv_gadget_core.h"
@@ -300,13 +302,6 @@ BfvGadgetCutArgs cut_args(const KernelEnv &env, const BfvDigitTab &tab, int L, i
     A.first = 0; A.own = nullptr; A.own_E = 0;
     return A;
 }
-unsigned streaming_grid(u64 n_polys, int logN, const char *what)
-{
-    const u64 blocks = (n_polys << (logN - 1)) / kBlock; // N / 2 is a multiple of kBlock: a block lies inside one polynomial
-    if (blocks > 0x7fffffffull) throw std::invalid_argument(std::string(what) + ": too many polynomials for one launch");
-    return (unsigned)blocks;
-}
-
 template <bool OWN>
 void launch_cut(const KernelEnv &env, const BfvGadgetCutArgs &A, bool cols)
 {
@@ -314,17 +309,8 @@ void launch_cut(const KernelEnv &env, const BfvGadgetCutArgs &A, bool cols)
         hipLaunchKernelGGL(k_bfv_gadget_spread<OWN>, dim3(streaming_grid(A.n_polys, A.logN, "gadget decomposition")), dim3(kBlock), 0, env.stream, A, env.primes);
         return;
     }
-    const u64 blocks = A.n_polys * 4;
-    if (blocks > 0x7fffffffull) throw std::invalid_argument("gadget decomposition: too many polynomials for one launch");
-    const dim3 g((unsigned)blocks), b(kBlock);
-    switch (env.logn1) {
-    case 1: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<1, OWN>), g, b, 0, env.stream, A, env.primes); break;
-    case 2: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<2, OWN>), g, b, 0, env.stream, A, env.primes); break;
-    case 3: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<3, OWN>), g, b, 0, env.stream, A, env.primes); break;
-    case 4: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<4, OWN>), g, b, 0, env.stream, A, env.primes); break;
-    case 5: hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<5, OWN>), g, b, 0, env.stream, A, env.primes); break;
-    default: throw std::invalid_argument("ring size out of range");
-    }
+    const dim3 g(grid_blocks(A.n_polys * 4, "gadget decomposition")), b(kBlock);
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL((k_bfv_gadget_cols_fwd<decltype(n1)::value, OWN>), g, b, 0, env.stream, A, env.primes); });
 }
 
 } // namespace

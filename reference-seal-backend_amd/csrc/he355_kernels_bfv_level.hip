@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 
 #include "he355_kernels.h"
@@ -214,14 +215,7 @@ void launch_bfv_mp_cols_fwd(const KernelEnv &env, int L, int size, u64 n_ops, u6
     BfvMpArgs A{};
     A.ct = ct; A.prep = nullptr; A.out = out; A.ix = ix; A.op_offset = op_offset; A.n_ops = n_ops; A.L = L; A.size = size; A.logn1 = env.logn1;
     const unsigned g = (unsigned)(n_ops * size * L * 4);
-    switch (env.logn1) {
-    case 1: hipLaunchKernelGGL(k_bfv_mp_cols_fwd<1>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); break;
-    case 2: hipLaunchKernelGGL(k_bfv_mp_cols_fwd<2>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); break;
-    case 3: hipLaunchKernelGGL(k_bfv_mp_cols_fwd<3>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); break;
-    case 4: hipLaunchKernelGGL(k_bfv_mp_cols_fwd<4>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); break;
-    case 5: hipLaunchKernelGGL(k_bfv_mp_cols_fwd<5>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); break;
-    default: throw std::invalid_argument("ring size out of range");
-    }
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL(k_bfv_mp_cols_fwd<decltype(n1)::value>, dim3(g), dim3(kBlock), 0, env.stream, A, env.primes); });
 }
 void launch_bfv_mp_rows(const KernelEnv &env, int L, int size, u64 n_ops, u64 op_offset, const u64 *ct, const u64 *prep, Indexer ix, u64 *out)
 {

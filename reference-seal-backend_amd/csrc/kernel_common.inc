@@ -1,5 +1,6 @@
-// kernel_common.inc -- helpers shared by the kernel translation units (he355_kernels.hip, he355_kernels_lds.hip): wavefront-scope hand-offs,
-// engine construction, row <-> register moves, the LDS-DMA row fetch and the wave-level row transforms.  Included INSIDE the anonymous
+// kernel_common.inc -- helpers shared by the kernel translation units (he355_kernels.hip, he355_kernels_lds.hip, he355_kernels_bfv_*.hip):
+// wavefront-scope hand-offs, engine construction, row <-> register moves, the LDS-DMA row fetch, the wave-level row transforms and, host
+// side, the LOGN1 dispatch and the grid sizes of the BFV PIR launches (dispatch_logn1, grid_blocks, streaming_grid).  Included INSIDE the anonymous
 // namespace of a kernel file (after ntt_core.h), once per build of the u64 engine; the text is what he355_kernels.hip held in place
 // through round 5 (same token stream: tools/kres.py shows identical registers / spills / LDS for every instantiation).
 constexpr int kBlock = 256;
@@ -70,6 +71,36 @@ __device__ __forceinline__ void store_rowC(u64 *row, int lane, const u64 v[kRowE
         p[0] = make_ulonglong2(v[4 * c + 0], v[4 * c + 1]);
         p[1] = make_ulonglong2(v[4 * c + 2], v[4 * c + 3]);
     }
+}
+
+// ---- host side: launches of the kernels with a column pass, and grids ------------------------------------------------------------------
+// launch(std::integral_constant<int, LOGN1>) for the ring's LOGN1 = logn1 in 1..5 (N = 2048 .. 32768; N = 1024 has no column pass)
+template <class Launch>
+void dispatch_logn1(int logn1, Launch &&launch)
+{
+    switch (logn1) {
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 2: launch(std::integral_constant<int, 2>()); break;
+    case 3: launch(std::integral_constant<int, 3>()); break;
+    case 4: launch(std::integral_constant<int, 4>()); break;
+    case 5: launch(std::integral_constant<int, 5>()); break;
+    default: throw std::invalid_argument("ring size out of range");
+    }
+}
+// a grid of `blocks` blocks, refused where it does not fit one launch ("<what>: too many <unit> for one launch").  `what` is a string
+// literal; this and streaming_grid are templates only so that the kernel files that include this text and launch no such grid
+// instantiate nothing (no unused-function warning, and no <string> asked of them).
+template <class What>
+unsigned grid_blocks(u64 blocks, What what, const char *unit = "polynomials")
+{
+    if (blocks > 0x7fffffffull) throw std::invalid_argument(std::string(what) + ": too many " + unit + " for one launch");
+    return (unsigned)blocks;
+}
+// the grid of a streaming kernel whose lanes own two coefficients each: N / 2 is a multiple of kBlock, so a block lies inside one polynomial
+template <class What>
+unsigned streaming_grid(u64 n_polys, int logN, What what, const char *unit = "polynomials")
+{
+    return grid_blocks((n_polys << (logN - 1)) / kBlock, what, unit);
 }
 
 // Key products issued together in the fused fp64 k_k3 (2 polynomials x kMacG / 2 elements): interleaved chains, at two waves per
