@@ -258,7 +258,7 @@ int he355_bfv_plain_to_ntt(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_
 int he355_bfv_multiply_plain_ntt(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_ct, const uint64_t *d_plain_ntt, he355_indexer ix, uint64_t *d_out);
 int he355_bfv_multiply_plain_accumulate(he355_ctx *ctx, int L, int size, uint64_t rows, uint64_t cols, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_i,
                                         uint64_t ct_stride_k, const uint64_t *d_plain_ntt, uint64_t pt_stride_k, uint64_t pt_stride_j, uint64_t *d_out);
-/* ---- monomial multiply and oblivious query expansion (BFV contexts only, else HE355_E_INVALID_ARGS, decided on the host before any device
+/* ---- monomial multiply, oblivious query expansion and ciphertext merge (BFV contexts only, else HE355_E_INVALID_ARGS, decided on the host before any device
  * is asked for; coefficient form; every L in 1..L_top).  he355_bfv_multiply_plain_accumulate scans a database with one ciphertext per
  * index of a dimension -- Enc(1) at the wanted index, Enc(0) elsewhere; instead of encrypting and uploading all of them a client sends
  * ONE ciphertext of sum_k m_k X^k and the server expands it obliviously (Angel, Chen, Laine, Setty, "PIR with compressed queries and
@@ -283,10 +283,38 @@ int he355_bfv_multiply_plain_accumulate(he355_ctx *ctx, int L, int size, uint64_
  *                                 Refused before the first launch, so that nothing is half-written: a count of 0 or above N, a bad L, a
  *                                 missing Galois key (the message names the element), d_out overlapping d_in.  n == 0 touches nothing;
  *                                 count == 1 copies.  Scratch: one pool block of 2^(d-1) n ciphertexts (a second identical call allocates
- *                                 nothing).  NOT for NTT-form ciphertexts: as in SEAL, transform after the expansion. */
+ *                                 nothing).  NOT for NTT-form ciphertexts: as in SEAL, transform after the expansion.
+ *   he355_bfv_merge               the expansion's transpose: `count` ciphertexts per result become ONE (PackLWEs / the partial-trace merge of
+ *                                 Chen, Dai, Kim, Song, "Efficient homomorphic conversion between (ring) LWE ciphertexts", Alg. 2, the response
+ *                                 packing of Spiral and Respire), so a server that answers `count` retrievals whose records each fill a
+ *                                 1/count share of the ring sends one reply instead of `count`.  Input k < count of result r < n is the
+ *                                 ciphertext at index k in_stride_k + r in_stride_r of d_in, strides in ciphertexts of 2 L N words:
+ *                                 (n, 1) is what he355_bfv_expand writes, (1, cols) what a scan's [rows][cols] results are; d_out is
+ *                                 [n][2][L][N]; 1 <= count <= N, d = ceil(log2 count).  The Galois elements are exactly
+ *                                 he355_bfv_expand_galois_elts(count): there is no enumerator of its own, and a client that uploaded expansion
+ *                                 keys needs no further key.  The definition, every + and - being he355_add / he355_sub on canonical residues,
+ *                                 every X^s he355_bfv_multiply_monomial, slots k >= count absent: for j = d-1 down to 0, s = 2^j, and every
+ *                                 slot k < s, with even = slot k and odd = slot k + s:
+ *                                     S = even + X^s odd,  D = even - X^s odd      (S = D = even where slot k + s is absent: the first level only)
+ *                                     slot k := S + he355_apply_galois(D, e_j)
+ *                                 d_out is slot 0 after level 0; count == 1 copies.  The call is bit-identical to this composition of the
+ *                                 public calls; it runs one launch and one batched key switch (D, with S as its addend) per level over
+ *                                 the pairs of all results, 2^d - 1 key switches per result in all.  If input k decrypts to
+ *                                 sum_i mu_(k,i) X^i, the result decrypts to the polynomial whose coefficient k + 2^d m is
+ *                                 2^d mu_(k, 2^d m) mod t for k < count and 0 for count <= k < 2^d (the client folds 2^-d mod t in; t is odd):
+ *                                 only the coefficients of input k at multiples of 2^d survive, moved up by k, and
+ *                                 he355_bfv_merge(he355_bfv_expand(q)) at count = 2^d decrypts to 4^d times the plaintext of q.
+ *                                 Refused before the first launch, so that nothing is half-written: a count of 0 or above N, a bad L, strides
+ *                                 under which two inputs lie at one place (a stride of 0 along an index that moves, or colliding indices), an
+ *                                 extent whose index arithmetic would wrap (past 2^60 words), more pairs than one launch's grid holds, a
+ *                                 missing Galois key (the message names the element), d_out overlapping the inputs (d_out may not lie inside
+ *                                 their span, a gap between strided inputs included).  n == 0 touches nothing.  Scratch: one pool block of
+ *                                 3 2^(d-1) n ciphertexts (2 n at d = 1; a second identical call allocates nothing; if it does not fit, the
+ *                                 allocator's error comes before any launch).  Coefficient form only, as the expansion. */
 int he355_bfv_multiply_monomial(he355_ctx *ctx, int L, int size, uint64_t n, const uint64_t *d_in, uint32_t exponent, uint64_t *d_out);
 uint64_t he355_bfv_expand_galois_elts(const he355_ctx *ctx, uint64_t count, uint32_t *out, uint64_t cap);
 int he355_bfv_expand(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, uint64_t count, uint64_t *d_out);
+int he355_bfv_merge(he355_ctx *ctx, int L, uint64_t n, uint64_t count, const uint64_t *d_in, uint64_t in_stride_k, uint64_t in_stride_r, uint64_t *d_out);
 /* ---- ciphertext decomposition for recursive (two-dimensional) PIR (BFV contexts only, coefficient-form ciphertexts, every L in 1..L_top).
  * A database seen as n1 x n2 needs n1 + n2 expanded children instead of n1 n2 (Angel, Chen, Laine, Setty, "Handling larger databases"): scan
  * the first dimension, CUT each of the n2 resulting ciphertexts into plaintexts, scan those with the second dimension's children; the client

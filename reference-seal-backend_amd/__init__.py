@@ -135,6 +135,7 @@ def lib():
             "he355_bfv_multiply_monomial": (i32, [vp, i32, i32, u64, vp, u32, vp]),
             "he355_bfv_expand_galois_elts": (u64, [vp, u64, C.POINTER(u32), u64]),
             "he355_bfv_expand": (i32, [vp, i32, u64, vp, u64, vp]),
+            "he355_bfv_merge": (i32, [vp, i32, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_digit_count": (u64, [vp, i32, C.POINTER(u32), u64]),
             "he355_bfv_decompose": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_bfv_decompose_ntt": (i32, [vp, i32, i32, u64, vp, i32, vp]),
@@ -197,7 +198,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -445,6 +446,12 @@ class Context:
     def bfv_expand(self, L, n, inp, count, out):
         """oblivious query expansion: inp [n][2][L][N] -> out [count][n][2][L][N], child k of query r at index k * n + r"""
         _check(lib().he355_bfv_expand(self.h, L, n, inp.ptr, count, out.ptr))
+
+    def bfv_merge(self, L, n, count, inp, stride_k, stride_r, out):
+        """the expansion's transpose: input k < count of result r < n at ciphertext k * stride_k + r * stride_r of inp -> out [n][2][L][N], whose
+        plaintext holds 2^d times coefficient 2^d m of input k at coefficient k + 2^d m, d = ceil(log2 count); the Galois keys are those of
+        bfv_expand_galois_elts(count)"""
+        _check(lib().he355_bfv_merge(self.h, L, n, count, inp.ptr, stride_k, stride_r, out.ptr))
 
     def bfv_digit_count(self, L: int) -> tuple[int, list[int]]:
         """(D(L), [D_0 .. D_(L-1)]): how many plaintexts bfv_decompose cuts one residue polynomial into under each prime of level L, digits

@@ -1,4 +1,4 @@
-// bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, decomposition, the external
+// bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, merge, decomposition, the external
 // product and its selectors, database bytes), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
 // device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands what the check worked out (the digit tables, F,
 // rows, terms, pass, the field width) to DeviceContext as a plan.  What needs the device or its state (keys present, the Galois keys, the
@@ -142,6 +142,45 @@ inline BfvExternalPlan plan_external_product(const Params &p, int L, int v, u64 
     if (ranges_overlap(out, n * ctn, ct, gadget_span_words(w, n, inner, ct_stride_r, ct_stride_k, ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the ciphertexts");
     if (ranges_overlap(out, n * ctn, rgsw, gadget_span_words(w, n, inner, rg_stride_r, rg_stride_k, rows * ctn))) throw std::invalid_argument(w + ": `d_out` overlaps the RGSW ciphertexts");
     return plan;
+}
+
+// ---- ciphertext merge (he355_bfv_merge) ------------------------------------------------------------------------------------------------
+// the merge, the expansion's transpose: input k < count of result r < n is ciphertext k stride_k + r stride_r of `in`, `out` is [n][2][L][N].
+// depth: the levels; half = 2^(depth-1) n, the pairs of the first level (0 at depth 0); scratch_cts: the pool block, S and D of the first
+// level and, unless that level is the last, its output (0 when n is 0 or the call only copies)
+struct BfvMergePlan {
+    int depth;
+    u64 half, scratch_cts;
+};
+inline u64 gcd_u64(u64 a, u64 b)
+{
+    while (b) { const u64 t = a % b; a = b; b = t; }
+    return a;
+}
+inline BfvMergePlan plan_merge(const Params &p, int L, u64 n, u64 count, const u64 *in, u64 stride_k, u64 stride_r, const u64 *out)
+{
+    const std::string w("he355_bfv_merge");
+    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
+    const int d = expand_depth(count);
+    if (!n) return {d, 0, 0};
+    // two inputs at one place: a stride of 0 along an index that moves, or k stride_k + r stride_r = k' stride_k + r' stride_r, which has a
+    // solution exactly when the smallest one, k - k' = stride_r / g and r' - r = stride_k / g (g the strides' gcd), lies inside the extents
+    if ((count > 1 && !stride_k) || (n > 1 && !stride_r)) throw std::invalid_argument(w + ": a stride of 0 puts two inputs at one place");
+    if (count > 1 && n > 1) {
+        const u64 g = gcd_u64(stride_k, stride_r);
+        if (stride_r / g <= count - 1 && stride_k / g <= n - 1) throw std::invalid_argument(w + ": under these strides two inputs lie at one place");
+    }
+    const size_t ctn = 2 * (size_t)L * p.N;
+    const size_t span = gadget_span_words(w, n, count, stride_r, stride_k, ctn); // checked: refused where the index arithmetic would wrap
+    const u64 blocks_per_ct = 2 * (u64)L * (p.N / 512);
+    const u128 half = d ? (u128)n << (d - 1) : 0;
+    if (n > 0x7fffffffull || half > 0x7fffffffull / blocks_per_ct) throw std::invalid_argument(w + ": too many polynomials for one launch");
+    // as integers: a span of up to 2^60 words behind any address may pass the end of the address space, where no pointer may be formed
+    const unsigned long long i0 = (unsigned long long)in, i1 = i0 + 8 * (unsigned long long)span, o0 = (unsigned long long)out, o1 = o0 + 8 * (unsigned long long)(n * ctn);
+    if (i1 < i0 || o1 < o0) throw std::invalid_argument(w + ": a range wraps the address space");
+    if (i0 < o1 && o0 < i1) throw std::invalid_argument(w + ": `d_out` overlaps the inputs (it may not lie inside their span)");
+    return {d, (u64)half, (u64)half * (d > 1 ? 3 : 2)};
 }
 
 // ---- RGSW selectors from ONE packed query ciphertext ---------------------------------------------------------------------------------

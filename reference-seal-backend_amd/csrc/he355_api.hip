@@ -1827,6 +1827,44 @@ public:
         }
         HIPCHECK(hipGetLastError());
     }
+    // The expansion's transpose (Chen, Dai, Kim, Song, "Efficient homomorphic conversion between (ring) LWE ciphertexts", Alg. 2): input k of
+    // result r at ciphertext k stride_k + r stride_r of `in` -> out [n][2][L][N].  Level j = d-1 .. 0 (s = 2^j) is ONE k_bfv_merge launch over the
+    // s n pairs of all results, pair k n + r, which leaves S = even + X^s odd and D = even - X^s odd (S = D = even where slot k + s is absent:
+    // the first level only) in two slabs, and ONE batched key switch of D with S as its addend, which leaves slot k of result r at k n + r:
+    // only the first level reads through the strides.  One pool block holds S, D and the level's output, each 2^(d-1) n ciphertexts, the first
+    // level's sizes (the later levels use the head of each; a level's output is consumed by the next merge launch before the next key switch
+    // writes there); the last level lands in `out`.  Everything runs on the context's stream; every refusal, the block's included, comes
+    // before the first launch.
+    void bfv_merge(const BfvMergePlan &pl, int L, u64 n, u64 count, const u64 *in, u64 stride_k, u64 stride_r, u64 *out)
+    {
+        use();
+        const int d = pl.depth;
+        const size_t N = P.N, ctn = 2 * (size_t)L * N;
+        if (d) require_keyswitch();
+        for (int j = d - 1; j >= 0; --j) {
+            const uint32_t elt = (uint32_t)(N >> j) + 1;
+            if (!galois_key(elt)) throw std::invalid_argument("he355_bfv_merge: Galois key of element " + std::to_string(elt) + " not present");
+        }
+        if (!n) return;
+        if (!d) { // count == 1: result r is its one input
+            if (stride_r == 1 || n == 1) HIPCHECK(hipMemcpyAsync(out, in, n * ctn * 8, hipMemcpyDeviceToDevice, stream_));
+            else
+                for (u64 r = 0; r < n; ++r) HIPCHECK(hipMemcpyAsync(out + r * ctn, in + r * stride_r * ctn, ctn * 8, hipMemcpyDeviceToDevice, stream_));
+            return;
+        }
+        const PoolBlock blk = scoped_block((size_t)pl.scratch_cts * ctn * 8);
+        u64 *S = blk.get(), *D = S + pl.half * ctn, *mid = D + pl.half * ctn; // mid: unused (and not there) when d == 1
+        const u64 *cur = in;
+        u64 have = count; // slots present
+        for (int j = d - 1; j >= 0; --j) {
+            const u64 s = (u64)1 << j;
+            launch_bfv_merge(env_, L, n, s, (have - s) * n, cur, stride_k, stride_r, S, D);
+            u64 *dst = j ? mid : out;
+            apply_galois(L, s * n, D, (uint32_t)(N >> j) + 1, dst, S);
+            cur = dst; stride_k = n; stride_r = 1; have = s;
+        }
+        HIPCHECK(hipGetLastError());
+    }
     // ---- ciphertext decomposition for recursive (two-dimensional) PIR (he355_kernels_bfv_digits.hip) ---------------------------------
     // [n][size][L][N] -> [n][F][N] coefficients mod t: one streaming launch
     void bfv_decompose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *plain)
@@ -2732,6 +2770,14 @@ int he355_bfv_expand(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint64
         need_bfv(c, "he355_bfv_expand");
         const BfvExpandPlan pl = plan_expand(*c->params, L, count);
         dev(c).bfv_expand(pl, L, n, in, count, out);
+    });
+}
+int he355_bfv_merge(he355_ctx *c, int L, uint64_t n, uint64_t count, const uint64_t *in, uint64_t in_stride_k, uint64_t in_stride_r, uint64_t *out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_merge");
+        const BfvMergePlan pl = plan_merge(*c->params, L, n, count, in, in_stride_k, in_stride_r, out);
+        dev(c).bfv_merge(pl, L, n, count, in, in_stride_k, in_stride_r, out);
     });
 }
 uint64_t he355_bfv_digit_count(const he355_ctx *c, int L, uint32_t *per_prime, uint64_t cap)

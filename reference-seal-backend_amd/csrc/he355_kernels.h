@@ -241,6 +241,7 @@ HE355_FWD(launch_bfv_noise_bits)
 HE355_FWD(launch_bfv_noise_finish)
 HE355_FWD(launch_bfv_plain_mac)
 HE355_FWD(launch_bfv_shift)
+HE355_FWD(launch_bfv_merge)
 HE355_FWD(launch_bfv_digits)
 HE355_FWD(launch_bfv_undigits)
 HE355_FWD(launch_bfv_digits_cols_fwd)

@@ -146,6 +146,10 @@ void launch_bfv_plain_mac(const KernelEnv &env, int L, int size, u64 rows, u64 c
 // prime p % L): x = in, or (even != null) 2 in - even -- the odd child X^(-s) (c - g) of the expansion from the node c and its even child
 // c + g.  out may overlap neither operand.  One launch.
 void launch_bfv_shift(const KernelEnv &env, int L, u64 n_polys, const u64 *in, const u64 *even, u32 e, u64 *out);
+// one level of he355_bfv_merge (arithmetic: bfv_merge_core.h): pair p = k n + r, k < s = 2^j, r < n, has its even operand at ciphertext
+// k stride_k + r stride_r of `in` ([2][L][N] words each) and its odd operand s stride_k behind it; S[p] = even + X^s odd, D[p] = even - X^s odd,
+// and S[p] = D[p] = even for the pairs p >= full, whose partner is absent.  S and D may overlap neither each other nor an operand.  One launch.
+void launch_bfv_merge(const KernelEnv &env, int L, u64 n, u64 s, u64 full, const u64 *in, u64 stride_k, u64 stride_r, u64 *S, u64 *D);
 // ---- BFV ciphertext decomposition for recursive PIR (he355_kernels_bfv_digits.hip; arithmetic: bfv_digits_core.h) ---------------------------
 // ct [n][size][L][N] coefficient form <-> plain [n][F][N] mod t, F = size D(L): digit g of polynomial k under prime i is plaintext
 // k D(L) + off_i + g (`tab`: bfv_digit_table of the level).  One launch each; the two slabs may not overlap.
