@@ -123,15 +123,18 @@ int he355_path_stats(he355_ctx *ctx, he355_path_stats_t *out, int reset);
  * (ring size, batch, strides: the ROUTED notes of DESIGN.md) and bit-identical by definition, so a result cannot tell which one ran; tests use
  * the counters to prove that the route they mean to hold to the oracle is the one that ran (tests/test_gpu_bfv_large_rings.py).  Counted on
  * the host where the calls branch; no counter is read by a launch.  A "pass" is one trip of he355_bfv_external_product or
- * he355_bfv_rgsw_from_bfv through its pool block of digit polynomials. */
+ * he355_bfv_rgsw_from_bfv through its pool block of digit polynomials, or of one level of he355_bfv_select; that call's passes also count in
+ * mac_gadget / mac_plain as the external product's do. */
 typedef struct {
     uint64_t cut_cols, cut_stream;         /* cuts of he355_bfv_gadget_decompose_ntt and of he355_bfv_external_product's passes: the fused column pass / the streaming cut */
     uint64_t mac_gadget, mac_plain;        /* he355_bfv_external_product passes by multiply-accumulate kernel: k_bfv_gadget_mac / k_bfv_plain_mac */
     uint64_t own_cols, own_stream;         /* he355_bfv_rgsw_from_bfv passes by cut: the column pass that also emits the slot's own row / the streaming cut */
     uint64_t digits_fused, digits_routed;  /* he355_bfv_decompose_ntt calls: the fused column pass / N = 1024's composition */
     uint64_t bytes_fused, bytes_routed;    /* he355_bfv_unpack_bytes_ntt: fused calls / passes of N = 1024's composition through its pool block */
-    uint64_t passes;                       /* pool-block passes of he355_bfv_external_product and he355_bfv_rgsw_from_bfv */
-    uint64_t reserved[5];
+    uint64_t passes;                       /* pool-block passes of he355_bfv_external_product, he355_bfv_rgsw_from_bfv and he355_bfv_select */
+    uint64_t select_cols, select_stream;   /* he355_bfv_select passes by cut: the column pass / the streaming cut, both of odd - even */
+    uint64_t select_tail_fused, select_tail_routed; /* he355_bfv_select levels by tail: the inverse column pass that adds the even node / N = 1024's composition */
+    uint64_t reserved[1];
 } he355_bfv_route_stats_t;
 int he355_bfv_route_stats(he355_ctx *ctx, he355_bfv_route_stats_t *out, int reset);
 /* Which route the context's BEHZ multiplies (he355_bfv_multiply, he355_bfv_multiply_relin_accumulate) took since he355_device_init (or the
@@ -391,6 +394,39 @@ int he355_bfv_gadget_decompose_ntt(he355_ctx *ctx, int L, int digit_bits, int si
 int he355_bfv_rgsw_encrypt(he355_ctx *ctx, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw);
 int he355_bfv_external_product(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
                                const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_k, uint64_t *d_out);
+/* ---- the selection tree: fold `count` ciphertexts with ceil(log2 count) RGSW bits (BFV contexts only, coefficient form in and out, every L in
+ * 1..L_top, digit_bits = v in 1..63, E = E(L) as above).  he355_bfv_external_product selects with ONE-HOT selectors, one RGSW ciphertext per
+ * candidate; as in OnionPIR and Spiral a selector per BIT of the index folds the candidates pairwise with a CMUX, even + RGSW(b) [.] (odd - even):
+ * 32 candidates need 5 selectors, and gadget noise enters m times one after the other instead of as a 2^m-term sum.
+ *   he355_bfv_select   leaf k < count of result r < n is the ciphertext [2][L][N] at index r ct_stride_r + k ct_stride_k of d_ct ((cols, 1): a
+ *                      scan's [rows][cols] results; (1, n): child-major).  m = ceil(log2 count); selector j < m of result r is the RGSW
+ *                      ciphertext [2E][2][L][N] (NTT form) at index r rg_stride_r + j rg_stride_j of d_rgsw ((n_sel, 1): what
+ *                      he355_bfv_rgsw_from_bfv writes; rg_stride_r == 0: all results share one set of bits).  d_out is [n][2][L][N].
+ *                      The definition, every + and - being he355_add / he355_sub on canonical residues: level j = 0 .. m-1 has c_j nodes per
+ *                      result, c_0 = count (the leaves), c_(j+1) = ceil(c_j / 2), and for every p < c_(j+1)
+ *                          node'(p) = node(2p) + he355_bfv_external_product(L, v, 1, 1, node(2p+1) - node(2p), RGSW(r, j))   where 2p+1 < c_j,
+ *                          node'(p) = node(2p), a copy,                                                                     where 2p+1 = c_j;
+ *                      d_out(r) is the one node left after level m-1.  The call is BIT-IDENTICAL to this composition of the public calls.
+ *                      count == 1 copies; n == 0 touches nothing.  Meaning: if selector j encrypts the bit b_j and leaf k has phase
+ *                      Delta mu_k + e_k, the result decrypts to the leaf with index sum_j b_j 2^j (the least significant bit is consumed
+ *                      first) where that index is below count.  Where it is not, the pass-through rule decides: at every level a node
+ *                      without a partner is taken whatever the bit says, so the result is the leaf reached by walking down from the root
+ *                      and, at level j, going to child 2p + b_j if it exists and to child 2p otherwise (count = 5, bits (1,0,1): leaf 4).
+ *                      One level is a pass loop over all pairs of all results: the digits of odd - even are cut straight from the two
+ *                      nodes (the difference is never stored), multiplied into the selector's rows, and the inverse column pass adds the
+ *                      even node and stores the next level's node; N = 1024 (no column pass) runs he355_ntt_inverse and a streaming add
+ *                      instead.  The nodes without a partner are moved by one copy launch per level that has one.
+ * Refused with HE355_E_INVALID_ARGS on the host, before any device is asked for, the output untouched: a CKKS context, L outside 1..L_top,
+ * digit_bits outside 1..63, count == 0 or above 2^24, leaf strides under which two leaves coincide (a stride of 0 along an index that moves, or
+ * colliding indices: he355_bfv_merge's rule), strides that take an operand past 2^60 words, more pairs than one launch's grid holds
+ * (n floor(count / 2) 2 L N / 512 above 2^31 - 1, or n above 2^31 - 1), d_out overlapping the leaves' span (a gap between strided leaves
+ * included) or the selectors.  The leaves and selectors are only read.  Everything is queued on the context's stream.  Scratch: one pool block
+ * of the two alternating node levels, (ceil(count/2) + ceil(count/4)) n ciphertexts (none at m = 1, the first term only at m = 2), and one of the
+ * digit slab of a pass of pairs (bfv_gadget_pass over level 0's pairs with 2E terms, about 4096 digit polynomials) with the pass's sums, 2 L
+ * polynomials per pair, behind it (N = 1024, whose tail runs once per level: the sums of level 0's n floor(count / 2) pairs); both are taken before the first launch, so the allocator's error comes before any launch, and a second
+ * identical call makes no raw allocation. */
+int he355_bfv_select(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t count, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
+                     const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_j, uint64_t *d_out);
 /* ---- RGSW selectors from ONE packed query ciphertext (BFV contexts only, every L in 1..L_top).  An RGSW ciphertext is [2E][2][L][N] words, and a
  * query of the external-product route carries one per index of a later dimension.  As in OnionPIR and Spiral the client instead packs the
  * selectors' gadget components into coefficients of a query ciphertext, the server expands it with he355_bfv_expand and turns each group of E

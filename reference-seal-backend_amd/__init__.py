@@ -46,7 +46,8 @@ class PathStats(C.Structure):
 
 class BfvRouteStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("cut_cols", "cut_stream", "mac_gadget", "mac_plain", "own_cols", "own_stream", "digits_fused",
-                                           "digits_routed", "bytes_fused", "bytes_routed", "passes")] + [("reserved", C.c_uint64 * 5)]
+                                           "digits_routed", "bytes_fused", "bytes_routed", "passes", "select_cols", "select_stream",
+                                           "select_tail_fused", "select_tail_routed")] + [("reserved", C.c_uint64 * 1)]
 
 
 class BfvMultiplyStats(C.Structure):
@@ -145,6 +146,7 @@ def lib():
             "he355_bfv_gadget_decompose_ntt": (i32, [vp, i32, i32, i32, u64, vp, vp]),
             "he355_bfv_rgsw_encrypt": (i32, [vp, i32, i32, u64, vp, u64, u64, vp]),
             "he355_bfv_external_product": (i32, [vp, i32, i32, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
+            "he355_bfv_select": (i32, [vp, i32, i32, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_selector_encrypt": (i32, [vp, i32, i32, u64, u64, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_rgsw_encrypt_secret": (i32, [vp, i32, i32, u64, u64, vp]),
             "he355_bfv_rgsw_from_bfv": (i32, [vp, i32, i32, i32, u64, u64, vp, u64, u64, vp, vp]),
@@ -198,7 +200,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -501,6 +503,12 @@ class Context:
         r ct_stride_r + kappa ct_stride_k, RGSW (r, kappa) at r rg_stride_r + kappa rg_stride_k (rg_stride_r == 0: one selector row for all)"""
         _check(lib().he355_bfv_external_product(self.h, L, digit_bits, n, inner, ct.ptr, ct_stride_r, ct_stride_k, rgsw.ptr, rg_stride_r,
                                                 rg_stride_k, out.ptr))
+
+    def bfv_select(self, L, digit_bits, n, count, ct, ct_stride_r, ct_stride_k, rgsw, rg_stride_r, rg_stride_j, out):
+        """the selection tree: out(r) [n][2][L][N] = the fold of result r's `count` leaves (leaf k at ciphertext r ct_stride_r + k ct_stride_k of ct)
+        under its ceil(log2 count) RGSW bits (bit j at RGSW ciphertext r rg_stride_r + j rg_stride_j; rg_stride_r == 0: one set for all results),
+        level by level node(2p) + RGSW(bit j) [.] (node(2p+1) - node(2p)): decrypts to leaf sum_j b_j 2^j, least significant bit first"""
+        _check(lib().he355_bfv_select(self.h, L, digit_bits, n, count, ct.ptr, ct_stride_r, ct_stride_k, rgsw.ptr, rg_stride_r, rg_stride_j, out.ptr))
 
     def bfv_selector_encrypt(self, L, digit_bits, n, n_sel, first_slot, count, sel, seed, first_index, out):
         """sel [n][n_sel] mod t -> out [n][2][L][N], coefficient form: encrypt_zero(seed, first_index + r) cut to L primes plus, at coefficient

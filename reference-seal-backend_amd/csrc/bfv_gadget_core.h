@@ -77,6 +77,13 @@ HE_HD u64 bfv_selector_value(u64 m, u64 t, int g, int v, u64 inv_pow2, const Mod
 // slot ciphertext c = (selector) E + f -> its row of the RGSW slab [.][2E][2][L][N]: k = 0 the slot's own transform, k = 1 its product with RGSW(s)
 HE_HD u64 bfv_selector_row(u64 c, u32 E, int k) { return (c / E) * 2 * E + (u64)k * E + c % E; }
 
+// ---- the selection tree (he355_bfv_select) --------------------------------------------------------------------------------------------
+// a level folds node 2p and node 2p + 1 into even + RGSW(bit) [.] (odd - even): the word whose digits the cut takes, and the tail's add.  Both are
+// he355_sub / he355_add on canonical residues, so the fused level equals the composition of the public calls bit for bit.
+HE_HD u64 bfv_select_diff(u64 odd, u64 even, u64 qi) { return submod(odd, even, qi); }
+HE_HD u64 bfv_select_diff_digit(u64 odd, u64 even, u64 qi, int g, int v, const ModU64 &mj) { return bfv_gadget_digit(bfv_select_diff(odd, even, qi), g, v, mj); }
+HE_HD u64 bfv_select_add(u64 product, u64 even, u64 qi) { return addmod(product, even, qi); }
+
 // passes of an external product: results per pass so that a pass holds at most about `cap` digit polynomials (terms per result =
 // inner 2 E(L)), never fewer than one result
 HE_HD u64 bfv_gadget_pass(u64 terms, u64 n, u64 cap)

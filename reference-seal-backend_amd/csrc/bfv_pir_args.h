@@ -1,5 +1,5 @@
 // bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, merge, decomposition, the external
-// product and its selectors, database bytes), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
+// product, the selection tree and its selectors, database bytes), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
 // device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands what the check worked out (the digit tables, F,
 // rows, terms, pass, the field width) to DeviceContext as a plan.  What needs the device or its state (keys present, the Galois keys, the
 // key-switch tables) is checked there.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
@@ -181,6 +181,66 @@ inline BfvMergePlan plan_merge(const Params &p, int L, u64 n, u64 count, const u
     if (i1 < i0 || o1 < o0) throw std::invalid_argument(w + ": a range wraps the address space");
     if (i0 < o1 && o0 < i1) throw std::invalid_argument(w + ": `d_out` overlaps the inputs (it may not lie inside their span)");
     return {d, (u64)half, (u64)half * (d > 1 ? 3 : 2)};
+}
+
+// ---- the selection tree (he355_bfv_select) ----------------------------------------------------------------------------------------------
+// Leaf k < count of result r < n is ciphertext r ct_stride_r + k ct_stride_k of `ct`, selector j < depth of result r the RGSW ciphertext
+// r rg_stride_r + j rg_stride_j of `rgsw`, `out` is [n][2][L][N].  depth = ceil(log2 count); c[j]: the nodes per result at level j (c[0] = count,
+// c[j+1] = ceil(c[j] / 2), c[depth] = 1); pairs(j) = n floor(c[j] / 2), the pairs of all results at level j (level 0 has the most); pass: pairs
+// per trip through the digit slab (bfv_gadget_pass over level 0's pairs with terms = rows = 2 E(L)); slab_polys: the residue-polynomial slots
+// ([N] words each) of that block, pass (rows + 2) L: the digits and, behind them, the pass's sums (N = 1024, whose tail runs once per level: the
+// sums of level 0's pairs, (pass rows + 2 pairs(0)) L); node_cts: the ciphertexts of the block that
+// holds the two alternating node levels, n c[1] (depth >= 2) + n c[2] (depth >= 3), at most (ceil(count/2) + ceil(count/4)) n.
+constexpr u64 kSelectMaxCount = (u64)1 << 24; // leaves per result
+constexpr int kSelectMaxDepth = 24;
+struct BfvSelectPlan {
+    BfvDigitTab tab;
+    u32 rows;
+    int depth;
+    u64 n;
+    u64 c[kSelectMaxDepth + 1];
+    u64 pass, slab_polys, node_cts;
+    u64 pairs(int j) const { return n * (c[j] / 2); }
+};
+inline BfvSelectPlan plan_select(const Params &p, int L, int v, u64 n, u64 count, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_j,
+                                 const u64 *out)
+{
+    const std::string w("he355_bfv_select");
+    BfvSelectPlan pl{};
+    pl.tab = gadget_table(p, w, L, v);
+    pl.rows = 2 * (u32)pl.tab.total;
+    if (count < 1 || count > kSelectMaxCount) throw std::invalid_argument(w + ": count must be in 1..2^24");
+    pl.depth = expand_depth(count);
+    pl.n = n;
+    pl.c[0] = count;
+    for (int j = 0; j < pl.depth; ++j) pl.c[j + 1] = (pl.c[j] + 1) / 2;
+    if (!n) return pl;
+    // two leaves at one place: plan_merge's rule
+    if ((count > 1 && !ct_stride_k) || (n > 1 && !ct_stride_r)) throw std::invalid_argument(w + ": a stride of 0 puts two leaves at one place");
+    if (count > 1 && n > 1) {
+        const u64 g = gcd_u64(ct_stride_k, ct_stride_r);
+        if (ct_stride_r / g <= count - 1 && ct_stride_k / g <= n - 1) throw std::invalid_argument(w + ": under these strides two leaves lie at one place");
+    }
+    const size_t ctn = 2 * (size_t)L * p.N;
+    const size_t span = gadget_span_words(w, n, count, ct_stride_r, ct_stride_k, ctn); // refused where the index arithmetic would wrap
+    const size_t rspan = pl.depth ? gadget_span_words(w, n, (u64)pl.depth, rg_stride_r, rg_stride_j, pl.rows * ctn) : 0;
+    // a level's pairs (count == 1: its n copies) as one streaming launch of 2 L N / 512 blocks per ciphertext: the passes launch fewer, the
+    // copy of the nodes without a partner at most n of them
+    const u128 units = (u128)n * (count > 1 ? count / 2 : 1);
+    if (n > 0x7fffffffull || units > 0x7fffffffull / (2 * (u64)L * (p.N / 512))) throw std::invalid_argument(w + ": more pairs than one launch's grid holds");
+    // as integers: a span of up to 2^60 words behind any address may pass the end of the address space, where no pointer may be formed
+    const unsigned long long o0 = (unsigned long long)out, o1 = o0 + 8 * (unsigned long long)(n * ctn);
+    const unsigned long long i0 = (unsigned long long)ct, i1 = i0 + 8 * (unsigned long long)span;
+    const unsigned long long r0 = (unsigned long long)rgsw, r1 = r0 + 8 * (unsigned long long)rspan;
+    if (i1 < i0 || o1 < o0 || r1 < r0) throw std::invalid_argument(w + ": a range wraps the address space");
+    if (i0 < o1 && o0 < i1) throw std::invalid_argument(w + ": `d_out` overlaps the leaves (it may not lie inside their span)");
+    if (rspan && r0 < o1 && o0 < r1) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
+    if (pl.depth) {
+        pl.pass = bfv_gadget_pass(pl.rows, pl.pairs(0), kGadgetPassPolys);
+        pl.slab_polys = (pl.pass * pl.rows + (p.N == 1024 ? pl.pairs(0) : pl.pass) * 2) * L;
+        pl.node_cts = (pl.depth >= 2 ? n * pl.c[1] : 0) + (pl.depth >= 3 ? n * pl.c[2] : 0);
+    }
+    return pl;
 }
 
 // ---- RGSW selectors from ONE packed query ciphertext ---------------------------------------------------------------------------------

@@ -1982,6 +1982,68 @@ public:
         launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
         HIPCHECK(hipGetLastError());
     }
+    // ---- the selection tree (he355_kernels_bfv_gadget.hip; the definition: include/he355.h) ---------------------------------------------------
+    // out(r) = the fold of result r's `count` leaves under its depth RGSW bits: level j turns the c_j nodes of every result into c_(j+1), node'(p) =
+    // node(2p) + RGSW(r, j) [.] (node(2p+1) - node(2p)), the node without a partner copied.  Nodes lie result-major, [n][c_j]: level 0 reads
+    // the caller's leaves through its strides, the later levels alternate between the two halves of one pool block, the last one lands in `out`.
+    // A level is a pass loop over all pairs of all results (pl.pass of them per trip through the second pool block: 2E digit polynomials per
+    // pair and, behind them, the pass's sums -- at N = 1024 the level's): the DIFF cut (bfv_external_product's route rule for that many results), its row pass, one
+    // multiply-accumulate (k_bfv_plain_mac where the level has exactly one pair) into the sums, the inverse row pass in place and the
+    // inverse column pass that adds the even node and stores the next level's node.  N = 1024 has no column pass: ROUTED to
+    // launch_ntt_inverse and a streaming add.  One copy launch per level moves the nodes without a partner.  Both blocks are taken before the
+    // first launch; everything runs on the context's stream.
+    void bfv_select(const BfvSelectPlan &pl, int L, u64 n, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_j, u64 *out)
+    {
+        use();
+        if (!n) return;
+        const size_t N = P.N, LN = (size_t)L * N, ctn = 2 * LN;
+        const int m = pl.depth;
+        if (!m) { // count == 1: result r is its one leaf
+            launch_bfv_select_copy(env_, L, n, 0, ct, ct_stride_r, ct_stride_k, out, 1);
+            HIPCHECK(hipGetLastError());
+            return;
+        }
+        const u32 rows = pl.rows;
+        const PoolBlock nodes = pl.node_cts ? scoped_block((size_t)pl.node_cts * ctn * 8) : PoolBlock();
+        const PoolBlock slab = scoped_block((size_t)pl.slab_polys * N * 8);
+        u64 *half[2] = {nodes ? nodes.get() : nullptr, nodes ? nodes.get() + n * pl.c[1] * ctn : nullptr};
+        u64 *sums = slab.get() + pl.pass * rows * LN;
+        // N = 1024: the sums of a whole LEVEL lie behind the digits and the routed tail runs once per level, not per pass -- the ring is
+        // launch-bound, and per pass the two extra launches lost to the composition at 16 passes (profiles/bfv_select.txt, part 2b)
+        const bool level_tail = env_.logn1 == 0;
+        const u64 *cur = ct;
+        u64 stride_a = ct_stride_r, stride_b = ct_stride_k;
+        for (int j = 0; j < m; ++j) {
+            const u64 group = pl.c[j] / 2, pairs = pl.pairs(j), c_next = pl.c[j + 1];
+            u64 *dst = j == m - 1 ? out : half[j & 1];
+            const u64 *rg = rgsw + (size_t)j * rg_stride_j * rows * ctn;
+            for (u64 p0 = 0; p0 < pairs; p0 += pl.pass) {
+                const u64 c = std::min<u64>(pl.pass, pairs - p0);
+                const bool cols = env_.logn1 != 0 && c * 2 * L * 4 >= kGadgetColsMinBlocks;
+                u64 *psum = sums + (level_tail ? p0 * ctn : 0);
+                ++routes_.passes;
+                ++(cols ? routes_.select_cols : routes_.select_stream);
+                launch_bfv_select_cut(env_, pl.tab, L, group, p0, c, cur, stride_a, stride_b, slab.get(), cols);
+                forward_rows_or_full(cols, poly_view(slab.get(), L, N, L), (u32)(c * rows));
+                // ROUTED as bfv_external_product routes one result: a level of exactly one pair is k_bfv_plain_mac's 1 x 1 form
+                const bool plain = pairs == 1;
+                ++(plain ? routes_.mac_plain : routes_.mac_gadget);
+                if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, rows, rg, 1, 1, slab.get(), 1, 1, psum);
+                else launch_bfv_select_mac(env_, L, group, p0, c, rows, slab.get(), rg, rg_stride_r, psum);
+                if (level_tail) continue;
+                launch_rows_inv(env_, poly_view(sums, L, N, L), (u32)(c * 2));
+                launch_bfv_select_tail(env_, L, group, p0, c, sums, cur, stride_a, stride_b, dst, c_next);
+            }
+            if (level_tail) {
+                launch_ntt_inverse(env_, poly_view(sums, L, N, L), (u32)(pairs * 2));
+                launch_bfv_select_tail(env_, L, group, 0, pairs, sums, cur, stride_a, stride_b, dst, c_next);
+            }
+            ++(level_tail ? routes_.select_tail_routed : routes_.select_tail_fused);
+            if (pl.c[j] & 1) launch_bfv_select_copy(env_, L, n, group, cur, stride_a, stride_b, dst, c_next);
+            cur = dst; stride_a = c_next; stride_b = 1;
+        }
+        HIPCHECK(hipGetLastError());
+    }
     // ---- RGSW selectors from ONE packed query ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) -------
     // sel [n][n_sel] mod t -> out [n][2][L][N], coefficient form: he355_encrypt_zero(seed, first_index + r) cut to the first L primes plus the planted
     // selectors.
@@ -2866,6 +2928,15 @@ int he355_bfv_rgsw_from_bfv(he355_ctx *c, int L, int digit_bits, int key_bits, u
         need_bfv(c, "he355_bfv_rgsw_from_bfv");
         const BfvFromBfvPlan pl = plan_from_bfv(*c->params, L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
         dev(c).bfv_rgsw_from_bfv(pl, L, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
+    });
+}
+int he355_bfv_select(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t count, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k, const uint64_t *d_rgsw,
+                     uint64_t rg_stride_r, uint64_t rg_stride_j, uint64_t *d_out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_select");
+        const BfvSelectPlan pl = plan_select(*c->params, L, digit_bits, n, count, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_j, d_out);
+        dev(c).bfv_select(pl, L, n, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_j, d_out);
     });
 }
 int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,

@@ -218,6 +218,7 @@ HE355_FWD(behz_cols_lds_limit)
 HE355_FWD(launch_behz_extend_cols)
 HE355_FWD(launch_behz_tensor_inv)
 HE355_FWD(launch_rows_fwd)
+HE355_FWD(launch_rows_inv)
 HE355_FWD(launch_behz_cols_floor_sk)
 HE355_FWD(launch_behz_rows_tensor)
 HE355_FWD(launch_cols_fwd)
@@ -255,6 +256,10 @@ HE355_FWD(launch_bfv_gadget_cut_own)
 HE355_FWD(launch_bfv_gadget_mac_own)
 HE355_FWD(launch_bfv_selector_plant)
 HE355_FWD(launch_bfv_secret_plain)
+HE355_FWD(launch_bfv_select_cut)
+HE355_FWD(launch_bfv_select_mac)
+HE355_FWD(launch_bfv_select_tail)
+HE355_FWD(launch_bfv_select_copy)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -2591,6 +2591,12 @@ void launch_rows_fwd(const KernelEnv &env, const PolyView &v, u32 n_items) // th
     if (!jobs) return;
     hipLaunchKernelGGL(k_rows_fwd, dim3(grid_for(jobs, kWaves)), dim3(kBlock), 0, env.stream, v, env.primes, jobs, env.logn1, env.logn1 > 0 ? 1 : 0);
 }
+void launch_rows_inv(const KernelEnv &env, const PolyView &v, u32 n_items) // the row half of launch_ntt_inverse (NTT form -> raw; N = 1024: coefficients)
+{
+    const u64 jobs = ((u64)n_items * v.polys_per_item) << env.logn1;
+    if (!jobs) return;
+    hipLaunchKernelGGL(k_rows_inv, dim3(grid_for(jobs, kWaves)), dim3(kBlock), 0, env.stream, v, env.primes, jobs, env.logn1);
+}
 void launch_cols_fwd(const KernelEnv &env, const PolyView &v, u32 n_items) // the column half of launch_ntt_forward (canonical -> raw)
 {
     const u64 polys = (u64)n_items * v.polys_per_item;

@@ -1,7 +1,7 @@
 // he355_kernels_bfv_gadget.hip -- the BFV external product RGSW(m) [.] BFV(mu) -> BFV(m mu): he355_bfv_gadget_decompose_ntt,
-// he355_bfv_rgsw_encrypt, he355_bfv_external_product; and the selectors a client packs into one query ciphertext:
+// he355_bfv_rgsw_encrypt, he355_bfv_external_product; the selection tree he355_bfv_select; and the selectors a client packs into one query ciphertext:
 // he355_bfv_selector_encrypt, he355_bfv_rgsw_encrypt_secret, he355_bfv_rgsw_from_bfv.  The per-coefficient arithmetic is bfv_gadget_core.h and bfv_mac_core.h
-// (host-compilable: tests/csim/sim_bfv_gadget.cpp runs the same text on the CPU).
+// (host-compilable: tests/csim/sim_bfv_gadget.cpp and sim_bfv_select.cpp run the same text on the CPU).
 //
 //   k_bfv_gadget_cols_fwd<LOGN1>   N >= 2048: the forward COLUMN pass of every digit polynomial of one ciphertext residue.  A block owns a
 //                        quarter of the 1024 columns of one residue polynomial (c, k, i); a lane owns one stride-1024 column and loads its
@@ -32,6 +32,15 @@
 //                        encryption of zero cut to L primes and, in polynomial 0 at a coefficient that is a slot of a digit of prime i,
 //                        bfv_selector_value of the slot's selector.
 //   k_bfv_secret_plain   the secret key's coefficients under prime 0 (0, 1, q_0 - 1) -> 0, 1, t - 1.
+// he355_bfv_select (one level = a pass loop over all pairs of all results) has kernel bodies of its own: as template forms of the kernels above
+// they changed the OWN instantiations' registers (profiles/bfv_select.txt), and those must compile what they compiled before:
+//   k_bfv_select_cols_fwd<LOGN1>, k_bfv_select_spread   the cut of odd - even: a lane loads the two nodes' words from their own addresses
+//                        and cuts the digits of submod(odd, even, q_i); the difference is never stored.
+//   k_bfv_select_mac     k_bfv_gadget_mac with inner = 1 whose "result" is a pair: pair c takes the selector row of result c / group, so the
+//                        blocks that share a row stay neighbours in the grid.
+//   k_bfv_select_cols_inv<LOGN1>  k_cols_inv's lane program on the sums' raw rows; after to_canon it adds the even node's word and stores the
+//                        next level's node.  k_bfv_select_add: the same add for N = 1024, whose sums launch_ntt_inverse leaves as
+//                        coefficients.  k_bfv_select_copy: the node without a partner, one launch per level that has one.
 // Launches: kernel_common.inc's dispatch_logn1 picks the LOGN1 instantiation, streaming_grid / grid_blocks size and bound the grids.
 #include <hip/hip_runtime.h>
 
@@ -218,6 +227,197 @@ __global__ void __launch_bounds__(kBlock) k_bfv_gadget_mac(BfvGadgetMacArgs A, c
     po[half] = make_ulonglong2(bfv_mac_reduce(acc[1][0], m), bfv_mac_reduce(acc[1][1], m));
 }
 
+// he355_bfv_select: the batch is PAIRS.  Residue polynomial p of the batch belongs to pair c = first + p / (2 L) = (a, b) = (c / n_b, c % n_b), whose
+// even node is the ciphertext at index a stride_a + 2 b stride_b and whose odd node lies stride_b behind it: -> the even node's words, and the
+// distance in words to the odd node's
+__device__ __forceinline__ const u64 *select_even(const BfvGadgetCutArgs &A, u64 p, u64 &to_odd)
+{
+    const u64 polys = 2 * (u64)A.L, c = A.first + p / polys, rest = p % polys;
+    const u64 at = (c / A.n_b) * A.stride_a + 2 * (c % A.n_b) * A.stride_b;
+    to_odd = (A.stride_b * polys) << A.logN;
+    return A.in + ((at * polys + rest) << A.logN);
+}
+// The DIFF form of k_bfv_gadget_cols_fwd, a kernel body of its own (the shared template changed the OWN instantiations' registers:
+// profiles/bfv_select.txt): a lane loads its words of the odd and of the even node from their own addresses and cuts the digits of odd - even;
+// the difference is never stored.  The rest is k_bfv_gadget_cols_fwd's text.
+template <int LOGN1>
+__global__ void __launch_bounds__(kBlock) k_bfv_select_cols_fwd(BfvGadgetCutArgs A, const PrimeDev *primes)
+{
+    constexpr int N1 = 1 << LOGN1;
+    const u64 p = blockIdx.x >> 2; // residue polynomial (pair 2 + k) L + i
+    const int col = ((blockIdx.x & 3) << 8) | threadIdx.x;
+    const int i = (int)(p % (u64)A.L), E = A.tab.D[i], v = A.tab.w;
+    const u64 f0 = bfv_gadget_first(A.tab, 2, p), qi = primes[i].q;
+    u64 to_odd;
+    const u64 *even = select_even(A, p, to_odd), *odd = even + to_odd;
+    u64 w[N1];
+#pragma unroll
+    for (int a = 0; a < N1; ++a) w[a] = bfv_select_diff(odd[(a << kRowLog) + col], even[(a << kRowLog) + col], qi);
+    for (int g = 0; g < E; ++g) {
+        for (int j = 0; j < A.L; ++j) {
+            const PrimeDev &P = primes[j];
+            const ModU64 mj = make_modu(P);
+            u64 *dst = A.out + (((f0 + g) * A.L + j) << (LOGN1 + kRowLog));
+            if (P.f64) {
+                const ArF64 ar = make_ar(P, (ArF64 *)nullptr);
+                double x[N1];
+#pragma unroll
+                for (int a = 0; a < N1; ++a) x[a] = ar.from_canon(bfv_gadget_digit(w[a], g, v, mj));
+                col_fwd<ArF64, LOGN1>(ar, x, ctw(P.fwd));
+#pragma unroll
+                for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = ar.to_raw(x[a]);
+            } else {
+                const ArU64 ar = make_ar(P, (ArU64 *)nullptr);
+                u64 x[N1];
+#pragma unroll
+                for (int a = 0; a < N1; ++a) x[a] = bfv_gadget_digit(w[a], g, v, mj);
+                col_fwd<ArU64, LOGN1>(ar, x, ctw(P.fwd));
+#pragma unroll
+                for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = x[a];
+            }
+        }
+    }
+}
+
+// the DIFF form of k_bfv_gadget_spread: two 16-byte loads, the digits of odd - even under every output prime
+__global__ void __launch_bounds__(kBlock) k_bfv_select_spread(BfvGadgetCutArgs A, const PrimeDev *primes)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (A.logN - 1), e2 = gid & (((u64)1 << (A.logN - 1)) - 1);
+    if (p >= A.n_polys) return;
+    const int i = (int)(p % (u64)A.L), E = A.tab.D[i], v = A.tab.w;
+    const u64 f0 = bfv_gadget_first(A.tab, 2, p), qi = primes[i].q;
+    u64 to_odd;
+    const u64 *even = select_even(A, p, to_odd);
+    const ulonglong2 x = reinterpret_cast<const ulonglong2 *>(even)[e2], y = reinterpret_cast<const ulonglong2 *>(even + to_odd)[e2];
+    for (int g = 0; g < E; ++g)
+        for (int j = 0; j < A.L; ++j) {
+            const ModU64 mj = make_modu(primes[j]);
+            reinterpret_cast<ulonglong2 *>(A.out + (((f0 + g) * A.L + j) << A.logN))[e2] =
+                make_ulonglong2(bfv_select_diff_digit(y.x, x.x, qi, g, v, mj), bfv_select_diff_digit(y.y, x.y, qi, g, v, mj));
+        }
+}
+
+// k_bfv_gadget_mac's plain form with inner = 1 for he355_bfv_select, a kernel body of its own: the "result" is pair `first` + r of a level,
+// digits [pair][rows][L][N], and its RGSW ciphertext is the one at index ((first + r) / group) rg_stride_r, group = the pairs per result --
+// the pairs of one result are neighbours in the grid, so the blocks that read the same selector row words still are.  out [pair][2][L][N].
+struct BfvSelectMacArgs {
+    const u64 *dig, *rgsw;
+    u64 *out;
+    u64 n, rg_stride_r, first, group;
+    u32 rows, pairs_blocks;
+    int L, logN;
+    u32 run[kMaxPrimes];
+};
+__global__ void __launch_bounds__(kBlock) k_bfv_select_mac(BfvSelectMacArgs A, const PrimeDev *primes)
+{
+    const u64 r = blockIdx.x % A.n;
+    const u32 rest = (u32)(blockIdx.x / A.n), eb = rest % A.pairs_blocks;
+    const int j = (int)(rest / A.pairs_blocks);
+    const u64 e2 = (u64)eb * kBlock + threadIdx.x;
+    const u64 N = (u64)1 << A.logN, LN = (u64)A.L << A.logN, half = LN / 2;
+    const ModU64 m = bfv_modu(primes[j]);
+    const u64 run = A.run[j];
+    const ulonglong2 *pd = reinterpret_cast<const ulonglong2 *>(A.dig + r * A.rows * LN + (u64)j * N) + e2;
+    const ulonglong2 *row = reinterpret_cast<const ulonglong2 *>(A.rgsw + ((A.first + r) / A.group) * A.rg_stride_r * A.rows * 2 * LN + (u64)j * N) + e2;
+
+    u128 acc[2][2] = {{0, 0}, {0, 0}}; // [polynomial][coefficient]
+    u64 left = run;
+    u32 f = 0;
+    while (f < A.rows) {
+        if (!left) { // the sums' residues start the next run as one term
+            bfv_mac_fold(acc[0][0], m); bfv_mac_fold(acc[0][1], m);
+            bfv_mac_fold(acc[1][0], m); bfv_mac_fold(acc[1][1], m);
+            left = run - 1;
+        }
+        const u32 end = A.rows - f < left ? A.rows : f + (u32)left;
+        left -= end - f;
+#pragma unroll 2
+        for (; f < end; ++f) {
+            const ulonglong2 d = pd[f * half], a = row[f * LN], b = row[f * LN + half];
+            bfv_mac_add(acc[0][0], a.x, d.x);
+            bfv_mac_add(acc[0][1], a.y, d.y);
+            bfv_mac_add(acc[1][0], b.x, d.x);
+            bfv_mac_add(acc[1][1], b.y, d.y);
+        }
+    }
+    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(A.out + r * 2 * LN + (u64)j * N) + e2;
+    po[0] = make_ulonglong2(bfv_mac_reduce(acc[0][0], m), bfv_mac_reduce(acc[0][1], m));
+    po[half] = make_ulonglong2(bfv_mac_reduce(acc[1][0], m), bfv_mac_reduce(acc[1][1], m));
+}
+
+// The tail of a level of he355_bfv_select and its pass-through copy.  Pair c = first + (the pass's pair index) is (r, b) = (c / group, c % group):
+// its even node is the ciphertext at index r stride_a + 2 b stride_b of `nodes`, its sums are `sums` [pair of the pass][2][L][N], and the next
+// level's node (r, b) is the ciphertext at index r out_stride + b of `out`.
+struct BfvSelectTailArgs {
+    const u64 *sums, *nodes;
+    u64 *out;
+    u64 first, group, stride_a, stride_b, out_stride;
+    u64 n_polys; // residue polynomials of the launch: pairs 2 L (the copy: n 2 L)
+    int L, logN;
+};
+// residue polynomial p = (pair of the pass) 2 L + (k L + i) -> where its even node's and its output's words start
+__device__ __forceinline__ void select_tail_at(const BfvSelectTailArgs &A, u64 p, const u64 *&even, u64 *&dst)
+{
+    const u64 polys = 2 * (u64)A.L, c = A.first + p / polys, rest = p % polys, r = c / A.group, b = c % A.group;
+    even = A.nodes + (((r * A.stride_a + 2 * b * A.stride_b) * polys + rest) << A.logN);
+    dst = A.out + (((r * A.out_stride + b) * polys + rest) << A.logN);
+}
+// k_cols_inv's lane program on the sums' raw rows; after to_canon the even node's word is added and the next level's node stored
+template <int LOGN1>
+__global__ void __launch_bounds__(kBlock) k_bfv_select_cols_inv(BfvSelectTailArgs A, const PrimeDev *primes)
+{
+    constexpr int N1 = 1 << LOGN1;
+    const u64 p = blockIdx.x >> 2;
+    const int col = ((blockIdx.x & 3) << 8) | threadIdx.x;
+    const PrimeDev &P = primes[(int)(p % (u64)A.L)];
+    const u64 *src = A.sums + (p << (LOGN1 + kRowLog)), *even;
+    u64 *dst;
+    select_tail_at(A, p, even, dst);
+    if (P.f64) {
+        const ArF64 ar = make_ar(P, (ArF64 *)nullptr);
+        double x[N1];
+#pragma unroll
+        for (int a = 0; a < N1; ++a) x[a] = ar.from_raw(src[(a << kRowLog) + col]);
+        col_inv<ArF64, LOGN1>(ar, x, ctw(P.inv), P.inv_w0_scaled);
+#pragma unroll
+        for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = bfv_select_add(ar.to_canon(x[a]), even[(a << kRowLog) + col], P.q);
+    } else {
+        const ArU64 ar = make_ar(P, (ArU64 *)nullptr);
+        u64 x[N1];
+#pragma unroll
+        for (int a = 0; a < N1; ++a) x[a] = src[(a << kRowLog) + col];
+        col_inv<ArU64, LOGN1>(ar, x, ctw(P.inv), P.inv_w0_scaled);
+#pragma unroll
+        for (int a = 0; a < N1; ++a) dst[(a << kRowLog) + col] = bfv_select_add(ar.to_canon(x[a]), even[(a << kRowLog) + col], P.q);
+    }
+}
+// N = 1024 (no column pass): the sums are coefficients already (launch_ntt_inverse); streaming, a lane owns two coefficients.  k_addsub's
+// indexer cannot say "node 2 b of result r", so the add is this kernel's
+__global__ void __launch_bounds__(kBlock) k_bfv_select_add(BfvSelectTailArgs A, const PrimeDev *primes)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (A.logN - 1), e2 = gid & (((u64)1 << (A.logN - 1)) - 1);
+    if (p >= A.n_polys) return;
+    const u64 q = primes[(int)(p % (u64)A.L)].q;
+    const u64 *even;
+    u64 *dst;
+    select_tail_at(A, p, even, dst);
+    const ulonglong2 x = reinterpret_cast<const ulonglong2 *>(A.sums + (p << A.logN))[e2], y = reinterpret_cast<const ulonglong2 *>(even)[e2];
+    reinterpret_cast<ulonglong2 *>(dst)[e2] = make_ulonglong2(bfv_select_add(x.x, y.x, q), bfv_select_add(x.y, y.y, q));
+}
+// the node without a partner (node 2 group of every result, where the level has an odd number of nodes) -> node `group` of the next level;
+// group == 0: a level of one node, he355_bfv_select's count == 1
+__global__ void __launch_bounds__(kBlock) k_bfv_select_copy(BfvSelectTailArgs A)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (A.logN - 1), e2 = gid & (((u64)1 << (A.logN - 1)) - 1);
+    if (p >= A.n_polys) return;
+    const u64 polys = 2 * (u64)A.L, r = p / polys, rest = p % polys;
+    reinterpret_cast<ulonglong2 *>(A.out + (((r * A.out_stride + A.group) * polys + rest) << A.logN))[e2] =
+        reinterpret_cast<const ulonglong2 *>(A.nodes + (((r * A.stride_a + 2 * A.group * A.stride_b) * polys + rest) << A.logN))[e2];
+}
+
 // zero [n_rows][2][L_in][N] (encryptions of zero, coefficient form), plain [n][N] mod t -> out [n_rows][2][L][N], n_rows = n 2 E(L)
 struct BfvPlantArgs {
     const u64 *zero, *plain;
@@ -360,6 +560,62 @@ void launch_bfv_gadget_mac_own(const KernelEnv &env, int L, u64 first, u64 count
 {
     if (!own_E) throw std::invalid_argument("he355_bfv_rgsw_from_bfv: no selectors");
     gadget_mac(env, L, count, 1, rows, dig, key, 0, 1, out, first, own_E);
+}
+// ---- he355_bfv_select: one pass of one level ----------------------------------------------------------------------------------------------
+void launch_bfv_select_cut(const KernelEnv &env, const BfvDigitTab &tab, int L, u64 group, u64 first, u64 count, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, bool cols)
+{
+    if (!count) return;
+    if (!group) throw std::invalid_argument("he355_bfv_select: a level without pairs has no cut");
+    BfvGadgetCutArgs A = cut_args(env, tab, L, 2, 1, count, nodes, stride_a, stride_b, out); // n_polys of `count` pairs
+    A.n_b = group; A.first = first;
+    if (env.logn1 == 0 && cols) throw std::invalid_argument("he355_bfv_select: N = 1024 has no column pass");
+    if (!cols) {
+        hipLaunchKernelGGL(k_bfv_select_spread, dim3(streaming_grid(A.n_polys, A.logN, "he355_bfv_select")), dim3(kBlock), 0, env.stream, A, env.primes);
+        return;
+    }
+    const dim3 g(grid_blocks(A.n_polys * 4, "he355_bfv_select")), b(kBlock);
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL((k_bfv_select_cols_fwd<decltype(n1)::value>), g, b, 0, env.stream, A, env.primes); });
+}
+void launch_bfv_select_mac(const KernelEnv &env, int L, u64 group, u64 first, u64 count, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 *out)
+{
+    if (!count) return;
+    if (!group || L < 1 || L > kMaxPrimes || rows < 2) throw std::invalid_argument("he355_bfv_select: level, rows or pairs out of range");
+    BfvSelectMacArgs A{};
+    A.dig = dig; A.rgsw = rgsw; A.out = out; A.n = count; A.rg_stride_r = rg_stride_r; A.first = first; A.group = group;
+    A.rows = rows; A.L = L; A.logN = env.logn1 + kRowLog;
+    A.pairs_blocks = (u32)((((u64)1 << A.logN) / 2) / kBlock);
+    for (int j = 0; j < L; ++j) {
+        A.run[j] = (u32)bfv_mac_run(env.prime_q[j]);
+        if (A.run[j] < 2) throw std::invalid_argument("he355_bfv_select: prime too wide for a 128-bit sum");
+    }
+    hipLaunchKernelGGL(k_bfv_select_mac, dim3(grid_blocks(gadget_mac_blocks(env, L, count), "he355_bfv_select", "pairs")), dim3(kBlock), 0, env.stream, A, env.primes);
+}
+static BfvSelectTailArgs select_tail_args(const KernelEnv &env, int L, u64 group, u64 first, u64 items, const u64 *sums, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out,
+                                          u64 out_stride)
+{
+    if (L < 1 || L > kMaxPrimes) throw std::invalid_argument("he355_bfv_select: level out of range");
+    BfvSelectTailArgs A{};
+    A.sums = sums; A.nodes = nodes; A.out = out; A.first = first; A.group = group; A.stride_a = stride_a; A.stride_b = stride_b; A.out_stride = out_stride;
+    A.n_polys = items * 2 * L; A.L = L; A.logN = env.logn1 + kRowLog;
+    return A;
+}
+void launch_bfv_select_tail(const KernelEnv &env, int L, u64 group, u64 first, u64 count, const u64 *sums, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride)
+{
+    if (!count) return;
+    if (!group) throw std::invalid_argument("he355_bfv_select: a level without pairs has no tail");
+    const BfvSelectTailArgs A = select_tail_args(env, L, group, first, count, sums, nodes, stride_a, stride_b, out, out_stride);
+    if (env.logn1 == 0) {
+        hipLaunchKernelGGL(k_bfv_select_add, dim3(streaming_grid(A.n_polys, A.logN, "he355_bfv_select")), dim3(kBlock), 0, env.stream, A, env.primes);
+        return;
+    }
+    const dim3 g(grid_blocks(A.n_polys * 4, "he355_bfv_select")), b(kBlock);
+    dispatch_logn1(env.logn1, [&](auto n1) { hipLaunchKernelGGL((k_bfv_select_cols_inv<decltype(n1)::value>), g, b, 0, env.stream, A, env.primes); });
+}
+void launch_bfv_select_copy(const KernelEnv &env, int L, u64 n, u64 group, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride)
+{
+    if (!n) return;
+    const BfvSelectTailArgs A = select_tail_args(env, L, group, 0, n, nullptr, nodes, stride_a, stride_b, out, out_stride);
+    hipLaunchKernelGGL(k_bfv_select_copy, dim3(streaming_grid(A.n_polys, A.logN, "he355_bfv_select")), dim3(kBlock), 0, env.stream, A);
 }
 void launch_bfv_rgsw_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, const u64 *zero, const u64 *plain, u64 t, u64 *out)
 {

@@ -67,6 +67,7 @@ bool launch_behz_extend_cols(const KernelEnv &env, const BehzDev &bz, const Behz
 bool launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_ops, u64 op_offset, const u64 *eq, const u64 *ebsk, u64 *dq,
                             u64 *ds);
 void launch_rows_fwd(const KernelEnv &env, const PolyView &v, u32 n_items); // row half of the forward transform, in place
+void launch_rows_inv(const KernelEnv &env, const PolyView &v, u32 n_items); // row half of the inverse transform, in place (N = 1024: all of it)
 bool launch_behz_cols_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *dq, const u64 *ds, u64 *out);
 // BEHZ steps (3)-(5) on rows, fused: x [n*4][Lx][N] after launch_cols_fwd -> forward row pass of a0, a1, b0, b1, dyadic tensor, inverse row
 // pass -> d [n*3][Lx][N] ready for launch_cols_inv (one block = the four rows of one (op, residue, row); no HBM round trip between them)
@@ -197,3 +198,15 @@ void launch_bfv_gadget_mac_own(const KernelEnv &env, int L, u64 first, u64 count
 void launch_bfv_selector_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, int L_in, u64 n, u64 n_sel, u64 first_slot, int d, const u64 *zero, const u64 *sel, u64 t, u64 *out);
 // s [N]: the secret key's coefficients under prime 0 (0, 1, q_0 - 1), in place -> mod t (0, 1, t - 1)
 void launch_bfv_secret_plain(const KernelEnv &env, u64 *s, u64 t);
+// ---- the BFV selection tree (he355_bfv_select; he355_kernels_bfv_gadget.hip; arithmetic: bfv_gadget_core.h) --------------------------------------
+// One pass of one level.  Pair c = first + (index in the pass) of the level is (r, b) = (c / group, c % group), group = the pairs per result; its
+// even node is the ciphertext ([2][L][N], coefficient form) at index r stride_a + 2 b stride_b of `nodes`, its odd node stride_b behind it.
+// The cut of odd - even into out [count][2E][L][N], as launch_bfv_gadget_cut (cols: raw columns, launch_rows_fwd finishes; else coefficient form)
+void launch_bfv_select_cut(const KernelEnv &env, const BfvDigitTab &tab, int L, u64 group, u64 first, u64 count, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, bool cols);
+// out[pair] = sum_(f < rows) dig[pair][f] (.) row f of the RGSW ciphertext at index r rg_stride_r of `rgsw`, canonical NTT form, out [count][2][L][N]
+void launch_bfv_select_mac(const KernelEnv &env, int L, u64 group, u64 first, u64 count, u32 rows, const u64 *dig, const u64 *rgsw, u64 rg_stride_r, u64 *out);
+// node (r, b) of the next level, the ciphertext at index r out_stride + b of `out`, = even node + sums[pair].  N >= 2048: sums are the raw rows
+// launch_rows_inv leaves, and the launch is the inverse column pass with the add behind it; N = 1024: sums are coefficients, a streaming add
+void launch_bfv_select_tail(const KernelEnv &env, int L, u64 group, u64 first, u64 count, const u64 *sums, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride);
+// node 2 group of every result r < n (the one without a partner) -> node `group` of the next level; group = 0: a level of one node
+void launch_bfv_select_copy(const KernelEnv &env, int L, u64 n, u64 group, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride);
