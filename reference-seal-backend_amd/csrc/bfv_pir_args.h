@@ -18,9 +18,26 @@ namespace he355 {
 
 // do the u64 ranges [p, p + np) and [q, q + nq) share an element?
 inline bool ranges_overlap(const u64 *p, size_t np, const u64 *q, size_t nq) { return np && nq && p < q + nq && q < p + np; }
+// [base, base + bytes) as integers: a span of up to 2^60 words behind any address may pass the end of the address space, where no pointer may be
+// formed, and such a range is refused
+struct AddrRange {
+    unsigned long long lo, hi;
+    bool overlaps(const AddrRange &o) const { return lo < hi && o.lo < o.hi && lo < o.hi && o.lo < hi; }
+};
+inline AddrRange byte_range(const std::string &w, const void *base, unsigned long long bytes)
+{
+    const unsigned long long lo = (unsigned long long)base;
+    if (lo + bytes < lo) throw std::invalid_argument(w + ": a range wraps the address space");
+    return {lo, lo + bytes};
+}
+inline AddrRange word_range(const std::string &w, const u64 *base, u64 words) { return byte_range(w, base, 8 * (unsigned long long)words); }
 inline void check_size(int size, int lo, int hi) // "ciphertext size must be 1..3" / "... 2 or 3"
 {
     if (size < lo || size > hi) throw std::invalid_argument("ciphertext size must be " + std::to_string(lo) + (hi == lo + 1 ? " or " : "..") + std::to_string(hi));
+}
+inline void check_level(const Params &p, const std::string &w, int L)
+{
+    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
 }
 // the first L primes of the chain (1 <= L <= L_top), as the table builders take them
 inline std::array<u64, kMaxPrimes> level_primes(const Params &p, int L)
@@ -33,7 +50,7 @@ inline std::array<u64, kMaxPrimes> level_primes(const Params &p, int L)
 // ---- monomial multiply and oblivious query expansion ------------------------------------------------------------------------------
 inline void check_monomial_args(const Params &p, int L, int size, u32 e)
 {
-    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_multiply_monomial: level out of range");
+    check_level(p, "he355_bfv_multiply_monomial", L);
     check_size(size, 1, 3);
     if (e >= 2 * p.N) throw std::invalid_argument("he355_bfv_multiply_monomial: the exponent must be below 2N (X^N = -1)");
 }
@@ -49,7 +66,7 @@ struct BfvExpandPlan {
 };
 inline BfvExpandPlan plan_expand(const Params &p, int L, u64 count)
 {
-    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument("he355_bfv_expand: level out of range");
+    check_level(p, "he355_bfv_expand", L);
     if (count < 1 || count > p.N) throw std::invalid_argument("he355_bfv_expand: count must be in 1..N");
     return {expand_depth(count)};
 }
@@ -65,7 +82,8 @@ inline BfvDigitTab digit_table(const Params &p, int L) { return bfv_digit_table(
 inline BfvDigitPlan plan_digits(const Params &p, const char *what, int L, int size, u64 n, const u64 *ct, const u64 *plain, bool ntt = false, int L_out = 0)
 {
     const std::string w(what);
-    if (L < 1 || (size_t)L > p.Ltop || L_out < (ntt ? 1 : 0) || (size_t)L_out > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    check_level(p, w, L);
+    if (L_out < (ntt ? 1 : 0) || (size_t)L_out > p.Ltop) throw std::invalid_argument(w + ": level out of range");
     check_size(size, 1, 3);
     if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
     const BfvDigitTab tab = digit_table(p, L);
@@ -79,7 +97,7 @@ constexpr u64 kGadgetPassPolys = 4096; // digit polynomials one pass of he355_bf
 inline u64 gadget_poly_blocks(const Params &p, bool cols) { return cols && p.N > 1024 ? 4 : p.N / 512; } // blocks per residue polynomial
 inline BfvDigitTab gadget_table(const Params &p, const std::string &w, int L, int v)
 {
-    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    check_level(p, w, L);
     if (!bfv_gadget_width_ok(v)) throw std::invalid_argument(w + ": digit_bits must be 1..63");
     return bfv_gadget_table(level_primes(p, L).data(), L, v);
 }
@@ -157,29 +175,32 @@ inline u64 gcd_u64(u64 a, u64 b)
     while (b) { const u64 t = a % b; a = b; b = t; }
     return a;
 }
+// two `noun` (item k < count of result r < n lies at k stride_k + r stride_r) at one place: a stride of 0 along an index that moves, or
+// k stride_k + r stride_r = k' stride_k + r' stride_r, which has a solution exactly when the smallest one, k - k' = stride_r / g and
+// r' - r = stride_k / g (g the strides' gcd), lies inside the extents
+inline void check_strides_apart(const std::string &w, const char *noun, u64 n, u64 count, u64 stride_r, u64 stride_k)
+{
+    if ((count > 1 && !stride_k) || (n > 1 && !stride_r)) throw std::invalid_argument(w + ": a stride of 0 puts two " + noun + " at one place");
+    if (count > 1 && n > 1) {
+        const u64 g = gcd_u64(stride_k, stride_r);
+        if (stride_r / g <= count - 1 && stride_k / g <= n - 1) throw std::invalid_argument(w + ": under these strides two " + noun + " lie at one place");
+    }
+}
 inline BfvMergePlan plan_merge(const Params &p, int L, u64 n, u64 count, const u64 *in, u64 stride_k, u64 stride_r, const u64 *out)
 {
     const std::string w("he355_bfv_merge");
-    if (L < 1 || (size_t)L > p.Ltop) throw std::invalid_argument(w + ": level out of range");
+    check_level(p, w, L);
     if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
     const int d = expand_depth(count);
     if (!n) return {d, 0, 0};
-    // two inputs at one place: a stride of 0 along an index that moves, or k stride_k + r stride_r = k' stride_k + r' stride_r, which has a
-    // solution exactly when the smallest one, k - k' = stride_r / g and r' - r = stride_k / g (g the strides' gcd), lies inside the extents
-    if ((count > 1 && !stride_k) || (n > 1 && !stride_r)) throw std::invalid_argument(w + ": a stride of 0 puts two inputs at one place");
-    if (count > 1 && n > 1) {
-        const u64 g = gcd_u64(stride_k, stride_r);
-        if (stride_r / g <= count - 1 && stride_k / g <= n - 1) throw std::invalid_argument(w + ": under these strides two inputs lie at one place");
-    }
+    check_strides_apart(w, "inputs", n, count, stride_r, stride_k);
     const size_t ctn = 2 * (size_t)L * p.N;
     const size_t span = gadget_span_words(w, n, count, stride_r, stride_k, ctn); // checked: refused where the index arithmetic would wrap
     const u64 blocks_per_ct = 2 * (u64)L * (p.N / 512);
     const u128 half = d ? (u128)n << (d - 1) : 0;
     if (n > 0x7fffffffull || half > 0x7fffffffull / blocks_per_ct) throw std::invalid_argument(w + ": too many polynomials for one launch");
-    // as integers: a span of up to 2^60 words behind any address may pass the end of the address space, where no pointer may be formed
-    const unsigned long long i0 = (unsigned long long)in, i1 = i0 + 8 * (unsigned long long)span, o0 = (unsigned long long)out, o1 = o0 + 8 * (unsigned long long)(n * ctn);
-    if (i1 < i0 || o1 < o0) throw std::invalid_argument(w + ": a range wraps the address space");
-    if (i0 < o1 && o0 < i1) throw std::invalid_argument(w + ": `d_out` overlaps the inputs (it may not lie inside their span)");
+    const AddrRange src = word_range(w, in, span), dst = word_range(w, out, n * ctn);
+    if (dst.overlaps(src)) throw std::invalid_argument(w + ": `d_out` overlaps the inputs (it may not lie inside their span)");
     return {d, (u64)half, (u64)half * (d > 1 ? 3 : 2)};
 }
 
@@ -215,12 +236,7 @@ inline BfvSelectPlan plan_select(const Params &p, int L, int v, u64 n, u64 count
     pl.c[0] = count;
     for (int j = 0; j < pl.depth; ++j) pl.c[j + 1] = (pl.c[j] + 1) / 2;
     if (!n) return pl;
-    // two leaves at one place: plan_merge's rule
-    if ((count > 1 && !ct_stride_k) || (n > 1 && !ct_stride_r)) throw std::invalid_argument(w + ": a stride of 0 puts two leaves at one place");
-    if (count > 1 && n > 1) {
-        const u64 g = gcd_u64(ct_stride_k, ct_stride_r);
-        if (ct_stride_r / g <= count - 1 && ct_stride_k / g <= n - 1) throw std::invalid_argument(w + ": under these strides two leaves lie at one place");
-    }
+    check_strides_apart(w, "leaves", n, count, ct_stride_r, ct_stride_k);
     const size_t ctn = 2 * (size_t)L * p.N;
     const size_t span = gadget_span_words(w, n, count, ct_stride_r, ct_stride_k, ctn); // refused where the index arithmetic would wrap
     const size_t rspan = pl.depth ? gadget_span_words(w, n, (u64)pl.depth, rg_stride_r, rg_stride_j, pl.rows * ctn) : 0;
@@ -228,13 +244,9 @@ inline BfvSelectPlan plan_select(const Params &p, int L, int v, u64 n, u64 count
     // copy of the nodes without a partner at most n of them
     const u128 units = (u128)n * (count > 1 ? count / 2 : 1);
     if (n > 0x7fffffffull || units > 0x7fffffffull / (2 * (u64)L * (p.N / 512))) throw std::invalid_argument(w + ": more pairs than one launch's grid holds");
-    // as integers: a span of up to 2^60 words behind any address may pass the end of the address space, where no pointer may be formed
-    const unsigned long long o0 = (unsigned long long)out, o1 = o0 + 8 * (unsigned long long)(n * ctn);
-    const unsigned long long i0 = (unsigned long long)ct, i1 = i0 + 8 * (unsigned long long)span;
-    const unsigned long long r0 = (unsigned long long)rgsw, r1 = r0 + 8 * (unsigned long long)rspan;
-    if (i1 < i0 || o1 < o0 || r1 < r0) throw std::invalid_argument(w + ": a range wraps the address space");
-    if (i0 < o1 && o0 < i1) throw std::invalid_argument(w + ": `d_out` overlaps the leaves (it may not lie inside their span)");
-    if (rspan && r0 < o1 && o0 < r1) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
+    const AddrRange src = word_range(w, ct, span), dst = word_range(w, out, n * ctn), sel = word_range(w, rgsw, rspan);
+    if (dst.overlaps(src)) throw std::invalid_argument(w + ": `d_out` overlaps the leaves (it may not lie inside their span)");
+    if (dst.overlaps(sel)) throw std::invalid_argument(w + ": `d_out` overlaps the selectors");
     if (pl.depth) {
         pl.pass = bfv_gadget_pass(pl.rows, pl.pairs(0), kGadgetPassPolys);
         pl.slab_polys = (pl.pass * pl.rows + (p.N == 1024 ? pl.pairs(0) : pl.pass) * 2) * L;
@@ -320,10 +332,8 @@ inline BfvBytesPlan plan_bytes(const Params &p, const char *what, u64 n, const v
         throw std::invalid_argument(s + ": d_bytes must be 8-byte aligned and stride_bytes a multiple of 8, at least 8 ceil(bytes_per_plain / 8)");
     if (n > 0x7fffffffull / (p.N / 256)) throw std::invalid_argument(s + ": too many plaintexts for one launch (n N / 256 must be below 2^31)");
     if (n) {
-        const unsigned long long b0 = (unsigned long long)bytes, b1 = b0 + (n - 1) * stride + tail;
-        const unsigned long long w0 = (unsigned long long)words, w1 = w0 + n * (L_out ? (u64)L_out : 1) * p.N * 8;
-        if (b1 < b0 || w1 < w0) throw std::invalid_argument(s + ": a range wraps the address space");
-        if (b0 < w1 && w0 < b1) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
+        const AddrRange br = byte_range(s, bytes, (n - 1) * stride + tail), wr = word_range(s, words, n * (L_out ? (u64)L_out : 1) * p.N);
+        if (br.overlaps(wr)) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
     }
     return {w};
 }

@@ -1909,16 +1909,18 @@ public:
         launch_bfv_digits(env_, pl.tab, L, size, n, ct, digits);
         HIPCHECK(hipGetLastError());
     }
-    // the cut of ciphertext (a, b) at index a stride_a + b stride_b into NTT-form digit polynomials [(a n_b + b) size E + f][L][N]: N >= 2048 the
-    // fused column pass and the row pass in place, N = 1024 the digits under every prime and the whole transform in place.  No scratch.
     // ROUTED: a block of the column pass walks all E_i L digit columns of its residue one after the other, so a batch of fewer blocks than
     // kGadgetColsMinBlocks (one per CU) leaves most of the chip idle and lost to the composition where it was measured (one ciphertext:
     // profiles/bfv_external_product.txt); such a batch takes N = 1024's path, whose work is spread over the digit polynomials.
     static constexpr u64 kGadgetColsMinBlocks = 256;
+    // does a cut of `cts` ciphertexts of `size` polynomials take the column pass?
+    bool gadget_cols(u64 cts, int size, int L) const { return env_.logn1 != 0 && cts * size * L * 4 >= kGadgetColsMinBlocks; }
+    // the cut of ciphertext (a, b) at index a stride_a + b stride_b into NTT-form digit polynomials [(a n_b + b) size E + f][L][N]: N >= 2048 the
+    // fused column pass and the row pass in place, N = 1024 the digits under every prime and the whole transform in place.  No scratch.
     void gadget_cut_ntt(const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out)
     {
         const u32 items = (u32)(n_a * n_b * size * tab.total);
-        const bool cols = env_.logn1 != 0 && n_a * n_b * size * L * 4 >= kGadgetColsMinBlocks;
+        const bool cols = gadget_cols(n_a * n_b, size, L);
         ++(cols ? routes_.cut_cols : routes_.cut_stream);
         launch_bfv_gadget_cut(env_, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out, cols);
         forward_rows_or_full(cols, poly_view(out, L, P.N, L), items);
@@ -2019,7 +2021,7 @@ public:
             const u64 *rg = rgsw + (size_t)j * rg_stride_j * rows * ctn;
             for (u64 p0 = 0; p0 < pairs; p0 += pl.pass) {
                 const u64 c = std::min<u64>(pl.pass, pairs - p0);
-                const bool cols = env_.logn1 != 0 && c * 2 * L * 4 >= kGadgetColsMinBlocks;
+                const bool cols = gadget_cols(c, 2, L);
                 u64 *psum = sums + (level_tail ? p0 * ctn : 0);
                 ++routes_.passes;
                 ++(cols ? routes_.select_cols : routes_.select_stream);
@@ -2086,7 +2088,7 @@ public:
         const size_t N = P.N, LN = (size_t)L * N;
         const u32 E = pl.tab.total, rows = pl.rows;
         const u64 C = pl.C, pass = pl.pass;
-        const bool cols = env_.logn1 != 0 && std::min<u64>(pass, C) * 2 * L * 4 >= kGadgetColsMinBlocks;
+        const bool cols = gadget_cols(std::min<u64>(pass, C), 2, L);
         const PoolBlock slab = scoped_block((size_t)pass * rows * LN * 8);
         for (u64 c0 = 0; c0 < C; c0 += pass) {
             const u64 c = std::min<u64>(pass, C - c0);

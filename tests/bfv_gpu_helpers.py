@@ -1,9 +1,13 @@
-"""What the BFV GPU test modules share (test_gpu_bfv_levels.py, test_gpu_bfv_noise.py, test_gpu_bfv_ntt_form.py): the parameter chains, the
-`be` fixture (imported by name), the device / oracle context pair, random operands and the check of a refused call."""
+"""What the BFV GPU test modules (test_gpu_bfv_*.py) share: the parameter chains, the `be` fixture (imported by name), the device / oracle
+context pair with its keys and expansion keys, random and edged operands, the sentinel convention around an output (sentinelled / inner_of,
+`At` a slab offset), the route counters, the raw-allocation comparison, the external product's definition by composition, and the check of a
+refused call."""
 import importlib
 
 import numpy as np
 import pytest
+
+from tools.probe_common import At  # noqa: F401 (the one definition, shared with the probes)
 
 CONFIGS = {
     # the CONFIGS of tests/test_gpu_parity_bfv.py
@@ -54,8 +58,39 @@ def pair(be, oracle, chain, keys=False):
     return g, o, N, sk, pk
 
 
+def expand_keys(g, o, sk, count, seed):
+    """{elt: key}: the Galois keys of an expansion (or merge) of `count`, level j's from seed + j, set on the device"""
+    gks = {}
+    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
+        gks[e] = o.keygen_galois(sk, e, seed + j)
+        g.set_galois_key(e, gks[e])
+    return gks
+
+
+def keyed(be, oracle, chain, count, seed):
+    g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
+    return g, o, N, sk, pk, expand_keys(g, o, sk, count, seed)
+
+
 def rand_cts(o, rng, n, L, size=2):
     return np.stack([o.random_poly(rng, L, size) for _ in range(n)])
+
+
+def edged(o, rng, n, L, size=2):
+    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
+    c = rand_cts(o, rng, n, L, size)
+    c[0, 0, 0, :] = 0
+    for i, q in enumerate(o.moduli[:L]):
+        c[n - 1, size - 1, i, :] = q - 1
+        c[1 % n, 0, i, 1::2] = 0
+        c[1 % n, 0, i, 0::2] = q - 1
+    return c
+
+
+def to_level(o, ct, L):
+    while ct.shape[1] > L:
+        ct = o.mod_switch_coeff(ct)
+    return ct
 
 
 def plains(o, rng, n, N):
@@ -84,3 +119,41 @@ def refused(be, f):
         f()
     assert ei.value.code == be.E_INVALID_ARGS, ei.value
     assert len(str(ei.value)) > len("he355 error 1: "), "a message goes with the code"
+
+
+def sentinelled(g, words, N):
+    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
+
+
+def inner_of(buf, N, what):
+    got = buf.download()
+    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
+    return got[N:-N]
+
+
+def routes(g):
+    """the counters of he355_bfv_route_stats that are not zero"""
+    return {k: c for k, c in g.bfv_route_stats().items() if c}
+
+
+def same_allocs(a, b):
+    return (a["raw_mallocs"], a["raw_frees"]) == (b["raw_mallocs"], b["raw_frees"])
+
+
+def ep_composition(g, L, v, n, inner, x, ct_at, rg, rg_stride_r, rows, N):
+    """the external product's definition, per result: gadget_decompose_ntt of its inner ciphertexts (gathered on the host),
+    multiply_plain_accumulate over the inner 2E terms with the RGSW rows as the ciphertext operand, transform_from_ntt.  x: the ciphertext
+    slab on the host, ct_at(r, k) its index"""
+    per = 2 * L * N
+    out = np.empty((n, 2, L, N), dtype=np.uint64)
+    dig, res = g.alloc(inner * rows * L * N), g.alloc(per)
+    for r in range(n):
+        cts = g.to_device(np.stack([x[ct_at(r, k)] for k in range(inner)]))
+        g.bfv_gadget_decompose_ntt(L, v, 2, inner, cts, dig)
+        g.bfv_multiply_plain_accumulate(L, 2, 1, 1, inner * rows, At(rg, r * rg_stride_r * rows * per), 1, 1, dig, 1, 1, res)
+        g.bfv_transform_from_ntt(L, 2, 1, res, res)
+        out[r] = res.download((2, L, N))
+        cts.free()
+    dig.free()
+    res.free()
+    return out

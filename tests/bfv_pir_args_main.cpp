@@ -10,27 +10,9 @@
 #include <vector>
 
 #include "../reference-seal-backend_amd/csrc/bfv_pir_args.h"
+#include "args_main_common.h"
 
 using namespace he355;
-
-static int failures = 0;
-template <class F> static void expect(bool refuse, const char *what, int k, F &&f) // k: the line of the case
-{
-    std::string why;
-    bool refused = false;
-    try {
-        f();
-    } catch (const std::invalid_argument &e) {
-        refused = true;
-        why = e.what();
-    }
-    if (refused != refuse) {
-        std::printf("%s, line %d: %s %s\n", what, k, refuse ? "accepted, must be refused" : "refused, must be accepted:", why.c_str());
-        ++failures;
-    }
-}
-#define BAD(what, ...) expect(true, what, __LINE__, [&] { __VA_ARGS__; })
-#define GOOD(what, ...) expect(false, what, __LINE__, [&] { __VA_ARGS__; })
 
 int main()
 {

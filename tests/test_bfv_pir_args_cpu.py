@@ -4,17 +4,8 @@ of the CPU refusal tests (N = 4096, {60, 40, 40, 60}, t of 20 bits) and calls ev
 tests use (levels and widths past their ends, n F at 2^32, grids at 2^31, strides that take a span past 2^60 words or wrap 64 bits, overlaps
 one word inside and right behind), and reads the plans back.  Compiled with g++ -fsanitize=address,undefined, the sanitizer runtimes linked
 statically (the program needs nothing of its environment and runs in the caller's, unchanged), and run as a child process: exit status 0.  The same refusals through the C ABI, with their return codes, are held by the tests/test_bfv_*_core_cpu.py modules.  No GPU."""
-import os
-import subprocess
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "reference-seal-backend_amd", "csrc")
+import sanitized_program
 
 
 def test_plan_program_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "bfv_pir_args")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-mfma", "-ffp-contract=off", "-DHE355_U64_FOLD=0", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, os.path.join(HERE, "bfv_pir_args_main.cpp"), os.path.join(CSRC, "he_params.cpp")], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "bfv_pir_args ok" in r.stdout
+    sanitized_program.run(tmp_path, "bfv_pir_args_main.cpp", "bfv_pir_args ok")

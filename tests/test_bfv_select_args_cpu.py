@@ -22,13 +22,12 @@ No GPU."""
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "reference-seal-backend_amd", "csrc")
+import sanitized_program
+
 N, BITS = 1024, [50, 40, 50]  # a small ring: the check never looks at a word, and the buffers stay small
 FILL = 0xABCD
 V = 20
@@ -149,9 +148,4 @@ def test_route_counters_keep_the_struct(be):
 
 
 def test_plan_program_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "bfv_select_args")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-mfma", "-ffp-contract=off", "-DHE355_U64_FOLD=0", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, os.path.join(HERE, "bfv_select_args_main.cpp"), os.path.join(CSRC, "he_params.cpp")], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "bfv_select_args ok" in r.stdout
+    sanitized_program.run(tmp_path, "bfv_select_args_main.cpp", "bfv_select_args ok")

@@ -18,13 +18,12 @@ bit-exact (np.array_equal, no tolerance):
 * end to end: n4096_d3, real keys, 16 records of Bmax random bytes, unpack_bytes_ntt at L_out = L_top, the query Enc(2^-4 X^i):
   expand(16) -> to_ntt -> bfv_multiply_plain_accumulate (1 x 1 x 16) -> from_ntt -> decrypt -> pack_bytes gives record i byte for byte, for
   two values of i; the noise budget is positive before the decryption."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 from bfv_bytes_ref import np_fields
-from bfv_gpu_helpers import SENT, be, pair, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, expand_keys, inner_of, pair, refused, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,13 +35,6 @@ IDS = ["n1024", "n2048", "n4096_d3", "n2048_w16", "n2048_w21"]
 BASE = 3  # the byte slab starts 3 bytes into its buffer
 
 
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
 def byte_slab(g, rng, n, B, stride, base=BASE):
     """(device buffer, host image as uint8, data [n][B]): 0xFF everywhere but the n plaintexts of B bytes at base + j stride"""
     size = (base + (n - 1) * stride + B + 16 + 7) // 8 * 8
@@ -52,16 +44,6 @@ def byte_slab(g, rng, n, B, stride, base=BASE):
     for j in range(n):
         img[base + j * stride: base + j * stride + B] = data[j]
     return g.to_device(img.view(np.uint64)), img, data
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
 
 
 def byte_sizes(Bmax):
@@ -84,7 +66,7 @@ def test_unpack_and_pack(be, oracle, chain):
                 want = np_fields(data, w, N)
                 out = sentinelled(g, n * N, N)
                 g.bfv_unpack_bytes(n, src, BASE, stride, B, At(out, N))
-                assert np.array_equal(inner(out, N, what).reshape(n, N), want), (what, "fields")
+                assert np.array_equal(inner_of(out, N, what).reshape(n, N), want), (what, "fields")
                 assert np.array_equal(src.download().view(np.uint8), img), (what, "input")
                 src.free()
                 # the inverse, from the coefficients as they lie on the device and from words with junk above bit w
@@ -102,7 +84,7 @@ def test_unpack_and_pack(be, oracle, chain):
                         assert np.array_equal(got.view(np.uint8), exp), (what, ps, name)
                         back.free()
                 assert np.array_equal(dj.download(want.shape), junk), (what, "pack's input")
-                assert np.array_equal(inner(out, N, what).reshape(n, N), want), (what, "pack's input")
+                assert np.array_equal(inner_of(out, N, what).reshape(n, N), want), (what, "pack's input")
                 dj.free()
                 out.free()
     g.close()
@@ -132,7 +114,7 @@ def test_unpack_ntt_equals_the_composition(be, oracle, chain):
                 want = composition(g, L_out, n, src, BASE, B, B, N)
                 buf = sentinelled(g, n * L_out * N, N)
                 g.bfv_unpack_bytes_ntt(L_out, n, src, BASE, B, B, At(buf, N))
-                assert np.array_equal(inner(buf, N, what).reshape(n, L_out, N), want), what
+                assert np.array_equal(inner_of(buf, N, what).reshape(n, L_out, N), want), what
                 assert np.array_equal(src.download().view(np.uint8), img), (what, "input")
                 src.free()
                 buf.free()
@@ -212,7 +194,7 @@ def test_n1024_second_pass_of_the_chunk_loop(be, oracle):
     g.bfv_unpack_bytes_ntt(L_out, n, src, BASE, B, B, At(buf, N))
     routes = {k: c for k, c in g.bfv_route_stats().items() if c}
     assert routes == {"bytes_routed": 2}, routes
-    got = inner(buf, N, "chunks").reshape(n, L_out, N)
+    got = inner_of(buf, N, "chunks").reshape(n, L_out, N)
     Bmax, w = g.bfv_bytes_per_plain()
     plain, ref = g.to_device(np_fields(data[-keep:], w, N)), g.alloc(keep * L_out * N)
     g.bfv_plain_to_ntt(L_out, keep, plain, ref)
@@ -248,8 +230,7 @@ def test_end_to_end_retrieval_of_byte_records(be, oracle):
     count, idx = 16, [11, 0]
     n = len(idx)
     g, o, N, sk, pk = pair(be, oracle, "n4096_d3", keys=True)
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        g.set_galois_key(e, o.keygen_galois(sk, e, 260 + j))
+    expand_keys(g, o, sk, count, 260)
     L, t = g.L, o.t
     Bmax, w = g.bfv_bytes_per_plain()
     rng = np.random.default_rng(95)

@@ -15,25 +15,17 @@ he355_bfv_decompose_ntt, he355_bfv_compose), bit-exact (np.array_equal, no toler
   database entry (i, j) exactly; the noise budget is positive after every stage (printed);
 * a second identical he355_bfv_decompose_ntt makes no raw hipMalloc (the fused path, and N = 1024's pool block), and he355_bfv_route_stats says
   which of the two ran."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
-from bfv_gpu_helpers import SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, expand_keys, inner_of, pair, rand_cts, refused, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 N2048 = (2048, [60, 40, 60], 20)
 CHAINS = ["n1024", N2048, "n4096_d3"]
 IDS = ["n1024", "n2048", "n4096_d3"]
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
 
 
 def table(moduli, t):
@@ -89,27 +81,6 @@ def test_np_reference_on_small_integers():
     assert np.array_equal(np_compose(d, q, t, 1, 2), x)
 
 
-def edged(o, rng, n, L, size):
-    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
-
-
 @pytest.mark.parametrize("chain", CHAINS, ids=IDS)
 def test_decompose_and_compose(be, oracle, chain):
     g, o, N, *_ = pair(be, oracle, chain)
@@ -126,17 +97,17 @@ def test_decompose_and_compose(be, oracle, chain):
                 buf = sentinelled(g, n * F * N, N)
                 g.bfv_decompose(L, size, n, dx, At(buf, N))
                 want = np_digits(x, o.moduli, o.t)
-                assert np.array_equal(inner(buf, N, what).reshape(n, F, N), want), (what, "digits")
+                assert np.array_equal(inner_of(buf, N, what).reshape(n, F, N), want), (what, "digits")
                 assert np.array_equal(dx.download((n, size, L, N)), x), (what, "input")
                 back = sentinelled(g, n * size * L * N, N)
                 g.bfv_compose(L, size, n, At(buf, N), At(back, N))
-                assert np.array_equal(inner(back, N, what).reshape(n, size, L, N), x), (what, "compose o decompose")
-                assert np.array_equal(inner(buf, N, what).reshape(n, F, N), want), (what, "compose's input")
+                assert np.array_equal(inner_of(back, N, what).reshape(n, size, L, N), x), (what, "compose o decompose")
+                assert np.array_equal(inner_of(buf, N, what).reshape(n, F, N), want), (what, "compose's input")
                 words = rng.integers(0, 2 ** 64, (n, F, N), dtype=np.uint64)  # full-range "digits"
                 words[0, 0, :] = 2 ** 64 - 1
                 dw = g.to_device(words)
                 g.bfv_compose(L, size, n, dw, At(back, N))
-                assert np.array_equal(inner(back, N, what).reshape(n, size, L, N), np_compose(words, o.moduli, o.t, size, L)), (what, "masked sum")
+                assert np.array_equal(inner_of(back, N, what).reshape(n, size, L, N), np_compose(words, o.moduli, o.t, size, L)), (what, "masked sum")
                 for b in (dx, buf, back, dw):
                     b.free()
     g.close()
@@ -169,7 +140,7 @@ def test_decompose_ntt_equals_the_composition(be, oracle, chain):
                     want = composition(g, L, size, n, dx, L_out, F, N)
                     buf = sentinelled(g, n * F * L_out * N, N)
                     g.bfv_decompose_ntt(L, size, n, dx, L_out, At(buf, N))
-                    assert np.array_equal(inner(buf, N, what).reshape(n, F, L_out, N), want), what
+                    assert np.array_equal(inner_of(buf, N, what).reshape(n, F, L_out, N), want), what
                     assert np.array_equal(dx.download((n, size, L, N)), x), (what, "input")
                     dx.free()
                     buf.free()
@@ -244,8 +215,7 @@ def test_end_to_end_two_dimensional_retrieval(be, oracle):
     n1 = n2 = 8
     count, n, idx = n1 + n2, 2, [(5, 2), (0, 7)]
     g, o, N, sk, pk = pair(be, oracle, "n4096_d3", keys=True)
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        g.set_galois_key(e, o.keygen_galois(sk, e, 160 + j))
+    expand_keys(g, o, sk, count, 160)
     L, t = g.L, o.t
     assert L == 3
     rng = np.random.default_rng(76)

@@ -16,24 +16,16 @@ he355_bfv_expand), bit-exact (np.array_equal, no tolerance):
 * end to end: n4096_d3, two queries 2^-4 X^idx -> expand -> to_ntt -> multiply_plain_accumulate over a 16 x 2 database -> from_ntt ->
               decrypt gives the database row, also after he355_bfv_mod_switch to L = 2 and L = 1; the noise budget stays positive;
 * a second identical he355_bfv_expand makes no raw hipMalloc."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 from bfv_expand_ref import children, expand_levels, np_shift
-from bfv_gpu_helpers import ALL, SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import ALL, SENT, At, be, edged, expand_keys, keyed, pair, rand_cts, refused, to_level  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 N2048 = (2048, [60, 40, 60], 20)
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
 
 
 def test_np_shift_is_the_schoolbook_product():
@@ -46,17 +38,6 @@ def test_np_shift_is_the_schoolbook_product():
         for i in range(N):
             want[(i + e) % N] = (want[(i + e) % N] + (-1 if ((i + e) // N) & 1 else 1) * int(a[0, i])) % q
         assert np_shift(a, e, [q])[0].tolist() == want, e
-
-
-def edged(o, rng, n, L, size):
-    """uniform rows mixed with all-0 and all-(q - 1) rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
 
 
 def monomial_plain(t, N, e):
@@ -144,12 +125,6 @@ def test_refusals(be, oracle):
 
 
 # ---- expansion against the definition, run in the oracle -------------------------------------------------------------------------------
-def to_level(o, ct, L):
-    while ct.shape[1] > L:
-        ct = o.mod_switch_coeff(ct)
-    return ct
-
-
 _CASES = {}
 
 
@@ -159,11 +134,8 @@ def expand_case(be, oracle, chain, L):
     if (chain, L) not in _CASES:
         g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
         rng = np.random.default_rng(63 + L)
-        gks = {}
-        for j, e in enumerate(g.bfv_expand_galois_elts(16)):
-            assert e == N // (1 << j) + 1
-            gks[e] = o.keygen_galois(sk, e, 80 + j)
-            g.set_galois_key(e, gks[e])
+        gks = expand_keys(g, o, sk, 16, 80)
+        assert list(gks) == [N // (1 << j) + 1 for j in range(len(gks))]
         m = rng.integers(0, o.t, N, dtype=np.uint64)
         q = np.stack([to_level(o, o.encrypt(pk, m, 90), L)] + [o.random_poly(rng, L, 2) for _ in range(2)])
         trees = [expand_levels(o, q[r], 4, gks, L) for r in range(3)]
@@ -249,15 +221,6 @@ def test_second_identical_expand_makes_no_raw_allocation(be, oracle):
 
 
 # ---- what the children decrypt to ---------------------------------------------------------------------------------------------
-def keyed(be, oracle, chain, count, seed):
-    g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
-    gks = {}
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        gks[e] = o.keygen_galois(sk, e, seed + j)
-        g.set_galois_key(e, gks[e])
-    return g, o, N, sk, pk, gks
-
-
 def test_deep_tree(be, oracle):
     """count = N = 2048: 11 levels, 2047 key switches, the last level's shift a whole 1024-word row; 128 MiB of children"""
     count = 2048

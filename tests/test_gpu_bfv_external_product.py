@@ -33,7 +33,7 @@ import numpy as np
 import pytest
 
 import bfv_gadget_ref as ref
-from bfv_gpu_helpers import SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, ep_composition, expand_keys, inner_of, pair, rand_cts, refused, routes, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,39 +41,6 @@ N2048 = (2048, [60, 40, 60], 20)
 CHAINS = ["n1024", N2048, "n4096_d3"]
 IDS = ["n1024", "n2048", "n4096_d3"]
 WIDTHS = (4, 20, 45, 63)
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def edged(o, rng, n, L, size=2):
-    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner_of(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
-
-
-def routes(g):
-    """the counters of he355_bfv_route_stats that are not zero"""
-    return {k: c for k, c in g.bfv_route_stats().items() if c}
 
 
 def ntt_forward(be, g, buf, n_polys, L):
@@ -215,24 +182,6 @@ def test_rgsw_encrypt_equals_the_definition(be, oracle, chain):
     g.close()
 
 
-def ep_composition(g, L, v, n, inner, x, ct_at, rg, rg_stride_r, rows, N):
-    """the definition, per result: gadget_decompose_ntt of its inner ciphertexts (gathered on the host), multiply_plain_accumulate over the
-    inner 2E terms with the RGSW rows as the ciphertext operand, transform_from_ntt.  x: the ciphertext slab on the host, ct_at(r, k) its index"""
-    per = 2 * L * N
-    out = np.empty((n, 2, L, N), dtype=np.uint64)
-    dig, res = g.alloc(inner * rows * L * N), g.alloc(per)
-    for r in range(n):
-        cts = g.to_device(np.stack([x[ct_at(r, k)] for k in range(inner)]))
-        g.bfv_gadget_decompose_ntt(L, v, 2, inner, cts, dig)
-        g.bfv_multiply_plain_accumulate(L, 2, 1, 1, inner * rows, At(rg, r * rg_stride_r * rows * per), 1, 1, dig, 1, 1, res)
-        g.bfv_transform_from_ntt(L, 2, 1, res, res)
-        out[r] = res.download((2, L, N))
-        cts.free()
-    dig.free()
-    res.free()
-    return out
-
-
 def ep_case(g, o, rng, L, v, n, inner, shared, child_major, N, what, routed=None):
     rows = 2 * g.bfv_gadget_count(L, v)[0]
     per = 2 * L * N
@@ -339,8 +288,7 @@ def test_end_to_end_two_dimensional_retrieval_one_reply(be, oracle):
     n1 = n2 = 8
     n, idx = 2, [(5, 2), (0, 7)]
     g, o, N, sk, pk = pair(be, oracle, "n4096_d3", keys=True)
-    for j, e in enumerate(g.bfv_expand_galois_elts(n1)):
-        g.set_galois_key(e, o.keygen_galois(sk, e, 160 + j))
+    expand_keys(g, o, sk, n1, 160)
     L, t, v = g.L, o.t, 20
     assert L == 3
     rng = np.random.default_rng(76)

@@ -31,7 +31,6 @@ rows at Lt = 3 and 10 at Lt = 2 for v = 20.  The shapes are the smallest that re
   the oracle's tree; he355_path_stats printed (which key-switch shapes carried it), not asserted.
 
 Not run: the pass split at N = 32768, and LOGN1 = 4 in the Shoup form."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -39,7 +38,7 @@ import pytest
 import bfv_ring_ref as ring
 import bfv_selector_ref as sel
 from bfv_expand_ref import children, expand_levels, np_shift
-from bfv_gpu_helpers import SENT, be, pair, rand_cts  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, ep_composition, expand_keys, inner_of, pair, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,34 +51,6 @@ CHAINS = {
 }
 IDS = list(CHAINS)
 V = 20
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def edged(o, rng, n, L, size=2):
-    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner_of(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
 
 
 _PAIRS = {}
@@ -203,24 +174,6 @@ def test_gadget_decompose_ntt(be, oracle, cid, v):
 
 
 # ---- he355_bfv_external_product ---------------------------------------------------------------------------------------------------------
-def ep_composition(g, L, v, n, inner, x, ct_at, rg, rg_stride_r, rows, N):
-    """the definition on the device, per result (test_gpu_bfv_external_product.py): gadget_decompose_ntt of its inner ciphertexts,
-    multiply_plain_accumulate over the inner 2E terms with the RGSW rows as the ciphertext operand, transform_from_ntt"""
-    per = 2 * L * N
-    out = np.empty((n, 2, L, N), dtype=np.uint64)
-    dig, res = g.alloc(inner * rows * L * N), g.alloc(per)
-    for r in range(n):
-        cts = g.to_device(np.stack([x[ct_at(r, k)] for k in range(inner)]))
-        g.bfv_gadget_decompose_ntt(L, v, 2, inner, cts, dig)
-        g.bfv_multiply_plain_accumulate(L, 2, 1, 1, inner * rows, At(rg, r * rg_stride_r * rows * per), 1, 1, dig, 1, 1, res)
-        g.bfv_transform_from_ntt(L, 2, 1, res, res)
-        out[r] = res.download((2, L, N))
-        cts.free()
-    dig.free()
-    res.free()
-    return out
-
-
 def ep_case(g, o, rng, cid, L, v, n, inner, shared, child_major, N, case, want, check=None):
     """one call against external_product_ref: every result, or the results `check` against the oracle and all of them against the composition"""
     rows = 2 * g.bfv_gadget_count(L, v)[0]
@@ -391,11 +344,8 @@ def test_expand(be, oracle, cid):
     g, o, N, sk, pk = chain_pair(be, oracle, cid)
     rng = np.random.default_rng(310)
     L, n, count = g.L, 3, 8
-    gks = {}
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        assert e == N // (1 << j) + 1
-        gks[e] = o.keygen_galois(sk, e, 190 + j)
-        g.set_galois_key(e, gks[e])
+    gks = expand_keys(g, o, sk, count, 190)
+    assert list(gks) == [N // (1 << j) + 1 for j in range(len(gks))]
     q = np.stack([o.encrypt(pk, rng.integers(0, o.t, N, dtype=np.uint64), 191)] + [o.random_poly(rng, L, 2) for _ in range(n - 1)])
     assert q.shape == (n, 2, L, N)
     dq = g.to_device(q)

@@ -16,12 +16,11 @@
 * refusals   : CKKS context, bad L, count 0 / N + 1, colliding and zero strides, a stride that wraps, a missing Galois key (named in the
                message; missing at the second level, nothing is written), d_out over the inputs: the code, a message, the output untouched;
 * a second identical he355_bfv_merge makes no raw hipMalloc."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
-from bfv_gpu_helpers import SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, expand_keys, keyed, pair, rand_cts, refused, to_level  # noqa: F401 (be: the fixture)
 from bfv_merge_ref import merge_levels, merged_plain
 
 pytestmark = pytest.mark.gpu
@@ -29,30 +28,6 @@ pytestmark = pytest.mark.gpu
 N2048 = (2048, [60, 40, 60], 20)
 COUNTS = (1, 2, 3, 5, 8, 16)
 KMAX, NMAX = 16, 3
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def to_level(o, ct, L):
-    while ct.shape[1] > L:
-        ct = o.mod_switch_coeff(ct)
-    return ct
-
-
-def edged(o, rng, n, L):
-    """uniform ciphertexts mixed with all-0 and all-(q - 1) rows"""
-    c = rand_cts(o, rng, n, L)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
 
 
 _CASES = {}
@@ -65,10 +40,7 @@ def merge_case(be, oracle, chain, L):
     if (chain, L) not in _CASES:
         g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
         rng = np.random.default_rng(73 + L)
-        gks = {}
-        for j, e in enumerate(g.bfv_expand_galois_elts(KMAX)):
-            gks[e] = o.keygen_galois(sk, e, 180 + j)
-            g.set_galois_key(e, gks[e])
+        gks = expand_keys(g, o, sk, KMAX, 180)
         x = np.empty((KMAX, NMAX, 2, L, N), dtype=np.uint64)
         for k in range(KMAX):
             x[k, 0] = to_level(o, o.encrypt(pk, rng.integers(0, o.t, N, dtype=np.uint64), 190 + k), L)
@@ -215,15 +187,6 @@ def test_second_identical_merge_makes_no_raw_allocation(be, oracle):
 
 
 # ---- what the result decrypts to --------------------------------------------------------------------------------------------------
-def keyed(be, oracle, chain, count, seed):
-    g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
-    gks = {}
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        gks[e] = o.keygen_galois(sk, e, seed + j)
-        g.set_galois_key(e, gks[e])
-    return g, o, N, sk, pk, gks
-
-
 def test_deep_tree(be, oracle):
     """count = N = 2048: 11 levels, 2047 key switches, the first level's shift a whole 1024-word row"""
     count = 2048

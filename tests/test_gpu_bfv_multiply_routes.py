@@ -25,27 +25,19 @@ threshold batch has more than 57 results: no share is sampled).
 
 Every output lies between a ring's worth of sentinel words before and after it; every operand is read back.
 Not run: LOGN1 = 4 in the Shoup form, and the halving of a chunk when the arena does not fit."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
 import bfv_multiply_plan as mp
-from bfv_gpu_helpers import SENT, be  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be  # noqa: F401 (be: the fixture)
 from bfv_multiply_operands import family_cts
 
 pytestmark = pytest.mark.gpu
 
 LEVELS = [(name, L) for name, spec in mp.CHAINS.items() for L in spec[3]]
 THRESHOLD_LEVELS = [(name, L) for name, spec in mp.CHAINS.items() for L in spec[4]]
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
 
 
 @pytest.fixture(scope="module")

@@ -15,23 +15,15 @@ transforms and Python integers, on the CONFIGS and the three random chains of te
 * ordering    : an asynchronous producer (he355_add into an operand) immediately followed by each new call, small chunks, dual stream;
 * refusals    : overlaps, inner == 0, size 0 or 4, L out of range: HE355_E_INVALID_ARGS and the outputs untouched;
 * no raw hipMalloc / hipFree in a second call."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
-from bfv_gpu_helpers import ALL, SENT, be, lift, pair, plains, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import ALL, SENT, At, be, lift, pair, plains, rand_cts, refused  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (1, 1, 7), (3, 2, 5), (1, 5, 16), (5, 1, 16)]
-
-
-class At:
-    """a device pointer `off` words into a slab (what a host hands the C ABI for one ciphertext of a batch)"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
 
 
 def ntt_cts(o, cts):

@@ -25,14 +25,13 @@ column pass, both engines) and n4096_d3 (fold form).
   difference;
 * refusals with a device context: a bad L, v, count, strides and overlaps leave the output sentinel-clean; n == 0 touches nothing; count == 1
   copies."""
-import ctypes as C
 import itertools
 
 import numpy as np
 import pytest
 
 import bfv_select_ref as ref
-from bfv_gpu_helpers import SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, expand_keys, inner_of, pair, rand_cts, refused, routes, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,39 +40,6 @@ CHAINS = ["n1024", N2048, "n4096_d3"]
 IDS = ["n1024", "n2048", "n4096_d3"]
 WIDTHS = (4, 20, 45, 63)
 LAYOUTS = ("row-major", "child-major", "padded")
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def edged(o, rng, n, L, size=2):
-    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner_of(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
-
-
-def routes(g):
-    """the counters of he355_bfv_route_stats that are not zero"""
-    return {k: c for k, c in g.bfv_route_stats().items() if c}
 
 
 def leaf_strides(layout, n, count):
@@ -269,8 +235,7 @@ def test_end_to_end_bit_selectors_in_one_query(be, oracle):
     L, t, v, kv = g.L, o.t, 20, 20
     assert L == 3
     E, rows = g.bfv_gadget_count(L, v)[0], 2 * g.bfv_gadget_count(L, kv)[0]
-    for j, e in enumerate(g.bfv_expand_galois_elts(64)):  # the keys of d = 6 hold those of d = 5
-        g.set_galois_key(e, o.keygen_galois(sk, e, 180 + j))
+    expand_keys(g, o, sk, 64, 180)  # the keys of d = 6 hold those of d = 5
     rng = np.random.default_rng(76)
     db = rng.integers(0, t, (n1, n2, N), dtype=np.uint64)  # the database of test_gpu_bfv_selectors.py
     db[5, 2, :4] = [0, 1, t - 1, t // 2]

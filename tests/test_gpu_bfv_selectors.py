@@ -33,45 +33,13 @@ import pytest
 
 import bfv_gadget_ref as gad
 import bfv_selector_ref as ref
-from bfv_gpu_helpers import SENT, be, pair, rand_cts, refused  # noqa: F401 (be: the fixture)
+from bfv_gpu_helpers import SENT, At, be, edged, expand_keys, inner_of, pair, rand_cts, refused, same_allocs, sentinelled  # noqa: F401 (be: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 N2048 = (2048, [60, 40, 60], 20)
 CHAINS = ["n1024", N2048, "n4096_d3"]
 IDS = ["n1024", "n2048", "n4096_d3"]
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def edged(o, rng, n, L, size=2):
-    """uniform rows mixed with all-0, all-(q - 1) and alternating rows"""
-    c = rand_cts(o, rng, n, L, size)
-    c[0, 0, 0, :] = 0
-    for i, q in enumerate(o.moduli[:L]):
-        c[n - 1, size - 1, i, :] = q - 1
-        c[1 % n, 0, i, 1::2] = 0
-        c[1 % n, 0, i, 0::2] = q - 1
-    return c
-
-
-def sentinelled(g, words, N):
-    return g.to_device(np.full(words + 2 * N, SENT, dtype=np.uint64))
-
-
-def inner_of(buf, N, what):
-    got = buf.download()
-    assert (got[:N] == SENT).all() and (got[-N:] == SENT).all(), (what, "sentinel")
-    return got[N:-N]
-
-
-def same_allocs(a, b):
-    return (a["raw_mallocs"], a["raw_frees"]) == (b["raw_mallocs"], b["raw_frees"])
 
 
 @pytest.mark.parametrize("chain", CHAINS, ids=IDS)
@@ -273,11 +241,6 @@ def test_rgsw_from_bfv_more_terms_than_a_run(be, oracle):
     g.close()
 
 
-def set_expand_keys(g, o, sk, count, seed):
-    for j, e in enumerate(g.bfv_expand_galois_elts(count)):
-        g.set_galois_key(e, o.keygen_galois(sk, e, seed + j))
-
-
 def test_meaning_with_real_keys(be, oracle):
     g, o, N, sk, pk = pair(be, oracle, "n4096_d3", keys=True)
     rng = np.random.default_rng(97)
@@ -287,7 +250,7 @@ def test_meaning_with_real_keys(be, oracle):
     ms = [0, 1, t - 1]
     n_sel = len(ms)
     count = n_sel * E
-    set_expand_keys(g, o, sk, count, 170)
+    expand_keys(g, o, sk, count, 170)
     query, kids, key = g.alloc(per), g.alloc(count * per), g.alloc(rows * per)
     g.bfv_selector_encrypt(L, v, 1, n_sel, 0, count, g.to_device(np.array([ms], dtype=np.uint64)), 121, 0, query)
     g.bfv_expand(L, 1, query, count, kids)
@@ -321,7 +284,7 @@ def test_end_to_end_one_ciphertext_per_query(be, oracle):
     count = n1 + n2 * E
     d = ref.depth(count)
     assert (E, count, d) == (7, 64, 6)
-    set_expand_keys(g, o, sk, count, 180)
+    expand_keys(g, o, sk, count, 180)
     rng = np.random.default_rng(76)
     db = rng.integers(0, t, (n1, n2, N), dtype=np.uint64)  # the database of test_gpu_bfv_external_product.py
     db[5, 2, :4] = [0, 1, t - 1, t // 2]

@@ -14,13 +14,14 @@ The report goes to stdout and to profiles/bfv_database.txt.
 Usage: python tools/bfv_database_probe.py [regions] [calls per region] [n ...]"""
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from tools.probe_common import At, alternated, fmt
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -34,29 +35,6 @@ def say(line=""):
     print(line, flush=True)
     report.write(line + "\n")
     report.flush()
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
 
 
 def shape(g, N, n):
@@ -81,7 +59,7 @@ def shape(g, N, n):
         k = min(step, n * L_out * N - off)
         if not np.array_equal(out.download_range(off, (k,)), ref.download_range(off, (k,))):
             raise SystemExit(f"N {N} n {n}: he355_bfv_unpack_bytes_ntt and the composition differ")
-    ta, tb = alternated(g, [fused, composed], [calls, calls])
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats, warmup=1)
     spread = tb[2] - tb[0]
     verdict = "accepted" if ta[1] < tb[1] - spread else "NOT accepted: not faster than the composition by more than its spread"
     written = n * L_out * N * 8
@@ -93,7 +71,7 @@ def shape(g, N, n):
     # (c) the path a caller had before: the widened slab over the bus, then the transform
     wide = plain.download()
     pt = lambda: g.bfv_plain_to_ntt(L_out, n, plain, ref)
-    tw, tn, tp, tf = alternated(g, [lambda: plain.upload(wide), lambda: src.upload(host_bytes), pt, fused], [1, 1, calls, calls])
+    tw, tn, tp, tf = alternated(g, [lambda: plain.upload(wide), lambda: src.upload(host_bytes), pt, fused], [1, 1, calls, calls], repeats, warmup=1)
     say(f"  (c) before: upload of the widened slab ({wide.nbytes} bytes) {fmt(tw)}  + he355_bfv_plain_to_ntt {fmt(tp)}   median sum {tw[1] + tp[1]:11.1f}")
     say(f"      now   : upload of the bytes        ({host_bytes.nbytes} bytes) {fmt(tn)}  + (a)                    {fmt(tf)}   median sum {tn[1] + tf[1]:11.1f}"
         f"   before / now {(tw[1] + tp[1]) / (tn[1] + tf[1]):6.3f} (bus alone {tw[1] / tn[1]:6.3f}, device alone {tp[1] / tf[1]:6.3f})")
@@ -106,21 +84,13 @@ def shape(g, N, n):
     m = n // 2  # he355_add over [m][2][1][N]: three slabs of n N words
     fs = [lambda: g.bfv_unpack_bytes(n, src, 0, B, B, plain), lambda: g.bfv_pack_bytes(n, plain, B, B, back),
           lambda: g.add(1, 2, m, out, At(out, n * N), be.Context.pairwise(), ref)]
-    ts = alternated(g, fs, [calls] * 3)
+    ts = alternated(g, fs, [calls] * 3, repeats, warmup=1)
     for name, t, nbytes in (("he355_bfv_unpack_bytes", ts[0], n * B + n * N * 8), ("he355_bfv_pack_bytes  ", ts[1], n * B + n * N * 8),
                             ("he355_add (k_addsub)  ", ts[2], 3 * n * N * 8)):
         say(f"  (d) {name} {nbytes:13d} compulsory bytes: {fmt(t)} us -> {nbytes / t[1] / 1e6:6.3f} TB/s at the median")
     for b in (src, plain, out, ref, back):
         b.free()
     g.pool_trim()
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        import ctypes as C
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
 
 
 for N, bits in RINGS:

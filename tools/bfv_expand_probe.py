@@ -15,7 +15,6 @@ keys by he355_keygen_galois), so the noise budget of the children is read off th
   same size.
 `monomial`: the monomial multiply alone (the A/B of two builds of the library, HE355_LIB_PATH: one process each, alternated by the caller).
 Usage: python tools/bfv_expand_probe.py [regions] [scale of the calls per region] [all | monomial]"""
-import ctypes as C
 import importlib
 import os
 import statistics
@@ -27,6 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated, fmt
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -34,37 +34,6 @@ scale = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 mode = sys.argv[3] if len(sys.argv) > 3 else "all"
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
 SHAPES = ((64, 1), (64, 16), (1024, 1), (1024, 16))  # (count, n)
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
 
 
 def expand_run(g, N, L, count, n, h2d):
@@ -117,7 +86,7 @@ def expand_run(g, N, L, count, n, h2d):
     ok = all(got[k, r, 0] == (1 if k == (7 * r + 3) % count else 0) and not got[k, r, 1:].any() for k in range(kc) for r in range(n))
     dec.free()
     calls = scale * (4 if count * n <= 1024 else 1)
-    ta, tb = alternated(g, [new, composed], [calls, calls])
+    ta, tb = alternated(g, [new, composed], [calls, calls], repeats)
     ks = ((1 << d) - 1) * n
     print(f"N = {N} L = {L}  count {count} (d = {d})  n {n}: {ks} key switches   us per call, min / median / max of {repeats} regions")
     print(f"  (a) he355_bfv_expand                {fmt(ta)}   per key switch {ta[1] / ks:8.2f}")
@@ -133,7 +102,7 @@ def expand_run(g, N, L, count, n, h2d):
         g.bfv_multiply_plain_accumulate(L, 2, n, 1, count, out, 1, n, ptn, 1, 0, res)
         g.bfv_transform_from_ntt(L, 2, n, res, res)
 
-    (ts,) = alternated(g, [scan], [calls])
+    (ts,) = alternated(g, [scan], [calls], repeats)
     up = count * n * per * 8 / h2d * 1e6
     print(f"  scan (to_ntt of the children, multiply_plain_accumulate over {count}, from_ntt) {fmt(ts)}")
     print(f"  expand + scan {ta[1] + ts[1]:11.1f} us   against {up:11.1f} us to upload {count * n} ciphertexts ({count * n * per * 8} bytes) at {h2d / 1e9:5.2f} GB/s:"
@@ -157,7 +126,7 @@ def monomial_rate(g, N, L):
         raise SystemExit(f"N {N}: he355_bfv_multiply_monomial and he355_bfv_multiply_plain by the monomial differ")
     g.fill_uniform(b, n * 2 * L, list(range(L)), 6)
     fs = [lambda e=e: g.bfv_multiply_monomial(L, 2, n, a, e, o) for e in (1, 2, 1024)] + [lambda: g.add(L, 2, n, a, b, be.Context.pairwise(), o)]
-    ts = alternated(g, fs, [10 * scale] * 4)
+    ts = alternated(g, fs, [10 * scale] * 4, repeats)
     for name, t, slabs in (("monomial e = 1   ", ts[0], 2), ("monomial e = 2   ", ts[1], 2), ("monomial e = 1024", ts[2], 2), ("he355_add        ", ts[3], 3)):
         print(f"N = {N} L = {L}  {name} over {n} ciphertexts ({slabs * n * per * 8} bytes): {fmt(t)} us -> {slabs * n * per * 8 / t[1] / 1e6:6.3f} TB/s at the median")
     print(f"  odd shift against even: e = 1 takes {ts[0][1] / ts[1][1]:5.3f} of e = 2's time", flush=True)

@@ -16,10 +16,8 @@
     mod_switch to L = 1, decompose_ntt, scan(32): F reply ciphertexts per query, decrypt, compose, decrypt).  Time per answer set, reply
     ciphertexts and bytes, query bytes (the RGSW selectors are the client's to send), noise budgets, and both answers against the database.
 Usage: python tools/bfv_external_probe.py [regions] [scale of the calls per region]"""
-import ctypes as C
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -27,48 +25,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated, fmt, verdict
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 scale = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
-
-
-def verdict(ta, tb):
-    spread = tb[2] - tb[0]
-    ok = ta[1] <= tb[1] + spread
-    return spread, "accepted" if ok else "NOT accepted: slower than the composition"
 
 
 def external_against_composition(g, N, n, inner, v, shared):
@@ -97,7 +59,7 @@ def external_against_composition(g, N, n, inner, v, shared):
         if not np.array_equal(out.download_range(lo * per, (k * per,)), ref.download_range(lo * per, (k * per,))):
             raise SystemExit(f"N {N} n {n} inner {inner} v {v}: he355_bfv_external_product and the composition differ")
     calls = scale * (10 if n * inner <= 64 else 1)
-    ta, tb = alternated(g, [fused, composed], [calls, calls])
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats)
     spread, word = verdict(ta, tb)
     print(f"N = {N} L = {L} v = {v} (2E = {rows})  n {n:5d} inner {inner}  {'one selector row' if shared else 'a row per result '}   "
           f"(a) fused {fmt(ta)}   (b) composition {fmt(tb)}   (b) / (a) {tb[1] / ta[1]:6.3f}   spread of (b) {spread:9.1f} us ({spread / tb[1] * 100:4.1f} %)   {word}",
@@ -129,7 +91,7 @@ def cut_against_composition(g, N, n, v):
         if not np.array_equal(out.download_range(lo * w, (k * w,)), ref.download_range(lo * w, (k * w,))):
             raise SystemExit(f"N {N} n {n} v {v}: he355_bfv_gadget_decompose_ntt and the composition differ")
     calls = scale * (20 if n <= 64 else 2)
-    ta, tb = alternated(g, [fused, composed], [calls, calls])
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats)
     spread, word = verdict(ta, tb)
     moved = (n * size * L * N + n * F * L * N) * 8  # the fused call's compulsory bytes: every ciphertext word read, every digit word written
     print(f"N = {N} L = {L} v = {v} (F = {F})  n {n:5d}   (a) he355_bfv_gadget_decompose_ntt {fmt(ta)} ({moved / ta[1] / 1e6:5.2f} TB/s of compulsory bytes)   "
@@ -209,7 +171,7 @@ def retrieval(g, N, n, db, dbn):
     g.bfv_compose(Ld, 2, n, pieces, glued)
     g.decrypt(Ld, 2, n, glued, final2)
     ok_r = np.array_equal(final2.download((n, N)), want)
-    te, tr = alternated(g, [by_external_product, by_recursion], [scale, scale])
+    te, tr = alternated(g, [by_external_product, by_recursion], [scale, scale], repeats)
     ct_bytes = lambda lv: 2 * lv * N * 8
     print(f"N = {N} L = {L}  1024 entries as 32 x 32, {n} quer{'y' if n == 1 else 'ies'}   us per answer set, min / median / max of {repeats} regions")
     print(f"  external product: expand(32), scan(32), mod_switch to L = {Le}, external product (v = {v}, 2E = {rows}, inner 32), mod_switch to L = 1  {fmt(te)}")

@@ -14,10 +14,8 @@ closed form (coefficient k + 2^d m is 2^d mu_(k, 2^d m)).
 s = 2), and he355_add over slabs of the same size, a few calls each and nothing else: the run to put under a kernel trace, whose per-kernel
 times give the streaming rate of k_bfv_merge (four slabs: two read, two written) beside k_addsub's (three).
 Usage: python tools/bfv_merge_probe.py [regions] [scale of the calls per region] [all | kernel]"""
-import ctypes as C
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -25,6 +23,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated, fmt
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -33,37 +32,6 @@ mode = sys.argv[3] if len(sys.argv) > 3 else "all"
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
 SHAPES = ((64, 1), (64, 16), (1024, 1), (1024, 16))  # (count, n)
 BATCH = 256  # plaintexts of one he355_encrypt call; input i encrypts plaintext i % BATCH
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
 
 
 def fresh_inputs(g, N, L, total, plain, dplain):
@@ -117,7 +85,7 @@ def merge_run(g, N, L, count, n, plain, dplain):
     ok = np.array_equal(dec.download((N,)), want)
     dec.free()
     calls = scale * (4 if count * n <= 1024 else 1)
-    ta, tb = alternated(g, [new, composed], [calls, calls])
+    ta, tb = alternated(g, [new, composed], [calls, calls], repeats)
     ks = ((1 << d) - 1) * n
     print(f"N = {N} L = {L}  count {count} (d = {d})  n {n}: {ks} key switches   us per call, min / median / max of {repeats} regions")
     print(f"  (a) he355_bfv_merge                             {fmt(ta)}   per key switch {ta[1] / ks:8.2f}")

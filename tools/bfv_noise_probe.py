@@ -12,13 +12,13 @@
 Usage: python tools/bfv_noise_probe.py [calls per region] [repeats] [table batch] [all | time | table | kernels]"""
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle as ho  # keys and the slot codec only: nothing timed goes through it
+from tools.probe_common import alternated, region
 
 be = importlib.import_module("reference-seal-backend_amd")
 calls = int(sys.argv[1]) if len(sys.argv) > 1 else 10
@@ -26,27 +26,6 @@ repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 tab_batch = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 mode = sys.argv[4] if len(sys.argv) > 4 else "all"
 SIZE = 2
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fa, fb, n_calls):
-    """(min, median, max) us per call of fa and of fb: `repeats` regions each, a, b, a, b, ... after a warm-up of both"""
-    for _ in range(3):
-        fa()
-        fb()
-    g.sync()
-    a, b = [], []
-    for _ in range(repeats):
-        a.append(region(g, fa, n_calls))
-        b.append(region(g, fb, n_calls))
-    s = lambda v: (min(v), statistics.median(v), max(v))
-    return s(a), s(b)
 
 
 def timing(N, bits):
@@ -61,7 +40,7 @@ def timing(N, bits):
         g.fill_uniform(ct, n * SIZE * L, list(range(L)), 1)
         k = max(2, calls // (1 if n < 1024 else 4))
         bits_ptr = out.ptr.value + 4 * n
-        tn, td = alternated(g, lambda: lib.he355_bfv_noise_budget(g.h, L, SIZE, n, ct.ptr, out.ptr, bits_ptr), lambda: g.decrypt(L, SIZE, n, ct, dec), k)
+        tn, td = alternated(g, [lambda: lib.he355_bfv_noise_budget(g.h, L, SIZE, n, ct.ptr, out.ptr, bits_ptr), lambda: g.decrypt(L, SIZE, n, ct, dec)], [k, k], repeats, warmup=3)
         f = lambda t: " / ".join(f"{v / n:9.3f}" for v in t)
         print(f"batch {n:5d}  he355_bfv_noise_budget {f(tn)}   he355_decrypt {f(td)}   ratio of medians {tn[1] / td[1]:.3f}", flush=True)
         for b in (ct, dec, out):

@@ -15,12 +15,13 @@ over its time; he355_add over a slab of the same order is timed beside it (k_add
 Usage: python tools/bfv_ntt_probe.py [regions] [scale of the calls per region] [all | fused | kernels]"""
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools.probe_common import alternated
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -29,26 +30,6 @@ mode = sys.argv[3] if len(sys.argv) > 3 else "all"
 SIZE = 2
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
 SHAPES = ((1, 64, 256), (16, 16, 64), (1, 1, 1024))
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
 
 
 def shape_run(g, N, L, rows, cols, inner):
@@ -90,11 +71,11 @@ def shape_run(g, N, L, rows, cols, inner):
         g.sync()
         print(f"N = {N} L = {L}  {rows} x {cols} x {inner}: compulsory bytes of the fused call {words * 8}", flush=True)
     elif mode == "fused":
-        (ta,) = alternated(g, [fused], [max(1, scale * min(20, (1 << 34) // (words * 8)))])
+        (ta,) = alternated(g, [fused], [max(1, scale * min(20, (1 << 34) // (words * 8)))], repeats)
         print(f"N = {N} L = {L}  {rows} x {cols} x {inner}  (a) fused accumulate {ta[0]:11.1f} / {ta[1]:11.1f} / {ta[2]:11.1f} us -> {words * 8 / ta[1] / 1e6:6.3f} TB/s", flush=True)
     else:
         ca = max(1, scale * min(20, (1 << 34) // (words * 8)))
-        ta, tb, tc = alternated(g, [fused, unfused, parent], [ca, scale, scale])
+        ta, tb, tc = alternated(g, [fused, unfused, parent], [ca, scale, scale], repeats)
         f = lambda t: " / ".join(f"{v:11.1f}" for v in t)
         terms = n * inner
         print(f"N = {N} L = {L}  rows x cols x inner = {rows} x {cols} x {inner}   us per call, min / median / max of {repeats} regions")
@@ -115,7 +96,7 @@ def addsub_rate(g, N, L):
     g.fill_uniform(a, n * SIZE * L, list(range(L)), 5)
     g.fill_uniform(b, n * SIZE * L, list(range(L)), 6)
     f = lambda: g.add(L, SIZE, n, a, b, be.Context.pairwise(), o)
-    (t,) = alternated(g, [f], [10 * scale])
+    (t,) = alternated(g, [f], [10 * scale], repeats)
     print(f"N = {N} L = {L}  he355_add over {n} ciphertexts ({3 * n * per * 8} bytes): {t[0]:9.1f} / {t[1]:9.1f} / {t[2]:9.1f} us -> {3 * n * per * 8 / t[1] / 1e6:6.3f} TB/s"
           f" at the median", flush=True)
     for x in (a, b, o):

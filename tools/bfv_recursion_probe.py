@@ -14,10 +14,8 @@ N = 32768 {60,40,40,60} (L_top = 3).
   two-dimensional answer is decrypted, composed, decrypted again and compared with the database entry.  The two paths compute different
   ciphertexts by construction: this is a time, not a parity.
 Usage: python tools/bfv_recursion_probe.py [regions] [scale of the calls per region]"""
-import ctypes as C
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -25,42 +23,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated, fmt
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 scale = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
 
 
 def fused_against_composition(g, N, n):
@@ -85,7 +53,7 @@ def fused_against_composition(g, N, n):
         if not np.array_equal(out.download_range(off, (k,)), ref.download_range(off, (k,))):
             raise SystemExit(f"N {N} n {n}: he355_bfv_decompose_ntt and the composition differ")
     calls = scale * (20 if n <= 32 else 2)
-    ta, tb = alternated(g, [fused, composed], [calls, calls])
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats)
     spread = tb[2] - tb[0]
     verdict = "accepted" if ta[1] <= tb[1] + spread else "NOT accepted: slower than the composition"
     print(f"N = {N} L = {L} -> L_out = {L_out}  n {n} (F = {F}, {n * F} plaintexts)   us per call, min / median / max of {repeats} regions")
@@ -113,7 +81,7 @@ def streaming_rate(g, N):
     g.fill_uniform(b, m * 2 * L, list(range(L)), 10)
     fs = [lambda: g.bfv_decompose(L, size, n, ct, plain), lambda: g.bfv_compose(L, size, n, plain, back),
           lambda: g.add(L, 2, m, a, b, be.Context.pairwise(), o)]
-    ts = alternated(g, fs, [10 * scale] * 3)
+    ts = alternated(g, fs, [10 * scale] * 3, repeats)
     moved = (n * per + n * F * N) * 8
     for name, t, nbytes in (("he355_bfv_decompose", ts[0], moved), ("he355_bfv_compose  ", ts[1], moved), ("he355_add          ", ts[2], 3 * m * 2 * L * N * 8)):
         print(f"N = {N} L = {L}  {name} over {n if 'add' not in name else m} ciphertexts ({nbytes} compulsory bytes): {fmt(t)} us -> {nbytes / t[1] / 1e6:6.3f} TB/s at the median",
@@ -188,7 +156,7 @@ def two_against_one(g, N, n, db, dbn):
     dec1 = g.alloc(n * N)
     g.decrypt(L, 2, n, res, dec1)
     ok1 = np.array_equal(dec1.download((n, N)), np.stack([db[i * n2 + j] for i, j in idx]))
-    t2, t1 = alternated(g, [two_d, one_d], [scale, scale])
+    t2, t1 = alternated(g, [two_d, one_d], [scale, scale], repeats)
     print(f"N = {N} L = {L}  1024 entries, {n} quer{'y' if n == 1 else 'ies'}   us per answer set, min / median / max of {repeats} regions")
     print(f"  two dimensions: expand(64), scan(32), mod_switch to L = 1, decompose_ntt (F = {F}), scan(32)  {fmt(t2)}")
     print(f"  one dimension : expand(1024), scan(1024)                                                   {fmt(t1)}   one / two {t1[1] / t2[1]:6.3f}")

@@ -17,10 +17,8 @@ with he355_bfv_rgsw_from_bfv).  Reports the server's time per answer set (median
 converted, the query slots, and the noise budget after every stage; every reply is decrypted and held to db[i][j].
 `n1024`: `call` on N = 1024 {50,40,50}, the ring without a column pass, whose tail is routed to launch_ntt_inverse and a streaming add.
 Usage: python tools/bfv_select_probe.py [regions] [call | retrieval | all | n1024]"""
-import ctypes as C
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -28,6 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -36,33 +35,6 @@ RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
 SMALL = ((1024, [50, 40, 50]),)  # no column pass: the streaming cut and the routed tail (launch_ntt_inverse + k_bfv_select_add)
 SHAPES = ((32, 1), (32, 16), (256, 1), (256, 16))  # (count, n)
 V = 20
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    """(min, median, max) us per call of every f of fs: `repeats` regions each, in turn, after a warm-up of all"""
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
 
 
 def fmt(t):
@@ -113,7 +85,7 @@ def call_run(g, N, L, count, n):
     fused()
     routes = {k: c for k, c in g.bfv_route_stats(reset=True).items() if c}
     calls = 4 if count * n <= 512 else 1
-    ta, tb = alternated(g, [fused, composed], calls)
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats)
     pairs = (count - 1) * n
     print(f"N = {N} L = {L}  count {count} (m = {m})  n {n}: {pairs} CMUXes   us per call, min / median / max of {repeats} regions")
     print(f"  (a) he355_bfv_select                        {fmt(ta)}   per CMUX {ta[1] / pairs:8.2f}   routes {routes}")
@@ -211,7 +183,7 @@ def retrieval_run(N, bits, nq=4):
 
     for packed in (False, True):
         a, b = route(True, packed), route(False, packed)
-        ta, tb = alternated(g, [a[1], b[1]], 2)
+        ta, tb = alternated(g, [a[1], b[1]], [2, 2], repeats)
         for (name, _, info, _), tt in ((a, ta), (b, tb)):
             print(f"  {name}: us per answer set, min / median / max of {repeats} regions {fmt(tt)}\n      {info}")
         print(f"      one-hot / bits {tb[1] / ta[1]:6.3f}   spread of one-hot {(tb[2] - tb[0]) / tb[1] * 100:4.1f} %", flush=True)

@@ -13,10 +13,8 @@
     (v = 20, inner 32), mod_switch to L = 1, one decrypt.  Time per answer set, query bytes per query against the 84148224 (N = 8192) and
     337117184 (N = 32768) bytes of the RGSW-upload route, the noise budget after every stage, and the answers against the database.
 Usage: python tools/bfv_selector_probe.py [regions] [scale of the calls per region] [rings: a comma list of N]"""
-import ctypes as C
 import importlib
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -24,6 +22,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import oracle as ho  # keys only: nothing timed goes through it
+from tools.probe_common import At, alternated, fmt
 
 be = importlib.import_module("reference-seal-backend_amd")
 repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -31,36 +30,6 @@ scale = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 only = [int(x) for x in sys.argv[3].split(",")] if len(sys.argv) > 3 else None
 RINGS = ((8192, [60, 40, 60]), (32768, [60, 40, 40, 60]))
 UPLOAD_ROUTE = {8192: 84148224, 32768: 337117184}  # profiles/bfv_external_product.txt (c) and the issue's N = 32768 figure
-
-
-class At:
-    """a device pointer `off` words into a slab"""
-
-    def __init__(self, buf, off):
-        self.ptr = C.c_void_p(buf.ptr.value + int(off) * 8)
-
-
-def region(g, f, n_calls):
-    g.timer_begin()
-    for _ in range(n_calls):
-        f()
-    return g.timer_end() / n_calls * 1e3  # us per call
-
-
-def alternated(g, fs, n_calls):
-    for f in fs:
-        f()
-        f()
-    g.sync()
-    t = [[] for _ in fs]
-    for _ in range(repeats):
-        for k, f in enumerate(fs):
-            t[k].append(region(g, f, n_calls[k]))
-    return [(min(v), statistics.median(v), max(v)) for v in t]
-
-
-def fmt(t):
-    return " / ".join(f"{v:11.1f}" for v in t)
 
 
 def verdict(ta, tb):
@@ -95,7 +64,7 @@ def from_bfv_against_composition(g, N, n, n_sel, v, kv):
         if not np.array_equal(out.download_range(lo * w, (k * w,)), ref.download_range(lo * w, (k * w,))):
             raise SystemExit(f"N {N} n {n} n_sel {n_sel} v {v} key_bits {kv}: he355_bfv_rgsw_from_bfv and the composition differ")
     calls = scale * (10 if S <= 32 else 1)
-    ta, tb = alternated(g, [fused, composed], [calls, calls])
+    ta, tb = alternated(g, [fused, composed], [calls, calls], repeats)
     spread, word = verdict(ta, tb)
     print(f"N = {N} L = {L} v = {v} (E = {E}) key_bits = {kv} (2 E_key = {rows})  n {n:3d} n_sel {n_sel:3d} ({S * E:5d} slot ciphertexts)   "
           f"(a) fused {fmt(ta)}   (b) composition {fmt(tb)}   (b) / (a) {tb[1] / ta[1]:6.3f}   spread of (b) {spread:9.1f} us ({spread / tb[1] * 100:4.1f} %)   {word}",
@@ -147,7 +116,7 @@ def retrieval(g, N, n, db, dbn, key, kv):
     final = g.alloc(n * N)
     g.decrypt(1, 2, n, low, final)
     ok = np.array_equal(final.download((n, N)), want)
-    (ta,) = alternated(g, [answer], [scale])
+    (ta,) = alternated(g, [answer], [scale], repeats)
     rows = 2 * g.bfv_gadget_count(L, kv)[0]
     print(f"N = {N} L = {L}  1024 entries as 32 x 32, {n} quer{'y' if n == 1 else 'ies'}   us per answer set, min / median / max of {repeats} regions")
     print(f"  packed query: expand({count}) (d = {d}), scan(32), rgsw_from_bfv (v = {v}, E = {E}, key_bits = {kv}), external product at L = {L} (inner 32), "
