@@ -501,6 +501,43 @@ uint64_t he355_bfv_bytes_per_plain(const he355_ctx *ctx, uint32_t *field_bits);
 int he355_bfv_unpack_bytes(he355_ctx *ctx, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain);
 int he355_bfv_unpack_bytes_ntt(he355_ctx *ctx, int L_out, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain_ntt);
 int he355_bfv_pack_bytes(he355_ctx *ctx, uint64_t n, const uint64_t *d_plain, uint64_t bytes_per_plain, uint64_t stride_bytes, void *d_bytes);
+/* ---- reply compression (BFV contexts only).  The last server step of a PIR round trip is he355_bfv_mod_switch to L = 1: two polynomials of
+ * 64-bit words under q = q_0, the first prime of the chain.  These calls switch the two halves of such a reply to the moduli 2^k0 (c0) and
+ * 2^k1 (c1), pack the bits, and decrypt the packed reply on the client.  [UPSTREAM-UNVERIFIED] the idea is SealPIR's, OnionPIR's and
+ * Spiral's; the definition is this library's own, exact integers, no tolerance:
+ *     switch     : for x in [0, q): cut_k(x) = floor((x 2^k + floor(q / 2)) / q) mod 2^k (q is odd: no ties; an x that rounds to 2^k wraps to 0);
+ *     layout     : one reply is the little-endian bit string of c0's N fields of k0 bits, then c1's N fields of k1 bits, coefficient e at bit
+ *                  e k.  N >= 1024, so c1 starts on a word boundary and a reply is exactly N (k0 + k1) / 64 whole 64-bit words,
+ *                  N (k0 + k1) / 8 bytes; fields straddle words whenever k does not divide 64;
+ *     decryption : unpack y0, y1; y1 centred is y1 - 2^k1 where y1 >= 2^(k1 - 1); w is the centred representative mod q_0 of its negacyclic
+ *                  product with the secret key (the integer product whenever N 2^(k1 - 1) |s|_inf < q_0 / 2: every accepted k1, ternary
+ *                  keys); z = (y0 2^(k1 - k0) + w) mod 2^k1; M = floor((t z + 2^(k1 - 1)) / 2^k1); the plaintext coefficient is M mod t;
+ *                  per reply r = the largest |t z - M 2^k1|, noise_bits = bit length of r, budget = max(0, k1 - noise_bits - 1):
+ *                  he355_bfv_noise_budget's formula with 2^k1 in the place of q;
+ *     accepted   : 2 <= k0 <= k1 and N 2^(k1 - 1) <= (q_0 - 1) / 2 (a 60-bit q_0: k1 <= 46 at N = 8192, k1 <= 44 at N = 32768);
+ *     safe       : k0 = bitlen(t) + 2, k1 = bitlen(t) + 2 + log2 N: for a ternary key and an input with at least 2 bits of invariant noise
+ *                  budget at L = 1 every coefficient decrypts correctly (|v'| <= 2^-3 + t 2^-(k0+1) + t N 2^-(k1+1) < 3/8); the reported
+ *                  budget may still be 0 there (the clamp).  Tighter widths are the caller's risk; the budget output says what is left.
+ *   he355_bfv_reply_bytes      bytes per reply, or 0 for a CKKS context or refused widths.  Host only.
+ *   he355_bfv_reply_safe_bits  writes the safe widths; returns 1 if they are accepted on this chain, else 0 (a 35-bit q_0 cannot hold
+ *                              them; 0 and nothing written for a CKKS context).  Host only.
+ *   he355_bfv_reply_compress   d_ct [n][2][L][N] coefficient form -> reply j at d_bytes + j stride_bytes.  For L > 1 it is, by definition,
+ *                              bit-identical to he355_bfv_mod_switch(L -> 1) followed by the L = 1 call (the L = 1 ciphertexts pass through
+ *                              one pool block).  d_bytes 8-byte aligned, stride_bytes a multiple of 8 and at least the reply size; nothing
+ *                              outside a reply's own words is written.
+ *   he355_bfv_reply_decrypt    replies -> d_plain [n][N] coefficients mod t, the layout he355_decrypt writes (it feeds he355_bfv_pack_bytes
+ *                              and he355_bfv_decode); d_budget, d_noise_bits int32 [n] on the device, either may be NULL.  Needs
+ *                              he355_set_secret_key and nothing else: one transform less per reply than he355_decrypt.
+ * Refused with HE355_E_INVALID_ARGS on the host, before any device is asked for, the outputs untouched: a CKKS context, L outside 1..L_top,
+ * widths outside the rule above, a d_bytes that is not 8-byte aligned, a stride that is too small or not a multiple of 8,
+ * (n - 1) stride + the reply size at or above 2^63 (a checked multiply), a grid above 2^31 - 1 blocks (n N / 256, or n times the 256-word
+ * blocks of a reply), any overlap of output and input; and, before the first launch, a missing secret key for the decrypt.  n == 0 touches nothing.  Everything is queued on
+ * the context's stream. */
+uint64_t he355_bfv_reply_bytes(const he355_ctx *ctx, int k0, int k1);
+int he355_bfv_reply_safe_bits(const he355_ctx *ctx, int *k0, int *k1);
+int he355_bfv_reply_compress(he355_ctx *ctx, int L, int k0, int k1, uint64_t n, const uint64_t *d_ct, void *d_bytes, uint64_t stride_bytes);
+int he355_bfv_reply_decrypt(he355_ctx *ctx, int k0, int k1, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t *d_plain, int32_t *d_budget,
+                            int32_t *d_noise_bits);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

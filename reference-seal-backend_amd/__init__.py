@@ -154,6 +154,10 @@ def lib():
             "he355_bfv_unpack_bytes": (i32, [vp, u64, vp, u64, u64, vp]),
             "he355_bfv_unpack_bytes_ntt": (i32, [vp, i32, u64, vp, u64, u64, vp]),
             "he355_bfv_pack_bytes": (i32, [vp, u64, vp, u64, u64, vp]),
+            "he355_bfv_reply_bytes": (u64, [vp, i32, i32]),
+            "he355_bfv_reply_safe_bits": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+            "he355_bfv_reply_compress": (i32, [vp, i32, i32, i32, u64, vp, vp, u64]),
+            "he355_bfv_reply_decrypt": (i32, [vp, i32, i32, u64, vp, u64, vp, vp, vp]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -200,7 +204,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -549,6 +553,36 @@ class Context:
         """the inverse of bfv_unpack_bytes: plain [n][N] (each word masked to w bits) -> ceil(B / 8) whole words per plaintext at
         byte_offset + j * stride_bytes of `buf` (both multiples of 8), the bytes past B in the last word zero"""
         _check(lib().he355_bfv_pack_bytes(self.h, n, plain.ptr, bytes_per_plain, stride_bytes, self._at(buf, byte_offset)))
+
+    def bfv_reply_bytes(self, k0, k1) -> int:
+        """bytes of one compressed reply, N (k0 + k1) / 8; 0 for a CKKS context or widths the chain refuses (host-side; no device needed)"""
+        return int(lib().he355_bfv_reply_bytes(self.h, k0, k1))
+
+    def bfv_reply_safe_bits(self):
+        """(k0, k1, accepted): the widths bitlen(t) + 2 and bitlen(t) + 2 + log2 N under which every coefficient of a reply with at least 2
+        bits of noise budget at L = 1 decrypts correctly, and whether this chain's first prime holds them (host-side; no device needed)"""
+        k0, k1 = C.c_int32(0), C.c_int32(0)
+        ok = lib().he355_bfv_reply_safe_bits(self.h, C.byref(k0), C.byref(k1))
+        return int(k0.value), int(k1.value), bool(ok)
+
+    def bfv_reply_compress(self, L, k0, k1, n, ct, buf, stride_bytes, byte_offset=0):
+        """ct [n][2][L][N] coefficient form -> reply j at byte_offset + j * stride_bytes of `buf` (both multiples of 8): switched to L = 1,
+        c0 cut to k0 bits and c1 to k1 bits per coefficient, bit-packed: bfv_reply_bytes(k0, k1) bytes each"""
+        _check(lib().he355_bfv_reply_compress(self.h, L, k0, k1, n, ct.ptr, self._at(buf, byte_offset), stride_bytes))
+
+    def bfv_reply_decrypt(self, k0, k1, n, buf, stride_bytes, plain, byte_offset=0, with_budget=False):
+        """the replies at byte_offset + j * stride_bytes of `buf` -> plain [n][N] mod t (needs set_secret_key); with_budget: returns
+        (budget, noise_bits), np.int32[n] each: max(0, k1 - noise_bits - 1) and the bit length of the largest rounding residue"""
+        if not with_budget:
+            _check(lib().he355_bfv_reply_decrypt(self.h, k0, k1, n, self._at(buf, byte_offset), stride_bytes, plain.ptr, None, None))
+            return None
+        out = DeviceBuffer(self, max(1, n))  # n budgets, then n noise_bits: int32 each, inside n uint64 words
+        try:
+            _check(lib().he355_bfv_reply_decrypt(self.h, k0, k1, n, self._at(buf, byte_offset), stride_bytes, plain.ptr, out.ptr, C.c_void_p(out.ptr.value + 4 * n)))
+            v = out.download().view(np.int32)
+        finally:
+            out.free()
+        return v[:n].copy(), v[n:2 * n].copy()
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

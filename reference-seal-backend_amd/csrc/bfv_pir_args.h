@@ -5,6 +5,7 @@
 // key-switch tables) is checked there.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
 // under the address and undefined-behaviour sanitizers.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <stdexcept>
 #include <string>
@@ -12,6 +13,7 @@
 #include "bfv_bytes_core.h"
 #include "bfv_digits_core.h"
 #include "bfv_gadget_core.h"
+#include "bfv_reply_core.h"
 #include "he_params.h"
 
 namespace he355 {
@@ -336,6 +338,45 @@ inline BfvBytesPlan plan_bytes(const Params &p, const char *what, u64 n, const v
         if (br.overlaps(wr)) throw std::invalid_argument(s + ": the bytes overlap the plaintexts");
     }
     return {w};
+}
+
+// ---- reply compression (he355_bfv_reply_compress, he355_bfv_reply_decrypt) -----------------------------------------------------------------
+// reply j: `bytes` whole words at bytes + j stride; `words`: the other side, [n][per] 64-bit words -- the ciphertexts [n][2][L][N]
+// (per = 2 L N, read) or the plaintexts [n][N] (per = N, written); `stats`: decrypt's int32 outputs [n], either may be null.
+struct BfvReplyPlan {
+    u64 bytes; // of one reply, N (k0 + k1) / 8
+};
+inline void check_reply_widths(const Params &p, const std::string &s, int k0, int k1)
+{
+    if (!bfv_reply_widths_ok(p.N, p.primes[0].q, k0, k1))
+        throw std::invalid_argument(s + ": the widths must satisfy 2 <= k0 <= k1 and N 2^(k1 - 1) <= (q_0 - 1) / 2");
+}
+inline BfvReplyPlan plan_reply(const Params &p, const char *what, int L, int k0, int k1, u64 n, const void *bytes, u64 stride, const u64 *words, u64 per,
+                               bool decrypt = false, const int32_t *stat_a = nullptr, const int32_t *stat_b = nullptr)
+{
+    const std::string s(what);
+    check_level(p, s, L);
+    if (p.plain_modulus < 2) throw std::invalid_argument(s + ": the plain modulus must be at least 2");
+    check_reply_widths(p, s, k0, k1);
+    const u64 B = bfv_reply_size(p.N, k0, k1);
+    if (((unsigned long long)bytes & 7) || (stride & 7) || stride < B)
+        throw std::invalid_argument(s + ": d_bytes must be 8-byte aligned and stride_bytes a multiple of 8, at least the reply size (he355_bfv_reply_bytes)");
+    // (n - 1) stride + B stays below 2^63: neither the range below nor a kernel's j * stride can wrap
+    if (n > 1 && n - 1 > (((u64)1 << 63) - 1 - B) / stride) throw std::invalid_argument(s + ": (n - 1) stride_bytes + the reply size must be below 2^63");
+    // the largest grid: a block per 256 coefficients (the client's kernels, the switch to L = 1) or per 256 words of a reply (the packing)
+    const u64 blocks = std::max<u64>(p.N / 256, (B / 8 + 255) / 256);
+    if (n > 0x7fffffffull / blocks) throw std::invalid_argument(s + ": too many replies for one launch (its grid must stay below 2^31 blocks)");
+    if (n) {
+        const AddrRange br = byte_range(s, bytes, (n - 1) * stride + B), wr = word_range(s, words, n * per);
+        if (br.overlaps(wr)) throw std::invalid_argument(s + ": the replies overlap the " + (decrypt ? "plaintexts" : "ciphertexts"));
+        for (const int32_t *st : {stat_a, stat_b}) {
+            if (!st) continue;
+            const AddrRange sr = byte_range(s, st, 4 * n);
+            if (sr.overlaps(br) || sr.overlaps(wr)) throw std::invalid_argument(s + ": a budget output overlaps the replies or the plaintexts");
+        }
+        if (stat_a && stat_b && byte_range(s, stat_a, 4 * n).overlaps(byte_range(s, stat_b, 4 * n))) throw std::invalid_argument(s + ": the two budget outputs overlap");
+    }
+    return {B};
 }
 
 } // namespace he355

@@ -2246,6 +2246,51 @@ public:
         launch_bfv_noise_finish(env_, n, budget, noise_bits, nc.q_bits);
         HIPCHECK(hipGetLastError());
     }
+    // ---- reply compression (he355_kernels_bfv_reply.hip; the definition: bfv_reply_core.h, include/he355.h) -----------------------------
+    // [n][2][L][N] coefficient form -> n replies.  L > 1 is, by definition, bfv_mod_switch(L -> 1) followed by the L = 1 call: the L = 1
+    // ciphertexts pass through one pool block held for the call.
+    void bfv_reply_compress(const BfvReplyPlan &, int L, int k0, int k1, u64 n, const u64 *ct, void *bytes, u64 stride)
+    {
+        use();
+        if (L > kBfvLevelMaxL) throw std::invalid_argument("he355_bfv_reply_compress: BFV modulus switching supports up to 16 data primes");
+        if (!n) return;
+        PoolBlock low;
+        if (L > 1) {
+            low = scoped_block((size_t)n * 2 * P.N * 8);
+            launch_bfv_mod_switch(env_, bfv_drop_table_dev(), (int)P.Ltop, L, 1, n * 2, ct, low.get());
+            ct = low.get();
+        }
+        launch_bfv_reply_pack(env_, k0, k1, n, ct, stride, bytes);
+        HIPCHECK(hipGetLastError());
+    }
+    // n replies -> plain [n][N] mod t, budget / noise_bits [n] int32 (either may be null).  Per chunk of at most 64 replies (as decrypt();
+    // never more than the batch chunk, he355_set_chunk): c1 unpacked, centred and lifted mod q_0 into client scratch, forward transform,
+    // product with the NTT-form secret key at prime 0 in place, inverse transform, then k_bfv_reply_finish adds c0's field, rounds, and
+    // gathers the largest residue's bit length in `budget` (or `noise_bits` when that is the only output), which k_bfv_noise_finish turns
+    // into the budget with 2^k1 in the place of q.  One transform less per reply than decrypt() spends: c0 is never transformed.
+    void bfv_reply_decrypt(const BfvReplyPlan &, int k0, int k1, u64 n, const void *bytes, u64 stride, u64 *plain, int32_t *budget, int32_t *noise_bits)
+    {
+        use();
+        if (!d_sk_) throw std::invalid_argument("he355_bfv_reply_decrypt: secret key not set (he355_set_secret_key)");
+        if (!n) return;
+        if (!bytes || !plain) throw std::invalid_argument("he355_bfv_reply_decrypt: null replies or null plaintext output");
+        const size_t N = P.N;
+        const u64 cmax = std::max<u64>(1, std::min<u64>(n, std::min<u64>(64, chunk_)));
+        u64 *prod = client_scratch(cmax * N);
+        int32_t *bits = budget ? budget : noise_bits;
+        if (bits) HIPCHECK(hipMemsetAsync(bits, 0, n * sizeof(int32_t), stream_));
+        for (u64 off = 0; off < n; off += cmax) {
+            const u64 c = std::min<u64>(cmax, n - off);
+            const unsigned char *src = static_cast<const unsigned char *>(bytes) + off * stride;
+            launch_bfv_reply_lift(env_, k0, k1, c, src, stride, prod);
+            launch_ntt_forward(env_, poly_view(prod, 1, N, 1), (u32)c);
+            launch_bfv_noise_dot_sk(env_, 1, 2, c, prod, d_sk_, prod);
+            launch_ntt_inverse(env_, poly_view(prod, 1, N, 1), (u32)c);
+            launch_bfv_reply_finish(env_, k0, k1, P.plain_modulus, c, src, stride, prod, plain + off * N, bits ? bits + off : nullptr);
+        }
+        if (budget) launch_bfv_noise_finish(env_, n, budget, noise_bits, k1);
+        HIPCHECK(hipGetLastError());
+    }
     // ---- encoders (CKKSEncoder / BatchEncoder) -------------------------------------------------------------------
     const EncTablesDev &enc_tables()
     {
@@ -2979,6 +3024,33 @@ int he355_bfv_pack_bytes(he355_ctx *c, uint64_t n, const uint64_t *d_plain, uint
         need_bfv(c, "he355_bfv_pack_bytes");
         const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_pack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, true);
         dev(c).bfv_pack_bytes(pl, n, d_plain, bytes_per_plain, stride_bytes, d_bytes);
+    });
+}
+uint64_t he355_bfv_reply_bytes(const he355_ctx *c, int k0, int k1)
+{
+    if (!c || c->params->scheme != kSchemeBFV || !bfv_reply_widths_ok(c->params->N, c->params->primes[0].q, k0, k1)) return 0;
+    return bfv_reply_size(c->params->N, k0, k1);
+}
+int he355_bfv_reply_safe_bits(const he355_ctx *c, int *k0, int *k1)
+{
+    if (!c || c->params->scheme != kSchemeBFV || c->params->plain_modulus < 2 || !k0 || !k1) return 0;
+    bfv_reply_safe(c->params->N, c->params->plain_modulus, *k0, *k1);
+    return bfv_reply_widths_ok(c->params->N, c->params->primes[0].q, *k0, *k1) ? 1 : 0;
+}
+int he355_bfv_reply_compress(he355_ctx *c, int L, int k0, int k1, uint64_t n, const uint64_t *d_ct, void *d_bytes, uint64_t stride_bytes)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_reply_compress");
+        const BfvReplyPlan pl = plan_reply(*c->params, "he355_bfv_reply_compress", L, k0, k1, n, d_bytes, stride_bytes, d_ct, 2 * (u64)(L > 0 ? L : 0) * c->params->N);
+        dev(c).bfv_reply_compress(pl, L, k0, k1, n, d_ct, d_bytes, stride_bytes);
+    });
+}
+int he355_bfv_reply_decrypt(he355_ctx *c, int k0, int k1, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t *d_plain, int32_t *d_budget, int32_t *d_noise_bits)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_reply_decrypt");
+        const BfvReplyPlan pl = plan_reply(*c->params, "he355_bfv_reply_decrypt", 1, k0, k1, n, d_bytes, stride_bytes, d_plain, c->params->N, true, d_budget, d_noise_bits);
+        dev(c).bfv_reply_decrypt(pl, k0, k1, n, d_bytes, stride_bytes, d_plain, d_budget, d_noise_bits);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

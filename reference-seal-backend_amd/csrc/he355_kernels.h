@@ -12,6 +12,7 @@
 #include "bfv_noise_core.h"
 #include "bfv_digits_core.h"
 #include "bfv_bytes_core.h"
+#include "bfv_reply_core.h"
 #include "bfv_gadget_core.h"
 
 namespace he355 {
@@ -249,6 +250,9 @@ HE355_FWD(launch_bfv_digits_cols_fwd)
 HE355_FWD(launch_bfv_unpack)
 HE355_FWD(launch_bfv_pack)
 HE355_FWD(launch_bfv_bytes_cols_fwd)
+HE355_FWD(launch_bfv_reply_pack)
+HE355_FWD(launch_bfv_reply_lift)
+HE355_FWD(launch_bfv_reply_finish)
 HE355_FWD(launch_bfv_gadget_cut)
 HE355_FWD(launch_bfv_gadget_mac)
 HE355_FWD(launch_bfv_rgsw_plant)

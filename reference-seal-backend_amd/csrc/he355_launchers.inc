@@ -172,6 +172,15 @@ void launch_bfv_pack(const KernelEnv &env, int w, u64 n, const u64 *plain, u64 B
 // prime i' < L_out after the column pass (raw of prime i'), what launch_bfv_unpack + launch_bfv_lift_plain + launch_cols_fwd would have left
 // there; launch_rows_fwd finishes it in place.  N >= 2048 only (N = 1024 has no column pass).
 void launch_bfv_bytes_cols_fwd(const KernelEnv &env, int w, u64 n, const void *bytes, u64 stride, u64 B, int L_out, u64 t, u64 *out);
+// ---- BFV reply compression (he355_kernels_bfv_reply.hip; arithmetic: bfv_reply_core.h) ------------------------------------------------------
+// Reply j is the N (k0 + k1) / 64 words at bytes + j stride (`bytes` 8-byte aligned, stride a multiple of 8 that holds a reply): c0's N
+// fields of k0 bits, then c1's N fields of k1 bits, under q_0 = env.prime_q[0].  ct [n][2][N], L = 1, coefficient form.
+void launch_bfv_reply_pack(const KernelEnv &env, int k0, int k1, u64 n, const u64 *ct, u64 stride, void *bytes);
+// out [n][N]: c1's fields centred and lifted mod q_0
+void launch_bfv_reply_lift(const KernelEnv &env, int k0, int k1, u64 n, const void *bytes, u64 stride, u64 *out);
+// prod [n][N]: the negacyclic product of the lifted c1 and the secret key mod q_0 -> plain [n][N] mod t; bits [n] (or null: nothing is
+// gathered): the maximum of the residues' bit lengths is atomicMax'ed into it, zeroed by the caller on the same stream
+void launch_bfv_reply_finish(const KernelEnv &env, int k0, int k1, u64 t, u64 n, const void *bytes, u64 stride, const u64 *prod, u64 *plain, int *bits);
 // ---- the BFV external product RGSW x ciphertext (he355_kernels_bfv_gadget.hip; arithmetic: bfv_gadget_core.h, bfv_mac_core.h) ----------------
 // The gadget cut in NTT form: ciphertext (a, b), a < n_a, b < n_b, at index a stride_a + b stride_b of `ct` ([size][L][N], coefficient
 // form) -> out [(a n_b + b) size E + f][L][N], digit polynomial f = k E(L) + off_i + g under every prime j < L (`tab`: bfv_gadget_table of the
