@@ -2,8 +2,8 @@
 the oracle, and what it decrypts to:
 
 * fresh oracle.encrypt inputs with full-range plaintexts merge into a ciphertext whose coefficient k + 2^d m is 2^d mu_(k, 2^d m) mod t for
-  k < count and 0 for count <= k < 2^d, with no wrong coefficient: (1024, {50, 40, 50}, t of 20 bits) at count 5, 8 and 16, and
-  (2048, {60, 40, 60}) at count 2048, all 11 levels;
+  k < count and 0 for count <= k < 2^d, with no wrong coefficient: (1024, {50, 40, 50}, t of 20 bits) at count 5, 8 and 16,
+  (2048, {60, 40, 60}) at count 2048, all 11 levels, and (1024, {45, 55, 50}) at count 5;
 * merge(expand(q)) at count 8 on n1024 decrypts to 64 m.
 No GPU."""
 import numpy as np
@@ -12,7 +12,8 @@ import pytest
 from bfv_expand_ref import children, expand_levels
 from bfv_merge_ref import decrypt, merge_levels, merged_plain
 
-SHAPES = [((1024, [50, 40, 50], 20), 5), ((1024, [50, 40, 50], 20), 8), ((1024, [50, 40, 50], 20), 16), ((2048, [60, 40, 60], 20), 2048)]
+SHAPES = [((1024, [50, 40, 50], 20), 5), ((1024, [50, 40, 50], 20), 8), ((1024, [50, 40, 50], 20), 16), ((2048, [60, 40, 60], 20), 2048),
+          ((1024, [45, 55, 50], 20), 5)]  # the last: an fp64 prime 0 beside a u64 one (test_gpu_bfv_chain_layouts.py)
 
 
 def keyed(oracle, chain, count, seed):
@@ -27,7 +28,13 @@ def keyed(oracle, chain, count, seed):
     return o, sk, pk, gks
 
 
-@pytest.mark.parametrize("chain,count", SHAPES, ids=[f"n{c[0]}-count{k}" for c, k in SHAPES])
+def shape_id(chain, count):
+    """n<N>-count<k>; a chain other than the two first ones also names its bit sizes, so that no two shapes share an id"""
+    tag = "" if chain[1] in ([50, 40, 50], [60, 40, 60]) else "-" + "_".join(str(b) for b in chain[1])
+    return f"n{chain[0]}{tag}-count{count}"
+
+
+@pytest.mark.parametrize("chain,count", SHAPES, ids=[shape_id(c, k) for c, k in SHAPES])
 def test_merge_decrypts_to_the_closed_form(oracle, chain, count):
     o, sk, pk, gks = keyed(oracle, chain, count, 300)
     N, t, L = o.N, o.t, o.L

@@ -1,5 +1,5 @@
 """The reference of BFV reply compression (tests/bfv_reply_ref.py: the definition of include/he355.h in Python integers) held to itself, at
-N = 1024 under a 60-bit fold prime and a 50-bit prime, with a ternary key of full weight:
+N = 1024 under a 60-bit fold prime, a 50-bit prime and the 45-bit first prime of {45, 55, 50}, with a ternary key of full weight:
 
 * an L = 1 ciphertext is built whose invariant noise t phase mod q (centred) lies ON the largest norm that leaves exactly 2 bits of noise
   budget, 2^(bitlen(q) - 3) - 1, with both signs (coefficients 0 and 1; the message there is what the congruence forces), and within t of
@@ -21,7 +21,7 @@ import bfv_reply_ref as ref
 
 N = 1024
 T = 1038337
-PRIMES = {"fold60": 0xfffffffffff2801, "shoup50": 0x3ffffffffa801}
+PRIMES = {"fold60": 0xfffffffffff2801, "shoup50": 0x3ffffffffa801, "f64_45": 0x1fffffff9001}  # the last: prime 0 of (1024, {45, 55, 50}), fp64 engine
 Q35 = 0x7ffffc801
 
 
@@ -110,6 +110,7 @@ def test_switch_edges():
 def test_widths():
     q60 = PRIMES["fold60"]
     assert ref.max_width(8192, q60) == 46 and ref.max_width(32768, q60) == 44 and ref.max_width(1024, q60) == 49
+    assert ref.max_width(N, PRIMES["f64_45"]) == 34 and ref.accepted(N, PRIMES["f64_45"], *ref.safe_bits(N, T))
     assert ref.safe_bits(8192, T) == (22, 35) and ref.reply_bytes(8192, 22, 35) == 58368
     assert ref.safe_bits(32768, T) == (22, 37) and ref.reply_bytes(32768, 22, 37) == 241664
     assert not ref.accepted(1024, Q35, *ref.safe_bits(1024, T))  # a 35-bit first prime cannot hold the safe pair

@@ -1,12 +1,16 @@
-"""The device-free references of bfv_ring_ref.py, held to Python integers before test_gpu_bfv_large_rings.py trusts them (no GPU):
+"""The device-free references of bfv_ring_ref.py, held to Python integers before test_gpu_bfv_large_rings.py and test_gpu_bfv_chain_layouts.py
+trust them (no GPU).  The first four run at N = 1024 on {50, 40, 50} and on the N = 1024 versions of the chain layouts: {45, 55, 50},
+{60, 60, 60}, {42, 38, 44} and {40, 60, 50, 60} (the counts pinned on the first chain stay pinned there):
 
-* external_product_ref and rgsw_from_bfv_ref (its k = 1 rows after oracle.intt) against the schoolbook negacyclic sum, N = 1024, {50, 40, 50}, at 8
+* external_product_ref and rgsw_from_bfv_ref (its k = 1 rows after oracle.intt) against the schoolbook negacyclic sum, at 8
   output coefficients (0, 1, 511, 512, 1022, 1023 and two random ones), both polynomials, every prime: N products per coefficient and term;
   the k = 0 rows are oracle.ntt of the slot ciphertext, and every row lies where bfv_selector_ref.row says;
 * decompose_ntt_ref, unpack_bytes_ntt_ref and gadget_ntt_ref against oracle.ntt of digits cut and lifted in Python integers (bfv_gadget_ref.digit /
   lift, int.from_bytes), whole polynomials of the source words those coefficients belong to; np_lift against bfv_gadget_ref.lift at its edges;
 * the five chains of test_gpu_bfv_large_rings.py build in the oracle, and their engines are what that module means: a 40-bit prime (fp64 engine)
-  beside 60-bit primes of the form 2^60 - c ... (fold form) or 50-bit primes (Shoup form); the plain moduli are the ones its shapes assume."""
+  beside 60-bit primes of the form 2^60 - c ... (fold form) or 50-bit primes (Shoup form); the plain moduli are the ones its shapes assume;
+* the five layouts of test_gpu_bfv_chain_layouts.py build in the oracle: bit lengths, t, the engine of every prime, the form by the rule of
+  he_params.cpp, the two data primes of {60, 60, 60}, the gadget totals at v = 20 and v = 4, and the reply widths each first prime accepts."""
 import numpy as np
 import pytest
 
@@ -15,6 +19,9 @@ import bfv_ring_ref as ring
 import bfv_selector_ref as sel
 
 N, BITS, PB = 1024, [50, 40, 50], 20
+# the chain every count below was first pinned on, then the N = 1024 versions of the layouts of test_gpu_bfv_chain_layouts.py: an fp64 prime 0
+# beside a u64 one, no fp64 prime, no u64 prime, and 60-bit primes in the Shoup form around a 40-bit one
+CTX_CHAINS = {"n1024": BITS, "f64_first": [45, 55, 50], "u64_only": [60, 60, 60], "f64_only": [42, 38, 44], "shoup_60": [40, 60, 50, 60]}
 LARGE = {
     "n8192_fold": (8192, [60, 40, 60], 20),
     "n16384_fold": (16384, [60, 40, 40, 60], 20),
@@ -24,9 +31,17 @@ LARGE = {
 }
 
 
-@pytest.fixture(scope="module")
-def ctx(oracle):
-    return oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=BITS, plain_bits=PB, sec128=False)
+@pytest.fixture(scope="module", params=list(CTX_CHAINS))
+def ctx(oracle, request):
+    bits = CTX_CHAINS[request.param]
+    o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=PB, sec128=False)
+    assert [q.bit_length() for q in o.moduli] == bits and o.L == len(bits) - 1
+    return o
+
+
+def pinned(o):
+    """the original chain, whose counts stay as they were asserted before the other chains came"""
+    return [q.bit_length() for q in o.moduli] == BITS
 
 
 def coefficients(rng):
@@ -79,7 +94,9 @@ def test_external_product_ref_is_the_schoolbook_sum(ctx):
     o, rng = ctx, np.random.default_rng(201)
     L, v, inner = o.L, 20, 2
     rows = 2 * gad.table(o.moduli[:L], v)[1][-1]
-    assert (L, rows) == (2, 10)
+    assert rows == 2 * sum(-(-q.bit_length() // v) for q in o.moduli[:L]) and rows >= 2 * L
+    if pinned(o):
+        assert (L, rows) == (2, 10)
     cts = edged(o, rng, inner, L)
     rg = uniform_rows(o, rng, inner * rows, L)
     got = ring.external_product_ref(o, cts, rg.reshape(inner, rows, 2, L, N), v)
@@ -94,7 +111,9 @@ def test_rgsw_from_bfv_ref_is_the_schoolbook_sum_and_the_row_rule(ctx):
     L, v, kv, n_rg = o.L, 45, 20, 2
     E = gad.table(o.moduli[:L], v)[1][-1]
     rows = 2 * gad.table(o.moduli[:L], kv)[1][-1]
-    assert (E, rows) == (3, 10)
+    assert E == sum(-(-q.bit_length() // v) for q in o.moduli[:L]) and rows == 2 * sum(-(-q.bit_length() // kv) for q in o.moduli[:L])
+    if pinned(o):
+        assert (E, rows) == (3, 10)
     slots = edged(o, rng, n_rg * E, L)
     key = uniform_rows(o, rng, rows, L)
     got = ring.rgsw_from_bfv_ref(o, slots, key, v, kv)
@@ -177,3 +196,40 @@ def test_the_large_chains_build_and_their_engines_are_what_is_meant(oracle, name
         assert all(q.bit_length() == 50 for q in wide)
     # the counts the large-ring shapes are sized by
     assert gad.table(data, 20)[1][-1] == {2: 5, 3: 7}[o.L]
+
+
+# the layouts of test_gpu_bfv_chain_layouts.py: (N, bit sizes), t, the u64 form by the rule of he_params.cpp (None: no u64 prime), the gadget
+# totals E(L) at v = 20 and v = 4 its shapes are sized by, the largest accepted reply width, whether the safe reply widths are accepted
+LAYOUTS = {
+    "f64_first": ((2048, [40, 60, 60]), 1032193, "fold", 5, 25, 28, False),
+    "u64_only": ((2048, [60, 60, 60]), 1032193, "fold", 6, 30, 48, True),
+    "f64_only": ((2048, [42, 38, 45, 44]), 1032193, None, 8, 33, 30, False),
+    "shoup_60": ((2048, [60, 50, 40, 60]), 1032193, "shoup", 8, 38, 48, True),
+    "f64_first_1024": ((1024, [45, 55, 50]), 1038337, "shoup", 6, 26, 34, True),
+}
+
+
+@pytest.mark.parametrize("name", list(LAYOUTS))
+def test_the_chain_layouts_build_and_their_engines_are_what_is_meant(oracle, name):
+    import bfv_reply_ref as rep
+    (n, bits), t, form, e20, e4, top, safe = LAYOUTS[name]
+    o = oracle.Context(oracle.SCHEME_BFV, n, bit_sizes=bits, plain_bits=20, sec128=False)
+    assert o.N == n and o.L == len(bits) - 1 and [q.bit_length() for q in o.moduli] == bits
+    assert o.t == t and t.bit_length() == 20
+    assert len(set(o.moduli)) == len(bits) and all(q % (2 * n) == 1 for q in o.moduli)
+    wide = [q for q in o.moduli if q >= 2 ** 47]  # the u64 engine's primes; the form is the context's, so the key prime counts
+    assert [q >= 2 ** 47 for q in o.moduli] == [b >= 47 for b in bits]
+    if form is None:
+        assert not wide
+    else:  # the fold form takes primes 2^60 - c with c < 2^26 only; one prime that is not selects the Shoup form for all
+        assert (form == "fold") == all(0 < 2 ** 60 - q < 2 ** 26 for q in wide)
+    if name == "u64_only":
+        assert o.moduli[:2] == [2 ** 60 - 0x27fff, 2 ** 60 - 0x17fff]
+    if name == "shoup_60":  # 60-bit primes of the fold's own shape, in the Shoup form because of the 50-bit prime
+        assert 0 < 2 ** 60 - o.moduli[0] < 2 ** 26 and o.moduli[1].bit_length() == 50
+    data = o.moduli[:o.L]
+    assert gad.table(data, 20)[1][-1] == e20 and gad.table(data, 4)[1][-1] == e4
+    assert gad.table(data, 63)[0] == [1] * o.L  # v = 63: the digit is the residue
+    q0 = o.moduli[0]
+    assert rep.max_width(n, q0) == top and rep.accepted(n, q0, *rep.safe_bits(n, t)) == safe
+    assert rep.safe_bits(n, t) == (22, 22 + n.bit_length() - 1)

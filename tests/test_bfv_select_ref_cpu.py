@@ -4,8 +4,8 @@
 * folding index lists and walking down from the root name the same leaf; where sum b_j 2^j < count that leaf is the index itself, and where it
   is not the leaf is still below count (the pass-through rule decides: count = 5, bits (1, 0, 1) give leaf 4);
 * every leaf is reachable;
-* the noiseless CMUX over polynomial leaves on negacyclic rings of 4 and 8 coefficients, under a 17-bit and a 40-bit modulus, returns exactly
-  the selected leaf's polynomial.
+* the noiseless CMUX over polynomial leaves on negacyclic rings of 4 and 8 coefficients, under a 17-bit, a 40-bit and a 45-bit modulus,
+  returns exactly the selected leaf's polynomial.
 No GPU."""
 import itertools
 import random
@@ -45,7 +45,7 @@ def test_which_leaf_every_bit_vector(count):
         assert ref.selected_leaf(5, (1, 0, 1)) == 4 and ref.selected_leaf(5, (1, 1, 1)) == 4 and ref.selected_leaf(5, (0, 1, 1)) == 4
 
 
-@pytest.mark.parametrize("n,q", [(4, 65537), (8, 1099511480321)])
+@pytest.mark.parametrize("n,q", [(4, 65537), (8, 1099511480321), (4, 0x1fffffff9001)])  # the last: prime 0 of (1024, {45, 55, 50})
 def test_noiseless_cmux_returns_the_selected_leaf(n, q):
     rng = random.Random(7 * n)
     for count in COUNTS:

@@ -25,7 +25,8 @@ import csim_lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
-CHAINS = {"n1024": (1024, [50, 40, 50], 20), "n2048": (2048, [60, 40, 60], 20), "n4096_d3": (4096, [60, 40, 40, 60], 20)}
+CHAINS = {"n1024": (1024, [50, 40, 50], 20), "n2048": (2048, [60, 40, 60], 20), "n4096_d3": (4096, [60, 40, 40, 60], 20),
+          "n1024_f64_first": (1024, [45, 55, 50], 20)}  # the last: an fp64 prime 0 beside a u64 one (test_gpu_bfv_chain_layouts.py)
 WIDTHS = (4, 20, 45, 63)
 NEW = ["he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv"]
 
@@ -154,7 +155,7 @@ def test_refusals_are_decided_on_the_host(be, newlib):
     E = ctx.bfv_gadget_count(Lt, v)[0]
     per = 2 * Lt * N
     a = np.full(4 * E * per + N, 0xABCD, dtype=np.uint64)      # selectors / slot ciphertexts, and room for an output behind them
-    k = np.full(2 * E * per, 0xABCD, dtype=np.uint64)          # the key
+    k = np.full(max(2 * E * per, 2 * 60 * 2 * N), 0xABCD, dtype=np.uint64)  # the key: 2 E rows at (Lt, v), 2 x 60 rows of 2 N words at (L, key_bits) = (1, 1)
     b = np.full(6 * E * per, 0xABCD, dtype=np.uint64)          # query ciphertexts / RGSW ciphertexts, and room for ciphertexts behind them
     pa, pk, pb = (x.ctypes.data_as(C.c_void_p) for x in (a, k, b))
     at = lambda base, words: C.c_void_p(base.value + 8 * words)
