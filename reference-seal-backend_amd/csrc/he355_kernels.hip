@@ -461,8 +461,24 @@ struct K1Args {
     KsGroups groups;           // K1_GALOIS, grouped launch (group_size > 0): op's source ciphertext and permutation table come from its group
 };
 
+// The two operand rows of a K1_MUL_C2 row job.  The throughput shape requests them before it stages the block's twiddles (k_k1): they need
+// none, and their way from HBM then runs beside the staging instead of behind its barrier.  (K1_MUL's four rows stay where they are:
+// held across the staging they cost its instantiations 30 registers and with them the third wave per SIMD.)
+struct K1RowsC2 {
+    u64 a1[kRowE], b1[kRowE];
+};
+__device__ __forceinline__ void k1_load_rows_c2(const K1Args &A, u64 op, int i, u32 a_row, int lane, K1RowsC2 &R)
+{
+    const u64 N = (u64)(1u << A.logn1) << kRowLog, P1 = (u64)A.L * N;
+    const u64 roff = (u64)i * N + ((u64)a_row << kRowLog);
+    const u64 r = A.op_offset + op;
+    load_rowC(A.a + (idx_a(A.ix, r) * 2 + 1) * P1 + roff, lane, R.a1);
+    load_rowC(A.b + (idx_b(A.ix, r) * 2 + 1) * P1 + roff, lane, R.b1);
+}
+
 template <class Ar, int MODE, class ITW = int>
-__device__ __forceinline__ void k1_job(const K1Args &A, const PrimeDev &P, u64 op, int i, u32 a_row, int lane, u64 *lds, bool valid, const ITW *staged = nullptr)
+__device__ __forceinline__ void k1_job(const K1Args &A, const PrimeDev &P, u64 op, int i, u32 a_row, int lane, u64 *lds, bool valid, const ITW *staged = nullptr,
+                                       const K1RowsC2 *rows_c2 = nullptr) // rows_c2 (K1_MUL_C2): the operand rows, requested by the caller
 {
     typedef typename Ar::T T;
     const Ar ar = make_ar(P, (Ar *)nullptr);
@@ -481,10 +497,8 @@ __device__ __forceinline__ void k1_job(const K1Args &A, const PrimeDev &P, u64 o
         u64 a0[kRowE], a1[kRowE], b0[kRowE], b1[kRowE];
         u64 v2[kRowE];
         if (MODE == K1_MUL_C2) { // only the key-switch target c2 = a1 b1, through the inverse row pass (c0, c1 are computed by the fused k_k3 from the operands): half the reads, a quarter of the writes
-            load_rowC(pa + P1, lane, a1);
-            load_rowC(pb + P1, lane, b1);
 #pragma unroll
-            for (int r2 = 0; r2 < kRowE; ++r2) x[r2] = ar.dy_mul(ar.dy_in(a1[r2]), ar.dy_in(b1[r2])); // the product as it is (fp64 engine: centred lazy, |x| < q): nothing here reads the canonical integer
+            for (int r2 = 0; r2 < kRowE; ++r2) x[r2] = ar.dy_mul(ar.dy_in(rows_c2->a1[r2]), ar.dy_in(rows_c2->b1[r2])); // the product as it is (fp64 engine: centred lazy, |x| < q): nothing here reads the canonical integer
             // (no c2n row either: the fused k_k3 of a ct x ct multiply forms a1 b1 itself, from the rows it reads for c0, c1)
         } else {
         load_rowC(pa, lane, a0); load_rowC(pa + P1, lane, a1);
@@ -595,9 +609,19 @@ __global__ void __launch_bounds__(kBlock) k_k1(K1Args A, const PrimeDev *primes)
     if (!valid) op = A.n_ops - 1;
     const PrimeDev &P = primes[i];
     const Ar ar = make_ar(P, (Ar *)nullptr);
-    const auto itw = stage_row_twiddles<Ar, kBlock>(P, ar, n1 + a_row, twl_raw, true);
-    __syncthreads();
-    k1_job<Ar, MODE>(A, P, op, i, a_row, lane, lds[wave], valid, &itw);
+    if constexpr (MODE == K1_MUL_C2) {
+        // the operand rows are requested first and read behind the barrier: results return in issue order, so the wait for the twiddles
+        // covers them too, and the block pays the longer of the two latencies, not their sum
+        K1RowsC2 rows;
+        k1_load_rows_c2(A, op, i, a_row, lane, rows);
+        const auto itw = stage_row_twiddles<Ar, kBlock>(P, ar, n1 + a_row, twl_raw, true);
+        __syncthreads();
+        k1_job<Ar, MODE>(A, P, op, i, a_row, lane, lds[wave], valid, &itw, &rows);
+    } else {
+        const auto itw = stage_row_twiddles<Ar, kBlock>(P, ar, n1 + a_row, twl_raw, true);
+        __syncthreads();
+        k1_job<Ar, MODE>(A, P, op, i, a_row, lane, lds[wave], valid, &itw);
+    }
 }
 // Latency shape: the fp64-engine residues (blocks 0 .. n_f - 1) and the u64-engine residues of one key switch in ONE launch (see k_k3_dual)
 template <int MODE, class Ar>

@@ -47,7 +47,7 @@
         Acc acc0[kRowE], acc1[kRowE];
 #pragma unroll
         for (int r = 0; r < kRowE; ++r) { acc0[r] = 0; acc1[r] = 0; }
-        auto tensor_init = [&]() {
+        auto tensor_init = [&](T c2[kRowE]) {
             if constexpr (TENSOR) {
                 // ct x ct multiply: c0 = a0 b0 and c1 = a0 b1 + a1 b0 are not read back from k_k1's c01 rows, they start the sums -- here,
                 // where no other row is live yet (the first digit row is on its way into LDS meanwhile).  The floor step computes
@@ -55,6 +55,8 @@
                 // handed key residues that carry the factor P^-1 already (DeviceContext::relin_scaled), so its sums ARE sums * P^-1 and the
                 // addend joins them as it is: the results are sums' - x * P^-1 and (sums' - x) * q_last^-1 (floor_fin_s / floor_fin2_s), the
                 // same residues exactly (modular identities), with two products per element fewer at this end and one fewer at that.
+                // Three products from one load and one conversion of each operand row: c0 = a0 b0, c2 = a1 b1 (the digit that lives under
+                // this prime, handed to the caller) and c1 = (a0 + a1)(b0 + b1) - c0 - c2, the same residue as a0 b1 + a1 b0 (dy_mul3).
                 const u64 tr = A.t_op_offset + op;
                 const u64 LNt = (u64)A.L * N;
                 const u64 *pa = A.ta + idx_a(A.tix, tr) * 2 * LNt + (u64)tt * N + rowoff;
@@ -64,9 +66,10 @@
                 load_rowC(pa + LNt, lane, a1); load_rowC(pb + LNt, lane, b1);
 #pragma unroll
                 for (int r = 0; r < kRowE; ++r) {
-                    const T x0 = ar.dy_in(a0[r]), x1 = ar.dy_in(a1[r]), y0 = ar.dy_in(b0[r]), y1 = ar.dy_in(b1[r]);
-                    acc0[r] = ar.acc_from_lazy(ar.dy_mul(x0, y0));
-                    acc1[r] = ar.acc_from_lazy(ar.dy_add(ar.dy_mul(x0, y1), ar.dy_mul(x1, y0)));
+                    T p0, p1;
+                    ar.dy_mul3(ar.dy_in(a0[r]), ar.dy_in(a1[r]), ar.dy_in(b0[r]), ar.dy_in(b1[r]), p0, p1, c2[r]);
+                    acc0[r] = ar.acc_from_lazy(p0);
+                    acc1[r] = ar.acc_from_lazy(p1);
                 }
             }
         };
@@ -144,20 +147,13 @@
         const int i_begin = nd * grp / split, i_end = nd * (grp + 1) / split;
         auto src_row = [&](int j) -> const u64 * { return A.d + ((op * (A.L + 1) + tt) * A.L + j) * N + rowoff; };
         if (i_begin < i_end) dma_row_to_lds<kDigitPieces>(src_row(digit(i_begin)), stage[wave], lane);
-        tensor_init();
+        T c2[kRowE]; // TENSOR: a1 b1 out of tensor_init, dead again behind the own digit's key product (nothing else lives across it)
+        tensor_init(c2);
         if (has_own && grp == 0) {
             if constexpr (TENSOR) {
-                // the digit that lives under this prime is c2 = a1 b1 in NTT form: formed here (k_k1 writes no c2n row for a ct x ct
-                // multiply) from the two operand rows tensor_init has just pulled through the caches
-                const u64 tr = A.t_op_offset + op;
-                const u64 LNt = (u64)A.L * N;
-                u64 a1[kRowE], b1[kRowE];
-                load_rowC(A.ta + (idx_a(A.tix, tr) * 2 + 1) * LNt + (u64)tt * N + rowoff, lane, a1);
-                load_rowC(A.tb + (idx_b(A.tix, tr) * 2 + 1) * LNt + (u64)tt * N + rowoff, lane, b1);
-                T x[kRowE];
-#pragma unroll
-                for (int r = 0; r < kRowE; ++r) x[r] = ar.dy_mul(ar.dy_in(a1[r]), ar.dy_in(b1[r])); // the product as it is (fp64 engine: centred lazy, |x| < q; the key product takes any |x k| < 2^100)
-                mac_digit(x, tt);
+                // the digit that lives under this prime is c2 = a1 b1 in NTT form (k_k1 writes no c2n row for a ct x ct multiply): the
+                // product as tensor_init formed it (fp64 engine: centred lazy, |x| < q; the key product takes any |x k| < 2^100)
+                mac_digit(c2, tt);
             } else {
                 T x[kRowE];
                 u64 v[kRowE];
@@ -233,14 +229,15 @@
             }
             acc_flush();
             // fp64 engine: the floor steps read the double sums as they are (no canonical integer in between).  Where this prime's bound
-            // does not hold for the launch's number of terms (at most L digits and the two operand products; modarith.h,
-            // floor_direct_terms) sums and correction row are re-centred first -- one wave-uniform branch per row.
+            // does not hold for the launch's number of terms (at most L digits and the operand products: three centred terms in c1 =
+            // (a0 + a1)(b0 + b1) - a0 b0 - a1 b1 of a ct x ct multiply, kTensorTerms; modarith.h, floor_direct_terms) sums and correction
+            // row are re-centred first -- one wave-uniform branch per row.
             // (Read here, behind the digit loop: one more value live across it costs the rotation instantiations spilled registers.)
             // kAccForms: the plain rotation / size-3 instantiation <FUSE, !TENSOR, !GROUPED> keeps the canonical forms -- with the accumulator
             // forms its allocation changes (34 -> 58 spilled registers on the fp64 engine, one reload inside the digit step, whose
             // s_waitcnt also waits for the prefetched row: DotProduct 38.9 -> 41.1 ms per step), the other instantiations' improves.
             constexpr bool kAccForms = TENSOR || GROUPED;
-            const bool direct = kAccForms && Ar::kAccDirect && floor_direct(P.acc_terms, (u32)A.L + 2);
+            const bool direct = kAccForms && Ar::kAccDirect && floor_direct(P.acc_terms, (u32)A.L + (TENSOR ? kTensorTerms : 2u));
             // correction rows: transform + floor step(s)
 #pragma unroll 1
             for (int i = nd; FUSE && i < n_rows; ++i) {

@@ -192,6 +192,16 @@ struct ArU64 {
     HE_HD T dy_in(u64 c) const { return c; }
     HE_HD T dy_mul(T x, T y) const { return barrett128((u128)x * y, mod()); }
     HE_HD T dy_add(T x, T y) const { return addmod(x, y, q); }
+    // The tensor of two size-2 ciphertexts from three products: c0 = a0 b0, c2 = a1 b1, c1 = (a0 + a1)(b0 + b1) - c0 - c2 == a0 b1 + a1 b0.
+    // Canonical in, canonical out: the sums are addmod results (below q, so the third product has the range of the other two,
+    // below q^2, which is dy_mul's own), the differences submod of canonical values.  Two addmod and two submod (two instructions
+    // each) for one 128-bit Barrett product.
+    HE_HD void dy_mul3(T a0, T a1, T b0, T b1, T &c0, T &c1, T &c2) const
+    {
+        c0 = dy_mul(a0, b0);
+        c2 = dy_mul(a1, b1);
+        c1 = submod(submod(dy_mul(addmod(a0, a1, q), addmod(b0, b1, q)), c0, q), c2, q);
+    }
     HE_HD u64 dy_out(T x) const { return x; }
     HE_HD T key_in(u64 bits) const { return bits; }
     typedef u64 Acc;
@@ -520,6 +530,17 @@ struct ArF64 {
     HE_HD T dy_in(u64 c) const { return u52_to_f64(c); }
     HE_HD T dy_mul(T x, T y) const { return mulmod_vv(x, y); }
     HE_HD T dy_add(T x, T y) const { return x + y; }
+    // The tensor of two size-2 ciphertexts from three products (see ArU64::dy_mul3), operands canonical as doubles.  The sums are
+    // exact integers below 2q < 2^48, their product is below 4 q^2 < 2^96, inside mulmod_vv's 2^100; each product comes back centred,
+    // |.| <= q (1/2 + 4q 2^-51) for the third (mulmod_vv's bound with |x| = 4q against a canonical y) and q (1/2 + q 2^-51) for c0 and
+    // c2, and c1 is the exact integer difference of the three: a centred lazy residue of a0 b1 + a1 b0 made of kTensorTerms terms,
+    // |c1| <= q (3/4 + 2 * 9/16) < 2q for every q < 2^47.
+    HE_HD void dy_mul3(T a0, T a1, T b0, T b1, T &c0, T &c1, T &c2) const
+    {
+        c0 = mulmod_vv(a0, b0);
+        c2 = mulmod_vv(a1, b1);
+        c1 = mulmod_vv(a0 + a1, b0 + b1) - c0 - c2;
+    }
     HE_HD u64 dy_out(T x) const { return to_canon2(x); }
     HE_HD T key_in(u64 bits) const { return from_raw(bits); }
     static constexpr bool kKeyQuotient = false;
@@ -681,12 +702,16 @@ struct ArF64 {
 //        the source is wider than 2q, plus at most one centred product of the merged second correction) and runs at most 5 column and
 //        10 row stages.
 //   acc: every term is a mulmod_vv product x * key, key canonical, |product| <= q (1/2 + |x| 2^-51).  The widest x is a digit row:
-//        below 2^47 out of its 48-bit packed form, then 10 row stages.  (The operand products a0 b0 ... and the own digit have
-//        |x| < q.)  `terms` products of that size are the bound of the sum.
-// The library admits fp64-engine primes up to 2^47 and chains up to kMaxPrimes: a 45-bit prime takes 24 terms (L <= 22 with the two
-// operand products of a ct x ct multiply), a 40-bit prime any chain, a 46- or 47-bit prime none (its correction rows alone can pass
+//        below 2^47 out of its 48-bit packed form, then 10 row stages.  (The own digit has |x| < q.  The operand products of a
+//        ct x ct multiply, ArF64::dy_mul3: a0 b0 and a1 b1 have |x| < q; the third, (a0 + a1)(b0 + b1), multiplies two values below 2q,
+//        which is the bound of |x| = 4q against a canonical key -- and 4q is below the digit row's 2^47 + 5q after ten stages.  So each
+//        of the kTensorTerms = 3 terms of c1 = (a0 + a1)(b0 + b1) - a0 b0 - a1 b1 is inside the bound of one term, and the c1 sums
+//        of such a launch hold L + kTensorTerms of them; the c0 sums L + 1.)  `terms` products of that size are the bound of the sum.
+// The library admits fp64-engine primes up to 2^47 and chains up to kMaxPrimes: a 45-bit prime takes 24 terms (L <= 21 with the three
+// operand terms of a ct x ct multiply), a 40-bit prime any chain, a 46- or 47-bit prime none (its correction rows alone can pass
 // 2^49) -- those launches re-centre sums and rows first (ArF64::floor_prep).
 constexpr double kFloorAccMax = 562949953421312.0, kFloorXMax = 562949953421312.0; // 2^49
+constexpr unsigned kTensorTerms = 3; // centred terms the operand rows put into one sum of a ct x ct multiply (k_k3<TENSOR>)
 HE_HD double f64_stage_growth(double m, double q, int stages)
 {
     for (int s = 0; s < stages; ++s) m += q * (0.5 + m * 4.440892098500626e-16); // 2^-51
