@@ -538,6 +538,54 @@ int he355_bfv_reply_safe_bits(const he355_ctx *ctx, int *k0, int *k1);
 int he355_bfv_reply_compress(he355_ctx *ctx, int L, int k0, int k1, uint64_t n, const uint64_t *d_ct, void *d_bytes, uint64_t stride_bytes);
 int he355_bfv_reply_decrypt(he355_ctx *ctx, int k0, int k1, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t *d_plain, int32_t *d_budget,
                             int32_t *d_noise_bits);
+/* ---- seeded BFV queries and Galois keys (BFV contexts only).  A secret-key encryption (c0, c1) has a uniform c1: the client sends c0 and the
+ * SEED of c1, and the server regenerates c1 on the device.  That halves every query ciphertext and every Galois key on the way up.
+ * [UPSTREAM-UNVERIFIED] the idea is SEAL's encrypt_zero_symmetric with a seeded c1 (Serializable<>), SealPIR's, OnionPIR's and Spiral's;
+ * the definition is this library's own, exact integers, no tolerance:
+ *     seeds      : a_seed IS PUBLIC AND TRAVELS WITH THE CIPHERTEXT.  noise_seed IS SECRET AND NEVER LEAVES THE CLIENT.  THE TWO MUST
+ *                  DIFFER: the generator is the library's counter-based one (csrc/client/sampler.h), whose mixing step splitmix64 is
+ *                  invertible, so whoever knows the seed of a stream knows the stream -- a call with a_seed == noise_seed would publish
+ *                  the error and is refused.  THE GENERATOR IS NOT A CRYPTOGRAPHIC XOF: the seeded half is only as unpredictable as
+ *                  splitmix64 makes it, exactly like every other random polynomial of this library; swapping in an XOF (SHAKE, BLAKE2
+ *                  as SEAL does) is out of scope here.  A (a_seed, index) pair must never be reused for two different ciphertexts, and a
+ *                  noise_seed never with another a_seed.
+ *     streams    : ciphertext r of a call is seeded ciphertext first_index + r, below 2^40.  Its uniform half under prime i uses stream
+ *                  seeded_a_stream(first_index + r, i) = 2^48 + 64 (first_index + r) + i, its error stream
+ *                  seeded_e_stream(first_index + r) = 2^48 + 64 (first_index + r) + 63 (sampler.h): apart from enc_stream and keygen_stream.
+ *     seeded half: IN NTT FORM, the form he355_keygen_* sample in: a^_i[n] = sample_uniform_at(a_seed, seeded_a_stream(first_index + r, i), n, q_i),
+ *                  n the position in he355_ntt_forward's output order.
+ *     seeded zero: at level L, built there (no special prime, no divide-and-round): c0_i = (-e - iNTT_i(a^_i (.) s^_i)) mod q_i with
+ *                  e[n] = sample_cbd_at(noise_seed, seeded_e_stream(first_index + r), n), and c1_i = iNTT_i(a^_i).  (c0, c1) is an ordinary
+ *                  coefficient-form BFV ciphertext [2][L][N] with phase c0 + c1 s = -e: every existing call accepts it.
+ *   he355_bfv_seeded_encrypt          (client) d_plain [n][N] mod t, or NULL for zeros -> d_c0 [n][L][N], coefficient form.  By definition d_c0
+ *                                     followed by he355_bfv_seeded_restore(ntt_form 0) is bit-identical to he355_bfv_add_plain(L, 2, ..) applied
+ *                                     to the restored seeded zero.  Needs he355_set_secret_key and nothing else.
+ *   he355_bfv_seeded_selector_encrypt (client) polynomial 0 of he355_bfv_selector_encrypt with its public-key zero replaced by the seeded zero:
+ *                                     the same plants in the same places, d_c0 [n][L][N].  The first dimension joins as before: the caller adds
+ *                                     this c0 to the he355_bfv_seeded_encrypt c0 of ANOTHER index range with he355_add(L, 1, n, ..) and sends
+ *                                     the one sum with both first_index values; the server restores the sum under one range and a zero c0 under
+ *                                     the other (or both c0's, if they travel apart) and adds the two with he355_add(L, 2, n, ..) -- the sum is a
+ *                                     ciphertext of the sum under the sum of the two seeded halves.
+ *   he355_bfv_seeded_restore          (server) d_c0 [n][L][N] -> d_out [n][2][L][N].  ntt_form 0: c0 copied, c1 = iNTT(a^): what he355_bfv_expand
+ *                                     reads.  ntt_form 1: c0 = NTT(c0), c1 = a^: the rows the NTT-form calls read, bit-identical to
+ *                                     he355_bfv_transform_to_ntt of the other form.  Needs no key and no scratch.
+ *   he355_keygen_galois_seeded        (client) the `b` halves [L_top][K][N], NTT form, of the Galois key of galois_elt into a DEVICE buffer; digit j,
+ *                                     prime i: a = sample_uniform_at(a_seed, keygen_stream(2 + elt, j, K, i), n, q_i), e = sample_cbd_at(noise_seed,
+ *                                     keygen_stream(2 + elt, j, K, K), n), b = -(a s + NTT(e)) + [i == j] (P mod q_j) s(X^elt) -- he355_keygen_galois's
+ *                                     key with the one seed split in two.  Installs nothing.  One a_seed may serve every element of a client.
+ *   he355_set_galois_key_seeded       (server) h_b [L_top][K][N] on the HOST -> key[j][0]; key[j][1] generated on the device from a_seed; by
+ *                                     definition bit-identical to he355_set_galois_key of the full key [L_top][2][K][N].
+ * Refused with HE355_E_INVALID_ARGS on the host, before any device is asked for, the outputs untouched: a CKKS context, L outside 1..L_top,
+ * ntt_form outside {0, 1}, a_seed == noise_seed, first_index + n wrapping or above 2^40, a slab of more than 2^60 words, a grid above
+ * 2^31 - 1 blocks (n L N / 512; restore: 2 n L N / 512), any overlap of output and input, he355_bfv_selector_encrypt's own rules, an invalid
+ * Galois element, a chain without a special prime; and, before the first launch, a missing secret key (the three client calls).  n == 0
+ * touches nothing.  Everything is queued on the context's stream; he355_set_galois_key_seeded returns with the key installed. */
+int he355_bfv_seeded_encrypt(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain, uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0);
+int he355_bfv_seeded_selector_encrypt(he355_ctx *ctx, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel,
+                                      uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0);
+int he355_bfv_seeded_restore(he355_ctx *ctx, int L, int ntt_form, uint64_t n, const uint64_t *d_c0, uint64_t a_seed, uint64_t first_index, uint64_t *d_out);
+int he355_keygen_galois_seeded(he355_ctx *ctx, uint32_t galois_elt, uint64_t a_seed, uint64_t noise_seed, uint64_t *d_b);
+int he355_set_galois_key_seeded(he355_ctx *ctx, uint32_t galois_elt, const uint64_t *h_b, uint64_t a_seed);
 /* Decryptor::invariant_noise_budget, batched: how many bits of noise budget each ciphertext has left AT ITS LEVEL -- what a caller asks
  * before he355_bfv_mod_switch ("is the switch safe?") or another multiply.  BFV contexts only; needs he355_set_secret_key.
  * d_ct [n][size][L][N] coefficient form, size 2 or 3, 1 <= L <= L_top (<= 16, as he355_decrypt).

@@ -158,6 +158,11 @@ def lib():
             "he355_bfv_reply_safe_bits": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
             "he355_bfv_reply_compress": (i32, [vp, i32, i32, i32, u64, vp, vp, u64]),
             "he355_bfv_reply_decrypt": (i32, [vp, i32, i32, u64, vp, u64, vp, vp, vp]),
+            "he355_bfv_seeded_encrypt": (i32, [vp, i32, u64, vp, u64, u64, u64, vp]),
+            "he355_bfv_seeded_selector_encrypt": (i32, [vp, i32, i32, u64, u64, u64, u64, vp, u64, u64, u64, vp]),
+            "he355_bfv_seeded_restore": (i32, [vp, i32, i32, u64, vp, u64, u64, vp]),
+            "he355_keygen_galois_seeded": (i32, [vp, u32, u64, u64, vp]),
+            "he355_set_galois_key_seeded": (i32, [vp, u32, _u64p, u64]),
             "he355_sum": (i32, [vp, i32, i32, u64, vp, vp]),
             "he355_multiply_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
             "he355_bfv_multiply_relin_accumulate": (i32, [vp, i32, u64, u64, u64, vp, u64, u64, vp, u64, u64, vp]),
@@ -204,7 +209,7 @@ C_ABI_SYMBOLS = [
     "he355_set_galois_key_synthetic", "he355_add", "he355_sub", "he355_multiply", "he355_bfv_multiply", "he355_multiply_relin",
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
-    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
+    "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
     "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
@@ -583,6 +588,30 @@ class Context:
         finally:
             out.free()
         return v[:n].copy(), v[n:2 * n].copy()
+
+    def bfv_seeded_encrypt(self, L, n, plain, a_seed, noise_seed, first_index, c0):
+        """(client) plain [n][N] mod t, or None for zeros -> c0 [n][L][N], coefficient form: Delta_L(m) - e - iNTT(a (.) s) with a the uniform
+        half a_seed (PUBLIC) stands for and e drawn from noise_seed (SECRET, different); needs set_secret_key only"""
+        _check(lib().he355_bfv_seeded_encrypt(self.h, L, n, plain.ptr if plain is not None else None, a_seed, noise_seed, first_index, c0.ptr))
+
+    def bfv_seeded_selector_encrypt(self, L, digit_bits, n, n_sel, first_slot, count, sel, a_seed, noise_seed, first_index, c0):
+        """(client) polynomial 0 of bfv_selector_encrypt over the seeded zero: c0 [n][L][N]"""
+        _check(lib().he355_bfv_seeded_selector_encrypt(self.h, L, digit_bits, n, n_sel, first_slot, count, sel.ptr, a_seed, noise_seed, first_index, c0.ptr))
+
+    def bfv_seeded_restore(self, L, ntt_form, n, c0, a_seed, first_index, out):
+        """(server) c0 [n][L][N] -> out [n][2][L][N]: ntt_form 0: (c0, iNTT(a)), coefficient form; 1: (NTT(c0), a); needs no key"""
+        _check(lib().he355_bfv_seeded_restore(self.h, L, ntt_form, n, c0.ptr, a_seed, first_index, out.ptr))
+
+    def keygen_galois_seeded(self, elt, a_seed, noise_seed, b):
+        """(client) the `b` halves [L_top][K][N] (NTT form) of the Galois key of `elt` whose `a` halves a_seed stands for, into the device
+        buffer b; installs nothing"""
+        _check(lib().he355_keygen_galois_seeded(self.h, elt, a_seed, noise_seed, b.ptr))
+
+    def set_galois_key_seeded(self, elt, b_halves: np.ndarray, a_seed):
+        """(server) set_galois_key of the key whose `b` halves are b_halves [L_top][K][N] (host) and whose `a` halves a_seed stands for"""
+        k = np.ascontiguousarray(b_halves, dtype=np.uint64)
+        assert k.size == self.L * self.K * self.N
+        _check(lib().he355_set_galois_key_seeded(self.h, elt, k.ctypes.data_as(_u64p), a_seed))
 
     def bfv_noise_budget(self, L, size, n, ct, with_bits=False):
         """Decryptor::invariant_noise_budget of n ciphertexts [n][size][L][N] (size 2 or 3; needs set_secret_key): np.int32[n] bits of

@@ -1,5 +1,5 @@
 // bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, merge, decomposition, the external
-// product, the selection tree and its selectors, database bytes), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
+// product, the selection tree and its selectors, database bytes, reply compression, seeded queries and keys), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
 // device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands what the check worked out (the digit tables, F,
 // rows, terms, pass, the field width) to DeviceContext as a plan.  What needs the device or its state (keys present, the Galois keys, the
 // key-switch tables) is checked there.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
@@ -14,6 +14,7 @@
 #include "bfv_digits_core.h"
 #include "bfv_gadget_core.h"
 #include "bfv_reply_core.h"
+#include "bfv_seeded_core.h"
 #include "he_params.h"
 
 namespace he355 {
@@ -377,6 +378,79 @@ inline BfvReplyPlan plan_reply(const Params &p, const char *what, int L, int k0,
         if (stat_a && stat_b && byte_range(s, stat_a, 4 * n).overlaps(byte_range(s, stat_b, 4 * n))) throw std::invalid_argument(s + ": the two budget outputs overlap");
     }
     return {B};
+}
+
+// ---- seeded queries and Galois keys (he355_bfv_seeded_*, he355_keygen_galois_seeded, he355_set_galois_key_seeded) ----------------------------
+// ciphertext r of a call is seeded ciphertext first_index + r; `c0` is [n][L][N], the restored ciphertexts [n][2][L][N]
+inline void check_seeded_seeds(const std::string &w, u64 a_seed, u64 noise_seed)
+{
+    // splitmix64 is a bijection: with one seed for both, the published seed would give the error away
+    if (a_seed == noise_seed) throw std::invalid_argument(w + ": a_seed (public) and noise_seed (secret) must differ");
+}
+inline void check_seeded_index(const std::string &w, u64 first_index, u64 n)
+{
+    if (first_index + n < first_index || first_index + n > kBfvSeededMaxIndex) throw std::invalid_argument(w + ": first_index + n must not exceed 2^40");
+}
+// `polys_per_ct` residue polynomials per ciphertext in the call's largest slab: its words stay below 2^60 and a streaming launch over it
+// (a block per 512 words) below 2^31 blocks; the transforms' grids are smaller
+inline void check_seeded_size(const Params &p, const std::string &w, u64 n, u64 polys_per_ct)
+{
+    if ((u128)n * polys_per_ct * p.N > ((u128)1 << 60)) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
+    if (n > 0x7fffffffull / (polys_per_ct * (p.N / 512))) throw std::invalid_argument(w + ": too many ciphertexts for one launch (its grid must stay below 2^31 blocks)");
+}
+inline void check_galois_elt(const Params &p, const std::string &w, uint32_t elt)
+{
+    if (!(elt & 1) || elt < 3 || elt >= 2 * p.N) throw std::invalid_argument(w + ": Galois element is not valid (odd, 3 .. 2N - 1)");
+    if (p.K < 2) throw std::invalid_argument(w + ": encryption parameters do not support key switching");
+}
+inline void plan_seeded_encrypt(const Params &p, int L, u64 n, const u64 *plain, u64 a_seed, u64 noise_seed, u64 first_index, const u64 *c0)
+{
+    const std::string w("he355_bfv_seeded_encrypt");
+    check_level(p, w, L);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    check_seeded_seeds(w, a_seed, noise_seed);
+    check_seeded_index(w, first_index, n);
+    check_seeded_size(p, w, n, (u64)L);
+    if (!n) return;
+    const AddrRange dst = word_range(w, c0, n * L * p.N); // (refused where it wraps the address space, with or without plaintexts)
+    if (plain && dst.overlaps(word_range(w, plain, n * p.N))) throw std::invalid_argument(w + ": `d_c0` overlaps the plaintexts");
+}
+inline void plan_seeded_restore(const Params &p, int L, int ntt_form, u64 n, const u64 *c0, u64 first_index, const u64 *out)
+{
+    const std::string w("he355_bfv_seeded_restore");
+    check_level(p, w, L);
+    if (ntt_form != 0 && ntt_form != 1) throw std::invalid_argument(w + ": ntt_form must be 0 or 1");
+    check_seeded_index(w, first_index, n);
+    check_seeded_size(p, w, n, 2 * (u64)L);
+    if (n && word_range(w, out, n * 2 * L * p.N).overlaps(word_range(w, c0, n * L * p.N))) throw std::invalid_argument(w + ": `d_out` overlaps `d_c0`");
+}
+// he355_bfv_selector_encrypt's rules (plan_selector) on a `c0` of [n][L][N], and the seeded ones
+inline BfvSelectorPlan plan_seeded_selector(const Params &p, int L, int v, u64 n, u64 n_sel, u64 first_slot, u64 count, const u64 *sel, u64 a_seed, u64 noise_seed,
+                                            u64 first_index, const u64 *c0)
+{
+    const std::string w("he355_bfv_seeded_selector_encrypt");
+    const BfvDigitTab tab = gadget_table(p, w, L, v);
+    if (p.plain_modulus < 2) throw std::invalid_argument(w + ": the plain modulus must be at least 2");
+    if (!n_sel) throw std::invalid_argument(w + ": n_sel must be at least 1");
+    if (count < 1 || count > p.N) throw std::invalid_argument(w + ": count must be in 1..N");
+    if ((u128)first_slot + (u128)n_sel * tab.total > count) throw std::invalid_argument(w + ": first_slot + n_sel E(L) must not exceed count");
+    check_seeded_seeds(w, a_seed, noise_seed);
+    check_seeded_index(w, first_index, n);
+    check_seeded_size(p, w, n, (u64)L);
+    if (n && word_range(w, c0, n * L * p.N).overlaps(word_range(w, sel, n * n_sel))) throw std::invalid_argument(w + ": `d_c0` overlaps the selectors");
+    return {tab, expand_depth(count)};
+}
+inline void plan_keygen_galois_seeded(const Params &p, uint32_t elt, u64 a_seed, u64 noise_seed)
+{
+    const std::string w("he355_keygen_galois_seeded");
+    check_galois_elt(p, w, elt);
+    check_seeded_seeds(w, a_seed, noise_seed);
+}
+inline void plan_set_galois_key_seeded(const Params &p, uint32_t elt, const u64 *h_b)
+{
+    const std::string w("he355_set_galois_key_seeded");
+    check_galois_elt(p, w, elt);
+    if (!h_b) throw std::invalid_argument(w + ": null key halves");
 }
 
 } // namespace he355

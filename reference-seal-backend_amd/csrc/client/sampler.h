@@ -68,6 +68,11 @@ HE_HD u64 keygen_stream(u64 key_id, u64 digit, u64 K, u64 which /* prime index, 
 }
 // streams of one asymmetric encryption, ciphertext index r: u, e0, e1
 HE_HD u64 enc_stream(u64 r, int which) { return 3 * r + (u64)which; }
+// streams of one seeded (secret-key) ciphertext, index r < 2^40: the uniform half under prime i < 63 (drawn from the PUBLIC seed) and the
+// error (drawn from the SECRET one).  They lie in [2^48, 2^48 + 2^46): above every enc_stream of an index below 2^40 (< 3 * 2^40) and every
+// keygen_stream (< 2^41: key_id < 2^18 + 2, digit < 64, K + 1 <= 64)
+HE_HD u64 seeded_a_stream(u64 r, u64 i) { return ((u64)1 << 48) + 64 * r + i; }
+HE_HD u64 seeded_e_stream(u64 r) { return ((u64)1 << 48) + 64 * r + 63; }
 
 } // namespace client
 } // namespace he355

@@ -368,7 +368,7 @@ public:
         if (!*slot) dmalloc(*slot, key_alloc_elems() * 8);
         const uint32_t *perm_tab = galois_elt ? perm(galois_elt) : nullptr;
         u64 *scr = client_scratch((P.Ltop * P.K + P.K) * P.N);
-        launch_keygen_kswitch(env_, *slot, scr, scr + P.Ltop * P.K * P.N, d_sk_, perm_tab, seed, galois_elt ? 2 + (u64)galois_elt : 1);
+        launch_keygen_kswitch(env_, *slot, scr, scr + P.Ltop * P.K * P.N, d_sk_, perm_tab, seed, seed, galois_elt ? 2 + (u64)galois_elt : 1);
         key_finish(*slot);
     }
     void key_finish(u64 *d_key)
@@ -2291,6 +2291,73 @@ public:
         if (budget) launch_bfv_noise_finish(env_, n, budget, noise_bits, k1);
         HIPCHECK(hipGetLastError());
     }
+    // ---- seeded queries and Galois keys (he355_kernels_bfv_seeded.hip; the definition: bfv_seeded_core.h, include/he355.h) ----------------
+    // The seeded zero of index first_index + r, built at level L where it will lie: c0 = -e - iNTT(a (.) s), plus Delta_L(m).  Three launches
+    // whatever n is, all in place on `c0` (no scratch, so nothing to chunk): a (.) s generated straight into it, the inverse transform, the finish.
+    void seeded_c0(const char *what, int L, u64 n, const u64 *plain, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
+    {
+        if (!d_sk_) throw std::invalid_argument(std::string(what) + ": secret key not set (he355_set_secret_key)");
+        if (!n) return;
+        const size_t N = P.N;
+        launch_bfv_seeded_gen(env_, L, n, a_seed, client::seeded_a_stream(first_index, 0), 64, c0, (u64)L * N, d_sk_);
+        launch_ntt_inverse(env_, poly_view(c0, L, N, L), (u32)n);
+        launch_bfv_seeded_finish(env_, L, n, c0, plain, bfv_delta(L), noise_seed, first_index, c0);
+    }
+    void bfv_seeded_encrypt(int L, u64 n, const u64 *plain, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
+    {
+        use();
+        seeded_c0("he355_bfv_seeded_encrypt", L, n, plain, a_seed, noise_seed, first_index, c0);
+        HIPCHECK(hipGetLastError());
+    }
+    // polynomial 0 of he355_bfv_selector_encrypt with the seeded zero in the place of the public-key one: the same plants in the same places
+    void bfv_seeded_selector_encrypt(const BfvSelectorPlan &pl, int L, u64 n, u64 n_sel, u64 first_slot, const u64 *sel, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
+    {
+        use();
+        seeded_c0("he355_bfv_seeded_selector_encrypt", L, n, nullptr, a_seed, noise_seed, first_index, c0);
+        launch_bfv_seeded_plant(env_, pl.tab, L, n, n_sel, first_slot, pl.depth, sel, P.plain_modulus, c0);
+        HIPCHECK(hipGetLastError());
+    }
+    // c0 [n][L][N] -> out [n][2][L][N]: c0 placed, the seeded half generated where it lies, then ONE transform in place over the half whose
+    // form has to change (ntt_form 0: c1 = iNTT(a); 1: c0 = NTT(c0)).  No scratch, so nothing to chunk; needs no key.
+    void bfv_seeded_restore(int L, int ntt_form, u64 n, const u64 *c0, u64 a_seed, u64 first_index, u64 *out)
+    {
+        use();
+        if (!n) return;
+        const size_t N = P.N, LN = (size_t)L * N;
+        launch_bfv_seeded_place(env_, L, n, c0, out);
+        launch_bfv_seeded_gen(env_, L, n, a_seed, client::seeded_a_stream(first_index, 0), 64, out + LN, 2 * LN, nullptr);
+        PolyView v = poly_view(out + (ntt_form ? 0 : LN), L, N, L);
+        v.item_stride = 2 * LN;
+        if (ntt_form) launch_ntt_forward(env_, v, (u32)n);
+        else launch_ntt_inverse(env_, v, (u32)n);
+        HIPCHECK(hipGetLastError());
+    }
+    // the `b` halves [L_top][K][N] of the Galois key of `galois_elt`, its `a` halves drawn from the public a_seed: the whole key is made in a
+    // pool block by the key generator's own launches, the halves copied out.  Installs nothing.
+    void keygen_galois_seeded(uint32_t galois_elt, u64 a_seed, u64 noise_seed, u64 *d_b)
+    {
+        use();
+        if (!d_sk_) throw std::invalid_argument("he355_keygen_galois_seeded: secret key not set (he355_set_secret_key)");
+        if (!d_b) throw std::invalid_argument("he355_keygen_galois_seeded: null output");
+        const size_t KN = P.K * P.N;
+        const PoolBlock key = scoped_block(P.Ltop * 2 * KN * 8);
+        const uint32_t *perm_tab = perm(galois_elt);
+        u64 *scr = client_scratch((P.Ltop * P.K + P.K) * P.N);
+        launch_keygen_kswitch(env_, key.get(), scr, scr + P.Ltop * KN, d_sk_, perm_tab, a_seed, noise_seed, 2 + (u64)galois_elt);
+        for (size_t j = 0; j < P.Ltop; ++j) HIPCHECK(hipMemcpyAsync(d_b + j * KN, key.get() + j * 2 * KN, KN * 8, hipMemcpyDeviceToDevice, stream_));
+        HIPCHECK(hipGetLastError());
+    }
+    // he355_set_galois_key of the key whose `b` halves are h_b and whose `a` halves are a_seed's: uploaded, generated, finished
+    void key_from_seeded(uint32_t galois_elt, const u64 *h_b, u64 a_seed)
+    {
+        use();
+        u64 **slot = galois_slot(galois_elt);
+        if (!*slot) dmalloc(*slot, key_alloc_elems() * 8);
+        const size_t KN = P.K * P.N;
+        for (size_t j = 0; j < P.Ltop; ++j) HIPCHECK(hipMemcpyAsync(*slot + j * 2 * KN, h_b + j * KN, KN * 8, hipMemcpyHostToDevice, stream_));
+        launch_bfv_seeded_gen(env_, (int)P.K, P.Ltop, a_seed, client::keygen_stream(2 + (u64)galois_elt, 0, P.K, 0), P.K + 1, *slot + KN, 2 * KN, nullptr);
+        key_finish(*slot);
+    }
     // ---- encoders (CKKSEncoder / BatchEncoder) -------------------------------------------------------------------
     const EncTablesDev &enc_tables()
     {
@@ -3051,6 +3118,47 @@ int he355_bfv_reply_decrypt(he355_ctx *c, int k0, int k1, uint64_t n, const void
         need_bfv(c, "he355_bfv_reply_decrypt");
         const BfvReplyPlan pl = plan_reply(*c->params, "he355_bfv_reply_decrypt", 1, k0, k1, n, d_bytes, stride_bytes, d_plain, c->params->N, true, d_budget, d_noise_bits);
         dev(c).bfv_reply_decrypt(pl, k0, k1, n, d_bytes, stride_bytes, d_plain, d_budget, d_noise_bits);
+    });
+}
+int he355_bfv_seeded_encrypt(he355_ctx *c, int L, uint64_t n, const uint64_t *d_plain, uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_seeded_encrypt");
+        plan_seeded_encrypt(*c->params, L, n, d_plain, a_seed, noise_seed, first_index, d_c0);
+        dev(c).bfv_seeded_encrypt(L, n, d_plain, a_seed, noise_seed, first_index, d_c0);
+    });
+}
+int he355_bfv_seeded_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel,
+                                      uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_seeded_selector_encrypt");
+        const BfvSelectorPlan pl = plan_seeded_selector(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, a_seed, noise_seed, first_index, d_c0);
+        dev(c).bfv_seeded_selector_encrypt(pl, L, n, n_sel, first_slot, d_sel, a_seed, noise_seed, first_index, d_c0);
+    });
+}
+int he355_bfv_seeded_restore(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *d_c0, uint64_t a_seed, uint64_t first_index, uint64_t *d_out)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_bfv_seeded_restore");
+        plan_seeded_restore(*c->params, L, ntt_form, n, d_c0, first_index, d_out);
+        dev(c).bfv_seeded_restore(L, ntt_form, n, d_c0, a_seed, first_index, d_out);
+    });
+}
+int he355_keygen_galois_seeded(he355_ctx *c, uint32_t galois_elt, uint64_t a_seed, uint64_t noise_seed, uint64_t *d_b)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_keygen_galois_seeded");
+        plan_keygen_galois_seeded(*c->params, galois_elt, a_seed, noise_seed);
+        dev(c).keygen_galois_seeded(galois_elt, a_seed, noise_seed, d_b);
+    });
+}
+int he355_set_galois_key_seeded(he355_ctx *c, uint32_t galois_elt, const uint64_t *h_b, uint64_t a_seed)
+{
+    return guarded([&] {
+        need_bfv(c, "he355_set_galois_key_seeded");
+        plan_set_galois_key_seeded(*c->params, galois_elt, h_b);
+        dev(c).key_from_seeded(galois_elt, h_b, a_seed);
     });
 }
 int he355_bfv_noise_budget(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *d_ct, int32_t *d_budget, int32_t *d_noise_bits)

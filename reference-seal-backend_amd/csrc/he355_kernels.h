@@ -264,6 +264,10 @@ HE355_FWD(launch_bfv_select_cut)
 HE355_FWD(launch_bfv_select_mac)
 HE355_FWD(launch_bfv_select_tail)
 HE355_FWD(launch_bfv_select_copy)
+HE355_FWD(launch_bfv_seeded_gen)
+HE355_FWD(launch_bfv_seeded_finish)
+HE355_FWD(launch_bfv_seeded_place)
+HE355_FWD(launch_bfv_seeded_plant)
 HE355_FWD(launch_dot_sk)
 HE355_FWD(launch_bfv_scale_round)
 HE355_FWD(launch_ckks_encode)

@@ -131,17 +131,18 @@ __global__ void __launch_bounds__(kBlock) k_bfv_scale_round(const u64 *phase, u6
 // Digit j of a key-switching key = Enc_sym(0) at the key level with (P mod q_j) * new_key added to residue j of the first
 // polynomial (keygenerator.cpp generate_one_kswitch_key).  key [Ld][2][K][N]; e [Ld][K][N] scratch.
 // Step 1: the uniform polynomials a (written straight into key[j][1], NTT form as SEAL samples them) and the error polynomials
-// (coefficient form, into e); counter-based streams keygen_stream(key_id, j, K, .) of client/sampler.h.
-__global__ void __launch_bounds__(kBlock) k_keygen_sample(u64 *key, u64 *e, const PrimeDev *primes, int K, int logN, int Ld, u64 seed, u64 key_id)
+// (coefficient form, into e); counter-based streams keygen_stream(key_id, j, K, .) of client/sampler.h.  a is drawn from a_seed and the
+// error from noise_seed: he355_keygen_relin / he355_keygen_galois pass one seed for both, he355_keygen_galois_seeded a public and a secret one.
+__global__ void __launch_bounds__(kBlock) k_keygen_sample(u64 *key, u64 *e, const PrimeDev *primes, int K, int logN, int Ld, u64 a_seed, u64 noise_seed, u64 key_id)
 {
     const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
     const u64 j = gid >> logN, n = gid & (((u64)1 << logN) - 1);
     if (j >= (u64)Ld) return;
-    const int v = client::sample_cbd_at(seed, client::keygen_stream(key_id, j, K, K), n);
+    const int v = client::sample_cbd_at(noise_seed, client::keygen_stream(key_id, j, K, K), n);
     for (int i = 0; i < K; ++i) {
         const u64 q = primes[i].q;
         e[((j * K + i) << logN) + n] = client::small_to_residue(v, q);
-        key[(((j * 2 + 1) * K + i) << logN) + n] = client::sample_uniform_at(seed, client::keygen_stream(key_id, j, K, i), n, q);
+        key[(((j * 2 + 1) * K + i) << logN) + n] = client::sample_uniform_at(a_seed, client::keygen_stream(key_id, j, K, i), n, q);
     }
 }
 // Step 2 (after the forward NTT of e): key[j][0][i] = -(a*s + e) (+ (P mod q_j) * new_key[j] when i == j)
@@ -400,11 +401,11 @@ void launch_bfv_decode_gather(const KernelEnv &env, u64 n_vec, const u64 *ev, lo
     hipLaunchKernelGGL(k_bfv_decode_gather, dim3(grid_for(n_vec * sr.total, kBlock)), dim3(kBlock), 0, env.stream, ev, out, slot_index, t, logN, n_vec, sr);
 }
 
-void launch_keygen_kswitch(const KernelEnv &env, u64 *key, u64 *e_scratch, u64 *target_scratch, const u64 *sk, const uint32_t *perm, u64 seed, u64 key_id)
+void launch_keygen_kswitch(const KernelEnv &env, u64 *key, u64 *e_scratch, u64 *target_scratch, const u64 *sk, const uint32_t *perm, u64 a_seed, u64 noise_seed, u64 key_id)
 {
     const int logN = env.logn1 + kRowLog, K = env.K, Ld = env.Ltop;
     hipLaunchKernelGGL(k_keygen_target, dim3(grid_for((u64)K << logN, kBlock)), dim3(kBlock), 0, env.stream, sk, perm, target_scratch, env.primes, K, logN);
-    hipLaunchKernelGGL(k_keygen_sample, dim3(grid_for((u64)Ld << logN, kBlock)), dim3(kBlock), 0, env.stream, key, e_scratch, env.primes, K, logN, Ld, seed, key_id);
+    hipLaunchKernelGGL(k_keygen_sample, dim3(grid_for((u64)Ld << logN, kBlock)), dim3(kBlock), 0, env.stream, key, e_scratch, env.primes, K, logN, Ld, a_seed, noise_seed, key_id);
     PolyView v;
     v.base = e_scratch; v.item_stride = (u64)K << logN; v.polys_per_item = K; v.pad_ = 0;
     for (int i = 0; i < K; ++i) v.prime_of[i] = (unsigned char)i;

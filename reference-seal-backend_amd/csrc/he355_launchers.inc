@@ -105,8 +105,9 @@ void launch_bfv_encode_scatter(const KernelEnv &env, u64 n_vec, const long long 
 void launch_bfv_decode_gather(const KernelEnv &env, u64 n_vec, const u64 *ev, long long *out, const uint32_t *slot_index, u64 t, const SlotRanges &sr);
 // ---- key generation on the device --------------------------------------------------------------------------------
 // key [Ltop][2][K][N] <- key-switching key for new_key = s^2 (perm == null) or s permuted by `perm` (Galois key);
-// e_scratch [Ltop][K][N], target_scratch [K][N]; randomness: keygen_stream(key_id, digit, ...) of `seed` (client/sampler.h)
-void launch_keygen_kswitch(const KernelEnv &env, u64 *key, u64 *e_scratch, u64 *target_scratch, const u64 *sk, const uint32_t *perm, u64 seed, u64 key_id);
+// e_scratch [Ltop][K][N], target_scratch [K][N]; randomness: keygen_stream(key_id, digit, ...) of client/sampler.h, the uniform halves from
+// `a_seed` and the errors from `noise_seed` (one seed for both: the keys of he355_keygen_relin / he355_keygen_galois)
+void launch_keygen_kswitch(const KernelEnv &env, u64 *key, u64 *e_scratch, u64 *target_scratch, const u64 *sk, const uint32_t *perm, u64 a_seed, u64 noise_seed, u64 key_id);
 // ---- key switch with one workgroup per residue polynomial, transforms resident in LDS (N <= 8192; he355_kernels_lds.hip) ----------
 // out[op] (out_op_stride words apart, [2][L][N]) = addend + key switch of the target under `key`; part: scratch of n_ops * ks_lds_part_words words
 bool ks_lds_supported(const KernelEnv &env, int L);
@@ -219,3 +220,15 @@ void launch_bfv_select_mac(const KernelEnv &env, int L, u64 group, u64 first, u6
 void launch_bfv_select_tail(const KernelEnv &env, int L, u64 group, u64 first, u64 count, const u64 *sums, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride);
 // node 2 group of every result r < n (the one without a partner) -> node `group` of the next level; group = 0: a level of one node
 void launch_bfv_select_copy(const KernelEnv &env, int L, u64 n, u64 group, const u64 *nodes, u64 stride_a, u64 stride_b, u64 *out, u64 out_stride);
+// ---- seeded BFV queries and Galois keys (he355_kernels_bfv_seeded.hip; arithmetic: bfv_seeded_core.h) ---------------------------------------------
+// The uniform polynomials a seed stands for, NTT form: polynomial (item, i), item < items, i < polys, is
+// sample_uniform_at(seed, stream0 + item stream_step + i, ., q_i), written to out + item item_stride + i N.  sk ([.][N] NTT form, row i under
+// prime i) not null: its product with row i of sk is written instead.  One launch.
+void launch_bfv_seeded_gen(const KernelEnv &env, int polys, u64 items, u64 seed, u64 stream0, u64 stream_step, u64 *out, u64 item_stride, const u64 *sk);
+// w [n][L][N] = iNTT(a (.) s), plain [n][N] mod t (null: zeros) -> c0 [n][L][N] = Delta_L(m) - e - w, e = sample_cbd_at(noise_seed,
+// seeded_e_stream(first_index + r), .); c0 may be w
+void launch_bfv_seeded_finish(const KernelEnv &env, int L, u64 n, const u64 *w, const u64 *plain, const BfvDeltaConst &dc, u64 noise_seed, u64 first_index, u64 *c0);
+// c0 [n][L][N] -> polynomial 0 of out [n][2][L][N]
+void launch_bfv_seeded_place(const KernelEnv &env, int L, u64 n, const u64 *c0, u64 *out);
+// launch_bfv_selector_plant's plant, added in place to c0 [n][L][N]
+void launch_bfv_seeded_plant(const KernelEnv &env, const BfvDigitTab &tab, int L, u64 n, u64 n_sel, u64 first_slot, int d, const u64 *sel, u64 t, u64 *c0);
