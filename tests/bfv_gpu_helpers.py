@@ -43,11 +43,16 @@ def be():
 
 
 def pair(be, oracle, chain, keys=False):
-    """(g, o, N, sk, pk): a device context and the oracle's of one chain -- a name of ALL, or (N, bit sizes, plain bits) itself; keys: the
+    """(g, o, N, sk, pk): a device context and the oracle's of one chain -- a name of ALL, (N, bit sizes, plain bits) itself, or
+    (N, primes, t) with the moduli themselves (told apart by size: no bit size passes 60, no admitted prime is below 12289); keys: the
     oracle's secret and public key, set on the device (else None)"""
     N, bits, pb = ALL[chain] if isinstance(chain, str) else chain
-    g = be.Context(be.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False, device=0)
-    o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False)
+    if max(bits) > 60:
+        g = be.Context(be.SCHEME_BFV, N, primes=list(bits), plain_modulus=pb, device=0)
+        o = oracle.Context(oracle.SCHEME_BFV, N, primes=list(bits), plain_modulus=pb)
+    else:
+        g = be.Context(be.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False, device=0)
+        o = oracle.Context(oracle.SCHEME_BFV, N, bit_sizes=bits, plain_bits=pb, sec128=False)
     assert g.moduli == o.moduli and g.t == o.t
     sk = pk = None
     if keys:

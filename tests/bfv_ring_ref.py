@@ -10,9 +10,11 @@ from bfv_bytes_ref import np_fields
 
 
 def np_lift(m, t, q):
-    """bfv_gadget_ref.lift under one prime, vectorised: m below floor((t + 1) / 2) as is, else m - t mod q (m < t < q)"""
+    """bfv_gadget_ref.lift under one prime, vectorised: m below floor((t + 1) / 2) as is, else m - t, both mod q (m < t < 2^32; q may
+    lie below t: the chains of tests/explicit_moduli.py)"""
     m = np.asarray(m, dtype=np.uint64)
-    return np.where(m < np.uint64((t + 1) // 2), m, m + np.uint64(q - t))
+    r = m % np.uint64(q)
+    return np.where(m < np.uint64((t + 1) // 2), r, (r + np.uint64(q - t % q)) % np.uint64(q))
 
 
 def ntt_all(o, x):

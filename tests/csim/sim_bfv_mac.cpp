@@ -30,6 +30,17 @@ void *sim_bfvmac_create(size_t N, const int *bits, size_t n_bits, int plain_bits
         return nullptr;
     }
 }
+// the same over explicit moduli (primes whose run length the prime-size rule never produces)
+void *sim_bfvmac_create_primes(size_t N, const uint64_t *primes, size_t n, uint64_t plain_modulus)
+{
+    try {
+        MacSim *s = new MacSim();
+        s->p = Params::create_primes(kSchemeBFV, N, std::vector<u64>(primes, primes + n), plain_modulus, false);
+        return s;
+    } catch (const std::exception &) {
+        return nullptr;
+    }
+}
 void sim_bfvmac_destroy(void *h)
 {
     MacSim *s = static_cast<MacSim *>(h);

@@ -201,6 +201,8 @@ def _csim():
     S = csim_lib.load(fold=False)  # (the fp64 engine's code is the same in both builds)
     S.sim_params_create.restype = C.c_void_p
     S.sim_params_create.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.c_int, C.c_int]
+    S.sim_params_create_primes.restype = C.c_void_p
+    S.sim_params_create_primes.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64]
     S.sim_params_destroy.argtypes = [C.c_void_p]
     S.sim_modulus.restype = C.c_uint64
     S.sim_modulus.argtypes = [C.c_void_p, C.c_size_t]
@@ -222,15 +224,19 @@ def fits_48_bound(m0: float, q: float, logn1: int) -> float:
     return m
 
 
-def worst_column(N: int, bits, j: int, t: int, seed: int = 20261017, uniform_columns: int = 100000) -> dict:
+def worst_column(N: int, bits, j: int, t: int, seed: int = 20261017, uniform_columns: int = 100000, primes=None, restarts: int = 30) -> dict:
     """Hill-climb over the N1 coefficients (< q_j) of one column of digit j for the largest |x| the direct-path forward column pass of
     fp64-engine target prime t leaves (tests/csim: sim_col_fwd_maxmag, the product's col_fwd_w on the CPU).  Returns the column, its
     magnitude, the largest magnitude over `uniform_columns` uniform columns and fits_48's bound for this (q_j, q_t, N1).  With exactly centred
     products (|t| <= q_t / 2 per stage) no column could pass q_j + LOGN1 q_t / 2; fits_48's bound lies above that by the slack it
-    allows the quotient estimate of every stage, and the search ends close to the former, not to the bound."""
+    allows the quotient estimate of every stage, and the search ends close to the former, not to the bound.  primes: the chain's moduli
+    themselves in place of `bits` (tests/explicit_moduli.py); restarts: of the hill climb."""
     import ctypes as C
     S = _csim()
-    h = S.sim_params_create(2, N, (C.c_int * len(bits))(*bits), len(bits), 0, 0)
+    if primes is not None:
+        h = S.sim_params_create_primes(2, N, (C.c_uint64 * len(primes))(*primes), len(primes), 0)
+    else:
+        h = S.sim_params_create(2, N, (C.c_int * len(bits))(*bits), len(bits), 0, 0)
     assert h
     try:
         assert S.sim_is_f64(h, t) and S.sim_is_f64(h, j)
@@ -245,7 +251,7 @@ def worst_column(N: int, bits, j: int, t: int, seed: int = 20261017, uniform_col
         rng = np.random.default_rng(seed)
         best = np.full(n1, qj - 1, dtype=np.uint64)
         best_m = mag(best)
-        for _ in range(30):  # restarts; each: coordinate ascent in random order until a whole sweep raises nothing
+        for _ in range(restarts):  # each: coordinate ascent in random order until a whole sweep raises nothing
             c = rng.integers(0, qj, n1, dtype=np.uint64)
             m = mag(c)
             for _ in range(20):

@@ -43,12 +43,27 @@ Lt = the chain's data level.
 10. reply_decrypt: random bytes, all ones, all zeros; the oracle's key and the constant keys +1, -1; with and without budget outputs.
 11. f64_first, f64_only: the safe widths are refused by compress and decrypt, outputs untouched; bfv_reply_bytes of them is 0.
 
+Four further layouts take their moduli from tests/golden/explicit_moduli.json (tests/explicit_moduli.py), not from the prime-size rule, and
+their plain modulus with them; the cases above run on them unchanged, and the asserts that pin bit lengths and a 20-bit t are replaced by the
+fixture's own primes and t:
+
+    aux46               t = 256       the two largest 46-bit primes as data primes: the device's auxiliary base has to leave them out
+    shoup_by_one_low60  t = 2^32 - 5  the Shoup form by one prime 2^59 + (small), whose 128-bit sums take 1023 terms; a 31-bit byte field
+    mac_337             t = 2^16      prime 0 near 2^59.8: 337-term runs, no power of two; t a power of two (w = 16)
+    tiny                batching t    {60, 14, 16, 31}-bit data primes, L = 4, a 32-bit batching t above three of its primes
+
+In case 4 the over-the-run shapes are sized so that the 337-term and the 1023-term prime fold inside a result: mac_337 L = 2, v = 4,
+inner = 7 (350 terms); shoup_by_one_low60 L = 3, v = 4, inner = 12 (1080 terms, above all three runs, the cut through the column pass).
+12. tiny: bfv_seeded_encrypt and bfv_seeded_restore against tests/bfv_seeded_ref.py (a 14-bit prime under the uniform sampler's limit).
+
 Not run: these layouts at N >= 8192, and two passes through the pool block on them."""
 
 import numpy as np
 import pytest
 
 import bfv_gadget_ref as gad
+import bfv_seeded_ref as seeded
+import explicit_moduli as xm
 import bfv_reply_ref as rep
 import bfv_ring_ref as ring
 import bfv_select_ref as tree
@@ -67,6 +82,19 @@ LAYOUTS = {
     "shoup_60": ((2048, [60, 50, 40, 60], 20), "shoup", 48, True),
     "f64_first_1024": ((1024, [45, 55, 50], 20), "shoup", 34, True),
 }
+# the layouts of explicit moduli: ((N, primes, t), form, top width, safe pair accepted) -- the last two by bfv_reply_ref's own rule
+EXPLICIT = {"aux46": "aux46_t256", "shoup_by_one_low60": "shoup_by_one_low60_t4294967291", "mac_337": "mac_337_t65536", "tiny": None}
+_FIX = xm.load()
+for _cid, _fid in EXPLICIT.items():
+    if _fid is None:
+        _fid = next(k for k, c in _FIX.items() if c.get("chain") == _cid and c.get("batching") and c["N"] == 2048)
+        EXPLICIT[_cid] = _fid
+    _c = _FIX[_fid]
+    assert _c["N"] == 2048
+    LAYOUTS[_cid] = ((_c["N"], _c["primes"], _c["t"]), xm.form_of(_c["primes"]), rep.max_width(_c["N"], _c["primes"][0]),
+                     rep.accepted(_c["N"], _c["primes"][0], *rep.safe_bits(_c["N"], _c["t"])))
+assert [LAYOUTS[k][0][2] for k in EXPLICIT] == [256, 2 ** 32 - 5, 2 ** 16, _FIX[EXPLICIT["tiny"]]["t"]] and (LAYOUTS["tiny"][0][2] - 1) % 4096 == 0
+assert [LAYOUTS[k][1] for k in EXPLICIT] == ["fold", "shoup", "shoup", "fold"]
 IDS = list(LAYOUTS)
 V = 20
 PAD = 24  # bytes between two replies
@@ -88,8 +116,13 @@ def layout_pair(be, oracle, cid):
     if cid not in _PAIRS:
         chain, form, top, safe = LAYOUTS[cid]
         g, o, N, sk, pk = pair(be, oracle, chain, keys=True)
-        assert [q.bit_length() for q in o.moduli] == chain[1] and g.L == len(chain[1]) - 1 and o.t.bit_length() == 20
-        assert [q < 2 ** 47 for q in o.moduli] == [b < 47 for b in chain[1]], "the engines, by the prime-size rule"
+        if cid in EXPLICIT:
+            assert o.moduli == g.moduli == chain[1] == _FIX[EXPLICIT[cid]]["primes"] and o.t == g.t == chain[2] and g.L == len(chain[1]) - 1
+            assert g.fp64 == [xm.is_f64(q) for q in chain[1]], "the engines, by the prime itself"
+            assert set(g.bfv_aux_base()).isdisjoint(chain[1])
+        else:
+            assert [q.bit_length() for q in o.moduli] == chain[1] and g.L == len(chain[1]) - 1 and o.t.bit_length() == 20
+            assert [q < 2 ** 47 for q in o.moduli] == [b < 47 for b in chain[1]], "the engines, by the prime-size rule"
         assert form_of(o.moduli) == form
         q0 = int(o.moduli[0])
         assert rep.max_width(N, q0) == top and rep.accepted(N, q0, *rep.safe_bits(N, o.t)) == safe
@@ -126,17 +159,17 @@ def same(got, want, cid, call, what, moduli=None, v=None):
 
 def planted(o, rng, L, size, N):
     """[size][L][N]: uniform, and for every ordered pair q_j < q_i of the first L primes residue i holds q_j - 1, q_j, q_j + 1, q_i - 1 at four
-    neighbouring columns of each group of 1024 coefficients: columns 0..3 for the first j, 1020..1023 for the second"""
+    neighbouring columns of each group of 1024 coefficients: columns 0..3 for the first j, 1020..1023 for the second, 512..515 for a third"""
     c = o.random_poly(rng, L, size)
     qs = [int(q) for q in o.moduli[:L]]
     pairs = 0
     for i, qi in enumerate(qs):
         below = [qj for qj in qs if qj < qi]
-        assert len(below) <= 2
+        assert len(below) <= 3
         for p, qj in enumerate(below):
             assert qj + 1 < qi
             for grp in range(N // 1024):
-                at = grp * 1024 + (0, 1020)[p]
+                at = grp * 1024 + (0, 1020, 512)[p]
                 c[:, i, at:at + 4] = np.array([qj - 1, qj, qj + 1, qi - 1], dtype=np.uint64)
             pairs += 1
     assert pairs == L * (L - 1) // 2
@@ -312,13 +345,14 @@ def test_external_product_many_results(be, oracle, cid):
     g, o, N, *_ = layout_pair(be, oracle, cid)
     rng = np.random.default_rng(505)
     L = g.L
-    inner = {3: 3, 2: 4}[L]
-    assert 4 * inner * L >= 32 > 3 * 3 * L  # 4 x inner x 2 x L x 4 blocks reach the column pass, 3 x 3 does not
+    inner = {4: 2, 3: 3, 2: 4}[L]
+    n_c = 3 if L < 4 else 2  # (c): 3 x 3 below four data primes, as ever; 2 x 3 at four
+    assert 4 * inner * L >= 32 > n_c * 3 * L  # 4 x inner x 2 x L x 4 blocks reach the column pass, (c) does not
     cut = "cut_cols" if N > 1024 else "cut_stream"
     cols, stream = {cut: 1, "mac_gadget": 1, "passes": 1}, {"cut_stream": 1, "mac_gadget": 1, "passes": 1}
     ep_case(g, o, rng, cid, L, V, 4, inner, False, False, N, f"(a) n = 4, inner = {inner}, a selector row per result", cols)
     ep_case(g, o, rng, cid, L, V, 4, inner, True, True, N, f"(b) n = 4, inner = {inner}, child-major, one selector row", cols)
-    ep_case(g, o, rng, cid, L, V, 3, 3, False, False, N, "(c) n = 3, inner = 3", stream)
+    ep_case(g, o, rng, cid, L, V, n_c, 3, False, False, N, f"(c) n = {n_c}, inner = 3", stream)
 
 
 @pytest.mark.parametrize("cid", IDS)
@@ -327,7 +361,7 @@ def test_external_product_one_result(be, oracle, cid):
     g, o, N, *_ = layout_pair(be, oracle, cid)
     rng = np.random.default_rng(506)
     L = g.L
-    inner = {3: 11, 2: 16}[L]
+    inner = {4: 8, 3: 11, 2: 16}[L]
     assert inner * L >= 32 > (inner - 1) * L and 3 * L < 32
     cut = "cut_cols" if N > 1024 else "cut_stream"
     ep_case(g, o, rng, cid, L, V, 1, inner, False, False, N, f"(d) n = 1, inner = {inner}", {cut: 1, "mac_plain": 1, "passes": 1})
@@ -339,25 +373,35 @@ def mac_run(q):
     return min(2 ** 16, (2 ** 128 - 1) // (q - 1) ** 2)
 
 
-@pytest.mark.parametrize("cid,L,inner,over", [("u64_only", 2, 5, (True, True)), ("shoup_60", 3, 4, (True, False, False))])
+@pytest.mark.parametrize("cid,L,inner,over", [("u64_only", 2, 5, (256, 256)), ("shoup_60", 3, 4, (256, None, None)),
+                                              ("mac_337", 2, 7, (337, None)), ("shoup_by_one_low60", 3, 12, (256, 256, 1023))])
 def test_external_product_more_terms_than_a_run(be, oracle, cid, L, inner, over):
     """v = 4, n = 2.  u64_only: 2E = 2 (15 + 15) = 60 rows, inner = 5 is 300 terms, above the 256-term run of BOTH 60-bit primes (a fold
     inside every result, under every prime).  shoup_60: 2E = 2 (15 + 13 + 10) = 76 rows, inner = 4 is 304 terms, above the run of the 60-bit
-    prime alone -- the 50- and 40-bit primes' runs are capped at 2^16.  One pass through the pool block each"""
+    prime alone -- the 50- and 40-bit primes' runs are capped at 2^16.  mac_337: 2E = 2 (15 + 10) = 50 rows, inner = 7 is 350 terms, above the 337
+    terms of prime 0 (the 40-bit prime: 2^16).  shoup_by_one_low60: 2E = 90 rows, inner = 12 is 1080 terms, above the 1023 terms of the prime
+    2^59 + (small) and four runs of the other two; its 72 residue polynomials take the column cut.  over: the run of each prime that folds
+    inside a result.  One pass through the pool block each"""
     g, o, N, *_ = layout_pair(be, oracle, cid)
     v, n = 4, 2
     assert g.L == L
     rows = 2 * g.bfv_gadget_count(L, v)[0]
     terms = inner * rows
-    assert rows == 2 * sum(-(-q.bit_length() // v) for q in o.moduli[:L]) and terms == {"u64_only": 300, "shoup_60": 304}[cid]
+    assert rows == 2 * sum(-(-q.bit_length() // v) for q in o.moduli[:L])
+    assert terms == {"u64_only": 300, "shoup_60": 304, "mac_337": 350, "shoup_by_one_low60": 1080}[cid]
     for j, q in enumerate(o.moduli[:L]):
         if over[j]:
-            assert q.bit_length() == 60 and terms > (2 ** 128 - 1) // (q - 1) ** 2 == 256 == mac_run(q), j
+            assert q.bit_length() == 60 and terms > (2 ** 128 - 1) // (q - 1) ** 2 == over[j] == mac_run(q), j
         else:
             assert q.bit_length() < 60 and mac_run(q) == 2 ** 16 > terms, j
-    assert 4096 // terms >= n and n * inner * L < 32  # one pass, the streaming cut
+    assert 4096 // terms >= n  # one pass
+    if cid in EXPLICIT and n * inner * L >= 32:
+        cut = "cut_cols"
+    else:
+        assert n * inner * L < 32  # the streaming cut
+        cut = "cut_stream"
     ep_case(g, o, np.random.default_rng(507), cid, L, v, n, inner, False, False, N, f"L = {L}, v = 4, n = 2, inner = {inner}: {terms} terms",
-            {"cut_stream": 1, "mac_gadget": 1, "passes": 1}, composed=True)
+            {cut: 1, "mac_gadget": 1, "passes": 1}, composed=True)
 
 
 # ---- 5. he355_bfv_rgsw_from_bfv ------------------------------------------------------------------------------------------------------------
@@ -593,7 +637,8 @@ def widths_of(g, cid, N):
     q = int(g.moduli[0])
     top, safe = LAYOUTS[cid][2:]
     k0, k1, ok = g.bfv_reply_safe_bits()
-    assert (k0, k1) == rep.safe_bits(N, g.t) == (22, 22 + N.bit_length() - 1) and ok == safe == rep.accepted(N, q, k0, k1)
+    tb = 20 if cid not in EXPLICIT else g.t.bit_length()  # bitlen(t) + 2, and log2 N more
+    assert (k0, k1) == rep.safe_bits(N, g.t) == (tb + 2, tb + 2 + N.bit_length() - 1) and ok == safe == rep.accepted(N, q, k0, k1)
     assert top == rep.max_width(N, q) and not rep.accepted(N, q, 2, top + 1) and g.bfv_reply_bytes(2, top + 1) == 0
     out = [(2, 2), (top, top)] + ([(k0, k1)] if ok else [])
     assert all(rep.accepted(N, q, *w) for w in out)
@@ -714,3 +759,48 @@ def test_reply_refusals_where_the_first_prime_cannot_hold_the_safe_widths(be, or
     assert np.array_equal(dx.download(x.shape), x), (cid, "operands")
     for b in (dx, by, pl):
         b.free()
+
+
+# ---- 12. he355_bfv_seeded_encrypt, he355_bfv_seeded_restore on the small primes ------------------------------------------------------------
+def test_seeded_encrypt_and_restore_on_tiny(be, oracle):
+    """the uniform half drawn under 14-, 16- and 31-bit primes (bfv_seeded_limit: the rejection bound of each) and the secret-key
+    product under them, against the definition in numpy and Python integers"""
+    cid = "tiny"
+    g, o, N, sk, pk = layout_pair(be, oracle, cid)
+    assert [q.bit_length() for q in o.moduli[:g.L]] == [60, 14, 16, 31]
+    rng = np.random.default_rng(516)
+    n, a_seed, e_seed, first = 5, 0xA5EED, 0x5EC4E7, 70
+    t = o.t
+    m = rng.integers(0, t, (n, N), dtype=np.uint64)
+    m[0, :5] = [0, 1, t // 2, t // 2 + 1, t - 1]
+    m[n - 1] = t - 1
+    dp = g.to_device(m)
+    for L in (g.L, 1):
+        per = L * N
+        buf = sentinelled(g, n * per, N)
+        begin(g)
+        g.bfv_seeded_encrypt(L, n, dp, a_seed, e_seed, first, At(buf, N))
+        c0 = inner_of(buf, N, ("seeded_encrypt", L)).reshape(n, L, N)
+        routed(g, cid, f"seeded_encrypt L = {L}", {})
+        for r in range(n):
+            same(c0[r], seeded.encrypt(o, sk, L, m[r:r + 1], a_seed, e_seed, first + r)[0], cid, "seeded_encrypt", f"L = {L}, row {r}")
+        dc = g.to_device(c0)
+        for form in (0, 1):
+            out = sentinelled(g, n * 2 * per, N)
+            g.bfv_seeded_restore(L, form, n, dc, a_seed, first, At(out, N))
+            got = inner_of(out, N, ("seeded_restore", L, form)).reshape(n, 2, L, N)
+            for r in range(n):
+                same(got[r], seeded.restore(o, L, form, c0[r:r + 1], a_seed, first + r)[0], cid, "seeded_restore", f"L = {L}, form {form}, row {r}")
+            out.free()
+        if L == g.L:  # and it decrypts
+            out = g.alloc(n * 2 * per)
+            g.bfv_seeded_restore(L, 0, n, dc, a_seed, first, out)
+            dec = g.alloc(n * N)
+            g.decrypt(L, 2, n, out, dec)
+            assert np.array_equal(dec.download((n, N)), m), (cid, "decrypt of the restored ciphertexts")
+            out.free()
+            dec.free()
+        assert np.array_equal(dp.download((n, N)), m), (cid, "plaintexts")
+        buf.free()
+        dc.free()
+    dp.free()

@@ -59,8 +59,16 @@ def be():
     return mod
 
 
-def make_pair(be, oracle, N, bits, force, scheme="ckks"):
+def make_pair(be, oracle, N, bits, force, scheme="ckks", primes=None, t=0):
+    """primes (and t for BFV): the moduli themselves instead of bit sizes (tests/explicit_moduli.py)"""
     bfv = scheme == "bfv"
+    if primes is not None:
+        assert not force
+        sid = (be.SCHEME_BFV, oracle.SCHEME_BFV) if bfv else (be.SCHEME_CKKS, oracle.SCHEME_CKKS)
+        g = be.Context(sid[0], N, primes=list(primes), plain_modulus=t, device=0)
+        o = oracle.Context(sid[1], N, primes=list(primes), plain_modulus=t)
+        assert g.moduli == o.moduli == list(primes) and g.t == o.t == t
+        return g, o
     if force:
         os.environ["HE355_FORCE_U64"] = "1"
     try:
