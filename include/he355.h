@@ -629,6 +629,41 @@ int he355_rotate_add(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, in
  * Galois key switches issued per ciphertext.  h_steps: host array.  Not in place. */
 int he355_rotate_sum(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, const int32_t *h_steps, uint64_t n_steps, uint64_t *d_out,
                      uint64_t *key_switches);
+/* Hoisted rotations (Halevi-Shoup): ONE ciphertext batch under MANY Galois elements, the digit lift of c1 -- everything of a key switch in
+ * front of the key product -- run once and shared by all of them (the diagonal method, baby-step/giant-step transforms, the slot <->
+ * coefficient maps, convolutions).  The definition is the library's own and NOT bit-identical to he355_apply_galois: for (c0, c1) at
+ * level L, element g with installed key key_g and g^-1 its inverse mod 2N,
+ *   key' = every residue polynomial of key_g permuted in NTT form by g^-1;  (u0, u1) = the ordinary key switch of c1 under key' added into
+ *   (c0, 0);  out = sigma_g applied to both polynomials (the NTT-domain permutation, or the signed coefficient gather for coefficient form)
+ * -- the digits of sigma(c1) are non-negative residues of -x where sigma of the digits is -(residue of x); they differ by multiples of q_j
+ * that the key absorbs, so the result decrypts to the same rotation with noise of the same bound.  g = 1 is the identity (out = in, no key).
+ * key' is built on first use and kept per element until that element's key is installed again or he355_hoist_release_keys: it DOUBLES the
+ * device memory of every hoisted element's key.  All chunks of a call run on one stream.  Every refusal is made on the host before any
+ * device work; n == 0 or n_elts == 0 touches nothing and returns success.  d_out may overlap neither d_in nor d_plain.
+ *
+ * out[r][i] = hoisted Galois map of in[i] under h_elts[r]; d_out [n_elts][n][2][L][N] (element-major).
+ * ntt_form: CKKS contexts 1 only; BFV contexts 0 = coefficient form (BFV kernels), 1 = NTT-form BFV ciphertexts (NTT-domain pipeline). */
+int he355_apply_galois_hoisted(he355_ctx *ctx, int L, int ntt_form, uint64_t n, const uint64_t *d_in, const uint32_t *h_elts, uint64_t n_elts,
+                               uint64_t *d_out);
+/* the same by steps (step 0 = identity); every non-zero step needs its OWN Galois key: no NAF fallback, a chain cannot be hoisted */
+int he355_rotate_hoisted(he355_ctx *ctx, int L, int ntt_form, uint64_t n, const uint64_t *d_in, const int32_t *h_steps, uint64_t n_steps,
+                         uint64_t *d_out);
+/* out[i] = sum_r plain[r] (.) hoisted(in[i], step r): the diagonal method's inner loop.  NTT-form ciphertexts only (CKKS; BFV as from
+ * he355_bfv_transform_to_ntt), d_plain [n_steps][L][N] NTT-form plaintexts shared by the batch, d_out [n][2][L][N]; no rescale.  Equal bit
+ * for bit to he355_multiply_plain + he355_add over the hoisted terms (canonical residues; modular addition is exact). */
+int he355_rotate_hoisted_plain_sum(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, const int32_t *h_steps, uint64_t n_steps,
+                                   const uint64_t *d_plain, uint64_t *d_out);
+/* What the hoisted calls of this context did since he355_device_init (or the last call with reset != 0); they count in no field of
+ * he355_path_stats_t. */
+typedef struct he355_hoist_stats {
+    uint64_t digit_lifts;   /* digit-lift sequences: one per chunk with a non-identity element, however many elements          */
+    uint64_t key_products;  /* key-product + mod-down + finish sequences: one per (chunk, non-identity element)                 */
+    uint64_t keys_permuted; /* permuted key copies built (first use, and again after the element's key was installed again)     */
+    uint64_t key_bytes;     /* device bytes the permuted copies hold now (a level: kept across reset)                            */
+    uint64_t reserved[4];
+} he355_hoist_stats_t;
+int he355_hoist_stats(he355_ctx *ctx, he355_hoist_stats_t *out, int reset);
+int he355_hoist_release_keys(he355_ctx *ctx);   /* frees the permuted copies; they are rebuilt on next use */
 /* accumulateCKKS / accumulateBFV: in place log-tree sum of the first `count` slots; d_tmp: scratch slab of the same size.
  * count == 0 is the reference's else-branch (src/engine/seal_context.cpp:312-316, 341-344): every ciphertext is replaced by a
  * FRESH encryption of zero (Encryptor::encrypt_zero; needs the public key; L must be the top level, as SEAL returns a

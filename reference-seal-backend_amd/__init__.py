@@ -44,6 +44,10 @@ class PathStats(C.Structure):
                                            "level_sum_launches_in_k3", "reserved")]
 
 
+class HoistStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes")] + [("reserved", C.c_uint64 * 4)]
+
+
 class BfvRouteStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("cut_cols", "cut_stream", "mac_gadget", "mac_plain", "own_cols", "own_stream", "digits_fused",
                                            "digits_routed", "bytes_fused", "bytes_routed", "passes", "select_cols", "select_stream",
@@ -173,6 +177,11 @@ def lib():
             "he355_rotate_each": (i32, [vp, i32, u64, vp, vp, vp]),
             "he355_rotate_sum": (i32, [vp, i32, u64, vp, vp, u64, vp, vp]),
             "he355_accumulate": (i32, [vp, i32, u64, vp, u64, vp]),
+            "he355_apply_galois_hoisted": (i32, [vp, i32, i32, u64, vp, C.POINTER(u32), u64, vp]),
+            "he355_rotate_hoisted": (i32, [vp, i32, i32, u64, vp, C.POINTER(C.c_int32), u64, vp]),
+            "he355_rotate_hoisted_plain_sum": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, vp, vp]),
+            "he355_hoist_stats": (i32, [vp, C.POINTER(HoistStats), i32]),
+            "he355_hoist_release_keys": (i32, [vp]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
             "he355_set_zero_stream": (i32, [vp, u64, u64]),
             "he355_ntt_forward": (i32, [vp, vp, u64, u8p, u32]),
@@ -210,7 +219,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -692,6 +701,31 @@ class Context:
 
     def rotate(self, L, n, inp, step, out):
         _check(lib().he355_rotate(self.h, L, n, inp.ptr, step, out.ptr))
+
+    def apply_galois_hoisted(self, L, n, inp, elts, out, ntt_form=True):
+        """out [len(elts)][n][2][L][N]: block r = the hoisted Galois map of inp under elts[r] (1: the identity); one digit lift per chunk is
+        shared by all elements, each of which needs its own Galois key.  Not bit-identical to apply_galois (include/he355.h)"""
+        arr = (C.c_uint32 * max(1, len(elts)))(*[int(v) for v in elts])
+        _check(lib().he355_apply_galois_hoisted(self.h, L, int(ntt_form), n, inp.ptr, arr, len(elts), out.ptr))
+
+    def rotate_hoisted(self, L, n, inp, steps, out, ntt_form=True):
+        """the same by steps (0: the identity); no NAF fallback"""
+        arr = (C.c_int32 * max(1, len(steps)))(*[int(v) for v in steps])
+        _check(lib().he355_rotate_hoisted(self.h, L, int(ntt_form), n, inp.ptr, arr, len(steps), out.ptr))
+
+    def rotate_hoisted_plain_sum(self, L, n, inp, steps, plain, out):
+        """out [n][2][L][N] = sum_r plain[r] (.) hoisted(inp, steps[r]); plain [len(steps)][L][N] NTT-form plaintexts; NTT-form ciphertexts"""
+        arr = (C.c_int32 * max(1, len(steps)))(*[int(v) for v in steps])
+        _check(lib().he355_rotate_hoisted_plain_sum(self.h, L, n, inp.ptr, arr, len(steps), plain.ptr, out.ptr))
+
+    def hoist_stats(self, reset: bool = False) -> dict:
+        """what the hoisted calls did (he355_hoist_stats): digit lifts, key products, permuted keys built, bytes those copies hold"""
+        st = HoistStats()
+        _check(lib().he355_hoist_stats(self.h, C.byref(st), int(reset)))
+        return {k: int(getattr(st, k)) for k, _ in HoistStats._fields_ if k != "reserved"}
+
+    def hoist_release_keys(self):
+        _check(lib().he355_hoist_release_keys(self.h))
 
     def rotate_each(self, L, n, inp, steps, out):
         arr = (C.c_int32 * n)(*[int(v) for v in steps])

@@ -23,6 +23,7 @@
 #include "he355_internal.h"
 #include "he355_kernels.h"
 #include "he_params.h"
+#include "hoist_args.h"
 #include "ntt_core.h"
 #include "client/he_client.h"
 #include "client/multiword.h"
@@ -266,6 +267,7 @@ private:
         pool_.raw_free(d_relin_);
         pool_.raw_free(d_relin_scaled_);
         for (auto &kv : d_galois_) pool_.raw_free(kv.second);
+        for (auto &kv : d_hoist_) pool_.raw_free(kv.second.p);
         for (Arena &a : arena_) pool_.raw_free(a.p);
         pool_.destroy();
         for (hipEvent_t e : {ev_fork_, ev_join_, ev0_, ev1_})
@@ -375,6 +377,8 @@ public:
     {
         const u64 n_polys = P.Ltop * 2 * P.K, total = n_polys * P.N;
         if (d_key == d_relin_) d_relin_scaled_ok_ = false; // the scaled copy follows the key
+        for (auto &kv : d_hoist_) // ... and so does the permuted copy of a Galois key (hoist_key): rebuilt on its next use
+            if (galois_key(kv.first) == d_key) kv.second.ok = false;
         key_quotients(d_key);
         hipLaunchKernelGGL(k_key_to_engine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, d_key, n_polys, P.logn, d_primes_, (int)P.K);
         HIPCHECK(hipGetLastError());
@@ -416,6 +420,43 @@ public:
     {
         auto it = d_galois_.find(elt);
         return it == d_galois_.end() ? nullptr : it->second;
+    }
+    // The Galois key of `elt` with every residue polynomial (and its Shoup-quotient block) permuted in NTT form by elt^-1: what a hoisted
+    // rotation multiplies the UNPERMUTED digits by (sum_j sigma(d_j) k_j = sigma(sum_j d_j sigma^-1(k_j))).  Built on first use, kept per
+    // element, rebuilt after the element's key is installed again (key_finish); a second allocation the size of the key.
+    const u64 *hoist_key(uint32_t elt)
+    {
+        HoistKey &hk = d_hoist_[elt];
+        if (!hk.ok) {
+            const u64 m = 2 * (u64)P.N;
+            u64 ginv = 1;
+            for (u64 x = 1; x < m; x += 2)
+                if (((x * elt) & (m - 1)) == 1) { ginv = x; break; }
+            const uint32_t *table = perm((uint32_t)ginv);
+            if (!hk.p) {
+                dmalloc(hk.p, key_alloc_elems() * 8);
+                hoist_.key_bytes += key_alloc_elems() * 8;
+            }
+            launch_key_permute(env_, galois_key(elt), hk.p, table, key_alloc_elems() / P.N);
+            HIPCHECK(hipGetLastError());
+            hk.ok = true;
+            ++hoist_.keys_permuted;
+        }
+        return hk.p;
+    }
+    void hoist_release_keys()
+    {
+        use();
+        HIPCHECK(hipStreamSynchronize(stream_));
+        for (auto &kv : d_hoist_) pool_.raw_free(kv.second.p);
+        d_hoist_.clear();
+        hoist_.key_bytes = 0;
+    }
+    he355_hoist_stats_t hoist_stats(bool reset)
+    {
+        const he355_hoist_stats_t s = hoist_;
+        if (reset) { hoist_ = he355_hoist_stats_t{}; hoist_.key_bytes = s.key_bytes; } // (the bytes are a level, not a count)
+        return s;
     }
     const uint32_t *perm(uint32_t elt)
     {
@@ -875,6 +916,73 @@ public:
         fr.out = out; fr.out_op_stride = (u64)size * L1N; fr.out_poly_stride = L1N;
         fr.tail_prime = -1; fr.tail = nullptr;
         launch_floor_rows(env, nc, fr);
+    }
+    // Hoisted rotations: out block r = sigma_g(c0 + u0, u1) of every input under element pl.elts[r], (u0, u1) the key switch of the input's
+    // c1 itself under hoist_key(g) -- the digit lift (the inverse row pass and k_k2n, or k_k2n on the coefficients) runs ONCE per chunk and
+    // the slab S.ks.d is then read by every element's key product.  One stream only: the slab and the sums' scratch are reused from element
+    // to element, and the plain sum read-modify-writes `out` in launch order.  Per element the unfused tail (k_k3 on all primes, the floor
+    // step's column and row halves with no addend; BFV coefficient form: the two BFV tail kernels onto (c0, 0)) into scratch, then the
+    // finishing kernel.  plain (optional, NTT pipeline only): [n_elts][L][N], out [n][2][L][N] = sum_r plain[r] (.) block r.
+    // Counted in he355_hoist_stats, in no field of he355_path_stats.
+    void rotate_hoisted(const HoistPlan &pl, int L, bool ntt_form, u64 n, const u64 *in, const u64 *plain, u64 *out)
+    {
+        use();
+        for (uint32_t e : pl.elts)
+            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
+        const bool coeff = P.scheme == kSchemeBFV && !ntt_form;
+        const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
+        const int SP = (int)P.K - 1;
+        std::vector<const uint32_t *> table(n_elts);
+        std::vector<const u64 *> key(n_elts, nullptr);
+        for (size_t r = 0; r < n_elts; ++r) {
+            const uint32_t e = pl.elts[r];
+            table[r] = coeff ? gather(e) : perm(e);
+            if (e != 1) key[r] = hoist_key(e);
+        }
+        const uint32_t *ident = pl.keyed && !coeff ? perm(1) : nullptr;
+        for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
+            const KernelEnv env = batch_env(0, !coeff);
+            const KsBuffers &B = S.ks; // (c01: the arena's [nc][2][L][N], every element's sums before the permutation)
+            const u64 *a = in + off * 2 * LN;
+            if (pl.keyed) {
+                ++hoist_.digit_lifts;
+                if (coeff) {
+                    launch_hoist_addend_coeff(env, L, nc, a, B.e);
+                    launch_k2(env, L, nc, B, a + LN, 2 * LN);
+                } else { // c1 as it lies (the identity's permutation) through the inverse row pass: c2n, c2r; nothing of c01 is written
+                    launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, Indexer{}, ident, B, nullptr, false, true, nullptr, true);
+                    launch_k2(env, L, nc, B);
+                }
+            }
+            for (size_t r = 0; r < n_elts; ++r) {
+                u64 *o = plain ? out + off * 2 * LN : out + ((u64)r * n + off) * 2 * LN;
+                const u64 *pt = plain ? plain + r * LN : nullptr;
+                if (!key[r]) { // the identity
+                    if (pt) launch_hoist_finish_ntt(env, L, nc, nullptr, a, table[r], o, pt, r == 0);
+                    else HIPCHECK(hipMemcpyAsync(o, a, nc * 2 * LN * 8, hipMemcpyDeviceToDevice, env.stream));
+                    continue;
+                }
+                ++hoist_.key_products;
+                launch_k3(env, L, nc, B, key[r]);
+                if (coeff) {
+                    launch_bfv_tail_sp(env, nc * 2, B.tpr, S.rlr);
+                    launch_bfv_tail_fin(env, L, nc, B.t, S.rlr, B.c01, B.c01_item_stride, B.e, 2 * LN);
+                    launch_hoist_finish_coeff(env, L, nc, B.c01, table[r], o);
+                } else {
+                    launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e);
+                    FloorRowsArgs fr;
+                    fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
+                    fr.cols = B.e;
+                    fr.tsrc = B.t; fr.tsrc_op_stride = 2 * LN; fr.tsrc_poly_stride = LN;
+                    fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
+                    fr.out = B.c01; fr.out_op_stride = B.c01_item_stride; fr.out_poly_stride = LN;
+                    fr.tail_prime = -1; fr.tail = nullptr;
+                    launch_floor_rows(env, nc, fr);
+                    launch_hoist_finish_ntt(env, L, nc, B.c01, a, table[r], o, pt, r == 0);
+                }
+            }
+        });
+        HIPCHECK(hipGetLastError());
     }
     void require_keyswitch() const
     {
@@ -2569,6 +2677,9 @@ private:
     bool dual_stream_ = true;
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
     he355_path_stats_t paths_{};
+    struct HoistKey { u64 *p = nullptr; bool ok = false; };
+    std::map<uint32_t, HoistKey> d_hoist_; // hoist_key(): the permuted copies of the Galois keys, per element
+    he355_hoist_stats_t hoist_{};
     he355_bfv_route_stats_t routes_{};
     he355_bfv_multiply_stats_t mul_routes_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
@@ -3197,6 +3308,40 @@ int he355_apply_galois(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint
 int he355_rotate(he355_ctx *c, int L, uint64_t n, const uint64_t *in, int step, uint64_t *out)
 {
     return guarded([&] { dev(c).rotate(L, n, in, step, out); });
+}
+static int hoisted_call(he355_ctx *c, const char *what, int L, int ntt_form, uint64_t n, const uint64_t *in, const uint32_t *elts, const int32_t *steps, uint64_t n_elts,
+                        const uint64_t *plain, uint64_t *out, bool plain_sum)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        const HoistPlan pl = plan_rotate_hoisted(*c->params, what, L, ntt_form, n, in, elts, steps, n_elts, plain, out, plain_sum);
+        if (pl.empty) return; // nothing to rotate: no buffer is touched, no device asked for
+        dev(c).rotate_hoisted(pl, L, ntt_form != 0, n, in, plain_sum ? plain : nullptr, out);
+    });
+}
+int he355_apply_galois_hoisted(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *in, const uint32_t *elts, uint64_t n_elts, uint64_t *out)
+{
+    if (n_elts && !elts) { g_last_error = "he355_apply_galois_hoisted: null elements"; return HE355_E_INVALID_ARGS; }
+    return hoisted_call(c, "he355_apply_galois_hoisted", L, ntt_form, n, in, elts, nullptr, n_elts, nullptr, out, false);
+}
+int he355_rotate_hoisted(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, uint64_t *out)
+{
+    return hoisted_call(c, "he355_rotate_hoisted", L, ntt_form, n, in, nullptr, steps, n_steps, nullptr, out, false);
+}
+int he355_rotate_hoisted_plain_sum(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, const uint64_t *plain, uint64_t *out)
+{
+    return hoisted_call(c, "he355_rotate_hoisted_plain_sum", L, 1, n, in, nullptr, steps, n_steps, plain, out, true);
+}
+int he355_hoist_stats(he355_ctx *c, he355_hoist_stats_t *out, int reset)
+{
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null pointer");
+        *out = dev(c).hoist_stats(reset != 0);
+    });
+}
+int he355_hoist_release_keys(he355_ctx *c)
+{
+    return guarded([&] { dev(c).hoist_release_keys(); });
 }
 int he355_rotate_each(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t *out)
 {

@@ -228,6 +228,10 @@ HE355_FWD(launch_behz_floor_sk)
 HE355_FWD(launch_bfv_galois)
 HE355_FWD(launch_bfv_tail_sp)
 HE355_FWD(launch_bfv_tail_fin)
+HE355_FWD(launch_key_permute)
+HE355_FWD(launch_hoist_finish_ntt)
+HE355_FWD(launch_hoist_addend_coeff)
+HE355_FWD(launch_hoist_finish_coeff)
 HE355_FWD(launch_rows_inv_select)
 HE355_FWD(launch_enc_sample)
 HE355_FWD(launch_enc_mul_pk)

@@ -85,6 +85,17 @@ void launch_bfv_tail_sp(const KernelEnv &env, u64 n_polys, const u64 *tpr, u64 *
 // c01 = add01 + key-switched part (add01 == nullptr: c01 += ...; relinearize hands the size-3 input's (c0, c1) here, nothing is copied)
 void launch_bfv_tail_fin(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *rp, u64 *c01, u64 c01_item_stride, const u64 *add01 = nullptr,
                          u64 add01_item_stride = 0);
+// ---- hoisted rotations (he355_kernels_hoist.hip) -----------------------------------------------------------
+// dst = the n_polys residue polynomials of src (an installed key and its quotient block), element e of each taken from perm[e]
+void launch_key_permute(const KernelEnv &env, const u64 *src, u64 *dst, const uint32_t *perm, u64 n_polys);
+// out [n_ops][2][L][N] = sigma_g(in.c0 + u.0, u.1), NTT form, perm = the element's NTT-domain permutation; plain ([L][N], optional):
+// out = plain (.) that (first) or out += plain (.) that
+void launch_hoist_finish_ntt(const KernelEnv &env, int L, u64 n_ops, const u64 *u, const u64 *in, const uint32_t *perm, u64 *out, const u64 *plain = nullptr,
+                             bool first = true);
+// dst [n_ops][2][L][N] = (ct.c0, 0)
+void launch_hoist_addend_coeff(const KernelEnv &env, int L, u64 n_ops, const u64 *ct, u64 *dst);
+// out [n_ops][2][L][N] = the signed coefficient gather of src, both polynomials
+void launch_hoist_finish_coeff(const KernelEnv &env, int L, u64 n_ops, const u64 *src, const uint32_t *gather, u64 *out);
 // inverse row pass of one residue of each poly: src [(op,k)] residue `prime` -> tail [(op,k)][N]
 void launch_rows_inv_select(const KernelEnv &env, int prime, u64 n_polys, const u64 *src, u64 src_poly_stride, u64 *tail);
 // ---- client side on the device: encryption / decryption (SURVEY.md 8f rank 1) ------------------------------
