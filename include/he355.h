@@ -653,6 +653,25 @@ int he355_rotate_hoisted(he355_ctx *ctx, int L, int ntt_form, uint64_t n, const 
  * for bit to he355_multiply_plain + he355_add over the hoisted terms (canonical residues; modular addition is exact). */
 int he355_rotate_hoisted_plain_sum(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, const int32_t *h_steps, uint64_t n_steps,
                                    const uint64_t *d_plain, uint64_t *d_out);
+/* The same sum with ONE mod-down ("double hoisting"): the key products stay in the extended basis Q P, are permuted, multiplied by plaintexts
+ * that also carry a residue under the special prime P = q_{K-1} and accumulated there; the part that needs no key is accumulated in Q.
+ * d_plain_qp [n_steps][L + 1][N], NTT form: rows 0 .. L - 1 under the data primes, row L under P (he355_plain_extend_special makes it).
+ *   d^_{j,i}   = the digits he355_apply_galois_hoisted lifts: c1[j] if i == j, else NTT_i(iNTT_j(c1[j]) mod q_i), i over the L data primes and P
+ *   S_r[k][i]  = sum_j d^_{j,i} (.) key'_r[j][k][i]                                   (keyed r; key'_r as above; no mod-down)
+ *   A[k][i]    = sum_{r keyed} sigma_{g_r}(S_r[k][i]) (.) plain_qp[r][i]              (L + 1 primes)
+ *   B[0][i]    = sum_{r keyed} sigma_{g_r}(c0[i]) (.) plain_qp[r][i] + sum_{r identity} c0[i] (.) plain_qp[r][i];  B[1][i] = sum_{r identity} c1[i] (.) plain_qp[r][i]
+ *   out[k][i]  = B[k][i] + (A[k][i] - NTT_i(delta_i)) P^-1 mod q_i,  h = floor(P / 2),  rho = (iNTT_P(A[k][L]) + h) mod P,
+ *                delta_i = (rho mod q_i - h mod q_i) mod q_i                           (a sum with no keyed element is B alone)
+ * Not the bits of he355_rotate_hoisted_plain_sum (a sum of mod-downs; this is the mod-down of a sum): the same plaintext after decryption,
+ * noise no larger, one rounding instead of n_steps.  The step rules, refusals and memory of the permuted keys are that call's. */
+int he355_rotate_hoisted_plain_sum_lazy(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, const int32_t *h_steps, uint64_t n_steps,
+                                        const uint64_t *d_plain_qp, uint64_t *d_out);
+/* d_plain_ntt [n][L][N] NTT-form plaintexts -> d_plain_qp [n][L + 1][N]: rows 0 .. L - 1 copied, row L = NTT_P(c mod P) with c the
+ * coefficients under prime 0 centred into (-q_0 / 2, q_0 / 2].  Exact when the plaintext's integer coefficients lie in that range: always
+ * for he355_bfv_plain_to_ntt's, for a CKKS plaintext when its scale leaves a bit of q_0.  d_mismatch (optional, one device word): the number
+ * of (coefficient, prime i >= 1) pairs whose residue is not c mod q_i -- 0: every prime agrees with prime 0; always 0 when L = 1; null skips
+ * the check and its transforms.  Needs a special prime (K >= 2); the two slabs may not overlap; n == 0 touches nothing. */
+int he355_plain_extend_special(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain_ntt, uint64_t *d_plain_qp, uint64_t *d_mismatch);
 /* What the hoisted calls of this context did since he355_device_init (or the last call with reset != 0); they count in no field of
  * he355_path_stats_t. */
 typedef struct he355_hoist_stats {
@@ -660,7 +679,9 @@ typedef struct he355_hoist_stats {
     uint64_t key_products;  /* key-product + mod-down + finish sequences: one per (chunk, non-identity element)                 */
     uint64_t keys_permuted; /* permuted key copies built (first use, and again after the element's key was installed again)     */
     uint64_t key_bytes;     /* device bytes the permuted copies hold now (a level: kept across reset)                            */
-    uint64_t reserved[4];
+    uint64_t mod_downs;     /* mod-downs: one per key product for the eager calls, one per chunk with a non-identity element for
+                             * he355_rotate_hoisted_plain_sum_lazy                                                                 */
+    uint64_t reserved[3];
 } he355_hoist_stats_t;
 int he355_hoist_stats(he355_ctx *ctx, he355_hoist_stats_t *out, int reset);
 int he355_hoist_release_keys(he355_ctx *ctx);   /* frees the permuted copies; they are rebuilt on next use */

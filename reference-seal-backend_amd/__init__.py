@@ -45,7 +45,7 @@ class PathStats(C.Structure):
 
 
 class HoistStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes")] + [("reserved", C.c_uint64 * 4)]
+    _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes", "mod_downs")] + [("reserved", C.c_uint64 * 3)]
 
 
 class BfvRouteStats(C.Structure):
@@ -180,6 +180,8 @@ def lib():
             "he355_apply_galois_hoisted": (i32, [vp, i32, i32, u64, vp, C.POINTER(u32), u64, vp]),
             "he355_rotate_hoisted": (i32, [vp, i32, i32, u64, vp, C.POINTER(C.c_int32), u64, vp]),
             "he355_rotate_hoisted_plain_sum": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, vp, vp]),
+            "he355_rotate_hoisted_plain_sum_lazy": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, vp, vp]),
+            "he355_plain_extend_special": (i32, [vp, i32, u64, vp, vp, vp]),
             "he355_hoist_stats": (i32, [vp, C.POINTER(HoistStats), i32]),
             "he355_hoist_release_keys": (i32, [vp]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
@@ -219,7 +221,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -717,6 +719,17 @@ class Context:
         """out [n][2][L][N] = sum_r plain[r] (.) hoisted(inp, steps[r]); plain [len(steps)][L][N] NTT-form plaintexts; NTT-form ciphertexts"""
         arr = (C.c_int32 * max(1, len(steps)))(*[int(v) for v in steps])
         _check(lib().he355_rotate_hoisted_plain_sum(self.h, L, n, inp.ptr, arr, len(steps), plain.ptr, out.ptr))
+
+    def rotate_hoisted_plain_sum_lazy(self, L, n, inp, steps, plain_qp, out):
+        """out [n][2][L][N] = the same sum with ONE mod-down: the key products are accumulated in the extended basis; plain_qp
+        [len(steps)][L + 1][N], row L under the special prime (plain_extend_special)"""
+        arr = (C.c_int32 * max(1, len(steps)))(*steps)
+        _check(lib().he355_rotate_hoisted_plain_sum_lazy(self.h, L, n, inp.ptr, arr, len(steps), plain_qp.ptr, out.ptr))
+
+    def plain_extend_special(self, L, n, plain_ntt, plain_qp, mismatch=None):
+        """plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N], row L under the special prime; mismatch (optional): one device word that
+        receives the number of (coefficient, prime >= 1) pairs that disagree with prime 0"""
+        _check(lib().he355_plain_extend_special(self.h, L, n, plain_ntt.ptr, plain_qp.ptr, mismatch.ptr if mismatch is not None else None))
 
     def hoist_stats(self, reset: bool = False) -> dict:
         """what the hoisted calls did (he355_hoist_stats): digit lifts, key products, permuted keys built, bytes those copies hold"""

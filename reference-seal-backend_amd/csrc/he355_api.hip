@@ -963,6 +963,7 @@ public:
                     continue;
                 }
                 ++hoist_.key_products;
+                ++hoist_.mod_downs; // (every element pays its own)
                 launch_k3(env, L, nc, B, key[r]);
                 if (coeff) {
                     launch_bfv_tail_sp(env, nc * 2, B.tpr, S.rlr);
@@ -982,6 +983,90 @@ public:
                 }
             }
         });
+        HIPCHECK(hipGetLastError());
+    }
+    // The lazy-mod-down plain sum: out [n][2][L][N] = B + moddown(A), A = sum_r plain_qp[r] (.) sigma_r(key product r) accumulated in the
+    // extended basis Q P, B = the part that needs no key accumulated in Q (the definition: include/he355.h).  The lift runs as in
+    // rotate_hoisted; every keyed element then pays launch_k3 and ONE accumulate launch, and the mod-down runs once per chunk.  No scratch
+    // of its own: B.c01 holds the Q part of A, B.tp its P part (k_k3 leaves the special prime's sums in B.tpr, after its inverse row pass;
+    // the accumulate kernel's special-prime waves transform them back -- k3_body.inc is untouched), the output chunk itself holds B and
+    // B.e the corrections.  One stream; NTT-domain pipeline only.
+    void rotate_hoisted_lazy(const HoistPlan &pl, int L, u64 n, const u64 *in, const u64 *plain_qp, u64 *out)
+    {
+        use();
+        for (uint32_t e : pl.elts)
+            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
+        const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
+        const int SP = (int)P.K - 1;
+        std::vector<const uint32_t *> table(n_elts, nullptr);
+        std::vector<const u64 *> key(n_elts, nullptr);
+        for (size_t r = 0; r < n_elts; ++r) {
+            const uint32_t e = pl.elts[r];
+            if (e != 1) { table[r] = perm(e); key[r] = hoist_key(e); }
+        }
+        const uint32_t *ident = pl.keyed ? perm(1) : nullptr;
+        for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
+            const KernelEnv env = batch_env(0, true);
+            const KsBuffers &B = S.ks;
+            const u64 *a = in + off * 2 * LN;
+            u64 *o = out + off * 2 * LN;
+            if (pl.keyed) {
+                ++hoist_.digit_lifts;
+                launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, Indexer{}, ident, B, nullptr, false, true, nullptr, true);
+                launch_k2(env, L, nc, B);
+            }
+            bool first_a = true, first_b = true;
+            for (size_t r = 0; r < n_elts; ++r) {
+                const u64 *pt = plain_qp + r * (LN + N);
+                if (!key[r]) {
+                    launch_hoist_acc_qp(env, L, nc, nullptr, nullptr, a, nullptr, pt, nullptr, 0, nullptr, o, false, first_b);
+                } else {
+                    ++hoist_.key_products;
+                    launch_k3(env, L, nc, B, key[r]);
+                    launch_hoist_acc_qp(env, L, nc, B.t, B.tpr, a, table[r], pt, B.c01, B.c01_item_stride, B.tp, o, first_a, first_b);
+                    first_a = false;
+                }
+                first_b = false;
+            }
+            if (!pl.keyed) return;
+            ++hoist_.mod_downs; // one per chunk, however many elements
+            PolyView pv = poly_view(B.tp, 1, N, 1);
+            pv.prime_of[0] = (unsigned char)SP;
+            launch_rows_inv(env, pv, (u32)(nc * 2));
+            launch_floor_cols(env, SP, L, nc * 2, B.tp, B.e);
+            FloorRowsArgs fr;
+            fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
+            fr.cols = B.e;
+            fr.tsrc = B.c01; fr.tsrc_op_stride = B.c01_item_stride; fr.tsrc_poly_stride = LN;
+            fr.addend = o; fr.add_op_stride = 2 * LN; fr.add_poly_stride = LN;
+            fr.out = o; fr.out_op_stride = 2 * LN; fr.out_poly_stride = LN;
+            fr.tail_prime = -1; fr.tail = nullptr;
+            launch_floor_rows(env, nc, fr);
+        });
+        HIPCHECK(hipGetLastError());
+    }
+    // plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N]: the rows copied and row L = NTT_P of the coefficients of row 0, centred
+    // (he355_plain_extend_special).  mismatch (optional, one device word): the (coefficient, prime >= 1) pairs that disagree with row 0.
+    void plain_extend_special(int L, u64 n, const u64 *plain_ntt, u64 *plain_qp, u64 *mismatch)
+    {
+        use();
+        const size_t N = P.N;
+        const int Lc = mismatch ? L : 1, SP = (int)P.K - 1;
+        if (mismatch) HIPCHECK(hipMemsetAsync(mismatch, 0, 8, stream_));
+        const u64 chunk = std::max<u64>(1, std::min<u64>(n, ((u64)1 << 27) / ((u64)Lc * N * 8)));
+        const PoolBlock tmp = scoped_block((size_t)chunk * Lc * N * 8);
+        for (u64 off = 0; off < n; off += chunk) {
+            const u64 c = std::min<u64>(chunk, n - off);
+            const u64 *src = plain_ntt + off * L * N;
+            u64 *dst = plain_qp + off * (L + 1) * N;
+            HIPCHECK(hipMemcpy2DAsync(tmp.get(), (size_t)Lc * N * 8, src, (size_t)L * N * 8, (size_t)Lc * N * 8, (size_t)c, hipMemcpyDeviceToDevice, stream_));
+            launch_ntt_inverse(env_, poly_view(tmp.get(), Lc, N, Lc), (u32)c);
+            launch_plain_extend(env_, L, c, src, tmp.get(), Lc, dst, mismatch);
+            PolyView pv = poly_view(dst + (size_t)L * N, 1, N, 1);
+            pv.item_stride = (u64)(L + 1) * N;
+            pv.prime_of[0] = (unsigned char)SP;
+            launch_ntt_forward(env_, pv, (u32)c);
+        }
         HIPCHECK(hipGetLastError());
     }
     void require_keyswitch() const
@@ -3331,6 +3416,24 @@ int he355_rotate_hoisted(he355_ctx *c, int L, int ntt_form, uint64_t n, const ui
 int he355_rotate_hoisted_plain_sum(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, const uint64_t *plain, uint64_t *out)
 {
     return hoisted_call(c, "he355_rotate_hoisted_plain_sum", L, 1, n, in, nullptr, steps, n_steps, plain, out, true);
+}
+int he355_rotate_hoisted_plain_sum_lazy(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, const uint64_t *plain_qp,
+                                        uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        const HoistPlan pl = plan_rotate_hoisted(*c->params, "he355_rotate_hoisted_plain_sum_lazy", L, 1, n, in, nullptr, steps, n_steps, plain_qp, out, true, true);
+        if (pl.empty) return; // nothing to sum: no buffer is touched, no device asked for
+        dev(c).rotate_hoisted_lazy(pl, L, n, in, plain_qp, out);
+    });
+}
+int he355_plain_extend_special(he355_ctx *c, int L, uint64_t n, const uint64_t *plain_ntt, uint64_t *plain_qp, uint64_t *mismatch)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        if (plan_plain_extend(*c->params, L, n, plain_ntt, plain_qp)) return;
+        dev(c).plain_extend_special(L, n, plain_ntt, plain_qp, mismatch);
+    });
 }
 int he355_hoist_stats(he355_ctx *c, he355_hoist_stats_t *out, int reset)
 {

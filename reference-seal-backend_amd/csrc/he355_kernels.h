@@ -230,6 +230,8 @@ HE355_FWD(launch_bfv_tail_sp)
 HE355_FWD(launch_bfv_tail_fin)
 HE355_FWD(launch_key_permute)
 HE355_FWD(launch_hoist_finish_ntt)
+HE355_FWD(launch_hoist_acc_qp)
+HE355_FWD(launch_plain_extend)
 HE355_FWD(launch_hoist_addend_coeff)
 HE355_FWD(launch_hoist_finish_coeff)
 HE355_FWD(launch_rows_inv_select)

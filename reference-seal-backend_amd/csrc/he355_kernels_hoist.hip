@@ -11,6 +11,12 @@
 //                          (Params::galois_perm_ntt), read whole in 16-byte loads -- the key switch's and, for polynomial 0, the input's c0 --
 //                          added, permuted through the wave's LDS row and stored in 16-byte stores.  <PLAIN>: times the plaintext's row, the
 //                          first element of the sum stores and later ones read-modify-write the output row (one stream, launches in order).
+//   k_hoist_acc_qp         the lazy plain sum (he355_rotate_hoisted_plain_sum_lazy): one wave per (ciphertext, polynomial, tile, row), tiles = the
+//                          data primes and the special prime.  The key product's ONE source row -- under the special prime k_k3 left it after
+//                          its inverse row pass: the wave runs the forward row pass -- permuted through the wave's LDS row, times the plaintext's
+//                          row, accumulated in Q P; c0's row goes through the same permutation into the output rows.  ONE mod-down follows.
+//   k_plain_extend         streaming (he355_plain_extend_special): the rows of a plaintext copied and its row under the special prime made
+//                          from the centred coefficients of row 0; optionally counts the coefficients whose other residues disagree.
 //   k_hoist_addend_coeff   streaming, once per chunk (BFV coefficient form): (c0, 0), what launch_bfv_tail_fin adds every element's key
 //                          switch into.
 //   k_hoist_finish_coeff   streaming: the signed gather of Params::galois_gather_coeff(g) on (c0 + u0, u1); a lane gathers two coefficients
@@ -121,6 +127,164 @@ __global__ void __launch_bounds__(kBlock) k_hoist_finish_ntt(HoistNttArgs A, con
     store_rowC(orow, lane, v);
 }
 
+struct HoistAccArgs {
+    const u64 *t;         // [n_ops][2][L][N]: one element's key product under the permuted key, data primes, canonical NTT form (KEYED)
+    const u64 *tpr;       // [n_ops][2][N]: the same under the special prime AFTER k_k3's inverse row pass (raw rows; coefficients when N = 1024) (KEYED)
+    const u64 *in;        // [n_ops][2][L][N]: the chunk's input ciphertexts
+    const uint32_t *perm; // [N]: Params::galois_perm_ntt(g) (KEYED)
+    const u64 *plain;     // [L + 1][N]: the element's plaintext, row L under the special prime (the identity reads rows 0 .. L - 1)
+    u64 *aq;              // [n_ops] x aq_op_stride, [2][L][N] each: the Q part of the accumulator A (KEYED)
+    u64 aq_op_stride;
+    u64 *ap;              // [n_ops][2][N]: the P part of A (KEYED)
+    u64 *out;             // [n_ops][2][L][N]: the accumulator B, the call's output rows
+    u64 n_ops;
+    int L, K, logn1;
+    u64 sp_fix;           // 1024^-1 mod P, what the forward row pass of an unnormalised inverse row pass leaves to divide out; N = 1024: 1
+    int first_a;          // A starts with this element (stored, not read)
+    int first_b;          // B starts with this term (stored, not read; a keyed first term zeroes polynomial 1 of B)
+};
+// The special prime's source row back in canonical NTT form, layout C: k_k3 leaves its sums after the inverse row pass (tpr), an
+// unnormalised Gentleman-Sande pass of ten stages whose N^-1 waits in the column pass (ntt_core.h: row_inv_A_w<., false>), so the forward
+// row pass of the same row returns 1024 times the sums and `fix` = 1024^-1 mod P takes that out.  N = 1024: the inverse row pass was the
+// whole transform, N^-1 = 1024^-1 included (bfly_inv_last), and the forward row pass returns the sums themselves (fix = 1, not multiplied).
+// The raw words are made canonical first: the forward pass then starts from the range it has after a column pass in either engine.
+template <class Ar>
+__device__ __forceinline__ void hoist_sp_row(const PrimeDev &P, const u64 *row, bool last, u32 rowbase, int lane, u64 *lds, const ModU64 &m, u64 fix, u64 v[kRowE])
+{
+    const Ar ar = make_ar(P, (Ar *)nullptr);
+    typename Ar::T x[kRowE];
+    load_rowA(row, lane, v);
+#pragma unroll
+    for (int r = 0; r < kRowE; ++r) x[r] = ar.from_canon(last ? v[r] : ar.to_canon(ar.from_raw(v[r])));
+    wave_rows_fwd(ar, tw_table(gtw(P.fwd), rowbase), lane, lds, x);
+#pragma unroll
+    for (int r = 0; r < kRowE; ++r) v[r] = last ? ar.to_canon(x[r]) : hoist_sp_unscale(ar.to_canon(x[r]), fix, m);
+}
+// One term of the lazy plain sum.  KEYED: one wave per (ciphertext, polynomial, tile 0 .. L, row): the ONE source row of the key product --
+// t for a data prime, tpr through hoist_sp_row for the special prime -- permuted through the wave's LDS row, times the plaintext's row, into A; for polynomial 0
+// and a data prime the same wave carries the input's c0 source row through the same permutation into B.  The identity (!KEYED): one wave per
+// (ciphertext, polynomial, data prime, row), the input's own row times the plaintext's into B, no permutation.
+template <bool KEYED>
+__global__ void __launch_bounds__(kBlock) k_hoist_acc_qp(HoistAccArgs A, const PrimeDev *primes)
+{
+    __shared__ u64 lds_all[kWaves][kLdsRow];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const u32 n1 = 1u << A.logn1;
+    const int tiles = KEYED ? A.L + 1 : A.L;
+    const u64 total = (A.n_ops * 2 * (u64)tiles) << A.logn1;
+    const u64 job = (u64)blockIdx.x * kWaves + wave;
+    if (job >= total) return; // (the whole wave; waves of a block share nothing)
+    const u32 a_row = (u32)(job & (n1 - 1));
+    const u64 pi = job >> A.logn1; // (op, polynomial, tile)
+    const int idx = (int)(pi % (u64)tiles);
+    const u64 ok = pi / (u64)tiles, op = ok >> 1; // ok = op * 2 + polynomial
+    const bool poly0 = (ok & 1) == 0;
+    const u64 N = (u64)n1 << kRowLog, arow = (u64)a_row << kRowLog;
+    const PrimeDev &P = primes[hoist_qp_prime(idx, A.L, A.K)];
+    const ModU64 m = make_modu(P);
+    const u64 ct_off = (ok * (u64)A.L + (u64)idx) * N; // the [op][polynomial][prime] layout of in / t / out (idx < L)
+    u64 v[kRowE], pt[kRowE], acc[kRowE];
+    load_rowC(A.plain + (u64)idx * N + arow, lane, pt);
+    if constexpr (!KEYED) {
+        load_rowC(A.in + ct_off + arow, lane, v);
+    } else {
+        u64 *lds = lds_all[wave];
+        const uint32_t *pm = A.perm + arow;
+        const u64 srow = (u64)hoist_src_row(__builtin_amdgcn_readfirstlane(pm[0])) << kRowLog;
+        const bool data = idx < A.L;
+        if (data) {
+            load_rowC(A.t + ct_off + srow, lane, v);
+        } else { // (wave-uniform)
+            const u32 rowbase = n1 + (u32)(srow >> kRowLog);
+            if (P.f64) hoist_sp_row<ArF64>(P, A.tpr + ok * N + srow, A.logn1 == 0, rowbase, lane, lds, m, A.sp_fix, v);
+            else hoist_sp_row<ArU64>(P, A.tpr + ok * N + srow, A.logn1 == 0, rowbase, lane, lds, m, A.sp_fix, v);
+        }
+        // the output positions this lane stores (layout C: four runs of four neighbours) and where each comes from in the source row
+        u32 pl[kRowE];
+        {
+            const uint32_t *pb = pm + ((lane >> 2) << 6) + ((lane & 3) << 2);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint4 w = *reinterpret_cast<const uint4 *>(pb + (c << 4));
+                pl[4 * c + 0] = (u32)lds_pad((int)hoist_src_elem(w.x)); pl[4 * c + 1] = (u32)lds_pad((int)hoist_src_elem(w.y));
+                pl[4 * c + 2] = (u32)lds_pad((int)hoist_src_elem(w.z)); pl[4 * c + 3] = (u32)lds_pad((int)hoist_src_elem(w.w));
+            }
+        }
+        lds_store_C(lds, lane, v);
+        HE_WAVE_SYNC();
+#pragma unroll
+        for (int r = 0; r < kRowE; ++r) v[r] = lds[pl[r]];
+        u64 *arw = data ? A.aq + op * A.aq_op_stride + ((ok & 1) * (u64)A.L + (u64)idx) * N + arow : A.ap + ok * N + arow;
+        if (A.first_a) {
+#pragma unroll
+            for (int r = 0; r < kRowE; ++r) acc[r] = 0;
+        } else {
+            load_rowC(arw, lane, acc);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowE; ++r) acc[r] = hoist_acc_term(acc[r], v[r], pt[r], m);
+        store_rowC(arw, lane, acc);
+        if (!data) return; // (wave-uniform: B lives under the data primes only)
+        if (!poly0) {      // B[1] takes identity terms only: a keyed first term starts it at zero
+            if (A.first_b) {
+#pragma unroll
+                for (int r = 0; r < kRowE; ++r) acc[r] = 0;
+                store_rowC(A.out + ct_off + arow, lane, acc);
+            }
+            return;
+        }
+        load_rowC(A.in + ct_off + srow, lane, v); // c0's source row through the same permutation
+        HE_WAVE_SYNC();                             // (every lane has read the key product's row out of LDS)
+        lds_store_C(lds, lane, v);
+        HE_WAVE_SYNC();
+#pragma unroll
+        for (int r = 0; r < kRowE; ++r) v[r] = lds[pl[r]];
+    }
+    u64 *orow = A.out + ct_off + arow;
+    if (A.first_b) {
+#pragma unroll
+        for (int r = 0; r < kRowE; ++r) acc[r] = 0;
+    } else {
+        load_rowC(orow, lane, acc);
+    }
+#pragma unroll
+    for (int r = 0; r < kRowE; ++r) acc[r] = hoist_acc_term(acc[r], v[r], pt[r], m);
+    store_rowC(orow, lane, acc);
+}
+
+struct PlainExtendArgs {
+    const u64 *src;   // [n][L][N]: the plaintexts, NTT form (rows 0 .. L - 1 are copied)
+    const u64 *coeff; // [n][Lc][N]: their rows 0 .. Lc - 1 in coefficient form; Lc = L with the check, else 1
+    u64 *dst;         // [n][L + 1][N]: row L = the centred coefficients of row 0 mod P, coefficient form (the forward transform follows)
+    u64 *mismatch;    // null: no check
+    u64 n_polys;      // n (L + 1)
+    int L, Lc, K, logN;
+};
+// streaming: a lane owns two neighbouring coefficients of one row of dst, 16-byte accesses
+__global__ void __launch_bounds__(kBlock) k_plain_extend(PlainExtendArgs A, const PrimeDev *primes)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (A.logN - 1);
+    if (p >= A.n_polys) return; // (a block lies inside one row: the whole block leaves)
+    const u32 e2 = (u32)(gid & (((u64)1 << (A.logN - 1)) - 1));
+    const int idx = (int)(p % (u64)(A.L + 1));
+    const u64 item = p / (u64)(A.L + 1);
+    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(A.dst + (p << A.logN)) + e2;
+    if (idx < A.L) *d = reinterpret_cast<const ulonglong2 *>(A.src + ((item * (u64)A.L + (u64)idx) << A.logN))[e2];
+    if (idx == 0 || (idx < A.L && !A.mismatch)) return;
+    const u64 q0 = primes[0].q, half0 = q0 >> 1;
+    const ModU64 m = make_modu(primes[hoist_qp_prime(idx, A.L, A.K)]);
+    const ulonglong2 c = reinterpret_cast<const ulonglong2 *>(A.coeff + ((item * (u64)A.Lc) << A.logN))[e2];
+    const ulonglong2 w = make_ulonglong2(hoist_centred_mod(c.x, q0, half0, m), hoist_centred_mod(c.y, q0, half0, m));
+    if (idx == A.L) {
+        *d = w;
+        return;
+    }
+    const ulonglong2 g = reinterpret_cast<const ulonglong2 *>(A.coeff + ((item * (u64)A.Lc + (u64)idx) << A.logN))[e2];
+    const unsigned bad = (unsigned)__popcll(__ballot(g.x != w.x)) + (unsigned)__popcll(__ballot(g.y != w.y));
+    if (bad && (threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long *>(A.mismatch), (unsigned long long)bad);
+}
+
 // ct [n_ops][2][L][N] -> dst, same layout: polynomial 0 copied, polynomial 1 zero
 __global__ void __launch_bounds__(kBlock) k_hoist_addend_coeff(const u64 *ct, u64 *dst, int L, int logN, u64 n_polys)
 {
@@ -162,6 +326,31 @@ void launch_hoist_finish_ntt(const KernelEnv &env, int L, u64 n_ops, const u64 *
     const dim3 g(grid_blocks((jobs + kWaves - 1) / kWaves, "hoisted rotation", "ciphertexts"));
     if (plain) hipLaunchKernelGGL(k_hoist_finish_ntt<true>, g, dim3(kBlock), 0, env.stream, A, env.primes);
     else hipLaunchKernelGGL(k_hoist_finish_ntt<false>, g, dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_hoist_acc_qp(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *tpr, const u64 *in, const uint32_t *perm, const u64 *plain_qp, u64 *aq,
+                         u64 aq_op_stride, u64 *ap, u64 *out, bool first_a, bool first_b)
+{
+    if (!n_ops) return;
+    const bool keyed = t != nullptr;
+    if (keyed && (!tpr || !perm || !aq || !ap)) throw std::runtime_error("lazy plain sum: a keyed term needs both halves of the key product, the permutation and the accumulators");
+    HoistAccArgs A{};
+    A.t = t; A.tpr = tpr; A.in = in; A.perm = perm; A.plain = plain_qp; A.aq = aq; A.aq_op_stride = aq_op_stride; A.ap = ap; A.out = out;
+    A.n_ops = n_ops; A.L = L; A.K = env.K; A.logn1 = env.logn1;
+    A.sp_fix = env.logn1 ? hoist_row_pass_fix(env.prime_q[env.K - 1]) : 1;
+    A.first_a = first_a ? 1 : 0; A.first_b = first_b ? 1 : 0;
+    const u64 jobs = (n_ops * 2 * (u64)(keyed ? L + 1 : L)) << env.logn1;
+    const dim3 g(grid_blocks((jobs + kWaves - 1) / kWaves, "lazy plain sum", "ciphertexts"));
+    if (keyed) hipLaunchKernelGGL(k_hoist_acc_qp<true>, g, dim3(kBlock), 0, env.stream, A, env.primes);
+    else hipLaunchKernelGGL(k_hoist_acc_qp<false>, g, dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_plain_extend(const KernelEnv &env, int L, u64 n, const u64 *src, const u64 *coeff, int Lc, u64 *dst, u64 *mismatch)
+{
+    if (!n) return;
+    if (Lc != (mismatch ? L : 1)) throw std::runtime_error("plaintext extension: the coefficient rows are row 0 alone, or all rows with the check");
+    PlainExtendArgs A{};
+    A.src = src; A.coeff = coeff; A.dst = dst; A.mismatch = mismatch; A.n_polys = n * (u64)(L + 1); A.L = L; A.Lc = Lc; A.K = env.K;
+    A.logN = env.logn1 + kRowLog;
+    hipLaunchKernelGGL(k_plain_extend, dim3(streaming_grid(A.n_polys, A.logN, "plaintext extension", "plaintexts")), dim3(kBlock), 0, env.stream, A, env.primes);
 }
 void launch_hoist_addend_coeff(const KernelEnv &env, int L, u64 n_ops, const u64 *ct, u64 *dst)
 {

@@ -92,6 +92,17 @@ void launch_key_permute(const KernelEnv &env, const u64 *src, u64 *dst, const ui
 // out = plain (.) that (first) or out += plain (.) that
 void launch_hoist_finish_ntt(const KernelEnv &env, int L, u64 n_ops, const u64 *u, const u64 *in, const uint32_t *perm, u64 *out, const u64 *plain = nullptr,
                              bool first = true);
+// One term of the lazy plain sum (he355_rotate_hoisted_plain_sum_lazy), plain_qp [L + 1][N] with row L under the special prime.
+// Keyed (t not null): t [n_ops][2][L][N] / tpr [n_ops][2][N] as launch_k3(K3_ALL) leaves them under the element's permuted key ->
+// A += plain_qp (.) sigma(t, NTT(tpr)), A = (aq: n_ops x aq_op_stride, [2][L][N] each; ap [n_ops][2][N], canonical NTT form under the
+// special prime), and out[.][0] += plain_qp (.) sigma(in.c0).  The identity (t null): out += plain_qp (.) in, both polynomials.
+// first_a / first_b: the accumulator A / out starts with this term (stored, not read; a keyed first term zeroes out[.][1]).
+void launch_hoist_acc_qp(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *tpr, const u64 *in, const uint32_t *perm, const u64 *plain_qp, u64 *aq,
+                         u64 aq_op_stride, u64 *ap, u64 *out, bool first_a, bool first_b);
+// he355_plain_extend_special's streaming half: src [n][L][N] NTT form -> dst [n][L + 1][N], rows 0 .. L - 1 copied, row L = the coefficients
+// of row 0 (coeff [n][Lc][N], coefficient form) centred and reduced mod the special prime, coefficient form (launch_ntt_forward follows).
+// mismatch (optional, one device word, zeroed by the caller; needs Lc = L, else Lc = 1): += the (coefficient, prime >= 1) pairs that disagree
+void launch_plain_extend(const KernelEnv &env, int L, u64 n, const u64 *src, const u64 *coeff, int Lc, u64 *dst, u64 *mismatch);
 // dst [n_ops][2][L][N] = (ct.c0, 0)
 void launch_hoist_addend_coeff(const KernelEnv &env, int L, u64 n_ops, const u64 *ct, u64 *dst);
 // out [n_ops][2][L][N] = the signed coefficient gather of src, both polynomials

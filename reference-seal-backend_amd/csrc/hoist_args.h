@@ -1,5 +1,5 @@
 // hoist_args.h -- the argument checks of the hoisted rotations (he355_apply_galois_hoisted, he355_rotate_hoisted,
-// he355_rotate_hoisted_plain_sum) that need no device, made ONCE per call in the style of bfv_pir_args.h: the C ABI wrapper runs the check
+// he355_rotate_hoisted_plain_sum, he355_rotate_hoisted_plain_sum_lazy, he355_plain_extend_special) that need no device, made ONCE per call in the style of bfv_pir_args.h: the C ABI wrapper runs the check
 // before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands the elements the check worked
 // out to DeviceContext.  Whether an element's Galois key is installed is the device context's to know; it checks that before its first launch.
 // Host-only on purpose: no HIP header, so tests/rotate_hoisted_args_main.cpp runs every check at its edges under the sanitizers.
@@ -18,8 +18,9 @@ struct HoistPlan {
 };
 // `in` [n][2][L][N]; `out` [n_elts][n][2][L][N], or with `plain_sum` [n][2][L][N] and `plain` [n_elts][L][N].  The elements come from
 // h_elts, or from h_steps (step 0: the identity; any other step through Params::galois_elt_from_step) when h_elts is null.
+// plain_special (he355_rotate_hoisted_plain_sum_lazy): every plaintext carries one more row, under the special prime: [n_elts][L + 1][N].
 inline HoistPlan plan_rotate_hoisted(const Params &p, const char *what, int L, int ntt_form, u64 n, const u64 *in, const uint32_t *h_elts, const int32_t *h_steps,
-                                     u64 n_elts, const u64 *plain, const u64 *out, bool plain_sum)
+                                     u64 n_elts, const u64 *plain, const u64 *out, bool plain_sum, bool plain_special = false)
 {
     const std::string w(what);
     check_level(p, w, L);
@@ -44,7 +45,7 @@ inline HoistPlan plan_rotate_hoisted(const Params &p, const char *what, int L, i
         pl.keyed += e != 1;
     }
     // every slab in words, formed in 128 bits: 2^60 words (2^63 bytes) is the most one may span
-    const u128 ctn = (u128)2 * (u128)L * p.N, in_w = (u128)n * ctn, out_w = plain_sum ? in_w : in_w * n_elts, plain_w = plain_sum ? (u128)n_elts * (u128)L * p.N : 0;
+    const u128 ctn = (u128)2 * (u128)L * p.N, in_w = (u128)n * ctn, out_w = plain_sum ? in_w : in_w * n_elts, plain_w = plain_sum ? (u128)n_elts * (u128)(L + (plain_special ? 1 : 0)) * p.N : 0;
     const u128 cap = (u128)1 << 60;
     if (n > cap || in_w > cap || out_w > cap || plain_w > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
     pl.empty = n == 0 || n_elts == 0;
@@ -53,9 +54,22 @@ inline HoistPlan plan_rotate_hoisted(const Params &p, const char *what, int L, i
     if (ro.overlaps(ri)) throw std::invalid_argument(w + ": `d_out` overlaps `d_in`");
     if (plain_sum) {
         if (!plain) throw std::invalid_argument(w + ": null plaintexts");
-        if (ro.overlaps(word_range(w, plain, (u64)plain_w))) throw std::invalid_argument(w + ": `d_out` overlaps `d_plain`");
+        if (ro.overlaps(word_range(w, plain, (u64)plain_w))) throw std::invalid_argument(w + (plain_special ? ": `d_out` overlaps `d_plain_qp`" : ": `d_out` overlaps `d_plain`"));
     }
     return pl;
+}
+// he355_plain_extend_special: plain_ntt [n][L][N] -> plain_qp [n][L + 1][N].  True: n == 0, the call touches nothing.
+inline bool plan_plain_extend(const Params &p, int L, u64 n, const u64 *plain_ntt, const u64 *plain_qp)
+{
+    const std::string w("he355_plain_extend_special");
+    check_level(p, w, L);
+    if (p.K < 2) throw std::invalid_argument(w + ": encryption parameters have no special prime");
+    const u128 in_w = (u128)n * (u128)L * p.N, out_w = (u128)n * (u128)(L + 1) * p.N, cap = (u128)1 << 60;
+    if (n > cap || in_w > cap || out_w > cap) throw std::invalid_argument(w + ": the plaintexts span more than 2^60 words");
+    if (n == 0) return true;
+    if (!plain_ntt || !plain_qp) throw std::invalid_argument(w + ": null pointer");
+    if (word_range(w, plain_qp, (u64)out_w).overlaps(word_range(w, plain_ntt, (u64)in_w))) throw std::invalid_argument(w + ": `d_plain_qp` overlaps `d_plain_ntt`");
+    return false;
 }
 
 } // namespace he355

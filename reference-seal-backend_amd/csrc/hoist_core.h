@@ -20,4 +20,29 @@ HE_HD u64 hoist_plain_term(u64 acc, u64 v, u64 plain, const ModU64 &m) { return 
 HE_HD u32 hoist_gather_src(u32 g) { return g & 0x7fffffffu; }
 HE_HD u64 hoist_gather_sign(u64 v, u32 g, u64 q) { return (g >> 31) && v ? q - v : v; }
 
+// ---- the lazy plain sum (k_hoist_acc_qp): the key products stay in the extended basis Q P, are permuted, multiplied by plaintexts that carry
+// a residue under the special prime and accumulated there; ONE mod-down per sum (he355_rotate_hoisted_plain_sum_lazy) ----------------------
+// tile idx of a level-L accumulator: the data primes 0 .. L - 1, then the special prime K - 1 (row L of a [L + 1][N] plaintext)
+HE_HD int hoist_qp_prime(int idx, int L, int K) { return idx < L ? idx : K - 1; }
+// one term of an accumulator (A in Q P, B in Q): acc + plain * v, canonical in and out, so the terms may come in any order (first: the
+// accumulator starts here, `acc` is passed as 0)
+HE_HD u64 hoist_acc_term(u64 acc, u64 v, u64 plain, const ModU64 &m) { return addmod(acc, mulmod(v, plain, m), m.q); }
+// The special prime's key product reaches the accumulate kernel after k_k3's inverse row pass; the wave runs the forward row pass on it.
+// Ten Gentleman-Sande stages without N^-1 and ten Cooley-Tukey stages make 2^10 times the row: fix = 1024^-1 mod q takes that out
+// (ten halvings of 1 mod the odd q).  N = 1024: the inverse pass carried N^-1 itself and nothing is left to take out.
+HE_HD u64 hoist_row_pass_fix(u64 q)
+{
+    u64 x = 1;
+    for (int s = 0; s < 10; ++s) x = (x & 1) ? (x >> 1) + (q >> 1) + 1 : x >> 1;
+    return x;
+}
+HE_HD u64 hoist_sp_unscale(u64 v, u64 fix, const ModU64 &m) { return mulmod(v, fix, m); }
+// he355_plain_extend_special: c, a residue under q0 (half0 = floor(q0 / 2)), centred into (-q0 / 2, q0 / 2] and reduced mod m.q
+HE_HD u64 hoist_centred_mod(u64 c, u64 q0, u64 half0, const ModU64 &m)
+{
+    if (c <= half0) return barrett64(c, m);
+    const u64 r = barrett64(q0 - c, m); // -(q0 - c)
+    return r ? m.q - r : 0;
+}
+
 } // namespace he355
