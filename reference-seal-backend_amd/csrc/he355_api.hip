@@ -25,6 +25,7 @@
 #include "he_params.h"
 #include "hoist_args.h"
 #include "ntt_core.h"
+#include "rotation_plan.h"
 #include "client/he_client.h"
 #include "client/multiword.h"
 
@@ -647,7 +648,7 @@ public:
     // coefficients per residue on (profiles/r05_latency_boundary.txt: N = 2^15 crosses between 4 and 5 ciphertexts at depth 6 and 16, 2^14
     // between 6 and 8, 2^13 at 12), so the default limit is 2^17 / N ciphertexts, at most 12; he355_set_latency_max replaces it.
     u64 lat_limit() const { return lat_auto_ ? std::min<u64>(12, std::max<u64>(1, ((u64)1 << 17) / P.N)) : lat_max_; }
-    // ... for a kernel environment (a BFV context runs its rotation chains in the NTT domain on the CKKS pipeline: ntt_env)
+    // ... for a kernel environment (a BFV context runs its rotation chains in the NTT domain on the CKKS pipeline: batch_env(0, true))
     bool latency_shape(const KernelEnv &e, u64 nc) const { return e.scheme == kSchemeCKKS && nc <= lat_limit() && P.K >= 2; }
     // Ring-in-LDS shape (he355_kernels_lds.hip): N <= 8192, L <= 6, NTT-domain pipeline, batches up to lds_limit() -- two
     // launches of L^2 + 2L one-polynomial workgroups per ciphertext instead of six launches through HBM.  Where the throughput shape's
@@ -708,7 +709,8 @@ public:
         return k3_can_fuse(e) && fuse_pays(e, nc, L) ? KsShape::Fused : KsShape::Unfused;
     }
     // the kernel environment of a batch on stream `which`
-    // ntt: the NTT-domain (CKKS) pipeline whatever the context's scheme (ntt_env)
+    // ntt: the NTT-domain (CKKS) pipeline whatever the context's scheme (a BFV context's tables are the same primes; only the data
+    // representation differs)
     KernelEnv batch_env(int which = 0, bool ntt = false) const
     {
         KernelEnv env = env_;
@@ -819,9 +821,12 @@ public:
                 } else if (in_k3) { // c0, c1 and the NTT-form c2 read from the size-3 input where it lies (k_k1 only sends c2 through the inverse row pass)
                     ops.c1_mode = 3; ops.c1_src = src.a + off * 3 * LN;
                 }
-                const K1Mode mode = product ? K1_MUL : galois ? K1_GALOIS : K1_CT3;
-                launch_k1(env, L, mode, nc, off, src.a, src.b, src.ix, src.table, B, src.addend, in_k3 && product, in_k3 && !product,
-                          grouped ? &groups : nullptr, in_k3 && galois);
+                K1Operands k1;
+                k1.mode = product ? K1_MUL : galois ? K1_GALOIS : K1_CT3;
+                k1.a = src.a; k1.b = src.b; k1.ix = src.ix; k1.op_offset = off; k1.perm = src.table; k1.addend = src.addend;
+                k1.no_c01 = in_k3 && product; k1.no_c1 = in_k3 && !product; k1.no_c0n = in_k3 && galois;
+                k1.groups = grouped ? &groups : nullptr;
+                launch_k1(env, L, nc, k1, B);
                 key_switch_tail(env, L, nc, S, shape, in_k3 && product ? relin_scaled() : src.key, ops, grouped ? &groups : nullptr, off, ro, fork);
                 return;
             }
@@ -850,10 +855,8 @@ public:
             u64 *part = reserve(arena_[kLat0 + (env.stream == stream2_ ? 1 : 0)], (size_t)std::max(kLatSplit, kLatSplitU64) * nc * 2 * (L + 1) * N * 8);
             launch_k3(env, L, nc, B, key, K3_ALL, nullptr, kLatSplit, part, kLatSplitU64);
             launch_k3_combine(env, L, nc, B, kLatSplit, part, kLatSplitU64);
-            launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e, 0, 0, nullptr, 0, kLatTargets);
         } else if (shape == KsShape::Unfused) {
             launch_k3(env, L, nc, B, key, K3_ALL, nullptr, 1, nullptr, 0, groups, g_off);
-            launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e);
         } else {
             // fused: special prime first, its correction through the column pass, then the data primes with the mod-down finished
             // inside K3 (the sums never go to HBM)
@@ -892,30 +895,79 @@ public:
             launch_k3(env, L, nc, B, key, K3_DATA_ONLY, &f, 1, nullptr, 0, groups, g_off);
             return;
         }
-        // the row half of the unfused mod-down: c01 += (t - NTT(e)) * P^-1, starting the rescale (tail of prime L-1) where one follows
-        FloorRowsArgs fr;
-        fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
-        fr.cols = B.e;
-        fr.tsrc = B.t; fr.tsrc_op_stride = 2 * LN; fr.tsrc_poly_stride = LN;
-        fr.addend = B.c01; fr.add_op_stride = B.c01_item_stride; fr.add_poly_stride = LN;
-        fr.out = B.c01; fr.out_op_stride = B.c01_item_stride; fr.out_poly_stride = LN;
-        fr.tail_prime = rescale_out ? L - 1 : -1;
-        fr.tail = S.rlr;
-        launch_floor_rows(env, nc, fr);
+        // the unfused mod-down: c01 += (t - NTT(e)) * P^-1, starting the rescale (tail of prime L-1) where one follows
+        floor_step(env, SP, L, 2, nc, B.tpr, B.e, {B.t, 2 * LN, LN}, {B.c01, B.c01_item_stride, LN}, {B.c01, B.c01_item_stride, LN}, rescale_out ? L - 1 : -1, S.rlr,
+                   lat ? kLatTargets : 1);
         if (rescale_out) rescale_tail(env, L, 2, nc, S, B.c01, 2 * LN, rescale_out);
     }
     void rescale_tail(const KernelEnv &env, int L, int size, u64 nc, const Scratch &S, const u64 *src, u64 src_op_stride, u64 *out)
     {
         const size_t N = P.N, LN = (size_t)L * N, L1N = (size_t)(L - 1) * N;
-        launch_floor_cols(env, L - 1, L - 1, nc * size, S.rlr, S.f, 0, 0, nullptr, 0, latency_shape(env, nc) ? kLatTargets : 1);
+        floor_step(env, L - 1, L - 1, size, nc, S.rlr, S.f, {src, src_op_stride, LN}, {}, {out, (u64)size * L1N, L1N}, -1, nullptr, latency_shape(env, nc) ? kLatTargets : 1);
+    }
+    // One unfused floor step -- the key switch's mod-down (source: the special prime) or a rescale (source: the last data prime) -- as its
+    // two launches: the column half, `src` [nc * n_src][N] (raw rows of the source prime) -> the corrections under n_tgt targets in `cols`
+    // (tsplit > 1, the latency shape: a column's targets dealt to that many blocks), then the row half, out = (tsrc - NTT(cols)) * s^-1
+    // (+ addend).  The three operands are strided (words from op to op and from polynomial to polynomial); tail_prime >= 0: the rows of that
+    // prime also leave through the inverse row pass into `tail`, the source of the floor step that follows.
+    template <class T> struct Strided {
+        T *p = nullptr;
+        u64 op_stride = 0, poly_stride = 0;
+    };
+    void floor_step(const KernelEnv &env, int src_prime, int n_tgt, int n_src, u64 nc, const u64 *src, u64 *cols, Strided<const u64> tsrc, Strided<const u64> addend,
+                    Strided<u64> out, int tail_prime = -1, u64 *tail = nullptr, int tsplit = 1)
+    {
+        launch_floor_cols(env, src_prime, n_tgt, nc * (u64)n_src, src, cols, 0, 0, nullptr, 0, tsplit);
         FloorRowsArgs fr;
-        fr.src_prime = L - 1; fr.n_tgt = L - 1; fr.n_src = size;
-        fr.cols = S.f;
-        fr.tsrc = src; fr.tsrc_op_stride = src_op_stride; fr.tsrc_poly_stride = LN;
-        fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
-        fr.out = out; fr.out_op_stride = (u64)size * L1N; fr.out_poly_stride = L1N;
-        fr.tail_prime = -1; fr.tail = nullptr;
+        fr.src_prime = src_prime; fr.n_tgt = n_tgt; fr.n_src = n_src;
+        fr.cols = cols;
+        fr.tsrc = tsrc.p; fr.tsrc_op_stride = tsrc.op_stride; fr.tsrc_poly_stride = tsrc.poly_stride;
+        fr.addend = addend.p; fr.add_op_stride = addend.op_stride; fr.add_poly_stride = addend.poly_stride;
+        fr.out = out.p; fr.out_op_stride = out.op_stride; fr.out_poly_stride = out.poly_stride;
+        fr.tail_prime = tail_prime; fr.tail = tail;
         launch_floor_rows(env, nc, fr);
+    }
+    // What a hoisted call sets up before its first launch.  Every keyed element's Galois key must be installed: refused before anything is
+    // built.  Then per element its table -- the NTT-domain permutation, or (coeff) the coefficient-form gather -- and its permuted key
+    // (hoist_key; null: the identity, which gets a table only with ident_tables: the blocks of rotate_hoisted are finished through one),
+    // and the identity's permutation for the digit lift of the NTT-domain pipeline.
+    struct HoistSetup {
+        std::vector<const uint32_t *> table;
+        std::vector<const u64 *> key;
+        const uint32_t *ident = nullptr;
+    };
+    HoistSetup hoist_setup(const HoistPlan &pl, bool coeff, bool ident_tables)
+    {
+        for (uint32_t e : pl.elts)
+            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
+        const size_t n_elts = pl.elts.size();
+        HoistSetup hs{std::vector<const uint32_t *>(n_elts, nullptr), std::vector<const u64 *>(n_elts, nullptr), nullptr};
+        for (size_t r = 0; r < n_elts; ++r) {
+            const uint32_t e = pl.elts[r];
+            if (e != 1 || ident_tables) hs.table[r] = coeff ? gather(e) : perm(e);
+            if (e != 1) hs.key[r] = hoist_key(e);
+        }
+        if (pl.keyed && !coeff) hs.ident = perm(1);
+        return hs;
+    }
+    // The one digit lift of a chunk of a hoisted call, counted in he355_hoist_stats: the input's c1 as it lies (the identity's permutation)
+    // through k_k1's inverse row pass -- c2n, c2r; nothing of c01 is written -- and k_k2n; coeff: (c0, 0) into B.e for the BFV tail, and
+    // k_k2n on the coefficients of c1.  op 0 of the chunk is ciphertext `off` of `in`.
+    void hoist_digit_lift(const KernelEnv &env, int L, u64 nc, u64 off, const u64 *in, const KsBuffers &B, bool coeff, const uint32_t *ident)
+    {
+        const size_t LN = (size_t)L * P.N;
+        ++hoist_.digit_lifts;
+        if (coeff) {
+            const u64 *a = in + off * 2 * LN;
+            launch_hoist_addend_coeff(env, L, nc, a, B.e);
+            launch_k2(env, L, nc, B, a + LN, 2 * LN);
+            return;
+        }
+        K1Operands k1;
+        k1.mode = K1_GALOIS; k1.a = in; k1.op_offset = off; k1.perm = ident;
+        k1.no_c1 = k1.no_c0n = true;
+        launch_k1(env, L, nc, k1, B);
+        launch_k2(env, L, nc, B);
     }
     // Hoisted rotations: out block r = sigma_g(c0 + u0, u1) of every input under element pl.elts[r], (u0, u1) the key switch of the input's
     // c1 itself under hoist_key(g) -- the digit lift (the inverse row pass and k_k2n, or k_k2n on the coefficients) runs ONCE per chunk and
@@ -927,59 +979,33 @@ public:
     void rotate_hoisted(const HoistPlan &pl, int L, bool ntt_form, u64 n, const u64 *in, const u64 *plain, u64 *out)
     {
         use();
-        for (uint32_t e : pl.elts)
-            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
         const bool coeff = P.scheme == kSchemeBFV && !ntt_form;
+        const HoistSetup hs = hoist_setup(pl, coeff, true);
         const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
         const int SP = (int)P.K - 1;
-        std::vector<const uint32_t *> table(n_elts);
-        std::vector<const u64 *> key(n_elts, nullptr);
-        for (size_t r = 0; r < n_elts; ++r) {
-            const uint32_t e = pl.elts[r];
-            table[r] = coeff ? gather(e) : perm(e);
-            if (e != 1) key[r] = hoist_key(e);
-        }
-        const uint32_t *ident = pl.keyed && !coeff ? perm(1) : nullptr;
         for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
             const KernelEnv env = batch_env(0, !coeff);
             const KsBuffers &B = S.ks; // (c01: the arena's [nc][2][L][N], every element's sums before the permutation)
             const u64 *a = in + off * 2 * LN;
-            if (pl.keyed) {
-                ++hoist_.digit_lifts;
-                if (coeff) {
-                    launch_hoist_addend_coeff(env, L, nc, a, B.e);
-                    launch_k2(env, L, nc, B, a + LN, 2 * LN);
-                } else { // c1 as it lies (the identity's permutation) through the inverse row pass: c2n, c2r; nothing of c01 is written
-                    launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, Indexer{}, ident, B, nullptr, false, true, nullptr, true);
-                    launch_k2(env, L, nc, B);
-                }
-            }
+            if (pl.keyed) hoist_digit_lift(env, L, nc, off, in, B, coeff, hs.ident);
             for (size_t r = 0; r < n_elts; ++r) {
                 u64 *o = plain ? out + off * 2 * LN : out + ((u64)r * n + off) * 2 * LN;
                 const u64 *pt = plain ? plain + r * LN : nullptr;
-                if (!key[r]) { // the identity
-                    if (pt) launch_hoist_finish_ntt(env, L, nc, nullptr, a, table[r], o, pt, r == 0);
+                if (!hs.key[r]) { // the identity
+                    if (pt) launch_hoist_finish_ntt(env, L, nc, nullptr, a, hs.table[r], o, pt, r == 0);
                     else HIPCHECK(hipMemcpyAsync(o, a, nc * 2 * LN * 8, hipMemcpyDeviceToDevice, env.stream));
                     continue;
                 }
                 ++hoist_.key_products;
                 ++hoist_.mod_downs; // (every element pays its own)
-                launch_k3(env, L, nc, B, key[r]);
+                launch_k3(env, L, nc, B, hs.key[r]);
                 if (coeff) {
                     launch_bfv_tail_sp(env, nc * 2, B.tpr, S.rlr);
                     launch_bfv_tail_fin(env, L, nc, B.t, S.rlr, B.c01, B.c01_item_stride, B.e, 2 * LN);
-                    launch_hoist_finish_coeff(env, L, nc, B.c01, table[r], o);
+                    launch_hoist_finish_coeff(env, L, nc, B.c01, hs.table[r], o);
                 } else {
-                    launch_floor_cols(env, SP, L, nc * 2, B.tpr, B.e);
-                    FloorRowsArgs fr;
-                    fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
-                    fr.cols = B.e;
-                    fr.tsrc = B.t; fr.tsrc_op_stride = 2 * LN; fr.tsrc_poly_stride = LN;
-                    fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
-                    fr.out = B.c01; fr.out_op_stride = B.c01_item_stride; fr.out_poly_stride = LN;
-                    fr.tail_prime = -1; fr.tail = nullptr;
-                    launch_floor_rows(env, nc, fr);
-                    launch_hoist_finish_ntt(env, L, nc, B.c01, a, table[r], o, pt, r == 0);
+                    floor_step(env, SP, L, 2, nc, B.tpr, B.e, {B.t, 2 * LN, LN}, {}, {B.c01, B.c01_item_stride, LN});
+                    launch_hoist_finish_ntt(env, L, nc, B.c01, a, hs.table[r], o, pt, r == 0);
                 }
             }
         });
@@ -994,36 +1020,24 @@ public:
     void rotate_hoisted_lazy(const HoistPlan &pl, int L, u64 n, const u64 *in, const u64 *plain_qp, u64 *out)
     {
         use();
-        for (uint32_t e : pl.elts)
-            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
+        const HoistSetup hs = hoist_setup(pl, false, false);
         const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
         const int SP = (int)P.K - 1;
-        std::vector<const uint32_t *> table(n_elts, nullptr);
-        std::vector<const u64 *> key(n_elts, nullptr);
-        for (size_t r = 0; r < n_elts; ++r) {
-            const uint32_t e = pl.elts[r];
-            if (e != 1) { table[r] = perm(e); key[r] = hoist_key(e); }
-        }
-        const uint32_t *ident = pl.keyed ? perm(1) : nullptr;
         for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
             const KernelEnv env = batch_env(0, true);
             const KsBuffers &B = S.ks;
             const u64 *a = in + off * 2 * LN;
             u64 *o = out + off * 2 * LN;
-            if (pl.keyed) {
-                ++hoist_.digit_lifts;
-                launch_k1(env, L, K1_GALOIS, nc, off, in, nullptr, Indexer{}, ident, B, nullptr, false, true, nullptr, true);
-                launch_k2(env, L, nc, B);
-            }
+            if (pl.keyed) hoist_digit_lift(env, L, nc, off, in, B, false, hs.ident);
             bool first_a = true, first_b = true;
             for (size_t r = 0; r < n_elts; ++r) {
                 const u64 *pt = plain_qp + r * (LN + N);
-                if (!key[r]) {
+                if (!hs.key[r]) {
                     launch_hoist_acc_qp(env, L, nc, nullptr, nullptr, a, nullptr, pt, nullptr, 0, nullptr, o, false, first_b);
                 } else {
                     ++hoist_.key_products;
-                    launch_k3(env, L, nc, B, key[r]);
-                    launch_hoist_acc_qp(env, L, nc, B.t, B.tpr, a, table[r], pt, B.c01, B.c01_item_stride, B.tp, o, first_a, first_b);
+                    launch_k3(env, L, nc, B, hs.key[r]);
+                    launch_hoist_acc_qp(env, L, nc, B.t, B.tpr, a, hs.table[r], pt, B.c01, B.c01_item_stride, B.tp, o, first_a, first_b);
                     first_a = false;
                 }
                 first_b = false;
@@ -1033,15 +1047,7 @@ public:
             PolyView pv = poly_view(B.tp, 1, N, 1);
             pv.prime_of[0] = (unsigned char)SP;
             launch_rows_inv(env, pv, (u32)(nc * 2));
-            launch_floor_cols(env, SP, L, nc * 2, B.tp, B.e);
-            FloorRowsArgs fr;
-            fr.src_prime = SP; fr.n_tgt = L; fr.n_src = 2;
-            fr.cols = B.e;
-            fr.tsrc = B.c01; fr.tsrc_op_stride = B.c01_item_stride; fr.tsrc_poly_stride = LN;
-            fr.addend = o; fr.add_op_stride = 2 * LN; fr.add_poly_stride = LN;
-            fr.out = o; fr.out_op_stride = 2 * LN; fr.out_poly_stride = LN;
-            fr.tail_prime = -1; fr.tail = nullptr;
-            launch_floor_rows(env, nc, fr);
+            floor_step(env, SP, L, 2, nc, B.tp, B.e, {B.c01, B.c01_item_stride, LN}, {o, 2 * LN, LN}, {o, 2 * LN, LN});
         });
         HIPCHECK(hipGetLastError());
     }
@@ -1181,120 +1187,42 @@ public:
         src.table = src.coeff ? gather(elt) : perm(elt);
         key_switch_batch(L, n, src, false, out, false);
     }
-    // Evaluator::rotate_internal: use the key of the step if present, otherwise the NAF decomposition
+    // the rotation plans of rotation_plan.h over the Galois keys this context holds: every refusal over a step and its keys is made there
+    std::vector<int> rotation_terms(int step) const
+    {
+        return he355::rotation_terms(P, step, [this](uint32_t e) { return galois_key(e) != nullptr; });
+    }
+    RotTrie rotation_trie(const int *steps, u64 n_steps) const
+    {
+        return he355::rotation_trie(P, steps, n_steps, [this](uint32_t e) { return galois_key(e) != nullptr; });
+    }
+    // Evaluator::rotate_internal: the key of the step if present, otherwise its NAF terms one after the other (rotation_terms)
     void rotate(int L, u64 n, const u64 *in, int step, u64 *out, const u64 *addend = nullptr, bool ntt_form = false)
     {
         use();
         const size_t bytes = n * 2 * (size_t)L * P.N * 8;
-        auto plain_copy = [&]() { // no rotation left: out = in (+ addend)
+        const std::vector<int> terms = rotation_terms(step); // (a missing key of ANY term is refused here: nothing is launched or reserved yet)
+        const size_t m = terms.size();
+        if (!m) { // no rotation: out = in (+ addend)
             if (addend) {
                 Indexer ixp{};
                 ixp.pairwise = 1;
                 addsub(L, 2, n, in, addend, ixp, out, false);
             } else if (in != out) HIPCHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, stream_));
-        };
-        if (step == 0) { plain_copy(); return; }
-        const uint32_t elt = P.galois_elt_from_step(step);
-        if (!elt) throw std::invalid_argument("step count too large");
-        if (galois_key(elt)) { apply_galois(L, n, in, elt, out, addend, ntt_form); return; }
-        std::vector<int> naf;
-        {
-            const bool neg = step < 0;
-            long v = neg ? -(long)step : step;
-            for (int i = 0; v; ++i) {
-                const int zi = (v & 1) ? 2 - (int)(v & 3) : 0;
-                v = (v - zi) >> 1;
-                if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
-            }
+            return;
         }
-        if (naf.size() == 1) throw std::invalid_argument("Galois key not present");
-        if (ranges_overlap(in, bytes / 8, out, bytes / 8)) throw std::invalid_argument("rotate cannot run in place: `out` overlaps `in`");
-        std::vector<int> steps;
-        for (int s : naf)
-            if ((size_t)(s < 0 ? -s : s) != P.N / 2) steps.push_back(s); // a term of N/2 is no rotation
-        if (steps.empty()) { plain_copy(); return; }
-        if (addend == out && steps.size() > 1) throw std::invalid_argument("rotate_add through several Galois steps cannot add in place");
-        u64 *rot_tmp = steps.size() > 1 ? reserve(arena_[kRotTmp], bytes) : nullptr;
+        if (terms[0] != step) { // NAF terms (a step with a key of its own is apply_galois itself, refusals included)
+            if (ranges_overlap(in, bytes / 8, out, bytes / 8)) throw std::invalid_argument("rotate cannot run in place: `out` overlaps `in`");
+            if (addend == out && m > 1) throw std::invalid_argument("rotate_add through several Galois steps cannot add in place");
+        }
+        u64 *rot_tmp = m > 1 ? reserve(arena_[kRotTmp], bytes) : nullptr;
         // ping-pong between out and the temporary so that the last rotation lands in out
         const u64 *cur = in;
-        const size_t m = steps.size();
         for (size_t t = 0; t < m; ++t) {
             u64 *dst = ((m - 1 - t) % 2 == 0) ? out : rot_tmp;
-            const uint32_t e = P.galois_elt_from_step(steps[t]);
-            if (!e || !galois_key(e)) throw std::invalid_argument("Galois key not present");
-            apply_galois(L, n, cur, e, dst, t + 1 == m ? addend : nullptr, ntt_form); // the addend joins the last step only
+            apply_galois(L, n, cur, P.galois_elt_from_step(terms[t]), dst, t + 1 == m ? addend : nullptr, ntt_form); // the addend joins the last step only
             cur = dst;
         }
-    }
-    // NAF terms of a rotation step in the order Evaluator::rotate_internal applies them (least significant first; a term of
-    // N/2 is no rotation); a step with its own Galois key is one term
-    std::vector<int> rotation_terms(int step)
-    {
-        std::vector<int> terms;
-        if (step == 0) return terms;
-        const uint32_t elt = P.galois_elt_from_step(step);
-        if (!elt) throw std::invalid_argument("step count too large");
-        if (galois_key(elt)) { terms.push_back(step); return terms; }
-        const bool neg = step < 0;
-        long v = neg ? -(long)step : step;
-        int n_naf = 0;
-        for (int i = 0; v; ++i) {
-            const int zi = (v & 1) ? 2 - (int)(v & 3) : 0;
-            v = (v - zi) >> 1;
-            if (!zi) continue;
-            ++n_naf;
-            const long t = (neg ? -zi : zi) * (1L << i);
-            if ((size_t)(t < 0 ? -t : t) != P.N / 2) terms.push_back((int)t);
-        }
-        if (n_naf == 1) throw std::invalid_argument("Galois key not present");
-        for (int t : terms) {
-            const uint32_t e = P.galois_elt_from_step(t);
-            if (!e || !galois_key(e)) throw std::invalid_argument("Galois key not present");
-        }
-        return terms;
-    }
-    // out = in + sum_j rotate(in, steps[j]): the inner loop of the row-major MatMult (bfv row .cpp:519-531, ckks row .cpp:502-514:
-    // result = base; result += rotate_rows(base, j * spacers) for j = 1 .. dim2-1).  Every rotation is what Evaluator::rotate_internal
-    // computes -- the step's own Galois key if present, else its NAF terms applied least significant first -- and all of them start from
-    // the same ciphertext, so two steps whose term sequences share a prefix share that prefix's intermediate CIPHERTEXT bit for bit
-    // (same operations on the same input).  The term sequences form a trie; each node is key-switched once, from its parent's
-    // ciphertext, and added to the running sum as often as steps end there (modular additions commute, so the order of the adds is
-    // free).  For steps j * 2^k, j = 1 .. 2^m - 1, every prefix of a NAF sequence is the NAF sequence of a smaller j: 127 key
-    // switches instead of 313 for the 128-column products of BASELINE configs[4].
-    //
-    // Round 4: the trie is walked LEVEL BY LEVEL, all nodes of a level in ONE kernel sequence (grouped key switches: every node's n
-    // ciphertexts are a group with its own Galois element and key, KsGroups).  A node-by-node walk issues 127 sequences over 64
-    // ciphertexts each at configs[4] -- the small-grid regime, 7.0-7.7 us per ciphertext and key switch; a level is 13-50 nodes, i.e.
-    // 800-3200 ciphertexts per sequence: 4.8 us (tools/ks_probe.py, profiles/r04_bfv_gather_fold_negative.txt).  The walk runs in the
-    // NTT domain on the fused CKKS pipeline for BOTH schemes: a BFV ciphertext is transformed once on the way in and the sum once on the
-    // way out; in between every operation (Galois permutation, the key switch's digit lifts, key products and mod-down, modular
-    // additions) is the same exact map on residues in either representation, since the NTT is a bijection that commutes with all of
-    // them -- (t - delta) P^-1 in coefficient form and (NTT(t) - NTT(delta)) P^-1 in NTT form are the same polynomial.
-    // Returns the number of key switches issued.  Not in place.
-    struct RotNode { uint32_t elt; int parent; u64 ends; std::vector<int> kids; int level, pos; };
-    std::vector<RotNode> rotation_trie(const int *steps, u64 n_steps, size_t &depth)
-    {
-        std::vector<RotNode> trie(1, RotNode{0, -1, 0, {}, 0, 0}); // node 0: the input itself
-        depth = 0;
-        for (u64 j = 0; j < n_steps; ++j) {
-            const std::vector<int> terms = rotation_terms(steps[j]);
-            int at = 0;
-            for (int t : terms) {
-                const uint32_t te = P.galois_elt_from_step(t); // steps that differ by the row length are the same rotation, same key
-                int next = -1;
-                for (int k : trie[(size_t)at].kids)
-                    if (trie[(size_t)k].elt == te) { next = k; break; }
-                if (next < 0) {
-                    next = (int)trie.size();
-                    trie.push_back(RotNode{te, at, 0, {}, trie[(size_t)at].level + 1, 0});
-                    trie[(size_t)at].kids.push_back(next);
-                }
-                at = next;
-            }
-            ++trie[(size_t)at].ends;
-            depth = std::max(depth, terms.size());
-        }
-        return trie;
     }
     // device copy of a level's group tables: [perm pointers | key pointers | src_block | mult], grown as needed
     struct GroupTables { KsGroups g; const u32 *d_mult; };
@@ -1328,13 +1256,6 @@ public:
         t.d_mult = reinterpret_cast<const u32 *>(d_tab + G * 20);
         return t;
     }
-    // the kernel environment of the NTT-domain pipeline (a BFV context's tables are the same primes; only the data representation differs)
-    KernelEnv ntt_env() const
-    {
-        KernelEnv e = env_;
-        e.scheme = kSchemeCKKS;
-        return e;
-    }
     // NTT-form ciphertexts: out[g * gs + c] = apply_galois(in[src_block[g] * gs + c], element / key of group g), c < gs = groups.group_size,
     // g < n / gs groups.  groups.sum_out (level_sum_pays): k_k3 adds every group's ciphertext into the sum itself; chunks are then whole groups
     // (returns false where it could not: the scratch arenas hold less than one group per launch -- the caller then sums the groups itself)
@@ -1344,63 +1265,59 @@ public:
         src.a = in; src.groups = groups;
         return key_switch_batch(L, n, src, false, out, false);
     }
+    // out = in + sum_j rotate(in, steps[j]): the inner loop of the row-major MatMult (bfv row .cpp:519-531, ckks row .cpp:502-514:
+    // result = base; result += rotate_rows(base, j * spacers) for j = 1 .. dim2-1).  Every rotation is what Evaluator::rotate_internal
+    // computes -- the step's own Galois key if present, else its NAF terms applied least significant first -- and all of them start from
+    // the same ciphertext, so two steps whose term sequences share a prefix share that prefix's intermediate CIPHERTEXT bit for bit
+    // (same operations on the same input).  The term sequences form a trie; each node is key-switched once, from its parent's
+    // ciphertext, and added to the running sum as often as steps end there (modular additions commute, so the order of the adds is
+    // free).  For steps j * 2^k, j = 1 .. 2^m - 1, every prefix of a NAF sequence is the NAF sequence of a smaller j: 127 key
+    // switches instead of 313 for the 128-column products of BASELINE configs[4].
+    //
+    // Round 4: the trie is walked LEVEL BY LEVEL, all nodes of a level in ONE kernel sequence (grouped key switches: every node's n
+    // ciphertexts are a group with its own Galois element and key, KsGroups).  A node-by-node walk issues 127 sequences over 64
+    // ciphertexts each at configs[4] -- the small-grid regime, 7.0-7.7 us per ciphertext and key switch; a level is 13-50 nodes, i.e.
+    // 800-3200 ciphertexts per sequence: 4.8 us (tools/ks_probe.py, profiles/r04_bfv_gather_fold_negative.txt).  The walk runs in the
+    // NTT domain on the fused CKKS pipeline for BOTH schemes: a BFV ciphertext is transformed once on the way in and the sum once on the
+    // way out; in between every operation (Galois permutation, the key switch's digit lifts, key products and mod-down, modular
+    // additions) is the same exact map on residues in either representation, since the NTT is a bijection that commutes with all of
+    // them -- (t - delta) P^-1 in coefficient form and (NTT(t) - NTT(delta)) P^-1 in NTT form are the same polynomial.
+    // Returns the number of key switches issued.  Not in place.
     u64 rotate_sum(int L, u64 n, const u64 *in, const int *steps, u64 n_steps, u64 *out)
     {
         use();
         check_level(L);
         const size_t per = 2 * (size_t)L * P.N, bytes = n * per * 8;
         if (ranges_overlap(in, n * per, out, n * per)) throw std::invalid_argument("rotate_sum cannot run in place: `out` overlaps `in`");
-        size_t depth = 0;
-        std::vector<RotNode> trie = rotation_trie(steps, n_steps, depth);
+        const RotTrie tr = rotation_trie(steps, n_steps); // (every node's key is there: a missing one is refused before anything is allocated)
+        const std::vector<RotNode> &trie = tr.nodes;
         if (!n) return 0;
-        const bool bfs_on = level_walk_;
-        const KernelEnv nenv = ntt_env();
-        // levels of the trie; a node's position inside its level is its group index
-        std::vector<std::vector<int>> levels(depth + 1);
-        size_t widest = 0;
-        for (size_t id = 0; id < trie.size(); ++id) {
-            trie[id].pos = (int)levels[(size_t)trie[id].level].size();
-            levels[(size_t)trie[id].level].push_back((int)id);
-            widest = std::max(widest, levels[(size_t)trie[id].level].size());
-        }
+        const KernelEnv nenv = batch_env(0, true);
         // node by node where that is the better shape: no fused path; CKKS batches so small that even the widest level stays within the
         // latency shape (digit-split k_k3: he355_set_latency_max) -- a BFV context has no latency shape, its levels always go grouped
-        if (!bfs_on || trie.size() == 1 || !k3_can_fuse(nenv) || latency_shape(env_, n * widest) || n > 0xFFFFFFFFull / trie.size())
-            return rotate_sum_by_node(L, n, in, trie, depth, out);
+        if (!level_walk_ || trie.size() == 1 || !k3_can_fuse(nenv) || latency_shape(env_, n * tr.widest) || n > 0xFFFFFFFFull / trie.size())
+            return rotate_sum_by_node(L, n, in, tr, out);
         require_keyswitch();
         const bool bfv = P.scheme == kSchemeBFV;
-        PolyView pv{};
-        pv.polys_per_item = 2 * L; pv.item_stride = per;
-        for (int p2 = 0; p2 < 2 * L; ++p2) pv.prime_of[p2] = (unsigned char)(p2 % L);
-        // every level's keys before anything is allocated: a missing key must not leave blocks behind
-        for (size_t lv = 1; lv <= depth; ++lv)
-            for (int id : levels[lv])
-                if (!galois_key(trie[(size_t)id].elt)) throw std::invalid_argument("Galois key not present");
-        // the one block this walk holds at a time (the previous level's ciphertexts): back to the pool however the walk ends
-        struct Held {
-            DevicePool &pool;
-            u64 *p = nullptr;
-            ~Held() { if (p) pool.release(p); }
-            void reset(u64 *q) { if (p) pool.release(p); p = q; } // (stream-ordered reuse: whatever takes the block next is queued behind these kernels)
-        } held{pool_};
+        // the one block this walk holds at a time (the previous level's ciphertexts): back to the pool however the walk ends (stream-ordered
+        // reuse: whatever takes the block next is queued behind these kernels)
+        PoolBlock held;
         // level 0: the input in NTT form (BFV: a transformed copy), the running sum starts as (1 + steps of 0) x input
         const u64 *src = in;
         if (bfv) {
-            held.reset(static_cast<u64 *>(pool_.alloc(bytes)));
-            HIPCHECK(hipMemcpyAsync(held.p, in, bytes, hipMemcpyDeviceToDevice, stream_));
-            pv.base = held.p;
-            launch_ntt_forward(env_, pv, (u32)n);
-            src = held.p;
+            held = PoolBlock(pool_, bytes);
+            HIPCHECK(hipMemcpyAsync(held.get(), in, bytes, hipMemcpyDeviceToDevice, stream_));
+            launch_ntt_forward(env_, poly_view(held.get(), 2 * L, P.N, L), (u32)n);
+            src = held.get();
         }
         HIPCHECK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, stream_));
         Indexer ixp{};
         ixp.pairwise = 1;
         for (u64 r = 0; r < trie[0].ends; ++r) addsub(L, 2, n, out, src, ixp, out, false);
         u64 switches = 0;
-        for (size_t lv = 1; lv <= depth; ++lv) {
-            const std::vector<int> &nodes = levels[lv];
+        for (size_t lv = 1; lv <= tr.depth(); ++lv) {
+            const std::vector<int> &nodes = tr.levels[lv];
             const size_t G = nodes.size();
-            if (!G) break;
             std::vector<const uint32_t *> perms(G);
             std::vector<const u64 *> keys(G);
             std::vector<u32> src_block(G), mult(G);
@@ -1417,27 +1334,23 @@ public:
                 if (in_k3 && !nd.kids.empty()) mult[g] |= kGroupKeepBit;
             }
             GroupTables gt = upload_groups(perms, keys, src_block, mult, (u32)n);
-            Held cur{pool_};
-            cur.reset(static_cast<u64 *>(pool_.alloc(G * bytes)));
+            PoolBlock cur(pool_, G * bytes); // (taken while the previous level's block is still held ...)
             if (in_k3) { gt.g.sum_out = out; gt.g.count = gt.d_mult; }
-            if (apply_galois_grouped(L, G * n, src, gt.g, cur.p)) ++paths_.level_sums_in_k3;
-            else { ++paths_.level_sums_by_kernel; launch_sum_groups(env_, L, n, (u32)G, cur.p, gt.d_mult, out); }
-            held.reset(cur.p);
-            cur.p = nullptr;
-            src = held.p;
+            if (apply_galois_grouped(L, G * n, src, gt.g, cur.get())) ++paths_.level_sums_in_k3;
+            else { ++paths_.level_sums_by_kernel; launch_sum_groups(env_, L, n, (u32)G, cur.get(), gt.d_mult, out); }
+            held = std::move(cur); // (... which leaves with `cur` at the end of this round, before the next level takes its own)
+            src = held.get();
             switches += G;
         }
-        held.reset(nullptr);
-        if (bfv) {
-            pv.base = out;
-            launch_ntt_inverse(env_, pv, (u32)n);
-        }
+        held = PoolBlock();
+        if (bfv) launch_ntt_inverse(env_, poly_view(out, 2 * L, P.N, L), (u32)n);
         HIPCHECK(hipGetLastError());
         return switches;
     }
     // the node-by-node walk (depth first, one key-switch sequence per node): the latency shape, the unfused sequence
-    u64 rotate_sum_by_node(int L, u64 n, const u64 *in, const std::vector<RotNode> &trie, size_t depth, u64 *out)
+    u64 rotate_sum_by_node(int L, u64 n, const u64 *in, const RotTrie &tr, u64 *out)
     {
+        const std::vector<RotNode> &trie = tr.nodes;
         const size_t per = 2 * (size_t)L * P.N, bytes = n * per * 8;
         HIPCHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, stream_));
         Indexer ixp{};
@@ -1447,8 +1360,7 @@ public:
         require_keyswitch();
         // one ciphertext slab per trie level (a node's ciphertext lives until its last child is done; a leaf needs one only when
         // several steps end there)
-        const size_t levels = depth;
-        u64 *rot_tmp = reserve(arena_[kRotTmp], levels * bytes);
+        u64 *rot_tmp = reserve(arena_[kRotTmp], tr.depth() * bytes);
         u64 switches = 0;
         // depth-first: (node, level of the node = number of terms applied)
         std::vector<std::pair<int, size_t>> stack;
@@ -1544,47 +1456,34 @@ public:
             zero_index_ += n;
             return;
         }
-        if (P.scheme == kSchemeBFV) { // SEALContextWrapper::accumulateBFV (seal_context.cpp:289-319)
-            const u64 half = P.N / 2;
-            const u64 row_count = count > half ? half : count;
-            int rot = 64 - __builtin_clzll(row_count);
-            if (((u64)1 << (rot - 1)) == row_count) --rot;
-            // The chain of rotate_rows + add_inplace (and the column swap) runs in the NTT domain on the fused pipeline the CKKS path uses
-            // (Galois permutation in k_k1, mod-down inside k_k3, the latency shape for small batches): the ciphertexts are transformed
-            // once on the way in and once on the way out, every step in between is the same exact map on residues in either
-            // representation (see rotate_sum).  Two or more steps pay for the two transforms (20 transforms per key switch at L = 3).
-            // Measured through the bridge (profiles/r04_bridge_phases.jsonl): it wins where the fused pipeline has a shape of its own -- the
-            // latency shape (1 ciphertext at N = 2^14: 2.02 -> 1.59 ms) -- and in the throughput regime (1024 ciphertexts at N = 2^14:
-            // 44.1 -> 38.9 ms); in between (64-80 ciphertexts at N <= 2^14) the BFV kernels' launches fill the chip better: 1.47 -> 1.77 ms.
-            const int n_steps = rot + (count > half ? 1 : 0);
-            const bool ntt_chain = level_walk_ && n_steps >= 2 && k3_can_fuse(ntt_env()) && (latency_shape(ntt_env(), n) || n * P.N >= ((u64)1 << 23));
-            PolyView pv{};
-            pv.base = inout; pv.polys_per_item = 2 * L; pv.item_stride = 2 * (u64)L * P.N;
-            for (int p2 = 0; p2 < 2 * L; ++p2) pv.prime_of[p2] = (unsigned char)(p2 % L);
-            if (ntt_chain) launch_ntt_forward(env_, pv, (u32)n);
-            u64 *cur = inout, *nxt = tmp; // ping-pong: nxt = cur + rotate(cur), one pipeline per step and no separate add
-            for (int i = 0; i < rot; ++i) {
-                rotate(L, n, cur, 1 << i, nxt, cur, ntt_chain); // rotate_rows + add_inplace
-                std::swap(cur, nxt);
-            }
-            if (count > half) {
-                apply_galois(L, n, cur, (uint32_t)(2 * P.N - 1), nxt, cur, ntt_chain); // rotate_columns + add_inplace
-                std::swap(cur, nxt);
-            }
-            if (cur != inout) HIPCHECK(hipMemcpyAsync(inout, cur, n * 2 * (size_t)L * P.N * 8, hipMemcpyDeviceToDevice, stream_));
-            if (ntt_chain) launch_ntt_inverse(env_, pv, (u32)n);
-            return;
+        // One ladder for both schemes: rotate by 1, 2, 4, .. and add, over the slots of a CKKS ciphertext (rotate_vector) or of one batching row
+        // of a BFV one (rotate_rows); accumulateBFV (seal_context.cpp:289-319) then swaps the columns when the count reaches past a row.
+        const bool bfv = P.scheme == kSchemeBFV;
+        const u64 half = P.N / 2, row_count = std::min(count, half);
+        const bool columns = bfv && count > half;
+        int rot = 64 - __builtin_clzll(row_count);
+        if (((u64)1 << (rot - 1)) == row_count) --rot;
+        // BFV: the chain of rotate_rows + add_inplace (and the column swap) runs in the NTT domain on the fused pipeline the CKKS path uses
+        // (Galois permutation in k_k1, mod-down inside k_k3, the latency shape for small batches): the ciphertexts are transformed
+        // once on the way in and once on the way out, every step in between is the same exact map on residues in either
+        // representation (see rotate_sum).  Two or more steps pay for the two transforms (20 transforms per key switch at L = 3).
+        // Measured through the bridge (profiles/r04_bridge_phases.jsonl): it wins where the fused pipeline has a shape of its own -- the
+        // latency shape (1 ciphertext at N = 2^14: 2.02 -> 1.59 ms) -- and in the throughput regime (1024 ciphertexts at N = 2^14:
+        // 44.1 -> 38.9 ms); in between (64-80 ciphertexts at N <= 2^14) the BFV kernels' launches fill the chip better: 1.47 -> 1.77 ms.
+        const KernelEnv nenv = batch_env(0, true);
+        const bool ntt_chain = bfv && level_walk_ && rot + (columns ? 1 : 0) >= 2 && k3_can_fuse(nenv) && (latency_shape(nenv, n) || n * P.N >= ((u64)1 << 23));
+        if (ntt_chain) launch_ntt_forward(env_, poly_view(inout, 2 * L, P.N, L), (u32)n);
+        u64 *cur = inout, *nxt = tmp; // ping-pong: nxt = cur + rotate(cur), one pipeline per step and no separate add
+        for (int i = 0; i < rot; ++i) {
+            rotate(L, n, cur, 1 << i, nxt, cur, ntt_chain); // rotate_vector / rotate_rows + add_inplace
+            std::swap(cur, nxt);
         }
-        const u64 slots = P.N / 2;
-        if (count > slots) count = slots;
-        int rotations = 64 - __builtin_clzll(count);
-        if (((u64)1 << (rotations - 1)) == count) --rotations;
-        u64 *cur = inout, *nxt = tmp;
-        for (int i = 0; i < rotations; ++i) {
-            rotate(L, n, cur, 1 << i, nxt, cur); // rotate_vector + add_inplace in one pipeline
+        if (columns) {
+            apply_galois(L, n, cur, (uint32_t)(2 * P.N - 1), nxt, cur, ntt_chain); // rotate_columns + add_inplace
             std::swap(cur, nxt);
         }
         if (cur != inout) HIPCHECK(hipMemcpyAsync(inout, cur, n * 2 * (size_t)L * P.N * 8, hipMemcpyDeviceToDevice, stream_));
+        if (ntt_chain) launch_ntt_inverse(env_, poly_view(inout, 2 * L, P.N, L), (u32)n);
     }
 
     // ---- BFV ------------------------------------------------------------------------------------------
@@ -1802,15 +1701,7 @@ public:
                 if (K > 1) {
                     const int SP = (int)K - 1;
                     launch_rows_inv_select(env_, SP, c * 2, e + (size_t)SP * N, (u64)K * N, tpr);
-                    launch_floor_cols(env_, SP, (int)L, c * 2, tpr, cols);
-                    FloorRowsArgs fr;
-                    fr.src_prime = SP; fr.n_tgt = (int)L; fr.n_src = 2;
-                    fr.cols = cols;
-                    fr.tsrc = e; fr.tsrc_op_stride = 2 * K * N; fr.tsrc_poly_stride = K * N;
-                    fr.addend = nullptr; fr.add_op_stride = 0; fr.add_poly_stride = 0;
-                    fr.out = o; fr.out_op_stride = 2 * L * N; fr.out_poly_stride = L * N;
-                    fr.tail_prime = -1; fr.tail = nullptr;
-                    launch_floor_rows(env_, c, fr);
+                    floor_step(env_, SP, (int)L, 2, c, tpr, cols, {e, 2 * K * N, K * N}, {}, {o, 2 * L * N, L * N});
                 } else {
                     HIPCHECK(hipMemcpyAsync(o, e, c * 2 * N * 8, hipMemcpyDeviceToDevice, stream_));
                 }

@@ -80,6 +80,22 @@ struct KsGroups {
 constexpr u32 kGroupKeepBit = 0x80000000u;
 constexpr int kMoveListCap = 64;
 enum K1Mode { K1_MUL = 0, K1_CT3 = 1, K1_GALOIS = 2 };
+// What launch_k1 reads and which of c01's rows it leaves to the fused k_k3 (the launcher's view; the kernels' own argument block is built from it)
+struct K1Operands {
+    K1Mode mode = K1_MUL;
+    // MUL: a, b [.][2][L][N], result r = op_offset + op takes a[idx_a(ix, r)], b[idx_b(ix, r)].  CT3: a [n][3][L][N].
+    // GALOIS: a [n][2][L][N], op reads ciphertext op_offset + op
+    const u64 *a = nullptr, *b = nullptr;
+    Indexer ix{};
+    u64 op_offset = 0;
+    const uint32_t *perm = nullptr; // GALOIS: the device permutation table (NTT-form gather) of the element
+    // GALOIS, optional [n][2][L][N] (indexed like `a`): the rotated ciphertext starts from it, i.e. the pipeline computes addend + rotate(a)
+    const u64 *addend = nullptr;
+    bool no_c01 = false; // MUL only: just the key-switch target c2 = a1 b1 is produced; c0, c1 are computed where they are consumed, K3Fuse::ta
+    bool no_c1 = false;  // GALOIS, CT3: polynomial 1 of c01 -- zeros, or the addend's -- is not written; the fused k_k3 takes it from K3Fuse::c1_mode
+    bool no_c0n = false; // GALOIS with no_c1: the permuted c0 is not written either -- the fused k_k3 gathers it from the input (K3Fuse::c1_mode 4, 5)
+    const KsGroups *groups = nullptr; // GALOIS without addend: a grouped launch, per-group elements (`perm` unused)
+};
 // K3: forward row pass of every (tt, j) + multiply-accumulate with the key -> t (data primes) / tpr (special)
 // BFV (env.scheme == 1): the products of ALL primes continue into the inverse row pass (t then holds raw rows)
 // `part`: all tiles, only the special prime's, or only the data primes'.  With `fuse` (data-prime tiles, CKKS: k3_can_fuse)

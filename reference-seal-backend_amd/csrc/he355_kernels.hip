@@ -746,14 +746,6 @@ __device__ __forceinline__ void store_pattern_rows_wide(__amdgpu_buffer_rsrc_t d
         __builtin_amdgcn_raw_buffer_store_b128(vh[k], dst, (int)lane_hi, k * 8 * (int)kSlotBytes, 0);
     HE_WAVE_SYNC(); // the tile is free again for the next target
 }
-// worst-case magnitude after the forward column pass of the fp64 engine from inputs |x| < m0 (ArF64::bfly_fwd: m -> m + q (1/2 + m 2^-51))
-template <int LOGN1> __device__ __forceinline__ bool fits_48(double m0, double q)
-{
-    double m = m0;
-#pragma unroll
-    for (int st = 0; st < LOGN1; ++st) m += q * (0.5 + m * 4.440892098500626e-16); // 2^-51
-    return m * 1.0000001 < 140737488355328.0;                                        // 2^47
-}
 
 // Per-target constants come through the constant address space (scalar loads): a vector load of a PrimeDev field would put an
 // s_waitcnt vmcnt(0) -- i.e. the full HBM write latency of the previous target's stores -- in front of every target.
@@ -2091,10 +2083,13 @@ void launch_mul3(const KernelEnv &env, int L, u64 n_results, const u64 *a, const
 // close to the fp64 engine's in length; the others -- whose dual kernels are the latency shape's, behind a function boundary -- keep
 // the 1024 they were swept at.  profiles/r05_dual_threshold_sweep.txt)
 constexpr unsigned kDualMaxBlocksK3 = 4096, kDualMaxBlocks = 1024;
-void launch_k1(const KernelEnv &env, int L, K1Mode mode, u64 n_ops, u64 op_offset, const u64 *a, const u64 *b, Indexer ix, const uint32_t *perm,
-               const KsBuffers &buf, const u64 *addend, bool no_c01, bool no_c1, const KsGroups *groups, bool no_c0n)
+void launch_k1(const KernelEnv &env, int L, u64 n_ops, const K1Operands &src, const KsBuffers &buf)
 {
     if (!n_ops) return;
+    const K1Mode mode = src.mode;
+    const u64 *const addend = src.addend;
+    const KsGroups *const groups = src.groups;
+    const bool no_c01 = src.no_c01, no_c1 = src.no_c1, no_c0n = src.no_c0n;
     if (groups && (mode != K1_GALOIS || addend)) throw std::runtime_error("grouped launch: rotations without addend only");
     if (no_c01 && mode != K1_MUL) throw std::runtime_error("no_c01: the ct x ct multiply only");
     if (no_c1 && mode != K1_GALOIS && mode != K1_CT3) throw std::runtime_error("no_c1: rotations and size-3 inputs only");
@@ -2103,9 +2098,9 @@ void launch_k1(const KernelEnv &env, int L, K1Mode mode, u64 n_ops, u64 op_offse
     if (no_c0n && (mode != K1_GALOIS || !no_c1 || (addend && groups))) throw std::runtime_error("no_c0n: rotations whose polynomial 1 is left to k_k3 only");
     A.no_c0n = no_c0n ? 1 : 0;
     A.groups = groups ? *groups : KsGroups{};
-    A.a = a; A.b = b; A.ix = ix; A.perm = perm; A.addend = addend;
+    A.a = src.a; A.b = src.b; A.ix = src.ix; A.perm = src.perm; A.addend = addend;
     A.c01 = buf.c01; A.c01_item_stride = buf.c01_item_stride; A.c2n = buf.c2n; A.c2r = buf.c2r;
-    A.n_ops = n_ops; A.op_offset = op_offset; A.L = L; A.logn1 = env.logn1; A.mode = (int)mode;
+    A.n_ops = n_ops; A.op_offset = src.op_offset; A.L = L; A.logn1 = env.logn1; A.mode = (int)mode;
     K1Args AP[2];
     unsigned gp[2] = {0, 0};
     for (int pass = 0; pass < 2; ++pass) { // pass 0: fp64-engine residues, pass 1: u64-engine residues

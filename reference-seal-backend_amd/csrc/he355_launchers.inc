@@ -19,15 +19,8 @@ void launch_mul3_acc(const KernelEnv &env, int L, u64 rows, u64 cols, int inner,
 void launch_sum_groups(const KernelEnv &env, int L, u64 n_cts, u32 n_groups, const u64 *in, const u32 *d_mult, u64 *out);
 // whole ciphertexts by index list (host array): gather dst[g] = src[idx[g]], scatter dst[idx[g]] = src[g], g < n
 void launch_move_cts(const KernelEnv &env, u64 *dst, const u64 *src, const uint32_t *idx, u64 n, u64 elems_per_ct, bool scatter);
-// K1: produce c01 / c2n / c2r for a chunk of ops.  MUL: a,b via indexer.  CT3: `a` is [n][3][L][N].
-// GALOIS: `a` is [n][2][L][N], perm = device permutation table (NTT-form gather); optional addend [n][2][L][N] (indexed like `a`):
-// the rotated ciphertext starts from it, i.e. the pipeline computes addend + rotate(a).
-void launch_k1(const KernelEnv &env, int L, K1Mode mode, u64 n_ops, u64 op_offset, const u64 *a, const u64 *b, Indexer ix,
-               const uint32_t *perm, const KsBuffers &buf, const u64 *addend = nullptr, bool no_c01 = false, bool no_c1 = false,
-               const KsGroups *groups = nullptr, bool no_c0n = false);
-// (no_c01, K1_MUL only: just the key-switch target c2 = a1 b1 is produced; c0, c1 are computed where they are consumed, K3Fuse::ta.
-//  no_c0n, K1_GALOIS without addend only: the permuted c0 is not written -- the fused k_k3 gathers it from the input (K3Fuse::c1_mode 4);
-//  no_c1, K1_GALOIS only: polynomial 1 of c01 -- zeros, or the addend's -- is not written; the fused k_k3 takes it from K3Fuse::c1_mode)
+// K1: produce c01 / c2n / c2r for a chunk of n_ops ops from the operands `src` names (K1Operands, he355_kernels.h)
+void launch_k1(const KernelEnv &env, int L, u64 n_ops, const K1Operands &src, const KsBuffers &buf);
 // K2: finish iNTT of each digit, lift to every key prime, forward column pass -> d
 // src_is_coeff (BFV): `src` already holds coefficient-form digits [op][L][N] (op stride src_op_stride) and every
 // (prime, digit) pair is lifted, including the digit's own prime

@@ -12,6 +12,7 @@
 #define HE355_LANE_SIM 1 // the wide-lazy u64 butterflies report sums that leave 64 bits (modarith.h)
 #include "../../reference-seal-backend_amd/csrc/he_params.h"
 #include "../../reference-seal-backend_amd/csrc/ntt_core.h"
+#include "../../reference-seal-backend_amd/csrc/rotation_plan.h"
 
 using namespace he355;
 namespace he355 {
@@ -269,6 +270,21 @@ static double col_w_maxmag_any(const Params &P, size_t t, const u64 *col)
     default: return -1.0;
     }
 }
+// sim_rotation_*: a key set given as Galois elements, and a refusal of csrc/rotation_plan.h as a return code
+struct KeySet {
+    const uint32_t *elts;
+    size_t n;
+    bool operator()(uint32_t e) const { return std::find(elts, elts + n, e) != elts + n; }
+};
+template <class F> static long rotation_plan_call(F &&f)
+{
+    try {
+        return f();
+    } catch (const std::invalid_argument &e) {
+        const std::string w = e.what();
+        return w == "step count too large" ? -1 : w == "Galois key not present" ? -2 : -3;
+    }
+}
 extern "C" {
 int sim_logn1(void *p) { return ((Params *)p)->logn1; }
 // max |x| after the direct-path forward column pass of fp64-engine target prime t on one column of N1 digit coefficients (-1: not an
@@ -394,5 +410,32 @@ void sim_galois_perm(void *p, uint32_t elt, uint32_t *out)
 {
     auto v = ((Params *)p)->galois_perm_ntt(elt);
     std::memcpy(out, v.data(), v.size() * 4);
+}
+// csrc/rotation_plan.h over the key set `keys` (n_keys Galois elements).  A refusal is the return value: -1 "step count too large",
+// -2 "Galois key not present" (anything else: -3), and nothing is written then.
+// the terms of one step -> terms (room for `cap`); returns their number
+long sim_rotation_terms(void *p, int step, const uint32_t *keys, size_t n_keys, int *terms, size_t cap)
+{
+    return rotation_plan_call([&]() -> long {
+        const std::vector<int> t = rotation_terms(*(Params *)p, step, KeySet{keys, n_keys});
+        if (t.size() > cap) return -3;
+        std::copy(t.begin(), t.end(), terms);
+        return (long)t.size();
+    });
+}
+// the trie of n_steps steps -> per node (room for `cap`) its element, parent, ends, level and position; returns the number of nodes, node 0 included
+long sim_rotation_trie(void *p, const int *steps, size_t n_steps, const uint32_t *keys, size_t n_keys, uint32_t *elt, int *parent, uint64_t *ends, int *level,
+                       int *pos, size_t cap)
+{
+    return rotation_plan_call([&]() -> long {
+        const RotTrie tr = rotation_trie(*(Params *)p, steps, n_steps, KeySet{keys, n_keys});
+        if (tr.nodes.size() > cap) return -3;
+        for (size_t i = 0; i < tr.nodes.size(); ++i) {
+            const RotNode &nd = tr.nodes[i];
+            elt[i] = nd.elt; parent[i] = nd.parent; ends[i] = nd.ends; level[i] = nd.level; pos[i] = nd.pos;
+            if (tr.levels[(size_t)nd.level][(size_t)nd.pos] != (int)i) return -3; // (levels and positions name each other)
+        }
+        return (long)tr.nodes.size();
+    });
 }
 }

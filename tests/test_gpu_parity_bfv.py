@@ -452,3 +452,93 @@ def test_rotate_sum_level_sum_inside_the_key_switch(be, oracle, scheme):
             assert np.array_equal(got[r], want), r
     finally:
         g.close()
+
+
+SENTINEL = 0x5A5A5A5A5A5A5A5A
+
+
+def small_pair(be, oracle, scheme):
+    """N = 2048, {60, 40, 60}: the smallest ring with a column pass, one data prime on each engine"""
+    N, bits = 2048, [60, 40, 60]
+    sch_g, sch_o = (be.SCHEME_BFV, oracle.SCHEME_BFV) if scheme == "bfv" else (be.SCHEME_CKKS, oracle.SCHEME_CKKS)
+    kw = dict(plain_bits=20) if scheme == "bfv" else {}
+    return be.Context(sch_g, N, bit_sizes=bits, sec128=False, device=0, **kw), oracle.Context(sch_o, N, bit_sizes=bits, sec128=False, **kw)
+
+
+@pytest.mark.parametrize("scheme", ["ckks", "bfv"])
+def test_rotate_refuses_a_missing_term_key_before_its_first_launch(be, oracle, scheme):
+    """A rotation through several NAF terms checks the key of EVERY term before anything is launched or reserved (csrc/rotation_plan.h).
+    11 = -1 - 4 + 16, and with three terms the first lands in `out`: with the keys of -1 and -4 alone the call is refused with "Galois key
+    not present", `out` still holds its sentinel, he355_path_stats counts no key switch and he355_alloc_stats has not moved (the rotation
+    temporary was not reserved).  The same with rotate_add and an addend.  With the key of 16 installed both calls equal the oracle."""
+    g, o = small_pair(be, oracle, scheme)
+    rng = np.random.default_rng(2048)
+    L, N = g.L, g.N
+    try:
+        keys = {}
+        for s in (-1, -4):
+            keys[o.galois_elt(s)] = o.random_kswitch_key(rng)
+            g.set_galois_key(o.galois_elt(s), keys[o.galois_elt(s)])
+        a, b = rand_cts(o, rng, 3, L), rand_cts(o, rng, 3, L)
+        da, db = g.to_device(a), g.to_device(b)
+        out = g.to_device(np.full(3 * 2 * L * N, SENTINEL, dtype=np.uint64))
+        for call in (lambda: g.rotate(L, 3, da, 11, out), lambda: g.rotate_add(L, 3, da, 11, db, out)):
+            g.path_stats(reset=True)
+            before = g.alloc_stats()
+            with pytest.raises(be.HE355Error, match="Galois key not present"):
+                call()
+            assert not any(g.path_stats().values())
+            assert g.alloc_stats() == before
+            assert (out.download() == SENTINEL).all()
+            assert np.array_equal(db.download((3, 2, L, N)), b) and np.array_equal(da.download((3, 2, L, N)), a)
+        keys[o.galois_elt(16)] = o.random_kswitch_key(rng)
+        g.set_galois_key(o.galois_elt(16), keys[o.galois_elt(16)])
+        g.rotate(L, 3, da, 11, out)
+        got = out.download((3, 2, L, N))
+        for r in range(3):
+            assert np.array_equal(got[r], o.rotate(a[r], 11, keys)), r
+        g.rotate_add(L, 3, da, 11, db, out)
+        got = out.download((3, 2, L, N))
+        for r in range(3):
+            assert np.array_equal(got[r], o.add(b[r], o.rotate(a[r], 11, keys))), r
+    finally:
+        g.close()
+
+
+def test_rotate_sum_level_walk_returns_its_pool_blocks(be, oracle):
+    """he355_rotate_sum's level walk holds pool blocks while it runs (a BFV context always walks by level, and holds a transformed copy of
+    the input besides): the live bytes of he355_alloc_stats are the same before and after a call -- one that succeeds, and one refused for
+    the missing key of a level-2 node (3 = -1 + 4 without the key of 4), which also leaves `out` alone."""
+    g, o = small_pair(be, oracle, "bfv")
+    rng = np.random.default_rng(4096)
+    L, N = g.L, g.N
+    try:
+        keys = {}
+        for s in (1, 2, -1):
+            keys[o.galois_elt(s)] = o.random_kswitch_key(rng)
+            g.set_galois_key(o.galois_elt(s), keys[o.galois_elt(s)])
+        a = rand_cts(o, rng, 2, L)
+        da = g.to_device(a)
+        out = g.to_device(np.full(2 * 2 * L * N, SENTINEL, dtype=np.uint64))
+        steps = [1, 2, 3]
+        live = g.alloc_stats()["live_bytes"]
+        with pytest.raises(be.HE355Error, match="Galois key not present"):
+            g.rotate_sum(L, 2, da, steps, out)
+        assert g.alloc_stats()["live_bytes"] == live
+        assert (out.download() == SENTINEL).all()
+        keys[o.galois_elt(4)] = o.random_kswitch_key(rng)
+        g.set_galois_key(o.galois_elt(4), keys[o.galois_elt(4)])
+        live = g.alloc_stats()["live_bytes"]
+        g.path_stats(reset=True)
+        assert g.rotate_sum(L, 2, da, steps, out) == 4
+        st = g.path_stats()
+        assert st["level_sums_in_k3"] + st["level_sums_by_kernel"] == 2  # the level walk: two levels
+        assert g.alloc_stats()["live_bytes"] == live
+        got = out.download((2, 2, L, N))
+        for r in range(2):
+            want = a[r].copy()
+            for s in steps:
+                want = o.add(want, o.rotate(a[r], s, keys))
+            assert np.array_equal(got[r], want), r
+    finally:
+        g.close()
