@@ -672,6 +672,36 @@ int he355_rotate_hoisted_plain_sum_lazy(he355_ctx *ctx, int L, uint64_t n, const
  * of (coefficient, prime i >= 1) pairs whose residue is not c mod q_i -- 0: every prime agrees with prime 0; always 0 when L = 1; null skips
  * the check and its transforms.  Needs a special prime (K >= 2); the two slabs may not overlap; n == 0 touches nothing. */
 int he355_plain_extend_special(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain_ntt, uint64_t *d_plain_qp, uint64_t *d_mismatch);
+/* The baby-step/giant-step linear transform on the hoisted rotations: for R = n_baby * n_giant diagonals about n_baby + n_giant key products
+ * and Galois keys instead of R - 1.
+ *   out[c] = sum_j rot_{G_j}( sum_i plain[j][i] (.) rot_{b_i}(in[c]) ),   b = h_baby, G = h_giant (steps; 0 = the identity)
+ * NTT-form ciphertexts only (CKKS; BFV as from he355_bfv_transform_to_ntt), d_in and d_out [n][2][L][N], no rescale.  d_plain_qp
+ * [n_giant][n_baby][L + 1][N] in the layout of he355_plain_extend_special, shared by the batch.  The caller supplies the plaintexts already
+ * PRE-ROTATED, plain[j][i] = rot_{-G_j}(diag_{G_j + b_i}): rot_G(p (.) x) = rot_G(p) (.) rot_G(x), so the outer rotation turns them back into
+ * the diagonals.  h_mask [n_giant][n_baby] bytes, may be null (every term): a zero byte means the term is absent.  A step is USED when a
+ * term that is not masked names it; every used non-zero step needs its OWN Galois key (no NAF fallback), a step that is not used needs none.
+ * The definition (all residues canonical; i over the L data primes and P, tile L = P; sigma_g the NTT-domain permutation; key'_g, the
+ * digits and the key product S without a mod-down as for he355_rotate_hoisted_plain_sum_lazy; mod_down that call's last line with B = 0):
+ *   1. baby terms, per ciphertext (the digits of c1 lifted once):
+ *        keyed i, element g:  T_i[k][i'] = sigma_g(S_i[k][i']),  and  T_i[0][i'] += P sigma_g(c0[i'])  on the data primes
+ *        identity:            T_i = (P c0, P c1) on the data primes, 0 under P
+ *   2. inner sum, per used row j:  E_j[k][i'] = sum_{i used} T_i[k][i'] (.) plain[j][i][i']            (L + 1 primes)
+ *   3. giant step:  identity row: Acc += E_j in Q P (no mod-down);
+ *                   keyed row, element h: e_j = mod_down(E_j) (a size-2 ciphertext in Q); S'_j = the key product of the digits of e_j[1]
+ *                   under key'_h;  Acc[k] += sigma_h(S'_j[k]),  Acc[0] += P sigma_h(e_j[0]) on the data primes
+ *   4. out = mod_down(Acc)
+ * Two exact facts let an implementation choose its buffers without changing a bit: mod_down(A + P B) = B + mod_down(A), because rho depends
+ * on the P-residue alone -- so c0 may be folded in as P c0 (here) or kept in a Q-side accumulator (the lazy call); and mod_down(P X) = X
+ * (rho = h, delta = 0), so a mod-down whose input has no key product in it may be skipped or run: the bits are the same.
+ * Refused on the host before any device work; n == 0, n_baby == 0 or n_giant == 0 touches nothing and returns success.  d_out may overlap
+ * neither d_in nor any word of d_plain_qp.  The call takes its baby store and two Q P blocks from the context's pool before its first
+ * launch (the allocator's error if they do not fit); he355_linear_transform_bsgs_scratch_bytes is an upper bound of that at the context's
+ * batch chunk: (n_baby + 2) blocks of min(chunk, n) [2][L + 1][N] ciphertexts, each rounded up by a size class of the pool; saturated at
+ * 2^64 - 1; 0 for a level out of range, for nothing to do and for more than 2^20 baby steps (the call refuses them).  The table of used
+ * terms lies in the context's own table ring, which is never rewritten under a queued launch: calls may follow each other without a sync. */
+int he355_linear_transform_bsgs(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in, const int32_t *h_baby, uint64_t n_baby, const int32_t *h_giant,
+                                uint64_t n_giant, const uint64_t *d_plain_qp, const uint8_t *h_mask, uint64_t *d_out);
+uint64_t he355_linear_transform_bsgs_scratch_bytes(const he355_ctx *ctx, int L, uint64_t n, uint64_t n_baby);
 /* What the hoisted calls of this context did since he355_device_init (or the last call with reset != 0); they count in no field of
  * he355_path_stats_t. */
 typedef struct he355_hoist_stats {
@@ -680,8 +710,11 @@ typedef struct he355_hoist_stats {
     uint64_t keys_permuted; /* permuted key copies built (first use, and again after the element's key was installed again)     */
     uint64_t key_bytes;     /* device bytes the permuted copies hold now (a level: kept across reset)                            */
     uint64_t mod_downs;     /* mod-downs: one per key product for the eager calls, one per chunk with a non-identity element for
-                             * he355_rotate_hoisted_plain_sum_lazy                                                                 */
-    uint64_t reserved[3];
+                             * he355_rotate_hoisted_plain_sum_lazy, one per (chunk, used keyed giant row) and one per chunk for
+                             * he355_linear_transform_bsgs (its digit_lifts: one per chunk with a used keyed baby and one per used
+                             * keyed giant row; its key_products: used keyed babies + used keyed giant rows, per chunk)             */
+    uint64_t inner_sums;    /* he355_linear_transform_bsgs: inner sums, one per (chunk, used giant row)                               */
+    uint64_t reserved[2];
 } he355_hoist_stats_t;
 int he355_hoist_stats(he355_ctx *ctx, he355_hoist_stats_t *out, int reset);
 int he355_hoist_release_keys(he355_ctx *ctx);   /* frees the permuted copies; they are rebuilt on next use */

@@ -45,7 +45,7 @@ class PathStats(C.Structure):
 
 
 class HoistStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes", "mod_downs")] + [("reserved", C.c_uint64 * 3)]
+    _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes", "mod_downs", "inner_sums")] + [("reserved", C.c_uint64 * 2)]
 
 
 class BfvRouteStats(C.Structure):
@@ -182,6 +182,8 @@ def lib():
             "he355_rotate_hoisted_plain_sum": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, vp, vp]),
             "he355_rotate_hoisted_plain_sum_lazy": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, vp, vp]),
             "he355_plain_extend_special": (i32, [vp, i32, u64, vp, vp, vp]),
+            "he355_linear_transform_bsgs": (i32, [vp, i32, u64, vp, C.POINTER(C.c_int32), u64, C.POINTER(C.c_int32), u64, vp, C.POINTER(C.c_uint8), vp]),
+            "he355_linear_transform_bsgs_scratch_bytes": (u64, [vp, i32, u64, u64]),
             "he355_hoist_stats": (i32, [vp, C.POINTER(HoistStats), i32]),
             "he355_hoist_release_keys": (i32, [vp]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
@@ -221,7 +223,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -725,6 +727,20 @@ class Context:
         [len(steps)][L + 1][N], row L under the special prime (plain_extend_special)"""
         arr = (C.c_int32 * max(1, len(steps)))(*steps)
         _check(lib().he355_rotate_hoisted_plain_sum_lazy(self.h, L, n, inp.ptr, arr, len(steps), plain_qp.ptr, out.ptr))
+
+    def linear_transform_bsgs(self, L, n, inp, baby, giant, plain_qp, out, mask=None):
+        """out [n][2][L][N] = sum_j rot_{giant[j]}(sum_i plain_qp[j][i] (.) rot_{baby[i]}(in)): plain_qp [len(giant)][len(baby)][L + 1][N],
+        pre-rotated by -giant[j]; mask (optional): len(giant) x len(baby) flags, a zero drops the term"""
+        b, g = (C.c_int32 * max(1, len(baby)))(*baby), (C.c_int32 * max(1, len(giant)))(*giant)
+        m = None
+        if mask is not None:
+            flat = [int(bool(v)) for row in mask for v in row]
+            m = (C.c_uint8 * max(1, len(flat)))(*flat)
+        _check(lib().he355_linear_transform_bsgs(self.h, L, n, inp.ptr, b, len(baby), g, len(giant), plain_qp.ptr, m, out.ptr))
+
+    def linear_transform_bsgs_scratch_bytes(self, L, n, n_baby) -> int:
+        """an upper bound of the pool bytes linear_transform_bsgs takes for n ciphertexts at the context's batch chunk"""
+        return int(lib().he355_linear_transform_bsgs_scratch_bytes(self.h, L, n, n_baby))
 
     def plain_extend_special(self, L, n, plain_ntt, plain_qp, mismatch=None):
         """plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N], row L under the special prime; mismatch (optional): one device word that

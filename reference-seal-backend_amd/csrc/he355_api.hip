@@ -936,20 +936,28 @@ public:
         std::vector<const u64 *> key;
         const uint32_t *ident = nullptr;
     };
-    HoistSetup hoist_setup(const HoistPlan &pl, bool coeff, bool ident_tables)
+    // (what: the call's name in front of the refusal; null: the bare message of the first hoisted calls)
+    void hoist_require_keys(const std::vector<uint32_t> &elts, const char *what = nullptr)
     {
-        for (uint32_t e : pl.elts)
-            if (e != 1 && !galois_key(e)) throw std::invalid_argument("Galois key not present");
-        const size_t n_elts = pl.elts.size();
+        for (uint32_t e : elts)
+            if (e != 1 && !galois_key(e)) throw std::invalid_argument(what ? std::string(what) + ": Galois key not present" : std::string("Galois key not present"));
+    }
+    HoistSetup hoist_setup(const std::vector<uint32_t> &elts, bool coeff, bool ident_tables, const char *what = nullptr)
+    {
+        hoist_require_keys(elts, what);
+        const size_t n_elts = elts.size();
         HoistSetup hs{std::vector<const uint32_t *>(n_elts, nullptr), std::vector<const u64 *>(n_elts, nullptr), nullptr};
+        bool keyed = false;
         for (size_t r = 0; r < n_elts; ++r) {
-            const uint32_t e = pl.elts[r];
+            const uint32_t e = elts[r];
             if (e != 1 || ident_tables) hs.table[r] = coeff ? gather(e) : perm(e);
             if (e != 1) hs.key[r] = hoist_key(e);
+            keyed |= e != 1;
         }
-        if (pl.keyed && !coeff) hs.ident = perm(1);
+        if (keyed && !coeff) hs.ident = perm(1);
         return hs;
     }
+    HoistSetup hoist_setup(const HoistPlan &pl, bool coeff, bool ident_tables) { return hoist_setup(pl.elts, coeff, ident_tables); }
     // The one digit lift of a chunk of a hoisted call, counted in he355_hoist_stats: the input's c1 as it lies (the identity's permutation)
     // through k_k1's inverse row pass -- c2n, c2r; nothing of c01 is written -- and k_k2n; coeff: (c0, 0) into B.e for the BFV tail, and
     // k_k2n on the coefficients of c1.  op 0 of the chunk is ciphertext `off` of `in`.
@@ -1048,6 +1056,109 @@ public:
             pv.prime_of[0] = (unsigned char)SP;
             launch_rows_inv(env, pv, (u32)(nc * 2));
             floor_step(env, SP, L, 2, nc, B.tp, B.e, {B.c01, B.c01_item_stride, LN}, {o, 2 * LN, LN}, {o, 2 * LN, LN});
+        });
+        HIPCHECK(hipGetLastError());
+    }
+    // What he355_linear_transform_bsgs takes from the pool at a chunk of `c` ciphertexts: the baby store, [slots][c][2][L + 1][N], and the two
+    // Q P blocks (the inner sum of a keyed giant row; the giant accumulator), [c][2][L][N] + [c][2][N] each -- in the pool's size classes.
+    static size_t bsgs_block_bytes(size_t c, int L, size_t N) { return DevicePool::size_class(c * 2 * (size_t)(L + 1) * N * 8); }
+    static size_t bsgs_store_bytes(size_t slots, size_t c, int L, size_t N) { return DevicePool::size_class(slots * c * 2 * (size_t)(L + 1) * N * 8); }
+    // he355_linear_transform_bsgs_scratch_bytes: the most a call with n_baby baby steps takes from the pool -- every baby used, the chunk the
+    // batch chunk (chunk_ops may only shorten it).  0 where the call does nothing or is refused (more than 2^20 babies are more than 2^20
+    // pairs); formed in 128 bits and saturated, so a huge batch cannot wrap into a small bound.
+    static u64 bsgs_scratch_bytes(size_t chunk, const Params &p, int L, u64 n, u64 n_baby)
+    {
+        const u64 c = std::min<u64>(chunk, n);
+        if (!c || !n_baby || n_baby > ((u64)1 << 20)) return 0;
+        const u128 block = (u128)c * 2 * (u128)(L + 1) * p.N * 8, cls = (u128)2 << 20; // (above 16 MiB the classes are multiples of 2 MiB: one more covers any rounding)
+        const u128 total = (u128)n_baby * block + cls + 2 * (block + cls);
+        return total > ~(u64)0 ? ~(u64)0 : (u64)total;
+    }
+    size_t chunk_limit() const { return chunk_; }
+    // The baby-step/giant-step linear transform on the hoisted rotations (the definition: include/he355.h).  Per chunk: ONE digit lift of the
+    // input, per used keyed baby launch_k3 and the rotate kernel into the baby store (T_i = sigma(S_i) with P sigma(c0) folded in; the
+    // identity: (P c0, P c1), streaming); then per used giant row the inner sum over its used terms -- straight into the accumulator for the
+    // identity row; for a keyed row into a Q P block, its mod-down into S.ks.c01 (free: k_k3 unfused never writes it), that ciphertext's own
+    // digit lift and key product, and the rotate kernel's accumulate form -- and the last mod-down into `out`.  The key-switch scratch is
+    // the chunk's arena, reused from step to step: one stream only.  The store and the two blocks come from the pool before the first launch;
+    // the term table lies in the context's table ring (table_ring).
+    void linear_transform_bsgs(const BsgsPlan &pl, int L, u64 n, const u64 *in, const u64 *plain_qp, u64 *out)
+    {
+        use();
+        const size_t N = P.N, LN = (size_t)L * N, QP = LN + N, n_baby = pl.baby.size(), n_giant = pl.giant.size();
+        const int SP = (int)P.K - 1;
+        auto used_row = [&](size_t j) { return pl.row_first[j + 1] > pl.row_first[j]; };
+        // the elements of the used steps, babies then giant rows (a step no kept term names counts as the identity: no key, no table)
+        std::vector<uint32_t> elts(n_baby + n_giant, 1);
+        for (size_t i = 0; i < n_baby; ++i)
+            if (pl.slot[i] >= 0) elts[i] = pl.baby[i];
+        for (size_t j = 0; j < n_giant; ++j)
+            if (used_row(j)) elts[n_baby + j] = pl.giant[j];
+        hoist_require_keys(elts, "he355_linear_transform_bsgs"); // before anything is allocated
+        // the chunk: the key-switch chunk (chunk_ops: the batch chunk, halved until the arena is reserved); the pool blocks are sized for it
+        const size_t chunk = chunk_ops(n, L, false);
+        const PoolBlock store = scoped_block(bsgs_store_bytes((size_t)pl.slots, chunk, L, N));
+        const PoolBlock blk_e = pl.keyed_rows ? scoped_block(bsgs_block_bytes(chunk, L, N)) : PoolBlock();
+        const PoolBlock blk_a = scoped_block(bsgs_block_bytes(chunk, L, N));
+        const HoistSetup hs = hoist_setup(elts, false, false, "he355_linear_transform_bsgs"); // (the permuted keys: the first launches)
+        const uint32_t *const *bperm = hs.table.data(), *const *gperm = hs.table.data() + n_baby;
+        const u64 *const *bkey = hs.key.data(), *const *gkey = hs.key.data() + n_baby;
+        const uint32_t *ident = perm(1);
+        // the term table goes through the table ring: a pool block written by a host copy would be outside the stream order that makes a
+        // pool release safe (device_pool.h), and a second call could rewrite it under this call's queued launches
+        const size_t t_bytes = (pl.terms.size() * 4 + 255) & ~(size_t)255;
+        const uint32_t *const d_terms = reinterpret_cast<const uint32_t *>(table_ring(t_bytes));
+        HIPCHECK(hipMemcpy(const_cast<uint32_t *>(d_terms), pl.terms.data(), pl.terms.size() * 4, hipMemcpyHostToDevice));
+        u64 *const st = store.get();
+        for_each_chunk(n, L, chunk, false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
+            const KernelEnv env = batch_env(0, true);
+            const KsBuffers &B = S.ks;
+            const u64 *a = in + off * 2 * LN;
+            u64 *o = out + off * 2 * LN;
+            u64 *eq = blk_e.get(), *ep = eq ? eq + nc * 2 * LN : nullptr; // [nc][2][L][N], then [nc][2][N]
+            u64 *aq = blk_a.get(), *ap = aq + nc * 2 * LN;
+            const u64 slot_words = nc * 2 * QP;
+            auto rows_inv_p = [&](u64 *p) {
+                PolyView pv = poly_view(p, 1, N, 1);
+                pv.prime_of[0] = (unsigned char)SP;
+                launch_rows_inv(env, pv, (u32)(nc * 2));
+            };
+            if (pl.keyed_babies) hoist_digit_lift(env, L, nc, off, in, B, false, ident);
+            for (size_t i = 0; i < n_baby; ++i) {
+                if (pl.slot[i] < 0) continue;
+                u64 *t = st + (u64)pl.slot[i] * slot_words; // [nc][2][L + 1][N]
+                if (!bkey[i]) {
+                    launch_bsgs_ident(env, L, nc, a, t);
+                    continue;
+                }
+                ++hoist_.key_products;
+                launch_k3(env, L, nc, B, bkey[i]);
+                launch_hoist_rot_qp(env, L, nc, B.t, B.tpr, a, bperm[i], t, QP, t + LN, QP, false);
+            }
+            bool first = true; // the accumulator starts with the first used row
+            for (size_t j = 0; j < n_giant; ++j) {
+                if (!used_row(j)) continue;
+                const uint32_t *terms = d_terms + 2 * pl.row_first[j];
+                const u64 n_terms = pl.row_first[j + 1] - pl.row_first[j];
+                const u64 *prow = plain_qp + (u64)j * n_baby * QP;
+                ++hoist_.inner_sums;
+                if (!gkey[j]) {
+                    launch_bsgs_inner(env, L, nc, st, prow, terms, n_terms, aq, ap, !first);
+                } else {
+                    launch_bsgs_inner(env, L, nc, st, prow, terms, n_terms, eq, ep, false);
+                    ++hoist_.mod_downs;
+                    rows_inv_p(ep);
+                    floor_step(env, SP, L, 2, nc, ep, B.e, {eq, 2 * LN, LN}, {}, {B.c01, B.c01_item_stride, LN});
+                    hoist_digit_lift(env, L, nc, 0, B.c01, B, false, ident);
+                    ++hoist_.key_products;
+                    launch_k3(env, L, nc, B, gkey[j]);
+                    launch_hoist_rot_qp(env, L, nc, B.t, B.tpr, B.c01, gperm[j], aq, LN, ap, N, !first);
+                }
+                first = false;
+            }
+            ++hoist_.mod_downs;
+            rows_inv_p(ap);
+            floor_step(env, SP, L, 2, nc, ap, B.e, {aq, 2 * LN, LN}, {}, {o, 2 * LN, LN});
         });
         HIPCHECK(hipGetLastError());
     }
@@ -1224,16 +1335,12 @@ public:
             cur = dst;
         }
     }
-    // device copy of a level's group tables: [perm pointers | key pointers | src_block | mult], grown as needed
-    struct GroupTables { KsGroups g; const u32 *d_mult; };
-    GroupTables upload_groups(const std::vector<const uint32_t *> &perms, const std::vector<const u64 *> &keys, const std::vector<u32> &src_block,
-                              const std::vector<u32> &mult, u32 group_size)
+    // The next region of `bytes` (a multiple of 256) of the context's table ring in HBM, for a small table a call uploads from the host with
+    // a synchronous copy: every upload takes the next region, so a region is never rewritten while kernels that were launched with it may
+    // still be running; when the ring wraps (or has to grow) the stream is drained first.  The copy is complete on return, whatever the
+    // runtime does with pageable memory, and everything that reads the region is launched afterwards.
+    unsigned char *table_ring(size_t bytes)
     {
-        const size_t G = perms.size(), bytes = (G * (8 + 8 + 4 + 4) + 255) & ~(size_t)255;
-        // The tables live in a ring in HBM: every upload takes the next region, so a region is never rewritten while kernels that were
-        // launched with it may still be running; when the ring wraps (or has to grow) the stream is drained first.  The copy itself is
-        // synchronous (complete on return, whatever the runtime does with pageable memory), and everything that reads the region is
-        // launched afterwards.
         Arena &ring = arena_[kGroups];
         if (bytes > ring.bytes || groups_next_ + bytes > ring.bytes) {
             HIPCHECK(hipStreamSynchronize(stream_));
@@ -1242,6 +1349,15 @@ public:
         }
         unsigned char *d_tab = reinterpret_cast<unsigned char *>(ring.p) + groups_next_;
         groups_next_ += bytes;
+        return d_tab;
+    }
+    // device copy of a level's group tables: [perm pointers | key pointers | src_block | mult], grown as needed
+    struct GroupTables { KsGroups g; const u32 *d_mult; };
+    GroupTables upload_groups(const std::vector<const uint32_t *> &perms, const std::vector<const u64 *> &keys, const std::vector<u32> &src_block,
+                              const std::vector<u32> &mult, u32 group_size)
+    {
+        const size_t G = perms.size(), bytes = (G * (8 + 8 + 4 + 4) + 255) & ~(size_t)255;
+        unsigned char *d_tab = table_ring(bytes);
         std::vector<unsigned char> h(bytes, 0);
         std::memcpy(h.data(), perms.data(), G * 8);
         std::memcpy(h.data() + G * 8, keys.data(), G * 8);
@@ -3317,6 +3433,21 @@ int he355_rotate_hoisted_plain_sum_lazy(he355_ctx *c, int L, uint64_t n, const u
         if (pl.empty) return; // nothing to sum: no buffer is touched, no device asked for
         dev(c).rotate_hoisted_lazy(pl, L, n, in, plain_qp, out);
     });
+}
+int he355_linear_transform_bsgs(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *baby, uint64_t n_baby, const int32_t *giant, uint64_t n_giant,
+                                const uint64_t *plain_qp, const uint8_t *mask, uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        const BsgsPlan pl = plan_linear_transform_bsgs(*c->params, L, n, in, baby, n_baby, giant, n_giant, plain_qp, mask, out);
+        if (pl.empty) return; // nothing to transform: no buffer is touched, no device asked for
+        dev(c).linear_transform_bsgs(pl, L, n, in, plain_qp, out);
+    });
+}
+uint64_t he355_linear_transform_bsgs_scratch_bytes(const he355_ctx *c, int L, uint64_t n, uint64_t n_baby)
+{
+    if (!c || L < 1 || (size_t)L > c->params->Ltop) return 0;
+    return DeviceContext::bsgs_scratch_bytes(c->dev ? c->dev->chunk_limit() : 1024, *c->params, L, n, n_baby);
 }
 int he355_plain_extend_special(he355_ctx *c, int L, uint64_t n, const uint64_t *plain_ntt, uint64_t *plain_qp, uint64_t *mismatch)
 {

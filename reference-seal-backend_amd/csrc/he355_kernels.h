@@ -247,6 +247,9 @@ HE355_FWD(launch_bfv_tail_fin)
 HE355_FWD(launch_key_permute)
 HE355_FWD(launch_hoist_finish_ntt)
 HE355_FWD(launch_hoist_acc_qp)
+HE355_FWD(launch_hoist_rot_qp)
+HE355_FWD(launch_bsgs_ident)
+HE355_FWD(launch_bsgs_inner)
 HE355_FWD(launch_plain_extend)
 HE355_FWD(launch_hoist_addend_coeff)
 HE355_FWD(launch_hoist_finish_coeff)

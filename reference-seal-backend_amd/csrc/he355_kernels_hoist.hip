@@ -15,6 +15,10 @@
 //                          data primes and the special prime.  The key product's ONE source row -- under the special prime k_k3 left it after
 //                          its inverse row pass: the wave runs the forward row pass -- permuted through the wave's LDS row, times the plaintext's
 //                          row, accumulated in Q P; c0's row goes through the same permutation into the output rows.  ONE mod-down follows.
+//   k_hoist_rot_qp         the baby-step/giant-step transform (he355_linear_transform_bsgs): k_hoist_acc_qp<true> without a plaintext -- the key
+//                          product's source row, P times c0's folded in for polynomial 0, permuted and stored (a baby term) or added into the
+//                          giant accumulator.  k_bsgs_ident: the identity baby, streaming.  k_bsgs_inner: a giant row's inner sum over its used
+//                          terms in 128-bit sums (bsgs_core.h), streaming, ciphertext-fastest so that the plaintext rows are re-read from cache.
 //   k_plain_extend         streaming (he355_plain_extend_special): the rows of a plaintext copied and its row under the special prime made
 //                          from the centred coefficients of row 0; optionally counts the coefficients whose other residues disagree.
 //   k_hoist_addend_coeff   streaming, once per chunk (BFV coefficient form): (c0, 0), what launch_bfv_tail_fin adds every element's key
@@ -27,6 +31,7 @@
 #include <string>
 #include <type_traits>
 
+#include "bsgs_core.h"
 #include "he355_kernels.h"
 #include "hoist_core.h"
 #include "ntt_core.h"
@@ -309,7 +314,197 @@ __global__ void __launch_bounds__(kBlock) k_hoist_finish_coeff(const u64 *src, u
         make_ulonglong2(hoist_gather_sign(s[hoist_gather_src(g.x)], g.x, q), hoist_gather_sign(s[hoist_gather_src(g.y)], g.y, q));
 }
 
+// ---- the baby-step/giant-step linear transform (he355_linear_transform_bsgs; arithmetic: bsgs_core.h) ----------------------------------
+struct HoistRotArgs {
+    const u64 *t;         // [n_ops][2][L][N]: one element's key product under the permuted key, data primes, canonical NTT form
+    const u64 *tpr;       // [n_ops][2][N]: the same under the special prime after k_k3's inverse row pass (hoist_sp_row)
+    const u64 *in;        // [n_ops][2][L][N]: the ciphertexts whose c1 was switched (c0 is read)
+    const uint32_t *perm; // [N]: Params::galois_perm_ntt(g)
+    u64 *dq;              // polynomial ok = op * 2 + k under data prime i: dq + ok * dq_poly_stride + i * N
+    u64 dq_poly_stride;
+    u64 *dp;              // ... under the special prime: dp + ok * dp_poly_stride
+    u64 dp_poly_stride;
+    u64 n_ops;
+    int L, K, logn1;
+    u64 sp_fix;           // as HoistAccArgs
+};
+// The sibling of k_hoist_acc_qp<true> without a plaintext: one wave per (ciphertext, polynomial, tile 0 .. L, row).  The key product's ONE
+// source row -- plus P times the input's c0 row for polynomial 0 under a data prime, added BEFORE the permutation: both lie in the same
+// source row, so one trip through the wave's LDS row carries both -- permuted and stored (!ACC: a baby term, or the first term of the giant
+// accumulator) or added into what the destination holds (ACC: the giant step; one stream, launches in order).
+template <bool ACC>
+__global__ void __launch_bounds__(kBlock) k_hoist_rot_qp(HoistRotArgs A, const PrimeDev *primes)
+{
+    __shared__ u64 lds_all[kWaves][kLdsRow];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const u32 n1 = 1u << A.logn1;
+    const int tiles = A.L + 1;
+    const u64 total = (A.n_ops * 2 * (u64)tiles) << A.logn1;
+    const u64 job = (u64)blockIdx.x * kWaves + wave;
+    if (job >= total) return; // (the whole wave; waves of a block share nothing)
+    const u32 a_row = (u32)(job & (n1 - 1));
+    const u64 pi = job >> A.logn1; // (op, polynomial, tile)
+    const int idx = (int)(pi % (u64)tiles);
+    const u64 ok = pi / (u64)tiles; // op * 2 + polynomial
+    const u64 N = (u64)n1 << kRowLog, arow = (u64)a_row << kRowLog;
+    const PrimeDev &P = primes[hoist_qp_prime(idx, A.L, A.K)];
+    const ModU64 m = make_modu(P);
+    u64 *lds = lds_all[wave];
+    const uint32_t *pm = A.perm + arow;
+    const u64 srow = (u64)hoist_src_row(__builtin_amdgcn_readfirstlane(pm[0])) << kRowLog;
+    const bool data = idx < A.L;
+    u64 v[kRowE];
+    if (data) {
+        const u64 ct_off = (ok * (u64)A.L + (u64)idx) * N;
+        load_rowC(A.t + ct_off + srow, lane, v);
+        if ((ok & 1) == 0) { // (wave-uniform)
+            const u64 pmq = bsgs_p_mod(primes[A.K - 1].q, m);
+            u64 c[kRowE];
+            load_rowC(A.in + ct_off + srow, lane, c);
+#pragma unroll
+            for (int r = 0; r < kRowE; ++r) v[r] = bsgs_fold_c0(v[r], c[r], pmq, m);
+        }
+    } else {
+        const u32 rowbase = n1 + (u32)(srow >> kRowLog);
+        if (P.f64) hoist_sp_row<ArF64>(P, A.tpr + ok * N + srow, A.logn1 == 0, rowbase, lane, lds, m, A.sp_fix, v);
+        else hoist_sp_row<ArU64>(P, A.tpr + ok * N + srow, A.logn1 == 0, rowbase, lane, lds, m, A.sp_fix, v);
+        HE_WAVE_SYNC(); // (the row pass is done with the LDS row)
+    }
+    // the output positions this lane stores (layout C: four runs of four neighbours) and where each comes from in the source row
+    u32 pl[kRowE];
+    {
+        const uint32_t *pb = pm + ((lane >> 2) << 6) + ((lane & 3) << 2);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint4 w = *reinterpret_cast<const uint4 *>(pb + (c << 4));
+            pl[4 * c + 0] = (u32)lds_pad((int)hoist_src_elem(w.x)); pl[4 * c + 1] = (u32)lds_pad((int)hoist_src_elem(w.y));
+            pl[4 * c + 2] = (u32)lds_pad((int)hoist_src_elem(w.z)); pl[4 * c + 3] = (u32)lds_pad((int)hoist_src_elem(w.w));
+        }
+    }
+    lds_store_C(lds, lane, v);
+    HE_WAVE_SYNC();
+#pragma unroll
+    for (int r = 0; r < kRowE; ++r) v[r] = lds[pl[r]];
+    u64 *drow = (data ? A.dq + ok * A.dq_poly_stride + (u64)idx * N : A.dp + ok * A.dp_poly_stride) + arow;
+    if constexpr (ACC) {
+        u64 acc[kRowE];
+        load_rowC(drow, lane, acc);
+#pragma unroll
+        for (int r = 0; r < kRowE; ++r) v[r] = bsgs_acc(acc[r], v[r], m.q);
+    }
+    store_rowC(drow, lane, v);
+}
+
+// The identity baby, streaming: dst [n_ops][2][L + 1][N] = (P c0, P c1) under the data primes and 0 under the special prime; a lane owns two
+// neighbouring coefficients, 16-byte accesses
+__global__ void __launch_bounds__(kBlock) k_bsgs_ident(const u64 *in, u64 *dst, const PrimeDev *primes, int L, int K, int logN, u64 n_polys)
+{
+    const u64 gid = (u64)blockIdx.x * kBlock + threadIdx.x;
+    const u64 p = gid >> (logN - 1); // (op, polynomial, tile)
+    if (p >= n_polys) return;        // (a block lies inside one row: the whole block leaves)
+    const u32 e2 = (u32)(gid & (((u64)1 << (logN - 1)) - 1));
+    const int idx = (int)(p % (u64)(L + 1));
+    const u64 ok = p / (u64)(L + 1);
+    ulonglong2 w = make_ulonglong2(0, 0);
+    if (idx < L) {
+        const ModU64 m = make_modu(primes[idx]);
+        const u64 pmq = bsgs_p_mod(primes[K - 1].q, m);
+        const ulonglong2 c = reinterpret_cast<const ulonglong2 *>(in + ((ok * (u64)L + (u64)idx) << logN))[e2];
+        w = make_ulonglong2(bsgs_ident_term(c.x, pmq, m), bsgs_ident_term(c.y, pmq, m));
+    }
+    reinterpret_cast<ulonglong2 *>(dst + (p << logN))[e2] = w;
+}
+
+struct BsgsInnerArgs {
+    const u64 *store;     // [n_slots][n_ops][2][L + 1][N]: the baby terms
+    const u64 *plain;     // the giant row's plaintexts, term i at plain + i * (L + 1) * N: [L + 1][N] each, shared by the chunk
+    const uint2 *terms;   // [n_terms]: the row's used terms, (slot in the store, plaintext of the row)
+    u32 n_terms;
+    u64 run;              // bsgs_run: the terms one 128-bit sum takes
+    u64 *dq;              // the sum's rows under the data primes, [n_ops][2][L][N] ...
+    u64 *dp;              // ... and under the special prime, [n_ops][2][N]
+    u64 n_ops;
+    int L, K, logN;
+    int acc;              // the identity row: the sum is added into what dq / dp hold (one load, one store)
+};
+// The inner sum of one giant row, streaming, no permutation: a lane owns two neighbouring coefficients of BOTH polynomials of one
+// (ciphertext, tile) -- one pass over the row's used terms, the plaintext's 16 bytes loaded once per term for the two polynomials, four 128-bit
+// sums, one reduction and one store each.  Blocks are numbered ciphertext-fastest: the blocks that are resident together read the SAME
+// plaintext segments (once from HBM, then from L2 / the memory-side cache) and differ only in their own store rows.
+__global__ void __launch_bounds__(kBlock) k_bsgs_inner(BsgsInnerArgs A, const PrimeDev *primes)
+{
+    const int seg_log = A.logN - 1 - 8; // blocks per row of N / 2 pairs (kBlock = 2^8 lanes)
+    const u64 b = blockIdx.x;
+    const u64 op = b % A.n_ops, rest = b / A.n_ops;
+    const int idx = (int)(rest >> seg_log);
+    if (idx > A.L) return; // (the whole block)
+    const u64 e2 = ((rest & (((u64)1 << seg_log) - 1)) << 8) + threadIdx.x;
+    const ModU64 m = make_modu(primes[hoist_qp_prime(idx, A.L, A.K)]);
+    const u64 N = (u64)1 << A.logN, tile = (u64)(A.L + 1) * N;
+    const u64 t_off = (op * 2 * (u64)(A.L + 1) + (u64)idx) * N, slot_stride = A.n_ops * 2 * tile;
+    u128 s00 = 0, s01 = 0, s10 = 0, s11 = 0;
+    u64 left = A.run;
+    for (u32 k = 0; k < A.n_terms; ++k) {
+        const uint2 tm = A.terms[k]; // (uniform)
+        const ulonglong2 p = reinterpret_cast<const ulonglong2 *>(A.plain + (u64)tm.y * tile + (u64)idx * N)[e2];
+        const u64 *t = A.store + (u64)tm.x * slot_stride + t_off;
+        const ulonglong2 a = reinterpret_cast<const ulonglong2 *>(t)[e2], c = reinterpret_cast<const ulonglong2 *>(t + tile)[e2];
+        if (bsgs_run_full(left, A.run)) {
+            bfv_mac_fold(s00, m); bfv_mac_fold(s01, m); bfv_mac_fold(s10, m); bfv_mac_fold(s11, m);
+        }
+        bfv_mac_add(s00, a.x, p.x); bfv_mac_add(s01, a.y, p.y); bfv_mac_add(s10, c.x, p.x); bfv_mac_add(s11, c.y, p.y);
+        --left;
+    }
+    ulonglong2 r0 = make_ulonglong2(bfv_mac_reduce(s00, m), bfv_mac_reduce(s01, m)), r1 = make_ulonglong2(bfv_mac_reduce(s10, m), bfv_mac_reduce(s11, m));
+    const bool data = idx < A.L;
+    u64 *d0 = data ? A.dq + (op * 2 * (u64)A.L + (u64)idx) * N : A.dp + op * 2 * N;
+    ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(d0) + e2, *o1 = reinterpret_cast<ulonglong2 *>(d0 + (data ? (u64)A.L * N : N)) + e2;
+    if (A.acc) {
+        const ulonglong2 x = *o0, y = *o1;
+        r0 = make_ulonglong2(bsgs_acc(x.x, r0.x, m.q), bsgs_acc(x.y, r0.y, m.q));
+        r1 = make_ulonglong2(bsgs_acc(y.x, r1.x, m.q), bsgs_acc(y.y, r1.y, m.q));
+    }
+    *o0 = r0;
+    *o1 = r1;
+}
+
 } // namespace
+
+void launch_hoist_rot_qp(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *tpr, const u64 *in, const uint32_t *perm, u64 *dq, u64 dq_poly_stride, u64 *dp,
+                         u64 dp_poly_stride, bool acc)
+{
+    if (!n_ops) return;
+    if (!t || !tpr || !in || !perm || !dq || !dp) throw std::runtime_error("linear transform: the rotate kernel needs both halves of the key product, the input, the permutation and the destination");
+    HoistRotArgs A{};
+    A.t = t; A.tpr = tpr; A.in = in; A.perm = perm; A.dq = dq; A.dq_poly_stride = dq_poly_stride; A.dp = dp; A.dp_poly_stride = dp_poly_stride;
+    A.n_ops = n_ops; A.L = L; A.K = env.K; A.logn1 = env.logn1;
+    A.sp_fix = env.logn1 ? hoist_row_pass_fix(env.prime_q[env.K - 1]) : 1;
+    const u64 jobs = (n_ops * 2 * (u64)(L + 1)) << env.logn1;
+    const dim3 g(grid_blocks((jobs + kWaves - 1) / kWaves, "linear transform", "ciphertexts"));
+    if (acc) hipLaunchKernelGGL(k_hoist_rot_qp<true>, g, dim3(kBlock), 0, env.stream, A, env.primes);
+    else hipLaunchKernelGGL(k_hoist_rot_qp<false>, g, dim3(kBlock), 0, env.stream, A, env.primes);
+}
+void launch_bsgs_ident(const KernelEnv &env, int L, u64 n_ops, const u64 *in, u64 *dst)
+{
+    if (!n_ops) return;
+    const int logN = env.logn1 + kRowLog;
+    const u64 n_polys = n_ops * 2 * (u64)(L + 1);
+    hipLaunchKernelGGL(k_bsgs_ident, dim3(streaming_grid(n_polys, logN, "linear transform", "ciphertexts")), dim3(kBlock), 0, env.stream, in, dst, env.primes, L, env.K, logN,
+                       n_polys);
+}
+void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store, const u64 *plain_row, const uint32_t *terms, u64 n_terms, u64 *dq, u64 *dp, bool acc)
+{
+    if (!n_ops) return;
+    if (!n_terms || n_terms > 0xffffffffull) throw std::runtime_error("linear transform: an inner sum takes between one and 2^32 - 1 terms");
+    BsgsInnerArgs A{};
+    A.store = store; A.plain = plain_row; A.terms = reinterpret_cast<const uint2 *>(terms); A.n_terms = (u32)n_terms;
+    u64 q[kMaxPrimes];
+    for (int i = 0; i <= L; ++i) q[i] = env.prime_q[hoist_qp_prime(i, L, env.K)];
+    A.run = bsgs_run(q, L + 1);
+    A.dq = dq; A.dp = dp; A.n_ops = n_ops; A.L = L; A.K = env.K; A.logN = env.logn1 + kRowLog; A.acc = acc ? 1 : 0;
+    const u64 blocks = (n_ops * (u64)(L + 1)) << (A.logN - 9);
+    hipLaunchKernelGGL(k_bsgs_inner, dim3(grid_blocks(blocks, "linear transform", "ciphertexts")), dim3(kBlock), 0, env.stream, A, env.primes);
+}
 
 void launch_key_permute(const KernelEnv &env, const u64 *src, u64 *dst, const uint32_t *perm, u64 n_polys)
 {

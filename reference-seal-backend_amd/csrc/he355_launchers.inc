@@ -92,6 +92,16 @@ void launch_hoist_finish_ntt(const KernelEnv &env, int L, u64 n_ops, const u64 *
 // first_a / first_b: the accumulator A / out starts with this term (stored, not read; a keyed first term zeroes out[.][1]).
 void launch_hoist_acc_qp(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *tpr, const u64 *in, const uint32_t *perm, const u64 *plain_qp, u64 *aq,
                          u64 aq_op_stride, u64 *ap, u64 *out, bool first_a, bool first_b);
+// The baby-step/giant-step transform (he355_linear_transform_bsgs).  The rotate kernel: t / tpr as launch_k3(K3_ALL) leaves them under the
+// element's permuted key, `in` [n_ops][2][L][N] the ciphertexts whose c1 was switched -> sigma(t + P in.c0, t.1) under the data primes into
+// dq + (op * 2 + k) * dq_poly_stride + i * N, sigma(NTT(tpr)) into dp + (op * 2 + k) * dp_poly_stride; acc: added into what lies there.
+void launch_hoist_rot_qp(const KernelEnv &env, int L, u64 n_ops, const u64 *t, const u64 *tpr, const u64 *in, const uint32_t *perm, u64 *dq, u64 dq_poly_stride, u64 *dp,
+                         u64 dp_poly_stride, bool acc);
+// the identity baby: dst [n_ops][2][L + 1][N] = P (.) in under the data primes, 0 under the special prime
+void launch_bsgs_ident(const KernelEnv &env, int L, u64 n_ops, const u64 *in, u64 *dst);
+// one giant row's inner sum: store [slots][n_ops][2][L + 1][N], plain_row = the row's plaintexts ([L + 1][N] each), terms [n_terms] device
+// pairs (slot, plaintext of the row) -> dq [n_ops][2][L][N], dp [n_ops][2][N]; acc: added into what lies there
+void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store, const u64 *plain_row, const uint32_t *terms, u64 n_terms, u64 *dq, u64 *dp, bool acc);
 // he355_plain_extend_special's streaming half: src [n][L][N] NTT form -> dst [n][L + 1][N], rows 0 .. L - 1 copied, row L = the coefficients
 // of row 0 (coeff [n][Lc][N], coefficient form) centred and reduced mod the special prime, coefficient form (launch_ntt_forward follows).
 // mismatch (optional, one device word, zeroed by the caller; needs Lc = L, else Lc = 1): += the (coefficient, prime >= 1) pairs that disagree
