@@ -19,7 +19,9 @@ in tests/linear_transform_bsgs_ref.py -- Python integers and the oracle's transf
 * sentinels on both sides of d_out; d_in and d_plain_qp re-read unchanged; he355_linear_transform_bsgs_scratch_bytes is at least the pool
   growth he355_alloc_stats sees across the call;
 * the two real-key cases of tests/test_linear_transform_bsgs_ref_cpu.py through the device, the plaintexts extended by
-  he355_plain_extend_special."""
+  he355_plain_extend_special.
+Layouts and rings beyond that table (an fp64 special prime, N = 16384 and 32768, explicit moduli, L = 1 under K = 5), a second fold of the
+inner sum and folds under 14- to 31-bit moduli live in tests/test_gpu_hoisted_layouts.py (the table: tests/hoisted_layouts.py)."""
 import zlib
 
 import numpy as np

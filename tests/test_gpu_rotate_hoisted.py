@@ -13,7 +13,9 @@ he355_rotate_hoisted_plain_sum against their definition -- the composition of or
   non-identity element), he355_path_stats untouched, he355_hoist_release_keys brings the bytes to zero and the next call is still right;
 * the plain sum equals the composed sum bit for bit (step 0 included); with real keys a 16-diagonal matrix decodes to numpy's product
   (CKKS: within rotate_hoisted_ref.CKKS_ERROR_CAP x the error of the same sum over he355_rotate; BFV: exactly);
-* BFV with real keys: he355_decrypt of the hoisted outputs equals that of he355_rotate; the noise budgets of both are printed, budget > 0."""
+* BFV with real keys: he355_decrypt of the hoisted outputs equals that of he355_rotate; the noise budgets of both are printed, budget > 0.
+Layouts and rings beyond this table -- the special prime in the fp64 engine, N = 16384 and 32768 through every call, explicit moduli, L = 1
+under K = 5, more Galois elements -- live in tests/test_gpu_hoisted_layouts.py (the table: tests/hoisted_layouts.py)."""
 import os
 import zlib
 
@@ -36,14 +38,16 @@ BFV = {"n1024": (1024, [50, 40, 40, 50], 20), "n2048": (2048, [60, 40, 60], 20)}
 STEPS = (1, 3, -2)
 
 
-def make_ckks(be, oracle, N, bits, force=False):
+def make_ckks(be, oracle, N, bits, force=False, primes=None):
+    """primes: the moduli themselves, the special prime last (`bits` is not read)"""
+    how = {"primes": list(primes)} if primes is not None else {"bit_sizes": bits, "sec128": False}
     if force:
         os.environ["HE355_FORCE_U64"] = "1"
     try:
-        g = be.Context(be.SCHEME_CKKS, N, bit_sizes=bits, sec128=False, device=0)
+        g = be.Context(be.SCHEME_CKKS, N, device=0, **how)
     finally:
         os.environ.pop("HE355_FORCE_U64", None)
-    o = oracle.Context(oracle.SCHEME_CKKS, N, bit_sizes=bits, sec128=False)
+    o = oracle.Context(oracle.SCHEME_CKKS, N, **how)
     assert g.moduli == o.moduli and (not force or not any(g.fp64))
     return g, o
 

@@ -12,7 +12,9 @@ bit for bit (np.array_equal, no tolerance), and with real keys against the eager
 * sentinels on both sides of d_out; d_in and d_plain_qp re-read unchanged;
 * ciphertexts and plaintexts all q_i - 1, c1 = 0, a key of all q_t - 1; a key installed again is followed;
 * he355_plain_extend_special on CKKS-encoded and BFV plaintexts, the mismatch count on a planted plaintext;
-* the two real-key cases of tests/test_rotate_hoisted_lazy_ref_cpu.py through the device, the plaintexts extended on the device."""
+* the two real-key cases of tests/test_rotate_hoisted_lazy_ref_cpu.py through the device, the plaintexts extended on the device.
+Layouts and rings beyond that table (an fp64 special prime, N = 16384 and 32768, explicit moduli, L = 1 under K = 5) live in
+tests/test_gpu_hoisted_layouts.py (the table: tests/hoisted_layouts.py)."""
 import zlib
 
 import numpy as np
