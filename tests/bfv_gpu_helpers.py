@@ -30,6 +30,8 @@ def random_chain(seed):
 ALL = dict(CONFIGS)
 for _s in (0, 3, 4):
     ALL[f"random{_s}"] = random_chain(_s)
+# the Shoup build of the u64 engine at LOGN1 = 4 (tests/shoup_rings.py, "n16384_60_50_40_60_shoup"): the level, NTT-form and noise calls
+ALL["n16384_shoup"] = (16384, [60, 50, 40, 60], 20)
 
 SENT = np.uint64(0x5E17155E17155E17)
 

@@ -270,7 +270,11 @@ CHAINS = {
     "n16384_60x4": ((16384, (60, 60, 60, 60, 60), 31), False, False, (3, 4), ()),
     "n32768_d3": ((32768, (60, 40, 40, 60), 20), False, False, (3, 1), ()),
     "n1024": ((1024, (50, 40, 50), 20), False, False, (2, 1), ()),
+    # the Shoup build of the u64 engine at LOGN1 = 4 and 5 (the chains of tests/shoup_rings.py: a 60- and a 50-bit prime on that engine)
+    "n16384_shoup": ((16384, (60, 50, 40, 60), 20), False, False, (3, 1), (3,)),
+    "n32768_shoup": ((32768, (60, 50, 40, 60), 20), False, False, (3,), ()),
 }
+SHOUP_RINGS = {"n16384_shoup": "n16384_60_50_40_60_shoup", "n32768_shoup": "n32768_60_50_40_60_shoup"}  # chain: its entry of shoup_rings.RINGS
 
 
 def chain_levels(name: str) -> dict:

@@ -33,7 +33,9 @@ BFV_DECRYPT_CHAINS = {  # name -> (N, bits, plain bits)
     "b50_40_t16": (1024, [50, 40, 50], 16), "b60x4_t31": (2048, [60] * 5, 31)}
 ENCRYPT_CHAINS = {  # name -> (scheme, N, bits, plain bits)
     "bfv_60_40_40_60": ("bfv", 1024, [60, 40, 40, 60], 20), "bfv_60_40_40_46": ("bfv", 1024, [60, 40, 40, 46], 20),
-    "ckks_60_45_45_60": ("ckks", 1024, [60, 45, 45, 60], 0)}
+    "ckks_60_45_45_60": ("ckks", 1024, [60, 45, 45, 60], 0),
+    # the Shoup build of the u64 engine at LOGN1 = 4 (tests/shoup_rings.py, "n16384_60_50_40_60_shoup")
+    "bfv_n16384_shoup": ("bfv", 16384, [60, 50, 40, 60], 20)}
 
 
 def prod(xs) -> int:

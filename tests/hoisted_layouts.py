@@ -16,6 +16,7 @@ the path of csrc/he355_kernels_hoist.hip that no context of the older table reac
 from __future__ import annotations
 
 import explicit_moduli as xm
+import shoup_rings as sr
 
 PLAIN_BITS = 20
 _FIXTURE = None
@@ -41,6 +42,10 @@ LAYOUTS = {
     "n16384": _ckks(16384, [60, 45, 60], "fold", "the lazy sum and the transform above N = 8192"),
     "n32768": _ckks(32768, [60, 45, 60], "fold", "the largest ring, default engines"),
     "deep_4096": _ckks(4096, [60, 40, 40, 40, 60], "fold", "L = 1 and 2 under K = 5: tile L is prime K - 1 across unused primes; one key digit of four"),
+    # the chains of tests/shoup_rings.py: the Shoup build of the u64 engine above N = 8192, a 60- and a 50-bit prime on it
+    "n8192_shoup": _ckks(8192, list(sr.MIXED), "shoup", "the Shoup form at logn1 = 3"),
+    "n16384_shoup": _ckks(16384, list(sr.MIXED), "shoup", "the Shoup form at logn1 = 4: the lazy sum, the transform and k_key_permute's quotient blocks"),
+    "n32768_shoup": _ckks(32768, list(sr.MIXED), "shoup", "the Shoup form on the largest ring"),
     # CKKS from the fixture
     "tiny": _fix("ckks", "tiny", "fold", "a 60-bit P and 59-bit centred coefficients under 14- to 31-bit moduli"),
     "tiny_n1024": _fix("ckks", "tiny_n1024", "fold", "the same with one row per polynomial"),
@@ -55,6 +60,7 @@ LAYOUTS = {
     # BFV: the eager call in both forms, the lazy sum and the transform on NTT-form residues
     "bfv_f64_only_1024": _bfv(1024, [42, 38, 44], None, "hoist_sp_row<ArF64> under BFV, `last`"),
     "bfv_f64_only_4096": _bfv(4096, [42, 38, 45, 44], None, "hoist_sp_row<ArF64> under BFV, logn1 = 2, three data primes"),
+    "bfv_n16384_shoup": _bfv(16384, list(sr.MIXED), "shoup", "the Shoup form at logn1 = 4 under BFV: the eager call in both forms"),
     "bfv_tiny_t256": _fix("bfv", "tiny_t256", "fold", "BFV over 14- to 31-bit primes"),
     "bfv_aux46_t256": _fix("bfv", "aux46_t256", "fold", "fp64 data primes of the auxiliary base's size under a 60-bit P"),
     "bfv_mac_337_t65536": _fix("bfv", "mac_337_t65536", "shoup", "a prime whose 128-bit sums take 337 terms beside a 256-term one"),

@@ -611,7 +611,12 @@ CHAINS = {
     "n16384_60_45_45_45_60_L4": ("ckks", 16384, (60, 45, 45, 45, 60)),        # no LDS shape: latency / unfused / fused
     "n32768_headline": ("ckks", 32768, HEADLINE_BITS),                        # L = 16 and L = 15: where fuse_pays' second clause decides
     "bfv_n8192_60_40_60": ("bfv", 8192, (60, 40, 60)),                        # the grouped NTT-domain path of a BFV context
+    # the Shoup build of the u64 engine (tests/shoup_rings.py holds the chains): the same rules, other machine code
+    "n16384_60_50_40_60_shoup": ("ckks", 16384, (60, 50, 40, 60)),            # LOGN1 = 4: latency / unfused / fused, every dual rule
+    "n8192_60_50_40_60_shoup": ("ckks", 8192, (60, 50, 40, 60)),              # LOGN1 = 3: the ring-in-LDS shape as well
+    "n16384_60_50_60_shoup": ("ckks", 16384, (60, 50, 60)),                   # no fp64 prime: no dual launches
 }
+SHOUP_CHAINS = tuple(k for k in CHAINS if k.endswith("_shoup"))  # each is an entry of shoup_rings.RINGS under the same name
 ALL_BUT_OG = tuple(d for d in DECISIONS if d != "og_per_block")
 CASES = [
     # (chain, op, L or None for the top level, decisions to pin or None for every one the chain reaches)
@@ -644,6 +649,18 @@ CASES = [
     ("n32768_headline", "apply_galois", 15, ("shape",)),
     ("bfv_n8192_60_40_60", "rotate_sum", None, None),
     ("bfv_n8192_60_40_60", "relinearize", None, None),  # (the coefficient-form key switch: no counter, no planned launches -- last)
+    ("n16384_60_50_40_60_shoup", "multiply_relin_rescale", None, None),
+    ("n16384_60_50_40_60_shoup", "multiply_relin_rescale_over_a", None, None),
+    ("n16384_60_50_40_60_shoup", "relinearize", None, None),
+    ("n16384_60_50_40_60_shoup", "apply_galois", None, None),
+    ("n16384_60_50_40_60_shoup", "rotate_sum", None, ALL_BUT_OG),
+    ("n16384_60_50_40_60_shoup", "rotate_each", None, None),
+    ("n8192_60_50_40_60_shoup", "multiply_relin_rescale", None, None),
+    ("n8192_60_50_40_60_shoup", "relinearize_rescale", None, None),
+    ("n8192_60_50_40_60_shoup", "rotate_add_in_place", None, None),
+    ("n8192_60_50_40_60_shoup", "rotate_sum", None, ALL_BUT_OG),
+    ("n16384_60_50_60_shoup", "multiply_relin_rescale", None, None),
+    ("n16384_60_50_60_shoup", "rotate_sum", None, ALL_BUT_OG),
 ]
 
 

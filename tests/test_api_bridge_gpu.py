@@ -90,6 +90,28 @@ def test_ckks_dot_product(backend, n):
     backend.destroy(hb)
 
 
+def test_ckks_dot_product_on_the_shoup_build_at_n16384(backend):
+    """50-bit coefficient moduli at N = 16384: the chain {60, 50, 50, 60} the bridge builds is Shoup-form with every prime on the u64
+    engine (asserted on a library context of the same chain), so multiply -> relinearize -> accumulate run the Shoup build's LOGN1 = 4
+    instantiations; the tolerance is test_ckks_dot_product's."""
+    import explicit_moduli as xm
+    be = importlib.import_module("reference-seal-backend_amd")
+    N, depth, bits, n = 16384, 3, 50, 100
+    g = be.Context(be.SCHEME_CKKS, N, bit_sizes=be.chain_bits(depth, bits), device=0)
+    try:
+        assert xm.bits_of(g.moduli) == [60, 50, 50, 60] and xm.form_of(g.moduli) == "shoup"
+        assert list(g.fp64) == [xm.is_f64(q) for q in g.moduli] == [False] * 4
+    finally:
+        g.close()
+    rng = np.random.default_rng(3 + N)
+    a, b = rng.uniform(-1, 1, (2, n)), rng.uniform(-1, 1, (2, n))
+    hb = backend.create(backend.find(W_DOT, SCHEME_CKKS, OFFLINE), ckks_params(n, N=N, depth=depth, bits=bits, scale=40), (2, 2))
+    res = backend.run(hb, [a, b], 1, np.float64)
+    want = (a @ b.T).reshape(4, 1)
+    assert np.allclose(res, want, atol=1e-3)
+    backend.destroy(hb)
+
+
 def test_bfv_eltwise_add(backend):
     rng = np.random.default_rng(4)
     n = 1000

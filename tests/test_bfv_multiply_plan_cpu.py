@@ -102,7 +102,9 @@ def test_the_case_table_takes_every_outcome_and_every_instantiation():
     for name, L, sizes in (("n8192_default", 2, {"rows_dual": 25, "rows_split": 26, "inv_dual": 34, "inv_split": 35}),
                            ("n16384_d3", 3, {"rows_dual": 9, "rows_split": 10, "inv_dual": 12, "inv_split": 13}),
                            # the split sides closest to the constant: 43 x 3 x 8 = 1032 and 57 x (12 + 6) = 1026 blocks
-                           ("n8192_shoup", 1, {"rows_dual": 42, "rows_split": 43, "inv_dual": 56, "inv_split": 57})):
+                           ("n8192_shoup", 1, {"rows_dual": 42, "rows_split": 43, "inv_dual": 56, "inv_split": 57}),
+                           # the Shoup build at LOGN1 = 4: two residues on the u64 engine, 9 x 7 x 16 = 1008 and 12 x (60 + 24) = 1008 blocks
+                           ("n16384_shoup", 3, {"rows_dual": 9, "rows_split": 10, "inv_dual": 12, "inv_split": 13})):
         got = {c.name.rsplit("_", 1)[0]: c.n for n_, L_, c in table if (n_, L_) == (name, L) and c.name.startswith(("rows_", "inv_"))}
         assert got == sizes, (name, got)
         lv = mp.chain_levels(name)[L]
@@ -115,7 +117,17 @@ def test_the_case_table_takes_every_outcome_and_every_instantiation():
     assert inst["n8192_d5", 5] == "<16,24>" and inst["n8192_d5", 4] == "<3,4,4,true>"
     assert inst["n8192_60x4", 4] == inst["n8192_60x4", 2] == "<3,4,6,false>"
     assert all(inst[k] == "<4,4,6,false>" for k in inst if k[0].startswith("n16384"))
-    assert all(inst[k] == "<4,6>" for k in inst if k[0] in ("n32768_d3", "n1024"))
+    assert all(inst[k] == "<4,6>" for k in inst if k[0] in ("n32768_d3", "n32768_shoup", "n1024"))
+    # the Shoup build at N >= 16384: the same instantiations as the fold chains of the same length -- other machine code -- with the
+    # 60- and the 50-bit data prime on the u64 engine, the 40-bit one and the whole auxiliary base on the fp64 engine
+    assert {k for k in inst if k[0] in mp.SHOUP_RINGS} == {("n16384_shoup", 3), ("n16384_shoup", 1), ("n32768_shoup", 3)}
+    s16, s32 = mp.chain_levels("n16384_shoup"), mp.chain_levels("n32768_shoup")
+    assert (s16[3].nB, s16[3].n_f, s16[3].n_u, s16[3].lds_bytes) == (3, 5, 2, 56 * KIB) and s16[3].fp64[:3] == (False, False, True)
+    assert (s16[1].nB, s16[1].n_f, s16[1].n_u, s16[1].lds_bytes) == (2, 3, 1, 32 * KIB)
+    assert (s32[3].nB, s32[3].n_f, s32[3].n_u) == (4, 6, 2) and s32[3].fp64[:3] == (False, False, True)
+    import shoup_rings as sr
+    for name, ring in mp.SHOUP_RINGS.items():
+        assert mp.CHAINS[name][0] == (sr.RINGS[ring]["N"], sr.RINGS[ring]["bits"], sr.PLAIN_BITS) and not mp.CHAINS[name][1], name
     x = mp.chain_levels("n8192_60x4")
     assert x[4].fp64[:4] == (False,) * 4 and x[2].fp64[:2] == (False,) * 2  # every data prime on the u64 engine
     assert not any(mp.chain_levels("n8192_force_u64")[2].fp64)

@@ -7,9 +7,10 @@ trust them (no GPU).  The first four run at N = 1024 on {50, 40, 50} and on the 
   the k = 0 rows are oracle.ntt of the slot ciphertext, and every row lies where bfv_selector_ref.row says;
 * decompose_ntt_ref, unpack_bytes_ntt_ref and gadget_ntt_ref against oracle.ntt of digits cut and lifted in Python integers (bfv_gadget_ref.digit /
   lift, int.from_bytes), whole polynomials of the source words those coefficients belong to; np_lift against bfv_gadget_ref.lift at its edges;
-* the five chains of test_gpu_bfv_large_rings.py build in the oracle, and their engines are what that module means: a 40-bit prime (fp64 engine)
-  beside 60-bit primes of the form 2^60 - c ... (fold form) or 50-bit primes (Shoup form); the plain moduli are the ones its shapes assume;
-* the five layouts of test_gpu_bfv_chain_layouts.py build in the oracle: bit lengths, t, the engine of every prime, the form by the rule of
+* the six chains of test_gpu_bfv_large_rings.py build in the oracle, and their engines are what that module means: a 40-bit prime (fp64 engine)
+  beside 60-bit primes of the form 2^60 - c ... (fold form) or 50-bit primes (Shoup form; n16384_shoup: a 60-bit beside a 50-bit one); the
+  plain moduli are the ones its shapes assume;
+* the six prime-size layouts of test_gpu_bfv_chain_layouts.py build in the oracle: bit lengths, t, the engine of every prime, the form by the rule of
   he_params.cpp, the two data primes of {60, 60, 60}, the gadget totals at v = 20 and v = 4, and the reply widths each first prime accepts."""
 import numpy as np
 import pytest
@@ -28,6 +29,7 @@ LARGE = {
     "n32768_fold": (32768, [60, 40, 40, 60], 20),
     "n8192_shoup": (8192, [50, 40, 50], 20),
     "n32768_shoup": (32768, [50, 40, 40, 50], 20),
+    "n16384_shoup": (16384, [60, 50, 40, 60], 20),  # tests/shoup_rings.py: 60-bit primes in the Shoup form, two data primes on the u64 engine
 }
 
 
@@ -192,10 +194,14 @@ def test_the_large_chains_build_and_their_engines_are_what_is_meant(oracle, name
     wide = [q for q in o.moduli if q >= 2 ** 47]  # the form is the context's: the key prime counts
     if name.endswith("fold"):  # the fold form takes primes 2^60 - c with c < 2^26 only (he_params.h, u64_fold)
         assert all(0 < 2 ** 60 - q < 2 ** 26 for q in wide)
+    elif name == "n16384_shoup":  # 60-bit primes of the fold's own shape, in the Shoup form because of the 50-bit prime
+        import shoup_rings as shoup
+        shoup.check("n16384_60_50_40_60_shoup", o.moduli, o.t)
+        assert [q.bit_length() for q in wide] == [60, 50, 60] and all(0 < 2 ** 60 - q < 2 ** 26 for q in wide if q.bit_length() == 60)
     else:
         assert all(q.bit_length() == 50 for q in wide)
-    # the counts the large-ring shapes are sized by
-    assert gad.table(data, 20)[1][-1] == {2: 5, 3: 7}[o.L]
+    # the counts the large-ring shapes are sized by (a 50-bit prime beside the 60-bit one: three digits of 20 bits more)
+    assert gad.table(data, 20)[1][-1] == (8 if name == "n16384_shoup" else {2: 5, 3: 7}[o.L])
 
 
 # the layouts of test_gpu_bfv_chain_layouts.py: (N, bit sizes), t, the u64 form by the rule of he_params.cpp (None: no u64 prime), the gadget
@@ -206,6 +212,7 @@ LAYOUTS = {
     "f64_only": ((2048, [42, 38, 45, 44]), 1032193, None, 8, 33, 30, False),
     "shoup_60": ((2048, [60, 50, 40, 60]), 1032193, "shoup", 8, 38, 48, True),
     "f64_first_1024": ((1024, [45, 55, 50]), 1038337, "shoup", 6, 26, 34, True),
+    "n16384_shoup": ((16384, [60, 50, 40, 60]), 786433, "shoup", 8, 38, 45, True),
 }
 
 
@@ -225,7 +232,7 @@ def test_the_chain_layouts_build_and_their_engines_are_what_is_meant(oracle, nam
         assert (form == "fold") == all(0 < 2 ** 60 - q < 2 ** 26 for q in wide)
     if name == "u64_only":
         assert o.moduli[:2] == [2 ** 60 - 0x27fff, 2 ** 60 - 0x17fff]
-    if name == "shoup_60":  # 60-bit primes of the fold's own shape, in the Shoup form because of the 50-bit prime
+    if name in ("shoup_60", "n16384_shoup"):  # 60-bit primes of the fold's own shape, in the Shoup form because of the 50-bit prime
         assert 0 < 2 ** 60 - o.moduli[0] < 2 ** 26 and o.moduli[1].bit_length() == 50
     data = o.moduli[:o.L]
     assert gad.table(data, 20)[1][-1] == e20 and gad.table(data, 4)[1][-1] == e4

@@ -56,7 +56,10 @@ In case 4 the over-the-run shapes are sized so that the 337-term and the 1023-te
 inner = 7 (350 terms); shoup_by_one_low60 L = 3, v = 4, inner = 12 (1080 terms, above all three runs, the cut through the column pass).
 12. tiny: bfv_seeded_encrypt and bfv_seeded_restore against tests/bfv_seeded_ref.py (a 14-bit prime under the uniform sampler's limit).
 
-Not run: these layouts at N >= 8192, and two passes through the pool block on them."""
+n16384_shoup is shoup_60 at N = 16384 (LOGN1 = 4; tests/shoup_rings.py): every case above once in the Shoup build's instantiations of
+the large ring, the planted ciphertext included.
+
+Not run: the other layouts at N >= 8192, and two passes through the pool block on them."""
 
 import numpy as np
 import pytest
@@ -68,6 +71,7 @@ import bfv_reply_ref as rep
 import bfv_ring_ref as ring
 import bfv_select_ref as tree
 import bfv_selector_ref as sel
+import shoup_rings as shoup
 from bfv_expand_ref import children, expand_levels
 from bfv_gpu_helpers import SENT, At, be, edged, ep_composition, expand_keys, inner_of, pair, rand_cts, refused, sentinelled, to_level  # noqa: F401 (be: the fixture)
 from bfv_merge_ref import merge_levels
@@ -81,7 +85,10 @@ LAYOUTS = {
     "f64_only": ((2048, [42, 38, 45, 44], 20), None, 30, False),
     "shoup_60": ((2048, [60, 50, 40, 60], 20), "shoup", 48, True),
     "f64_first_1024": ((1024, [45, 55, 50], 20), "shoup", 34, True),
+    # shoup_60 at LOGN1 = 4 (tests/shoup_rings.py): every call of this module once in the Shoup build's N = 16384 instantiations
+    "n16384_shoup": (shoup.spec("n16384_60_50_40_60_shoup"), "shoup", 45, True),
 }
+SHOUP_RINGS = {"n16384_shoup": "n16384_60_50_40_60_shoup"}  # layout: its entry of shoup_rings.RINGS
 # the layouts of explicit moduli: ((N, primes, t), form, top width, safe pair accepted) -- the last two by bfv_reply_ref's own rule
 EXPLICIT = {"aux46": "aux46_t256", "shoup_by_one_low60": "shoup_by_one_low60_t4294967291", "mac_337": "mac_337_t65536", "tiny": None}
 _FIX = xm.load()
@@ -124,6 +131,9 @@ def layout_pair(be, oracle, cid):
             assert [q.bit_length() for q in o.moduli] == chain[1] and g.L == len(chain[1]) - 1 and o.t.bit_length() == 20
             assert [q < 2 ** 47 for q in o.moduli] == [b < 47 for b in chain[1]], "the engines, by the prime-size rule"
         assert form_of(o.moduli) == form
+        if cid in SHOUP_RINGS:
+            shoup.check_device(SHOUP_RINGS[cid], g)
+            shoup.check(SHOUP_RINGS[cid], o.moduli, g.t)
         q0 = int(o.moduli[0])
         assert rep.max_width(N, q0) == top and rep.accepted(N, q0, *rep.safe_bits(N, o.t)) == safe
         _PAIRS[cid] = (g, o, N, sk, pk)

@@ -5,7 +5,7 @@ the other PIR modules stop at N = 4096 (LOGN1 <= 2).  Chains, each with a 40-bit
 
     n8192_fold   (8192, {60, 40, 60})       LOGN1 3, fold form       n8192_shoup  (8192, {50, 40, 50})       LOGN1 3, Shoup form
     n16384_fold  (16384, {60, 40, 40, 60})  LOGN1 4, fold form       n32768_shoup (32768, {50, 40, 40, 50})  LOGN1 5, Shoup form
-    n32768_fold  (32768, {60, 40, 40, 60})  LOGN1 5, fold form
+    n32768_fold  (32768, {60, 40, 40, 60})  LOGN1 5, fold form       n16384_shoup (16384, {60, 50, 40, 60})  LOGN1 4, Shoup form, two u64 data primes
 
 Operands are uniform rows mixed with all-0, all-(q - 1) and alternating 0 / (q - 1) rows; every output lies between a ring's worth of
 sentinel words before and after it; every operand is read back.  The routes of a call are bit-identical by definition, so every case resets
@@ -30,13 +30,14 @@ rows at Lt = 3 and 10 at Lt = 2 for v = 20.  The shapes are the smallest that re
 * he355_bfv_expand: count = 8, n = 3 (one real encryption, two random_poly queries), L = Lt, keys from oracle.keygen_galois, every child against
   the oracle's tree; he355_path_stats printed (which key-switch shapes carried it), not asserted.
 
-Not run: the pass split at N = 32768, and LOGN1 = 4 in the Shoup form."""
+Not run: the pass split at N = 32768."""
 
 import numpy as np
 import pytest
 
 import bfv_ring_ref as ring
 import bfv_selector_ref as sel
+import shoup_rings as shoup
 from bfv_expand_ref import children, expand_levels, np_shift
 from bfv_gpu_helpers import SENT, At, be, edged, ep_composition, expand_keys, inner_of, pair, sentinelled  # noqa: F401 (be: the fixture)
 
@@ -48,7 +49,9 @@ CHAINS = {
     "n32768_fold": "n32768_d3",
     "n8192_shoup": (8192, [50, 40, 50], 20),
     "n32768_shoup": (32768, [50, 40, 40, 50], 20),
+    "n16384_shoup": shoup.spec("n16384_60_50_40_60_shoup"),  # LOGN1 = 4 in the Shoup form: a 60- and a 50-bit prime on its u64 engine
 }
+SHOUP_RINGS = {"n16384_shoup": "n16384_60_50_40_60_shoup"}  # chain: its entry of shoup_rings.RINGS
 IDS = list(CHAINS)
 V = 20
 
@@ -63,6 +66,9 @@ def chain_pair(be, oracle, cid):
         assert N >= 8192 and g.L in (2, 3)
         data = o.moduli[:g.L]  # a prime for each engine under the default assignment (below 2^47: fp64), whatever HE355_FORCE_U64 says
         assert any(q < 2 ** 47 for q in data) and any(q >= 2 ** 47 for q in data), "both engines"
+        if cid in SHOUP_RINGS:
+            shoup.check_device(SHOUP_RINGS[cid], g)
+            shoup.check(SHOUP_RINGS[cid], o.moduli, g.t)
         _PAIRS[cid] = (g, o, N, sk, pk)
     return _PAIRS[cid]
 

@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 
 import bfv_multiply_plan as mp
+import shoup_rings as sr
 from bfv_gpu_helpers import SENT, At, be  # noqa: F401 (be: the fixture)
 from bfv_multiply_operands import family_cts
 
@@ -65,6 +66,9 @@ def contexts(be, oracle):
             assert g.moduli == o.moduli and g.t == o.t
             if force:
                 assert not any(g.fp64)
+            if name in mp.SHOUP_RINGS:  # the Shoup build of the u64 engine: the chain's form, engines and plain modulus are the table's
+                sr.check_device(mp.SHOUP_RINGS[name], g)
+                sr.check(mp.SHOUP_RINGS[name], o.moduli, g.t)
             made[name] = (g, o)
         return made[name]
 

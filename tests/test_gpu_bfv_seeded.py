@@ -30,8 +30,8 @@ from bfv_gpu_helpers import SENT, At, be, inner_of, pair, plains, rand_cts, refu
 
 pytestmark = pytest.mark.gpu
 
-CHAINS = ["n1024", "n4096_d3", (2048, [40, 60, 60], 20), (2048, [42, 38, 45, 44], 20)]
-IDS = ["n1024", "n4096_d3", "n2048_40_60_60", "n2048_42_38_45_44"]
+CHAINS = ["n1024", "n4096_d3", (2048, [40, 60, 60], 20), (2048, [42, 38, 45, 44], 20), "n16384_shoup"]  # the last: the Shoup build at LOGN1 = 4
+IDS = ["n1024", "n4096_d3", "n2048_40_60_60", "n2048_42_38_45_44", "n16384_shoup"]
 E_SEED = 0x5EC4E75EED
 FIRST = 1000
 ROWS = (0, 1, 3, 32)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import sampler_np as sn
+import shoup_rings as shoup
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,14 @@ CASES = {
     # 17 data primes: more than the 16 the device-side BFV decryptor / BEHZ multiply support -- encryption must still be exact
     # (round 1 overran a 16-entry table here); decryption of such a context runs on the host client
     "bfv_n32768_17_data_primes": ("bfv", 32768, [60] + [45] * 16 + [60], 20),
+    # the Shoup build of the u64 engine at LOGN1 = 4 (tests/shoup_rings.py): k_enc_mul_pk and the decryptors on a 60- and a 50-bit prime
+    "ckks_n16384_shoup": ("ckks", 16384, shoup.bits("n16384_60_50_40_60_shoup"), 0),
+    "bfv_n16384_shoup": ("bfv", 16384, shoup.bits("n16384_60_50_40_60_shoup"), shoup.PLAIN_BITS),
+    "ckks_n8192_shoup": ("ckks", 8192, shoup.bits("n8192_60_50_40_60_shoup"), 0),     # and at LOGN1 = 3 and 5
+    "bfv_n32768_shoup": ("bfv", 32768, shoup.bits("n32768_60_50_40_60_shoup"), shoup.PLAIN_BITS),
 }
+SHOUP_RINGS = {"ckks_n16384_shoup": "n16384_60_50_40_60_shoup", "bfv_n16384_shoup": "n16384_60_50_40_60_shoup",
+               "ckks_n8192_shoup": "n8192_60_50_40_60_shoup", "bfv_n32768_shoup": "n32768_60_50_40_60_shoup"}
 
 
 @pytest.fixture(scope="module")
@@ -41,6 +49,8 @@ def case(request, be, oracle):
     g = be.Context(sid_g, N, bit_sizes=bits, plain_bits=pb, sec128=False, device=0)
     o = oracle.Context(sid_o, N, bit_sizes=bits, plain_bits=pb, sec128=False)
     assert g.moduli == o.moduli
+    if request.param in SHOUP_RINGS:
+        shoup.check_device(SHOUP_RINGS[request.param], g)
     sk = o.keygen_secret(11)
     pk = o.keygen_public(sk, 12)
     g.set_public_key(pk)

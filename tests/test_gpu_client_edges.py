@@ -14,6 +14,7 @@ import pytest
 import client_operands as co
 import edge_operands as eo
 import sampler_np as sn
+import shoup_rings as shoup
 
 pytestmark = pytest.mark.gpu
 
@@ -237,6 +238,8 @@ def test_encrypt_under_the_constant_public_key(be, oracle, chain):
     scheme, N, bits, pb = co.ENCRYPT_CHAINS[chain]
     ckks = scheme == "ckks"
     g, o = _pair(be, oracle, scheme, N, bits, pb)
+    if chain == "bfv_n16384_shoup":
+        shoup.check_device("n16384_60_50_40_60_shoup", g)
     L = g.L
     pk, Cs = co.const_public_key(o.moduli, N)
     rng = np.random.default_rng(29)

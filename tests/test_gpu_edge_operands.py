@@ -12,7 +12,7 @@ chunks of 2, so an offset or a leak between batch rows shows.  Everything is bit
 Chains: {60,45,45,60} N = 4096 (mixed engines, fold build), {60,60,60,60} N = 2048 (fold only), {55,52,50,58} (Shoup build, runs of six),
 {60,45,45,60} with every prime forced onto the u64 engine, {47,46,45,44,47} N = 32768 and {46,47,60,46} N = 4096 (the re-centring and
 general-path digit lifts; the latter's special prime is far below q_2, so identity(2) drives the mod-down through every residue edge at
-large quotients), {60,45,45,58} (special prime below q_0), {60 x 7} and nine primes of 50 - 59 bits (full accumulation runs of both builds), the headline chain {60, 45 x 15, 60} at N = 32768, and BFV {60,40,40,60}.
+large quotients), {60,45,45,58} (special prime below q_0), {60 x 7} and nine primes of 50 - 59 bits (full accumulation runs of both builds), {60,50,40,60} at N = 16384 (the Shoup build at LOGN1 = 4: tests/shoup_rings.py), the headline chain {60, 45 x 15, 60} at N = 32768, and BFV {60,40,40,60}.
 For N <= 8192 the key-switching ops run under the ring-in-LDS, latency and throughput shapes, he355_path_stats proving which ran.
 tests/test_edge_operands_cpu.py holds the oracle to the exact model and to the closed form at the same operands, without a GPU."""
 import importlib
@@ -30,6 +30,7 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, HERE)
 import edge_operands as eo  # noqa: E402
 import make_exact_vectors_edges as mk  # noqa: E402
+import shoup_rings as sr  # noqa: E402
 
 CHAINS = {
     # name: (N, key-level bit sizes, force_u64)
@@ -44,6 +45,8 @@ CHAINS = {
     # primes never reach kAccRun products): six 60-bit digits on the fold build (a run of 5, then 1), eight Shoup-form digits (6, then 2)
     "n4096_60x7_fold_full_runs": (4096, [60] * 7, False),
     "n4096_50_to_59_x9_shoup_full_runs": (4096, [55, 52, 50, 58, 53, 51, 54, 56, 57], False),
+    # the Shoup build at LOGN1 = 4 (tests/shoup_rings.py): a 60- and a 50-bit prime on its u64 engine, an fp64 prime between them
+    "n16384_60_50_40_60_shoup": (16384, sr.bits("n16384_60_50_40_60_shoup"), False),
 }
 KEYS = ["uniform", "qm1", "identity_first", "identity_last"]
 # the families that take turns at positions 2 and 4 of a batch (position 0: qm1_coeff, or planted under an identity key)
@@ -86,6 +89,8 @@ def make_pair(be, oracle, N, bits, force, scheme="ckks", primes=None, t=0):
 def pair(request, be, oracle):
     N, bits, force = CHAINS[request.param]
     g, o = make_pair(be, oracle, N, bits, force)
+    if request.param in sr.RINGS:
+        sr.check_device(request.param, g)
     yield g, o, request.param
     g.close()
 
@@ -377,8 +382,9 @@ def test_key_switching_ops(pair, be, kind):
             check_all({"rotate_sum": out.download((n, 2, L, N))}, want, what + (shape,))
         if N > 8192:
             # a batch large enough for the fused key product (k_k3 with the floor in its epilogue; small rings would need hundreds of
-            # ciphertexts): the same five rows repeated to 32, one chunk
-            big = 32
+            # ciphertexts): the same five rows repeated to the first batch with 128 special-prime blocks (fuse_pays, he355_api.hip:
+            # N / 1024 blocks per op-group of eight -- 32 ciphertexts at N = 32768, 64 at N = 16384), one chunk
+            big = 8 * -(-128 // (N // 1024))
             idx = np.arange(big) % n
             g.set_chunk(1024)
             g.path_stats(reset=True)

@@ -34,6 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import edge_operands as eo  # noqa: E402
 import launch_plan as lp  # noqa: E402
+import shoup_rings as shoup  # noqa: E402
 
 _SHAPE_ENV = ("HE355_CHUNK", "HE355_LATENCY_MAX", "HE355_LEVEL_WALK", "HE355_LDS_MAX", "HE355_FORCE_U64")
 DEFAULT_SHAPES = not any(os.environ.get(k) for k in _SHAPE_ENV)
@@ -43,10 +44,12 @@ CHAINS = {
     "n4096_47_46_45_44_47": (4096, [47, 46, 45, 44, 47], 251, "uniform"),
     "n4096_60_45x7_60": (4096, [60] + [45] * 7 + [60], 251, "qm1"),
     "n32768_60_40_40_60": (32768, [60, 40, 40, 60], 27, "uniform"),
+    # the Shoup build at LOGN1 = 4 (tests/shoup_rings.py): its fp64 prime's floor forms beside a 60- and a 50-bit prime of the u64 engine
+    "n16384_60_50_40_60_shoup": (16384, [60, 50, 40, 60], 59, "uniform"),
 }
 OPS = ["multiply_relin", "multiply_relin_rescale", "relinearize", "relinearize_rescale", "rotate", "rotate_add"]
 # rotate_sum with the level sums inside k_k3 (level_sum_pays: whole groups of eight, 512 blocks in the data-prime launch): chain -> batch
-SUM_BATCH = {"n4096_47_46_45_44_47": 256, "n4096_60_45x7_60": 256, "n32768_60_40_40_60": 48}
+SUM_BATCH = {"n4096_47_46_45_44_47": 256, "n4096_60_45x7_60": 256, "n32768_60_40_40_60": 48, "n16384_60_50_40_60_shoup": 88}
 
 
 @pytest.fixture(scope="module")
@@ -65,6 +68,8 @@ class State:
         self.g = be.Context(be.SCHEME_CKKS, N, device=0, **kw)
         self.o = o = ho.Context(ho.SCHEME_CKKS, N, **kw)
         assert self.g.moduli == o.moduli
+        if name in shoup.RINGS:
+            shoup.check_device(name, self.g)
         self.L = L = self.g.L
         self.chain = lp.chain("ckks", N, bits, self.g.fp64)
         assert lp.ks_shape(self.chain, L, n, "product", True) == "fused" and lp.ks_shape(self.chain, L, n - 8, "product", True) != "fused" and n % 8

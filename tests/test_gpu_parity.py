@@ -10,6 +10,8 @@ import zlib
 import numpy as np
 import pytest
 
+import shoup_rings as sr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -30,6 +32,11 @@ CONFIGS = {
     "n8192_default": (8192, [60, 45, 60], False),
     "n16384_d4": (16384, [60, 45, 45, 45, 60], False),
     "n32768_d4": (32768, [60, 45, 45, 45, 60], False),
+    # the Shoup build of the u64 engine at N >= 8192 (tests/shoup_rings.py): LOGN1 = 3, 4, 5, both engines; 45-bit primes forced onto it
+    "n8192_60_50_40_60_shoup": (8192, sr.bits("n8192_60_50_40_60_shoup"), False),
+    "n16384_60_50_40_60_shoup": (16384, sr.bits("n16384_60_50_40_60_shoup"), False),
+    "n32768_60_50_40_60_shoup": (32768, sr.bits("n32768_60_50_40_60_shoup"), False),
+    "n16384_60_45_45_60_forced_shoup": (16384, sr.bits("n16384_60_45_45_60_forced_shoup"), True),
 }
 
 
@@ -45,6 +52,9 @@ def make_pair(be, oracle, name):
     assert g.moduli == o.moduli
     if force:
         assert not any(g.fp64)
+    if name in sr.RINGS:
+        assert sr.RINGS[name]["forced"] == force
+        sr.check_device(name, g)
     return g, o
 
 

@@ -17,6 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import shoup_rings as shoup  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 # (as tests/test_gpu_bench_shapes.py: the path counters describe the library's own choice of shape)
@@ -38,6 +40,8 @@ CASES = {
     "n4096_last_prime_u64_fold": (4096, [60, 45, 60, 60], False, 256, False, None),
     "n4096_last_prime_u64_shoup": (4096, [50, 50, 50, 50], False, 256, False, None),
     "n32768_l16_bench_ring": (32768, [60] + [45] * 15 + [60], True, 32, True, (0, 1, 15, 31)),
+    # the Shoup build at LOGN1 = 4 (tests/shoup_rings.py); fused from 57 ciphertexts at N = 16384 (16 x ceil(n / 8) >= 128 blocks)
+    "n16384_60_50_40_60_shoup": (16384, [60, 50, 40, 60], False, 64, True, None),
 }
 
 
@@ -48,6 +52,8 @@ def test_both_orders_of_the_rescale_tail_equal_the_oracle(be, oracle, case):
     try:
         o = oracle.Context(oracle.SCHEME_CKKS, N, bit_sizes=bits, sec128=sec128)
         assert g.moduli == o.moduli
+        if case in shoup.RINGS:
+            shoup.check_device(case, g)
         rng = np.random.default_rng(N + n)
         L = g.L
         assert L == len(bits) - 1

@@ -38,6 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import edge_operands as eo  # noqa: E402
 import launch_plan as lp  # noqa: E402
+import shoup_rings as sr  # noqa: E402
 from bfv_gpu_helpers import SENT  # noqa: E402
 
 # (tests/test_gpu_bench_shapes.py) the counter assertions describe the library's own choice of shape
@@ -81,6 +82,8 @@ class ChainState:
         self.g = be.Context(be.SCHEME_BFV if self.bfv else be.SCHEME_CKKS, N, device=0, **kw)
         self.o = ho.Context(ho.SCHEME_BFV if self.bfv else ho.SCHEME_CKKS, N, **kw)
         assert self.g.moduli == self.o.moduli
+        if name in lp.SHOUP_CHAINS:  # the Shoup build of the u64 engine: the chain's form and engines are the table's
+            sr.check_device(name, self.g)
         self.N = N
         self.chain = lp.chain(scheme, N, bits, self.g.fp64)
         self.rng = np.random.default_rng(list(lp.CHAINS).index(name) + 77)

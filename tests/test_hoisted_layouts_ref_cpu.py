@@ -55,10 +55,12 @@ def test_ckks_closed_form_at_c1_zero(oracle, name):
 
 
 def test_the_table_holds_the_paths_it_names():
-    assert len(hl.CKKS) == 16 and len(hl.BFV) == 7
+    assert len(hl.CKKS) == 19 and len(hl.BFV) == 8
+    shoup_large = {k for k in hl.LAYOUTS if hl.entry(k)["form"] == "shoup" and hl.entry(k)["N"] >= 8192}  # the Shoup build from N = 8192
+    assert shoup_large == {"n8192_shoup", "n16384_shoup", "n32768_shoup", "bfv_n16384_shoup"}
     for name in hl.LAYOUTS:
         e = hl.entry(name)
-        assert e["N"] in (1024, 2048, 4096, 16384, 32768) and len(e["bits"]) >= 3 and e["for"], name
+        assert e["N"] in (1024, 2048, 4096, 8192, 16384, 32768) and len(e["bits"]) >= 3 and e["for"], name
     fp64 = lambda name: hl.engines(hl.entry(name)["primes"])[0]
     assert fp64("unsorted_small_special")[-1] and not fp64("tiny")[-1]
     assert set(hl.EDGED) == {"f64_only_1024", "f64_only_4096", "f64_only_32768", "tiny", "tiny_n1024", "unsorted_small_special",

@@ -132,6 +132,52 @@ def test_case_table_takes_every_outcome_of_every_decision():
     assert (72, 149) in [(c, n) for _, c, n in lp.mixed_shape_calls(ch, ch.Ltop)]  # chunk 72 with n = 2 x 72 + 5 at {60,45,60}, N = 8192
 
 
+def test_shoup_rows_of_the_case_table():
+    """The rows that run the Shoup build of the u64 engine at N >= 8192: their chains are entries of tests/shoup_rings.py under the same
+    names (bit sizes, ring, engines), the selection rules do not look at the form -- the same boundaries as a fold chain of the same
+    length -- and between them the rows reach every shape the ring admits, with both engines in every dual rule at {60, 50, 40, 60}."""
+    import shoup_rings as sr
+    assert lp.SHOUP_CHAINS == ("n16384_60_50_40_60_shoup", "n8192_60_50_40_60_shoup", "n16384_60_50_60_shoup")
+    for name in lp.SHOUP_CHAINS:
+        scheme, N, bits = lp.CHAINS[name]
+        e = sr.RINGS[name]
+        assert scheme == "ckks" and (N, bits) == (e["N"], e["bits"]) and lp.engines(bits) == e["fp64"] and not e["forced"], name
+    rows = {}
+    for name, op, L, ns in lp.case_table():
+        if name in lp.SHOUP_CHAINS:
+            rows.setdefault(name, {})[op] = (L, ns)
+    assert sorted(rows["n16384_60_50_40_60_shoup"]) == ["apply_galois", "multiply_relin_rescale", "multiply_relin_rescale_over_a", "relinearize",
+                                                        "rotate_each", "rotate_sum"]
+    assert sorted(rows["n8192_60_50_40_60_shoup"]) == ["multiply_relin_rescale", "relinearize_rescale", "rotate_add_in_place", "rotate_sum"]
+    assert sorted(rows["n16384_60_50_60_shoup"]) == ["multiply_relin_rescale", "rotate_sum"]
+    # N = 2^14, L = 3: latency to 8, unfused to 56, fused from 57 (16 x ceil(n / 8) >= 128); L = 2 on the u64 engine alone: the same
+    ch = lp.case_chain("n16384_60_50_40_60_shoup")
+    assert ch.logn1 == 4 and shapes(ch, 3, [8, 9, 56, 57]) == ["latency", "unfused", "unfused", "fused"]
+    assert shapes(ch, 3, [8, 9, 56, 57], apart=False) == ["latency", "unfused", "unfused", "fused"]
+    assert rows["n16384_60_50_40_60_shoup"]["multiply_relin_rescale"] == (3, [1, 8, 9, 10, 11, 15, 16, 17, 21, 22, 40, 41, 56, 57, 63, 64, 65, 85, 86])
+    assert rows["n16384_60_50_40_60_shoup"]["rotate_sum"] == (3, [1, 2, 3, 4, 5, 6, 7, 8, 9, 14, 15, 18, 19, 23, 24, 25, 28, 29, 87, 88, 256, 257])
+    u = lp.case_chain("n16384_60_50_60_shoup")
+    assert shapes(u, 2, [8, 9, 56, 57]) == ["latency", "unfused", "unfused", "fused"]
+    assert rows["n16384_60_50_60_shoup"]["multiply_relin_rescale"] == (2, [1, 8, 9, 15, 16, 17, 32, 33, 40, 41, 56, 57, 63, 64, 65, 128, 129])
+    # N = 8192, L = 3: the ring-in-LDS shape to 32 (384 / 12), unfused to 120, fused from 121
+    c8 = lp.case_chain("n8192_60_50_40_60_shoup")
+    assert c8.logn1 == 3 and lp.lds_limit(c8, 3) == 32 and shapes(c8, 3, [32, 33, 120, 121]) == ["lds", "unfused", "unfused", "fused"]
+    assert rows["n8192_60_50_40_60_shoup"]["multiply_relin_rescale"] == (3, [1, 32, 33, 36, 37, 39, 40, 41, 80, 81, 85, 86, 120, 121, 127, 128, 129])
+    for name, want in (("n16384_60_50_40_60_shoup", {"latency", "unfused", "fused"}), ("n8192_60_50_40_60_shoup", {"lds", "unfused", "fused"}),
+                       ("n16384_60_50_60_shoup", {"latency", "unfused", "fused"})):
+        ch = lp.case_chain(name)
+        dual = set()
+        for op, (L, ns) in rows[name].items():
+            got = {c.shape for n in ns for c in lp.plan_call(ch, op, L, n).chunks}
+            assert got == want, (name, op, got)  # every shape the chain reaches is run -- and asserted through he355_path_stats -- per op
+            dual |= {l.family for n in ns for l in lp.plan_call(ch, op, L, n).launches() if l.family.endswith(("dual", "dual8"))}
+        if name == "n16384_60_50_60_shoup":
+            assert dual == {"k_k2n_dual"}, dual  # no fp64 prime: no launch for both engines; k_k2n_dual pairs the two digit kinds (60 / 50 bits)
+        else:
+            assert dual >= {"k_k1_dual", "k_k3_dual8", "k_floor_rows_dual"}, (name, dual)
+    assert max(ns[-1] for r in rows.values() for _, ns in r.values()) <= 257  # (the largest batch: 257 ciphertexts of 3 x 16384 words a polynomial)
+
+
 def test_rotation_terms_and_trie():
     assert lp.naf_terms(3, 8192) == [-1, 4] and lp.naf_terms(5, 8192) == [1, 4] and lp.naf_terms(-3, 8192) == [1, -4]
     assert lp.rotation_terms(3, 8192, (1, 2, 4, -1)) == [-1, 4] and lp.rotation_terms(2, 8192, (1, 2, 4, -1)) == [2]
