@@ -718,6 +718,83 @@ typedef struct he355_hoist_stats {
 } he355_hoist_stats_t;
 int he355_hoist_stats(he355_ctx *ctx, he355_hoist_stats_t *out, int reset);
 int he355_hoist_release_keys(he355_ctx *ctx);   /* frees the permuted copies; they are rebuilt on next use */
+/* ---- polynomial evaluation (CKKS) on a fused scalar combination ----
+ * he355_combine_scalars: out = sum_t a_t * ct_t + a_const, a constant polynomial being the same residue in every NTT slot:
+ *   out[c][k][i][e] = (sum_t h_scalars[t][i] * term_t[c][k][i][e] + (k == 0 ? h_const[i] : 0)) mod q_i,   i < L
+ * Everything canonical in and out; the integer sum is reduced once.  Term t is [n][size][L_t][N] with L_t = h_terms[t].L >= L, read with
+ * its own stride: rows >= L are ignored (he355_mod_switch_drop's rule, no copy).  Terms may repeat a pointer.  Residues are added whatever
+ * they stand for, as he355_add: any context (CKKS, NTT-form BFV).  One streaming launch (k_scalar_combine): T reads and one write.
+ * Refused on the host before any device work (HE355_E_INVALID_ARGS, the message names the call): L outside 1..L_top, a term level below L
+ * or above L_top, size outside 2..3, null lists or null terms with work to do, more than 2^20 terms, a scalar or constant >= q_i, slabs
+ * past 2^60 words or wrapping the address space, d_out overlapping any word of any term, n_terms == 0 with a constant.  n == 0, or
+ * n_terms == 0 without a constant, touches nothing and succeeds.  The term table lies in the context's table ring: calls may follow
+ * each other without a sync. */
+typedef struct { const uint64_t *d_ct; int32_t L; int32_t reserved; } he355_term; /* [n][size][L][N], L >= the call's L */
+int he355_combine_scalars(he355_ctx *ctx, int L, int size, uint64_t n, const he355_term *h_terms, uint64_t n_terms,
+                          const uint64_t *h_scalars /* [n_terms][L] canonical residues */, const uint64_t *h_const /* [L] or NULL */,
+                          uint64_t *d_out /* [n][size][L][N] */);
+/* Host only: out[i] = a mod q_i for i < L, a = the integer nearest v, ties to even (Python: int(round(v)) % q_i); a negative a gives
+ * q_i - (|a| mod q_i), or 0.  A double >= 2^52 is its own integer, taken exactly as m * 2^e in 128 bits.  Refused: non-finite v,
+ * |v| >= 2^126, L outside 1..L_top, null out. */
+int he355_ckks_scalar_residues(const he355_ctx *ctx, int L, double v, uint64_t *out /* [L] */);
+/* he355_ckks_eval_poly: out = p(in), p(x) = sum_k c_k x^k (monomial basis, real coefficients, trailing zeros trimmed), on a power tree
+ * of logarithmic depth.  d_in [n][2][L][N] at scale in_scale -> d_out [n][2][L - depth][N] at the nominal scale out_scale.
+ * The definition (tests/ckks_eval_poly_ref.py restates it on the oracle).  "Level" is the number of data primes; q[l] is prime index l,
+ * the one a rescale from l + 1 primes drops.  All scale arithmetic is IEEE double in the order written.
+ *   powers  m = 2^log_baby; babies x^1 .. x^(m-1), giants x^(m 2^j) while the exponent is <= the degree.  A power is computed only if a
+ *           non-zero coefficient's leaf uses it, a node's split uses it, or a needed power is built from it.
+ *           x^k = x^floor(k/2) * x^ceil(k/2): the higher operand dropped to the lower one's level l, one he355_multiply_relin with rescale:
+ *           level l - 1, scale s_a * s_b / q[l - 1].  (x^k lies at level L - ceil(log2 k).)
+ *   eval(p, Lt, S), deg p < m (a leaf):  T = S * q[Lt]; per non-zero c_k, k >= 1, the scalar he355_ckks_scalar_residues(Lt + 1, (c_k * T) / s_k);
+ *           the constant he355_ckks_scalar_residues(Lt + 1, c_0 * T) when c_0 != 0; ONE he355_combine_scalars at level Lt + 1 over the used
+ *           powers, each read at its own level, then he355_rescale to Lt.  A leaf whose powers lie below Lt + 1 is refused.
+ *   eval(p, Lt, S), otherwise (a node):  e = the largest giant exponent <= deg p, g = x^e at scale s_g, p = lo + x^e hi, T = S * q[Lt].
+ *           hi of degree >= 1:  H = eval(hi, Lt + 1, T / s_g);  prod = he355_multiply_relin(H, drop(g, Lt + 1), rescale = 1)
+ *           hi a constant c:    prod = he355_rescale(he355_combine_scalars(Lt + 1, {g}, scalar (c * T) / s_g))       (no product)
+ *           lo all zero: prod.  lo a constant c_0: he355_combine_scalars(Lt, {prod}, scalar 1, constant c_0 * S).  else prod + eval(lo, Lt, S).
+ *           The nominal scale of the result is exactly S.
+ *   depth   leaf: 1 + max over used k >= 1 of ceil(log2 k).  node: max(1 + max(depth(hi), ceil(log2 e)) -- 1 + ceil(log2 e) for a
+ *           constant hi --, depth(lo) for a lo of degree >= 1).  The call is eval(p, L - depth, out_scale).
+ *           log_baby = 1 gives the least depth, ceil(log2(deg + 1)); a larger baby side costs one more level at some degrees and saves
+ *           ciphertext products: he355_ckks_eval_poly_plan states the trade.
+ * n is processed in the key-switch chunk.  The power store and the node temporaries are ONE block taken from the context's pool after the
+ * relinearization-key check and before the first launch (the allocator's error if it does not fit; nothing is launched then).
+ * Refused on the host before any device work: a BFV context, L outside 1..L_top, no non-zero coefficient above c_0, more than 1024
+ * coefficients, log_baby outside 1..6, a non-finite coefficient, a scale that is non-finite or <= 0, depth >= L, a scalar
+ * he355_ckks_scalar_residues refuses, d_out overlapping d_in, null pointers with work to do.  A missing relinearization key is
+ * "relinearization key not present", said before anything is allocated.  n == 0 touches nothing. */
+typedef struct he355_poly_plan {
+    int32_t depth, L_out;     /* levels the call consumes; the level of d_out = L - depth                                        */
+    int32_t min_scalar_bits;  /* the least floor(log2 |a|) over the non-zero integer scalars of leaves: the caller's precision check
+                               * (a scalar of b bits carries its coefficient to about 2^-b); -1: every scalar rounded to zero       */
+    int32_t degree;           /* after trimming                                                                                   */
+    uint64_t products;        /* he355_multiply_relin calls per chunk: power tree + nodes                                          */
+    uint64_t combinations;    /* k_scalar_combine launches per chunk                                                              */
+    uint64_t rescales;        /* he355_rescale calls per chunk (leaves; the products carry their own)                              */
+    uint64_t drops, adds;     /* he355_mod_switch_drop copies and he355_add calls per chunk                                        */
+    uint64_t powers;          /* powers computed, x^1 not counted                                                                  */
+    uint64_t chunks;          /* ceil(n / min(n, batch chunk)): he355_poly_stats grows by chunks * the counts above                */
+    uint64_t pool_bytes;      /* an upper bound of the pool bytes the call takes at the context's batch chunk; 0 for n == 0        */
+    double out_scale;         /* the nominal scale of d_out: out_scale as given                                                    */
+    uint64_t power_mask[16];  /* bit k: x^k is computed (k >= 2)                                                                    */
+    uint64_t reserved[5];
+} he355_poly_plan_t;          /* 256 bytes */
+int he355_ckks_eval_poly_plan(const he355_ctx *ctx, int L, const double *h_coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
+                              uint64_t n, he355_poly_plan_t *out);
+int he355_ckks_eval_poly(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in /* [n][2][L][N] */, const double *h_coeffs, uint64_t n_coeffs, int log_baby,
+                         double in_scale, double out_scale, uint64_t *d_out /* [n][2][L - depth][N] */);
+/* What he355_combine_scalars and he355_ckks_eval_poly of this context ran since he355_device_init (or the last call with reset != 0);
+ * he355_path_stats counts the products' key switches as for any he355_multiply_relin, he355_hoist_stats nothing. */
+typedef struct he355_poly_stats {
+    uint64_t combinations; /* k_scalar_combine launches (he355_combine_scalars: one per call with work)   */
+    uint64_t products;     /* he355_multiply_relin calls made by he355_ckks_eval_poly, per chunk           */
+    uint64_t rescales;     /* he355_rescale calls made by it, per chunk                                    */
+    uint64_t drops, adds;  /* he355_mod_switch_drop copies / he355_add calls made by it, per chunk         */
+    uint64_t chunks;       /* chunks he355_ckks_eval_poly walked                                           */
+    uint64_t calls;        /* he355_ckks_eval_poly calls with work                                         */
+    uint64_t reserved;
+} he355_poly_stats_t;
+int he355_poly_stats(he355_ctx *ctx, he355_poly_stats_t *out, int reset);
 /* accumulateCKKS / accumulateBFV: in place log-tree sum of the first `count` slots; d_tmp: scratch slab of the same size.
  * count == 0 is the reference's else-branch (src/engine/seal_context.cpp:312-316, 341-344): every ciphertext is replaced by a
  * FRESH encryption of zero (Encryptor::encrypt_zero; needs the public key; L must be the top level, as SEAL returns a

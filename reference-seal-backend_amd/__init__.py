@@ -48,6 +48,20 @@ class HoistStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("digit_lifts", "key_products", "keys_permuted", "key_bytes", "mod_downs", "inner_sums")] + [("reserved", C.c_uint64 * 2)]
 
 
+class PolyStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("combinations", "products", "rescales", "drops", "adds", "chunks", "calls")] + [("reserved", C.c_uint64)]
+
+
+class PolyPlan(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("depth", "L_out", "min_scalar_bits", "degree")]
+                + [(k, C.c_uint64) for k in ("products", "combinations", "rescales", "drops", "adds", "powers", "chunks", "pool_bytes")]
+                + [("out_scale", C.c_double), ("power_mask", C.c_uint64 * 16), ("reserved", C.c_uint64 * 5)])
+
+
+class Term(C.Structure):
+    _fields_ = [("d_ct", C.c_void_p), ("L", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BfvRouteStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("cut_cols", "cut_stream", "mac_gadget", "mac_plain", "own_cols", "own_stream", "digits_fused",
                                            "digits_routed", "bytes_fused", "bytes_routed", "passes", "select_cols", "select_stream",
@@ -186,6 +200,11 @@ def lib():
             "he355_linear_transform_bsgs_scratch_bytes": (u64, [vp, i32, u64, u64]),
             "he355_hoist_stats": (i32, [vp, C.POINTER(HoistStats), i32]),
             "he355_hoist_release_keys": (i32, [vp]),
+            "he355_combine_scalars": (i32, [vp, i32, i32, u64, C.POINTER(Term), u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "he355_ckks_scalar_residues": (i32, [vp, i32, C.c_double, C.POINTER(C.c_uint64)]),
+            "he355_ckks_eval_poly_plan": (i32, [vp, i32, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, u64, C.POINTER(PolyPlan)]),
+            "he355_ckks_eval_poly": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, vp]),
+            "he355_poly_stats": (i32, [vp, C.POINTER(PolyStats), i32]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
             "he355_set_zero_stream": (i32, [vp, u64, u64]),
             "he355_ntt_forward": (i32, [vp, vp, u64, u8p, u32]),
@@ -223,7 +242,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -752,6 +771,41 @@ class Context:
         st = HoistStats()
         _check(lib().he355_hoist_stats(self.h, C.byref(st), int(reset)))
         return {k: int(getattr(st, k)) for k, _ in HoistStats._fields_ if k != "reserved"}
+
+    def combine_scalars(self, L, size, n, terms, scalars, out, const=None):
+        """out [n][size][L][N] = sum_t scalars[t][i] * terms[t] + (polynomial 0: const[i]); terms: (buffer, level) pairs, a level >= L read
+        with its own stride; scalars: len(terms) rows of L canonical residues; const: L residues or None"""
+        tt = (Term * max(1, len(terms)))(*[Term(getattr(b.ptr, "value", b.ptr), int(lv), 0) for b, lv in terms])
+        flat = [int(v) for row in scalars for v in row]
+        sc = (C.c_uint64 * max(1, len(flat)))(*flat)
+        cc = (C.c_uint64 * L)(*[int(v) for v in const]) if const is not None else None
+        _check(lib().he355_combine_scalars(self.h, L, size, n, tt, len(terms), sc, cc, out.ptr))
+
+    def ckks_scalar_residues(self, L, v) -> list:
+        """the residues of the integer nearest v (ties to even) under the first L primes"""
+        out = (C.c_uint64 * max(1, L))()
+        _check(lib().he355_ckks_scalar_residues(self.h, L, float(v), out))
+        return [int(x) for x in out[:L]]
+
+    def ckks_eval_poly_plan(self, L, coeffs, log_baby, in_scale, out_scale, n=1) -> dict:
+        """what ckks_eval_poly would do (he355_poly_plan_t): depth, L_out, counts per chunk, the powers computed, min_scalar_bits, pool_bytes"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        pl = PolyPlan()
+        _check(lib().he355_ckks_eval_poly_plan(self.h, L, cs, len(coeffs), log_baby, in_scale, out_scale, n, C.byref(pl)))
+        d = {k: getattr(pl, k) for k, _ in PolyPlan._fields_ if k not in ("reserved", "power_mask")}
+        d["powers_computed"] = [k for k in range(1024) if (pl.power_mask[k // 64] >> (k % 64)) & 1]
+        return d
+
+    def ckks_eval_poly(self, L, n, inp, coeffs, log_baby, in_scale, out_scale, out):
+        """out [n][2][L - depth][N] = sum_k coeffs[k] in^k at the nominal scale out_scale; inp [n][2][L][N] at in_scale"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        _check(lib().he355_ckks_eval_poly(self.h, L, n, inp.ptr, cs, len(coeffs), log_baby, in_scale, out_scale, out.ptr))
+
+    def poly_stats(self, reset: bool = False) -> dict:
+        """what combine_scalars and ckks_eval_poly ran (he355_poly_stats)"""
+        st = PolyStats()
+        _check(lib().he355_poly_stats(self.h, C.byref(st), int(reset)))
+        return {k: int(getattr(st, k)) for k, _ in PolyStats._fields_ if k != "reserved"}
 
     def hoist_release_keys(self):
         _check(lib().he355_hoist_release_keys(self.h))

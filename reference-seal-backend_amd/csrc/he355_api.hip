@@ -25,6 +25,7 @@
 #include "he_params.h"
 #include "hoist_args.h"
 #include "ntt_core.h"
+#include "poly_args.h"
 #include "rotation_plan.h"
 #include "client/he_client.h"
 #include "client/multiword.h"
@@ -1161,6 +1162,83 @@ public:
             floor_step(env, SP, L, 2, nc, ap, B.e, {aq, 2 * LN, LN}, {}, {o, 2 * LN, LN});
         });
         HIPCHECK(hipGetLastError());
+    }
+    // he355_combine_scalars: one launch of k_scalar_combine over `n` ciphertexts.  The table -- [n_terms] {slab, level} pairs, the scalars
+    // [n_terms][L], the constant [L] -- takes one region of the table ring (table_ring): calls may follow each other without a sync.
+    struct PolyTerm { const u64 *p; int L; };
+    void combine_scalars(int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out)
+    {
+        use();
+        const size_t t_words = 2 * (size_t)n_terms, s_words = (size_t)n_terms * (size_t)L, words = t_words + s_words + (h_const ? (size_t)L : 0);
+        std::vector<u64> h(words);
+        for (size_t t = 0; t < n_terms; ++t) {
+            h[2 * t] = (u64)(uintptr_t)terms[t].p;
+            h[2 * t + 1] = (u64)terms[t].L; // (the kernel's row of the term: (c * size + k) * L_t + i)
+        }
+        std::memcpy(h.data() + t_words, h_scalars, s_words * 8);
+        if (h_const) std::memcpy(h.data() + t_words + s_words, h_const, (size_t)L * 8);
+        const size_t bytes = (words * 8 + 255) & ~(size_t)255;
+        u64 *d_tab = reinterpret_cast<u64 *>(table_ring(bytes));
+        HIPCHECK(hipMemcpy(d_tab, h.data(), words * 8, hipMemcpyHostToDevice));
+        ++poly_.combinations;
+        launch_scalar_combine(batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+        HIPCHECK(hipGetLastError());
+    }
+    // he355_ckks_eval_poly: the plan's steps (poly_args.h), chunk by chunk in the key-switch chunk.  The power store and the temporaries are
+    // ONE pool block sized for the chunk, taken after the key check and before the first launch; every step is queued on the one stream.
+    void eval_poly(const PolyPlan &pl, int L, u64 n, const u64 *in, u64 *out)
+    {
+        use();
+        require_keyswitch();
+        if (!d_relin_) throw std::invalid_argument("he355_ckks_eval_poly: relinearization key not present"); // before anything is allocated
+        const size_t chunk = chunk_ops(n, L, false);
+        const PoolBlock blk = scoped_block((size_t)pl.words_per_ct * chunk * 8);
+        const size_t N = P.N;
+        Indexer pw{};
+        pw.b1 = 1; pw.pairwise = 1;
+        ++poly_.calls;
+        for (u64 off = 0; off < n; off += chunk) {
+            const u64 nc = std::min<u64>(chunk, n - off);
+            ++poly_.chunks;
+            auto at = [&](int b) -> u64 * {
+                const PolyBuf &B = pl.bufs[(size_t)b];
+                if (B.kind == 0) return const_cast<u64 *>(in) + off * 2 * (size_t)B.L * N;
+                if (B.kind == 1) return out + off * 2 * (size_t)B.L * N;
+                return blk.get() + B.off * nc;
+            };
+            for (const PolyStep &s : pl.steps) {
+                switch (s.op) {
+                case kPolyMulRelin:
+                    ++poly_.products;
+                    multiply_relin(s.L, nc, at(s.a), at(s.b), pw, true, at(s.dst));
+                    break;
+                case kPolyDrop:
+                    ++poly_.drops;
+                    mod_switch_drop(pl.bufs[(size_t)s.a].L, s.L, nc * 2, at(s.a), at(s.dst));
+                    break;
+                case kPolyRescale:
+                    ++poly_.rescales;
+                    rescale(s.L, 2, nc, at(s.a), at(s.dst));
+                    break;
+                case kPolyAdd:
+                    ++poly_.adds;
+                    addsub(s.L, 2, nc, at(s.a), at(s.b), pw, at(s.dst), false);
+                    break;
+                case kPolyCombine: {
+                    std::vector<PolyTerm> t;
+                    for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
+                    combine_scalars(s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst));
+                    break;
+                }
+                }
+            }
+        }
+    }
+    he355_poly_stats_t poly_stats(bool reset)
+    {
+        const he355_poly_stats_t s = poly_;
+        if (reset) poly_ = he355_poly_stats_t{};
+        return s;
     }
     // plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N]: the rows copied and row L = NTT_P of the coefficients of row 0, centred
     // (he355_plain_extend_special).  mismatch (optional, one device word): the (coefficient, prime >= 1) pairs that disagree with row 0.
@@ -2772,6 +2850,7 @@ private:
     struct HoistKey { u64 *p = nullptr; bool ok = false; };
     std::map<uint32_t, HoistKey> d_hoist_; // hoist_key(): the permuted copies of the Galois keys, per element
     he355_hoist_stats_t hoist_{};
+    he355_poly_stats_t poly_{};
     he355_bfv_route_stats_t routes_{};
     he355_bfv_multiply_stats_t mul_routes_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
@@ -3462,6 +3541,55 @@ int he355_hoist_stats(he355_ctx *c, he355_hoist_stats_t *out, int reset)
     return guarded([&] {
         if (!out) throw std::invalid_argument("null pointer");
         *out = dev(c).hoist_stats(reset != 0);
+    });
+}
+int he355_combine_scalars(he355_ctx *c, int L, int size, uint64_t n, const he355_term *terms, uint64_t n_terms, const uint64_t *scalars, const uint64_t *cst, uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        if (plan_combine_scalars(*c->params, L, size, n, terms, n_terms, scalars, cst, out)) return; // nothing to combine: no buffer is touched, no device asked for
+        DeviceContext &d = dev(c);
+        std::vector<DeviceContext::PolyTerm> t((size_t)n_terms);
+        for (size_t k = 0; k < t.size(); ++k) t[k] = {terms[k].d_ct, terms[k].L};
+        d.combine_scalars(L, size, n, t.data(), n_terms, scalars, cst, out);
+    });
+}
+int he355_ckks_scalar_residues(const he355_ctx *c, int L, double v, uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        poly_scalar_residues(*c->params, "he355_ckks_scalar_residues", L, v, out);
+    });
+}
+int he355_ckks_eval_poly_plan(const he355_ctx *c, int L, const double *coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale, uint64_t n,
+                              he355_poly_plan_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        if (!out) throw std::invalid_argument("he355_ckks_eval_poly_plan: null plan");
+        const u64 chunk = c->dev ? c->dev->chunk_limit() : 1024;
+        const PolyPlan pl = plan_eval_poly(*c->params, "he355_ckks_eval_poly_plan", L, n, nullptr, coeffs, n_coeffs, log_baby, in_scale, out_scale, nullptr, false, chunk);
+        *out = pl.info;
+        // one block of min(chunk, n) times the plan's words, rounded up by a size class of the pool (at most 2 MiB: device_pool.h)
+        const u128 bytes = (u128)pl.words_per_ct * std::min<u64>(chunk, n) * 8, bound = bytes + ((u128)2 << 20);
+        out->pool_bytes = !n ? 0 : bound > ~(u64)0 ? ~(u64)0 : (u64)bound;
+    });
+}
+int he355_ckks_eval_poly(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const double *coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
+                         uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        const PolyPlan pl = plan_eval_poly(*c->params, "he355_ckks_eval_poly", L, n, in, coeffs, n_coeffs, log_baby, in_scale, out_scale, out, true, 1024);
+        if (pl.empty) return; // nothing to evaluate: no buffer is touched, no device asked for
+        dev(c).eval_poly(pl, L, n, in, out);
+    });
+}
+int he355_poly_stats(he355_ctx *c, he355_poly_stats_t *out, int reset)
+{
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null pointer");
+        *out = dev(c).poly_stats(reset != 0);
     });
 }
 int he355_hoist_release_keys(he355_ctx *c)

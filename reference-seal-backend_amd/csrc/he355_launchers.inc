@@ -102,6 +102,9 @@ void launch_bsgs_ident(const KernelEnv &env, int L, u64 n_ops, const u64 *in, u6
 // one giant row's inner sum: store [slots][n_ops][2][L + 1][N], plain_row = the row's plaintexts ([L + 1][N] each), terms [n_terms] device
 // pairs (slot, plaintext of the row) -> dq [n_ops][2][L][N], dp [n_ops][2][N]; acc: added into what lies there
 void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store, const u64 *plain_row, const uint32_t *terms, u64 n_terms, u64 *dq, u64 *dp, bool acc);
+// he355_combine_scalars (he355_kernels_poly.hip): out [n][size][L][N] = sum_t scalars[t][i] * term_t + (polynomial 0: cst[i]); d_terms [n_terms]
+// device pairs of words {the term's slab [n][size][L_t][N], L_t >= L}, d_scalars [n_terms][L], d_const [L] or null -- all canonical
+void launch_scalar_combine(const KernelEnv &env, int L, int size, u64 n, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *out);
 // he355_plain_extend_special's streaming half: src [n][L][N] NTT form -> dst [n][L + 1][N], rows 0 .. L - 1 copied, row L = the coefficients
 // of row 0 (coeff [n][Lc][N], coefficient form) centred and reduced mod the special prime, coefficient form (launch_ntt_forward follows).
 // mismatch (optional, one device word, zeroed by the caller; needs Lc = L, else Lc = 1): += the (coefficient, prime >= 1) pairs that disagree
