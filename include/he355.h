@@ -795,6 +795,45 @@ typedef struct he355_poly_stats {
     uint64_t reserved;
 } he355_poly_stats_t;
 int he355_poly_stats(he355_ctx *ctx, he355_poly_stats_t *out, int reset);
+/* ---- the modulus raise (CKKS): from q_0 alone back up the chain, on a fused lift-and-transform kernel ----
+ * Every other level operation goes down (he355_rescale, he355_mod_switch_drop); this one takes a ciphertext whose chain is used up back to
+ * L_to primes, the first step of a bootstrapping circuit.  The definition (tests/ckks_mod_raise_ref.py restates it on the oracle), for every
+ * polynomial p of the n * size:
+ *   x   = iNTT_{q_0}(in[p][0])                                    (coefficients, canonical under q_0)
+ *   c_e = x_e if x_e <= (q_0 - 1) / 2, else x_e - q_0             (the centred integer: he355_plain_extend_special's range)
+ *   out[p][j] = NTT_{q_j}(c mod q_j), canonical, j < L_to
+ * so the raised ciphertext decrypts over q_0 .. q_{L_to - 1} to m + q_0 * I with a small integer polynomial I (|I| <= (h + 2) / 2 for a
+ * ternary secret of Hamming weight h); removing q_0 * I is the circuit's business (linear transforms, he355_ckks_eval_poly).
+ * Only row 0 of the input is read, with the input's own [L_in][N] stride: rows >= 1 are ignored (he355_mod_switch_drop's rule, no copy).
+ * out[p][0] is in[p][0] bit for bit, made by a copy.  L_to = 1 is that copy alone; L_to > L_in is the use; L_to <= L_in means the same.
+ * The call equals, bit for bit, the composition of public calls: copy row 0, he355_ntt_inverse (prime 0), he355_ckks_lift_centred,
+ * he355_ntt_forward (primes 0 .. L_to - 1) -- without the coefficient slab and the lifted slab in memory: N >= 2048 runs the inverse row
+ * pass of row 0 into a compact tail, ONE kernel that finishes the inverse transform of a column, lifts it and runs the forward column pass
+ * per target (k_raise_cols), and the forward row pass in place; N = 1024, which has no column pass, runs inverse transform ->
+ * k_raise_lift -> forward transform.  n is processed in the key-switch chunk (he355_set_chunk).  A chunk of nc ciphertexts with
+ * nc * size * 4 below the device's compute-unit count deals the targets of a column to
+ * tsplit = min(L_to - 1, ceil(CUs / (nc * size * 4))) blocks (he355_set_latency_max(0) switches this off with the other latency shapes).
+ * he355_ckks_lift_centred is the middle step on its own: d_coeff [n_polys][N], coefficients canonical under q_0 -> d_out [n_polys][L_to][N],
+ * row j = c mod q_j, canonical, coefficient form (row 0 = the input).  One streaming launch.
+ * Refused on the host before any device work (HE355_E_INVALID_ARGS, the message names the call): a BFV context, L_in or L_to outside
+ * 1..L_top, size outside 1..3, null pointers with work to do, slabs past 2^60 words or wrapping the address space, d_out overlapping any
+ * word of d_in (its ignored rows count) or of d_coeff, a slab that is not 16-byte aligned (the kernels move two words at a time; an offset
+ * of whole polynomials into an aligned slab stays aligned).  n == 0 touches nothing and needs no device. */
+int he355_ckks_mod_raise(he355_ctx *ctx, int L_in, int L_to, int size, uint64_t n, const uint64_t *d_in /* [n][size][L_in][N], NTT form */,
+                         uint64_t *d_out /* [n][size][L_to][N], NTT form */);
+int he355_ckks_lift_centred(he355_ctx *ctx, int L_to, uint64_t n_polys, const uint64_t *d_coeff /* [n_polys][N], coefficients, canonical under q_0 */,
+                            uint64_t *d_out /* [n_polys][L_to][N], coefficients */);
+/* What the two calls of this context ran since he355_device_init (or the last call with reset != 0); he355_path_stats, he355_hoist_stats
+ * and he355_poly_stats count nothing of them. */
+typedef struct he355_raise_stats {
+    uint64_t calls;              /* he355_ckks_mod_raise calls with work                                             */
+    uint64_t chunks;             /* chunks they walked                                                               */
+    uint64_t fused_launches;     /* k_raise_cols launches (N >= 2048, L_to >= 2: one per chunk)                      */
+    uint64_t streaming_launches; /* k_raise_lift launches (N = 1024 with L_to >= 2: one per chunk; he355_ckks_lift_centred: one) */
+    uint64_t split_launches;     /* the fused launches that dealt a column's targets to tsplit > 1 blocks            */
+    uint64_t reserved[3];
+} he355_raise_stats_t;           /* 64 bytes */
+int he355_raise_stats(he355_ctx *ctx, he355_raise_stats_t *out, int reset);
 /* accumulateCKKS / accumulateBFV: in place log-tree sum of the first `count` slots; d_tmp: scratch slab of the same size.
  * count == 0 is the reference's else-branch (src/engine/seal_context.cpp:312-316, 341-344): every ciphertext is replaced by a
  * FRESH encryption of zero (Encryptor::encrypt_zero; needs the public key; L must be the top level, as SEAL returns a

@@ -52,6 +52,10 @@ class PolyStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("combinations", "products", "rescales", "drops", "adds", "chunks", "calls")] + [("reserved", C.c_uint64)]
 
 
+class RaiseStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "fused_launches", "streaming_launches", "split_launches")] + [("reserved", C.c_uint64 * 3)]
+
+
 class PolyPlan(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("depth", "L_out", "min_scalar_bits", "degree")]
                 + [(k, C.c_uint64) for k in ("products", "combinations", "rescales", "drops", "adds", "powers", "chunks", "pool_bytes")]
@@ -205,6 +209,9 @@ def lib():
             "he355_ckks_eval_poly_plan": (i32, [vp, i32, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, u64, C.POINTER(PolyPlan)]),
             "he355_ckks_eval_poly": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, vp]),
             "he355_poly_stats": (i32, [vp, C.POINTER(PolyStats), i32]),
+            "he355_ckks_mod_raise": (i32, [vp, i32, i32, i32, u64, vp, vp]),
+            "he355_ckks_lift_centred": (i32, [vp, i32, u64, vp, vp]),
+            "he355_raise_stats": (i32, [vp, C.POINTER(RaiseStats), i32]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
             "he355_set_zero_stream": (i32, [vp, u64, u64]),
             "he355_ntt_forward": (i32, [vp, vp, u64, u8p, u32]),
@@ -242,7 +249,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_ckks_mod_raise", "he355_ckks_lift_centred", "he355_raise_stats", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -806,6 +813,21 @@ class Context:
         st = PolyStats()
         _check(lib().he355_poly_stats(self.h, C.byref(st), int(reset)))
         return {k: int(getattr(st, k)) for k, _ in PolyStats._fields_ if k != "reserved"}
+
+    def ckks_mod_raise(self, L_in, L_to, size, n, inp, out):
+        """out [n][size][L_to][N] = the residue under q_0 of inp [n][size][L_in][N] (row 0 of every polynomial; the rest is ignored), read as
+        centred integers and re-expressed under q_0 .. q_{L_to - 1}, NTT form in and out (he355_ckks_mod_raise)"""
+        _check(lib().he355_ckks_mod_raise(self.h, L_in, L_to, size, n, inp.ptr, out.ptr))
+
+    def ckks_lift_centred(self, L_to, n_polys, coeff, out):
+        """out [n_polys][L_to][N] = the coefficients coeff [n_polys][N] (canonical under q_0), centred, mod q_j in row j; coefficient form"""
+        _check(lib().he355_ckks_lift_centred(self.h, L_to, n_polys, coeff.ptr, out.ptr))
+
+    def raise_stats(self, reset: bool = False) -> dict:
+        """what ckks_mod_raise and ckks_lift_centred ran (he355_raise_stats)"""
+        st = RaiseStats()
+        _check(lib().he355_raise_stats(self.h, C.byref(st), int(reset)))
+        return {k: int(getattr(st, k)) for k, _ in RaiseStats._fields_ if k != "reserved"}
 
     def hoist_release_keys(self):
         _check(lib().he355_hoist_release_keys(self.h))

@@ -26,6 +26,7 @@
 #include "hoist_args.h"
 #include "ntt_core.h"
 #include "poly_args.h"
+#include "raise_args.h"
 #include "rotation_plan.h"
 #include "client/he_client.h"
 #include "client/multiword.h"
@@ -258,6 +259,9 @@ private:
         if (env_u64("HE355_LATENCY_MAX", v)) set_latency_max(v);
         if (env_u64("HE355_LDS_MAX", v)) set_lds_max(v);
         if (env_u64("HE355_CHUNK", v) && v > 0) chunk_ = (size_t)v;
+        int cus = 0;
+        HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_));
+        cus_ = cus > 0 ? (u64)cus : 1;
     }
     // drain, free the tables, the keys and the arenas, destroy the pool, then the events and streams (whatever of them exists)
     void teardown()
@@ -1238,6 +1242,58 @@ public:
     {
         const he355_poly_stats_t s = poly_;
         if (reset) poly_ = he355_poly_stats_t{};
+        return s;
+    }
+    // he355_ckks_mod_raise: row 0 of every polynomial copied on the stream, then chunk by chunk (the key-switch chunk, in ciphertexts) the
+    // inverse row pass of row 0 into a compact tail [nc size][N] from the pool (k_rows_inv_select, prime 0), the fused column kernel
+    // (k_raise_cols; N = 1024 has no column pass: k_raise_lift on the finished coefficients) and the forward row pass over rows 1 .. L_to - 1
+    // in place.  A chunk of fewer than CUs / 4 polynomials deals the targets of a column to raise_tsplit blocks, as the latency shape of the
+    // key switch does -- unless the latency shapes are switched off (he355_set_latency_max(0)).
+    void mod_raise(int L_in, int L_to, int size, u64 n, const u64 *in, u64 *out)
+    {
+        use();
+        const size_t N = P.N;
+        ++raise_.calls;
+        const u64 chunk = std::min<u64>(chunk_, n);
+        const PoolBlock tail = L_to > 1 ? scoped_block((size_t)chunk * size * N * 8) : PoolBlock();
+        const bool split_on = lat_auto_ || lat_max_ > 0;
+        for (u64 off = 0; off < n; off += chunk) {
+            const u64 np = std::min<u64>(chunk, n - off) * (u64)size;
+            const u64 *src = in + off * size * (size_t)L_in * N;
+            u64 *dst = out + off * size * (size_t)L_to * N;
+            ++raise_.chunks;
+            HIPCHECK(hipMemcpy2DAsync(dst, (size_t)L_to * N * 8, src, (size_t)L_in * N * 8, N * 8, (size_t)np, hipMemcpyDeviceToDevice, stream_));
+            if (L_to > 1) {
+                launch_rows_inv_select(env_, 0, np, src, (u64)L_in * N, tail.get());
+                if (P.logn1 == 0) {
+                    ++raise_.streaming_launches;
+                    launch_raise_lift(env_, L_to, 1, np, tail.get(), dst);
+                } else {
+                    const int tsplit = split_on ? raise_tsplit(np, L_to, cus_) : 1;
+                    ++raise_.fused_launches;
+                    if (tsplit > 1) ++raise_.split_launches;
+                    launch_raise_cols(env_, L_to, np, tail.get(), dst, tsplit);
+                }
+                PolyView pv = poly_view(dst + N, L_to - 1, N, L_to);
+                pv.item_stride = (u64)L_to * N;
+                for (int j = 1; j < L_to; ++j) pv.prime_of[j - 1] = (unsigned char)j;
+                launch_rows_fwd(env_, pv, (u32)np);
+            }
+        }
+        HIPCHECK(hipGetLastError());
+    }
+    // he355_ckks_lift_centred: one streaming launch
+    void lift_centred(int L_to, u64 n_polys, const u64 *coeff, u64 *out)
+    {
+        use();
+        ++raise_.streaming_launches;
+        launch_raise_lift(env_, L_to, 0, n_polys, coeff, out);
+        HIPCHECK(hipGetLastError());
+    }
+    he355_raise_stats_t raise_stats(bool reset)
+    {
+        const he355_raise_stats_t s = raise_;
+        if (reset) raise_ = he355_raise_stats_t{};
         return s;
     }
     // plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N]: the rows copied and row L = NTT_P of the coefficients of row 0, centred
@@ -2851,6 +2907,8 @@ private:
     std::map<uint32_t, HoistKey> d_hoist_; // hoist_key(): the permuted copies of the Galois keys, per element
     he355_hoist_stats_t hoist_{};
     he355_poly_stats_t poly_{};
+    he355_raise_stats_t raise_{};
+    u64 cus_ = 1; // compute units of the device (the small-batch split of the modulus raise)
     he355_bfv_route_stats_t routes_{};
     he355_bfv_multiply_stats_t mul_routes_{};
     bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
@@ -3590,6 +3648,29 @@ int he355_poly_stats(he355_ctx *c, he355_poly_stats_t *out, int reset)
     return guarded([&] {
         if (!out) throw std::invalid_argument("null pointer");
         *out = dev(c).poly_stats(reset != 0);
+    });
+}
+int he355_ckks_mod_raise(he355_ctx *c, int L_in, int L_to, int size, uint64_t n, const uint64_t *in, uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        if (plan_mod_raise(*c->params, L_in, L_to, size, n, in, out)) return; // nothing to raise: no buffer is touched, no device asked for
+        dev(c).mod_raise(L_in, L_to, size, n, in, out);
+    });
+}
+int he355_ckks_lift_centred(he355_ctx *c, int L_to, uint64_t n_polys, const uint64_t *coeff, uint64_t *out)
+{
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("null context");
+        if (plan_lift_centred(*c->params, L_to, n_polys, coeff, out)) return;
+        dev(c).lift_centred(L_to, n_polys, coeff, out);
+    });
+}
+int he355_raise_stats(he355_ctx *c, he355_raise_stats_t *out, int reset)
+{
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null pointer");
+        *out = dev(c).raise_stats(reset != 0);
     });
 }
 int he355_hoist_release_keys(he355_ctx *c)

@@ -251,6 +251,8 @@ HE355_FWD(launch_hoist_rot_qp)
 HE355_FWD(launch_bsgs_ident)
 HE355_FWD(launch_bsgs_inner)
 HE355_FWD(launch_scalar_combine)
+HE355_FWD(launch_raise_lift)
+HE355_FWD(launch_raise_cols)
 HE355_FWD(launch_plain_extend)
 HE355_FWD(launch_hoist_addend_coeff)
 HE355_FWD(launch_hoist_finish_coeff)

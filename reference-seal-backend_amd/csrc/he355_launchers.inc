@@ -105,6 +105,13 @@ void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store,
 // he355_combine_scalars (he355_kernels_poly.hip): out [n][size][L][N] = sum_t scalars[t][i] * term_t + (polynomial 0: cst[i]); d_terms [n_terms]
 // device pairs of words {the term's slab [n][size][L_t][N], L_t >= L}, d_scalars [n_terms][L], d_const [L] or null -- all canonical
 void launch_scalar_combine(const KernelEnv &env, int L, int size, u64 n, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *out);
+// ---- the CKKS modulus raise (he355_kernels_raise.hip; arithmetic: raise_core.h) ------------------------------------------------------------
+// coeff [n_polys][N], coefficients canonical under q_0 -> rows first .. L_to - 1 of out [n_polys][L_to][N]: the centred coefficient mod q_j,
+// canonical, coefficient form (first = 0: he355_ckks_lift_centred; first = 1: row 0 is the caller's).  One streaming launch.
+void launch_raise_lift(const KernelEnv &env, int L_to, int first, u64 n_polys, const u64 *coeff, u64 *out);
+// tail [n_polys][N] as launch_rows_inv_select(prime 0) leaves it -> rows 1 .. L_to - 1 of out [n_polys][L_to][N] after the forward column pass
+// (raw of prime j; launch_rows_fwd finishes them in place).  tsplit > 1: a column's targets dealt to that many blocks.  N >= 2048 only.
+void launch_raise_cols(const KernelEnv &env, int L_to, u64 n_polys, const u64 *tail, u64 *out, int tsplit = 1);
 // he355_plain_extend_special's streaming half: src [n][L][N] NTT form -> dst [n][L + 1][N], rows 0 .. L - 1 copied, row L = the coefficients
 // of row 0 (coeff [n][Lc][N], coefficient form) centred and reduced mod the special prime, coefficient form (launch_ntt_forward follows).
 // mismatch (optional, one device word, zeroed by the caller; needs Lc = L, else Lc = 1): += the (coefficient, prime >= 1) pairs that disagree
