@@ -8,7 +8,7 @@
 namespace he355 {
 
 // Device constants of the BEHZ multiply, derived from BehzTables (he_params.h) with every chain of constant factors folded into one
-// (he355_api.hip, DeviceContext::behz): each step is then ONE 128-bit sum of products and ONE Barrett reduction -- same residues.
+// (he_params.cpp, Params::behz_host; DeviceContext::behz uploads them): each step is then ONE 128-bit sum of products and ONE Barrett reduction -- same residues.
 // All pointers are HBM.  Bsk order: B_0..B_{nB-1}, m_sk (S = nB + 1); p_j the j-th of them.
 struct BehzDev {
     int L, nB;

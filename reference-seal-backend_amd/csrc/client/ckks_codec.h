@@ -7,7 +7,9 @@
 // built once on the host and copied to the device, so both sides execute the same IEEE operations in the same order and
 // produce the same bits.
 #pragma once
-#include "../modarith.h"
+#include <stdexcept>
+
+#include "../device_types.h"
 
 #if defined(__clang__)
 #define HE_FP_STRICT _Pragma("clang fp contract(off)")
@@ -16,6 +18,22 @@
 #endif
 
 namespace he355 {
+
+// the slot ranges of a decode call, checked against the encoder's slot count (ranges == null: every slot)
+inline SlotRanges slot_ranges(const u64 *ranges, u64 n_ranges, u64 slots)
+{
+    SlotRanges sr{};
+    if (!ranges) { sr.n = 1; sr.first[0] = 0; sr.count[0] = sr.total = (u32)slots; return sr; }
+    if (n_ranges < 1 || n_ranges > (u64)kMaxSlotRanges) throw std::invalid_argument("decode: 1 to 4 slot ranges");
+    sr.n = (u32)n_ranges;
+    for (u64 g = 0; g < n_ranges; ++g) {
+        const u64 first = ranges[2 * g], count = ranges[2 * g + 1];
+        if (first > slots || count > slots - first) throw std::invalid_argument("decode: slot range outside the encoder's slots");
+        sr.first[g] = (u32)first; sr.count[g] = (u32)count; sr.total += (u32)count;
+    }
+    return sr;
+}
+
 namespace client {
 
 struct Cplx {

@@ -29,6 +29,15 @@ struct PrimeDev {
     alignas(64) double colw[64];
 };
 
+// Per (source prime s, target prime i) constants of the RNS divide-and-round ("floor") step used by the
+// key-switch mod-down (s = special prime) and by rescale (s = last data prime).  Device array [K][K].
+struct FloorConst {
+    u64 inv, inv_shoup;   // s^-1 mod q_i (+ Shoup quotient)
+    double inv_d, inv_i;  // same for the fp64 engine: value and fl(value/q_i)
+    u64 half_mod;         // floor(s/2) mod q_i
+    u64 src_mod;          // s mod q_i
+};
+
 // How result r picks its operands (HEBench outer product, ckks eltwise .cpp:334-336, or pairwise)
 struct Indexer {
     u64 a_base, b_base; // value_index of operand 0 / 1
@@ -78,6 +87,15 @@ HE_HD const u64 *behz_src_ct(const BehzSrc &s, u64 item, u64 ct_words)
 }
 HE_HD u64 ord_a(const BehzSrc &s, u64 r) { return (r / s.ix.gs) * s.I + (r % s.ix.gs) / s.ix.b1; }
 HE_HD u64 ord_b(const BehzSrc &s, u64 r) { return s.na + (r / s.ix.gs) * s.J + (r % s.ix.gs) % s.ix.b1; }
+
+// the slots a decode writes per plaintext: up to kMaxSlotRanges ranges [first, first + count) of the slot vector, written one after the other
+// (out row = `total` values).  A workload's decode() reads the first n / dim3 slots of a result -- and BFV MatMultRow those of both batching rows
+// (bfv row .cpp:339-369) -- not the N/2 or N the encoder has
+constexpr int kMaxSlotRanges = 4;
+struct SlotRanges {
+    u32 n, total;
+    u32 first[kMaxSlotRanges], count[kMaxSlotRanges];
+};
 
 // A batch of residue polynomials for the generic transform kernels:
 // poly p of item it lives at base + it*item_stride + p*N and belongs to prime prime_of[p] (255 = skip).

@@ -18,8 +18,10 @@
 #include <vector>
 
 #include "../../include/he355.h"
+#include "behz_lists.h"
 #include "bfv_pir_args.h"
 #include "device_pool.h"
+#include "device_tables.h"
 #include "he355_internal.h"
 #include "he355_kernels.h"
 #include "he_params.h"
@@ -203,51 +205,14 @@ private:
         for (size_t i = 0; i < n_all; ++i) {
             const PrimeTables &pt = i < K ? P.primes[i] : i < K + P.aux.size() ? P.aux[i - K] : plain_tables_;
             Tw16 *dfwd = upload_owned(pt.fwd.data(), N), *dinv = upload_owned(pt.inv.data(), N);
-            PrimeDev &d = pd[i];
-            const ArU64 au = pt.aru();
-            const ArF64 af = pt.arf();
-            d.q = pt.q; d.cr0 = pt.mod.cr0; d.cr1 = pt.mod.cr1;
-            d.ninv = au.ninv; d.ninv_q = au.ninv_q;
-            d.qd = af.q; d.qinv = af.qinv; d.ninv_d = af.ninv; d.ninv_i = af.ninv_i;
-            d.fwd = dfwd; d.inv = dinv; d.inv_w0_scaled = pt.inv_w0_scaled;
-            d.f64 = pt.f64 ? 1 : 0;
-            d.acc_terms = pt.f64 ? floor_direct_terms(pt.q) : 0;
-            for (size_t k = 0; k < 64; ++k) d.colw[k] = 0.0;
-            if (pt.f64)
-                for (size_t k = 0; k < 32 && k < N; ++k) { d.colw[k] = ArF64::tw_w(pt.fwd[k]); d.colw[32 + k] = ArF64::tw_w(pt.inv[k]); }
-            d.k2_direct = d.k2_lift = 0;
-            d.pow32 = (double)((((u64)1) << 32) % pt.q);
+            prime_dev_fill(pd[i], pt, N);
+            pd[i].fwd = dfwd; pd[i].inv = dinv;
             env_.prime_f64[i] = pt.f64 ? 1 : 0;
             env_.prime_q[i] = pt.q;
         }
-        // k_k2n's lift classes per (digit prime j, fp64-engine target prime t) -- the same rule the kernel's general path evaluates
-        for (size_t j = 0; j < K; ++j)
-            for (size_t t = 0; t < K; ++t) {
-                if (!P.primes[t].f64) continue;
-                const u64 qj = P.primes[j].q, qt = P.primes[t].q;
-                const bool df = (qj >> 52) == 0, direct = df && !(qj > 2 * qt);
-                double m = df ? (direct ? (double)qj : 0.5 * (double)qt + 1.0) : (double)qt;
-                for (int st = 0; st < P.logn1; ++st) m += (double)qt * (0.5 + m * 4.440892098500626e-16);
-                if (!(m * 1.0000001 < 140737488355328.0)) continue;
-                (direct ? pd[j].k2_direct : pd[j].k2_lift) |= (u64)1 << t;
-            }
+        k2_lift_masks(P, pd.data());
         d_primes_ = upload_owned(pd.data(), n_all);
-        std::vector<FloorConst> fc(K * K);
-        for (size_t s = 0; s < K; ++s)
-            for (size_t i = 0; i < K; ++i) {
-                FloorConst &f = fc[s * K + i];
-                std::memset(&f, 0, sizeof(f));
-                if (s == i) continue;
-                const u64 qi = P.primes[i].q, qs = P.primes[s].q;
-                const u64 inv = Params::invmod(qs % qi, qi);
-                f.inv = inv;
-                f.inv_shoup = pre_word(inv, qi, P.primes[i].fold); // the u64 engine's companion word (Shoup quotient, or inv 2^32 mod q_i)
-                f.inv_d = (double)inv;
-                f.inv_i = (double)inv / (double)qi;
-                f.half_mod = (qs >> 1) % qi;
-                f.src_mod = qs % qi;
-            }
-        d_floor_ = upload_owned(fc.data(), K * K);
+        d_floor_ = upload_owned(floor_const_table(P).data(), K * K);
         env_.primes = d_primes_;
         env_.floor_consts = d_floor_;
         env_.N = (int)N; env_.logn1 = P.logn1; env_.K = (int)K; env_.Ltop = (int)P.Ltop; env_.scheme = P.scheme;
@@ -255,10 +220,11 @@ private:
         env_.u64_fold = P.u64_fold;
         const char *ds = std::getenv("HE355_DUAL_STREAM");
         if (ds) dual_stream_ = ds[0] != '0';
+        lim_.N = N; lim_.K = (int)K;
         u64 v = 0;
         if (env_u64("HE355_LATENCY_MAX", v)) set_latency_max(v);
         if (env_u64("HE355_LDS_MAX", v)) set_lds_max(v);
-        if (env_u64("HE355_CHUNK", v) && v > 0) chunk_ = (size_t)v;
+        if (env_u64("HE355_CHUNK", v) && v > 0) lim_.chunk = (size_t)v;
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_));
         cus_ = cus > 0 ? (u64)cus : 1;
@@ -316,28 +282,25 @@ public:
         return PoolBlock(pool_, bytes);
     }
     DevicePool::Stats alloc_stats() const { return pool_.stats(); }
+    // the one read of a counter block (every *_stats call): its value, and the block back at zero where the caller asks
+    template <class S> static S take_stats(S &counters, bool reset)
+    {
+        const S s = counters;
+        if (reset) counters = S{};
+        return s;
+    }
     // which shape / schedule the key switches of this context took (he355_path_stats): counted per kernel sequence (one chunk of a batch)
-    he355_path_stats_t path_stats(bool reset)
-    {
-        const he355_path_stats_t s = paths_;
-        if (reset) paths_ = he355_path_stats_t{};
-        return s;
-    }
+    he355_path_stats_t path_stats(bool reset) { return take_stats(paths_, reset); }
     // which route the BFV PIR calls of this context took (he355_bfv_route_stats): counted on the host where the calls branch, read by no launch
-    he355_bfv_route_stats_t bfv_route_stats(bool reset)
-    {
-        const he355_bfv_route_stats_t s = routes_;
-        if (reset) routes_ = he355_bfv_route_stats_t{};
-        return s;
-    }
+    he355_bfv_route_stats_t bfv_route_stats(bool reset) { return take_stats(routes_, reset); }
     size_t pool_trim() { sync(); return pool_.trim(); }
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
     const KernelEnv &env() const { return env_; }
-    void set_chunk(size_t c) { chunk_ = c ? c : 1; }
-    void set_latency_max(u64 n) { lat_auto_ = n == ~(u64)0; lat_max_ = lat_auto_ ? 0 : n; } // ~0: back to lat_limit()'s rule
+    void set_chunk(size_t c) { lim_.chunk = c ? c : 1; }
+    void set_latency_max(u64 n) { lim_.set_latency_max(n); } // ~0: back to lat_limit()'s rule
     void set_level_walk(bool on) { level_walk_ = on; }
-    void set_lds_max(u64 n) { lds_auto_ = n == ~(u64)0; lds_max_ = lds_auto_ ? 0 : n; }
+    void set_lds_max(u64 n) { lim_.set_lds_max(n); }
 
     size_t key_elems() const { return P.Ltop * 2 * P.K * P.N; }
     size_t n_q_primes() const
@@ -460,8 +423,8 @@ public:
     }
     he355_hoist_stats_t hoist_stats(bool reset)
     {
-        const he355_hoist_stats_t s = hoist_;
-        if (reset) { hoist_ = he355_hoist_stats_t{}; hoist_.key_bytes = s.key_bytes; } // (the bytes are a level, not a count)
+        const he355_hoist_stats_t s = take_stats(hoist_, reset);
+        hoist_.key_bytes = s.key_bytes; // (the bytes are a level, not a count)
         return s;
     }
     const uint32_t *perm(uint32_t elt)
@@ -538,12 +501,6 @@ public:
         u64 *rlr; // [C][3][N]  tail of the rescale prime after the inverse row pass
         u64 *f;   // [C][3][L][N]
     };
-    // layout of the scratch arena (one per stream) for `c` ops at level L
-    size_t scratch_words_per_op(int L) const
-    {
-        const size_t N = P.N, LN = (size_t)L * N;
-        return 2 * LN + LN + LN + (size_t)(L + 1) * LN + 2 * LN + 2 * N + 2 * N + 2 * LN + 3 * N + 3 * LN;
-    }
     // ---- the context's grow-on-demand device buffers (Arena, device_pool.h), one per use: which buffer serves which call is fixed
     enum { kScratch0, kScratch1, // key-switch scratch, one per stream (scratch())
            kLat0, kLat1,         // partial sums of the digit-split K3 (latency shape), one per stream: chunks of the two are in flight together
@@ -584,28 +541,20 @@ public:
             return false;
         }
     }
-    // the one halving loop: c, halved until fits(c) says yes; 0 when not even one fits
-    template <class F> static size_t halve_until_fit(size_t c, F &&fits)
-    {
-        for (;; c = (c + 1) / 2) {
-            if (fits(c)) return c;
-            if (c == 1) return 0;
-        }
-    }
-    // Ciphertexts per chunk for a batch of n at level L: chunk_ (default 1024, HE355_CHUNK / he355_set_chunk), halved until the scratch
+    // Ciphertexts per chunk for a batch of n at level L: lim_.chunk (default 1024, HE355_CHUNK / he355_set_chunk), halved until the scratch
     // arena(s) it needs -- two when the batch is cut and the chunks alternate between the streams -- are RESERVED (try_reserve: growing one
     // arena frees only that one).  On return scratch(c, L, which) does not allocate.
     size_t chunk_ops(u64 n, int L, bool may_dual)
     {
-        const size_t per_op = scratch_words_per_op(L) * 8;
-        const size_t c = halve_until_fit(std::min<u64>(chunk_, n ? n : 1), [&](size_t k) { return try_reserve(&arena_[kScratch0], (may_dual && n > k) ? 2 : 1, per_op * k, k == 1); });
+        const size_t per_op = scratch_words_per_op(P.N, L) * 8;
+        const size_t c = halve_until_fit(std::min<u64>(lim_.chunk, n ? n : 1), [&](size_t k) { return try_reserve(&arena_[kScratch0], (may_dual && n > k) ? 2 : 1, per_op * k, k == 1); });
         if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the key-switch scratch of one ciphertext (" + std::to_string(per_op) + " bytes) does not fit");
         return c;
     }
     Scratch scratch(size_t c, int L, int which = 0)
     {
         const size_t N = P.N, LN = (size_t)L * N;
-        const size_t per_op = scratch_words_per_op(L);
+        const size_t per_op = scratch_words_per_op(N, L);
         Scratch s;
         u64 *p = reserve(arena_[kScratch0 + which], per_op * c * 8);
         s.ks.c01 = p; p += c * 2 * LN; s.ks.c01_item_stride = 2 * LN;
@@ -621,71 +570,20 @@ public:
         return s;
     }
 
-    // The fused mod-down runs the special prime's tiles as a launch of their own, ahead of the data primes' (their epilogue needs its
-    // result): n1 rows x nc / 8 op-groups of blocks.  With a handful of ciphertexts at a small ring that launch is a few dozen blocks
-    // on 256 CUs -- as long as the data primes' launch and nearly idle -- and the unfused sequence (every prime's tiles in ONE launch,
-    // then the two floor kernels) is the shorter chain: fused from 128 such blocks up.
-    bool fuse_pays(const KernelEnv &e, u64 nc, int L) const
-    {
-        // ... or from 1536 (tile, op-group) units of the data primes' launch up: at L = 16 that launch is 16 times the special prime's, and what
-        // the fused epilogue saves (the sums' trip through HBM, k_floor_rows) outweighs the idle launch ahead of it from 17 ciphertexts on at
-        // N = 2^15 instead of 25 (batch 20 / 24 of the headline shape: 1.64 -> 1.45 / 1.79 -> 1.52 ms, DotProduct -9 %; profiles/r05_latency_boundary.txt)
-        const u64 sp_blocks = ((u64)1 << e.logn1) * ((nc + 7) / 8);
-        return sp_blocks >= 128 || sp_blocks * (u64)L >= 1536;
-    }
-    // he355_rotate_sum: the level's sum formed by k_k3 itself (KsGroups::sum_out).  The launch then has (tiles x n / 8) blocks however many
-    // groups the level has, so it needs enough of them to fill the chip, groups of a multiple of eight ciphertexts, the fused path for
-    // every chunk, and counts that leave bit 31 free.
-    bool level_sum_pays(const KernelEnv &e, int L, u64 n) const
-    {
-        if (n % 8 || !k3_can_fuse(e) || !fuse_pays(e, n, L) || (u64)chunk_ < n) return false; // (a launch holds whole groups, and takes the fused path)
-        return (((u64)L << e.logn1) * (n / 8)) >= 512;                                      // blocks of the data-prime launch
-    }
-    // latency shape of the key switch: batches of at most lat_limit() ciphertexts, CKKS pipeline
-    // digit groups per fp64-engine tile (480 tiles x 4 single-wave blocks fill the chip once at batch 1), per u64-engine tile (64 tiles, rows
-    // 2.5x as long), blocks per column for the targets of k_k2n / k_floor_colsn
-    static constexpr int kLatTargets = 8;
-    // Digit groups per tile of the latency shape (n_split > 1 is what selects the shape).  fp64-engine
-    // tiles: 480 x 2 single-wave blocks are ONE round of the chip's 1024 one-wave slots, 480 x 4 were two rounds of half the work each with
-    // twice the start-ups and partial sums (batch 1: 0.326 -> 0.312 ms, batch 8: 0.98 -> 0.91 ms; 3 and 8 groups measured slower).
-    static constexpr int kLatSplit = 2, kLatSplitU64 = 8;
-    // Where the latency shape stops paying is a matter of rows, not of ciphertexts: the throughput kernels fill the chip from about 2^17
-    // coefficients per residue on (profiles/r05_latency_boundary.txt: N = 2^15 crosses between 4 and 5 ciphertexts at depth 6 and 16, 2^14
-    // between 6 and 8, 2^13 at 12), so the default limit is 2^17 / N ciphertexts, at most 12; he355_set_latency_max replaces it.
-    u64 lat_limit() const { return lat_auto_ ? std::min<u64>(12, std::max<u64>(1, ((u64)1 << 17) / P.N)) : lat_max_; }
-    // ... for a kernel environment (a BFV context runs its rotation chains in the NTT domain on the CKKS pipeline: batch_env(0, true))
-    bool latency_shape(const KernelEnv &e, u64 nc) const { return e.scheme == kSchemeCKKS && nc <= lat_limit() && P.K >= 2; }
-    // Ring-in-LDS shape (he355_kernels_lds.hip): N <= 8192, L <= 6, NTT-domain pipeline, batches up to lds_limit() -- two
-    // launches of L^2 + 2L one-polynomial workgroups per ciphertext instead of six launches through HBM.  Where the throughput shape's
-    // better use of the chip overtakes it was measured (profiles/r06_lds_shape.txt); he355_set_lds_max / HE355_LDS_MAX replace the rule.
-    // The rule: while k_lds_digits' grid, (L + 1) L blocks per ciphertext, runs in at most one and a half rounds of the chip -- 256 CUs, one
-    // 8-wave block each at N = 8192 (two, four, eight blocks per CU for the smaller rings): 64 ciphertexts at {60, 40, 60} (32: 61 against 78 us
-    // per key switch, 64: 89 against 95, 96: 131 against 113), 32 at {60, 40, 40, 60}; beyond that the HBM throughput shapes use the chip
-    // better (profiles/r06_lds_shape.txt; a "one inverse transform, every target" form of the kernels for larger batches was built, bit-exact,
-    // and lost everywhere: same file, tools/patches/r06_lds_source_major.patch).  he355_set_lds_max / HE355_LDS_MAX replace the rule.
-    u64 lds_limit(const KernelEnv &e, int L) const
-    {
-        if (!lds_auto_) return lds_max_;
-        const u64 blocks = (u64)384 << (3 - std::min(3, e.logn1));
-        return std::max<u64>(1, blocks / ((u64)(L + 1) * (u64)L));
-    }
-    // (also the test of he355_rescale's two-launch form)
-    bool lds_shape(const KernelEnv &e, int L, u64 nc) const { return e.scheme == kSchemeCKKS && ks_lds_supported(e, L) && nc <= lds_limit(e, L); }
+    // The shape rules (ks_shape.h) for a kernel environment of this context -- a BFV context's batch_env(0, true) is on the CKKS pipeline
+    bool fuse_pays(const KernelEnv &e, u64 nc, int L) const { return he355::fuse_pays(ks_dims(e), nc, L); }
+    bool level_sum_pays(const KernelEnv &e, int L, u64 n) const { return he355::level_sum_pays(ks_dims(e), lim_, L, n); }
+    bool latency_shape(const KernelEnv &e, u64 nc) const { return he355::latency_shape(ks_dims(e), lim_, nc); }
+    bool lds_shape(const KernelEnv &e, int L, u64 nc) const { return he355::lds_shape(ks_dims(e), lim_, L, nc); }
+    KsShape ks_shape(const KernelEnv &e, int L, u64 nc, KsKind kind, bool out_apart) const { return he355::ks_shape(ks_dims(e), lim_, L, nc, kind, out_apart); }
     // scratch of the shape: the arena behind c01 holds k_lds_digits' partial products, (2L + 4) L N words per ciphertext, for every L <= 6
     u64 *lds_part(const Scratch &S, int L) const
     {
-        const size_t need = (size_t)ks_lds_part_words(env_, L), have = scratch_words_per_op(L) - 2 * (size_t)L * P.N;
+        const size_t need = (size_t)ks_lds_part_words(env_, L), have = scratch_words_per_op(P.N, L) - 2 * (size_t)L * P.N;
         if (need > have) throw std::logic_error("ring-in-LDS key switch: the arena is too small for the partial products");
         return S.ks.c2n;
     }
 
-    // What a key switch switches.  key_switch_batch alone turns it into k_k1's flags, K3Fuse's operand fields and LdsKsOperands.
-    enum class KsKind {
-        Product, // a * b of two size-2 ciphertexts: a, b [.][2][L][N], result r takes a[idx_a(ix, r)], b[idx_b(ix, r)] (he355_multiply_relin)
-        Size3,   // a [n][3][L][N]: c2 switched, added into (c0, c1) (he355_relinearize)
-        Galois,  // a [n][2][L][N] under element elt (table: its NTT-domain permutation or coefficient-form gather), out = addend + galois(a)
-        Grouped, // a [.][2][L][N] in groups of groups.group_size ciphertexts, per-group elements and keys (he355_rotate_sum, rotate_each)
-    };
     struct KsSource {
         KsKind kind;
         const u64 *a = nullptr, *b = nullptr;
@@ -697,22 +595,6 @@ public:
         KsGroups groups{};
         bool coeff = false;          // a BFV context's coefficient-form ciphertexts (else the NTT-domain pipeline)
     };
-    enum class KsShape { Lds, Latency, Fused, Unfused, BfvCoeff };
-    // The shape of one chunk's key switch: the whole rule.  The first row that holds:
-    //   BfvCoeff | e.scheme is BFV: coefficient-form ciphertexts of a BFV context (the BFV kernels; no he355_path_stats counter)
-    //   Lds      | not grouped, out_apart, lds_shape(e, L, nc): CKKS / NTT-domain pipeline, ks_lds_supported(e, L), nc <= lds_limit(e, L)
-    //   Latency  | not grouped, latency_shape(e, nc)
-    //   Fused    | k3_can_fuse(e), fuse_pays(e, nc, L)  (and c01 a slab [nc][2][L][N] of its own: key_switch_batch always lays it out so)
-    //   Unfused  | otherwise
-    // out_apart: `out` shares no word with a product's operands or a size-3 input (a rotation may add into `out`: always apart).  k_k3 forms
-    // c0, c1 itself (K3Fuse operands, k_k1 does not write them) exactly when the shape is Fused and out_apart.
-    KsShape ks_shape(const KernelEnv &e, int L, u64 nc, KsKind kind, bool out_apart) const
-    {
-        if (e.scheme != kSchemeCKKS) return KsShape::BfvCoeff;
-        if (kind != KsKind::Grouped && out_apart && lds_shape(e, L, nc)) return KsShape::Lds;
-        if (kind != KsKind::Grouped && latency_shape(e, nc)) return KsShape::Latency;
-        return k3_can_fuse(e) && fuse_pays(e, nc, L) ? KsShape::Fused : KsShape::Unfused;
-    }
     // the kernel environment of a batch on stream `which`
     // ntt: the NTT-domain (CKKS) pipeline whatever the context's scheme (a BFV context's tables are the same primes; only the data
     // representation differs)
@@ -1064,22 +946,7 @@ public:
         });
         HIPCHECK(hipGetLastError());
     }
-    // What he355_linear_transform_bsgs takes from the pool at a chunk of `c` ciphertexts: the baby store, [slots][c][2][L + 1][N], and the two
-    // Q P blocks (the inner sum of a keyed giant row; the giant accumulator), [c][2][L][N] + [c][2][N] each -- in the pool's size classes.
-    static size_t bsgs_block_bytes(size_t c, int L, size_t N) { return DevicePool::size_class(c * 2 * (size_t)(L + 1) * N * 8); }
-    static size_t bsgs_store_bytes(size_t slots, size_t c, int L, size_t N) { return DevicePool::size_class(slots * c * 2 * (size_t)(L + 1) * N * 8); }
-    // he355_linear_transform_bsgs_scratch_bytes: the most a call with n_baby baby steps takes from the pool -- every baby used, the chunk the
-    // batch chunk (chunk_ops may only shorten it).  0 where the call does nothing or is refused (more than 2^20 babies are more than 2^20
-    // pairs); formed in 128 bits and saturated, so a huge batch cannot wrap into a small bound.
-    static u64 bsgs_scratch_bytes(size_t chunk, const Params &p, int L, u64 n, u64 n_baby)
-    {
-        const u64 c = std::min<u64>(chunk, n);
-        if (!c || !n_baby || n_baby > ((u64)1 << 20)) return 0;
-        const u128 block = (u128)c * 2 * (u128)(L + 1) * p.N * 8, cls = (u128)2 << 20; // (above 16 MiB the classes are multiples of 2 MiB: one more covers any rounding)
-        const u128 total = (u128)n_baby * block + cls + 2 * (block + cls);
-        return total > ~(u64)0 ? ~(u64)0 : (u64)total;
-    }
-    size_t chunk_limit() const { return chunk_; }
+    size_t chunk_limit() const { return lim_.chunk; }
     // The baby-step/giant-step linear transform on the hoisted rotations (the definition: include/he355.h).  Per chunk: ONE digit lift of the
     // input, per used keyed baby launch_k3 and the rotate kernel into the baby store (T_i = sigma(S_i) with P sigma(c0) folded in; the
     // identity: (P c0, P c1), streaming); then per used giant row the inner sum over its used terms -- straight into the accumulator for the
@@ -1238,12 +1105,7 @@ public:
             }
         }
     }
-    he355_poly_stats_t poly_stats(bool reset)
-    {
-        const he355_poly_stats_t s = poly_;
-        if (reset) poly_ = he355_poly_stats_t{};
-        return s;
-    }
+    he355_poly_stats_t poly_stats(bool reset) { return take_stats(poly_, reset); }
     // he355_ckks_mod_raise: row 0 of every polynomial copied on the stream, then chunk by chunk (the key-switch chunk, in ciphertexts) the
     // inverse row pass of row 0 into a compact tail [nc size][N] from the pool (k_rows_inv_select, prime 0), the fused column kernel
     // (k_raise_cols; N = 1024 has no column pass: k_raise_lift on the finished coefficients) and the forward row pass over rows 1 .. L_to - 1
@@ -1254,9 +1116,9 @@ public:
         use();
         const size_t N = P.N;
         ++raise_.calls;
-        const u64 chunk = std::min<u64>(chunk_, n);
+        const u64 chunk = std::min<u64>(lim_.chunk, n);
         const PoolBlock tail = L_to > 1 ? scoped_block((size_t)chunk * size * N * 8) : PoolBlock();
-        const bool split_on = lat_auto_ || lat_max_ > 0;
+        const bool split_on = lim_.lat_auto || lim_.lat_max > 0;
         for (u64 off = 0; off < n; off += chunk) {
             const u64 np = std::min<u64>(chunk, n - off) * (u64)size;
             const u64 *src = in + off * size * (size_t)L_in * N;
@@ -1290,12 +1152,7 @@ public:
         launch_raise_lift(env_, L_to, 0, n_polys, coeff, out);
         HIPCHECK(hipGetLastError());
     }
-    he355_raise_stats_t raise_stats(bool reset)
-    {
-        const he355_raise_stats_t s = raise_;
-        if (reset) raise_ = he355_raise_stats_t{};
-        return s;
-    }
+    he355_raise_stats_t raise_stats(bool reset) { return take_stats(raise_, reset); }
     // plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N]: the rows copied and row L = NTT_P of the coefficients of row 0, centred
     // (he355_plain_extend_special).  mismatch (optional, one device word): the (coefficient, prime >= 1) pairs that disagree with row 0.
     void plain_extend_special(int L, u64 n, const u64 *plain_ntt, u64 *plain_qp, u64 *mismatch)
@@ -1758,9 +1615,9 @@ public:
     he355_bfv_multiply_stats_t bfv_multiply_stats(bool reset)
     {
         use();
-        he355_bfv_multiply_stats_t s = mul_routes_;
-        s.lds_limit = behz_cols_lds_limit(env_);
-        if (reset) mul_routes_ = he355_bfv_multiply_stats_t{};
+        const auto lds_limit = behz_cols_lds_limit(env_);
+        he355_bfv_multiply_stats_t s = take_stats(mul_routes_, reset);
+        s.lds_limit = lds_limit;
         return s;
     }
     // out(i, j) = sum_k relinearize(multiply(a(i, k), b(k, j))): the multiply / relinearize_inplace / add_inplace loop of the BFV
@@ -1839,34 +1696,26 @@ public:
         const bool fuse_cols = behz_cols_fusable(env_, Z);
         BehzSrc src{};
         src.a = a; src.b = b; src.ix = ix;
-        // Distinct operands: result r = (g, i, j) reads a(g, i) and b(g, j).  Where every operand serves several results (outer products,
-        // the terms of a matrix product) each is extended to Bsk and transformed ONCE (steps (1)-(3) per operand instead of per result:
-        // SEAL's multiply recomputes them for every pair, the values are the same), and a result costs its dyadic tensor, three inverse
-        // transforms and steps (6)-(8).
-        const u64 gsz = std::min<u64>(ix.gs, n), G = ix.gs >= n ? 1 : (n + ix.gs - 1) / ix.gs;
-        src.I = (gsz + ix.b1 - 1) / ix.b1; src.J = std::min<u64>(ix.b1, gsz); src.na = G * src.I;
-        const u64 n_cts = src.na + G * src.J;
-        const size_t e_words = (size_t)n_cts * 2 * (L + S) * N, per_res = (3 * L + 3 * S) * N;
-        {   // a chunk's results are written before the next chunk's operands are read: `out` needs a slab of its own
-            const size_t a_cts = (size_t)(ix.a_base + (G - 1) * ix.a_sg + (src.I - 1) * ix.a_si + 1), b_cts = (size_t)(ix.b_base + (G - 1) * ix.b_sg + (src.J - 1) * ix.b_sj + 1);
-            if (ranges_overlap(out, (size_t)n * 3 * L * N, a, a_cts * 2 * L * N) || ranges_overlap(out, (size_t)n * 3 * L * N, b, b_cts * 2 * L * N))
-                throw std::invalid_argument("he355_bfv_multiply: `out` overlaps an operand");
-        }
-        bool lists = (G == 1 || (n % ix.gs == 0 && ix.gs % ix.b1 == 0)) && n_cts <= n; // at least two times fewer extensions than the 2 n of the per-pair path
+        const BehzLists g = behz_lists(ix, n, L, S, N); // the distinct operands and the words either path takes (behz_lists.h)
+        src.I = g.I; src.J = g.J; src.na = g.na;
+        // a chunk's results are written before the next chunk's operands are read: `out` needs a slab of its own
+        if (ranges_overlap(out, (size_t)n * 3 * L * N, a, g.a_cts * 2 * L * N) || ranges_overlap(out, (size_t)n * 3 * L * N, b, g.b_cts * 2 * L * N))
+            throw std::invalid_argument("he355_bfv_multiply: `out` overlaps an operand");
+        bool lists = g.may_list;
         Arena &arena = arena_[kBfv];
-        size_t c = std::min<size_t>(chunk_, (size_t)n);
+        size_t c = std::min<size_t>(lim_.chunk, (size_t)n);
         if (lists) {
-            const size_t cl = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, (e_words + per_res * k) * 8); });
+            const size_t cl = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, (g.e_words + g.per_res * k) * 8); });
             lists = cl != 0; // else: the operand set does not fit beside one result -- per-pair path below, from one result per chunk
             c = lists ? cl : 1;
         }
         if (lists) {
             src.lists = 1;
             ++mul_routes_.calls_lists;
-            u64 *eq = arena.p, *eb = eq + (size_t)n_cts * 2 * L * N, *dq = eb + (size_t)n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
-            behz_extend_fwd_cols(Z, src, fuse_cols, n_cts, eq, eb, vq, vb);
-            vq.base = eq; launch_rows_fwd(env_, vq, (u32)(n_cts * 2));
-            vb.base = eb; launch_rows_fwd(env_, vb, (u32)(n_cts * 2));
+            u64 *eq = arena.p, *eb = eq + (size_t)g.n_cts * 2 * L * N, *dq = eb + (size_t)g.n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
+            behz_extend_fwd_cols(Z, src, fuse_cols, g.n_cts, eq, eb, vq, vb);
+            vq.base = eq; launch_rows_fwd(env_, vq, (u32)(g.n_cts * 2));
+            vb.base = eb; launch_rows_fwd(env_, vb, (u32)(g.n_cts * 2));
             for (u64 off = 0; off < n; off += c) {
                 const u64 nc = std::min<u64>(c, n - off);
                 ++mul_routes_.chunks;
@@ -1876,8 +1725,7 @@ public:
             HIPCHECK(hipGetLastError());
             return;
         }
-        const size_t per_op = (4 * L + 4 * S) * N + per_res;
-        c = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, per_op * k * 8); });
+        c = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, g.per_op * k * 8); });
         if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the BFV multiply scratch of one ciphertext does not fit");
         ++mul_routes_.calls_pairs;
         u64 *xq = arena.p, *xb = xq + c * 4 * L * N, *dq = xb + c * 4 * S * N, *ds = dq + c * 3 * L * N;
@@ -2484,30 +2332,11 @@ public:
     const CrtTablesDev &crt_tables(int L)
     {
         return per_level(crt_, L, [&] {
-            // one block: Q | floor(Q / 2) | the L punctured products (`words` words each) | their inverses mod q_i
-            const int words = L + 2;
-            const size_t o_half = words, o_punct = 2 * (size_t)words, o_inv = o_punct + (size_t)L * words;
-            std::vector<u64> h(o_inv + L, 0);
-            u64 *Q = h.data(), *halfQ = Q + o_half;
-            Q[0] = 1;
-            for (int i = 0; i < L; ++i) client::mw_mul_small(Q, words, P.primes[i].q);
-            for (int i = 0; i < words; ++i) halfQ[i] = (Q[i] >> 1) | (i + 1 < words ? Q[i + 1] << 63 : 0);
-            for (int i = 0; i < L; ++i) {
-                u64 *p = h.data() + o_punct + (size_t)i * words;
-                p[0] = 1;
-                u64 pm = 1;
-                const u64 qi = P.primes[i].q;
-                for (int k = 0; k < L; ++k)
-                    if (k != i) {
-                        client::mw_mul_small(p, words, P.primes[k].q);
-                        pm = (u64)(((u128)pm * (P.primes[k].q % qi)) % qi);
-                    }
-                h[o_inv + i] = Params::invmod(pm, qi);
-            }
-            const u64 *d = upload_owned(h.data(), h.size());
+            const CrtTablesHost c = crt_tables_host(P, L); // one block (device_tables.h)
+            const u64 *d = upload_owned(c.h.data(), c.h.size());
             CrtTablesDev t;
-            t.L = L; t.words = words; t.Q = d; t.halfQ = d + o_half; t.punct = d + o_punct; t.inv = d + o_inv;
-            t.Qd = client::mw_to_double(Q, words); t.t = P.plain_modulus;
+            t.L = L; t.words = c.words; t.Q = d; t.halfQ = d + c.o_half; t.punct = d + c.o_punct; t.inv = d + c.o_inv;
+            t.Qd = c.Qd; t.t = P.plain_modulus;
             return t;
         });
     }
@@ -2551,7 +2380,7 @@ public:
     u64 noise_chunk(u64 n) const
     {
         const u64 by_ring = std::min<u64>(1024, std::max<u64>(64, ((u64)1 << 21) / P.N));
-        return std::max<u64>(1, std::min<u64>(n, std::min<u64>(by_ring, chunk_)));
+        return std::max<u64>(1, std::min<u64>(n, std::min<u64>(by_ring, lim_.chunk)));
     }
     void bfv_noise_budget(int L, int size, u64 n, const u64 *ct, int32_t *budget, int32_t *noise_bits)
     {
@@ -2609,7 +2438,7 @@ public:
         if (!n) return;
         if (!bytes || !plain) throw std::invalid_argument("he355_bfv_reply_decrypt: null replies or null plaintext output");
         const size_t N = P.N;
-        const u64 cmax = std::max<u64>(1, std::min<u64>(n, std::min<u64>(64, chunk_)));
+        const u64 cmax = std::max<u64>(1, std::min<u64>(n, std::min<u64>(64, lim_.chunk)));
         u64 *prod = client_scratch(cmax * N);
         int32_t *bits = budget ? budget : noise_bits;
         if (bits) HIPCHECK(hipMemsetAsync(bits, 0, n * sizeof(int32_t), stream_));
@@ -2729,20 +2558,6 @@ public:
         HIPCHECK(hipMemcpyAsync(&err, d_err_, sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
         if (err) throw std::invalid_argument("encoded values are too large");
-    }
-    // the slot ranges of a decode call, checked against the encoder's slot count (ranges == null: every slot)
-    SlotRanges slot_ranges(const u64 *ranges, u64 n_ranges, u64 slots) const
-    {
-        SlotRanges sr{};
-        if (!ranges) { sr.n = 1; sr.first[0] = 0; sr.count[0] = sr.total = (u32)slots; return sr; }
-        if (n_ranges < 1 || n_ranges > (u64)kMaxSlotRanges) throw std::invalid_argument("decode: 1 to 4 slot ranges");
-        sr.n = (u32)n_ranges;
-        for (u64 g = 0; g < n_ranges; ++g) {
-            const u64 first = ranges[2 * g], count = ranges[2 * g + 1];
-            if (first > slots || count > slots - first) throw std::invalid_argument("decode: slot range outside the encoder's slots");
-            sr.first[g] = (u32)first; sr.count[g] = (u32)count; sr.total += (u32)count;
-        }
-        return sr;
     }
     // CKKSEncoder::decode: [n][L][N] NTT-form plaintexts -> [n][total] real slot values (ranges == null: all N/2)
     void ckks_decode(int L, u64 n, const u64 *plain, double scale, double *out, const u64 *ranges = nullptr, u64 n_ranges = 0)
@@ -2876,8 +2691,7 @@ private:
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     KernelEnv env_{};
     PrimeDev *d_primes_ = nullptr;
-    u64 lat_max_ = 0;              // largest batch that takes the latency shape once set (HE355_LATENCY_MAX; 0: never) ...
-    bool lat_auto_ = true;         // ... until then lat_limit()'s rule
+    KsLimits lim_; // what the shape rules read of this context (ks_shape.h): its ring and chain, the latency / LDS limits, the chunk
     FloorConst *d_floor_ = nullptr;
     std::vector<void *> owned_;
     u64 *d_relin_ = nullptr;
@@ -2911,12 +2725,9 @@ private:
     u64 cus_ = 1; // compute units of the device (the small-batch split of the modulus raise)
     he355_bfv_route_stats_t routes_{};
     he355_bfv_multiply_stats_t mul_routes_{};
-    bool lds_auto_ = true; // lds_limit()'s rule until set_lds_max (HE355_LDS_MAX)
-    u64 lds_max_ = 0;
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
     size_t groups_next_ = 0; // upload_groups: the next free byte of the kGroups ring
     std::map<int, BehzDev> behz_;
-    size_t chunk_ = 1024;
     DevicePool pool_;
 };
 
@@ -3584,7 +3395,7 @@ int he355_linear_transform_bsgs(he355_ctx *c, int L, uint64_t n, const uint64_t 
 uint64_t he355_linear_transform_bsgs_scratch_bytes(const he355_ctx *c, int L, uint64_t n, uint64_t n_baby)
 {
     if (!c || L < 1 || (size_t)L > c->params->Ltop) return 0;
-    return DeviceContext::bsgs_scratch_bytes(c->dev ? c->dev->chunk_limit() : 1024, *c->params, L, n, n_baby);
+    return bsgs_scratch_bytes(c->dev ? c->dev->chunk_limit() : 1024, *c->params, L, n, n_baby);
 }
 int he355_plain_extend_special(he355_ctx *c, int L, uint64_t n, const uint64_t *plain_ntt, uint64_t *plain_qp, uint64_t *mismatch)
 {

@@ -14,17 +14,9 @@
 #include "bfv_bytes_core.h"
 #include "bfv_reply_core.h"
 #include "bfv_gadget_core.h"
+#include "ks_shape.h"
 
 namespace he355 {
-
-// Per (source prime s, target prime i) constants of the RNS divide-and-round ("floor") step used by the
-// key-switch mod-down (s = special prime) and by rescale (s = last data prime).  Device array [K][K].
-struct FloorConst {
-    u64 inv, inv_shoup;   // s^-1 mod q_i (+ Shoup quotient)
-    double inv_d, inv_i;  // same for the fp64 engine: value and fl(value/q_i)
-    u64 half_mod;         // floor(s/2) mod q_i
-    u64 src_mod;          // s mod q_i
-};
 
 // Optional HIP-event probe around the launches of the dominant kernel (k_k3, fp64 engine): bench.py reports that
 // kernel's average launch duration from inside the timed region (events on the stream the kernel runs on).
@@ -141,8 +133,9 @@ struct K3Fuse {
     const uint32_t *gperm = nullptr;
     u64 gsrc_op_offset = 0;
 };
-// The fused mod-down (CKKS only); whether it pays for a batch is fuse_pays' rule (he355_api.hip).
-inline bool k3_can_fuse(const KernelEnv &env) { return env.scheme == 2 && env.K >= 2; }
+// the dimensions of an environment the shape rules read (ks_shape.h), and k3_can_fuse over them
+inline KsDims ks_dims(const KernelEnv &env) { return KsDims{env.scheme, env.logn1, env.K}; }
+inline bool k3_can_fuse(const KernelEnv &env) { return k3_can_fuse(ks_dims(env)); }
 // floor step, row half: out[(op,k,i)] = (tsrc[(op,k,i)] - NTT(dst_cols[(op,k,i)])) * s^-1 (+ addend) mod q_i.
 // Strides are in u64 elements.  If tail_prime >= 0 the rows of that prime additionally go through the
 // inverse row pass into tail[(op,k)] (next floor step's source).
@@ -187,15 +180,6 @@ struct LdsKsOperands {
     u64 op_offset = 0;
     const uint32_t *perm = nullptr;
     unsigned char perm_src_row[32] = {}; // LDSKS_GALOIS: the ONE source row row a of the permuted polynomial comes from (perm[a * 1024] >> 10; Params::galois_perm_ntt)
-};
-
-// the slots a decode writes per plaintext: up to kMaxSlotRanges ranges [first, first + count) of the slot vector, written one after the other
-// (out row = `total` values).  A workload's decode() reads the first n / dim3 slots of a result -- and BFV MatMultRow those of both batching rows
-// (bfv row .cpp:339-369) -- not the N/2 or N the encoder has
-constexpr int kMaxSlotRanges = 4;
-struct SlotRanges {
-    u32 n, total;
-    u32 first[kMaxSlotRanges], count[kMaxSlotRanges];
 };
 
 // ---- the launchers: two builds of the device code -----------------------------------------------------------------------

@@ -545,8 +545,7 @@ template <int LOGN1> void launch_ks_lds_n(const KernelEnv &env, const LdsKsArgs 
 
 } // namespace
 
-// (L <= 6: the partial products, (2L + 4) L N words per ciphertext, live in the key-switch arena behind c01 -- (L + 10) L N words)
-bool ks_lds_supported(const KernelEnv &env, int L) { return env.logn1 >= 0 && env.logn1 <= 3 && L >= 1 && L <= 6 && env.K >= 2 && L <= env.K - 1; }
+bool ks_lds_supported(const KernelEnv &env, int L) { return he355::ks_lds_supported(ks_dims(env), L); }
 u64 ks_lds_part_words(const KernelEnv &env, int L) { return (u64)(L + 2) * 2 * (u64)L * (u64)env.N; }
 
 // CKKS rescale of n_ops size-`size` ciphertexts at level L (src: [size][L][N] per op, src_op_stride words apart) into out [n_ops][size][L-1][N]:

@@ -129,6 +129,22 @@ inline BsgsPlan plan_linear_transform_bsgs(const Params &p, int L, u64 n, const 
     if (ro.overlaps(word_range(w, plain_qp, (u64)plain_w))) throw std::invalid_argument(w + ": `d_out` overlaps `d_plain_qp`");
     return pl;
 }
+// What he355_linear_transform_bsgs takes from the pool at a chunk of `c` ciphertexts: the baby store, [slots][c][2][L + 1][N], and the two
+// Q P blocks (the inner sum of a keyed giant row; the giant accumulator), [c][2][L][N] + [c][2][N] each.  Raw bytes:
+// DevicePool::alloc rounds a request to its size class itself (device_pool.h, which needs HIP and is not included here).
+inline size_t bsgs_block_bytes(size_t c, int L, size_t N) { return c * 2 * (size_t)(L + 1) * N * 8; }
+inline size_t bsgs_store_bytes(size_t slots, size_t c, int L, size_t N) { return slots * c * 2 * (size_t)(L + 1) * N * 8; }
+// he355_linear_transform_bsgs_scratch_bytes: the most a call with n_baby baby steps takes from the pool -- every baby used, the chunk the
+// batch chunk (chunk_ops may only shorten it).  0 where the call does nothing or is refused (more than 2^20 babies are more than 2^20
+// pairs); formed in 128 bits and saturated, so a huge batch cannot wrap into a small bound.
+inline u64 bsgs_scratch_bytes(size_t chunk, const Params &p, int L, u64 n, u64 n_baby)
+{
+    const u64 c = std::min<u64>(chunk, n);
+    if (!c || !n_baby || n_baby > ((u64)1 << 20)) return 0;
+    const u128 block = (u128)c * 2 * (u128)(L + 1) * p.N * 8, cls = (u128)2 << 20; // (above 16 MiB the classes are multiples of 2 MiB: one more covers any rounding)
+    const u128 total = (u128)n_baby * block + cls + 2 * (block + cls);
+    return total > ~(u64)0 ? ~(u64)0 : (u64)total;
+}
 // he355_plain_extend_special: plain_ntt [n][L][N] -> plain_qp [n][L + 1][N].  True: n == 0, the call touches nothing.
 inline bool plan_plain_extend(const Params &p, int L, u64 n, const u64 *plain_ntt, const u64 *plain_qp)
 {

@@ -697,7 +697,7 @@ struct ArF64 {
 // ---- which launches may take ArF64's direct floor forms (host side; PrimeDev::acc_terms) ----------------------------------------
 // The forms are exact for |acc| <= kFloorAccMax and |x| <= kFloorXMax.  Both magnitudes follow from the prime and the number of
 // accumulated terms, by the growth rule of the fp64 butterfly the host already sizes the kernels' 48-bit rows with (the lift classes of
-// DeviceContext::init, he355_api.hip): a stage takes |.| <= m to m + q (1/2 + m 2^-51).
+// k2_lift_class, device_tables.h): a stage takes |.| <= m to m + q (1/2 + m 2^-51).
 //   x:   a correction row enters the forward column pass below 4q (a centred or canonical residue of the source prime, re-centred when
 //        the source is wider than 2q, plus at most one centred product of the merged second correction) and runs at most 5 column and
 //        10 row stages.

@@ -1,6 +1,6 @@
-"""The host-side kernel selection of the BEHZ multiply (`bfv_multiply3` in csrc/he355_api.hip, the `launch_behz_*` functions and
-`behz_cols_fusable` in csrc/he355_kernels.hip) restated in plain Python, in the manner of tests/launch_plan.py: it restates the rules, it
-does not link them.  Tests use it to (a) derive the batches that lie on both sides of every decision instead of guessing them and (b) assert
+"""The host-side kernel selection of the BEHZ multiply (`behz_lists` in csrc/behz_lists.h and `bfv_multiply3` in csrc/he355_api.hip, the
+`launch_behz_*` functions and `behz_cols_fusable` in csrc/he355_kernels.hip) restated in plain Python, in the manner of tests/launch_plan.py:
+it restates the rules, it does not link them (tests/test_bfv_multiply_plan_cpu.py holds `takes_lists` to the header).  Tests use it to (a) derive the batches that lie on both sides of every decision instead of guessing them and (b) assert
 the counters of `he355_bfv_multiply_stats` against a plan.  When the restatement and the product disagree, the product decides and this
 file is what gets corrected.
 
@@ -27,7 +27,7 @@ from dataclasses import dataclass
 
 K_WAVES = 4                      # kernel_common.inc
 DUAL_MAX_BLOCKS = 1024           # he355_kernels.hip: kDualMaxBlocks
-DEFAULT_CHUNK = 1024             # he355_api.hip: chunk_
+DEFAULT_CHUNK = 1024             # ks_shape.h: KsLimits::chunk
 LDS_NO_OPT_IN = 64 << 10         # what every HIP device grants a block without asking
 LDS_MI355X = 160 << 10           # CDNA4: the LDS of one CU, all of which one workgroup may take
 GS_ALL = 2 ** 64 - 1             # Indexer3::gs of an outer product (one group)
@@ -118,7 +118,7 @@ def levels(N: int, bits: tuple, plain_bits: int, force_u64: bool = False, seal_b
         sim.sim_behz_destroy(h)
 
 
-# ---- decision 1: the distinct-operand lists (bfv_multiply3) ------------------------------------------------------------------------------
+# ---- decision 1: the distinct-operand lists (behz_lists.h) ------------------------------------------------------------------------------
 def indexer(kind: str, b1: int = 1):
     """(gs, b1) of Context.pairwise() / Context.outer(.., b1) after to_ix3 (device_types.h)"""
     return (1, 1) if kind == "pairwise" else (GS_ALL, b1)

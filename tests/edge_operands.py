@@ -217,7 +217,7 @@ def _csim():
 
 def fits_48_bound(m0: float, q: float, logn1: int) -> float:
     """the worst-case magnitude after the forward column pass from inputs |x| < m0, as the host's lift classes
-    (DeviceContext::init, he355_api.hip) compute it: per stage m -> m + q (1/2 + m 2^-51); the 48-bit rows need it below 2^47"""
+    (k2_lift_class, csrc/device_tables.h) compute it: per stage m -> m + q (1/2 + m 2^-51); the 48-bit rows need it below 2^47"""
     m = m0
     for _ in range(logn1):
         m += q * (0.5 + m * 2.0 ** -51)

@@ -9,7 +9,7 @@ tests/golden/explicit_moduli.json, the pinned chains that sit on both sides of e
 
     engine        q < 2^47: the fp64 engine, else the u64 engine                                   (he_params.cpp, Params::build)
     fold form     every chain prime >= 2^47 is 2^60 - c with 0 < c < 2^26, else the Shoup form     (modarith.h, fold_prime_ok)
-    lift class    of (digit prime q_j, fp64 target q_t) in k_k2n: direct, lift or general          (he355_api.hip, DeviceContext::init)
+    lift class    of (digit prime q_j, fp64 target q_t) in k_k2n: direct, lift or general          (device_tables.h, k2_lift_class)
     direct floor  acc_terms of an fp64 prime: 0 above the x-bound, else floor(2^49 / term bound)   (modarith.h, floor_direct_terms)
     mac run       floor((2^128 - 1) / (q - 1)^2), capped at 2^16                                   (bfv_mac_core.h, bfv_mac_run)
 

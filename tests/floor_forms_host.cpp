@@ -2,39 +2,16 @@
 // (floor_fin*(acc_canon(acc), ...)) and the forms that take the accumulator, over arrays, for both engines.  Compiled by the test,
 // once per form of the u64 engine (-DHE355_U64_FOLD=0 / 1), and loaded through ctypes.
 #include <cstddef>
-#include <cstring>
 
+#include "device_tables.h"
 #include "modarith.h"
 
 using namespace he355;
 
 namespace {
-// the fields of FloorConst (csrc/he355_kernels.h) the floor steps read, filled as DeviceContext fills them (csrc/he355_api.hip)
-struct FC {
-    u64 inv, inv_shoup;
-    double inv_d, inv_i;
-};
-u64 invmod(u64 a, u64 q) // q prime
-{
-    u64 r = 1, b = a % q, e = q - 2;
-    while (e) {
-        if (e & 1) r = (u64)((u128)r * b % q);
-        b = (u64)((u128)b * b % q);
-        e >>= 1;
-    }
-    return r;
-}
-FC make_fc(u64 qs, u64 qi)
-{
-    FC f;
-    std::memset(&f, 0, sizeof(f));
-    const u64 inv = invmod(qs % qi, qi);
-    f.inv = inv;
-    f.inv_shoup = pre_word(inv, qi, HE355_U64_FOLD != 0);
-    f.inv_d = (double)inv;
-    f.inv_i = (double)inv / (double)qi;
-    return f;
-}
+// the floor steps' constants are the product's own: floor_const of csrc/device_tables.h, as DeviceContext::init uploads them
+using FC = FloorConst;
+FC make_fc(u64 qs, u64 qi) { return floor_const(qs, qi, HE355_U64_FOLD != 0); }
 ArF64 make_f64(u64 q)
 {
     ArF64 a;

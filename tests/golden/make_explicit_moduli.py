@@ -27,7 +27,7 @@ CSRC = os.path.join(TESTS, "..", "reference-seal-backend_amd", "csrc")
 def host_lib(directory):
     so = os.path.join(directory, "libfloor_forms_gen.so")
     subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DHE355_U64_FOLD=0", "-I", CSRC,
-                    os.path.join(TESTS, "floor_forms_host.cpp"), "-o", so], check=True)
+                    os.path.join(TESTS, "floor_forms_host.cpp"), os.path.join(CSRC, "he_params.cpp"), "-o", so], check=True)
     S = C.CDLL(so)
     S.ff_direct_terms.restype = C.c_uint32
     S.ff_direct_terms.argtypes = [C.c_uint64]

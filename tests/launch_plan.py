@@ -1,9 +1,9 @@
 """The library's kernel-selection rules restated in plain Python (a helper module: no GPU, no ctypes, nothing compiled).
 
-A key switch is never "the key switch": per chunk the library picks a kernel sequence (`ks_shape`, csrc/he355_api.hip) and per launch a
+A key switch is never "the key switch": per chunk the library picks a kernel sequence (`ks_shape`, csrc/ks_shape.h) and per launch a
 grid (`launch_k1`, `launch_k2`, `launch_k3`, `launch_floor_cols`, `launch_floor_rows`, csrc/he355_kernels.hip; the ring-in-LDS launchers
 of csrc/he355_kernels_lds.hip) from the batch, the ring, the level and the engine of each prime.  This module restates those rules -- it
-does not link them -- so that tests can (a) derive the batch sizes that lie on both sides of every threshold instead of guessing them,
+does not link them (tests/test_launch_plan_cpu.py holds the shape rule to csrc/ks_shape.h on the CPU) -- so that tests can (a) derive the batch sizes that lie on both sides of every threshold instead of guessing them,
 (b) assert the path counters of `he355_path_stats` against a plan, and (c) compare a kernel trace with the planned launches
 (tools/plan_vs_trace.py).  When the restatement and the product disagree, the product decides and this file is what gets corrected.
 
@@ -20,7 +20,7 @@ from dataclasses import dataclass, field
 
 K_WAVES, K_BLOCK = 4, 256                      # kernel_common.inc
 DUAL_MAX_BLOCKS, DUAL_MAX_BLOCKS_K3 = 1024, 4096  # he355_kernels.hip
-LAT_TARGETS, LAT_SPLIT, LAT_SPLIT_U64 = 8, 2, 8   # he355_api.hip: kLatTargets, kLatSplit, kLatSplitU64
+LAT_TARGETS, LAT_SPLIT, LAT_SPLIT_U64 = 8, 2, 8   # ks_shape.h: kLatTargets, kLatSplit, kLatSplitU64
 DEFAULT_CHUNK = 1024
 SCAN_MAX = 512                                 # the largest batch boundary_cases looks at
 
@@ -60,7 +60,7 @@ def chain(scheme: str, N: int, bits, fp64=None) -> Chain:
     return Chain(scheme, N, tuple(bits), tuple(bool(x) for x in fp64) if fp64 is not None else engines(bits))
 
 
-# ---- the shape rule (he355_api.hip) -------------------------------------------------------------------------------------------------
+# ---- the shape rule (ks_shape.h; tests/test_launch_plan_cpu.py holds each function to it) ----------------------------------------------
 def lat_limit(ch: Chain) -> int:
     return min(12, max(1, (1 << 17) // ch.N))
 

@@ -123,7 +123,7 @@ def test_behz_coefficient_arithmetic_equals_integer_arithmetic(sim, monkeypatch,
 
 
 def _lists(n, gs, b1):
-    """The distinct-operand lists of a batch as DeviceContext::bfv_multiply3 sizes them (he355_api.hip)."""
+    """The distinct-operand lists of a batch as behz_lists sizes them (csrc/behz_lists.h; held to it in the test below)."""
     gsz = min(gs, n)
     G = 1 if gs >= n else (n + gs - 1) // gs
     I, J = (gsz + b1 - 1) // b1, min(b1, gsz)
@@ -145,6 +145,13 @@ def test_transformed_once_lists_address_each_results_operands(sim, name, n, ix):
     G, I, J, na = _lists(n, gs, b1)
     nb = G * J
     ixa = arr(ix)
+    # ... and the header says the same of them, takes the lists, and spans the operands up to the last one a result reads
+    sim.sim_behz_lists.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+    hdr = (C.c_uint64 * 11)()
+    sim.sim_behz_lists(ixa, n, 2, 3, 4096, hdr)
+    assert [int(v) for v in hdr[:6]] == [G, I, J, na, na + nb, 1]
+    assert int(hdr[9]) == 1 + max(a_base + (r // gs if gs < 2 ** 63 else 0) * a_sg + ((r % gs if gs < 2 ** 63 else r) // b1) * a_si for r in range(n))
+    assert int(hdr[10]) == 1 + max(b_base + (r // gs if gs < 2 ** 63 else 0) * b_sg + ((r % gs if gs < 2 ** 63 else r) % b1) * b_sj for r in range(n))
     used = set()
     for r in range(n):
         out = (C.c_uint64 * 5)()

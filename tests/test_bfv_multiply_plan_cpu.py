@@ -1,5 +1,5 @@
 """tests/bfv_multiply_plan.py -- the restatement of the BEHZ multiply's host-side kernel selection -- pinned to the numbers of the launchers
-(csrc/he355_kernels.hip, `bfv_multiply3` in csrc/he355_api.hip), and the case table of tests/test_gpu_bfv_multiply_routes.py shown to take
+(csrc/he355_kernels.hip) and to the operand-list geometry `bfv_multiply3` runs on (csrc/behz_lists.h, through tests/csim), and the case table of tests/test_gpu_bfv_multiply_routes.py shown to take
 every outcome of every decision and each of the seven fused and two unfused instantiations at least once.  The auxiliary bases come from
 the CPU build of the product's parameter code (tests/csim).  No GPU."""
 import ctypes as C
@@ -69,6 +69,41 @@ def test_lists_or_per_pair():
     assert not mp.takes_lists(1, mp.GS_ALL, 1) and not mp.takes_lists(2, mp.GS_ALL, 2) and mp.takes_lists(4, mp.GS_ALL, 2)
     assert mp.takes_lists(8, 4, 2) and mp.takes_lists(720, 80, 8)      # the groups of he355_bfv_multiply_relin_accumulate
     assert not mp.takes_lists(7, 4, 2) and not mp.takes_lists(8, 4, 3)  # an incomplete group, a ragged row inside a group
+
+
+def test_lists_or_per_pair_equals_the_header():
+    """mp.takes_lists and the sizes it is made of against csrc/behz_lists.h (tests/csim/sim_rules.cpp): every call of the case table at its
+    own level, base size and ring, and the batches of test_lists_or_per_pair.  An Indexer3 as to_ix3 (device_types.h) and
+    he355_bfv_multiply_relin_accumulate make it: the strides do not enter the decision."""
+    import csim_lib
+    S = csim_lib.load()
+    u64p = C.POINTER(C.c_uint64)
+    S.sim_behz_lists.argtypes = [u64p, C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, u64p]
+
+    def header(n, gs, b1, L, S_, N):
+        ix = (0, 0, 1, 1, 1, 0, 1, 0) if (gs, b1) == (1, 1) else (0, 0, gs, b1, 0, 1, 0, 1) if gs == mp.GS_ALL else (0, 0, gs, b1, gs // b1, 1, b1, 1)
+        out = (C.c_uint64 * 11)()
+        S.sim_behz_lists((C.c_uint64 * 8)(*ix), n, L, S_, N, out)
+        return dict(zip(("G", "I", "J", "na", "n_cts", "may_list", "e_words", "per_res", "per_op", "a_cts", "b_cts"), (int(v) for v in out)))
+
+    def check(n, gs, b1, L, S_, N):
+        g = header(n, gs, b1, L, S_, N)
+        assert (g["na"], g["n_cts"]) == (g["G"] * g["I"], g["G"] * (g["I"] + g["J"])), (n, gs, b1)  # (G, I, J themselves: test_behz_sim_cpu.py)
+        assert bool(g["may_list"]) == mp.takes_lists(n, gs, b1), (n, gs, b1)
+        assert g["e_words"] == g["n_cts"] * 2 * (L + S_) * N and g["per_res"] == 3 * (L + S_) * N and g["per_op"] == 7 * (L + S_) * N
+        return g
+
+    took = set()
+    for name, L, case in mp.case_table():
+        lv = mp.chain_levels(name)[L]
+        g = check(case.n, *mp.indexer(case.kind, case.b1), L, lv.S, lv.N)
+        took.add(bool(g["may_list"]))
+        # the spans the overlap check reads: the last operand of each side, from base 0
+        assert (g["a_cts"], g["b_cts"]) == ((case.n, case.n) if case.kind == "pairwise" else (g["I"], g["J"])), case
+    assert took == {True, False}
+    for n, gs, b1 in [(1, 1, 1), (3, 1, 1), (26, 1, 1), (6, mp.GS_ALL, 2), (5, mp.GS_ALL, 2), (6, mp.GS_ALL, 3), (1, mp.GS_ALL, 1), (2, mp.GS_ALL, 2),
+                      (4, mp.GS_ALL, 2), (8, 4, 2), (720, 80, 8), (7, 4, 2), (8, 4, 3)]:
+        check(n, gs, b1, 2, 3, 8192)
 
 
 def test_plans_of_single_calls():

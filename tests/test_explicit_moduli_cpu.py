@@ -3,8 +3,8 @@
  1. the fixture is what its generator writes (regenerated where sympy is present) and every modulus is an NTT-friendly prime;
  2. every chain has the property it exists for, seen from two sides: the rule restated in Python (explicit_moduli.py) and the library's
     host side (the lane simulator's Params in both builds, ff_direct_terms / ff_x_bound of floor_forms_host.cpp, the device-less
-    Context's fp64 and bfv_aux_base).  The lift classes of k_k2n are computed on the device side of DeviceContext::init only and have no
-    host export: their pairs are held to the restated rule here, and told apart on the device by tests/test_gpu_explicit_moduli.py;
+    Context's fp64 and bfv_aux_base).  The lift classes of k_k2n are the masks of csrc/device_tables.h, which DeviceContext::init uploads:
+    the restated rule is held to them pair by pair here, and the classes are told apart on the device by tests/test_gpu_explicit_moduli.py;
  3. the reference alone is right on these chains: the oracle equals the exact integer model (tests/golden/exact_model.py) on the
     N = 1024 versions of the chains -- the CKKS pipeline operations of test_exact_model.py, Model.bfv_multiply on operand families of
     bfv_multiply_operands.py, and encrypt -> decrypt under every plain modulus;
@@ -47,7 +47,7 @@ def be():
 def ff(tmp_path_factory):
     so = str(tmp_path_factory.mktemp("explicit_moduli") / "libfloor_forms.so")
     subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DHE355_U64_FOLD=0", "-I", CSRC,
-                    os.path.join(HERE, "floor_forms_host.cpp"), "-o", so], check=True)
+                    os.path.join(HERE, "floor_forms_host.cpp"), os.path.join(CSRC, "he_params.cpp"), "-o", so], check=True)
     S = C.CDLL(so)
     S.ff_direct_terms.restype = C.c_uint32
     S.ff_direct_terms.argtypes = [C.c_uint64]
@@ -212,6 +212,48 @@ def test_lift_classes_on_both_sides_of_each_threshold():
         assert not any(oracle_is_prime(v) for v in range(q_in + 2 * N, q_out, 2 * N))
         # the bound the inside target's fullest row reaches, under 2^47 by less than the next prime would take
         assert eo.fits_48_bound(float(q_in), float(q_in), logn1) * 1.0000001 < 2.0 ** 47 <= eo.fits_48_bound(float(q_out), float(q_out), logn1) * 1.0000001
+
+
+def test_lift_classes_equal_the_masks_the_device_context_uploads():
+    """xm.lift_class against csrc/device_tables.h (tests/csim/sim_rules.cpp): every (digit prime, fp64-engine target) pair of every chain of
+    the fixture -- the ratio_two, fits48, engine_edge_47 and xbound chains sit within 2^-26 of the thresholds -- under every logn1 the
+    fixture uses, pair by pair (k2_lift_class), and as the masks k2_lift_masks makes of the chain's own Params at the chain's own ring.
+    The two agree bit for bit because both run the same IEEE double operations in the same order, one rounding each: the csim build uses
+    -ffp-contract=off, and the product's host build targets baseline x86-64, which has no fused multiply-add to contract into."""
+    S = _sim(False)  # (the Shoup build makes Params of any chain; the rule does not look at the form)
+    S.sim_k2_lift_class.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
+    S.sim_k2_lift_masks.argtypes = [C.c_void_p, u64p, u64p]
+    S.sim_K.restype = C.c_size_t
+    S.sim_K.argtypes = [C.c_void_p]
+    names = ("general", "direct", "lift")
+    logn1s = sorted({c["N"].bit_length() - 11 for c in CH.values()})
+    assert logn1s[0] == 0 and logn1s[-1] == 5
+    seen = set()
+    for cid, c in CH.items():
+        primes = c["primes"]
+        for qt in (q for q in primes if xm.is_f64(q)):
+            for qj in primes:
+                for logn1 in logn1s:
+                    want = xm.lift_class(qj, qt, logn1)
+                    assert names[S.sim_k2_lift_class(qj, qt, logn1)] == want, (cid, hex(qj), hex(qt), logn1)
+                    seen.add(want)
+        h = create(S, c)
+        assert h, cid
+        try:
+            K, logn1 = S.sim_K(h), c["N"].bit_length() - 11
+            assert K == len(primes)
+            direct, lift = (C.c_uint64 * K)(), (C.c_uint64 * K)()
+            S.sim_k2_lift_masks(h, direct, lift)
+            for j, qj in enumerate(primes):
+                want = {t: xm.lift_class(qj, qt, logn1) for t, qt in enumerate(primes) if xm.is_f64(qt)}
+                assert direct[j] == sum(1 << t for t, w in want.items() if w == "direct"), (cid, j)
+                assert lift[j] == sum(1 << t for t, w in want.items() if w == "lift"), (cid, j)
+        finally:
+            S.sim_params_destroy(h)
+    assert seen == set(names)
+    for cid in ("ratio_two", "engine_edge_47", "fits48_inside_2048", "fits48_outside_32768"):
+        assert cid in CH
+    assert any(k.startswith("xbound") for k in CH)
 
 
 def oracle_is_prime(v):

@@ -3,7 +3,7 @@ Python integers and against the composition they replace (floor_fin*(acc_canon(a
 forms state; the raw tail's acc_to_inv / acc_park; and the host-side rule that decides which launches may take the direct forms.
 
 tests/floor_forms_host.cpp includes the header and is compiled here with the host compiler, once per form of the u64 engine
-(HE355_U64_FOLD = 0 / 1), and loaded through ctypes.  Constants are built as DeviceContext builds FloorConst."""
+(HE355_U64_FOLD = 0 / 1), and loaded through ctypes.  Constants are floor_const's (csrc/device_tables.h), the ones DeviceContext uploads."""
 import ctypes as C
 import itertools
 import json
@@ -52,7 +52,7 @@ def lib(request, tmp_path_factory):
     fold = request.param
     so = str(tmp_path_factory.mktemp("floor_forms") / f"libfloor_forms_{fold}.so")
     subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", f"-DHE355_U64_FOLD={fold}", "-I", CSRC,
-                    os.path.join(HERE, "floor_forms_host.cpp"), "-o", so], check=True)
+                    os.path.join(HERE, "floor_forms_host.cpp"), os.path.join(CSRC, "he_params.cpp"), "-o", so], check=True)
     S = C.CDLL(so)
     assert S.ff_fold_build() == fold
     for fn, t in ((S.ff_f64, f64p), (S.ff_u64, u64p)):

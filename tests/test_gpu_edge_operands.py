@@ -382,7 +382,7 @@ def test_key_switching_ops(pair, be, kind):
             check_all({"rotate_sum": out.download((n, 2, L, N))}, want, what + (shape,))
         if N > 8192:
             # a batch large enough for the fused key product (k_k3 with the floor in its epilogue; small rings would need hundreds of
-            # ciphertexts): the same five rows repeated to the first batch with 128 special-prime blocks (fuse_pays, he355_api.hip:
+            # ciphertexts): the same five rows repeated to the first batch with 128 special-prime blocks (fuse_pays, ks_shape.h:
             # N / 1024 blocks per op-group of eight -- 32 ciphertexts at N = 32768, 64 at N = 16384), one chunk
             big = 8 * -(-128 // (N // 1024))
             idx = np.arange(big) % n

@@ -1,11 +1,19 @@
 """tests/launch_plan.py -- the library's kernel-selection rules restated in Python -- pinned to what the product's comments, profiles/
 and tests/test_gpu_bench_shapes.py state, and the completeness of the case table of tests/test_gpu_selection_boundaries.py: over that
-table every selection decision takes every one of its outcomes at least once.  Nothing of the product is compiled or loaded here."""
+table every selection decision takes every one of its outcomes at least once.  The shape rule itself is held to the product's text:
+csrc/ks_shape.h through the entry points of tests/csim/sim_rules.cpp, cell by cell over every chain, level and batch the restatement was
+built for, and the three host headers of the device context's rules at their edges under the sanitizers (tests/shape_rules_main.cpp).
+No GPU, and the device library is not loaded."""
+import ctypes as C
 import os
 import sys
 
+import pytest
+
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import csim_lib  # noqa: E402
 import launch_plan as lp  # noqa: E402
+import sanitized_program  # noqa: E402
 
 HEADLINE = lp.chain("ckks", 32768, lp.HEADLINE_BITS)
 
@@ -22,7 +30,7 @@ def test_engine_rule_matches_the_chains_the_gpu_tests_assert():
 
 
 def test_headline_boundaries():
-    # he355_api.hip, lat_limit / fuse_pays: N = 2^15 crosses between 4 and 5 ciphertexts; fused from 17 at L = 16 instead of 25
+    # ks_shape.h, lat_limit / fuse_pays: N = 2^15 crosses between 4 and 5 ciphertexts; fused from 17 at L = 16 instead of 25
     assert lp.lat_limit(HEADLINE) == 4
     assert shapes(HEADLINE, 16, [4, 5, 16, 17]) == ["latency", "unfused", "unfused", "fused"]
     for L in (15, 12, 11, 6, 1):
@@ -35,7 +43,7 @@ def test_headline_boundaries():
 
 
 def test_lds_limits():
-    # he355_api.hip, lds_limit: 64 ciphertexts at {60, 40, 60}, 32 at {60, 40, 40, 60} (N = 8192); profiles/r06_lds_shape.txt
+    # ks_shape.h, lds_limit: 64 ciphertexts at {60, 40, 60}, 32 at {60, 40, 40, 60} (N = 8192); profiles/r06_lds_shape.txt
     assert lp.lds_limit(lp.chain("ckks", 8192, [60, 40, 60]), 2) == 64
     assert lp.lds_limit(lp.chain("ckks", 8192, [60, 40, 40, 60]), 3) == 32
     ch = lp.chain("ckks", 2048, [46, 40, 40, 46])  # the n2048_f64 chain
@@ -183,3 +191,105 @@ def test_rotation_terms_and_trie():
     assert lp.rotation_terms(3, 8192, (1, 2, 4, -1)) == [-1, 4] and lp.rotation_terms(2, 8192, (1, 2, 4, -1)) == [2]
     assert lp.rotation_trie_levels((1, 2, 3), 8192, (1, 2, 4, -1)) == [3, 1]
     assert lp.galois_elt(1, 8192) == 3 and lp.galois_elt(0, 8192) == 16383 and lp.galois_elt(-1, 8192) == pow(3, 4095, 16384)
+
+
+# ---- the restatement held to csrc/ks_shape.h ---------------------------------------------------------------------------------------------
+SHAPES = ("lds", "latency", "fused", "unfused", "bfv_coeff")  # KsShape, in order
+KINDS = ("product", "size3", "galois", "grouped")             # KsKind, in order
+SCHEME_BFV, SCHEME_CKKS = 1, 2
+AUTO, NEVER = 2 ** 64 - 1, 0  # what he355_set_latency_max / he355_set_lds_max take: 2^64 - 1 is "back to the rule", 0 "never"
+HUGE = 2 ** 64 - 2            # the largest limit that IS a limit (no call of the suite sets it: it shows the rule's other conditions alone)
+
+
+def limits(lat=AUTO, lds=AUTO, chunk=lp.DEFAULT_CHUNK):
+    """{latency max, LDS max, chunk}: the two limits as the API takes them, mapped by KsLimits' own setters (sim_rules.cpp: limits_of)"""
+    return (C.c_uint64 * 3)(lat, lds, chunk)
+
+
+@pytest.fixture(scope="module")
+def rules():
+    S = csim_lib.load()
+    u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+    S.sim_ks_shape.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int]
+    S.sim_lat_limit.restype = C.c_uint64
+    S.sim_lat_limit.argtypes = [C.c_uint64, C.c_int, u64p]
+    S.sim_lds_limit.restype = C.c_uint64
+    S.sim_lds_limit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, u64p, C.c_int]
+    S.sim_ks_scan.restype = C.c_uint64
+    S.sim_ks_scan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, u64p, C.c_int, C.c_uint64, u64p, C.c_size_t, u8p, u8p, u8p, u64p, u8p]
+    return S
+
+
+def test_shape_rule_equals_the_header_over_every_chain_level_and_batch(rules):
+    """lp.ks_shape, fuse_pays, level_sum_pays, lat_limit, lds_limit and lds_supported against csrc/ks_shape.h: every chain of lp.CHAINS,
+    L = 1 .. L_top, n = 1 .. lp.SCAN_MAX, the four kinds, `out` apart or not; level_sum_pays at the default chunk, at the chunks of this
+    module's own cases and at those of the mixed-shape calls.  The environment is the NTT-domain pipeline's (scheme CKKS: what
+    batch_env(0, true) makes of a BFV context too), which is where every planned launch runs; one filled array per chain."""
+    mixed = lp.case_chain("n8192_60_45_60_both_engines")
+    chunks = sorted({lp.DEFAULT_CHUNK, 320, 32} | {c for _, c, _ in lp.mixed_shape_calls(mixed, mixed.Ltop)})
+    nmax = lp.SCAN_MAX
+    for name in lp.CHAINS:
+        ch = lp.case_chain(name)
+        Lt = ch.Ltop
+        shape, fuse = (C.c_uint8 * (Lt * nmax * 8))(), (C.c_uint8 * (Lt * nmax))()
+        lsum = (C.c_uint8 * (len(chunks) * Lt * nmax))()
+        lds_lim, lds_ok = (C.c_uint64 * Lt)(), (C.c_uint8 * Lt)()
+        lat = rules.sim_ks_scan(SCHEME_CKKS, ch.logn1, ch.K, ch.N, ch.K, limits(), Lt, nmax, (C.c_uint64 * len(chunks))(*chunks), len(chunks),
+                                shape, fuse, lsum, lds_lim, lds_ok)
+        assert lat == lp.lat_limit(ch), name
+        for L in range(1, Lt + 1):
+            assert lds_lim[L - 1] == lp.lds_limit(ch, L) and bool(lds_ok[L - 1]) == lp.lds_supported(ch, L), (name, L)
+            for n in range(1, nmax + 1):
+                at = (L - 1) * nmax + n - 1
+                assert bool(fuse[at]) == lp.fuse_pays(ch, n, L), (name, L, n)
+                for k, kind in enumerate(KINDS):
+                    for apart in (False, True):
+                        assert SHAPES[shape[(at * 4 + k) * 2 + apart]] == lp.ks_shape(ch, L, n, kind, apart), (name, L, n, kind, apart)
+                for ci, c in enumerate(chunks):
+                    assert bool(lsum[ci * Lt * nmax + at]) == lp.level_sum_pays(ch, L, n, c), (name, L, n, c)
+
+
+def test_shape_rule_with_the_limits_set(rules):
+    """he355_set_latency_max / he355_set_lds_max (launch_plan.py has no overrides: literal expectations).  Limit 0: the shape is never taken.
+    Limit 2^64 - 1: the rule applies again -- the same limits and the same shapes as a context nobody set a limit on.  A limit between:
+    that batch and no larger; HUGE, the largest value that is a limit, leaves the rule's other conditions to decide alone.  And the two
+    inputs are two: a BFV context's own environment has one shape whatever the limits."""
+    ch = lp.case_chain("n8192_60_45_60_both_engines")  # N = 8192, L = 2: LDS to 64, latency to 12, unfused to 120, fused from 121
+    def shape(n, lim, kind="product", apart=True, scheme=SCHEME_CKKS, L=2, c=ch):
+        return SHAPES[rules.sim_ks_shape(scheme, c.logn1, c.K, c.N, c.K, lim, L, n, KINDS.index(kind), apart)]
+    def lat_lds(lim, L=2):
+        return rules.sim_lat_limit(ch.N, ch.K, lim), rules.sim_lds_limit(SCHEME_CKKS, ch.logn1, ch.K, ch.N, ch.K, lim, L)
+    auto_rows = ["lds", "lds", "unfused", "unfused", "fused"]
+    assert [shape(n, limits()) for n in (1, 64, 65, 120, 121)] == auto_rows and lat_lds(limits()) == (12, 64)
+    # 2^64 - 1 handed to either setter, or to both: the AUTO rows again, not "every batch"
+    for lim in (limits(lat=2 ** 64 - 1), limits(lds=2 ** 64 - 1), limits(lat=2 ** 64 - 1, lds=2 ** 64 - 1)):
+        assert lat_lds(lim) == (12, 64)
+        assert [shape(n, lim) for n in (1, 64, 65, 120, 121)] == auto_rows
+        assert [shape(n, lim, apart=False) for n in (12, 13, 120, 121)] == ["latency", "unfused", "unfused", "fused"]
+        assert shape(2 ** 40, lim) == "fused"
+    assert lat_lds(limits(lat=NEVER, lds=2 ** 64 - 1)) == (0, 64) and lat_lds(limits(lat=2 ** 64 - 1, lds=NEVER)) == (12, 0)
+    # limit 0: never
+    assert [shape(n, limits(lds=NEVER)) for n in (1, 12, 13, 64, 121)] == ["latency", "latency", "unfused", "unfused", "fused"]
+    assert [shape(n, limits(lds=NEVER, lat=NEVER)) for n in (1, 12, 120, 121)] == ["unfused", "unfused", "unfused", "fused"]
+    assert [shape(n, limits(lat=NEVER)) for n in (1, 64, 65)] == ["lds", "lds", "unfused"]
+    # a finite limit: that batch and no larger
+    assert [shape(n, limits(lds=5, lat=7)) for n in (5, 6, 7, 8)] == ["lds", "latency", "latency", "unfused"]
+    assert lat_lds(limits(lat=7, lds=5)) == (7, 5) and lat_lds(limits(lat=HUGE, lds=HUGE)) == (HUGE, HUGE)
+    assert [shape(n, limits(lds=HUGE)) for n in (65, 121, 512, 2 ** 40)] == ["lds"] * 4
+    assert [shape(n, limits(lds=HUGE), apart=False) for n in (12, 13, 121)] == ["latency", "unfused", "fused"]  # (`out` over an operand: never LDS)
+    assert [shape(n, limits(lds=NEVER, lat=HUGE)) for n in (13, 121, 2 ** 40)] == ["latency"] * 3
+    assert [shape(n, limits(lds=NEVER, lat=HUGE), kind="grouped") for n in (13, 121)] == ["unfused", "fused"]  # grouped: neither small shape
+    # where the ring-in-LDS kernels do not exist no limit brings them: L = 7 of a nine-prime chain at N = 8192, any level at N = 2^14
+    deep = lp.chain("ckks", 8192, [60] + [45] * 7 + [60])
+    assert shape(1, limits(lds=HUGE), L=7, c=deep) == "latency" and shape(1, limits(lds=HUGE), L=6, c=deep) == "lds"
+    wide = lp.case_chain("n16384_60_45_45_45_60_L4")
+    assert shape(1, limits(lds=HUGE), L=4, c=wide) == "latency" and shape(9, limits(lds=HUGE), L=4, c=wide) == "unfused"
+    # a BFV context's coefficient-form environment: one shape; the same context on the NTT-domain pipeline: the rule
+    b = lp.case_chain("bfv_n8192_60_40_60")
+    for lim in (limits(), limits(lds=HUGE, lat=HUGE), limits(lds=NEVER, lat=NEVER)):
+        assert {shape(n, lim, kind=k, scheme=SCHEME_BFV, c=b) for n in (1, 64, 121) for k in KINDS} == {"bfv_coeff"}
+    assert [shape(n, limits(), kind="galois", c=b) for n in (64, 65, 121)] == ["lds", "unfused", "fused"]
+
+
+def test_the_rule_headers_under_the_sanitizers(tmp_path):
+    sanitized_program.run(tmp_path, "shape_rules_main.cpp", "shape_rules ok")
