@@ -1,8 +1,8 @@
 // bfv_pir_args.h -- the argument checks of the BFV PIR calls that need no device (monomial multiply, expansion, merge, decomposition, the external
-// product, the selection tree and its selectors, database bytes, reply compression, seeded queries and keys), each made ONCE per call: the C ABI wrapper (he355_api.hip) runs the check before it asks for a
-// device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands what the check worked out (the digit tables, F,
-// rows, terms, pass, the field width) to DeviceContext as a plan.  What needs the device or its state (keys present, the Galois keys, the
-// key-switch tables) is checked there.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
+// product, the selection tree and its selectors, database bytes, reply compression, seeded queries and keys), each made ONCE per call: the C ABI function (bfv_pir.inc) runs the check before it asks for a
+// device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and keeps what the check worked out (the digit tables, F,
+// rows, terms, pass, the field width) as its plan.  What needs the device or its state (keys present, the Galois keys, the
+// key-switch tables) is checked after that, in the same function.  Host-only on purpose: no HIP header, so tests/bfv_pir_args_main.cpp runs every check at its edges
 // under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <algorithm>

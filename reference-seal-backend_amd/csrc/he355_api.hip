@@ -1,4 +1,5 @@
-// he355_api.hip — device context, per-op kernel sequences and the C ABI declared in include/he355.h.
+// he355_api.hip — the device context (the engine: memory, keys, chunk loop, key switch, rotations, BFV multiply, client calls) and the C ABI
+// declared in include/he355.h; four call families have their launch sequences with their entry points in the .inc files included last.
 // Host code is C++17; the only way into the GPU is through the launchers of he355_kernels.h.
 // There is no CPU implementation of any evaluator op in this library: without a HIP device every device
 // entry point fails with HE355_E_DEVICE.
@@ -282,6 +283,15 @@ public:
         return PoolBlock(pool_, bytes);
     }
     DevicePool::Stats alloc_stats() const { return pool_.stats(); }
+    // the counter blocks of every *_stats call, counted on the host where the calls branch and read by no launch
+    struct Counters {
+        he355_path_stats_t paths{};
+        he355_hoist_stats_t hoist{};
+        he355_poly_stats_t poly{};
+        he355_raise_stats_t raise{};
+        he355_bfv_route_stats_t routes{};
+        he355_bfv_multiply_stats_t mul_routes{};
+    };
     // the one read of a counter block (every *_stats call): its value, and the block back at zero where the caller asks
     template <class S> static S take_stats(S &counters, bool reset)
     {
@@ -290,13 +300,25 @@ public:
         return s;
     }
     // which shape / schedule the key switches of this context took (he355_path_stats): counted per kernel sequence (one chunk of a batch)
-    he355_path_stats_t path_stats(bool reset) { return take_stats(paths_, reset); }
+    he355_path_stats_t path_stats(bool reset) { return take_stats(count_.paths, reset); }
     // which route the BFV PIR calls of this context took (he355_bfv_route_stats): counted on the host where the calls branch, read by no launch
-    he355_bfv_route_stats_t bfv_route_stats(bool reset) { return take_stats(routes_, reset); }
+    he355_bfv_route_stats_t bfv_route_stats(bool reset) { return take_stats(count_.routes, reset); }
+    he355_poly_stats_t poly_stats(bool reset) { return take_stats(count_.poly, reset); }
+    he355_raise_stats_t raise_stats(bool reset) { return take_stats(count_.raise, reset); }
     size_t pool_trim() { sync(); return pool_.trim(); }
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
     const KernelEnv &env() const { return env_; }
+    // ---- what the call families use (the *.inc files he355_api.hip includes last): read access for the sequences that live there
+    const Params &params() const { return P; }
+    const KsLimits &limits() const { return lim_; }
+    size_t chunk_limit() const { return lim_.chunk; }
+    u64 compute_units() const { return cus_; }
+    const u64 *public_key() const { return d_pk_; }
+    const u64 *secret_key() const { return d_sk_; }
+    Counters &counters() { return count_; }
+    // the kBfv arena holding `bytes` (he355_bfv_multiply_plain's prepared plaintexts), or null where it does not fit
+    u64 *bfv_arena(size_t bytes) { return try_reserve(&arena_[kBfv], 1, bytes) ? arena_[kBfv].p : nullptr; }
     void set_chunk(size_t c) { lim_.chunk = c ? c : 1; }
     void set_latency_max(u64 n) { lim_.set_latency_max(n); } // ~0: back to lat_limit()'s rule
     void set_level_walk(bool on) { level_walk_ = on; }
@@ -404,12 +426,12 @@ public:
             const uint32_t *table = perm((uint32_t)ginv);
             if (!hk.p) {
                 dmalloc(hk.p, key_alloc_elems() * 8);
-                hoist_.key_bytes += key_alloc_elems() * 8;
+                count_.hoist.key_bytes += key_alloc_elems() * 8;
             }
             launch_key_permute(env_, galois_key(elt), hk.p, table, key_alloc_elems() / P.N);
             HIPCHECK(hipGetLastError());
             hk.ok = true;
-            ++hoist_.keys_permuted;
+            ++count_.hoist.keys_permuted;
         }
         return hk.p;
     }
@@ -419,12 +441,12 @@ public:
         HIPCHECK(hipStreamSynchronize(stream_));
         for (auto &kv : d_hoist_) pool_.raw_free(kv.second.p);
         d_hoist_.clear();
-        hoist_.key_bytes = 0;
+        count_.hoist.key_bytes = 0;
     }
     he355_hoist_stats_t hoist_stats(bool reset)
     {
-        const he355_hoist_stats_t s = take_stats(hoist_, reset);
-        hoist_.key_bytes = s.key_bytes; // (the bytes are a level, not a count)
+        const he355_hoist_stats_t s = take_stats(count_.hoist, reset);
+        count_.hoist.key_bytes = s.key_bytes; // (the bytes are a level, not a count)
         return s;
     }
     const uint32_t *perm(uint32_t elt)
@@ -672,7 +694,7 @@ public:
                 }
             } else if (shape == KsShape::Lds) {
                 // a ring that fits LDS: the tensor product / permutation, key switch and the add in two launches (the operands are read where they lie)
-                ++paths_.ks_lds;
+                ++count_.paths.ks_lds;
                 LdsKsOperands o;
                 if (product) {
                     o.mode = LDSKS_MUL; o.a = src.a; o.b = src.b; o.ix = src.ix; o.op_offset = off;
@@ -691,8 +713,8 @@ public:
             } else {
                 const bool fused = shape == KsShape::Fused;
                 if (groups.sum_out && !fused) throw std::logic_error("level sum: the fused key switch only");
-                ++(fused ? paths_.ks_fused : shape == KsShape::Latency ? paths_.ks_latency : paths_.ks_unfused);
-                if (fused && groups.sum_out) ++paths_.level_sum_launches_in_k3;
+                ++(fused ? count_.paths.ks_fused : shape == KsShape::Latency ? count_.paths.ks_latency : count_.paths.ks_unfused);
+                if (fused && groups.sum_out) ++count_.paths.level_sum_launches_in_k3;
                 // c0, c1 of the ciphertext the switched key part is added into: written by k_k1, or (in_k3) formed by k_k3 where it adds them
                 // in -- k_k1 is HBM-bound and then reads and writes less, k_k3 is not and reads the operand rows instead of c01
                 const bool in_k3 = fused && out_apart;
@@ -813,369 +835,6 @@ public:
         fr.out = out.p; fr.out_op_stride = out.op_stride; fr.out_poly_stride = out.poly_stride;
         fr.tail_prime = tail_prime; fr.tail = tail;
         launch_floor_rows(env, nc, fr);
-    }
-    // What a hoisted call sets up before its first launch.  Every keyed element's Galois key must be installed: refused before anything is
-    // built.  Then per element its table -- the NTT-domain permutation, or (coeff) the coefficient-form gather -- and its permuted key
-    // (hoist_key; null: the identity, which gets a table only with ident_tables: the blocks of rotate_hoisted are finished through one),
-    // and the identity's permutation for the digit lift of the NTT-domain pipeline.
-    struct HoistSetup {
-        std::vector<const uint32_t *> table;
-        std::vector<const u64 *> key;
-        const uint32_t *ident = nullptr;
-    };
-    // (what: the call's name in front of the refusal; null: the bare message of the first hoisted calls)
-    void hoist_require_keys(const std::vector<uint32_t> &elts, const char *what = nullptr)
-    {
-        for (uint32_t e : elts)
-            if (e != 1 && !galois_key(e)) throw std::invalid_argument(what ? std::string(what) + ": Galois key not present" : std::string("Galois key not present"));
-    }
-    HoistSetup hoist_setup(const std::vector<uint32_t> &elts, bool coeff, bool ident_tables, const char *what = nullptr)
-    {
-        hoist_require_keys(elts, what);
-        const size_t n_elts = elts.size();
-        HoistSetup hs{std::vector<const uint32_t *>(n_elts, nullptr), std::vector<const u64 *>(n_elts, nullptr), nullptr};
-        bool keyed = false;
-        for (size_t r = 0; r < n_elts; ++r) {
-            const uint32_t e = elts[r];
-            if (e != 1 || ident_tables) hs.table[r] = coeff ? gather(e) : perm(e);
-            if (e != 1) hs.key[r] = hoist_key(e);
-            keyed |= e != 1;
-        }
-        if (keyed && !coeff) hs.ident = perm(1);
-        return hs;
-    }
-    HoistSetup hoist_setup(const HoistPlan &pl, bool coeff, bool ident_tables) { return hoist_setup(pl.elts, coeff, ident_tables); }
-    // The one digit lift of a chunk of a hoisted call, counted in he355_hoist_stats: the input's c1 as it lies (the identity's permutation)
-    // through k_k1's inverse row pass -- c2n, c2r; nothing of c01 is written -- and k_k2n; coeff: (c0, 0) into B.e for the BFV tail, and
-    // k_k2n on the coefficients of c1.  op 0 of the chunk is ciphertext `off` of `in`.
-    void hoist_digit_lift(const KernelEnv &env, int L, u64 nc, u64 off, const u64 *in, const KsBuffers &B, bool coeff, const uint32_t *ident)
-    {
-        const size_t LN = (size_t)L * P.N;
-        ++hoist_.digit_lifts;
-        if (coeff) {
-            const u64 *a = in + off * 2 * LN;
-            launch_hoist_addend_coeff(env, L, nc, a, B.e);
-            launch_k2(env, L, nc, B, a + LN, 2 * LN);
-            return;
-        }
-        K1Operands k1;
-        k1.mode = K1_GALOIS; k1.a = in; k1.op_offset = off; k1.perm = ident;
-        k1.no_c1 = k1.no_c0n = true;
-        launch_k1(env, L, nc, k1, B);
-        launch_k2(env, L, nc, B);
-    }
-    // Hoisted rotations: out block r = sigma_g(c0 + u0, u1) of every input under element pl.elts[r], (u0, u1) the key switch of the input's
-    // c1 itself under hoist_key(g) -- the digit lift (the inverse row pass and k_k2n, or k_k2n on the coefficients) runs ONCE per chunk and
-    // the slab S.ks.d is then read by every element's key product.  One stream only: the slab and the sums' scratch are reused from element
-    // to element, and the plain sum read-modify-writes `out` in launch order.  Per element the unfused tail (k_k3 on all primes, the floor
-    // step's column and row halves with no addend; BFV coefficient form: the two BFV tail kernels onto (c0, 0)) into scratch, then the
-    // finishing kernel.  plain (optional, NTT pipeline only): [n_elts][L][N], out [n][2][L][N] = sum_r plain[r] (.) block r.
-    // Counted in he355_hoist_stats, in no field of he355_path_stats.
-    void rotate_hoisted(const HoistPlan &pl, int L, bool ntt_form, u64 n, const u64 *in, const u64 *plain, u64 *out)
-    {
-        use();
-        const bool coeff = P.scheme == kSchemeBFV && !ntt_form;
-        const HoistSetup hs = hoist_setup(pl, coeff, true);
-        const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
-        const int SP = (int)P.K - 1;
-        for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
-            const KernelEnv env = batch_env(0, !coeff);
-            const KsBuffers &B = S.ks; // (c01: the arena's [nc][2][L][N], every element's sums before the permutation)
-            const u64 *a = in + off * 2 * LN;
-            if (pl.keyed) hoist_digit_lift(env, L, nc, off, in, B, coeff, hs.ident);
-            for (size_t r = 0; r < n_elts; ++r) {
-                u64 *o = plain ? out + off * 2 * LN : out + ((u64)r * n + off) * 2 * LN;
-                const u64 *pt = plain ? plain + r * LN : nullptr;
-                if (!hs.key[r]) { // the identity
-                    if (pt) launch_hoist_finish_ntt(env, L, nc, nullptr, a, hs.table[r], o, pt, r == 0);
-                    else HIPCHECK(hipMemcpyAsync(o, a, nc * 2 * LN * 8, hipMemcpyDeviceToDevice, env.stream));
-                    continue;
-                }
-                ++hoist_.key_products;
-                ++hoist_.mod_downs; // (every element pays its own)
-                launch_k3(env, L, nc, B, hs.key[r]);
-                if (coeff) {
-                    launch_bfv_tail_sp(env, nc * 2, B.tpr, S.rlr);
-                    launch_bfv_tail_fin(env, L, nc, B.t, S.rlr, B.c01, B.c01_item_stride, B.e, 2 * LN);
-                    launch_hoist_finish_coeff(env, L, nc, B.c01, hs.table[r], o);
-                } else {
-                    floor_step(env, SP, L, 2, nc, B.tpr, B.e, {B.t, 2 * LN, LN}, {}, {B.c01, B.c01_item_stride, LN});
-                    launch_hoist_finish_ntt(env, L, nc, B.c01, a, hs.table[r], o, pt, r == 0);
-                }
-            }
-        });
-        HIPCHECK(hipGetLastError());
-    }
-    // The lazy-mod-down plain sum: out [n][2][L][N] = B + moddown(A), A = sum_r plain_qp[r] (.) sigma_r(key product r) accumulated in the
-    // extended basis Q P, B = the part that needs no key accumulated in Q (the definition: include/he355.h).  The lift runs as in
-    // rotate_hoisted; every keyed element then pays launch_k3 and ONE accumulate launch, and the mod-down runs once per chunk.  No scratch
-    // of its own: B.c01 holds the Q part of A, B.tp its P part (k_k3 leaves the special prime's sums in B.tpr, after its inverse row pass;
-    // the accumulate kernel's special-prime waves transform them back -- k3_body.inc is untouched), the output chunk itself holds B and
-    // B.e the corrections.  One stream; NTT-domain pipeline only.
-    void rotate_hoisted_lazy(const HoistPlan &pl, int L, u64 n, const u64 *in, const u64 *plain_qp, u64 *out)
-    {
-        use();
-        const HoistSetup hs = hoist_setup(pl, false, false);
-        const size_t N = P.N, LN = (size_t)L * N, n_elts = pl.elts.size();
-        const int SP = (int)P.K - 1;
-        for_each_chunk(n, L, chunk_ops(n, L, false), false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
-            const KernelEnv env = batch_env(0, true);
-            const KsBuffers &B = S.ks;
-            const u64 *a = in + off * 2 * LN;
-            u64 *o = out + off * 2 * LN;
-            if (pl.keyed) hoist_digit_lift(env, L, nc, off, in, B, false, hs.ident);
-            bool first_a = true, first_b = true;
-            for (size_t r = 0; r < n_elts; ++r) {
-                const u64 *pt = plain_qp + r * (LN + N);
-                if (!hs.key[r]) {
-                    launch_hoist_acc_qp(env, L, nc, nullptr, nullptr, a, nullptr, pt, nullptr, 0, nullptr, o, false, first_b);
-                } else {
-                    ++hoist_.key_products;
-                    launch_k3(env, L, nc, B, hs.key[r]);
-                    launch_hoist_acc_qp(env, L, nc, B.t, B.tpr, a, hs.table[r], pt, B.c01, B.c01_item_stride, B.tp, o, first_a, first_b);
-                    first_a = false;
-                }
-                first_b = false;
-            }
-            if (!pl.keyed) return;
-            ++hoist_.mod_downs; // one per chunk, however many elements
-            PolyView pv = poly_view(B.tp, 1, N, 1);
-            pv.prime_of[0] = (unsigned char)SP;
-            launch_rows_inv(env, pv, (u32)(nc * 2));
-            floor_step(env, SP, L, 2, nc, B.tp, B.e, {B.c01, B.c01_item_stride, LN}, {o, 2 * LN, LN}, {o, 2 * LN, LN});
-        });
-        HIPCHECK(hipGetLastError());
-    }
-    size_t chunk_limit() const { return lim_.chunk; }
-    // The baby-step/giant-step linear transform on the hoisted rotations (the definition: include/he355.h).  Per chunk: ONE digit lift of the
-    // input, per used keyed baby launch_k3 and the rotate kernel into the baby store (T_i = sigma(S_i) with P sigma(c0) folded in; the
-    // identity: (P c0, P c1), streaming); then per used giant row the inner sum over its used terms -- straight into the accumulator for the
-    // identity row; for a keyed row into a Q P block, its mod-down into S.ks.c01 (free: k_k3 unfused never writes it), that ciphertext's own
-    // digit lift and key product, and the rotate kernel's accumulate form -- and the last mod-down into `out`.  The key-switch scratch is
-    // the chunk's arena, reused from step to step: one stream only.  The store and the two blocks come from the pool before the first launch;
-    // the term table lies in the context's table ring (table_ring).
-    void linear_transform_bsgs(const BsgsPlan &pl, int L, u64 n, const u64 *in, const u64 *plain_qp, u64 *out)
-    {
-        use();
-        const size_t N = P.N, LN = (size_t)L * N, QP = LN + N, n_baby = pl.baby.size(), n_giant = pl.giant.size();
-        const int SP = (int)P.K - 1;
-        auto used_row = [&](size_t j) { return pl.row_first[j + 1] > pl.row_first[j]; };
-        // the elements of the used steps, babies then giant rows (a step no kept term names counts as the identity: no key, no table)
-        std::vector<uint32_t> elts(n_baby + n_giant, 1);
-        for (size_t i = 0; i < n_baby; ++i)
-            if (pl.slot[i] >= 0) elts[i] = pl.baby[i];
-        for (size_t j = 0; j < n_giant; ++j)
-            if (used_row(j)) elts[n_baby + j] = pl.giant[j];
-        hoist_require_keys(elts, "he355_linear_transform_bsgs"); // before anything is allocated
-        // the chunk: the key-switch chunk (chunk_ops: the batch chunk, halved until the arena is reserved); the pool blocks are sized for it
-        const size_t chunk = chunk_ops(n, L, false);
-        const PoolBlock store = scoped_block(bsgs_store_bytes((size_t)pl.slots, chunk, L, N));
-        const PoolBlock blk_e = pl.keyed_rows ? scoped_block(bsgs_block_bytes(chunk, L, N)) : PoolBlock();
-        const PoolBlock blk_a = scoped_block(bsgs_block_bytes(chunk, L, N));
-        const HoistSetup hs = hoist_setup(elts, false, false, "he355_linear_transform_bsgs"); // (the permuted keys: the first launches)
-        const uint32_t *const *bperm = hs.table.data(), *const *gperm = hs.table.data() + n_baby;
-        const u64 *const *bkey = hs.key.data(), *const *gkey = hs.key.data() + n_baby;
-        const uint32_t *ident = perm(1);
-        // the term table goes through the table ring: a pool block written by a host copy would be outside the stream order that makes a
-        // pool release safe (device_pool.h), and a second call could rewrite it under this call's queued launches
-        const size_t t_bytes = (pl.terms.size() * 4 + 255) & ~(size_t)255;
-        const uint32_t *const d_terms = reinterpret_cast<const uint32_t *>(table_ring(t_bytes));
-        HIPCHECK(hipMemcpy(const_cast<uint32_t *>(d_terms), pl.terms.data(), pl.terms.size() * 4, hipMemcpyHostToDevice));
-        u64 *const st = store.get();
-        for_each_chunk(n, L, chunk, false, [&](u64 off, u64 nc, int, Scratch S, hipEvent_t) {
-            const KernelEnv env = batch_env(0, true);
-            const KsBuffers &B = S.ks;
-            const u64 *a = in + off * 2 * LN;
-            u64 *o = out + off * 2 * LN;
-            u64 *eq = blk_e.get(), *ep = eq ? eq + nc * 2 * LN : nullptr; // [nc][2][L][N], then [nc][2][N]
-            u64 *aq = blk_a.get(), *ap = aq + nc * 2 * LN;
-            const u64 slot_words = nc * 2 * QP;
-            auto rows_inv_p = [&](u64 *p) {
-                PolyView pv = poly_view(p, 1, N, 1);
-                pv.prime_of[0] = (unsigned char)SP;
-                launch_rows_inv(env, pv, (u32)(nc * 2));
-            };
-            if (pl.keyed_babies) hoist_digit_lift(env, L, nc, off, in, B, false, ident);
-            for (size_t i = 0; i < n_baby; ++i) {
-                if (pl.slot[i] < 0) continue;
-                u64 *t = st + (u64)pl.slot[i] * slot_words; // [nc][2][L + 1][N]
-                if (!bkey[i]) {
-                    launch_bsgs_ident(env, L, nc, a, t);
-                    continue;
-                }
-                ++hoist_.key_products;
-                launch_k3(env, L, nc, B, bkey[i]);
-                launch_hoist_rot_qp(env, L, nc, B.t, B.tpr, a, bperm[i], t, QP, t + LN, QP, false);
-            }
-            bool first = true; // the accumulator starts with the first used row
-            for (size_t j = 0; j < n_giant; ++j) {
-                if (!used_row(j)) continue;
-                const uint32_t *terms = d_terms + 2 * pl.row_first[j];
-                const u64 n_terms = pl.row_first[j + 1] - pl.row_first[j];
-                const u64 *prow = plain_qp + (u64)j * n_baby * QP;
-                ++hoist_.inner_sums;
-                if (!gkey[j]) {
-                    launch_bsgs_inner(env, L, nc, st, prow, terms, n_terms, aq, ap, !first);
-                } else {
-                    launch_bsgs_inner(env, L, nc, st, prow, terms, n_terms, eq, ep, false);
-                    ++hoist_.mod_downs;
-                    rows_inv_p(ep);
-                    floor_step(env, SP, L, 2, nc, ep, B.e, {eq, 2 * LN, LN}, {}, {B.c01, B.c01_item_stride, LN});
-                    hoist_digit_lift(env, L, nc, 0, B.c01, B, false, ident);
-                    ++hoist_.key_products;
-                    launch_k3(env, L, nc, B, gkey[j]);
-                    launch_hoist_rot_qp(env, L, nc, B.t, B.tpr, B.c01, gperm[j], aq, LN, ap, N, !first);
-                }
-                first = false;
-            }
-            ++hoist_.mod_downs;
-            rows_inv_p(ap);
-            floor_step(env, SP, L, 2, nc, ap, B.e, {aq, 2 * LN, LN}, {}, {o, 2 * LN, LN});
-        });
-        HIPCHECK(hipGetLastError());
-    }
-    // he355_combine_scalars: one launch of k_scalar_combine over `n` ciphertexts.  The table -- [n_terms] {slab, level} pairs, the scalars
-    // [n_terms][L], the constant [L] -- takes one region of the table ring (table_ring): calls may follow each other without a sync.
-    struct PolyTerm { const u64 *p; int L; };
-    void combine_scalars(int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out)
-    {
-        use();
-        const size_t t_words = 2 * (size_t)n_terms, s_words = (size_t)n_terms * (size_t)L, words = t_words + s_words + (h_const ? (size_t)L : 0);
-        std::vector<u64> h(words);
-        for (size_t t = 0; t < n_terms; ++t) {
-            h[2 * t] = (u64)(uintptr_t)terms[t].p;
-            h[2 * t + 1] = (u64)terms[t].L; // (the kernel's row of the term: (c * size + k) * L_t + i)
-        }
-        std::memcpy(h.data() + t_words, h_scalars, s_words * 8);
-        if (h_const) std::memcpy(h.data() + t_words + s_words, h_const, (size_t)L * 8);
-        const size_t bytes = (words * 8 + 255) & ~(size_t)255;
-        u64 *d_tab = reinterpret_cast<u64 *>(table_ring(bytes));
-        HIPCHECK(hipMemcpy(d_tab, h.data(), words * 8, hipMemcpyHostToDevice));
-        ++poly_.combinations;
-        launch_scalar_combine(batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // he355_ckks_eval_poly: the plan's steps (poly_args.h), chunk by chunk in the key-switch chunk.  The power store and the temporaries are
-    // ONE pool block sized for the chunk, taken after the key check and before the first launch; every step is queued on the one stream.
-    void eval_poly(const PolyPlan &pl, int L, u64 n, const u64 *in, u64 *out)
-    {
-        use();
-        require_keyswitch();
-        if (!d_relin_) throw std::invalid_argument("he355_ckks_eval_poly: relinearization key not present"); // before anything is allocated
-        const size_t chunk = chunk_ops(n, L, false);
-        const PoolBlock blk = scoped_block((size_t)pl.words_per_ct * chunk * 8);
-        const size_t N = P.N;
-        Indexer pw{};
-        pw.b1 = 1; pw.pairwise = 1;
-        ++poly_.calls;
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            ++poly_.chunks;
-            auto at = [&](int b) -> u64 * {
-                const PolyBuf &B = pl.bufs[(size_t)b];
-                if (B.kind == 0) return const_cast<u64 *>(in) + off * 2 * (size_t)B.L * N;
-                if (B.kind == 1) return out + off * 2 * (size_t)B.L * N;
-                return blk.get() + B.off * nc;
-            };
-            for (const PolyStep &s : pl.steps) {
-                switch (s.op) {
-                case kPolyMulRelin:
-                    ++poly_.products;
-                    multiply_relin(s.L, nc, at(s.a), at(s.b), pw, true, at(s.dst));
-                    break;
-                case kPolyDrop:
-                    ++poly_.drops;
-                    mod_switch_drop(pl.bufs[(size_t)s.a].L, s.L, nc * 2, at(s.a), at(s.dst));
-                    break;
-                case kPolyRescale:
-                    ++poly_.rescales;
-                    rescale(s.L, 2, nc, at(s.a), at(s.dst));
-                    break;
-                case kPolyAdd:
-                    ++poly_.adds;
-                    addsub(s.L, 2, nc, at(s.a), at(s.b), pw, at(s.dst), false);
-                    break;
-                case kPolyCombine: {
-                    std::vector<PolyTerm> t;
-                    for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
-                    combine_scalars(s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst));
-                    break;
-                }
-                }
-            }
-        }
-    }
-    he355_poly_stats_t poly_stats(bool reset) { return take_stats(poly_, reset); }
-    // he355_ckks_mod_raise: row 0 of every polynomial copied on the stream, then chunk by chunk (the key-switch chunk, in ciphertexts) the
-    // inverse row pass of row 0 into a compact tail [nc size][N] from the pool (k_rows_inv_select, prime 0), the fused column kernel
-    // (k_raise_cols; N = 1024 has no column pass: k_raise_lift on the finished coefficients) and the forward row pass over rows 1 .. L_to - 1
-    // in place.  A chunk of fewer than CUs / 4 polynomials deals the targets of a column to raise_tsplit blocks, as the latency shape of the
-    // key switch does -- unless the latency shapes are switched off (he355_set_latency_max(0)).
-    void mod_raise(int L_in, int L_to, int size, u64 n, const u64 *in, u64 *out)
-    {
-        use();
-        const size_t N = P.N;
-        ++raise_.calls;
-        const u64 chunk = std::min<u64>(lim_.chunk, n);
-        const PoolBlock tail = L_to > 1 ? scoped_block((size_t)chunk * size * N * 8) : PoolBlock();
-        const bool split_on = lim_.lat_auto || lim_.lat_max > 0;
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 np = std::min<u64>(chunk, n - off) * (u64)size;
-            const u64 *src = in + off * size * (size_t)L_in * N;
-            u64 *dst = out + off * size * (size_t)L_to * N;
-            ++raise_.chunks;
-            HIPCHECK(hipMemcpy2DAsync(dst, (size_t)L_to * N * 8, src, (size_t)L_in * N * 8, N * 8, (size_t)np, hipMemcpyDeviceToDevice, stream_));
-            if (L_to > 1) {
-                launch_rows_inv_select(env_, 0, np, src, (u64)L_in * N, tail.get());
-                if (P.logn1 == 0) {
-                    ++raise_.streaming_launches;
-                    launch_raise_lift(env_, L_to, 1, np, tail.get(), dst);
-                } else {
-                    const int tsplit = split_on ? raise_tsplit(np, L_to, cus_) : 1;
-                    ++raise_.fused_launches;
-                    if (tsplit > 1) ++raise_.split_launches;
-                    launch_raise_cols(env_, L_to, np, tail.get(), dst, tsplit);
-                }
-                PolyView pv = poly_view(dst + N, L_to - 1, N, L_to);
-                pv.item_stride = (u64)L_to * N;
-                for (int j = 1; j < L_to; ++j) pv.prime_of[j - 1] = (unsigned char)j;
-                launch_rows_fwd(env_, pv, (u32)np);
-            }
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    // he355_ckks_lift_centred: one streaming launch
-    void lift_centred(int L_to, u64 n_polys, const u64 *coeff, u64 *out)
-    {
-        use();
-        ++raise_.streaming_launches;
-        launch_raise_lift(env_, L_to, 0, n_polys, coeff, out);
-        HIPCHECK(hipGetLastError());
-    }
-    he355_raise_stats_t raise_stats(bool reset) { return take_stats(raise_, reset); }
-    // plain_ntt [n][L][N] NTT form -> plain_qp [n][L + 1][N]: the rows copied and row L = NTT_P of the coefficients of row 0, centred
-    // (he355_plain_extend_special).  mismatch (optional, one device word): the (coefficient, prime >= 1) pairs that disagree with row 0.
-    void plain_extend_special(int L, u64 n, const u64 *plain_ntt, u64 *plain_qp, u64 *mismatch)
-    {
-        use();
-        const size_t N = P.N;
-        const int Lc = mismatch ? L : 1, SP = (int)P.K - 1;
-        if (mismatch) HIPCHECK(hipMemsetAsync(mismatch, 0, 8, stream_));
-        const u64 chunk = std::max<u64>(1, std::min<u64>(n, ((u64)1 << 27) / ((u64)Lc * N * 8)));
-        const PoolBlock tmp = scoped_block((size_t)chunk * Lc * N * 8);
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 c = std::min<u64>(chunk, n - off);
-            const u64 *src = plain_ntt + off * L * N;
-            u64 *dst = plain_qp + off * (L + 1) * N;
-            HIPCHECK(hipMemcpy2DAsync(tmp.get(), (size_t)Lc * N * 8, src, (size_t)L * N * 8, (size_t)Lc * N * 8, (size_t)c, hipMemcpyDeviceToDevice, stream_));
-            launch_ntt_inverse(env_, poly_view(tmp.get(), Lc, N, Lc), (u32)c);
-            launch_plain_extend(env_, L, c, src, tmp.get(), Lc, dst, mismatch);
-            PolyView pv = poly_view(dst + (size_t)L * N, 1, N, 1);
-            pv.item_stride = (u64)(L + 1) * N;
-            pv.prime_of[0] = (unsigned char)SP;
-            launch_ntt_forward(env_, pv, (u32)c);
-        }
-        HIPCHECK(hipGetLastError());
     }
     void require_keyswitch() const
     {
@@ -1443,8 +1102,8 @@ public:
             GroupTables gt = upload_groups(perms, keys, src_block, mult, (u32)n);
             PoolBlock cur(pool_, G * bytes); // (taken while the previous level's block is still held ...)
             if (in_k3) { gt.g.sum_out = out; gt.g.count = gt.d_mult; }
-            if (apply_galois_grouped(L, G * n, src, gt.g, cur.get())) ++paths_.level_sums_in_k3;
-            else { ++paths_.level_sums_by_kernel; launch_sum_groups(env_, L, n, (u32)G, cur.get(), gt.d_mult, out); }
+            if (apply_galois_grouped(L, G * n, src, gt.g, cur.get())) ++count_.paths.level_sums_in_k3;
+            else { ++count_.paths.level_sums_by_kernel; launch_sum_groups(env_, L, n, (u32)G, cur.get(), gt.d_mult, out); }
             held = std::move(cur); // (... which leaves with `cur` at the end of this round, before the next level takes its own)
             src = held.get();
             switches += G;
@@ -1616,7 +1275,7 @@ public:
     {
         use();
         const auto lds_limit = behz_cols_lds_limit(env_);
-        he355_bfv_multiply_stats_t s = take_stats(mul_routes_, reset);
+        he355_bfv_multiply_stats_t s = take_stats(count_.mul_routes, reset);
         s.lds_limit = lds_limit;
         return s;
     }
@@ -1658,11 +1317,11 @@ public:
     void behz_extend_fwd_cols(const BehzDev &Z, const BehzSrc &src, bool fuse_cols, u64 n_items, u64 *xq, u64 *xb, PolyView vq, PolyView vb)
     {
         if (fuse_cols) {
-            ++mul_routes_.cols_fused;
-            mul_routes_.cols_exact += launch_behz_extend_cols(env_, Z, src, n_items, xq, xb);
+            ++count_.mul_routes.cols_fused;
+            count_.mul_routes.cols_exact += launch_behz_extend_cols(env_, Z, src, n_items, xq, xb);
         } else {
-            ++mul_routes_.cols_unfused;
-            mul_routes_.coef_wide += launch_behz_extend(env_, Z, src, n_items, xq, xb);
+            ++count_.mul_routes.cols_unfused;
+            count_.mul_routes.coef_wide += launch_behz_extend(env_, Z, src, n_items, xq, xb);
             vq.base = xq; launch_cols_fwd(env_, vq, (u32)(n_items * 2));
             vb.base = xb; launch_cols_fwd(env_, vb, (u32)(n_items * 2));
         }
@@ -1671,13 +1330,13 @@ public:
     void behz_inv_cols_floor(const BehzDev &Z, bool fuse_cols, u64 nc, u64 *dq, u64 *ds, u64 *out, PolyView vq, PolyView vb)
     {
         if (fuse_cols) {
-            ++mul_routes_.cols_fused;
-            mul_routes_.cols_exact += launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out);
+            ++count_.mul_routes.cols_fused;
+            count_.mul_routes.cols_exact += launch_behz_cols_floor_sk(env_, Z, nc, dq, ds, out);
         } else {
-            ++mul_routes_.cols_unfused;
+            ++count_.mul_routes.cols_unfused;
             vq.base = dq; launch_cols_inv(env_, vq, (u32)(nc * 3));
             vb.base = ds; launch_cols_inv(env_, vb, (u32)(nc * 3));
-            mul_routes_.coef_wide += launch_behz_floor_sk(env_, Z, nc, dq, ds, out);
+            count_.mul_routes.coef_wide += launch_behz_floor_sk(env_, Z, nc, dq, ds, out);
         }
     }
     void bfv_multiply3(int L, u64 n, const u64 *a, const u64 *b, Indexer3 ix, u64 *out)
@@ -1711,15 +1370,15 @@ public:
         }
         if (lists) {
             src.lists = 1;
-            ++mul_routes_.calls_lists;
+            ++count_.mul_routes.calls_lists;
             u64 *eq = arena.p, *eb = eq + (size_t)g.n_cts * 2 * L * N, *dq = eb + (size_t)g.n_cts * 2 * S * N, *ds = dq + c * 3 * L * N;
             behz_extend_fwd_cols(Z, src, fuse_cols, g.n_cts, eq, eb, vq, vb);
             vq.base = eq; launch_rows_fwd(env_, vq, (u32)(g.n_cts * 2));
             vb.base = eb; launch_rows_fwd(env_, vb, (u32)(g.n_cts * 2));
             for (u64 off = 0; off < n; off += c) {
                 const u64 nc = std::min<u64>(c, n - off);
-                ++mul_routes_.chunks;
-                ++(launch_behz_tensor_inv(env_, Z, src, nc, off, eq, eb, dq, ds) ? mul_routes_.inv_dual : mul_routes_.inv_split);
+                ++count_.mul_routes.chunks;
+                ++(launch_behz_tensor_inv(env_, Z, src, nc, off, eq, eb, dq, ds) ? count_.mul_routes.inv_dual : count_.mul_routes.inv_split);
                 behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
             }
             HIPCHECK(hipGetLastError());
@@ -1727,7 +1386,7 @@ public:
         }
         c = halve_until_fit(c, [&](size_t k) { return try_reserve(&arena, 1, g.per_op * k * 8); });
         if (!c) throw OutOfDeviceMemory("HIP error: out of device memory: the BFV multiply scratch of one ciphertext does not fit");
-        ++mul_routes_.calls_pairs;
+        ++count_.mul_routes.calls_pairs;
         u64 *xq = arena.p, *xb = xq + c * 4 * L * N, *dq = xb + c * 4 * S * N, *ds = dq + c * 3 * L * N;
         for (u64 off = 0; off < n; off += c) {
             const u64 nc = std::min<u64>(c, n - off);
@@ -1736,8 +1395,8 @@ public:
             // passes and steps (6)-(8)
             src.op_offset = off;
             behz_extend_fwd_cols(Z, src, fuse_cols, nc * 2, xq, xb, vq, vb);
-            ++mul_routes_.chunks;
-            ++(launch_behz_rows_tensor(env_, Z, nc, xq, xb, dq, ds) ? mul_routes_.rows_dual : mul_routes_.rows_split);
+            ++count_.mul_routes.chunks;
+            ++(launch_behz_rows_tensor(env_, Z, nc, xq, xb, dq, ds) ? count_.mul_routes.rows_dual : count_.mul_routes.rows_split);
             behz_inv_cols_floor(Z, fuse_cols, nc, dq, ds, out + off * 3 * (size_t)L * N, vq, vb);
         }
         HIPCHECK(hipGetLastError());
@@ -1835,500 +1494,6 @@ public:
         a_lo = idx_a(ix, 0); a_n = idx_a(ix, n - 1) - a_lo + 1;
         b_lo = ix.b_base; b_n = ix.pairwise ? n : std::min<u64>(n, ix.b1);
     }
-    // Evaluator::mod_switch_to (BFV): [n][size][L][N] -> [n][size][L_to][N], L - L_to divide-and-round steps in one launch
-    void bfv_mod_switch(int L, int L_to, int size, u64 n, const u64 *in, u64 *out)
-    {
-        use();
-        check_level(L);
-        if (L_to < 1 || L_to > L) throw std::invalid_argument("target level out of range");
-        check_size(size, 1, 3);
-        if (L > kBfvLevelMaxL) throw std::invalid_argument("BFV modulus switching supports up to 16 data primes");
-        const size_t N = P.N, n_polys = (size_t)n * size;
-        if (ranges_overlap(in, n_polys * L * N, out, n_polys * L_to * N)) throw std::invalid_argument("he355_bfv_mod_switch: `out` overlaps `in`");
-        if (!n) return;
-        if (L_to == L) {
-            HIPCHECK(hipMemcpyAsync(out, in, n_polys * L * N * 8, hipMemcpyDeviceToDevice, stream_));
-            return;
-        }
-        launch_bfv_mod_switch(env_, bfv_drop_table_dev(), (int)P.Ltop, L, L_to, n_polys, in, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // Evaluator::add_plain / sub_plain (BFV): out = ct +- (Delta_L(plain), 0, ..); plain [.][N] mod t
-    void bfv_addsub_plain(int L, int size, u64 n, const u64 *ct, const u64 *plain, Indexer ix, u64 *out, bool sub)
-    {
-        use();
-        check_level(L);
-        check_size(size, 1, 3);
-        if (!n) return;
-        const size_t N = P.N, ctn = (size_t)size * L * N;
-        u64 a_lo, a_n, b_lo, b_n;
-        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
-        // in place exactly where every ciphertext serves one result (pairwise, or one plaintext per ciphertext): result r then reads what it writes
-        const bool in_place = out == ct + a_lo * ctn && (ix.pairwise || ix.b1 == 1);
-        if (!in_place && ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn)) throw std::invalid_argument("he355_bfv_add_plain / sub_plain: `out` overlaps the ciphertexts (in place only when each serves one result)");
-        if (ranges_overlap(out, n * ctn, plain + b_lo * N, b_n * N)) throw std::invalid_argument("he355_bfv_add_plain / sub_plain: `out` overlaps the plaintexts");
-        launch_bfv_addsub_plain(env_, L, size, n, ct, plain, ix, out, bfv_delta(L), sub);
-        HIPCHECK(hipGetLastError());
-    }
-    // Evaluator::multiply_plain (BFV, multiply_plain_normal): every polynomial times the centred lift of the plaintext, negacyclic.
-    // Each distinct plaintext of the call is lifted and transformed once under the L primes (on stream_, ahead of the chunk loop: the
-    // fork event chunk 0 records orders the second stream behind it, and behind whatever produced the operands); a chunk is three
-    // launches -- forward column pass ct -> out, the fused row kernel in place on out, inverse column pass.
-    void bfv_multiply_plain(int L, int size, u64 n, const u64 *ct, const u64 *plain, Indexer ix, u64 *out)
-    {
-        use();
-        check_level(L);
-        check_size(size, 1, 3);
-        if (!n) return;
-        const size_t N = P.N, LN = (size_t)L * N, ctn = (size_t)size * LN;
-        u64 a_lo, a_n, b_lo, b_n;
-        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
-        if (ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn) || ranges_overlap(out, n * ctn, plain + b_lo * N, b_n * N))
-            throw std::invalid_argument("he355_bfv_multiply_plain: `out` overlaps an operand");
-        if (!try_reserve(&arena_[kBfv], 1, b_n * LN * 8)) throw OutOfDeviceMemory("HIP error: out of device memory: the prepared plaintexts of he355_bfv_multiply_plain do not fit");
-        u64 *prep = arena_[kBfv].p;
-        plain_to_ntt(L, b_n, plain + b_lo * N, prep);
-        for_each_chunk(n, L, chunk_ops(n, L, true), true, [&](u64 off, u64 nc, int which, const Scratch &, hipEvent_t fork) {
-            const KernelEnv env = batch_env(which);
-            launch_bfv_mp_cols_fwd(env, L, size, nc, off, ct, ix, out);
-            launch_bfv_mp_rows(env, L, size, nc, off, ct, prep, ix, out);
-            launch_cols_inv(env, poly_view(out + off * ctn, size * L, N, L), (u32)nc);
-            if (fork) HIPCHECK(hipEventRecord(fork, env.stream));
-        });
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- NTT-form BFV operands (he355_kernels_bfv_ntt.hip) -------------------------------------------------------------------
-    // Evaluator::transform_to_ntt_inplace / transform_from_ntt_inplace of ciphertexts: [n][size][L][N], polynomial (k, i) under prime i.
-    // In place, or apart (copied, then transformed where it lands).  The library does not track which form a slab is in.
-    void bfv_transform(int L, int size, u64 n, const u64 *in, u64 *out, bool inverse)
-    {
-        const char *what = inverse ? "he355_bfv_transform_from_ntt" : "he355_bfv_transform_to_ntt";
-        use();
-        check_level(L);
-        check_size(size, 1, 3);
-        const size_t N = P.N, words = (size_t)n * size * L * N;
-        if (out != in && ranges_overlap(in, words, out, words)) throw std::invalid_argument(std::string(what) + ": `out` overlaps `in` (in place: the same pointer)");
-        if (n * size > 0xffffffffull) throw std::invalid_argument(std::string(what) + ": too many polynomials for one call");
-        if (!n) return;
-        if (out != in) HIPCHECK(hipMemcpyAsync(out, in, words * 8, hipMemcpyDeviceToDevice, stream_));
-        const PolyView v = poly_view(out, L, N, L);
-        if (inverse) launch_ntt_inverse(env_, v, (u32)(n * size));
-        else launch_ntt_forward(env_, v, (u32)(n * size));
-        HIPCHECK(hipGetLastError());
-    }
-    // Evaluator::transform_to_ntt_inplace(Plaintext, parms_id): plain [n][N] mod t -> out [n][L][N], the centred lift he355_bfv_multiply_plain
-    // multiplies by, transformed under primes 0 .. L-1
-    void bfv_plain_to_ntt(int L, u64 n, const u64 *plain, u64 *out)
-    {
-        use();
-        check_level(L);
-        const size_t N = P.N;
-        if (ranges_overlap(out, (size_t)n * L * N, plain, (size_t)n * N)) throw std::invalid_argument("he355_bfv_plain_to_ntt: `out` overlaps the plaintexts");
-        if (n > 0xffffffffull) throw std::invalid_argument("he355_bfv_plain_to_ntt: too many plaintexts for one call");
-        if (!n) return;
-        plain_to_ntt(L, n, plain, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // Evaluator::multiply_plain on NTT-form operands (multiply_plain_ntt): every polynomial times the NTT-form plaintext, k_plain_op's product
-    void bfv_multiply_plain_ntt(int L, int size, u64 n, const u64 *ct, const u64 *pt, Indexer ix, u64 *out)
-    {
-        use();
-        check_level(L);
-        check_size(size, 1, 3);
-        if (!n) return;
-        const size_t LN = (size_t)L * P.N, ctn = (size_t)size * LN;
-        u64 a_lo, a_n, b_lo, b_n;
-        indexer_span(ix, n, a_lo, a_n, b_lo, b_n);
-        // in place exactly where every ciphertext serves one result: result r then reads the words it writes (as he355_bfv_add_plain)
-        const bool in_place = out == ct + a_lo * ctn && (ix.pairwise || ix.b1 == 1);
-        if (!in_place && ranges_overlap(out, n * ctn, ct + a_lo * ctn, a_n * ctn)) throw std::invalid_argument("he355_bfv_multiply_plain_ntt: `out` overlaps the ciphertexts (in place only when each serves one result)");
-        if (ranges_overlap(out, n * ctn, pt + b_lo * LN, b_n * LN)) throw std::invalid_argument("he355_bfv_multiply_plain_ntt: `out` overlaps the plaintexts");
-        launch_plain_op(env_, L, size, n, ct, pt, ix, out, 0);
-        HIPCHECK(hipGetLastError());
-    }
-    // out(i, j) = sum_k ct(i, k) (.) pt(k, j): the multiply_plain / add_inplace loop of a plaintext matrix x encrypted vector, one launch on
-    // the context's stream (nothing to fork: no scratch, no second stream)
-    void bfv_multiply_plain_accumulate(int L, int size, u64 rows, u64 cols, u64 inner, const u64 *ct, u64 ct_stride_i, u64 ct_stride_k, const u64 *pt,
-                                       u64 pt_stride_k, u64 pt_stride_j, u64 *out)
-    {
-        use();
-        check_level(L);
-        check_size(size, 1, 3);
-        if (inner < 1 || inner > 0x7fffffff) throw std::invalid_argument("inner dimension out of range");
-        const u64 n = rows * cols;
-        if (!n) return;
-        const size_t LN = (size_t)L * P.N, ctn = (size_t)size * LN;
-        const size_t n_ct = (size_t)((inner - 1) * ct_stride_k + (rows - 1) * ct_stride_i + 1), n_pt = (size_t)((inner - 1) * pt_stride_k + (cols - 1) * pt_stride_j + 1);
-        if (ranges_overlap(out, n * ctn, ct, n_ct * ctn) || ranges_overlap(out, n * ctn, pt, n_pt * LN))
-            throw std::invalid_argument("he355_bfv_multiply_plain_accumulate: `out` overlaps an operand");
-        launch_bfv_plain_mac(env_, L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- monomial multiply and oblivious query expansion (he355_kernels_bfv_expand.hip) -------------------------------------------
-    // The argument checks that need no device are bfv_pir_args.h's: the C ABI makes them before it asks for one and passes on their plan.
-    // out = in X^e for every polynomial of [n][size][L][N], coefficient form: one launch
-    void bfv_multiply_monomial(int L, int size, u64 n, const u64 *in, u32 e, u64 *out)
-    {
-        use();
-        const size_t words = (size_t)n * size * L * P.N;
-        if (ranges_overlap(in, words, out, words)) throw std::invalid_argument("he355_bfv_multiply_monomial: `out` overlaps `in`");
-        launch_bfv_shift(env_, L, n * size * L, in, nullptr, e, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // Oblivious expansion (Angel et al., "PIR with compressed queries", Alg. 3): in [n][2][L][N] -> out [count][n][2][L][N], child k of query r
-    // at index k n + r.  Level j (s = 2^j) turns the s n nodes it reads, node k of query r at k n + r, into 2 s n: ONE batched key switch
-    // with the node itself as the addend leaves the even children c + g where the nodes' indices are (k_bfv_galois forms c0 + sigma(c0) and
-    // passes c1 through, k_bfv_tail_fin adds the switched part; the addend is only read, so it may be the input), and one k_bfv_shift
-    // launch writes the odd children X^(-s) (2c - even) behind them, at (k + s) n + r -- the last level only those below `count`.  The
-    // levels alternate between `out` and one pool block of 2^(d-1) n ciphertexts (what level d - 2 writes), the parity chosen so that
-    // level d - 1 lands in `out`; everything runs on the context's stream.  Every refusal comes before the first launch.
-    void bfv_expand(const BfvExpandPlan &pl, int L, u64 n, const u64 *in, u64 count, u64 *out)
-    {
-        use();
-        const int d = pl.depth;
-        const size_t N = P.N, ctn = 2 * (size_t)L * N;
-        if (d) require_keyswitch();
-        for (int j = 0; j < d; ++j) {
-            const uint32_t elt = (uint32_t)(N >> j) + 1;
-            if (!galois_key(elt)) throw std::invalid_argument("he355_bfv_expand: Galois key of element " + std::to_string(elt) + " not present");
-        }
-        if (ranges_overlap(in, n * ctn, out, count * n * ctn)) throw std::invalid_argument("he355_bfv_expand: `out` overlaps `in`");
-        if (!n) return;
-        if (!d) {
-            HIPCHECK(hipMemcpyAsync(out, in, n * ctn * 8, hipMemcpyDeviceToDevice, stream_));
-            return;
-        }
-        const PoolBlock tmp = d > 1 ? scoped_block(((size_t)n << (d - 1)) * ctn * 8) : PoolBlock();
-        const u64 *cur = in;
-        for (int j = 0; j < d; ++j) {
-            const u64 s = (u64)1 << j, odd = std::min<u64>(s, count - s); // (count - s < s at the last level only)
-            u64 *dst = (d - 1 - j) % 2 == 0 ? out : tmp.get();
-            apply_galois(L, s * n, cur, (uint32_t)(N >> j) + 1, dst, cur);
-            launch_bfv_shift(env_, L, odd * n * 2 * L, cur, dst, (u32)(2 * N - s), dst + s * n * ctn);
-            cur = dst;
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    // The expansion's transpose (Chen, Dai, Kim, Song, "Efficient homomorphic conversion between (ring) LWE ciphertexts", Alg. 2): input k of
-    // result r at ciphertext k stride_k + r stride_r of `in` -> out [n][2][L][N].  Level j = d-1 .. 0 (s = 2^j) is ONE k_bfv_merge launch over the
-    // s n pairs of all results, pair k n + r, which leaves S = even + X^s odd and D = even - X^s odd (S = D = even where slot k + s is absent:
-    // the first level only) in two slabs, and ONE batched key switch of D with S as its addend, which leaves slot k of result r at k n + r:
-    // only the first level reads through the strides.  One pool block holds S, D and the level's output, each 2^(d-1) n ciphertexts, the first
-    // level's sizes (the later levels use the head of each; a level's output is consumed by the next merge launch before the next key switch
-    // writes there); the last level lands in `out`.  Everything runs on the context's stream; every refusal, the block's included, comes
-    // before the first launch.
-    void bfv_merge(const BfvMergePlan &pl, int L, u64 n, u64 count, const u64 *in, u64 stride_k, u64 stride_r, u64 *out)
-    {
-        use();
-        const int d = pl.depth;
-        const size_t N = P.N, ctn = 2 * (size_t)L * N;
-        if (d) require_keyswitch();
-        for (int j = d - 1; j >= 0; --j) {
-            const uint32_t elt = (uint32_t)(N >> j) + 1;
-            if (!galois_key(elt)) throw std::invalid_argument("he355_bfv_merge: Galois key of element " + std::to_string(elt) + " not present");
-        }
-        if (!n) return;
-        if (!d) { // count == 1: result r is its one input
-            if (stride_r == 1 || n == 1) HIPCHECK(hipMemcpyAsync(out, in, n * ctn * 8, hipMemcpyDeviceToDevice, stream_));
-            else
-                for (u64 r = 0; r < n; ++r) HIPCHECK(hipMemcpyAsync(out + r * ctn, in + r * stride_r * ctn, ctn * 8, hipMemcpyDeviceToDevice, stream_));
-            return;
-        }
-        const PoolBlock blk = scoped_block((size_t)pl.scratch_cts * ctn * 8);
-        u64 *S = blk.get(), *D = S + pl.half * ctn, *mid = D + pl.half * ctn; // mid: unused (and not there) when d == 1
-        const u64 *cur = in;
-        u64 have = count; // slots present
-        for (int j = d - 1; j >= 0; --j) {
-            const u64 s = (u64)1 << j;
-            launch_bfv_merge(env_, L, n, s, (have - s) * n, cur, stride_k, stride_r, S, D);
-            u64 *dst = j ? mid : out;
-            apply_galois(L, s * n, D, (uint32_t)(N >> j) + 1, dst, S);
-            cur = dst; stride_k = n; stride_r = 1; have = s;
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- ciphertext decomposition for recursive (two-dimensional) PIR (he355_kernels_bfv_digits.hip) ---------------------------------
-    // [n][size][L][N] -> [n][F][N] coefficients mod t: one streaming launch
-    void bfv_decompose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *plain)
-    {
-        use();
-        launch_bfv_digits(env_, pl.tab, L, size, n, ct, plain);
-        HIPCHECK(hipGetLastError());
-    }
-    // the inverse: [n][F][N] -> [n][size][L][N], canonical whatever the digits are
-    void bfv_compose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *plain, u64 *ct)
-    {
-        use();
-        launch_bfv_undigits(env_, pl.tab, L, size, n, plain, ct);
-        HIPCHECK(hipGetLastError());
-    }
-    // [n][size][L][N] -> [n][F][L_out][N], by definition bfv_decompose + bfv_plain_to_ntt(L_out, n F).  N >= 2048: the fused column pass
-    // reads the ciphertext, cuts, lifts and writes out(f, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is
-    // routed to the composition, its [n][F][N] slab a pool block (a second identical call allocates nothing).
-    void bfv_decompose_ntt(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, int L_out, u64 *out)
-    {
-        use();
-        const size_t N = P.N, F = pl.F;
-        if (!n) return;
-        if (env_.logn1 == 0) {
-            ++routes_.digits_routed;
-            const PoolBlock tmp = scoped_block((size_t)n * F * N * 8);
-            launch_bfv_digits(env_, pl.tab, L, size, n, ct, tmp.get());
-            plain_to_ntt(L_out, n * F, tmp.get(), out);
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        ++routes_.digits_fused;
-        launch_bfv_digits_cols_fwd(env_, pl.tab, L, size, n, ct, L_out, P.plain_modulus, out);
-        launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)(n * F));
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- the external product RGSW x ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) ----------
-    // [n][size][L][N] -> [n][size E][N], the plain integer digits of width v: he355_bfv_decompose's launch with the width-v table
-    void bfv_gadget_decompose(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *digits)
-    {
-        use();
-        launch_bfv_digits(env_, pl.tab, L, size, n, ct, digits);
-        HIPCHECK(hipGetLastError());
-    }
-    // ROUTED: a block of the column pass walks all E_i L digit columns of its residue one after the other, so a batch of fewer blocks than
-    // kGadgetColsMinBlocks (one per CU) leaves most of the chip idle and lost to the composition where it was measured (one ciphertext:
-    // profiles/bfv_external_product.txt); such a batch takes N = 1024's path, whose work is spread over the digit polynomials.
-    static constexpr u64 kGadgetColsMinBlocks = 256;
-    // does a cut of `cts` ciphertexts of `size` polynomials take the column pass?
-    bool gadget_cols(u64 cts, int size, int L) const { return env_.logn1 != 0 && cts * size * L * 4 >= kGadgetColsMinBlocks; }
-    // the cut of ciphertext (a, b) at index a stride_a + b stride_b into NTT-form digit polynomials [(a n_b + b) size E + f][L][N]: N >= 2048 the
-    // fused column pass and the row pass in place, N = 1024 the digits under every prime and the whole transform in place.  No scratch.
-    void gadget_cut_ntt(const BfvDigitTab &tab, int L, int size, u64 n_a, u64 n_b, const u64 *ct, u64 stride_a, u64 stride_b, u64 *out)
-    {
-        const u32 items = (u32)(n_a * n_b * size * tab.total);
-        const bool cols = gadget_cols(n_a * n_b, size, L);
-        ++(cols ? routes_.cut_cols : routes_.cut_stream);
-        launch_bfv_gadget_cut(env_, tab, L, size, n_a, n_b, ct, stride_a, stride_b, out, cols);
-        forward_rows_or_full(cols, poly_view(out, L, P.N, L), items);
-    }
-    // [n][size][L][N] -> [n][size E][L][N]: by definition bfv_gadget_decompose, then he355_ntt_forward of every digit polynomial under every prime
-    void bfv_gadget_decompose_ntt(const BfvDigitPlan &pl, int L, int size, u64 n, const u64 *ct, u64 *out)
-    {
-        use();
-        if (!n) return;
-        gadget_cut_ntt(pl.tab, L, size, n, 1, ct, 1, 0, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // `rows` encryptions of zero, he355_encrypt_zero(seed, first_index + row), for a plant kernel that cuts them to the first L primes: made
-    // in `out` itself at L == L_top (the kernel then works in place, the block returned is empty), below it in the pool block returned
-    PoolBlock zeros_at_level(int L, u64 rows, u64 seed, u64 first_index, u64 *out)
-    {
-        PoolBlock hold = (size_t)L < P.Ltop ? scoped_block((size_t)rows * 2 * P.Ltop * P.N * 8) : PoolBlock();
-        encrypt(rows, nullptr, seed, first_index, hold ? hold.get() : out);
-        return hold;
-    }
-    // plain [n][N] mod t -> out [n][2E][2][L][N] NTT form: row f of RGSW r is he355_encrypt_zero(seed, first_index + r 2E + f) cut to the first L
-    // primes, plus the planted term.
-    void bfv_rgsw_encrypt(const BfvRgswPlan &pl, int L, u64 n, const u64 *plain, u64 seed, u64 first_index, u64 *out)
-    {
-        use();
-        if (!n) return;
-        if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt: public key not set");
-        const PoolBlock hold = zeros_at_level(L, pl.rows, seed, first_index, out);
-        const u64 *zero = hold ? hold.get() : out;
-        launch_bfv_rgsw_plant(env_, pl.tab, L, (int)P.Ltop, n, zero, plain, P.plain_modulus, out);
-        launch_ntt_forward(env_, poly_view(out, L, P.N, L), (u32)(pl.rows * 2));
-        HIPCHECK(hipGetLastError());
-    }
-    // out(r) = sum_kappa rgsw(r, kappa) [.] ct(r, kappa), coefficient form in and out.  By definition bfv_gadget_decompose_ntt of the inner
-    // ciphertexts of each result, he355_bfv_multiply_plain_accumulate(L, 2, 1, 1, inner 2E) with the RGSW rows as the ciphertext operand, and
-    // he355_bfv_transform_from_ntt.  The digit slab of a pass of results (bfv_gadget_pass: about kGadgetPassPolys digit polynomials, at least
-    // one result) is one pool block; a pass is the cut, its row pass and one batched multiply-accumulate; one inverse transform ends the call.
-    void bfv_external_product(const BfvExternalPlan &pl, int L, u64 n, u64 inner, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r,
-                              u64 rg_stride_k, u64 *out)
-    {
-        use();
-        if (!n) return;
-        const size_t N = P.N, LN = (size_t)L * N;
-        const u32 rows = pl.rows;
-        const u64 terms = pl.terms, pass = pl.pass;
-        const PoolBlock slab = scoped_block((size_t)pass * terms * LN * 8);
-        for (u64 r0 = 0; r0 < n; r0 += pass) {
-            const u64 c = std::min<u64>(pass, n - r0);
-            gadget_cut_ntt(pl.tab, L, 2, c, inner, ct + r0 * ct_stride_r * 2 * LN, ct_stride_r, ct_stride_k, slab.get());
-            const u64 *rg = rgsw + r0 * rg_stride_r * rows * 2 * LN;
-            // ROUTED: a call for ONE result whose RGSW rows follow one another is the composition's own inner product, and
-            // k_bfv_plain_mac's 1 x 1 form (two terms' loads in flight) measured 2-17 % ahead of k_bfv_gadget_mac there
-            // (profiles/bfv_external_product.txt).  Only n == 1 was measured, so only n == 1 is routed: a pass that holds one result
-            // of many (inner 2E above 2048, or a ragged last pass) stays with k_bfv_gadget_mac.
-            const bool plain = n == 1 && (inner == 1 || rg_stride_k == 1);
-            ++routes_.passes;
-            ++(plain ? routes_.mac_plain : routes_.mac_gadget);
-            if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, terms, rg, 1, 1, slab.get(), 1, 1, out + r0 * 2 * LN);
-            else launch_bfv_gadget_mac(env_, L, c, inner, rows, slab.get(), rg, rg_stride_r, rg_stride_k, out + r0 * 2 * LN);
-        }
-        launch_ntt_inverse(env_, poly_view(out, L, N, L), (u32)(n * 2));
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- the selection tree (he355_kernels_bfv_gadget.hip; the definition: include/he355.h) ---------------------------------------------------
-    // out(r) = the fold of result r's `count` leaves under its depth RGSW bits: level j turns the c_j nodes of every result into c_(j+1), node'(p) =
-    // node(2p) + RGSW(r, j) [.] (node(2p+1) - node(2p)), the node without a partner copied.  Nodes lie result-major, [n][c_j]: level 0 reads
-    // the caller's leaves through its strides, the later levels alternate between the two halves of one pool block, the last one lands in `out`.
-    // A level is a pass loop over all pairs of all results (pl.pass of them per trip through the second pool block: 2E digit polynomials per
-    // pair and, behind them, the pass's sums -- at N = 1024 the level's): the DIFF cut (bfv_external_product's route rule for that many results), its row pass, one
-    // multiply-accumulate (k_bfv_plain_mac where the level has exactly one pair) into the sums, the inverse row pass in place and the
-    // inverse column pass that adds the even node and stores the next level's node.  N = 1024 has no column pass: ROUTED to
-    // launch_ntt_inverse and a streaming add.  One copy launch per level moves the nodes without a partner.  Both blocks are taken before the
-    // first launch; everything runs on the context's stream.
-    void bfv_select(const BfvSelectPlan &pl, int L, u64 n, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *rgsw, u64 rg_stride_r, u64 rg_stride_j, u64 *out)
-    {
-        use();
-        if (!n) return;
-        const size_t N = P.N, LN = (size_t)L * N, ctn = 2 * LN;
-        const int m = pl.depth;
-        if (!m) { // count == 1: result r is its one leaf
-            launch_bfv_select_copy(env_, L, n, 0, ct, ct_stride_r, ct_stride_k, out, 1);
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        const u32 rows = pl.rows;
-        const PoolBlock nodes = pl.node_cts ? scoped_block((size_t)pl.node_cts * ctn * 8) : PoolBlock();
-        const PoolBlock slab = scoped_block((size_t)pl.slab_polys * N * 8);
-        u64 *half[2] = {nodes ? nodes.get() : nullptr, nodes ? nodes.get() + n * pl.c[1] * ctn : nullptr};
-        u64 *sums = slab.get() + pl.pass * rows * LN;
-        // N = 1024: the sums of a whole LEVEL lie behind the digits and the routed tail runs once per level, not per pass -- the ring is
-        // launch-bound, and per pass the two extra launches lost to the composition at 16 passes (profiles/bfv_select.txt, part 2b)
-        const bool level_tail = env_.logn1 == 0;
-        const u64 *cur = ct;
-        u64 stride_a = ct_stride_r, stride_b = ct_stride_k;
-        for (int j = 0; j < m; ++j) {
-            const u64 group = pl.c[j] / 2, pairs = pl.pairs(j), c_next = pl.c[j + 1];
-            u64 *dst = j == m - 1 ? out : half[j & 1];
-            const u64 *rg = rgsw + (size_t)j * rg_stride_j * rows * ctn;
-            for (u64 p0 = 0; p0 < pairs; p0 += pl.pass) {
-                const u64 c = std::min<u64>(pl.pass, pairs - p0);
-                const bool cols = gadget_cols(c, 2, L);
-                u64 *psum = sums + (level_tail ? p0 * ctn : 0);
-                ++routes_.passes;
-                ++(cols ? routes_.select_cols : routes_.select_stream);
-                launch_bfv_select_cut(env_, pl.tab, L, group, p0, c, cur, stride_a, stride_b, slab.get(), cols);
-                forward_rows_or_full(cols, poly_view(slab.get(), L, N, L), (u32)(c * rows));
-                // ROUTED as bfv_external_product routes one result: a level of exactly one pair is k_bfv_plain_mac's 1 x 1 form
-                const bool plain = pairs == 1;
-                ++(plain ? routes_.mac_plain : routes_.mac_gadget);
-                if (plain) launch_bfv_plain_mac(env_, L, 2, 1, 1, rows, rg, 1, 1, slab.get(), 1, 1, psum);
-                else launch_bfv_select_mac(env_, L, group, p0, c, rows, slab.get(), rg, rg_stride_r, psum);
-                if (level_tail) continue;
-                launch_rows_inv(env_, poly_view(sums, L, N, L), (u32)(c * 2));
-                launch_bfv_select_tail(env_, L, group, p0, c, sums, cur, stride_a, stride_b, dst, c_next);
-            }
-            if (level_tail) {
-                launch_ntt_inverse(env_, poly_view(sums, L, N, L), (u32)(pairs * 2));
-                launch_bfv_select_tail(env_, L, group, 0, pairs, sums, cur, stride_a, stride_b, dst, c_next);
-            }
-            ++(level_tail ? routes_.select_tail_routed : routes_.select_tail_fused);
-            if (pl.c[j] & 1) launch_bfv_select_copy(env_, L, n, group, cur, stride_a, stride_b, dst, c_next);
-            cur = dst; stride_a = c_next; stride_b = 1;
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- RGSW selectors from ONE packed query ciphertext (he355_kernels_bfv_gadget.hip; the definition: bfv_gadget_core.h, include/he355.h) -------
-    // sel [n][n_sel] mod t -> out [n][2][L][N], coefficient form: he355_encrypt_zero(seed, first_index + r) cut to the first L primes plus the planted
-    // selectors.
-    void bfv_selector_encrypt(const BfvSelectorPlan &pl, int L, u64 n, u64 n_sel, u64 first_slot, const u64 *sel, u64 seed, u64 first_index, u64 *out)
-    {
-        use();
-        if (!n) return;
-        if (!d_pk_) throw std::invalid_argument("he355_bfv_selector_encrypt: public key not set");
-        const PoolBlock hold = zeros_at_level(L, n, seed, first_index, out);
-        const u64 *zero = hold ? hold.get() : out;
-        launch_bfv_selector_plant(env_, pl.tab, L, (int)P.Ltop, n, n_sel, first_slot, pl.depth, zero, sel, P.plain_modulus, out);
-        HIPCHECK(hipGetLastError());
-    }
-    // RGSW(s) at (L, key_bits): by definition bfv_rgsw_encrypt of the secret key's coefficients mod t (0, 1, t - 1).  The context holds s in NTT
-    // form: prime 0's residue goes through the inverse transform in one pool block of N words and is mapped there; the block is held across
-    // the inner call, whose plan (n = 1) is made here, once the plaintext has its address.
-    void bfv_rgsw_encrypt_secret(int L, int kv, u64 seed, u64 first_index, u64 *out)
-    {
-        use();
-        if (!d_sk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: secret key not set");
-        if (!d_pk_) throw std::invalid_argument("he355_bfv_rgsw_encrypt_secret: public key not set");
-        const size_t N = P.N;
-        const PoolBlock s = scoped_block(N * 8);
-        HIPCHECK(hipMemcpyAsync(s.get(), d_sk_, N * 8, hipMemcpyDeviceToDevice, stream_));
-        launch_ntt_inverse(env_, poly_view(s.get(), 1, N, 1), 1);
-        launch_bfv_secret_plain(env_, s.get(), P.plain_modulus);
-        HIPCHECK(hipGetLastError());
-        bfv_rgsw_encrypt(plan_rgsw(P, L, kv, 1, s.get(), out), L, 1, s.get(), seed, first_index, out);
-    }
-    // out [n][n_sel][2E][2][L][N], NTT form.  Slot ciphertext c = (r n_sel + b) E + f (coefficient form, read where it lies): row f of RGSW (r, b) is its
-    // forward transform, row E + f the NTT-form sums of its key_bits digits against RGSW(s) -- what he355_bfv_external_product leaves before its
-    // inverse transform, which he355_bfv_transform_to_ntt would only undo.  A pass of slot ciphertexts (bfv_gadget_pass over the key's 2 E_key
-    // terms, one pool block as in bfv_external_product) is the cut, which also emits the slot's own column (gadget_cut_ntt's route, decided once per
-    // call from the first pass: every pass must leave the k = 0 rows in the same state), the digits' row pass and one multiply-accumulate into the
-    // k = 1 rows.  One row pass over the k = 0 rows, in place, ends the call.
-    void bfv_rgsw_from_bfv(const BfvFromBfvPlan &pl, int L, u64 n, u64 n_sel, const u64 *ct, u64 ct_stride_r, u64 ct_stride_k, const u64 *key, u64 *out)
-    {
-        use();
-        if (!n) return;
-        const size_t N = P.N, LN = (size_t)L * N;
-        const u32 E = pl.tab.total, rows = pl.rows;
-        const u64 C = pl.C, pass = pl.pass;
-        const bool cols = gadget_cols(std::min<u64>(pass, C), 2, L);
-        const PoolBlock slab = scoped_block((size_t)pass * rows * LN * 8);
-        for (u64 c0 = 0; c0 < C; c0 += pass) {
-            const u64 c = std::min<u64>(pass, C - c0);
-            ++routes_.passes;
-            ++(cols ? routes_.own_cols : routes_.own_stream);
-            launch_bfv_gadget_cut_own(env_, pl.ktab, L, n_sel * E, c0, c, ct, ct_stride_r, ct_stride_k, slab.get(), out, E, cols);
-            forward_rows_or_full(cols, poly_view(slab.get(), L, N, L), (u32)(c * rows));
-            launch_bfv_gadget_mac_own(env_, L, c0, c, rows, slab.get(), key, out, E);
-        }
-        // the k = 0 rows: rows f0 .. f0 + R - 1 of every RGSW ciphertext are one item of R 2L polynomials, the items 2E 2L polynomials apart
-        const u32 R = std::max<u32>(1, 64 / (2 * (u32)L));
-        for (u32 f0 = 0; f0 < E; f0 += R) {
-            PolyView pv = poly_view(out + (size_t)f0 * 2 * LN, (int)(std::min<u32>(R, E - f0) * 2 * L), N, L);
-            pv.item_stride = (u64)2 * E * 2 * LN;
-            forward_rows_or_full(cols, pv, (u32)(n * n_sel));
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- a PIR database from packed bytes (he355_kernels_bfv_bytes.hip; the definition: bfv_bytes_core.h, include/he355.h) ----------------
-    // bytes -> [n][N] coefficients mod t: one streaming launch
-    void bfv_unpack_bytes(const BfvBytesPlan &pl, u64 n, const void *bytes, u64 stride, u64 B, u64 *plain)
-    {
-        use();
-        launch_bfv_unpack(env_, pl.w, n, bytes, stride, B, plain);
-        HIPCHECK(hipGetLastError());
-    }
-    // the inverse: [n][N] words, each masked to w bits -> ceil(B / 8) whole words per plaintext
-    void bfv_pack_bytes(const BfvBytesPlan &pl, u64 n, const u64 *plain, u64 B, u64 stride, void *bytes)
-    {
-        use();
-        launch_bfv_pack(env_, pl.w, n, plain, B, stride, bytes);
-        HIPCHECK(hipGetLastError());
-    }
-    // bytes -> [n][L_out][N], by definition bfv_unpack_bytes + bfv_plain_to_ntt(L_out, n).  N >= 2048: the fused column pass reads the bytes,
-    // cuts, lifts and writes out(j, i'), the row pass runs in place -- no scratch.  N = 1024 has no column pass and is routed to the
-    // composition, kBytesChunk plaintexts at a time through one pool block (a database is large; a second identical call allocates nothing).
-    void bfv_unpack_bytes_ntt(const BfvBytesPlan &pl, int L_out, u64 n, const void *bytes, u64 stride, u64 B, u64 *out)
-    {
-        use();
-        const size_t N = P.N;
-        if (!n) return;
-        if (env_.logn1 == 0) {
-            const u64 chunk = n < kBytesChunk ? n : kBytesChunk;
-            const PoolBlock tmp = scoped_block((size_t)chunk * N * 8);
-            for (u64 j = 0; j < n; j += chunk) {
-                const u64 c = n - j < chunk ? n - j : chunk;
-                ++routes_.bytes_routed;
-                launch_bfv_unpack(env_, pl.w, c, static_cast<const unsigned char *>(bytes) + j * stride, stride, B, tmp.get());
-                plain_to_ntt(L_out, c, tmp.get(), out + (size_t)j * L_out * N);
-            }
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        ++routes_.bytes_fused;
-        launch_bfv_bytes_cols_fwd(env_, pl.w, n, bytes, stride, B, L_out, P.plain_modulus, out);
-        launch_rows_fwd(env_, poly_view(out, L_out, N, L_out), (u32)n);
-        HIPCHECK(hipGetLastError());
-    }
     const CrtTablesDev &crt_tables(int L)
     {
         return per_level(crt_, L, [&] {
@@ -2407,92 +1572,6 @@ public:
             launch_bfv_noise_bits(env_, size, c, part, src, budget + off, crt, nc);
         }
         launch_bfv_noise_finish(env_, n, budget, noise_bits, nc.q_bits);
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- reply compression (he355_kernels_bfv_reply.hip; the definition: bfv_reply_core.h, include/he355.h) -----------------------------
-    // [n][2][L][N] coefficient form -> n replies.  L > 1 is, by definition, bfv_mod_switch(L -> 1) followed by the L = 1 call: the L = 1
-    // ciphertexts pass through one pool block held for the call.
-    void bfv_reply_compress(const BfvReplyPlan &, int L, int k0, int k1, u64 n, const u64 *ct, void *bytes, u64 stride)
-    {
-        use();
-        if (L > kBfvLevelMaxL) throw std::invalid_argument("he355_bfv_reply_compress: BFV modulus switching supports up to 16 data primes");
-        if (!n) return;
-        PoolBlock low;
-        if (L > 1) {
-            low = scoped_block((size_t)n * 2 * P.N * 8);
-            launch_bfv_mod_switch(env_, bfv_drop_table_dev(), (int)P.Ltop, L, 1, n * 2, ct, low.get());
-            ct = low.get();
-        }
-        launch_bfv_reply_pack(env_, k0, k1, n, ct, stride, bytes);
-        HIPCHECK(hipGetLastError());
-    }
-    // n replies -> plain [n][N] mod t, budget / noise_bits [n] int32 (either may be null).  Per chunk of at most 64 replies (as decrypt();
-    // never more than the batch chunk, he355_set_chunk): c1 unpacked, centred and lifted mod q_0 into client scratch, forward transform,
-    // product with the NTT-form secret key at prime 0 in place, inverse transform, then k_bfv_reply_finish adds c0's field, rounds, and
-    // gathers the largest residue's bit length in `budget` (or `noise_bits` when that is the only output), which k_bfv_noise_finish turns
-    // into the budget with 2^k1 in the place of q.  One transform less per reply than decrypt() spends: c0 is never transformed.
-    void bfv_reply_decrypt(const BfvReplyPlan &, int k0, int k1, u64 n, const void *bytes, u64 stride, u64 *plain, int32_t *budget, int32_t *noise_bits)
-    {
-        use();
-        if (!d_sk_) throw std::invalid_argument("he355_bfv_reply_decrypt: secret key not set (he355_set_secret_key)");
-        if (!n) return;
-        if (!bytes || !plain) throw std::invalid_argument("he355_bfv_reply_decrypt: null replies or null plaintext output");
-        const size_t N = P.N;
-        const u64 cmax = std::max<u64>(1, std::min<u64>(n, std::min<u64>(64, lim_.chunk)));
-        u64 *prod = client_scratch(cmax * N);
-        int32_t *bits = budget ? budget : noise_bits;
-        if (bits) HIPCHECK(hipMemsetAsync(bits, 0, n * sizeof(int32_t), stream_));
-        for (u64 off = 0; off < n; off += cmax) {
-            const u64 c = std::min<u64>(cmax, n - off);
-            const unsigned char *src = static_cast<const unsigned char *>(bytes) + off * stride;
-            launch_bfv_reply_lift(env_, k0, k1, c, src, stride, prod);
-            launch_ntt_forward(env_, poly_view(prod, 1, N, 1), (u32)c);
-            launch_bfv_noise_dot_sk(env_, 1, 2, c, prod, d_sk_, prod);
-            launch_ntt_inverse(env_, poly_view(prod, 1, N, 1), (u32)c);
-            launch_bfv_reply_finish(env_, k0, k1, P.plain_modulus, c, src, stride, prod, plain + off * N, bits ? bits + off : nullptr);
-        }
-        if (budget) launch_bfv_noise_finish(env_, n, budget, noise_bits, k1);
-        HIPCHECK(hipGetLastError());
-    }
-    // ---- seeded queries and Galois keys (he355_kernels_bfv_seeded.hip; the definition: bfv_seeded_core.h, include/he355.h) ----------------
-    // The seeded zero of index first_index + r, built at level L where it will lie: c0 = -e - iNTT(a (.) s), plus Delta_L(m).  Three launches
-    // whatever n is, all in place on `c0` (no scratch, so nothing to chunk): a (.) s generated straight into it, the inverse transform, the finish.
-    void seeded_c0(const char *what, int L, u64 n, const u64 *plain, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
-    {
-        if (!d_sk_) throw std::invalid_argument(std::string(what) + ": secret key not set (he355_set_secret_key)");
-        if (!n) return;
-        const size_t N = P.N;
-        launch_bfv_seeded_gen(env_, L, n, a_seed, client::seeded_a_stream(first_index, 0), 64, c0, (u64)L * N, d_sk_);
-        launch_ntt_inverse(env_, poly_view(c0, L, N, L), (u32)n);
-        launch_bfv_seeded_finish(env_, L, n, c0, plain, bfv_delta(L), noise_seed, first_index, c0);
-    }
-    void bfv_seeded_encrypt(int L, u64 n, const u64 *plain, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
-    {
-        use();
-        seeded_c0("he355_bfv_seeded_encrypt", L, n, plain, a_seed, noise_seed, first_index, c0);
-        HIPCHECK(hipGetLastError());
-    }
-    // polynomial 0 of he355_bfv_selector_encrypt with the seeded zero in the place of the public-key one: the same plants in the same places
-    void bfv_seeded_selector_encrypt(const BfvSelectorPlan &pl, int L, u64 n, u64 n_sel, u64 first_slot, const u64 *sel, u64 a_seed, u64 noise_seed, u64 first_index, u64 *c0)
-    {
-        use();
-        seeded_c0("he355_bfv_seeded_selector_encrypt", L, n, nullptr, a_seed, noise_seed, first_index, c0);
-        launch_bfv_seeded_plant(env_, pl.tab, L, n, n_sel, first_slot, pl.depth, sel, P.plain_modulus, c0);
-        HIPCHECK(hipGetLastError());
-    }
-    // c0 [n][L][N] -> out [n][2][L][N]: c0 placed, the seeded half generated where it lies, then ONE transform in place over the half whose
-    // form has to change (ntt_form 0: c1 = iNTT(a); 1: c0 = NTT(c0)).  No scratch, so nothing to chunk; needs no key.
-    void bfv_seeded_restore(int L, int ntt_form, u64 n, const u64 *c0, u64 a_seed, u64 first_index, u64 *out)
-    {
-        use();
-        if (!n) return;
-        const size_t N = P.N, LN = (size_t)L * N;
-        launch_bfv_seeded_place(env_, L, n, c0, out);
-        launch_bfv_seeded_gen(env_, L, n, a_seed, client::seeded_a_stream(first_index, 0), 64, out + LN, 2 * LN, nullptr);
-        PolyView v = poly_view(out + (ntt_form ? 0 : LN), L, N, L);
-        v.item_stride = 2 * LN;
-        if (ntt_form) launch_ntt_forward(env_, v, (u32)n);
-        else launch_ntt_inverse(env_, v, (u32)n);
         HIPCHECK(hipGetLastError());
     }
     // the `b` halves [L_top][K][N] of the Galois key of `galois_elt`, its `a` halves drawn from the public a_seed: the whole key is made in a
@@ -2716,15 +1795,10 @@ private:
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     bool dual_stream_ = true;
     std::map<uint32_t, std::array<unsigned char, 32>> perm_rows_;
-    he355_path_stats_t paths_{};
+    Counters count_;
     struct HoistKey { u64 *p = nullptr; bool ok = false; };
     std::map<uint32_t, HoistKey> d_hoist_; // hoist_key(): the permuted copies of the Galois keys, per element
-    he355_hoist_stats_t hoist_{};
-    he355_poly_stats_t poly_{};
-    he355_raise_stats_t raise_{};
     u64 cus_ = 1; // compute units of the device (the small-batch split of the modulus raise)
-    he355_bfv_route_stats_t routes_{};
-    he355_bfv_multiply_stats_t mul_routes_{};
     bool level_walk_ = !(getenv("HE355_LEVEL_WALK") && getenv("HE355_LEVEL_WALK")[0] == '0'); // he355_rotate_sum: trie levels as grouped launches
     size_t groups_next_ = 0; // upload_groups: the next free byte of the kGroups ring
     std::map<int, BehzDev> behz_;
@@ -3036,266 +2110,6 @@ static void need_bfv(const he355_ctx *c, const char *what)
     if (!c) throw std::invalid_argument("null context");
     if (c->params->scheme != kSchemeBFV) throw std::invalid_argument(std::string(what) + " needs a BFV context");
 }
-int he355_bfv_mod_switch(he355_ctx *c, int L, int L_to, int size, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_mod_switch"); dev(c).bfv_mod_switch(L, L_to, size, n, in, out); });
-}
-int he355_bfv_add_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_add_plain"); dev(c).bfv_addsub_plain(L, size, n, ct, pt, to_ix(ix), out, false); });
-}
-int he355_bfv_sub_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_sub_plain"); dev(c).bfv_addsub_plain(L, size, n, ct, pt, to_ix(ix), out, true); });
-}
-int he355_bfv_multiply_plain(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain"); dev(c).bfv_multiply_plain(L, size, n, ct, pt, to_ix(ix), out); });
-}
-int he355_bfv_transform_to_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_transform_to_ntt"); dev(c).bfv_transform(L, size, n, in, out, false); });
-}
-int he355_bfv_transform_from_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_transform_from_ntt"); dev(c).bfv_transform(L, size, n, in, out, true); });
-}
-int he355_bfv_plain_to_ntt(he355_ctx *c, int L, uint64_t n, const uint64_t *plain, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_plain_to_ntt"); dev(c).bfv_plain_to_ntt(L, n, plain, out); });
-}
-int he355_bfv_multiply_plain_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, const uint64_t *pt, he355_indexer ix, uint64_t *out)
-{
-    return guarded([&] { need_bfv(c, "he355_bfv_multiply_plain_ntt"); dev(c).bfv_multiply_plain_ntt(L, size, n, ct, pt, to_ix(ix), out); });
-}
-int he355_bfv_multiply_plain_accumulate(he355_ctx *c, int L, int size, uint64_t rows, uint64_t cols, uint64_t inner, const uint64_t *ct, uint64_t ct_stride_i,
-                                        uint64_t ct_stride_k, const uint64_t *pt, uint64_t pt_stride_k, uint64_t pt_stride_j, uint64_t *out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_multiply_plain_accumulate");
-        dev(c).bfv_multiply_plain_accumulate(L, size, rows, cols, inner, ct, ct_stride_i, ct_stride_k, pt, pt_stride_k, pt_stride_j, out);
-    });
-}
-int he355_bfv_multiply_monomial(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *in, uint32_t exponent, uint64_t *out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_multiply_monomial");
-        check_monomial_args(*c->params, L, size, exponent);
-        dev(c).bfv_multiply_monomial(L, size, n, in, exponent, out);
-    });
-}
-uint64_t he355_bfv_expand_galois_elts(const he355_ctx *c, uint64_t count, uint32_t *out, uint64_t cap)
-{
-    if (!c || c->params->scheme != kSchemeBFV || count < 1 || count > c->params->N) return 0;
-    const int d = expand_depth(count);
-    for (int j = 0; j < d && (uint64_t)j < cap; ++j) out[j] = (uint32_t)(c->params->N >> j) + 1;
-    return (uint64_t)d;
-}
-int he355_bfv_expand(he355_ctx *c, int L, uint64_t n, const uint64_t *in, uint64_t count, uint64_t *out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_expand");
-        const BfvExpandPlan pl = plan_expand(*c->params, L, count);
-        dev(c).bfv_expand(pl, L, n, in, count, out);
-    });
-}
-int he355_bfv_merge(he355_ctx *c, int L, uint64_t n, uint64_t count, const uint64_t *in, uint64_t in_stride_k, uint64_t in_stride_r, uint64_t *out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_merge");
-        const BfvMergePlan pl = plan_merge(*c->params, L, n, count, in, in_stride_k, in_stride_r, out);
-        dev(c).bfv_merge(pl, L, n, count, in, in_stride_k, in_stride_r, out);
-    });
-}
-uint64_t he355_bfv_digit_count(const he355_ctx *c, int L, uint32_t *per_prime, uint64_t cap)
-{
-    if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || c->params->plain_modulus < 2) return 0;
-    const BfvDigitTab tab = digit_table(*c->params, L);
-    for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
-    return tab.total;
-}
-int he355_bfv_decompose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, uint64_t *plain)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_decompose");
-        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_decompose", L, size, n, ct, plain);
-        dev(c).bfv_decompose(pl, L, size, n, ct, plain);
-    });
-}
-int he355_bfv_decompose_ntt(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *ct, int L_out, uint64_t *plain_ntt)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_decompose_ntt");
-        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_decompose_ntt", L, size, n, ct, plain_ntt, true, L_out);
-        dev(c).bfv_decompose_ntt(pl, L, size, n, ct, L_out, plain_ntt);
-    });
-}
-int he355_bfv_compose(he355_ctx *c, int L, int size, uint64_t n, const uint64_t *plain, uint64_t *ct)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_compose");
-        const BfvDigitPlan pl = plan_digits(*c->params, "he355_bfv_compose", L, size, n, ct, plain);
-        dev(c).bfv_compose(pl, L, size, n, plain, ct);
-    });
-}
-uint64_t he355_bfv_gadget_count(const he355_ctx *c, int L, int digit_bits, uint32_t *per_prime, uint64_t cap)
-{
-    if (!c || c->params->scheme != kSchemeBFV || L < 1 || (size_t)L > c->params->Ltop || !bfv_gadget_width_ok(digit_bits)) return 0;
-    const BfvDigitTab tab = bfv_gadget_table(level_primes(*c->params, L).data(), L, digit_bits);
-    for (int i = 0; i < L && (uint64_t)i < cap; ++i) per_prime[i] = tab.D[i];
-    return tab.total;
-}
-int he355_bfv_gadget_decompose(he355_ctx *c, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_gadget_decompose");
-        const BfvDigitPlan pl = plan_gadget_cut(*c->params, "he355_bfv_gadget_decompose", L, digit_bits, size, n, d_ct, d_digits, false);
-        dev(c).bfv_gadget_decompose(pl, L, size, n, d_ct, d_digits);
-    });
-}
-int he355_bfv_gadget_decompose_ntt(he355_ctx *c, int L, int digit_bits, int size, uint64_t n, const uint64_t *d_ct, uint64_t *d_digits_ntt)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_gadget_decompose_ntt");
-        const BfvDigitPlan pl = plan_gadget_cut(*c->params, "he355_bfv_gadget_decompose_ntt", L, digit_bits, size, n, d_ct, d_digits_ntt, true);
-        dev(c).bfv_gadget_decompose_ntt(pl, L, size, n, d_ct, d_digits_ntt);
-    });
-}
-int he355_bfv_rgsw_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, const uint64_t *d_plain, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_rgsw_encrypt");
-        const BfvRgswPlan pl = plan_rgsw(*c->params, L, digit_bits, n, d_plain, d_rgsw);
-        dev(c).bfv_rgsw_encrypt(pl, L, n, d_plain, seed, first_index, d_rgsw);
-    });
-}
-int he355_bfv_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel, uint64_t seed,
-                               uint64_t first_index, uint64_t *d_out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_selector_encrypt");
-        const BfvSelectorPlan pl = plan_selector(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, d_out);
-        dev(c).bfv_selector_encrypt(pl, L, n, n_sel, first_slot, d_sel, seed, first_index, d_out);
-    });
-}
-int he355_bfv_rgsw_encrypt_secret(he355_ctx *c, int L, int key_bits, uint64_t seed, uint64_t first_index, uint64_t *d_rgsw)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_rgsw_encrypt_secret");
-        check_rgsw_secret_args(*c->params, L, key_bits);
-        dev(c).bfv_rgsw_encrypt_secret(L, key_bits, seed, first_index, d_rgsw);
-    });
-}
-int he355_bfv_rgsw_from_bfv(he355_ctx *c, int L, int digit_bits, int key_bits, uint64_t n, uint64_t n_sel, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
-                            const uint64_t *d_key, uint64_t *d_rgsw)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_rgsw_from_bfv");
-        const BfvFromBfvPlan pl = plan_from_bfv(*c->params, L, digit_bits, key_bits, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
-        dev(c).bfv_rgsw_from_bfv(pl, L, n, n_sel, d_ct, ct_stride_r, ct_stride_k, d_key, d_rgsw);
-    });
-}
-int he355_bfv_select(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t count, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k, const uint64_t *d_rgsw,
-                     uint64_t rg_stride_r, uint64_t rg_stride_j, uint64_t *d_out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_select");
-        const BfvSelectPlan pl = plan_select(*c->params, L, digit_bits, n, count, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_j, d_out);
-        dev(c).bfv_select(pl, L, n, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_j, d_out);
-    });
-}
-int he355_bfv_external_product(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t inner, const uint64_t *d_ct, uint64_t ct_stride_r, uint64_t ct_stride_k,
-                               const uint64_t *d_rgsw, uint64_t rg_stride_r, uint64_t rg_stride_k, uint64_t *d_out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_external_product");
-        const BfvExternalPlan pl = plan_external_product(*c->params, L, digit_bits, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
-        dev(c).bfv_external_product(pl, L, n, inner, d_ct, ct_stride_r, ct_stride_k, d_rgsw, rg_stride_r, rg_stride_k, d_out);
-    });
-}
-uint64_t he355_bfv_bytes_per_plain(const he355_ctx *c, uint32_t *field_bits)
-{
-    if (!c || c->params->scheme != kSchemeBFV || c->params->plain_modulus < 2) return 0;
-    const int w = bfv_bitlen(c->params->plain_modulus) - 1;
-    if (field_bits) *field_bits = (uint32_t)w;
-    return bfv_bytes_max(c->params->N, w);
-}
-int he355_bfv_unpack_bytes(he355_ctx *c, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_unpack_bytes");
-        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_unpack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, false);
-        dev(c).bfv_unpack_bytes(pl, n, d_bytes, stride_bytes, bytes_per_plain, d_plain);
-    });
-}
-int he355_bfv_unpack_bytes_ntt(he355_ctx *c, int L_out, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t bytes_per_plain, uint64_t *d_plain_ntt)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_unpack_bytes_ntt");
-        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_unpack_bytes_ntt", n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt, false, true, L_out);
-        dev(c).bfv_unpack_bytes_ntt(pl, L_out, n, d_bytes, stride_bytes, bytes_per_plain, d_plain_ntt);
-    });
-}
-int he355_bfv_pack_bytes(he355_ctx *c, uint64_t n, const uint64_t *d_plain, uint64_t bytes_per_plain, uint64_t stride_bytes, void *d_bytes)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_pack_bytes");
-        const BfvBytesPlan pl = plan_bytes(*c->params, "he355_bfv_pack_bytes", n, d_bytes, stride_bytes, bytes_per_plain, d_plain, true);
-        dev(c).bfv_pack_bytes(pl, n, d_plain, bytes_per_plain, stride_bytes, d_bytes);
-    });
-}
-uint64_t he355_bfv_reply_bytes(const he355_ctx *c, int k0, int k1)
-{
-    if (!c || c->params->scheme != kSchemeBFV || !bfv_reply_widths_ok(c->params->N, c->params->primes[0].q, k0, k1)) return 0;
-    return bfv_reply_size(c->params->N, k0, k1);
-}
-int he355_bfv_reply_safe_bits(const he355_ctx *c, int *k0, int *k1)
-{
-    if (!c || c->params->scheme != kSchemeBFV || c->params->plain_modulus < 2 || !k0 || !k1) return 0;
-    bfv_reply_safe(c->params->N, c->params->plain_modulus, *k0, *k1);
-    return bfv_reply_widths_ok(c->params->N, c->params->primes[0].q, *k0, *k1) ? 1 : 0;
-}
-int he355_bfv_reply_compress(he355_ctx *c, int L, int k0, int k1, uint64_t n, const uint64_t *d_ct, void *d_bytes, uint64_t stride_bytes)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_reply_compress");
-        const BfvReplyPlan pl = plan_reply(*c->params, "he355_bfv_reply_compress", L, k0, k1, n, d_bytes, stride_bytes, d_ct, 2 * (u64)(L > 0 ? L : 0) * c->params->N);
-        dev(c).bfv_reply_compress(pl, L, k0, k1, n, d_ct, d_bytes, stride_bytes);
-    });
-}
-int he355_bfv_reply_decrypt(he355_ctx *c, int k0, int k1, uint64_t n, const void *d_bytes, uint64_t stride_bytes, uint64_t *d_plain, int32_t *d_budget, int32_t *d_noise_bits)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_reply_decrypt");
-        const BfvReplyPlan pl = plan_reply(*c->params, "he355_bfv_reply_decrypt", 1, k0, k1, n, d_bytes, stride_bytes, d_plain, c->params->N, true, d_budget, d_noise_bits);
-        dev(c).bfv_reply_decrypt(pl, k0, k1, n, d_bytes, stride_bytes, d_plain, d_budget, d_noise_bits);
-    });
-}
-int he355_bfv_seeded_encrypt(he355_ctx *c, int L, uint64_t n, const uint64_t *d_plain, uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_seeded_encrypt");
-        plan_seeded_encrypt(*c->params, L, n, d_plain, a_seed, noise_seed, first_index, d_c0);
-        dev(c).bfv_seeded_encrypt(L, n, d_plain, a_seed, noise_seed, first_index, d_c0);
-    });
-}
-int he355_bfv_seeded_selector_encrypt(he355_ctx *c, int L, int digit_bits, uint64_t n, uint64_t n_sel, uint64_t first_slot, uint64_t count, const uint64_t *d_sel,
-                                      uint64_t a_seed, uint64_t noise_seed, uint64_t first_index, uint64_t *d_c0)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_seeded_selector_encrypt");
-        const BfvSelectorPlan pl = plan_seeded_selector(*c->params, L, digit_bits, n, n_sel, first_slot, count, d_sel, a_seed, noise_seed, first_index, d_c0);
-        dev(c).bfv_seeded_selector_encrypt(pl, L, n, n_sel, first_slot, d_sel, a_seed, noise_seed, first_index, d_c0);
-    });
-}
-int he355_bfv_seeded_restore(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *d_c0, uint64_t a_seed, uint64_t first_index, uint64_t *d_out)
-{
-    return guarded([&] {
-        need_bfv(c, "he355_bfv_seeded_restore");
-        plan_seeded_restore(*c->params, L, ntt_form, n, d_c0, first_index, d_out);
-        dev(c).bfv_seeded_restore(L, ntt_form, n, d_c0, a_seed, first_index, d_out);
-    });
-}
 int he355_keygen_galois_seeded(he355_ctx *c, uint32_t galois_elt, uint64_t a_seed, uint64_t noise_seed, uint64_t *d_b)
 {
     return guarded([&] {
@@ -3349,139 +2163,11 @@ int he355_rotate(he355_ctx *c, int L, uint64_t n, const uint64_t *in, int step, 
 {
     return guarded([&] { dev(c).rotate(L, n, in, step, out); });
 }
-static int hoisted_call(he355_ctx *c, const char *what, int L, int ntt_form, uint64_t n, const uint64_t *in, const uint32_t *elts, const int32_t *steps, uint64_t n_elts,
-                        const uint64_t *plain, uint64_t *out, bool plain_sum)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        const HoistPlan pl = plan_rotate_hoisted(*c->params, what, L, ntt_form, n, in, elts, steps, n_elts, plain, out, plain_sum);
-        if (pl.empty) return; // nothing to rotate: no buffer is touched, no device asked for
-        dev(c).rotate_hoisted(pl, L, ntt_form != 0, n, in, plain_sum ? plain : nullptr, out);
-    });
-}
-int he355_apply_galois_hoisted(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *in, const uint32_t *elts, uint64_t n_elts, uint64_t *out)
-{
-    if (n_elts && !elts) { g_last_error = "he355_apply_galois_hoisted: null elements"; return HE355_E_INVALID_ARGS; }
-    return hoisted_call(c, "he355_apply_galois_hoisted", L, ntt_form, n, in, elts, nullptr, n_elts, nullptr, out, false);
-}
-int he355_rotate_hoisted(he355_ctx *c, int L, int ntt_form, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, uint64_t *out)
-{
-    return hoisted_call(c, "he355_rotate_hoisted", L, ntt_form, n, in, nullptr, steps, n_steps, nullptr, out, false);
-}
-int he355_rotate_hoisted_plain_sum(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, const uint64_t *plain, uint64_t *out)
-{
-    return hoisted_call(c, "he355_rotate_hoisted_plain_sum", L, 1, n, in, nullptr, steps, n_steps, plain, out, true);
-}
-int he355_rotate_hoisted_plain_sum_lazy(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *steps, uint64_t n_steps, const uint64_t *plain_qp,
-                                        uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        const HoistPlan pl = plan_rotate_hoisted(*c->params, "he355_rotate_hoisted_plain_sum_lazy", L, 1, n, in, nullptr, steps, n_steps, plain_qp, out, true, true);
-        if (pl.empty) return; // nothing to sum: no buffer is touched, no device asked for
-        dev(c).rotate_hoisted_lazy(pl, L, n, in, plain_qp, out);
-    });
-}
-int he355_linear_transform_bsgs(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const int32_t *baby, uint64_t n_baby, const int32_t *giant, uint64_t n_giant,
-                                const uint64_t *plain_qp, const uint8_t *mask, uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        const BsgsPlan pl = plan_linear_transform_bsgs(*c->params, L, n, in, baby, n_baby, giant, n_giant, plain_qp, mask, out);
-        if (pl.empty) return; // nothing to transform: no buffer is touched, no device asked for
-        dev(c).linear_transform_bsgs(pl, L, n, in, plain_qp, out);
-    });
-}
-uint64_t he355_linear_transform_bsgs_scratch_bytes(const he355_ctx *c, int L, uint64_t n, uint64_t n_baby)
-{
-    if (!c || L < 1 || (size_t)L > c->params->Ltop) return 0;
-    return bsgs_scratch_bytes(c->dev ? c->dev->chunk_limit() : 1024, *c->params, L, n, n_baby);
-}
-int he355_plain_extend_special(he355_ctx *c, int L, uint64_t n, const uint64_t *plain_ntt, uint64_t *plain_qp, uint64_t *mismatch)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        if (plan_plain_extend(*c->params, L, n, plain_ntt, plain_qp)) return;
-        dev(c).plain_extend_special(L, n, plain_ntt, plain_qp, mismatch);
-    });
-}
 int he355_hoist_stats(he355_ctx *c, he355_hoist_stats_t *out, int reset)
 {
     return guarded([&] {
         if (!out) throw std::invalid_argument("null pointer");
         *out = dev(c).hoist_stats(reset != 0);
-    });
-}
-int he355_combine_scalars(he355_ctx *c, int L, int size, uint64_t n, const he355_term *terms, uint64_t n_terms, const uint64_t *scalars, const uint64_t *cst, uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        if (plan_combine_scalars(*c->params, L, size, n, terms, n_terms, scalars, cst, out)) return; // nothing to combine: no buffer is touched, no device asked for
-        DeviceContext &d = dev(c);
-        std::vector<DeviceContext::PolyTerm> t((size_t)n_terms);
-        for (size_t k = 0; k < t.size(); ++k) t[k] = {terms[k].d_ct, terms[k].L};
-        d.combine_scalars(L, size, n, t.data(), n_terms, scalars, cst, out);
-    });
-}
-int he355_ckks_scalar_residues(const he355_ctx *c, int L, double v, uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        poly_scalar_residues(*c->params, "he355_ckks_scalar_residues", L, v, out);
-    });
-}
-int he355_ckks_eval_poly_plan(const he355_ctx *c, int L, const double *coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale, uint64_t n,
-                              he355_poly_plan_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        if (!out) throw std::invalid_argument("he355_ckks_eval_poly_plan: null plan");
-        const u64 chunk = c->dev ? c->dev->chunk_limit() : 1024;
-        const PolyPlan pl = plan_eval_poly(*c->params, "he355_ckks_eval_poly_plan", L, n, nullptr, coeffs, n_coeffs, log_baby, in_scale, out_scale, nullptr, false, chunk);
-        *out = pl.info;
-        // one block of min(chunk, n) times the plan's words, rounded up by a size class of the pool (at most 2 MiB: device_pool.h)
-        const u128 bytes = (u128)pl.words_per_ct * std::min<u64>(chunk, n) * 8, bound = bytes + ((u128)2 << 20);
-        out->pool_bytes = !n ? 0 : bound > ~(u64)0 ? ~(u64)0 : (u64)bound;
-    });
-}
-int he355_ckks_eval_poly(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const double *coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
-                         uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        const PolyPlan pl = plan_eval_poly(*c->params, "he355_ckks_eval_poly", L, n, in, coeffs, n_coeffs, log_baby, in_scale, out_scale, out, true, 1024);
-        if (pl.empty) return; // nothing to evaluate: no buffer is touched, no device asked for
-        dev(c).eval_poly(pl, L, n, in, out);
-    });
-}
-int he355_poly_stats(he355_ctx *c, he355_poly_stats_t *out, int reset)
-{
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null pointer");
-        *out = dev(c).poly_stats(reset != 0);
-    });
-}
-int he355_ckks_mod_raise(he355_ctx *c, int L_in, int L_to, int size, uint64_t n, const uint64_t *in, uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        if (plan_mod_raise(*c->params, L_in, L_to, size, n, in, out)) return; // nothing to raise: no buffer is touched, no device asked for
-        dev(c).mod_raise(L_in, L_to, size, n, in, out);
-    });
-}
-int he355_ckks_lift_centred(he355_ctx *c, int L_to, uint64_t n_polys, const uint64_t *coeff, uint64_t *out)
-{
-    return guarded([&] {
-        if (!c) throw std::invalid_argument("null context");
-        if (plan_lift_centred(*c->params, L_to, n_polys, coeff, out)) return;
-        dev(c).lift_centred(L_to, n_polys, coeff, out);
-    });
-}
-int he355_raise_stats(he355_ctx *c, he355_raise_stats_t *out, int reset)
-{
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null pointer");
-        *out = dev(c).raise_stats(reset != 0);
     });
 }
 int he355_hoist_release_keys(he355_ctx *c)
@@ -3618,3 +2304,9 @@ int he355_set_chunk(he355_ctx *c, uint64_t ops)
 }
 
 } // extern "C"
+
+// the call families: launch sequences and C ABI of each, one file per family
+#include "hoisted_rotations.inc"
+#include "ckks_poly_raise.inc"
+#include "bfv_operands.inc"
+#include "bfv_pir.inc"

@@ -190,7 +190,7 @@ namespace ks_fold {
 #include "he355_launchers.inc"
 }
 #if !defined(HE355_KNS)
-// Host side (he355_api.hip): every launcher takes the KernelEnv first, and the environment knows which build its tables were made
+// Host side (he355_api.hip and the call families' .inc files it includes): every launcher takes the KernelEnv first, and the environment knows which build its tables were made
 // for -- the call sites name the launcher, these forwarders pick the namespace.
 #define HE355_FWD(name)                                                                                                   \
     template <class... A> inline auto name(const KernelEnv &env, A &&...a) -> decltype(ks_shoup::name(env, std::forward<A>(a)...)) \

@@ -1,7 +1,7 @@
 // hoist_args.h -- the argument checks of the hoisted rotations (he355_apply_galois_hoisted, he355_rotate_hoisted,
 // he355_rotate_hoisted_plain_sum, he355_rotate_hoisted_plain_sum_lazy, he355_linear_transform_bsgs, he355_plain_extend_special) that need no device, made ONCE per call in the style of bfv_pir_args.h: the C ABI wrapper runs the check
-// before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands the elements the check worked
-// out to DeviceContext.  Whether an element's Galois key is installed is the device context's to know; it checks that before its first launch.
+// before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and keeps the elements the check worked
+// out as the plan of the C ABI function (hoisted_rotations.inc).  Whether an element's Galois key is installed is the device context's to know; it checks that before its first launch.
 // Host-only on purpose: no HIP header, so tests/rotate_hoisted_args_main.cpp runs every check at its edges under the sanitizers.
 #pragma once
 #include <vector>

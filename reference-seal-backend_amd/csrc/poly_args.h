@@ -1,7 +1,7 @@
 // poly_args.h -- the argument checks of he355_combine_scalars and he355_ckks_scalar_residues and the host plan of he355_ckks_eval_poly
-// (power tree, split tree, levels, scales, integer scalars, buffers), made ONCE per call in the style of hoist_args.h: the C ABI wrapper
-// runs them before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and hands the plan to
-// DeviceContext, which only walks its steps.  Whether the relinearization key is installed is the device context's to know.
+// (power tree, split tree, levels, scales, integer scalars, buffers), made ONCE per call in the style of hoist_args.h: the C ABI function
+// (ckks_poly_raise.inc) runs them before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and
+// then only walks the plan's steps.  Whether the relinearization key is installed is the device context's to know.
 // Host-only on purpose: no HIP header, so tests/ckks_eval_poly_args_main.cpp runs every check at its edges under the sanitizers.
 // The definition the plan implements is written out in include/he355.h; tests/ckks_eval_poly_ref.py restates it on the oracle.
 #pragma once

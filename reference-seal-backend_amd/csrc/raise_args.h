@@ -1,6 +1,6 @@
 // raise_args.h -- the argument checks of he355_ckks_mod_raise and he355_ckks_lift_centred, made ONCE per call in the style of poly_args.h:
-// the C ABI wrapper runs them before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device exists or not -- and
-// DeviceContext only launches.  Host-only on purpose: no HIP header, so tests/ckks_mod_raise_args_main.cpp runs every check at its edges
+// the C ABI function (ckks_poly_raise.inc) runs them before it asks for a device -- a refusal is HE355_E_INVALID_ARGS whether a device
+// exists or not -- and then only launches.  Host-only on purpose: no HIP header, so tests/ckks_mod_raise_args_main.cpp runs every check at its edges
 // under the sanitizers.  The definition of the raise is written out in include/he355.h; tests/ckks_mod_raise_ref.py restates it on the oracle.
 #pragma once
 #include <string>
