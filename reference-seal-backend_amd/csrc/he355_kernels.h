@@ -15,6 +15,7 @@
 #include "bfv_reply_core.h"
 #include "bfv_gadget_core.h"
 #include "ks_shape.h"
+#include "ks_launch.h"
 
 namespace he355 {
 
@@ -90,9 +91,8 @@ struct K1Operands {
 };
 // K3: forward row pass of every (tt, j) + multiply-accumulate with the key -> t (data primes) / tpr (special)
 // BFV (env.scheme == 1): the products of ALL primes continue into the inverse row pass (t then holds raw rows)
-// `part`: all tiles, only the special prime's, or only the data primes'.  With `fuse` (data-prime tiles, CKKS: k3_can_fuse)
+// `part` (K3Part, ks_launch.h): all tiles, only the special prime's, or only the data primes'.  With `fuse` (data-prime tiles, CKKS: k3_can_fuse)
 // the mod-down is finished inside the kernel: c01 += (sums - NTT(cols)) * P^-1, no t slab, no k_floor_rows.
-enum K3Part { K3_ALL = 0, K3_SPECIAL_ONLY = 1, K3_DATA_ONLY = 2 };
 struct K3Fuse {
     const u64 *cols;     // [n_ops*2][L][N] output of launch_floor_cols(special prime -> L targets)
     u64 *c01;
@@ -135,6 +135,7 @@ struct K3Fuse {
 };
 // the dimensions of an environment the shape rules read (ks_shape.h), and k3_can_fuse over them
 inline KsDims ks_dims(const KernelEnv &env) { return KsDims{env.scheme, env.logn1, env.K}; }
+inline KsLaunchDims ks_launch_dims(const KernelEnv &env) { return KsLaunchDims{env.scheme, env.logn1, env.K, env.prime_f64, env.prime_q}; } // ... and the launch geometry (ks_launch.h)
 inline bool k3_can_fuse(const KernelEnv &env) { return k3_can_fuse(ks_dims(env)); }
 // floor step, row half: out[(op,k,i)] = (tsrc[(op,k,i)] - NTT(dst_cols[(op,k,i)])) * s^-1 (+ addend) mod q_i.
 // Strides are in u64 elements.  If tail_prime >= 0 the rows of that prime additionally go through the

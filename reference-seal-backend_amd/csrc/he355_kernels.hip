@@ -2077,12 +2077,13 @@ void launch_mul3(const KernelEnv &env, int L, u64 n_results, const u64 *a, const
     hipLaunchKernelGGL(k_mul3, dim3(grid_for(threads, kBlock)), dim3(kBlock), 0, env.stream, a, b, out, ix, env.primes, L, logN, n_results);
 }
 
-// The two engines' launches of a stage as one kernel (k_k1_dual, k_k2n_dual, k_k3_dual, k_floor_rows_dual) in the latency shape, and
-// for small grids of the throughput shape: up to this many blocks for both engines together (profiles/r04_dual_engine_latency.txt)
-// (round 5: per kernel.  k_k3's shared launch pays up to a few thousand blocks since the fold form of the u64 engine brought its blocks
-// close to the fp64 engine's in length; the others -- whose dual kernels are the latency shape's, behind a function boundary -- keep
-// the 1024 they were swept at.  profiles/r05_dual_threshold_sweep.txt)
-constexpr unsigned kDualMaxBlocksK3 = 4096, kDualMaxBlocks = 1024;
+// (which launches of a stage run as one kernel for both engines, and every grid below: ks_launch.h)
+template <size_t N> void copy_list(unsigned char (&dst)[N], int &n, const IndexList &l)
+{
+    static_assert(N >= sizeof(l.at), "an argument block's list holds every prime");
+    n = l.n;
+    std::copy(l.at, l.at + l.n, dst);
+}
 void launch_k1(const KernelEnv &env, int L, u64 n_ops, const K1Operands &src, const KsBuffers &buf)
 {
     if (!n_ops) return;
@@ -2101,36 +2102,29 @@ void launch_k1(const KernelEnv &env, int L, u64 n_ops, const K1Operands &src, co
     A.a = src.a; A.b = src.b; A.ix = src.ix; A.perm = src.perm; A.addend = addend;
     A.c01 = buf.c01; A.c01_item_stride = buf.c01_item_stride; A.c2n = buf.c2n; A.c2r = buf.c2r;
     A.n_ops = n_ops; A.op_offset = src.op_offset; A.L = L; A.logn1 = env.logn1; A.mode = (int)mode;
-    K1Args AP[2];
-    unsigned gp[2] = {0, 0};
-    for (int pass = 0; pass < 2; ++pass) { // pass 0: fp64-engine residues, pass 1: u64-engine residues
-        A.n_i = 0;
-        for (int i = 0; i < L; ++i)
-            if ((env.prime_f64[i] != 0) == (pass == 0)) A.i_list[A.n_i++] = (unsigned char)i;
-        AP[pass] = A;
-        gp[pass] = A.n_i ? grid_for((n_ops * A.n_i) << env.logn1, kWaves) : 0;
-    }
-    // (k_k1 proper -- the throughput shape -- maps a block onto one (residue, row) tile and four consecutive ops: its own grid below)
+    const bool c2_only = mode == K1_MUL && no_c01;
+    const K1Geometry G = k1_geometry(ks_launch_dims(env), L, n_ops, c2_only);
+    K1Args AP[2] = {A, A}; // [0]: fp64-engine residues, [1]: u64-engine residues
+    for (int pass = 0; pass < 2; ++pass) copy_list(AP[pass].i_list, AP[pass].n_i, G.i_list[pass]);
     const hipStream_t st = env.stream;
-    if (gp[0] && gp[1] && (n_ops <= 8 || gp[0] + gp[1] <= kDualMaxBlocks) && mode != K1_MUL_C2 && !(mode == K1_MUL && no_c01)) {
-        // latency shape / small grids: one launch for both engines
-        const dim3 grid(gp[0] + gp[1]);
-        if (mode == K1_MUL) hipLaunchKernelGGL((k_k1_dual<K1_MUL>), grid, dim3(kBlock), 0, st, AP[0], AP[1], gp[0], env.primes);
-        else if (mode == K1_CT3) hipLaunchKernelGGL((k_k1_dual<K1_CT3>), grid, dim3(kBlock), 0, st, AP[0], AP[1], gp[0], env.primes);
-        else hipLaunchKernelGGL((k_k1_dual<K1_GALOIS>), grid, dim3(kBlock), 0, st, AP[0], AP[1], gp[0], env.primes);
+    if (G.dual) {
+        const dim3 grid(G.dual_grid[0] + G.dual_grid[1]);
+        if (mode == K1_MUL) hipLaunchKernelGGL((k_k1_dual<K1_MUL>), grid, dim3(kBlock), 0, st, AP[0], AP[1], G.dual_grid[0], env.primes);
+        else if (mode == K1_CT3) hipLaunchKernelGGL((k_k1_dual<K1_CT3>), grid, dim3(kBlock), 0, st, AP[0], AP[1], G.dual_grid[0], env.primes);
+        else hipLaunchKernelGGL((k_k1_dual<K1_GALOIS>), grid, dim3(kBlock), 0, st, AP[0], AP[1], G.dual_grid[0], env.primes);
         return;
     }
     for (int pass = 0; pass < 2; ++pass) {
-        if (!gp[pass]) continue;
+        if (!G.grid[pass]) continue;
         const K1Args &AA = AP[pass];
-        const dim3 grid((unsigned)((((u64)AA.n_i) << env.logn1) * ((n_ops + kWaves - 1) / kWaves)));
+        const dim3 grid(G.grid[pass]);
         if (pass == 0) {
-            if (mode == K1_MUL && no_c01) hipLaunchKernelGGL((k_k1<K1_MUL_C2, ArF64>), grid, dim3(kBlock), 0, st, AA, env.primes);
+            if (c2_only) hipLaunchKernelGGL((k_k1<K1_MUL_C2, ArF64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else if (mode == K1_MUL) hipLaunchKernelGGL((k_k1<K1_MUL, ArF64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else if (mode == K1_CT3) hipLaunchKernelGGL((k_k1<K1_CT3, ArF64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else hipLaunchKernelGGL((k_k1<K1_GALOIS, ArF64>), grid, dim3(kBlock), 0, st, AA, env.primes);
         } else {
-            if (mode == K1_MUL && no_c01) hipLaunchKernelGGL((k_k1<K1_MUL_C2, ArU64>), grid, dim3(kBlock), 0, st, AA, env.primes);
+            if (c2_only) hipLaunchKernelGGL((k_k1<K1_MUL_C2, ArU64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else if (mode == K1_MUL) hipLaunchKernelGGL((k_k1<K1_MUL, ArU64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else if (mode == K1_CT3) hipLaunchKernelGGL((k_k1<K1_CT3, ArU64>), grid, dim3(kBlock), 0, st, AA, env.primes);
             else hipLaunchKernelGGL((k_k1<K1_GALOIS, ArU64>), grid, dim3(kBlock), 0, st, AA, env.primes);
@@ -2141,53 +2135,29 @@ void launch_k1(const KernelEnv &env, int L, u64 n_ops, const K1Operands &src, co
 void launch_k2(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, const u64 *src, u64 src_op_stride, int tsplit)
 {
     if (!n_ops) return;
+    const KsLaunchDims dims = ks_launch_dims(env);
     K2Args A;
     A.c2r = src ? src : buf.c2r;
     A.src_op_stride = src ? src_op_stride : (u64)L * env.N;
     A.src_is_coeff = src ? 1 : 0;
     A.d = buf.d; A.n_ops = n_ops; A.L = L; A.K = env.K; A.ckks = env.scheme == 2;
-    A.f64_mask = 0; A.tsplit = tsplit > 1 ? tsplit : 1;
-    for (int t = 0; t < env.K; ++t) A.f64_mask |= (u64)(env.prime_f64[t] != 0) << t;
-    // Small grids: the targets of a (digit, column block) dealt to 2 or 4 blocks (blockIdx.y, as the latency shape does) when
-    // that fills the rounds of blocks better -- 512 blocks run at a time (two per CU); a block pays the digit's inverse column
-    // pass once and a forward column pass + stores per target.  64 BFV ciphertexts at L = 3: 768 blocks = 1.5 rounds of all four
-    // targets, or 3 full rounds of two targets each.  Only taken for a modelled gain of 5 % or more (the headline's 61440 blocks
-    // stay whole).
-    auto target_split = [&](unsigned gw) {
-        if (tsplit > 1) return tsplit;
-        int ts = 1;
-        const int n_tgt = L + 1 - (A.ckks ? 1 : 0);
-        auto cost = [&](int c) { return (double)(((u64)gw * c + 511) / 512) * (1.0 + 1.2 * ((n_tgt + c - 1) / c)); };
-        const double c1 = cost(1);
-        double best = c1;
-        for (int c = 2; c <= 4; c <<= 1)
-            if (cost(c) < best * 0.95 && cost(c) < c1 * 0.95) { best = cost(c); ts = c; }
-        return ts;
-    };
-    K2Args AK[2];
-    unsigned gk[2] = {0, 0};
-    for (int wide = 0; wide < 2; ++wide) { // digits below 2^52, then the 60-bit ones: one instantiation each
-        A.n_dig = 0;
-        for (int j = 0; j < L; ++j)
-            if ((env.prime_q[j] >> 52 != 0) == (wide != 0)) A.dig_list[A.n_dig++] = (unsigned char)j;
-        AK[wide] = A;
-        gk[wide] = (unsigned)(n_ops * A.n_dig * 4);
+    A.f64_mask = f64_mask(dims);
+    const K2Geometry G = k2_geometry(dims, L, n_ops, tsplit);
+    K2Args AK[2] = {A, A}; // digits below 2^52, then the 60-bit ones
+    for (int wide = 0; wide < 2; ++wide) {
+        copy_list(AK[wide].dig_list, AK[wide].n_dig, G.dig_list[wide]);
+        AK[wide].tsplit = G.ts[wide];
     }
-    if (gk[0] && gk[1]) { // latency shape or a small grid: both digit kinds in one launch (k_k2n_dual)
-        const int ts = target_split(gk[0] + gk[1]);
-        if (tsplit > 1 || (gk[0] + gk[1]) * (unsigned)ts <= kDualMaxBlocks) {
-            AK[0].tsplit = AK[1].tsplit = ts;
-            const dim3 gd(gk[0] + gk[1], (unsigned)ts);
-#define HE355_K2D(L1) case L1: hipLaunchKernelGGL((k_k2n_dual<L1>), gd, dim3(kBlock), 0, env.stream, AK[0], AK[1], gk[0], env.primes); break;
-            switch (env.logn1) { HE355_K2D(0) HE355_K2D(1) HE355_K2D(2) HE355_K2D(3) HE355_K2D(4) HE355_K2D(5) }
+    if (G.dual) {
+        const dim3 gd(G.gx[0] + G.gx[1], (unsigned)G.ts[0]);
+#define HE355_K2D(L1) case L1: hipLaunchKernelGGL((k_k2n_dual<L1>), gd, dim3(kBlock), 0, env.stream, AK[0], AK[1], G.gx[0], env.primes); break;
+        switch (env.logn1) { HE355_K2D(0) HE355_K2D(1) HE355_K2D(2) HE355_K2D(3) HE355_K2D(4) HE355_K2D(5) }
 #undef HE355_K2D
-            return;
-        }
+        return;
     }
     for (int wide = 0; wide < 2; ++wide) {
-        if (!gk[wide]) continue;
-        AK[wide].tsplit = target_split(gk[wide]);
-        const dim3 gd(gk[wide], (unsigned)AK[wide].tsplit);
+        if (!G.gx[wide]) continue;
+        const dim3 gd(G.gx[wide], (unsigned)G.ts[wide]);
 #define HE355_K2N(L1)                                                                                                         \
     case L1:                                                                                                                  \
         if (wide) hipLaunchKernelGGL((k_k2n<L1, true>), gd, dim3(kBlock), 0, env.stream, AK[wide], env.primes);               \
@@ -2198,121 +2168,59 @@ void launch_k2(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
     }
 }
 
-
 void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, const u64 *key, K3Part part, const K3Fuse *fuse, int n_split, u64 *split_part,
                int n_split_u64, const KsGroups *groups, u64 g_op_offset)
 {
     if (groups && (n_split > 1 || (fuse && fuse->ta))) throw std::runtime_error("grouped keys: the 8-wave rotation instantiations only");
-    if (n_split_u64 <= 0) n_split_u64 = n_split;
-    if (n_split > 1 && (fuse || !split_part)) throw std::runtime_error("digit-split K3: unfused launches with a partial-sum buffer only");
-    const unsigned char *prime_f64 = env.prime_f64;
+    if (n_split > 1 && !fuse && !split_part) throw std::runtime_error("digit-split K3: unfused launches with a partial-sum buffer only");
+    K3Request rq;
+    rq.L = L; rq.n_ops = n_ops; rq.part = part; rq.n_split = n_split; rq.n_split_u64 = n_split_u64;
+    rq.fuse = fuse != nullptr; rq.tt_lo = fuse ? fuse->tt_lo : 0; rq.tt_hi = fuse ? fuse->tt_hi : 0; rq.rescale = fuse && fuse->cols2;
+    rq.grouped = groups != nullptr; rq.group_size = groups ? groups->group_size : 0; rq.sum_out = groups && groups->sum_out; rq.g_op_offset = g_op_offset;
+    const K3Geometry G = k3_geometry(ks_launch_dims(env), rq);
     if (!n_ops) return;
     if (fuse && (part != K3_DATA_ONLY || !k3_can_fuse(env))) throw std::runtime_error("fused mod-down: data-prime tiles only");
-    struct { K3Args A; unsigned g; bool f64; int waves; } pend[2];
-    int n_pend = 0;
-    for (int pass = 0; pass < 2; ++pass) { // pass 0: fp64-engine primes, pass 1: u64-engine primes
-        K3Args A;
-        A.d = buf.d; A.c2n = buf.c2n; A.key = key; A.t = buf.t; A.tp = buf.tp; A.tpr = buf.tpr;
-        A.n_ops = n_ops; A.L = L; A.K = env.K; A.logn1 = env.logn1; A.ckks = env.scheme == 2;
-        A.cols = fuse ? fuse->cols : nullptr; A.c01 = fuse ? fuse->c01 : nullptr; A.c01_item_stride = fuse ? fuse->c01_item_stride : 0;
-        A.cols2 = fuse ? fuse->cols2 : nullptr; A.out2 = fuse ? fuse->out : nullptr;
-        A.c1_mode = fuse ? fuse->c1_mode : 0; A.c1_src = fuse ? fuse->c1_src : nullptr;
-        A.gsrc = fuse ? fuse->gsrc : nullptr; A.gperm = fuse ? fuse->gperm : nullptr; A.gsrc_op_offset = fuse ? fuse->gsrc_op_offset : 0;
-        if ((A.c1_mode == 4 || A.c1_mode == 5) && (!A.gsrc || (!groups && !A.gperm))) throw std::runtime_error("gathered rotation: the input slab and its permutation are needed");
-        if (A.c1_mode == 5 && !A.c1_src) throw std::runtime_error("gathered rotation with addend: the addend rows are needed");
-        A.ta = fuse ? fuse->ta : nullptr; A.tb = fuse ? fuse->tb : nullptr; A.tix = fuse ? fuse->tix : Indexer{}; A.t_op_offset = fuse ? fuse->t_op_offset : 0;
-        if (fuse && fuse->cols2 && fuse->tt_hi > L - 1) throw std::runtime_error("fused rescale: only primes below the one divided out");
-        if (fuse && fuse->raw_tail) { // the rescale's divided-out prime: operand-formed sums, inverse row pass, raw rows (no floor step)
-            if (!fuse->ta || fuse->tt_hi != fuse->tt_lo + 1 || groups) throw std::runtime_error("raw tail: one prime of a ct x ct multiply");
-            A.tpr = fuse->raw_tail;
-        }
-        A.fc = env.floor_consts;
-        A.n_split = n_split > 1 ? (pass == 0 ? n_split : n_split_u64) : 1; A.part = split_part;
-        A.n_tt = 0;
-        A.n_q = 0;
-        for (int t = 0; t < env.K; ++t) A.n_q += prime_f64[t] == 0;
-        A.keyq_offset = (u64)env.Ltop * 2 * env.K * env.N; // the quotient array follows the key in the same allocation
-        A.keyq = key ? key + A.keyq_offset : nullptr;
-        A.groups = groups ? *groups : KsGroups{}; A.g_op_offset = g_op_offset;
-        for (int tt = 0; tt <= L; ++tt) {
-            if ((part == K3_SPECIAL_ONLY && tt != L) || (part == K3_DATA_ONLY && tt == L)) continue;
-            if (fuse && (tt < fuse->tt_lo || tt >= fuse->tt_hi)) continue;
-            const int t = (tt == L) ? env.K - 1 : tt;
-            if ((prime_f64[t] != 0) == (pass == 0)) {
-                int slot = 0;
-                for (int u = 0; u < t; ++u) slot += prime_f64[u] == 0;
-                A.q_slot[A.n_tt] = (unsigned char)slot;
-                A.tt_list[A.n_tt++] = (unsigned char)tt;
-            }
-        }
-        if (!A.n_tt) continue;
-        int waves = A.n_split > 1 ? 1 : 8; // latency shape: one wave per block, one (tile, op, digit group) each; else the 8-wave shape
-        const u64 tiles = (u64)A.n_tt << env.logn1;
-        // enough blocks to keep every CU busy for several rounds, few enough that start-up costs are amortised
-        // Op-groups per block: more of them amortise the block's start-up (twiddle staging, ~4 us) over more work, fewer of them give the
-        // dispatcher more blocks to fill the 256 CUs with.  What counts for small grids is the number of ROUNDS of blocks: 64 tiles x 8
-        // op-groups (BFV, 64 ciphertexts, L = 3) are two rounds of 256 one-group blocks or ONE round of two-group blocks, the same work
-        // with half the start-ups (configs[4]: 65.3 -> 63.4 ms).  So: the candidate sizes from the shape's maximum down, each priced as
-        // rounds x (groups x work per group + start-up), ties to the larger.  (Maximum for the 8-wave shape: 4 once a tile has 128
-        // op-groups -- chunks of 1024 ciphertexts: 50.3 vs 50.9 ms per step with 2 -- and 2 below that, where 4 measured slower;
-        // profiles/r03_chunk_sweep.txt.)
-        u64 n_og = 0;
-        u32 ogpb = 1;
-        unsigned g = 0;
-        auto size_grid = [&](int w) {
-            n_og = (n_ops + w - 1) / w;
-            const u32 og_max = w == 8 ? (n_og >= 128 ? 4 : 2) : 4;
-            ogpb = og_max;
-            {
-                const double work = (pass == 0 ? 7.0 : 14.0) * (L + 2) * (w == 4 ? 0.5 : 1.0), startup = 4.0; // us per op-group (one row step per digit + epilogue), per block
-                double best = 0;
-                for (u32 c = og_max; c >= 1; c >>= 1) {
-                    const u64 blocks = tiles * ((n_og + c - 1) / c);
-                    const double cost = (double)((blocks + 255) / 256) * (c * work + startup);
-                    if (c == og_max || cost < best * 0.999) { best = cost; ogpb = c; }
-                }
-            }
-            const u64 n_ogb = (n_og + ogpb - 1) / ogpb;
-            g = (unsigned)(((tiles + 7) / 8) * 8 * n_ogb);
-        };
-        size_grid(waves);
-        const bool level_sum = groups && groups->sum_out && fuse; // (the special prime's launch ahead of it writes no ciphertext rows)
-        if (level_sum) {
-            // one block per (tile, eight ciphertexts), walking this launch's groups in turn (see KsGroups::sum_out)
-            const u64 gs8 = groups->group_size / 8;
-            if (waves != 8 || groups->group_size % 8 || n_ops % groups->group_size || g_op_offset % groups->group_size)
-                throw std::runtime_error("level sum in k_k3: fused 8-wave launches over whole groups of a multiple of eight ciphertexts");
-            ogpb = (u32)(n_og / gs8);
-            g = (unsigned)(((tiles + 7) / 8) * 8 * gs8);
-        }
-        // u64-engine tiles of a small grid (at most half the CUs busy with 8-wave blocks): FOUR waves per block -- one per SIMD, each at
-        // the full issue rate instead of half of it, and twice the blocks; the serial digit loop of a tile is what such a launch lasts
-        if (pass == 1 && waves == 8 && g <= 128 && !level_sum) {
-            size_grid(4);
-            // (a CU holds ONE block of either shape -- the LDS arrays -- so the four-wave blocks must still fit one round together with the
-            // fp64-engine blocks they may share the launch with)
-            if (g + (n_pend ? pend[0].g : 0) <= 256) waves = 4;
-            else size_grid(8);
-        }
-        A.og_per_block = ogpb;
-        A.og_stride = level_sum ? (u32)(groups->group_size / 8) : 1u;
-        pend[n_pend].A = A; pend[n_pend].g = g; pend[n_pend].f64 = pass == 0; pend[n_pend].waves = waves;
-        ++n_pend;
+    K3Args A;
+    A.d = buf.d; A.c2n = buf.c2n; A.key = key; A.t = buf.t; A.tp = buf.tp; A.tpr = buf.tpr;
+    A.n_ops = n_ops; A.L = L; A.K = env.K; A.logn1 = env.logn1; A.ckks = env.scheme == 2;
+    A.cols = fuse ? fuse->cols : nullptr; A.c01 = fuse ? fuse->c01 : nullptr; A.c01_item_stride = fuse ? fuse->c01_item_stride : 0;
+    A.cols2 = fuse ? fuse->cols2 : nullptr; A.out2 = fuse ? fuse->out : nullptr;
+    A.c1_mode = fuse ? fuse->c1_mode : 0; A.c1_src = fuse ? fuse->c1_src : nullptr;
+    A.gsrc = fuse ? fuse->gsrc : nullptr; A.gperm = fuse ? fuse->gperm : nullptr; A.gsrc_op_offset = fuse ? fuse->gsrc_op_offset : 0;
+    if ((A.c1_mode == 4 || A.c1_mode == 5) && (!A.gsrc || (!groups && !A.gperm))) throw std::runtime_error("gathered rotation: the input slab and its permutation are needed");
+    if (A.c1_mode == 5 && !A.c1_src) throw std::runtime_error("gathered rotation with addend: the addend rows are needed");
+    A.ta = fuse ? fuse->ta : nullptr; A.tb = fuse ? fuse->tb : nullptr; A.tix = fuse ? fuse->tix : Indexer{}; A.t_op_offset = fuse ? fuse->t_op_offset : 0;
+    if (fuse && fuse->raw_tail) { // the rescale's divided-out prime: operand-formed sums, inverse row pass, raw rows (no floor step)
+        if (!fuse->ta || fuse->tt_hi != fuse->tt_lo + 1 || groups) throw std::runtime_error("raw tail: one prime of a ct x ct multiply");
+        A.tpr = fuse->raw_tail;
     }
+    A.fc = env.floor_consts;
+    A.part = split_part;
+    A.n_q = G.n_q;
+    A.keyq_offset = (u64)env.Ltop * 2 * env.K * env.N; // the quotient array follows the key in the same allocation
+    A.keyq = key ? key + A.keyq_offset : nullptr;
+    A.groups = groups ? *groups : KsGroups{}; A.g_op_offset = g_op_offset;
+    K3Args AP[2] = {A, A};
+    for (int i = 0; i < G.n_pend; ++i) {
+        const K3Pass &P = G.pend[i];
+        copy_list(AP[i].tt_list, AP[i].n_tt, P.tt_list);
+        std::copy(P.q_slot, P.q_slot + P.tt_list.n, AP[i].q_slot);
+        AP[i].n_split = P.n_split; AP[i].og_per_block = P.og_per_block; AP[i].og_stride = P.og_stride;
+    }
+    const K3Pass *const pend = G.pend;
     const hipStream_t st3 = env.stream;
     const bool tensor = fuse && fuse->ta, raw_tail = fuse && fuse->raw_tail; // (raw_tail: one prime, so one engine and no dual launch)
-    if (n_pend == 2 && pend[0].waves == 1) { // latency shape
-        const unsigned ny = (unsigned)std::max(pend[0].A.n_split, pend[1].A.n_split);
-        hipLaunchKernelGGL(k_k3_dual, dim3(pend[0].g + pend[1].g, ny), dim3(64), 0, st3, pend[0].A, pend[1].A, pend[1].g, env.primes);
+    if (G.form == K3Form::Dual) { // latency shape
+        const unsigned ny = (unsigned)std::max(pend[0].n_split, pend[1].n_split);
+        hipLaunchKernelGGL(k_k3_dual, dim3(pend[0].g + pend[1].g, ny), dim3(64), 0, st3, AP[0], AP[1], pend[1].g, env.primes);
         return;
     }
-    // throughput shape, small grids (up to two blocks per CU for both engines together): both engines in one launch
-    if (n_pend == 2 && pend[0].waves == 8 && pend[0].g + pend[1].g <= kDualMaxBlocksK3) {
+    if (G.form == K3Form::Dual8) {
         const dim3 gd(pend[0].g + pend[1].g);
-#define HE355_K3D8(F, T, G)                                                                                                                     \
-    do {                                                                                                                                        \
-        if (pend[1].waves == 4) hipLaunchKernelGGL((k_k3_dual8<F, T, G, 4>), gd, dim3(512), 0, st3, pend[0].A, pend[1].A, pend[1].g, env.primes); \
-        else hipLaunchKernelGGL((k_k3_dual8<F, T, G, 8>), gd, dim3(512), 0, st3, pend[0].A, pend[1].A, pend[1].g, env.primes);                    \
+#define HE355_K3D8(F, T, G_)                                                                                                                  \
+    do {                                                                                                                                      \
+        if (pend[1].waves == 4) hipLaunchKernelGGL((k_k3_dual8<F, T, G_, 4>), gd, dim3(512), 0, st3, AP[0], AP[1], pend[1].g, env.primes);     \
+        else hipLaunchKernelGGL((k_k3_dual8<F, T, G_, 8>), gd, dim3(512), 0, st3, AP[0], AP[1], pend[1].g, env.primes);                        \
     } while (0)
         if (groups) { if (fuse) HE355_K3D8(true, false, true); else HE355_K3D8(false, false, true); }
         else if (tensor) HE355_K3D8(true, true, false);
@@ -2321,8 +2229,8 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
 #undef HE355_K3D8
         return;
     }
-    for (int i = 0; i < n_pend; ++i) {
-        const K3Args &A = pend[i].A;
+    for (int i = 0; i < G.n_pend; ++i) {
+        const K3Args &AA = AP[i];
         const unsigned g = pend[i].g;
         const bool f64 = pend[i].f64;
         KernelProbe *pr = f64 && pend[i].waves == 8 ? env.probe : nullptr;
@@ -2338,31 +2246,31 @@ void launch_k3(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &buf, con
             (void)hipEventRecord(pr->start[slot], env.stream);
         }
         if (pend[i].waves == 1) {
-            const dim3 gd(g, (unsigned)A.n_split);
-            if (f64) hipLaunchKernelGGL((k_k3<ArF64, 1>), gd, dim3(64), 0, st3, A, env.primes);
-            else hipLaunchKernelGGL((k_k3<ArU64, 1>), gd, dim3(64), 0, st3, A, env.primes);
+            const dim3 gd(g, (unsigned)AA.n_split);
+            if (f64) hipLaunchKernelGGL((k_k3<ArF64, 1>), gd, dim3(64), 0, st3, AA, env.primes);
+            else hipLaunchKernelGGL((k_k3<ArU64, 1>), gd, dim3(64), 0, st3, AA, env.primes);
         } else if (pend[i].waves == 4) { // (u64 engine, small grid)
-            if (groups && fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
-            else if (groups) hipLaunchKernelGGL((k_k3<ArU64, 4, false, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
-            else if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 4, false, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
-            else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 4, true, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
-            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true>), dim3(g), dim3(256), 0, st3, A, env.primes);
-            else hipLaunchKernelGGL((k_k3<ArU64, 4>), dim3(g), dim3(256), 0, st3, A, env.primes);
+            if (groups && fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true, false, true>), dim3(g), dim3(256), 0, st3, AA, env.primes);
+            else if (groups) hipLaunchKernelGGL((k_k3<ArU64, 4, false, false, true>), dim3(g), dim3(256), 0, st3, AA, env.primes);
+            else if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 4, false, true>), dim3(g), dim3(256), 0, st3, AA, env.primes);
+            else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 4, true, true>), dim3(g), dim3(256), 0, st3, AA, env.primes);
+            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 4, true>), dim3(g), dim3(256), 0, st3, AA, env.primes);
+            else hipLaunchKernelGGL((k_k3<ArU64, 4>), dim3(g), dim3(256), 0, st3, AA, env.primes);
         } else if (groups) {
-            if (f64 && fuse) hipLaunchKernelGGL((k_k3<ArF64, 8, true, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (f64) hipLaunchKernelGGL((k_k3<ArF64, 8, false, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else hipLaunchKernelGGL((k_k3<ArU64, 8, false, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            if (f64 && fuse) hipLaunchKernelGGL((k_k3<ArF64, 8, true, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (f64) hipLaunchKernelGGL((k_k3<ArF64, 8, false, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else hipLaunchKernelGGL((k_k3<ArU64, 8, false, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
         } else if (f64) {
-            if (raw_tail) hipLaunchKernelGGL((k_k3<ArF64, 8, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (tensor) hipLaunchKernelGGL((k_k3<ArF64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (fuse) hipLaunchKernelGGL((k_k3<ArF64, 8, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else hipLaunchKernelGGL((k_k3<ArF64, 8>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            if (raw_tail) hipLaunchKernelGGL((k_k3<ArF64, 8, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (tensor) hipLaunchKernelGGL((k_k3<ArF64, 8, true, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (fuse) hipLaunchKernelGGL((k_k3<ArF64, 8, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else hipLaunchKernelGGL((k_k3<ArF64, 8>), dim3(g), dim3(512), 0, st3, AA, env.primes);
         } else {
-            if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 8, false, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 8, true, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true>), dim3(g), dim3(512), 0, st3, A, env.primes);
-            else hipLaunchKernelGGL((k_k3<ArU64, 8>), dim3(g), dim3(512), 0, st3, A, env.primes);
+            if (raw_tail) hipLaunchKernelGGL((k_k3<ArU64, 8, false, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (tensor) hipLaunchKernelGGL((k_k3<ArU64, 8, true, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else if (fuse) hipLaunchKernelGGL((k_k3<ArU64, 8, true>), dim3(g), dim3(512), 0, st3, AA, env.primes);
+            else hipLaunchKernelGGL((k_k3<ArU64, 8>), dim3(g), dim3(512), 0, st3, AA, env.primes);
         }
         if (slot >= 0) (void)hipEventRecord(pr->stop[slot], env.stream);
     }
@@ -2376,8 +2284,7 @@ void launch_k3_combine(const KernelEnv &env, int L, u64 n_ops, const KsBuffers &
     K3CombineArgs A;
     A.part = split_part; A.t = buf.t; A.tpr = buf.tpr; A.n_ops = n_ops; A.n_split = n_split; A.n_split_u64 = n_split_u64; A.L = L; A.K = env.K; A.logn1 = env.logn1;
     A.ckks = env.scheme == 2;
-    const u64 jobs = (n_ops * 2 * (u64)(L + 1)) << env.logn1;
-    hipLaunchKernelGGL(k_k3_combine, dim3(grid_for(jobs, kWaves)), dim3(kBlock), 0, env.stream, A, env.primes);
+    hipLaunchKernelGGL(k_k3_combine, dim3(k3_combine_grid(ks_launch_dims(env), L, n_ops)), dim3(kBlock), 0, env.stream, A, env.primes);
 }
 
 void launch_floor_cols(const KernelEnv &env, int src_prime, int n_tgt, u64 n_polys, const u64 *src, u64 *dst, int tgt_first, int dst_ntgt, const u64 *src2,
@@ -2385,14 +2292,14 @@ void launch_floor_cols(const KernelEnv &env, int src_prime, int n_tgt, u64 n_pol
 {
     if (sub2 && !src2) throw std::runtime_error("floor column pass: the earlier correction comes from the merged source");
     if (!n_polys || n_tgt <= 0) return;
+    const FloorColsGrid gc = floor_cols_grid(n_polys, tsplit);
     FloorColsArgs A;
     A.src = src; A.dst = dst; A.src_prime = src_prime; A.n_tgt = n_tgt; A.K = env.K; A.fc = env.floor_consts;
     A.tgt_first = tgt_first; A.dst_ntgt = dst_ntgt > 0 ? dst_ntgt : n_tgt;
     A.src2 = src2; A.src2_prime = src2_prime; A.sub2 = sub2;
-    A.tsplit = tsplit > 1 ? tsplit : 1;
-    const dim3 g((unsigned)(n_polys * 4), (unsigned)A.tsplit);
-    A.f64_mask = 0;
-    for (int t = 0; t < env.K; ++t) A.f64_mask |= (u64)(env.prime_f64[t] != 0) << t;
+    A.tsplit = (int)gc.y;
+    const dim3 g(gc.x, gc.y);
+    A.f64_mask = f64_mask(ks_launch_dims(env));
 #define HE355_FCN(L1)                                                                                                          \
     case L1:                                                                                                                   \
         if (src2) hipLaunchKernelGGL((k_floor_colsn<L1, true>), g, dim3(kBlock), 0, env.stream, A, env.primes);                \
@@ -2404,53 +2311,32 @@ void launch_floor_cols(const KernelEnv &env, int src_prime, int n_tgt, u64 n_pol
 
 void launch_floor_rows(const KernelEnv &env, u64 n_ops, const FloorRowsArgs &args)
 {
-    const unsigned char *prime_f64 = env.prime_f64;
     if (!n_ops) return;
-    const u64 n_jobs = n_ops * args.n_src;
-    // per block: up to 8 jobs per wave, fewer when that would leave CUs without blocks
-    u32 jpb = 8 * kWaves;
-    while (jpb > (u32)kWaves && (((u64)args.n_tgt << env.logn1) * ((n_jobs + jpb - 1) / jpb) < 256u * 8 || jpb / 2 >= n_jobs)) jpb >>= 1;
-    if (args.tail_prime < 0) { // no tail prime; latency shape or small grids: both engines in one launch
-        FloorRowsDev AE[2];
-        unsigned ge[2] = {0, 0};
-        for (int e = 0; e < 2; ++e) {
-            FloorRowsDev &A = AE[e];
-            A.a = args; A.fc = env.floor_consts; A.n_ops = n_ops; A.K = env.K; A.logn1 = env.logn1;
-            A.jobs_per_block = jpb;
-            A.n_i = 0;
-            for (int i = 0; i < args.n_tgt; ++i)
-                if ((prime_f64[i] != 0) == (e == 0)) A.i_list[A.n_i++] = (unsigned char)i;
-            ge[e] = (unsigned)((((u64)A.n_i) << env.logn1) * ((n_jobs + jpb - 1) / jpb));
-        }
-        if (ge[0] && ge[1] && (n_ops <= 8 || ge[0] + ge[1] <= kDualMaxBlocks)) {
-            hipLaunchKernelGGL(k_floor_rows_dual, dim3(ge[0] + ge[1]), dim3(kBlock), 0, env.stream, AE[0], AE[1], ge[0], env.primes);
-            return;
-        }
-    }
-    for (int pass = 0; pass < 4; ++pass) { // (engine, tail) combinations; the tail prime gets its own launch
-        const bool f64 = pass < 2, tail = pass & 1;
-        FloorRowsDev A;
+    const FloorRowsGeometry G = floor_rows_geometry(ks_launch_dims(env), n_ops, args.n_tgt, args.n_src, args.tail_prime);
+    FloorRowsDev AE[4]; // the (engine, tail) passes
+    for (int pass = 0; pass < 4; ++pass) {
+        FloorRowsDev &A = AE[pass];
         A.a = args; A.fc = env.floor_consts; A.n_ops = n_ops; A.K = env.K; A.logn1 = env.logn1;
-        A.jobs_per_block = jpb;
-        A.n_i = 0;
-        for (int i = 0; i < args.n_tgt; ++i)
-            if ((prime_f64[i] != 0) == f64 && (i == args.tail_prime) == tail) A.i_list[A.n_i++] = (unsigned char)i;
-        if (!A.n_i) continue;
-        const unsigned g = (unsigned)((((u64)A.n_i) << env.logn1) * ((n_jobs + jpb - 1) / jpb));
-        const hipStream_t st = env.stream;
-        if (f64 && !tail) hipLaunchKernelGGL((k_floor_rows<ArF64, false>), dim3(g), dim3(kBlock), 0, st, A, env.primes);
-        else if (f64) hipLaunchKernelGGL((k_floor_rows<ArF64, true>), dim3(g), dim3(kBlock), 0, st, A, env.primes);
-        else if (!tail) hipLaunchKernelGGL((k_floor_rows<ArU64, false>), dim3(g), dim3(kBlock), 0, st, A, env.primes);
-        else hipLaunchKernelGGL((k_floor_rows<ArU64, true>), dim3(g), dim3(kBlock), 0, st, A, env.primes);
+        A.jobs_per_block = G.jobs_per_block;
+        copy_list(A.i_list, A.n_i, G.i_list[pass]);
     }
+    const hipStream_t st = env.stream;
+    if (G.dual) {
+        hipLaunchKernelGGL(k_floor_rows_dual, dim3(G.g[0] + G.g[2]), dim3(kBlock), 0, st, AE[0], AE[2], G.g[0], env.primes);
+        return;
+    }
+    if (G.g[0]) hipLaunchKernelGGL((k_floor_rows<ArF64, false>), dim3(G.g[0]), dim3(kBlock), 0, st, AE[0], env.primes);
+    if (G.g[1]) hipLaunchKernelGGL((k_floor_rows<ArF64, true>), dim3(G.g[1]), dim3(kBlock), 0, st, AE[1], env.primes);
+    if (G.g[2]) hipLaunchKernelGGL((k_floor_rows<ArU64, false>), dim3(G.g[2]), dim3(kBlock), 0, st, AE[2], env.primes);
+    if (G.g[3]) hipLaunchKernelGGL((k_floor_rows<ArU64, true>), dim3(G.g[3]), dim3(kBlock), 0, st, AE[3], env.primes);
 }
 
 void launch_rows_inv_select(const KernelEnv &env, int prime, u64 n_polys, const u64 *src, u64 src_poly_stride, u64 *tail)
 {
     if (!n_polys) return;
     const u64 jobs = n_polys << env.logn1;
-    hipLaunchKernelGGL(k_rows_inv_select, dim3(grid_for(jobs, kWaves)), dim3(kBlock), 0, env.stream, src, src_poly_stride, tail, env.primes, prime, jobs,
-                       env.logn1);
+    hipLaunchKernelGGL(k_rows_inv_select, dim3(rows_inv_select_grid(ks_launch_dims(env), n_polys)), dim3(kBlock), 0, env.stream, src, src_poly_stride, tail,
+                       env.primes, prime, jobs, env.logn1);
 }
 
 bool launch_behz_extend(const KernelEnv &env, const BehzDev &bz, const BehzSrc &src, u64 n_cts, u64 *xq, u64 *xbsk)
@@ -2548,6 +2434,17 @@ bool launch_behz_cols_floor_sk(const KernelEnv &env, const BehzDev &bz, u64 n_op
 #undef HE355_FLR
     return exact;
 }
+// the residues of both bases one engine owns: base, index in it, device prime (BehzRowsArgs, BehzTensorArgs)
+template <class Args> void behz_residues(const KernelEnv &env, const BehzDev &bz, bool f64, Args &A)
+{
+    const auto prime_of = [&](int i) { return i < bz.L ? i : (int)bz.bsk_prime[i - bz.L]; };
+    const IndexList l = engine_list(env.prime_f64, f64, bz.L + bz.nB + 1, prime_of);
+    A.n_r = l.n;
+    for (int k = 0; k < l.n; ++k) {
+        const int i = l.at[k], base = i < bz.L ? 0 : 1;
+        A.r_base[k] = (unsigned char)base; A.r_idx[k] = (unsigned char)(base ? i - bz.L : i); A.r_prime[k] = (unsigned char)prime_of(i);
+    }
+}
 bool launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops, const u64 *xq, const u64 *xbsk, u64 *dq, u64 *ds)
 {
     if (!n_ops) return false;
@@ -2558,13 +2455,7 @@ bool launch_behz_rows_tensor(const KernelEnv &env, const BehzDev &bz, u64 n_ops,
         BehzRowsArgs &A = AE[pass];
         A.x[0] = xq; A.x[1] = xbsk; A.d[0] = dq; A.d[1] = ds; A.Lx[0] = bz.L; A.Lx[1] = S;
         A.n_ops = n_ops; A.logn1 = env.logn1;
-        A.n_r = 0;
-        for (int i = 0; i < bz.L + S; ++i) {
-            const int base = i < bz.L ? 0 : 1, idx = base ? i - bz.L : i, prime = base ? bz.bsk_prime[idx] : idx;
-            if ((env.prime_f64[prime] != 0) != (pass == 0)) continue;
-            A.r_base[A.n_r] = (unsigned char)base; A.r_idx[A.n_r] = (unsigned char)idx; A.r_prime[A.n_r] = (unsigned char)prime;
-            ++A.n_r;
-        }
+        behz_residues(env, bz, pass == 0, A);
         ge[pass] = (unsigned)((n_ops * A.n_r) << env.logn1);
     }
     if (ge[0] && ge[1] && ge[0] + ge[1] <= kDualMaxBlocks) {
@@ -2586,13 +2477,7 @@ bool launch_behz_tensor_inv(const KernelEnv &env, const BehzDev &bz, const BehzS
         BehzTensorArgs &A = AE[pass];
         A.e[0] = eq; A.e[1] = ebsk; A.d[0] = dq; A.d[1] = ds; A.Lx[0] = bz.L; A.Lx[1] = S;
         A.src = src; A.n_ops = n_ops; A.op_offset = op_offset; A.logn1 = env.logn1;
-        A.n_r = 0;
-        for (int i = 0; i < bz.L + S; ++i) {
-            const int base = i < bz.L ? 0 : 1, idx = base ? i - bz.L : i, prime = base ? bz.bsk_prime[idx] : idx;
-            if ((env.prime_f64[prime] != 0) != (pass == 0)) continue;
-            A.r_base[A.n_r] = (unsigned char)base; A.r_idx[A.n_r] = (unsigned char)idx; A.r_prime[A.n_r] = (unsigned char)prime;
-            ++A.n_r;
-        }
+        behz_residues(env, bz, pass == 0, A);
         jobs[pass] = ((n_ops * A.n_r) << env.logn1) * 3;
     }
     const unsigned g0 = grid_for(jobs[0], kWaves), g1 = grid_for(jobs[1], kWaves);

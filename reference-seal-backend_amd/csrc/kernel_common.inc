@@ -3,8 +3,7 @@
 // side, the LOGN1 dispatch and the grid sizes of the BFV PIR launches (dispatch_logn1, grid_blocks, streaming_grid).  Included INSIDE the anonymous
 // namespace of a kernel file (after ntt_core.h), once per build of the u64 engine; the text is what he355_kernels.hip held in place
 // through round 5 (same token stream: tools/kres.py shows identical registers / spills / LDS for every instantiation).
-constexpr int kBlock = 256;
-constexpr int kWaves = 4;
+// (kBlock, kWaves -- the block of the row kernels -- are ks_launch.h's, where the grids that assume them are computed)
 
 // Each wave exchanges data only inside its own LDS region: LDS instructions of one wave execute in
 // order, so a wavefront-scope release/acquire pair (compiler ordering only) is all the hand-off needs.

@@ -1,9 +1,11 @@
 """The library's kernel-selection rules restated in plain Python (a helper module: no GPU, no ctypes, nothing compiled).
 
 A key switch is never "the key switch": per chunk the library picks a kernel sequence (`ks_shape`, csrc/ks_shape.h) and per launch a
-grid (`launch_k1`, `launch_k2`, `launch_k3`, `launch_floor_cols`, `launch_floor_rows`, csrc/he355_kernels.hip; the ring-in-LDS launchers
-of csrc/he355_kernels_lds.hip) from the batch, the ring, the level and the engine of each prime.  This module restates those rules -- it
-does not link them (tests/test_launch_plan_cpu.py holds the shape rule to csrc/ks_shape.h on the CPU) -- so that tests can (a) derive the batch sizes that lie on both sides of every threshold instead of guessing them,
+grid (csrc/ks_launch.h, which `launch_k1`, `launch_k2`, `launch_k3`, `launch_k3_combine`, `launch_floor_cols`, `launch_floor_rows` and
+`launch_rows_inv_select` of csrc/he355_kernels.hip call; the ring-in-LDS launchers of csrc/he355_kernels_lds.hip hold theirs) from the
+batch, the ring, the level and the engine of each prime.  This module restates those rules -- it does not link them
+(tests/test_launch_plan_cpu.py holds the shape rule to csrc/ks_shape.h and every `plan_*` launcher function to csrc/ks_launch.h on the
+CPU; the three grids of the LDS shape in `plan_chunk` are literals) -- so that tests can (a) derive the batch sizes that lie on both sides of every threshold instead of guessing them,
 (b) assert the path counters of `he355_path_stats` against a plan, and (c) compare a kernel trace with the planned launches
 (tools/plan_vs_trace.py).  When the restatement and the product disagree, the product decides and this file is what gets corrected.
 
@@ -18,8 +20,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-K_WAVES, K_BLOCK = 4, 256                      # kernel_common.inc
-DUAL_MAX_BLOCKS, DUAL_MAX_BLOCKS_K3 = 1024, 4096  # he355_kernels.hip
+K_WAVES, K_BLOCK = 4, 256                      # ks_launch.h: kWaves, kBlock
+DUAL_MAX_BLOCKS, DUAL_MAX_BLOCKS_K3 = 1024, 4096  # ks_launch.h: kDualMaxBlocks, kDualMaxBlocksK3
 LAT_TARGETS, LAT_SPLIT, LAT_SPLIT_U64 = 8, 2, 8   # ks_shape.h: kLatTargets, kLatSplit, kLatSplitU64
 DEFAULT_CHUNK = 1024
 SCAN_MAX = 512                                 # the largest batch boundary_cases looks at
@@ -167,7 +169,7 @@ def plan_k2(ch: Chain, L: int, n: int, tsplit: int = 1) -> list:
 
 
 def _size_grid(tiles: int, n_ops: int, w: int, u64_pass: bool, L: int):
-    """launch_k3's size_grid: (op-groups, op-groups per block, blocks)"""
+    """ks_launch.h, k3_size_grid: (op-groups, op-groups per block, blocks)"""
     n_og = _cdiv(n_ops, w)
     og_max = (4 if n_og >= 128 else 2) if w == 8 else 4
     work = (14.0 if u64_pass else 7.0) * (L + 2) * (0.5 if w == 4 else 1.0)
@@ -647,8 +649,6 @@ CASES = [
     ("n32768_headline", "rotate_add_in_place", 16, ("shape",)),
     ("n32768_headline", "multiply_relin", 15, ("shape",)),
     ("n32768_headline", "apply_galois", 15, ("shape",)),
-    ("bfv_n8192_60_40_60", "rotate_sum", None, None),
-    ("bfv_n8192_60_40_60", "relinearize", None, None),  # (the coefficient-form key switch: no counter, no planned launches -- last)
     ("n16384_60_50_40_60_shoup", "multiply_relin_rescale", None, None),
     ("n16384_60_50_40_60_shoup", "multiply_relin_rescale_over_a", None, None),
     ("n16384_60_50_40_60_shoup", "relinearize", None, None),
@@ -661,6 +661,10 @@ CASES = [
     ("n8192_60_50_40_60_shoup", "rotate_sum", None, ALL_BUT_OG),
     ("n16384_60_50_60_shoup", "multiply_relin_rescale", None, None),
     ("n16384_60_50_60_shoup", "rotate_sum", None, ALL_BUT_OG),
+    # (the BFV chain last, its coefficient-form key switch -- no counter, no planned launches -- the last row of all: tools/plan_vs_trace.py
+    # deals the traced dispatches to the calls in order, and what that row dispatches is planned by nobody)
+    ("bfv_n8192_60_40_60", "rotate_sum", None, None),
+    ("bfv_n8192_60_40_60", "relinearize", None, None),
 ]
 
 

@@ -1,7 +1,8 @@
-// shape_rules_main.cpp -- TEST-ONLY, stand-alone.  Walks the device context's host rules -- csrc/ks_shape.h, csrc/device_tables.h and
-// csrc/behz_lists.h -- at their edges: batches of 0, 1, 2^32 and 2^63, L = 1 and L_top, logn1 = 0 and 5 (N = 1024 and 32768), a one-prime
+// shape_rules_main.cpp -- TEST-ONLY, stand-alone.  Walks the device context's host rules -- csrc/ks_shape.h, csrc/ks_launch.h,
+// csrc/device_tables.h and csrc/behz_lists.h -- at their edges: batches of 0, 1, 2^32 and 2^63, L = 1 and L_top, logn1 = 0 and 5 (N = 1024 and 32768), a one-prime
 // chain (K = 1), each limit set to 0 (the shape is never taken), to 2^64 - 1 (the rule applies again) and to 2^64 - 2, indexers with gs >= n and
-// with gs that does not divide n -- compiled with -fsanitize=address,undefined (tests/test_launch_plan_cpu.py).  The rules shift by logn1,
+// with gs that does not divide n; the launch geometry at no ops, L = 1, chains of one engine, kMaxPrimes primes with every list full, the
+// level sum's and the other geometry refusals (caught, their texts checked) and the largest grid of the case table -- compiled with -fsanitize=address,undefined (tests/test_launch_plan_cpu.py).  The rules shift by logn1,
 // multiply batch sizes the caller chose and index tables by prime: none of it may overflow a signed type, shift out of range, divide by zero or
 // reach outside a vector (unsigned wrap at an absurd batch is the product's behaviour and stays).  Where a value can be checked in a line it
 // is: the tables' inverses invert, the masks name fp64-engine targets only, the lists of a batch hold every operand a result reads.
@@ -12,6 +13,7 @@
 
 #include "../reference-seal-backend_amd/csrc/behz_lists.h"
 #include "../reference-seal-backend_amd/csrc/device_tables.h"
+#include "../reference-seal-backend_amd/csrc/ks_launch.h"
 #include "../reference-seal-backend_amd/csrc/ks_shape.h"
 #include "args_main_common.h"
 
@@ -67,6 +69,120 @@ static void walk_shapes(const Params &P)
     }
     must(halve_until_fit(1000, [](size_t k) { return k <= 7; }) == 4 && halve_until_fit(1, [](size_t) { return false; }) == 0 &&
              halve_until_fit(5, [](size_t k) { return k == 1; }) == 1, "halve_until_fit");
+}
+
+// ks_launch.h over one set of dimensions: every launcher's geometry at level L for n ops.  The lists of the two engines (digit kinds,
+// passes) partition their range, a grid has a block for every job, and a k_k3 grid is whole 8-tile groups.
+static void walk_geometry(const KsLaunchDims &e, int L, u64 n)
+{
+    for (int c2 = 0; c2 < 2; ++c2) {
+        const K1Geometry G = k1_geometry(e, L, n, c2 != 0);
+        must(G.i_list[0].n + G.i_list[1].n == L, "k_k1: every residue on one engine");
+        for (int p = 0; p < 2; ++p) must((u64)G.grid[p] * kWaves >= (n * G.i_list[p].n) << e.logn1 && (G.grid[p] != 0) == (G.dual_grid[p] != 0), "k_k1: a wave per row job");
+        must(!G.dual || (!c2 && G.grid[0] && G.grid[1] && (n <= 8 || G.dual_grid[0] + G.dual_grid[1] <= kDualMaxBlocks)), "k_k1_dual: both engines, small grids");
+    }
+    for (int tsplit : {1, kLatTargets}) {
+        const K2Geometry G = k2_geometry(e, L, n, tsplit);
+        must(G.dig_list[0].n + G.dig_list[1].n == L && G.gx[0] + G.gx[1] == (unsigned)(n * L * 4), "k_k2n: every digit of one kind");
+        for (int w = 0; w < 2; ++w) must(!G.gx[w] || (tsplit > 1 ? G.ts[w] == tsplit : G.ts[w] == 1 || G.ts[w] == 2 || G.ts[w] == 4), "k_k2n: target split");
+        must(!G.dual || (G.gx[0] && G.gx[1]), "k_k2n_dual: both digit kinds");
+    }
+    must(f64_mask(e) >> (e.K < 64 ? e.K : 63) <= 1, "f64_mask: the chain's primes only");
+    for (int part = 0; part < 3; ++part)
+        for (int form = 0; form < 4; ++form) { // unfused; fused over [0, L); grouped with the level sum; the latency splits
+            K3Request r;
+            r.L = L; r.n_ops = n; r.part = (K3Part)part;
+            if (form == 1 || form == 2) { r.fuse = true; r.tt_lo = 0; r.tt_hi = L; }
+            if (form == 2) { r.grouped = true; r.group_size = 8; r.sum_out = true; }
+            if (form == 3) { r.n_split = kLatSplit; r.n_split_u64 = kLatSplitU64; }
+            if (form == 2 && n % 8) continue;
+            const K3Geometry G = k3_geometry(e, r);
+            int tiles = 0;
+            for (int i = 0; i < G.n_pend; ++i) {
+                const K3Pass &P = G.pend[i];
+                tiles += P.tt_list.n;
+                must(P.tt_list.n > 0 && P.g > 0 && (P.waves == 1 || P.g % 8 == 0), "k_k3: whole 8-tile groups");
+                must(P.waves == (form == 3 ? 1 : P.waves) && (P.waves == 1 || P.waves == 8 || (P.waves == 4 && !P.f64)), "k_k3: waves");
+                const u64 tiles8 = ((((u64)P.tt_list.n << e.logn1) + 7) / 8) * 8;
+                if (!G.level_sum) must((u64)P.g / tiles8 * P.og_per_block * P.waves >= n && P.og_stride == 1, "k_k3: every op in an op-group of a block");
+                else must((u64)P.g / tiles8 == 1 && (u64)P.og_per_block * 8 == n && P.og_stride == 1, "k_k3: the level sum walks the groups");
+                for (int k = 0; k < P.tt_list.n; ++k) must(P.tt_list.at[k] <= L && P.q_slot[k] <= G.n_q, "k_k3: tiles and quotient slots");
+            }
+            const int want = n == 0 ? 0 : r.fuse ? (part == K3_DATA_ONLY ? L : part == K3_ALL ? L : 0) : part == K3_ALL ? L + 1 : part == K3_SPECIAL_ONLY ? 1 : L;
+            must(tiles == want, "k_k3: every tile of the part on one engine");
+            must(G.form == K3Form::Separate || G.n_pend == 2, "k_k3_dual / k_k3_dual8: both engines");
+        }
+    must((u64)k3_combine_grid(e, L, n) * kWaves >= (n * 2 * (u64)(L + 1)) << e.logn1, "k_k3_combine");
+    must(floor_cols_grid(n * 2, 1).y == 1 && floor_cols_grid(n * 2, kLatTargets).y == (unsigned)kLatTargets && floor_cols_grid(n * 2, 0).x == (unsigned)(n * 8), "k_floor_colsn");
+    for (int n_tgt : {L, L - 1})
+        for (int n_src : {2, 3})
+            for (int tail : {-1, n_tgt - 1}) {
+                const FloorRowsGeometry G = floor_rows_geometry(e, n, n_tgt, n_src, tail);
+                must(G.jobs_per_block >= (u32)kWaves && G.jobs_per_block <= 8u * kWaves, "k_floor_rows: jobs per block");
+                must(G.i_list[0].n + G.i_list[1].n + G.i_list[2].n + G.i_list[3].n == n_tgt && G.i_list[1].n + G.i_list[3].n == (tail >= 0 ? 1 : 0), "k_floor_rows: every target in one pass");
+                for (int p = 0; p < 4; ++p) must((u64)G.g[p] * G.jobs_per_block >= (n * n_src * G.i_list[p].n) << e.logn1, "k_floor_rows: a block for every job");
+                must(!G.dual || (tail < 0 && G.g[0] && G.g[2]), "k_floor_rows_dual: both engines, no tail prime");
+            }
+    must((u64)rows_inv_select_grid(e, n * 2) * kWaves >= (n * 2) << e.logn1, "k_rows_inv_select");
+}
+static void refused(const char *text, const KsLaunchDims &e, const K3Request &r)
+{
+    try {
+        (void)k3_geometry(e, r);
+    } catch (const std::runtime_error &x) {
+        must(std::string(x.what()) == text, text);
+        return;
+    }
+    must(false, text);
+}
+static void walk_launches(const Params &P)
+{
+    std::vector<unsigned char> f64(P.K);
+    std::vector<u64> q(P.K);
+    for (size_t i = 0; i < P.K; ++i) { f64[i] = P.primes[i].f64 ? 1 : 0; q[i] = P.primes[i].q; }
+    const KsLaunchDims e{kSchemeCKKS, P.logn1, (int)P.K, f64.data(), q.data()};
+    for (int L : {1, (int)P.Ltop})
+        for (u64 n : {(u64)0, (u64)1, (u64)7, (u64)8, (u64)64, (u64)512}) walk_geometry(e, L, n);
+    // the refusals that are part of the geometry
+    if (P.K >= 2) {
+        const int L = (int)P.Ltop;
+        K3Request r;
+        r.L = L; r.n_ops = 64; r.part = K3_DATA_ONLY; r.fuse = true; r.tt_lo = 0; r.tt_hi = L; r.grouped = true; r.sum_out = true;
+        const char *sum = "level sum in k_k3: fused 8-wave launches over whole groups of a multiple of eight ciphertexts";
+        r.group_size = 12; refused(sum, e, r);                      // not a multiple of eight
+        r.group_size = 24; refused(sum, e, r);                      // not whole groups
+        r.group_size = 16; r.g_op_offset = 8; refused(sum, e, r);   // the launch does not start at a group
+        r.g_op_offset = 16; GOOD("level sum", (void)k3_geometry(e, r));
+        r.n_split = 2; refused("digit-split K3: unfused launches with a partial-sum buffer only", e, r);
+        r.n_ops = 0; refused("digit-split K3: unfused launches with a partial-sum buffer only", e, r); // (refused before the empty launch returns)
+        K3Request t;
+        t.L = L; t.n_ops = 1; t.part = K3_DATA_ONLY; t.fuse = true; t.rescale = true; t.tt_lo = 0; t.tt_hi = L;
+        refused("fused rescale: only primes below the one divided out", e, t);
+        t.tt_hi = L - 1; GOOD("fused rescale", (void)k3_geometry(e, t));
+        t.n_ops = 0; t.tt_hi = L; GOOD("no ops, no refusal of the range", must(k3_geometry(e, t).n_pend == 0, "no ops: no launch"));
+    }
+}
+// kMaxPrimes primes: every list full -- all on the fp64 engine, all on the u64 engine (narrow and wide digits), and alternating
+static void walk_full_lists()
+{
+    for (int kind = 0; kind < 4; ++kind) {
+        unsigned char f64[kMaxPrimes];
+        u64 q[kMaxPrimes];
+        for (int i = 0; i < kMaxPrimes; ++i) {
+            f64[i] = kind == 0 ? 1 : kind == 3 ? i & 1 : 0;
+            q[i] = f64[i] ? (u64)1 << 44 : kind == 1 ? (u64)1 << 49 : (u64)1 << 59;
+        }
+        for (int logn1 : {0, 5}) {
+            const KsLaunchDims e{kSchemeCKKS, logn1, kMaxPrimes, f64, q};
+            for (u64 n : {(u64)1, (u64)512}) walk_geometry(e, kMaxPrimes - 1, n);
+            must(k1_geometry(e, kMaxPrimes, 1, false).i_list[kind == 0 ? 0 : 1].n == (kind == 3 ? kMaxPrimes / 2 : kMaxPrimes), "k_k1: a full list");
+            must(floor_rows_geometry(e, 1, kMaxPrimes, 2, -1).i_list[kind == 0 ? 0 : 2].n == (kind == 3 ? kMaxPrimes / 2 : kMaxPrimes), "k_floor_rows: a full list");
+            K3Request r;
+            r.L = kMaxPrimes - 1; r.n_ops = 1;
+            must(k3_geometry(e, r).pend[0].tt_list.n == (kind == 3 ? kMaxPrimes / 2 : kMaxPrimes), "k_k3: a full list");
+            must(k2_geometry(e, kMaxPrimes, 1, 1).dig_list[kind == 2 ? 1 : 0].n == (kind == 3 ? kMaxPrimes / 2 : kMaxPrimes), "k_k2n: a full list");
+        }
+    }
 }
 
 static void walk_tables(const Params &P)
@@ -134,15 +250,24 @@ int main()
 {
     // N = 1024 (logn1 = 0) and N = 32768 (logn1 = 5); a one-prime chain, the smallest key-switching chain and a deep one
     for (size_t N : {(size_t)1024, (size_t)32768}) {
-        for (const std::vector<int> &bits : {std::vector<int>{50}, std::vector<int>{50, 50}, std::vector<int>{60, 45, 40, 60, 45, 40, 45, 60}}) {
+        // ... and chains of one engine: {50, 50} the u64 engine's, {45, 44, 46} the fp64 engine's
+        for (const std::vector<int> &bits : {std::vector<int>{50}, std::vector<int>{50, 50}, std::vector<int>{45, 44, 46}, std::vector<int>{60, 45, 40, 60, 45, 40, 45, 60}}) {
             std::unique_ptr<Params> pp(Params::create(kSchemeCKKS, N, bits, 0, false));
             GOOD("shape rules", walk_shapes(*pp));
+            GOOD("launch geometry", walk_launches(*pp));
             GOOD("device tables", walk_tables(*pp));
         }
         std::unique_ptr<Params> pb(Params::create(kSchemeBFV, N, {60, 40, 60}, 20, false));
         GOOD("shape rules, BFV context", walk_shapes(*pb));
         GOOD("device tables, BFV context", walk_tables(*pb));
         for (int L : {1, 2}) GOOD("BEHZ lists", walk_lists(L, pb->behz_nB(L) + 1, N));
+    }
+    GOOD("launch geometry, kMaxPrimes primes", walk_full_lists());
+    { // the largest grid of the case table: the headline chain {60, 45 x 15, 60} at N = 32768, L = 16, 512 ciphertexts
+        std::vector<int> bits(17, 45);
+        bits.front() = bits.back() = 60;
+        std::unique_ptr<Params> ph(Params::create(kSchemeCKKS, 32768, bits, 0, false));
+        GOOD("launch geometry, headline chain", walk_launches(*ph));
     }
     if (failures) return 1;
     std::printf("shape_rules ok\n");

@@ -1,8 +1,9 @@
 """tests/launch_plan.py -- the library's kernel-selection rules restated in Python -- pinned to what the product's comments, profiles/
 and tests/test_gpu_bench_shapes.py state, and the completeness of the case table of tests/test_gpu_selection_boundaries.py: over that
-table every selection decision takes every one of its outcomes at least once.  The shape rule itself is held to the product's text:
-csrc/ks_shape.h through the entry points of tests/csim/sim_rules.cpp, cell by cell over every chain, level and batch the restatement was
-built for, and the three host headers of the device context's rules at their edges under the sanitizers (tests/shape_rules_main.cpp).
+table every selection decision takes every one of its outcomes at least once.  The restatement itself is held to the product's text:
+the shape rule to csrc/ks_shape.h and every launcher's grids to csrc/ks_launch.h through the entry points of tests/csim/sim_rules.cpp,
+cell by cell over every chain, level and batch the restatement was built for, and the four host headers of the device context's rules
+at their edges under the sanitizers (tests/shape_rules_main.cpp).
 No GPU, and the device library is not loaded."""
 import ctypes as C
 import os
@@ -217,6 +218,11 @@ def rules():
     S.sim_lds_limit.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, u64p, C.c_int]
     S.sim_ks_scan.restype = C.c_uint64
     S.sim_ks_scan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, u64p, C.c_int, C.c_uint64, u64p, C.c_size_t, u8p, u8p, u8p, u64p, u8p]
+    i32p = C.POINTER(C.c_int32)
+    S.sim_kl_consts.restype = None
+    S.sim_kl_consts.argtypes = [i32p]
+    S.sim_kl_scan.restype = None
+    S.sim_kl_scan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u8p, u64p, C.c_int, C.c_uint64, i32p, C.c_size_t, i32p]
     return S
 
 
@@ -247,6 +253,101 @@ def test_shape_rule_equals_the_header_over_every_chain_level_and_batch(rules):
                         assert SHAPES[shape[(at * 4 + k) * 2 + apart]] == lp.ks_shape(ch, L, n, kind, apart), (name, L, n, kind, apart)
                 for ci, c in enumerate(chunks):
                     assert bool(lsum[ci * Lt * nmax + at]) == lp.level_sum_pays(ch, L, n, c), (name, L, n, c)
+
+
+# ---- the launch geometry held to csrc/ks_launch.h ------------------------------------------------------------------------------------------
+K3_ALL, K3_SPECIAL, K3_DATA = 0, 1, 2  # K3Part, in order
+AT_L, AT_L1, NO_TAIL = -1, -2, -100      # level arguments of sim_kl_scan: L, L - 1; no tail prime
+GS_N = -1                              # group size: the batch itself (rotate_sum: one group per trie node)
+PARTS = {K3_ALL: "all", K3_SPECIAL: "special", K3_DATA: "data"}
+# launch_k3 as plan_chunk issues it: {part, fuse (3: with the rescale's second floor step), tt_lo, tt_hi, n_split, n_split_u64, group size, sum_out}
+K3_COMBOS = (
+    [(part, 0, 0, 0, 1, 0, 0, 0) for part in PARTS]                                         # unfused: all / special / data
+    + [(K3_DATA, 1, 0, AT_L, 1, 0, 0, 0), (K3_DATA, 3, 0, AT_L1, 1, 0, 0, 0), (K3_DATA, 1, AT_L1, AT_L, 1, 0, 0, 0)]  # fused over [0, L), [0, L-1), [L-1, L)
+    + [(K3_ALL, 0, 0, 0, lp.LAT_SPLIT, lp.LAT_SPLIT_U64, 0, 0)]                              # the latency splits
+    + [c for gs in (1, GS_N) for c in ((K3_ALL, 0, 0, 0, 1, 0, gs, 0), (K3_SPECIAL, 0, 0, 0, 1, 0, gs, 0), (K3_DATA, 1, 0, AT_L, 1, 0, gs, 0))]  # grouped
+    + [(K3_SPECIAL, 0, 0, 0, 1, 0, gs, 1) for gs in (8, GS_N)]                               # the special prime's launch ahead of a level sum
+    + [(K3_DATA, 1, 0, AT_L, 1, 0, gs, 1) for gs in (1, 8, 12, GS_N)]                        # the level sum: groups of a multiple of eight or not
+)
+LAUNCHERS = {
+    # name: (launcher code of sim_kl_scan, kernel families by form, the combinations, lp's plan of one combination)
+    "launch_k1": (0, ("k_k1", "k_k1_dual"), [(c2,) for c2 in (0, 1)], None),
+    "launch_k2": (1, ("k_k2n", "k_k2n_dual"), [(1,), (lp.LAT_TARGETS,)], lambda ch, L, n, c: lp.plan_k2(ch, L, n, c[0])),
+    "launch_k3": (2, ("k_k3", "k_k3_dual", "k_k3_dual8"), K3_COMBOS, None),
+    "launch_k3_combine": (3, ("k_k3_combine",), [()], lambda ch, L, n, c: lp.plan_k3_combine(ch, L, n)),
+    "launch_floor_cols": (4, ("k_floor_colsn",), [(size, tgt, ts) for size in (2, 3) for tgt in (1, AT_L1, AT_L) for ts in (1, lp.LAT_TARGETS)], None),
+    "launch_floor_rows": (5, ("k_floor_rows", "k_floor_rows_dual"), [(tgt, n_src, tail) for tgt in (AT_L, AT_L1) for n_src in (2, 3) for tail in (NO_TAIL, tgt - 1)], None),
+    "launch_rows_inv_select": (6, ("k_rows_inv_select",), [(2,), (3,)], lambda ch, L, n, c: lp.plan_rows_inv_select(ch, n * c[0])),
+}
+
+
+def _level(L, v):
+    return v if v >= 0 else L + 1 + v
+
+
+def _plans(name, ch, L, n, c):
+    """lp's plans of combination c of launcher `name`: [launches] per restated argument set that the combination stands for, or None where
+    the restatement refuses the arguments"""
+    if name == "launch_k1":  # the header reads one flag of (mode, no_c01): the ct x ct multiply that leaves c0, c1 to k_k3
+        return [lp.plan_k1(ch, L, mode, n, no_c01) for mode in ("product", "size3", "galois") for no_c01 in (False, True)
+                if (mode == "product" and no_c01) == bool(c[0])]
+    if name == "launch_k3":
+        part, fuse, lo, hi, n_split, n_split_u64, gs, sum_out = c
+        try:
+            return [lp.plan_k3(ch, L, n, PARTS[part], bool(fuse), _level(L, lo), _level(L, hi), n_split, n_split_u64, n if gs == GS_N else gs, bool(sum_out))]
+        except AssertionError:
+            return None
+    if name == "launch_floor_cols":
+        return [lp.plan_floor_cols(ch, n * c[0], _level(L, c[1]), c[2])]
+    if name == "launch_floor_rows":
+        return [lp.plan_floor_rows(ch, n, _level(L, c[0]), c[1], -1 if c[2] == NO_TAIL else _level(L, c[2]))]
+    return [LAUNCHERS[name][3](ch, L, n, c)]
+
+
+def _row(families, l):
+    """one planned launch as sim_kl_scan's row"""
+    form = families.index(l.family)
+    og_u64 = int(l.note.split("u64")[1]) if form == 2 else 0
+    engine = {"fp64": 1, "u64": 2}.get(l.engine, 0)
+    if l.family == "k_k2n":
+        engine = 2 if l.note == "60-bit digits" else 1
+    return [form, l.grid[0], l.grid[1], l.block, l.og_per_block, og_u64, l.waves, l.ts, engine]
+
+
+def test_launch_constants_are_the_headers(rules):
+    out = (C.c_int32 * 7)()
+    rules.sim_kl_consts(out)
+    assert list(out) == [lp.K_WAVES, lp.K_BLOCK, lp.DUAL_MAX_BLOCKS, lp.DUAL_MAX_BLOCKS_K3, lp.LAT_TARGETS, lp.LAT_SPLIT, lp.LAT_SPLIT_U64]
+
+
+@pytest.mark.parametrize("name", list(LAUNCHERS))
+def test_launch_geometry_equals_the_header_over_every_chain_level_and_batch(rules, name):
+    """lp.plan_k1, plan_k2 (_target_split), plan_k3 (_size_grid), plan_k3_combine, plan_floor_cols, plan_floor_rows and plan_rows_inv_select
+    against csrc/ks_launch.h: every chain of lp.CHAINS, L = 1 .. L_top, n = 1 .. lp.SCAN_MAX, every argument combination plan_chunk,
+    plan_rescale_tail, _plan_rotate_sum and _plan_rotate_each can issue.  Per launch: the family (dual, dual8 or the engine's own), grid
+    x and y, threads per block, op-groups per block (both sides of k_k3_dual8), waves, target split, engine.  The header reads moduli where
+    the restatement reads bit sizes: a stand-in modulus of the stated bit length (only q >> 52 is read), engines from lp.engines."""
+    code, families, combos, _ = LAUNCHERS[name]
+    nmax, nc = lp.SCAN_MAX, len(combos)
+    flat = (C.c_int32 * (nc * 8))(*[v for c in combos for v in tuple(c) + (0,) * (8 - len(c))])
+    for cname in lp.CHAINS:
+        ch = lp.case_chain(cname)
+        Lt = ch.Ltop
+        out = (C.c_int32 * (Lt * nmax * nc * 37))()
+        rules.sim_kl_scan(code, SCHEME_CKKS, ch.logn1, ch.K, (C.c_uint8 * ch.K)(*ch.fp64), (C.c_uint64 * ch.K)(*[1 << (b - 1) for b in ch.bits]),
+                          Lt, nmax, flat, nc, out)
+        got = out[:]
+        for L in range(1, Lt + 1):
+            for n in range(1, nmax + 1):
+                for ci, c in enumerate(combos):
+                    at = (((L - 1) * nmax + n - 1) * nc + ci) * 37
+                    plans = _plans(name, ch, L, n, c)
+                    if plans is None:
+                        assert got[at] == -1, (cname, L, n, c)
+                        continue
+                    for ls in plans:
+                        want = [len(ls)] + [v for l in ls for v in _row(families, l)]
+                        assert got[at:at + len(want)] == want, (cname, L, n, c, ls)
 
 
 def test_shape_rule_with_the_limits_set(rules):
