@@ -1,5 +1,5 @@
 // behz_core.h -- the per-coefficient arithmetic of the BEHZ multiply (base extension with the Montgomery correction; times t, fast
-// floor, Shenoy-Kumaresan) and the constants it runs on.  Host-compilable on purpose: the HIP kernels (he355_kernels.hip: k_behz_extend,
+// floor, Shenoy-Kumaresan) and the constants it runs on.  Host-compilable on purpose: the HIP kernels (he355_kernels_behz.hip: k_behz_extend,
 // k_behz_extend_cols, k_behz_floor_sk, k_behz_cols_floor_sk) and the test-only lane simulator (tests/csim/sim_behz.cpp, which holds
 // these very functions to exact integer arithmetic on the CPU, extremes of the Shenoy-Kumaresan bound included) compile the same text.
 #pragma once

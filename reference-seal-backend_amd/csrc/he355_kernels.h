@@ -1,4 +1,4 @@
-// he355_kernels.h — host-callable launchers of the HIP kernels (implemented in he355_kernels.hip).
+// he355_kernels.h — host-callable launchers of the HIP kernels (each implemented in the he355_kernels*.hip file of the kernels it launches).
 // All launchers enqueue on `stream` and return immediately; none allocates or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // he355_launchers.inc -- prototypes of the host-callable launchers, included by he355_kernels.h once per build of the device code
 // (namespace ks_shoup: the u64 engine multiplies by constants through Shoup quotients; namespace ks_fold: through the fold reduction
-// for primes 2^60 - c, modarith.h).  he355_kernels.hip / he355_kernels_client.hip are compiled twice, each time into one of the two.
+// for primes 2^60 - c, modarith.h).  Every he355_kernels*.hip is compiled twice, each time into one of the two.
 // ---- generic transforms over a PolyView (in place) ---------------------------------------------------
 void launch_ntt_forward(const KernelEnv &env, const PolyView &v, u32 n_items);  // canonical -> canonical NTT form
 void launch_ntt_inverse(const KernelEnv &env, const PolyView &v, u32 n_items);  // canonical NTT form -> coefficients

@@ -1,4 +1,4 @@
-// Body of k_k2n (he355_kernels.hip), textually included: in the template kernel k_k2n<LOGN1, WIDE> (K2N_BID_X = blockIdx.x: the token
+// Body of k_k2n (he355_kernels_ks.hip), textually included: in the template kernel k_k2n<LOGN1, WIDE> (K2N_BID_X = blockIdx.x: the token
 // stream, and with it the code object of the headline's instantiations, is what it was before the split) and, behind a function
 // boundary, once per digit kind in k_k2n_dual (latency shape).  In scope at the point of inclusion: LOGN1, WIDE, A (K2Args), primes.
     constexpr int N1 = 1 << LOGN1;

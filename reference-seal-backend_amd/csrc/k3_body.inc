@@ -1,4 +1,4 @@
-// Body of k_k3 (he355_kernels.hip), textually included: once in the template kernel k_k3<Ar, WAVES, FUSE, TENSOR, GROUPED>
+// Body of k_k3 (he355_kernels_k3.hip), textually included: once in the template kernel k_k3<Ar, WAVES, FUSE, TENSOR, GROUPED>
 // (K3_BID_X / K3_BID_Y = blockIdx.x / blockIdx.y: the same token stream as before the split, hence the same code object -- the
 // register allocation of the headline's instantiations is the product's bottleneck and a __device__ function boundary changed it,
 // 48.5 -> 49.0 ms per step) and once per engine in k_k3_dual, the latency shape's both-engines-in-one-launch kernel.

@@ -1,8 +1,9 @@
-// kernel_common.inc -- helpers shared by the kernel translation units (he355_kernels.hip, he355_kernels_lds.hip, he355_kernels_bfv_*.hip):
-// wavefront-scope hand-offs, engine construction, row <-> register moves, the LDS-DMA row fetch, the wave-level row transforms and, host
-// side, the LOGN1 dispatch and the grid sizes of the BFV PIR launches (dispatch_logn1, grid_blocks, streaming_grid).  Included INSIDE the anonymous
-// namespace of a kernel file (after ntt_core.h), once per build of the u64 engine; the text is what he355_kernels.hip held in place
-// through round 5 (same token stream: tools/kres.py shows identical registers / spills / LDS for every instantiation).
+// kernel_common.inc -- helpers shared by the kernel translation units (every he355_kernels*.hip, one kernel family each):
+// wavefront-scope hand-offs, engine construction, row <-> register moves, the LDS-DMA row fetch, the wave-level row transforms, the
+// block's twiddle staging and, host side, the LOGN1 dispatch of every launcher with a per-ring instantiation and the grid sizes of the
+// BFV PIR launches (dispatch_logn1, grid_blocks, streaming_grid).  Included INSIDE the anonymous namespace of a kernel file (after
+// ntt_core.h), once per build of the u64 engine; the text is what one kernel file held in place through round 5 and the key-switch
+// files shared until they were split (same token stream: tools/kres.py shows identical registers / spills / LDS for every instantiation).
 // (kBlock, kWaves -- the block of the row kernels -- are ks_launch.h's, where the grids that assume them are computed)
 
 // Each wave exchanges data only inside its own LDS region: LDS instructions of one wave execute in
@@ -73,11 +74,16 @@ __device__ __forceinline__ void store_rowC(u64 *row, int lane, const u64 v[kRowE
 }
 
 // ---- host side: launches of the kernels with a column pass, and grids ------------------------------------------------------------------
-// launch(std::integral_constant<int, LOGN1>) for the ring's LOGN1 = logn1 in 1..5 (N = 2048 .. 32768; N = 1024 has no column pass)
-template <class Launch>
+// launch(std::integral_constant<int, LOGN1>) for the ring's LOGN1 = logn1 in LO..5 (N = 2048 .. 32768; LO = 1: N = 1024 has no column
+// pass; LO = 0: the kernels that take N = 1024 as a column of one).  A context has no other ring (Params: N in [1024, 32768]).
+template <int LO = 1, class Launch>
 void dispatch_logn1(int logn1, Launch &&launch)
 {
-    switch (logn1) {
+    static_assert(LO == 0 || LO == 1, "the lowest ring is N = 1024 or N = 2048");
+    switch (logn1 < LO ? -1 : logn1) {
+    case 0:
+        if constexpr (LO == 0) launch(std::integral_constant<int, 0>());
+        break;
     case 1: launch(std::integral_constant<int, 1>()); break;
     case 2: launch(std::integral_constant<int, 2>()); break;
     case 3: launch(std::integral_constant<int, 3>()); break;
@@ -249,3 +255,36 @@ __device__ __forceinline__ void wave_rows_inv(const Ar &ar, const PrimeDev &P, b
     else row_inv_A_w<Ar, false>(ar, x, wa, P.inv_w0_scaled);
 }
 
+// Stage the 1023 forward twiddles of row `rowbase` of prime P in LDS (one copy per block): every wave, digit and op
+// of a (prime, row) tile reads them from there (ds_read, lane-dependent index) instead of L2.  fp64 engine: w only.
+// The caller synchronises the block before the first use.
+template <class Ar, int BLOCK>
+__device__ __forceinline__ typename std::conditional<std::is_same<Ar, ArF64>::value, TwRowF64, TwRow>::type
+stage_row_twiddles(const PrimeDev &P, const Ar &ar, u32 rowbase, unsigned char *twl_raw, bool inverse = false)
+{
+    constexpr bool kF64 = std::is_same<Ar, ArF64>::value;
+    typename std::conditional<kF64, TwRowF64, TwRow>::type twr;
+    const gtw_t gf = gtw(inverse ? P.inv : P.fwd); // (the two tables share their indexing: entry (rowbase << s) + g of stage s)
+    constexpr int kIter = (kRowTw + BLOCK - 1) / BLOCK;
+    Tw16 tmp[kIter];
+#pragma unroll
+    for (int k = 0; k < kIter; ++k) { // all loads in flight together
+        const u32 i = threadIdx.x + k * BLOCK;
+        tmp[k] = tw_load(gf, tw_row_source(rowbase, i + 1 < (u32)kRowTw ? i : 0));
+    }
+    if constexpr (kF64) {
+        double *twl = reinterpret_cast<double *>(twl_raw);
+#pragma unroll
+        for (int k = 0; k < kIter; ++k)
+            if (threadIdx.x + k * BLOCK < (u32)kRowTw) twl[threadIdx.x + k * BLOCK] = ArF64::tw_w(tmp[k]);
+        twr.t = twl;
+        twr.qinv = ar.qinv;
+    } else {
+        Tw16 *twl = reinterpret_cast<Tw16 *>(twl_raw);
+#pragma unroll
+        for (int k = 0; k < kIter; ++k)
+            if (threadIdx.x + k * BLOCK < (u32)kRowTw) twl[threadIdx.x + k * BLOCK] = tmp[k];
+        twr.t = twl;
+    }
+    return twr;
+}

@@ -1,7 +1,8 @@
 // ks_launch.h -- the launch geometry of the key-switch kernels, spelt once: which kernels of a chunk's sequence (ks_shape.h) run as one
 // launch for both engines or as one per engine, with which grid, and what each launch's argument block says about its share of the work
-// (the engine's primes, op-groups per block, waves, target split).  The launchers of he355_kernels.hip -- launch_k1, launch_k2, launch_k3,
-// launch_k3_combine, launch_floor_cols, launch_floor_rows, launch_rows_inv_select -- call these functions, fill the kernels' argument blocks
+// (the engine's primes, op-groups per block, waves, target split).  The launchers of he355_kernels_ks.hip (launch_k1, launch_k2,
+// launch_floor_cols, launch_floor_rows), he355_kernels_k3.hip (launch_k3, launch_k3_combine) and he355_kernels.hip
+// (launch_rows_inv_select) call these functions, fill the kernels' argument blocks
 // from the operands and the plan, and launch; nothing here reserves, launches or counts.  The rules read KsLaunchDims, what a launcher
 // reads of its KernelEnv (he355_kernels.h: ks_launch_dims).  Host-only, like ks_shape.h (no HIP header): tests/csim returns the plans to
 // tests/test_launch_plan_cpu.py, which holds tests/launch_plan.py's restatement to them, and tests/shape_rules_main.cpp walks their edges
@@ -47,6 +48,13 @@ template <class PrimeOf> IndexList engine_list(const unsigned char *prime_f64, b
         if (p >= 0 && (prime_f64[p] != 0) == f64) l.at[l.n++] = (unsigned char)i;
     }
     return l;
+}
+// a list into the fixed array and count of a kernel's argument block
+template <size_t N> void copy_list(unsigned char (&dst)[N], int &n, const IndexList &l)
+{
+    static_assert(N >= sizeof(l.at), "an argument block's list holds every prime");
+    n = l.n;
+    std::copy(l.at, l.at + l.n, dst);
 }
 // bit t: the fp64 engine owns target prime t (k_k2n, k_floor_colsn)
 inline u64 f64_mask(const KsLaunchDims &e)

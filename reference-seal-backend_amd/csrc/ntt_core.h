@@ -447,7 +447,7 @@ template <class Ar, int LOGN1, class TW> HE_HD void col_fwd(const Ar &ar, typena
 //   * the twiddles as bare doubles (PrimeDev::colw: 8 bytes per entry in scalar registers instead of 16),
 //   * the first stage reading its inputs through in(a) (the lifted source column is kept for the next target prime, so the
 //     stage writes x out of place instead of transforming a copy),
-//   * BIAS: the last stage adds `bias` to both outputs, (X + bias) +- t.  With bias = kPackBias (he355_kernels.hip) and
+//   * BIAS: the last stage adds `bias` to both outputs, (X + bias) +- t.  With bias = kPackBias (kernel_common.inc) and
 //     |X +- t| < 2^47 every sum is an integer in [2^52, 2^53), hence exact, and the outputs are the 48-bit row patterns themselves:
 //     one addition per butterfly instead of one per element.
 template <int LOGN1, bool BIAS, class In, class TW> HE_HD void col_fwd_w(const ArF64 &ar, In in, double x[1 << LOGN1], TW cw, double bias)

@@ -1,5 +1,5 @@
 """The host-side kernel selection of the BEHZ multiply (`behz_lists` in csrc/behz_lists.h and `bfv_multiply3` in csrc/he355_api.hip, the
-`launch_behz_*` functions and `behz_cols_fusable` in csrc/he355_kernels.hip) restated in plain Python, in the manner of tests/launch_plan.py:
+`launch_behz_*` functions and `behz_cols_fusable` in csrc/he355_kernels_behz.hip) restated in plain Python, in the manner of tests/launch_plan.py:
 it restates the rules, it does not link them (tests/test_bfv_multiply_plan_cpu.py holds `takes_lists` to the header).  Tests use it to (a) derive the batches that lie on both sides of every decision instead of guessing them and (b) assert
 the counters of `he355_bfv_multiply_stats` against a plan.  When the restatement and the product disagree, the product decides and this
 file is what gets corrected.
@@ -26,7 +26,7 @@ import os
 from dataclasses import dataclass
 
 K_WAVES = 4                      # kernel_common.inc
-DUAL_MAX_BLOCKS = 1024           # he355_kernels.hip: kDualMaxBlocks
+DUAL_MAX_BLOCKS = 1024           # ks_launch.h: kDualMaxBlocks
 DEFAULT_CHUNK = 1024             # ks_shape.h: KsLimits::chunk
 LDS_NO_OPT_IN = 64 << 10         # what every HIP device grants a block without asking
 LDS_MI355X = 160 << 10           # CDNA4: the LDS of one CU, all of which one workgroup may take

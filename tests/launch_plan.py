@@ -2,7 +2,7 @@
 
 A key switch is never "the key switch": per chunk the library picks a kernel sequence (`ks_shape`, csrc/ks_shape.h) and per launch a
 grid (csrc/ks_launch.h, which `launch_k1`, `launch_k2`, `launch_k3`, `launch_k3_combine`, `launch_floor_cols`, `launch_floor_rows` and
-`launch_rows_inv_select` of csrc/he355_kernels.hip call; the ring-in-LDS launchers of csrc/he355_kernels_lds.hip hold theirs) from the
+`launch_rows_inv_select` of csrc/he355_kernels_ks.hip, he355_kernels_k3.hip and he355_kernels.hip call; the ring-in-LDS launchers of csrc/he355_kernels_lds.hip hold theirs) from the
 batch, the ring, the level and the engine of each prime.  This module restates those rules -- it does not link them
 (tests/test_launch_plan_cpu.py holds the shape rule to csrc/ks_shape.h and every `plan_*` launcher function to csrc/ks_launch.h on the
 CPU; the three grids of the LDS shape in `plan_chunk` are literals) -- so that tests can (a) derive the batch sizes that lie on both sides of every threshold instead of guessing them,

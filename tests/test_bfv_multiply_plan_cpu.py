@@ -1,5 +1,5 @@
 """tests/bfv_multiply_plan.py -- the restatement of the BEHZ multiply's host-side kernel selection -- pinned to the numbers of the launchers
-(csrc/he355_kernels.hip) and to the operand-list geometry `bfv_multiply3` runs on (csrc/behz_lists.h, through tests/csim), and the case table of tests/test_gpu_bfv_multiply_routes.py shown to take
+(csrc/he355_kernels_behz.hip) and to the operand-list geometry `bfv_multiply3` runs on (csrc/behz_lists.h, through tests/csim), and the case table of tests/test_gpu_bfv_multiply_routes.py shown to take
 every outcome of every decision and each of the seven fused and two unfused instantiations at least once.  The auxiliary bases come from
 the CPU build of the product's parameter code (tests/csim).  No GPU."""
 import ctypes as C

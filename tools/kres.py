@@ -53,4 +53,4 @@ def main(path, flt=""):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "reference-seal-backend_amd/csrc/_obj/he355_kernels.o", sys.argv[2] if len(sys.argv) > 2 else "")
+    main(sys.argv[1] if len(sys.argv) > 1 else "reference-seal-backend_amd/csrc/_obj/he355_kernels_k3.fold.o", sys.argv[2] if len(sys.argv) > 2 else "")
