@@ -791,10 +791,58 @@ typedef struct he355_poly_stats {
     uint64_t rescales;     /* he355_rescale calls made by it, per chunk                                    */
     uint64_t drops, adds;  /* he355_mod_switch_drop copies / he355_add calls made by it, per chunk         */
     uint64_t chunks;       /* chunks he355_ckks_eval_poly walked                                           */
-    uint64_t calls;        /* he355_ckks_eval_poly calls with work                                         */
-    uint64_t reserved;
+    uint64_t calls;        /* he355_ckks_eval_poly / he355_ckks_eval_poly_complex calls with work          */
+    uint64_t complex_combinations; /* k_scalar_combine_cplx launches; `combinations` does not count them   */
 } he355_poly_stats_t;
 int he355_poly_stats(he355_ctx *ctx, he355_poly_stats_t *out, int reset);
+/* ---- complex CKKS slots: codec, complex scalars and complex polynomial coefficients ----
+ * The encoders place slot j at zeta^(3^j) (SEAL's slot map).  Because 3 = 3 (mod 4), X^(N/2) evaluates to i * (-1)^j in slot j: it is NOT
+ * "multiply by i".  What exists is J(X) = X^(N/4) + X^(3N/4):
+ *   J decodes to sqrt(2) * i in EVERY slot, exactly;
+ *   NTT_{q_i}(J)[e] = u_i when bit (log2 N - 2) of the NTT index e is 0, and q_i - u_i when it is 1;  u_i = NTT_{q_i}(J)[0],  u_i^2 = -2 (mod q_i).
+ * So a complex constant at weight W is the integer polynomial A + B * J, A = rint(Re * W), B = rint(Im * W / sqrt(2)): in NTT form ONE of two
+ * residues per prime, A +- B * u_i, chosen by s(e) = bit (log2 N - 2) of e.  Like every scalar of he355_ckks_eval_poly it carries its scale.
+ *
+ * he355_ckks_encode_complex: he355_ckks_encode with d_values [n][count][2] doubles (re, then im): z[slot_index[i]] = v and
+ *   z[slot_index[N/2 + i]] = conj(v); everything else is the shared code of client/ckks_codec.h in the same order of IEEE operations, with
+ *   the same overflow refusal ("encoded values are too large": a non-finite value ends there).  Values with im = +0.0 give the residues of
+ *   he355_ckks_encode bit for bit (the signed zeros of the conjugate reach only results that are zero).
+ * he355_ckks_decode_complex / _slots: d_out [n][N/2][2] / [n][sum of counts][2]; the re parts are the bits of he355_ckks_decode /
+ *   he355_ckks_decode_slots, the im parts the .im the transform already holds.  The same two kernels, then one gather of the wanted pairs.
+ * Both agree with client::Client::ckks_encode_complex / ckks_decode_complex (the host client, csrc/client/he_client.h) bit for bit.
+ * Refused on the host before any device work (HE355_E_INVALID_ARGS, the message names the call): a BFV context, count > N/2, L outside
+ * 1..L_top or above 16, a scale that is not finite and positive, 0 or more than 4 ranges or one outside the N/2 slots, null pointers with
+ * work to do, slabs past 2^60 words or wrapping the address space.  n == 0 touches nothing. */
+int he355_ckks_encode_complex(he355_ctx *ctx, uint64_t n, const double *d_values /* [n][count][2] */, uint64_t count, double scale,
+                              uint64_t *d_plain /* [n][L_top][N], NTT form */);
+int he355_ckks_decode_complex(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain, double scale, double *d_out /* [n][N/2][2] */);
+int he355_ckks_decode_complex_slots(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_plain, double scale, const uint64_t *ranges, uint64_t n_ranges,
+                                    double *d_out /* [n][sum of counts][2] */);
+/* Host only: out[i] = u_i.  Refused: L outside 1..L_top, null out. */
+int he355_ckks_complex_unit(const he355_ctx *ctx, int L, uint64_t *out /* [L] */);
+/* Host only: A = the integer of he355_ckks_scalar_residues(v_re), B = that of v_im / sqrt(2.0) (an IEEE division: Python's
+ * v_im / math.sqrt(2.0)); out[0][i] = (A + B * u_i) mod q_i, out[1][i] = (A - B * u_i) mod q_i, canonical.  Refuses what
+ * he355_ckks_scalar_residues refuses, for either part. */
+int he355_ckks_complex_scalar_residues(const he355_ctx *ctx, int L, double v_re, double v_im, uint64_t *out /* [2][L] */);
+/* he355_combine_scalars with the scalar and the constant picked per NTT index:
+ *   out[c][k][i][e] = (sum_t h_scalars[t][s(e)][i] * term_t[c][k][i][e] + (k == 0 ? h_const[s(e)][i] : 0)) mod q_i,  s(e) = bit (log2 N - 2) of e
+ * Any pair of canonical residues is allowed, not only A +- B * u.  Terms, levels, strides, the overlap rules, the 2^20-term cap, the table
+ * ring and every refusal are he355_combine_scalars', under this call's name; with both halves equal it gives that call's bits.  One
+ * streaming launch of k_scalar_combine_cplx (he355_poly_stats: complex_combinations). */
+int he355_combine_scalars_complex(he355_ctx *ctx, int L, int size, uint64_t n, const he355_term *h_terms, uint64_t n_terms,
+                                  const uint64_t *h_scalars /* [n_terms][2][L] canonical residues */, const uint64_t *h_const /* [2][L] or NULL */,
+                                  uint64_t *d_out /* [n][size][L][N] */);
+/* he355_ckks_eval_poly with complex coefficients c_k = h_re[k] + i * h_im[k] (both lists n_coeffs long).  The tree, the depth, the power
+ * set, the levels and the products are he355_ckks_eval_poly's; a coefficient is zero when both of its parts are.  Every scalar
+ * (c_k * T) / s_k becomes the pair ((re_k * T) / s_k, (im_k * T) / s_k) given to he355_ckks_complex_scalar_residues, every constant c * T
+ * or c * S a pair in the same way; every leaf and every constant combination is ONE he355_combine_scalars_complex.  The plan's
+ * `combinations` counts those launches (he355_poly_stats: complex_combinations grows by them, combinations by none); min_scalar_bits is
+ * the least over the non-zero integers A and B.  With h_im all zero the output equals he355_ckks_eval_poly's bit for bit.  The input slots
+ * may themselves be complex.  Refusals: he355_ckks_eval_poly's under this call's name, and a null h_im. */
+int he355_ckks_eval_poly_complex_plan(const he355_ctx *ctx, int L, const double *h_re, const double *h_im, uint64_t n_coeffs, int log_baby, double in_scale,
+                                      double out_scale, uint64_t n, he355_poly_plan_t *out);
+int he355_ckks_eval_poly_complex(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in /* [n][2][L][N] */, const double *h_re, const double *h_im,
+                                 uint64_t n_coeffs, int log_baby, double in_scale, double out_scale, uint64_t *d_out /* [n][2][L - depth][N] */);
 /* ---- the modulus raise (CKKS): from q_0 alone back up the chain, on a fused lift-and-transform kernel ----
  * Every other level operation goes down (he355_rescale, he355_mod_switch_drop); this one takes a ciphertext whose chain is used up back to
  * L_to primes, the first step of a bootstrapping circuit.  The definition (tests/ckks_mod_raise_ref.py restates it on the oracle), for every

@@ -49,7 +49,7 @@ class HoistStats(C.Structure):
 
 
 class PolyStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("combinations", "products", "rescales", "drops", "adds", "chunks", "calls")] + [("reserved", C.c_uint64)]
+    _fields_ = [(k, C.c_uint64) for k in ("combinations", "products", "rescales", "drops", "adds", "chunks", "calls", "complex_combinations")]
 
 
 class RaiseStats(C.Structure):
@@ -209,6 +209,14 @@ def lib():
             "he355_ckks_eval_poly_plan": (i32, [vp, i32, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, u64, C.POINTER(PolyPlan)]),
             "he355_ckks_eval_poly": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, vp]),
             "he355_poly_stats": (i32, [vp, C.POINTER(PolyStats), i32]),
+            "he355_ckks_encode_complex": (i32, [vp, u64, vp, u64, C.c_double, vp]),
+            "he355_ckks_decode_complex": (i32, [vp, i32, u64, vp, C.c_double, vp]),
+            "he355_ckks_decode_complex_slots": (i32, [vp, i32, u64, vp, C.c_double, _u64p, u64, vp]),
+            "he355_ckks_complex_unit": (i32, [vp, i32, C.POINTER(C.c_uint64)]),
+            "he355_ckks_complex_scalar_residues": (i32, [vp, i32, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+            "he355_combine_scalars_complex": (i32, [vp, i32, i32, u64, C.POINTER(Term), u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "he355_ckks_eval_poly_complex_plan": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, u64, C.POINTER(PolyPlan)]),
+            "he355_ckks_eval_poly_complex": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, vp]),
             "he355_ckks_mod_raise": (i32, [vp, i32, i32, i32, u64, vp, vp]),
             "he355_ckks_lift_centred": (i32, [vp, i32, u64, vp, vp]),
             "he355_raise_stats": (i32, [vp, C.POINTER(RaiseStats), i32]),
@@ -249,7 +257,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_ckks_mod_raise", "he355_ckks_lift_centred", "he355_raise_stats", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_ckks_encode_complex", "he355_ckks_decode_complex", "he355_ckks_decode_complex_slots", "he355_ckks_complex_unit", "he355_ckks_complex_scalar_residues", "he355_combine_scalars_complex", "he355_ckks_eval_poly_complex_plan", "he355_ckks_eval_poly_complex", "he355_ckks_mod_raise", "he355_ckks_lift_centred", "he355_raise_stats", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -813,6 +821,61 @@ class Context:
         st = PolyStats()
         _check(lib().he355_poly_stats(self.h, C.byref(st), int(reset)))
         return {k: int(getattr(st, k)) for k, _ in PolyStats._fields_ if k != "reserved"}
+
+    # ---- complex slots ----
+    def ckks_encode_complex(self, n, values, count, scale, plain):
+        """values [n][count][2] doubles (re, im) -> plain [n][L_top][N]; the conjugate slots hold conj(v)"""
+        _check(lib().he355_ckks_encode_complex(self.h, n, values.ptr, count, scale, plain.ptr))
+
+    def ckks_decode_complex(self, L, n, plain, scale, out):
+        """out [n][N/2][2]: (re, im) of every slot"""
+        _check(lib().he355_ckks_decode_complex(self.h, L, n, plain.ptr, scale, out.ptr))
+
+    def ckks_decode_complex_slots(self, L, n, plain, scale, ranges, out):
+        """only the slots of `ranges` = [(first, count), ...]: out is [n][sum of counts][2]"""
+        arr, k = self._ranges(ranges)
+        _check(lib().he355_ckks_decode_complex_slots(self.h, L, n, plain.ptr, scale, arr, k, out.ptr))
+
+    def ckks_complex_unit(self, L) -> list:
+        """u_i = NTT_{q_i}(X^(N/4) + X^(3N/4))[0] for the first L primes: u_i^2 = -2 (mod q_i)"""
+        out = (C.c_uint64 * max(1, L))()
+        _check(lib().he355_ckks_complex_unit(self.h, L, out))
+        return [int(x) for x in out[:L]]
+
+    def ckks_complex_scalar_residues(self, L, v_re, v_im) -> list:
+        """[[(A + B u_i) % q_i], [(A - B u_i) % q_i]] with A = round(v_re), B = round(v_im / sqrt(2))"""
+        out = (C.c_uint64 * max(1, 2 * L))()
+        _check(lib().he355_ckks_complex_scalar_residues(self.h, L, float(v_re), float(v_im), out))
+        return [[int(x) for x in out[:L]], [int(x) for x in out[L:2 * L]]]
+
+    def combine_scalars_complex(self, L, size, n, terms, scalars, out, const=None):
+        """combine_scalars with two residues per (term, prime): scalars[t] = [L residues where bit (log2 N - 2) of the NTT index is 0,
+        L residues where it is 1]; const: such a pair or None"""
+        tt = (Term * max(1, len(terms)))(*[Term(getattr(b.ptr, "value", b.ptr), int(lv), 0) for b, lv in terms])
+        flat = [int(v) for pair in scalars for row in pair for v in row]
+        sc = (C.c_uint64 * max(1, len(flat)))(*flat)
+        cc = (C.c_uint64 * (2 * L))(*[int(v) for row in const for v in row]) if const is not None else None
+        _check(lib().he355_combine_scalars_complex(self.h, L, size, n, tt, len(terms), sc, cc, out.ptr))
+
+    @staticmethod
+    def _parts(coeffs):
+        re = (C.c_double * max(1, len(coeffs)))(*[complex(c).real for c in coeffs])
+        im = (C.c_double * max(1, len(coeffs)))(*[complex(c).imag for c in coeffs])
+        return re, im
+
+    def ckks_eval_poly_complex_plan(self, L, coeffs, log_baby, in_scale, out_scale, n=1) -> dict:
+        """ckks_eval_poly_plan for complex coefficients (Python complex numbers)"""
+        re, im = self._parts(coeffs)
+        pl = PolyPlan()
+        _check(lib().he355_ckks_eval_poly_complex_plan(self.h, L, re, im, len(coeffs), log_baby, in_scale, out_scale, n, C.byref(pl)))
+        d = {k: getattr(pl, k) for k, _ in PolyPlan._fields_ if k not in ("reserved", "power_mask")}
+        d["powers_computed"] = [k for k in range(1024) if (pl.power_mask[k // 64] >> (k % 64)) & 1]
+        return d
+
+    def ckks_eval_poly_complex(self, L, n, inp, coeffs, log_baby, in_scale, out_scale, out):
+        """ckks_eval_poly for complex coefficients (Python complex numbers): every leaf is one combine_scalars_complex"""
+        re, im = self._parts(coeffs)
+        _check(lib().he355_ckks_eval_poly_complex(self.h, L, n, inp.ptr, re, im, len(coeffs), log_baby, in_scale, out_scale, out.ptr))
 
     def ckks_mod_raise(self, L_in, L_to, size, n, inp, out):
         """out [n][size][L_to][N] = the residue under q_0 of inp [n][size][L_in][N] (row 0 of every polynomial; the rest is ignored), read as

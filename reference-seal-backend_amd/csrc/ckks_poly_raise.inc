@@ -3,24 +3,85 @@
 
 // he355_combine_scalars: one launch of k_scalar_combine over `n` ciphertexts.  The table -- [n_terms] {slab, level} pairs, the scalars
 // [n_terms][L], the constant [L] -- takes one region of the table ring (table_ring): calls may follow each other without a sync.
+// halves = 2: he355_combine_scalars_complex -- scalars [n_terms][2][L], the constant [2][L], one launch of k_scalar_combine_cplx.
 struct PolyTerm { const u64 *p; int L; };
-static void combine_scalars(DeviceContext &d, int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out)
+static void combine_scalars(DeviceContext &d, int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out, int halves = 1)
 {
     d.use();
-    const size_t t_words = 2 * (size_t)n_terms, s_words = (size_t)n_terms * (size_t)L, words = t_words + s_words + (h_const ? (size_t)L : 0);
+    const size_t Lh = (size_t)L * (size_t)halves;
+    const size_t t_words = 2 * (size_t)n_terms, s_words = (size_t)n_terms * Lh, words = t_words + s_words + (h_const ? Lh : 0);
     std::vector<u64> h(words);
     for (size_t t = 0; t < n_terms; ++t) {
         h[2 * t] = (u64)(uintptr_t)terms[t].p;
         h[2 * t + 1] = (u64)terms[t].L; // (the kernel's row of the term: (c * size + k) * L_t + i)
     }
     std::memcpy(h.data() + t_words, h_scalars, s_words * 8);
-    if (h_const) std::memcpy(h.data() + t_words + s_words, h_const, (size_t)L * 8);
+    if (h_const) std::memcpy(h.data() + t_words + s_words, h_const, Lh * 8);
     const size_t bytes = (words * 8 + 255) & ~(size_t)255;
     u64 *d_tab = reinterpret_cast<u64 *>(d.table_ring(bytes));
     HIPCHECK(hipMemcpy(d_tab, h.data(), words * 8, hipMemcpyHostToDevice));
-    ++d.counters().poly.combinations;
-    launch_scalar_combine(d.batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+    if (halves == 2) {
+        ++d.counters().poly.complex_combinations;
+        launch_scalar_combine_cplx(d.batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+    } else {
+        ++d.counters().poly.combinations;
+        launch_scalar_combine(d.batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+    }
     HIPCHECK(hipGetLastError());
+}
+
+// The walk of a polynomial plan (poly_args.h), chunk by chunk in the key-switch chunk: he355_ckks_eval_poly and he355_ckks_eval_poly_complex.
+// The power store and the temporaries are ONE pool block sized for the chunk, taken after the key check and before the first launch; every
+// step is queued on the one stream.
+static void run_poly_plan(he355_ctx *c, const PolyPlan &pl, const char *what, int L, u64 n, const u64 *in, u64 *out)
+{
+    DeviceContext &d = dev(c);
+    d.use();
+    const Params &P = d.params();
+    d.require_keyswitch();
+    if (!d.relin_key()) throw std::invalid_argument(std::string(what) + ": relinearization key not present"); // before anything is allocated
+    const size_t chunk = d.chunk_ops(n, L, false);
+    const PoolBlock blk = d.scoped_block((size_t)pl.words_per_ct * chunk * 8);
+    const size_t N = P.N;
+    Indexer pw{};
+    pw.b1 = 1; pw.pairwise = 1;
+    ++d.counters().poly.calls;
+    for (u64 off = 0; off < n; off += chunk) {
+        const u64 nc = std::min<u64>(chunk, n - off);
+        ++d.counters().poly.chunks;
+        auto at = [&](int b) -> u64 * {
+            const PolyBuf &B = pl.bufs[(size_t)b];
+            if (B.kind == 0) return const_cast<u64 *>(in) + off * 2 * (size_t)B.L * N;
+            if (B.kind == 1) return out + off * 2 * (size_t)B.L * N;
+            return blk.get() + B.off * nc;
+        };
+        for (const PolyStep &s : pl.steps) {
+            switch (s.op) {
+            case kPolyMulRelin:
+                ++d.counters().poly.products;
+                d.multiply_relin(s.L, nc, at(s.a), at(s.b), pw, true, at(s.dst));
+                break;
+            case kPolyDrop:
+                ++d.counters().poly.drops;
+                d.mod_switch_drop(pl.bufs[(size_t)s.a].L, s.L, nc * 2, at(s.a), at(s.dst));
+                break;
+            case kPolyRescale:
+                ++d.counters().poly.rescales;
+                d.rescale(s.L, 2, nc, at(s.a), at(s.dst));
+                break;
+            case kPolyAdd:
+                ++d.counters().poly.adds;
+                d.addsub(s.L, 2, nc, at(s.a), at(s.b), pw, at(s.dst), false);
+                break;
+            case kPolyCombine: {
+                std::vector<PolyTerm> t;
+                for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
+                combine_scalars(d, s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst), s.cplx ? 2 : 1);
+                break;
+            }
+            }
+        }
+    }
 }
 
 extern "C" {
@@ -56,8 +117,7 @@ int he355_ckks_eval_poly_plan(const he355_ctx *c, int L, const double *coeffs, u
         out->pool_bytes = !n ? 0 : bound > ~(u64)0 ? ~(u64)0 : (u64)bound;
     });
 }
-// he355_ckks_eval_poly: the plan's steps (poly_args.h), chunk by chunk in the key-switch chunk.  The power store and the temporaries are
-// ONE pool block sized for the chunk, taken after the key check and before the first launch; every step is queued on the one stream.
+// he355_ckks_eval_poly: the plan's steps (poly_args.h), walked by run_poly_plan
 int he355_ckks_eval_poly(he355_ctx *c, int L, uint64_t n, const uint64_t *in, const double *coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
                          uint64_t *out)
 {
@@ -65,53 +125,7 @@ int he355_ckks_eval_poly(he355_ctx *c, int L, uint64_t n, const uint64_t *in, co
         if (!c) throw std::invalid_argument("null context");
         const PolyPlan pl = plan_eval_poly(*c->params, "he355_ckks_eval_poly", L, n, in, coeffs, n_coeffs, log_baby, in_scale, out_scale, out, true, 1024);
         if (pl.empty) return; // nothing to evaluate: no buffer is touched, no device asked for
-        DeviceContext &d = dev(c);
-        d.use();
-        const Params &P = d.params();
-        d.require_keyswitch();
-        if (!d.relin_key()) throw std::invalid_argument("he355_ckks_eval_poly: relinearization key not present"); // before anything is allocated
-        const size_t chunk = d.chunk_ops(n, L, false);
-        const PoolBlock blk = d.scoped_block((size_t)pl.words_per_ct * chunk * 8);
-        const size_t N = P.N;
-        Indexer pw{};
-        pw.b1 = 1; pw.pairwise = 1;
-        ++d.counters().poly.calls;
-        for (u64 off = 0; off < n; off += chunk) {
-            const u64 nc = std::min<u64>(chunk, n - off);
-            ++d.counters().poly.chunks;
-            auto at = [&](int b) -> u64 * {
-                const PolyBuf &B = pl.bufs[(size_t)b];
-                if (B.kind == 0) return const_cast<u64 *>(in) + off * 2 * (size_t)B.L * N;
-                if (B.kind == 1) return out + off * 2 * (size_t)B.L * N;
-                return blk.get() + B.off * nc;
-            };
-            for (const PolyStep &s : pl.steps) {
-                switch (s.op) {
-                case kPolyMulRelin:
-                    ++d.counters().poly.products;
-                    d.multiply_relin(s.L, nc, at(s.a), at(s.b), pw, true, at(s.dst));
-                    break;
-                case kPolyDrop:
-                    ++d.counters().poly.drops;
-                    d.mod_switch_drop(pl.bufs[(size_t)s.a].L, s.L, nc * 2, at(s.a), at(s.dst));
-                    break;
-                case kPolyRescale:
-                    ++d.counters().poly.rescales;
-                    d.rescale(s.L, 2, nc, at(s.a), at(s.dst));
-                    break;
-                case kPolyAdd:
-                    ++d.counters().poly.adds;
-                    d.addsub(s.L, 2, nc, at(s.a), at(s.b), pw, at(s.dst), false);
-                    break;
-                case kPolyCombine: {
-                    std::vector<PolyTerm> t;
-                    for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
-                    combine_scalars(d, s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst));
-                    break;
-                }
-                }
-            }
-        }
+        run_poly_plan(c, pl, "he355_ckks_eval_poly", L, n, in, out);
     });
 }
 int he355_poly_stats(he355_ctx *c, he355_poly_stats_t *out, int reset)

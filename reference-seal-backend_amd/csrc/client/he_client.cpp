@@ -287,6 +287,24 @@ std::vector<u64> Client::ckks_encode(const double *values, size_t count, double 
         z[bitrev_u32(slot_index_[i], P.logn)].re = values[i];
         z[bitrev_u32(slot_index_[half + i], P.logn)].re = values[i]; // conjugate of a real value
     }
+    return ckks_encode_placed(z, scale);
+}
+std::vector<u64> Client::ckks_encode_complex(const double *values, size_t count, double scale) const
+{
+    const size_t N = P.N, half = N / 2;
+    if (count > half) throw std::invalid_argument("Not enough slots available to create packed plaintext");
+    std::vector<Cplx> z(N, Cplx{0.0, 0.0});
+    for (size_t i = 0; i < count; ++i) {
+        const Cplx v{values[2 * i], values[2 * i + 1]};
+        z[bitrev_u32(slot_index_[i], P.logn)] = v;
+        z[bitrev_u32(slot_index_[half + i], P.logn)] = cconj(v);
+    }
+    return ckks_encode_placed(z, scale);
+}
+// the encoder behind the placement: transform, twist, scale, round, residues, forward NTT
+std::vector<u64> Client::ckks_encode_placed(std::vector<Cplx> &z, double scale) const
+{
+    const size_t N = P.N;
     fft_stages(z, fft_w_, false);
     std::vector<u64> out(P.Ltop * N);
     for (size_t n = 0; n < N; ++n) {
@@ -304,7 +322,21 @@ std::vector<u64> Client::ckks_encode(const double *values, size_t count, double 
 
 void Client::ckks_decode(const u64 *plain_ntt, size_t L, double scale, double *out) const
 {
-    const size_t N = P.N, half = N / 2;
+    const std::vector<Cplx> z = ckks_decode_transform(plain_ntt, L, scale);
+    for (size_t i = 0; i < P.N / 2; ++i) out[i] = z[slot_index_[i]].re;
+}
+void Client::ckks_decode_complex(const u64 *plain_ntt, size_t L, double scale, double *out) const
+{
+    const std::vector<Cplx> z = ckks_decode_transform(plain_ntt, L, scale);
+    for (size_t i = 0; i < P.N / 2; ++i) {
+        out[2 * i] = z[slot_index_[i]].re;
+        out[2 * i + 1] = z[slot_index_[i]].im;
+    }
+}
+// the decoder up to the slots: inverse NTT, CRT composition, centring, twist, transform
+std::vector<Cplx> Client::ckks_decode_transform(const u64 *plain_ntt, size_t L, double scale) const
+{
+    const size_t N = P.N;
     std::vector<u64> coeff(plain_ntt, plain_ntt + L * N);
     for (size_t i = 0; i < L; ++i) host_ntt_inverse(P.primes[i], N, coeff.data() + i * N);
     const Crt crt(P, L);
@@ -323,7 +355,7 @@ void Client::ckks_decode(const u64 *plain_ntt, size_t L, double scale, double *o
         z[bitrev_u32((u32)n, P.logn)] = ckks_decode_coeff(v, zeta_[n], scale);
     }
     fft_stages(z, fft_w_, true); // unnormalised inverse transform = evaluation at the slots' points
-    for (size_t i = 0; i < half; ++i) out[i] = z[slot_index_[i]].re;
+    return z;
 }
 
 std::vector<u64> Client::bfv_encode(const int64_t *values, size_t count) const

@@ -47,6 +47,10 @@ public:
     std::vector<u64> ckks_encode(const double *values, size_t count, double scale) const;
     // CKKSEncoder::decode: [L][N] NTT-form plaintext -> N/2 real parts
     void ckks_decode(const u64 *plain_ntt, size_t L, double scale, double *out) const;
+    // the same with complex slots: values [count][2] (re, im), the conjugate slots hold conj(v); out [N/2][2].  The re parts of the
+    // decode are ckks_decode's bits; values with im = +0.0 encode to ckks_encode's bits.
+    std::vector<u64> ckks_encode_complex(const double *values, size_t count, double scale) const;
+    void ckks_decode_complex(const u64 *plain_ntt, size_t L, double scale, double *out) const;
     // BatchEncoder::encode / decode: N int64 slots <-> [N] coefficients mod t
     std::vector<u64> bfv_encode(const int64_t *values, size_t count) const;
     void bfv_decode(const u64 *plain, int64_t *out) const;
@@ -75,6 +79,8 @@ private:
     void sample_uniform(std::vector<u64> &out, size_t nmod);
     void enc_zero_symmetric(u64 *out /*[2][K][N]*/, u64 key_id, u64 digit);
     std::vector<u64> make_kswitch_key(const std::vector<u64> &new_key, u64 key_id);
+    std::vector<u64> ckks_encode_placed(std::vector<Cplx> &z, double scale) const;
+    std::vector<Cplx> ckks_decode_transform(const u64 *plain_ntt, size_t L, double scale) const;
     void divide_round_last(const std::vector<u64> &in, size_t size, std::vector<u64> &out) const; // key level -> data level
 
     const Params &P;

@@ -1618,7 +1618,8 @@ public:
         return enc_;
     }
     // CKKSEncoder::encode: values [n][count] (count <= N/2) at `scale` -> [n][Ltop][N] NTT-form plaintexts
-    void ckks_encode(u64 n, const double *values, u64 count, double scale, u64 *plain)
+    // (cplx: values [n][count][2], re then im -- he355_ckks_encode_complex, its arguments checked by cplx_args.h)
+    void ckks_encode(u64 n, const double *values, u64 count, double scale, u64 *plain, bool cplx = false)
     {
         use();
         if (P.scheme != kSchemeCKKS) throw std::invalid_argument("he355_ckks_encode needs a CKKS context");
@@ -1630,7 +1631,8 @@ public:
         HIPCHECK(hipMemsetAsync(d_err_, 0, sizeof(int), stream_));
         for (u64 off = 0; off < n; off += cmax) {
             const u64 c = std::min<u64>(cmax, n - off);
-            launch_ckks_encode(env_, c, values + off * count, count, scale, zbuf, plain + off * L * N, T, d_err_);
+            if (cplx) launch_ckks_encode_cplx(env_, c, values + off * count * 2, count, scale, zbuf, plain + off * L * N, T, d_err_);
+            else launch_ckks_encode(env_, c, values + off * count, count, scale, zbuf, plain + off * L * N, T, d_err_);
             launch_ntt_forward(env_, poly_view(plain + off * L * N, (int)L, N, (int)L), (u32)c);
         }
         int err = 0;
@@ -1639,7 +1641,9 @@ public:
         if (err) throw std::invalid_argument("encoded values are too large");
     }
     // CKKSEncoder::decode: [n][L][N] NTT-form plaintexts -> [n][total] real slot values (ranges == null: all N/2)
-    void ckks_decode(int L, u64 n, const u64 *plain, double scale, double *out, const u64 *ranges = nullptr, u64 n_ranges = 0)
+    // (cplx: [n][total][2], re then im -- he355_ckks_decode_complex: the same two kernels asked for no slot, then the (re, im) pairs of the
+    // wanted slots gathered out of the transforms they leave in zbuf)
+    void ckks_decode(int L, u64 n, const u64 *plain, double scale, double *out, const u64 *ranges = nullptr, u64 n_ranges = 0, bool cplx = false)
     {
         use();
         check_level(L);
@@ -1655,7 +1659,12 @@ public:
             const u64 c = std::min<u64>(cmax, n - off);
             HIPCHECK(hipMemcpyAsync(coeff, plain + off * L * N, c * L * N * 8, hipMemcpyDeviceToDevice, stream_));
             launch_ntt_inverse(env_, poly_view(coeff, L, N, L), (u32)c);
-            launch_ckks_decode(env_, c, coeff, scale, zbuf, out + off * sr.total, T, crt, sr);
+            if (cplx) {
+                launch_ckks_decode(env_, c, coeff, scale, zbuf, out, T, crt, SlotRanges{});
+                launch_ckks_gather_cplx(env_, c, zbuf, out + off * sr.total * 2, T, sr);
+            } else {
+                launch_ckks_decode(env_, c, coeff, scale, zbuf, out + off * sr.total, T, crt, sr);
+            }
         }
         HIPCHECK(hipGetLastError());
     }
@@ -2308,5 +2317,6 @@ int he355_set_chunk(he355_ctx *c, uint64_t ops)
 // the call families: launch sequences and C ABI of each, one file per family
 #include "hoisted_rotations.inc"
 #include "ckks_poly_raise.inc"
+#include "ckks_complex.inc"
 #include "bfv_operands.inc"
 #include "bfv_pir.inc"

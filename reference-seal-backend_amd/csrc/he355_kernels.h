@@ -236,6 +236,9 @@ HE355_FWD(launch_hoist_rot_qp)
 HE355_FWD(launch_bsgs_ident)
 HE355_FWD(launch_bsgs_inner)
 HE355_FWD(launch_scalar_combine)
+HE355_FWD(launch_scalar_combine_cplx)
+HE355_FWD(launch_ckks_encode_cplx)
+HE355_FWD(launch_ckks_gather_cplx)
 HE355_FWD(launch_raise_lift)
 HE355_FWD(launch_raise_cols)
 HE355_FWD(launch_plain_extend)

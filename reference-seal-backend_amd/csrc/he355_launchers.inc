@@ -105,6 +105,14 @@ void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store,
 // he355_combine_scalars (he355_kernels_poly.hip): out [n][size][L][N] = sum_t scalars[t][i] * term_t + (polynomial 0: cst[i]); d_terms [n_terms]
 // device pairs of words {the term's slab [n][size][L_t][N], L_t >= L}, d_scalars [n_terms][L], d_const [L] or null -- all canonical
 void launch_scalar_combine(const KernelEnv &env, int L, int size, u64 n, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *out);
+// ---- complex CKKS slots (he355_kernels_cplx.hip; arithmetic: cplx_core.h) --------------------------------------------------------------------
+// he355_combine_scalars_complex: launch_scalar_combine with d_scalars [n_terms][2][L] and d_const [2][L] or null, the half picked by bit
+// (log2 N - 2) of the NTT index
+void launch_scalar_combine_cplx(const KernelEnv &env, int L, int size, u64 n, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *out);
+// values [n][count][2] (re, im) -> plain [n][Ltop][N] coefficient form, as launch_ckks_encode
+void launch_ckks_encode_cplx(const KernelEnv &env, u64 n_vec, const double *values, u64 count, double scale, void *zbuf, u64 *plain, const EncTablesDev &t, int *err);
+// zbuf [n][N] as launch_ckks_decode leaves it (the finished transforms) -> out [n][sr.total][2]: (re, im) of the slots of sr's ranges
+void launch_ckks_gather_cplx(const KernelEnv &env, u64 n_vec, const void *zbuf, double *out, const EncTablesDev &t, const SlotRanges &sr);
 // ---- the CKKS modulus raise (he355_kernels_raise.hip; arithmetic: raise_core.h) ------------------------------------------------------------
 // coeff [n_polys][N], coefficients canonical under q_0 -> rows first .. L_to - 1 of out [n_polys][L_to][N]: the centred coefficient mod q_j,
 // canonical, coefficient form (first = 0: he355_ckks_lift_centred; first = 1: row 0 is the caller's).  One streaming launch.

@@ -4,6 +4,8 @@
 // then only walks the plan's steps.  Whether the relinearization key is installed is the device context's to know.
 // Host-only on purpose: no HIP header, so tests/ckks_eval_poly_args_main.cpp runs every check at its edges under the sanitizers.
 // The definition the plan implements is written out in include/he355.h; tests/ckks_eval_poly_ref.py restates it on the oracle.
+// he355_combine_scalars_complex and he355_ckks_eval_poly_complex (ckks_complex.inc) take the same checks and the same planner under their
+// own names: two residues per scalar (halves = 2), a coefficient a (re, im) pair (cplx) -- tests/ckks_complex_args_main.cpp.
 #pragma once
 #include <cmath>
 #include <map>
@@ -13,6 +15,7 @@
 
 #include "../../include/he355.h"
 #include "bfv_pir_args.h"
+#include "cplx_args.h"
 #include "poly_core.h"
 
 namespace he355 {
@@ -29,22 +32,24 @@ inline void poly_scalar_residues(const Params &p, const std::string &w, int L, d
 }
 
 // ---- he355_combine_scalars -----------------------------------------------------------------------------------------------------------
-// True: n == 0, or no term and no constant -- the call touches nothing.
-inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const he355_term *terms, u64 n_terms, const u64 *scalars, const u64 *cst, const u64 *out)
+// True: n == 0, or no term and no constant -- the call touches nothing.  halves = 2: he355_combine_scalars_complex under its own name --
+// scalars [n_terms][2][L], cst [2][L], every other rule the same.
+inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const he355_term *terms, u64 n_terms, const u64 *scalars, const u64 *cst, const u64 *out,
+                                 int halves = 1)
 {
-    const std::string w("he355_combine_scalars");
+    const std::string w(halves == 2 ? "he355_combine_scalars_complex" : "he355_combine_scalars");
     check_level(p, w, L);
     if (size < 2 || size > 3) throw std::invalid_argument(w + ": ciphertext size must be 2 or 3");
     if (n_terms > ((u64)1 << 20)) throw std::invalid_argument(w + ": too many terms for one call (at most 2^20)");
     if (n_terms && (!terms || !scalars)) throw std::invalid_argument(w + ": null terms or scalars");
     for (u64 t = 0; t < n_terms; ++t) {
         if (terms[t].L < L || (size_t)terms[t].L > p.Ltop) throw std::invalid_argument(w + ": term " + std::to_string(t) + " lies at a level below the call's or above the top");
-        for (int i = 0; i < L; ++i)
-            if (scalars[t * (u64)L + (u64)i] >= p.primes[i].q) throw std::invalid_argument(w + ": a scalar of term " + std::to_string(t) + " is not a canonical residue");
+        for (int i = 0; i < halves * L; ++i)
+            if (scalars[t * (u64)(halves * L) + (u64)i] >= p.primes[i % L].q) throw std::invalid_argument(w + ": a scalar of term " + std::to_string(t) + " is not a canonical residue");
     }
     if (cst)
-        for (int i = 0; i < L; ++i)
-            if (cst[i] >= p.primes[i].q) throw std::invalid_argument(w + ": the constant is not a canonical residue");
+        for (int i = 0; i < halves * L; ++i)
+            if (cst[i] >= p.primes[i % L].q) throw std::invalid_argument(w + ": the constant is not a canonical residue");
     // every slab in words, formed in 128 bits: 2^60 words (2^63 bytes) is the most one may span
     const u128 cap = (u128)1 << 60, out_w = (u128)n * (u128)size * (u128)L * p.N;
     if (n > cap || out_w > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
@@ -74,6 +79,7 @@ struct PolyStep {
     std::vector<int> terms;    // kPolyCombine: the term buffers ...
     std::vector<u64> scalars;  // ... [terms][L] residues ...
     std::vector<u64> cst;      // ... and the constant [L], empty: none
+    bool cplx = false;         // he355_ckks_eval_poly_complex: scalars [terms][2][L], cst [2][L] (k_scalar_combine_cplx)
 };
 struct PolyPlan {
     he355_poly_plan_t info{};
@@ -92,16 +98,27 @@ inline int poly_clog2(u64 k) // ceil(log2 k), k >= 1
 
 class PolyPlanner {
 public:
-    PolyPlanner(const Params &p, const std::string &w, int L, int log_baby, double in_scale) : P(p), w_(w), L_(L), m_((u64)1 << log_baby)
+    PolyPlanner(const Params &p, const std::string &w, int L, int log_baby, double in_scale, bool cplx = false) : P(p), w_(w), L_(L), m_((u64)1 << log_baby), cplx_(cplx)
     {
         level_[1] = L;
         scale_[1] = in_scale;
     }
-    typedef std::vector<double> Poly; // trimmed: the last coefficient is not zero (or the vector is empty)
-    static Poly trimmed(const double *c, u64 n)
+    // A coefficient: the real call's has im = 0.  Zero when both parts are.
+    struct Coef {
+        double re, im;
+        bool zero() const { return re == 0.0 && im == 0.0; }
+    };
+    typedef std::vector<Coef> Poly; // trimmed: the last coefficient is not zero (or the vector is empty)
+    static Poly trimmed(const Coef *c, u64 n)
     {
-        while (n && c[n - 1] == 0.0) --n;
+        while (n && c[n - 1].zero()) --n;
         return Poly(c, c + n);
+    }
+    static Poly trimmed(const double *re, const double *im, u64 n)
+    {
+        Poly p((size_t)n);
+        for (u64 k = 0; k < n; ++k) p[(size_t)k] = {re[k], im ? im[k] : 0.0};
+        return trimmed(p.data(), n);
     }
     u64 giant_below(u64 deg) const // the largest m 2^j <= deg (deg >= m)
     {
@@ -115,7 +132,7 @@ public:
         if (deg < m_) {
             int d = 0;
             for (u64 k = 1; k <= deg; ++k)
-                if (p[k] != 0.0) d = std::max(d, poly_clog2(k));
+                if (!p[k].zero()) d = std::max(d, poly_clog2(k));
             return 1 + d;
         }
         const u64 e = giant_below(deg);
@@ -128,7 +145,7 @@ public:
         const u64 deg = p.size() - 1;
         if (deg < m_) {
             for (u64 k = 1; k <= deg; ++k)
-                if (p[k] != 0.0) need_[k] = true;
+                if (!p[k].zero()) need_[k] = true;
             return;
         }
         const u64 e = giant_below(deg);
@@ -165,17 +182,17 @@ public:
         const u64 deg = p.size() - 1;
         const double T = S * (double)P.primes[Lt].q;
         if (deg < m_) {
-            std::vector<std::pair<u64, double>> t;
+            std::vector<LeafTerm> t;
             for (u64 k = 1; k <= deg; ++k)
-                if (p[k] != 0.0) t.push_back({k, (p[k] * T) / scale_[k]});
-            return leaf(pl, t, p[0] != 0.0, p[0] * T, Lt, dst);
+                if (!p[k].zero()) t.push_back({k, (p[k].re * T) / scale_[k], (p[k].im * T) / scale_[k]});
+            return leaf(pl, t, !p[0].zero(), p[0].re * T, p[0].im * T, Lt, dst);
         }
         const u64 e = giant_below(deg);
         const Poly hi(p.begin() + e, p.end()), lo = trimmed(p.data(), e);
         const bool sum = !lo.empty();
         int prod;
         if (hi.size() == 1) {
-            prod = leaf(pl, {{e, (hi[0] * T) / scale_[e]}}, false, 0.0, Lt, sum ? -1 : dst);
+            prod = leaf(pl, {{e, (hi[0].re * T) / scale_[e], (hi[0].im * T) / scale_[e]}}, false, 0.0, 0.0, Lt, sum ? -1 : dst);
         } else {
             const int H = eval(pl, hi, Lt + 1, T / scale_[e], -1);
             if (level_[e] < Lt + 1) throw std::invalid_argument(w_ + ": a split's power lies below its product's level");
@@ -190,9 +207,9 @@ public:
         if (lo.size() == 1) { // a constant: prod * 1 + c_0 S, one combination at the result's level
             PolyStep s{kPolyCombine, Lt};
             s.terms = {prod};
-            s.scalars.assign((size_t)Lt, 1);
-            s.cst.resize((size_t)Lt);
-            poly_scalar_residues(P, w_, Lt, lo[0] * S, s.cst.data());
+            s.cplx = cplx_;
+            s.scalars.assign((size_t)Lt * (cplx_ ? 2 : 1), 1);
+            residues(Lt, lo[0].re * S, lo[0].im * S, s.cst);
             s.dst = out;
             push(pl, std::move(s));
             return out;
@@ -226,29 +243,42 @@ private:
         push(pl, std::move(s));
         return drops_[key] = b;
     }
-    // one combination at level Lt + 1 over powers (exponent, scalar as a double), then the rescale to Lt
-    int leaf(PolyPlan &pl, const std::vector<std::pair<u64, double>> &t, bool has_const, double cst, int Lt, int dst)
+    struct LeafTerm { u64 k; double re, im; }; // (exponent, scalar as doubles; im is read by the complex call alone)
+    // the residues of one scalar appended to `to`: [L], or the pair [2][L] of he355_ckks_complex_scalar_residues; mags: |A| (and |B|)
+    void residues(int L, double re, double im, std::vector<u64> &to, u128 *mags = nullptr)
+    {
+        const size_t at = to.size();
+        to.resize(at + (size_t)L * (cplx_ ? 2 : 1));
+        if (cplx_) {
+            cplx_scalar_residues(P, w_, L, re, im, to.data() + at, mags);
+            return;
+        }
+        poly_scalar_residues(P, w_, L, re, to.data() + at);
+        if (mags) {
+            bool neg;
+            poly_scalar_integer(re, mags[0], neg);
+            mags[1] = 0;
+        }
+    }
+    // one combination at level Lt + 1 over powers, then the rescale to Lt
+    int leaf(PolyPlan &pl, const std::vector<LeafTerm> &t, bool has_const, double cst_re, double cst_im, int Lt, int dst)
     {
         const int Lc = Lt + 1;
         PolyStep s{kPolyCombine, Lc};
-        s.scalars.resize(t.size() * (size_t)Lc);
+        s.cplx = cplx_;
         for (size_t j = 0; j < t.size(); ++j) {
-            if (level_[t[j].first] < Lc) throw std::invalid_argument(w_ + ": a leaf's power lies below the leaf's level");
-            s.terms.push_back(buf_[t[j].first]);
-            poly_scalar_residues(P, w_, Lc, t[j].second, s.scalars.data() + j * (size_t)Lc);
-            u128 mag;
-            bool neg;
-            poly_scalar_integer(t[j].second, mag, neg);
-            if (mag) {
-                int bits = 0;
-                while (mag >> (bits + 1)) ++bits;
-                if (pl.info.min_scalar_bits < 0 || bits < pl.info.min_scalar_bits) pl.info.min_scalar_bits = bits;
-            }
+            if (level_[t[j].k] < Lc) throw std::invalid_argument(w_ + ": a leaf's power lies below the leaf's level");
+            s.terms.push_back(buf_[t[j].k]);
+            u128 mags[2];
+            residues(Lc, t[j].re, t[j].im, s.scalars, mags);
+            for (u128 mag : mags)
+                if (mag) {
+                    int bits = 0;
+                    while (mag >> (bits + 1)) ++bits;
+                    if (pl.info.min_scalar_bits < 0 || bits < pl.info.min_scalar_bits) pl.info.min_scalar_bits = bits;
+                }
         }
-        if (has_const) {
-            s.cst.resize((size_t)Lc);
-            poly_scalar_residues(P, w_, Lc, cst, s.cst.data());
-        }
+        if (has_const) residues(Lc, cst_re, cst_im, s.cst);
         const int tmp = add_buf(pl, 2, Lc);
         s.dst = tmp;
         push(pl, std::move(s));
@@ -273,6 +303,7 @@ private:
     const std::string w_;
     const int L_;
     const u64 m_;
+    const bool cplx_;
     bool need_[1024] = {};
     int level_[1024] = {}, buf_[1024] = {};
     double scale_[1024] = {};
@@ -282,22 +313,23 @@ private:
 
 // `chunk`: the context's batch chunk (info.chunks, and the caller's bound of the pool bytes); in / out may be null for a plan alone
 // (check_ptrs false: he355_ckks_eval_poly_plan)
+// im_coeffs: the imaginary parts of he355_ckks_eval_poly_complex (cplx true; both lists are needed), null for the real call
 inline PolyPlan plan_eval_poly(const Params &p, const char *what, int L, u64 n, const u64 *in, const double *coeffs, u64 n_coeffs, int log_baby, double in_scale,
-                               double out_scale, const u64 *out, bool check_ptrs, u64 chunk)
+                               double out_scale, const u64 *out, bool check_ptrs, u64 chunk, const double *im_coeffs = nullptr, bool cplx = false)
 {
     const std::string w(what);
     if (p.scheme != kSchemeCKKS) throw std::invalid_argument(w + ": polynomial evaluation is a CKKS operation");
     check_level(p, w, L);
     if (p.K < 2) throw std::invalid_argument(w + ": encryption parameters do not support key switching");
     if (n_coeffs > 1024) throw std::invalid_argument(w + ": too many coefficients (at most 1024)");
-    if (n_coeffs && !coeffs) throw std::invalid_argument(w + ": null coefficients");
+    if (n_coeffs && (!coeffs || (cplx && !im_coeffs))) throw std::invalid_argument(w + ": null coefficients");
     if (log_baby < 1 || log_baby > 6) throw std::invalid_argument(w + ": log_baby must be 1..6");
     for (u64 k = 0; k < n_coeffs; ++k)
-        if (!std::isfinite(coeffs[k])) throw std::invalid_argument(w + ": coefficient " + std::to_string(k) + " is not finite");
+        if (!std::isfinite(coeffs[k]) || (cplx && !std::isfinite(im_coeffs[k]))) throw std::invalid_argument(w + ": coefficient " + std::to_string(k) + " is not finite");
     if (!std::isfinite(in_scale) || !std::isfinite(out_scale) || in_scale <= 0 || out_scale <= 0) throw std::invalid_argument(w + ": a scale must be finite and positive");
-    const PolyPlanner::Poly poly = PolyPlanner::trimmed(coeffs, n_coeffs);
+    const PolyPlanner::Poly poly = PolyPlanner::trimmed(coeffs, cplx ? im_coeffs : nullptr, n_coeffs);
     if (poly.size() < 2) throw std::invalid_argument(w + ": no non-zero coefficient above c_0 (nothing to evaluate on a ciphertext)");
-    PolyPlanner pp(p, w, L, log_baby, in_scale);
+    PolyPlanner pp(p, w, L, log_baby, in_scale, cplx);
     PolyPlan pl;
     pl.info.depth = pp.depth(poly);
     pl.info.degree = (int32_t)poly.size() - 1;

@@ -175,6 +175,7 @@ def run(name, n=64):
     g.close()
 
 
-for name in SHAPES:
-    if which in ("all", name):
-        run(name)
+if __name__ == "__main__":
+    for name in SHAPES:
+        if which in ("all", name):
+            run(name)
