@@ -882,6 +882,78 @@ typedef struct he355_raise_stats {
     uint64_t reserved[3];
 } he355_raise_stats_t;           /* 64 bytes */
 int he355_raise_stats(he355_ctx *ctx, he355_raise_stats_t *out, int reset);
+/* ---- EvalMod (CKKS): Chebyshev-basis evaluation on a fused combine-and-rescale step ----
+ * he355_combine_scalars_rescale equals, bit for bit, he355_combine_scalars into a temporary [n][size][L][N] followed by he355_rescale:
+ *   d_out [n][size][L - 1][N] = rescale(sum_t a_t * ct_t + a_const)
+ * without the temporary.  Per chunk (the key-switch chunk, he355_set_chunk): row L - 1 of the combination alone into a compact pool block
+ * (k_scalar_combine_row), its inverse row pass and the floor step's column half exactly as he355_rescale runs them (with its latency split;
+ * he355_set_latency_max(0) switches that off), then ONE row kernel (k_floor_rows_combine) that forms the sums of rows 0 .. L - 2 from the
+ * term rows themselves -- each term read with its own [L_t][N] stride, integer sums under every prime -- and finishes the floor step on
+ * them.  There is no ring-in-LDS form and no dual-engine launch; the bits are he355_rescale's in whichever form that call takes.
+ * Refused on the host before any device work (the message names this call): everything he355_combine_scalars refuses, L < 2, a BFV context,
+ * d_out [n][size][L - 1][N] overlapping any word of any term.  n == 0, or n_terms == 0 without a constant, touches nothing. */
+int he355_combine_scalars_rescale(he355_ctx *ctx, int L, int size, uint64_t n, const he355_term *h_terms, uint64_t n_terms,
+                                  const uint64_t *h_scalars /* [n_terms][L] canonical residues */, const uint64_t *h_const /* [L] or NULL */,
+                                  uint64_t *d_out /* [n][size][L - 1][N] */);
+/* he355_ckks_eval_chebyshev: out = p(u), p(u) = sum_k c_k T_k(u) (Chebyshev polynomials of the first kind, real coefficients, trailing zeros
+ * trimmed), u the input at in_scale, assumed in [-1, 1].  An affine map from [a, b] is the caller's: subtract the constant (a + b) / 2 with
+ * he355_combine_scalars and pass in_scale * (b - a) / 2 as in_scale.  Arguments, levels, chunking, memory and refusals are
+ * he355_ckks_eval_poly's; one more refusal: a coefficient that becomes non-finite in a split.  The monomial tree cannot serve here: the
+ * monomial coefficients of a degree 15..63 cosine on [-K, K] are too ill-conditioned at this library's scales, and a Chebyshev step must
+ * subtract BEFORE the rescale -- which is he355_combine_scalars_rescale.
+ * The definition (tests/ckks_eval_mod_ref.py restates it on the oracle).  All scale arithmetic is IEEE double in the order written;
+ * scalar_residues is he355_ckks_scalar_residues, drop is he355_mod_switch_drop, q[l] is prime index l.
+ *   powers  m = 2^log_baby; babies T_1 .. T_(m-1), giants T_(m 2^j) while the index is <= the degree.  The needed set is
+ *           he355_ckks_eval_poly's, closed under the halves a = ceil(k/2), b = floor(k/2).  T_1 = the input, level L, scale s_1 = in_scale.
+ *           For k >= 2 in increasing order:  l = min(level_a, level_b);  W = s_a * s_b;
+ *             P = he355_multiply_relin(drop(T_a, l), drop(T_b, l), rescale = 0);
+ *             k even:  T_k = he355_combine_scalars_rescale(l, {P}, scalar 2, constant scalar_residues(l, -W));
+ *             k odd:   T_k = he355_combine_scalars_rescale(l, {P, T_1 read at level L}, scalars {2, scalar_residues(l, -(W / s_1))});
+ *           T_k lies at level l - 1 with scale s_k = W / q[l - 1].  (T_(a+b) = 2 T_a T_b - T_(a-b); with halves a - b is 0 or 1.)
+ *   eval(p, Lt, S), deg p < m (a leaf):  he355_ckks_eval_poly's leaf verbatim -- T = S * q[Lt], scalars (c_k * T) / s_k, constant c_0 * T --
+ *           as ONE he355_combine_scalars_rescale at level Lt + 1.
+ *   eval(p, Lt, S), otherwise (a node):  e = the largest giant <= deg p.  The split is in the Chebyshev basis: hi[0] = c_e;
+ *           lo = c_0 .. c_(e-1); for k = e + 1 .. deg in increasing order hi[k - e] = 2.0 * c_k and lo[2e - k] = lo[2e - k] - c_k; lo is
+ *           trimmed (a coefficient that cancels to 0.0 is zero).  Then he355_ckks_eval_poly's node rule unchanged, with g = T_e:
+ *           H = eval(hi, Lt + 1, T / s_g) and the product with rescale = 1; a constant hi is a one-term leaf of T_e; a constant lo is a
+ *           he355_combine_scalars with scalar 1 and the constant; otherwise he355_add.
+ *   depth   he355_ckks_eval_poly's formulas on the split above; the call is eval(p, L - depth, out_scale).
+ * The plan reuses he355_poly_plan_t: `rescales` counts the fused steps, `combinations` the he355_combine_scalars launches, pool_bytes
+ * includes the fused steps' row block. */
+int he355_ckks_eval_chebyshev_plan(const he355_ctx *ctx, int L, const double *h_coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
+                                   uint64_t n, he355_poly_plan_t *out);
+int he355_ckks_eval_chebyshev(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in /* [n][2][L][N] */, const double *h_coeffs, uint64_t n_coeffs, int log_baby,
+                              double in_scale, double out_scale, uint64_t *d_out /* [n][2][L - depth][N] */);
+/* he355_ckks_eval_mod: y_0 = p(u) by he355_ckks_eval_chebyshev, then r = double_angles (0..8) steps y <- 2 y^2 - 1.  The depth is
+ * depth(p) + r and must be below L; d_out lies at level L - depth(p) - r.
+ *   scales  l_0 = L - depth(p), l_j = l_0 - j.  S_r = out_scale; backwards S_(j-1) = sqrt(S_j * q[l_j]) (the IEEE square root); the
+ *           Chebyshev part runs at the target S_0.  Forwards s_0 = S_0, s_j = (s_(j-1) * s_(j-1)) / q[l_j].
+ *   step j  z = he355_multiply_relin(y, y, rescale = 1);  y_j = he355_combine_scalars(l_j, {z}, scalar 2, constant scalar_residues(l_j, -s_j)).
+ * The plan's out_scale is s_r, the scale d_out carries: out_scale up to rounding.  Its products and combinations include the steps', and
+ * reserved[0] holds double_angles.  With r = 0 the call gives he355_ckks_eval_chebyshev's bits.
+ * Use.  After he355_ckks_mod_raise a ciphertext holds t = m + q_0 * I with |I| < K.  Pass h_coeffs = the Chebyshev interpolant of
+ * cos((2 pi / 2^r) (K u - 1/4)) on [-1, 1] and in_scale = q_0 * K (then u = t / (q_0 K)); after the r double angles the result is
+ * cos(2 pi t / q_0 - pi / 2) = sin(2 pi t / q_0) ~ 2 pi m / q_0 at out_scale, so a message at scale Delta is read at scale
+ * out_scale * 2 pi Delta / q_0.  The C ABI takes coefficients only, so that no libm call is part of a bit-exact definition.
+ * The powers' scales follow s_k = s_a * s_b / q[l - 1]: they stay put when in_scale is about the size of the primes the powers rescale by
+ * and grow with k when it is far above them, until a scalar passes 2^126 and the call is refused -- so EvalMod's levels take primes near
+ * q_0 * K, as bootstrapping chains do (in_scale = 12 * q_0 over 45-bit primes is refused from degree 16 on). */
+int he355_ckks_eval_mod_plan(const he355_ctx *ctx, int L, const double *h_coeffs, uint64_t n_coeffs, int log_baby, double in_scale, double out_scale,
+                             int double_angles, uint64_t n, he355_poly_plan_t *out);
+int he355_ckks_eval_mod(he355_ctx *ctx, int L, uint64_t n, const uint64_t *d_in /* [n][2][L][N] */, const double *h_coeffs, uint64_t n_coeffs, int log_baby,
+                        double in_scale, double out_scale, int double_angles, uint64_t *d_out /* [n][2][L - depth - r][N] */);
+/* What the three calls above ran on this context since he355_device_init (or the last call with reset != 0).  he355_poly_stats does not
+ * move for them; he355_path_stats counts the products' key switches as for any he355_multiply_relin. */
+typedef struct he355_cheb_stats {
+    uint64_t calls;         /* he355_ckks_eval_chebyshev / he355_ckks_eval_mod calls with work                              */
+    uint64_t chunks;        /* chunks they walked                                                                           */
+    uint64_t products;      /* he355_multiply_relin calls they made, per chunk (the double angles' squares included)         */
+    uint64_t fused_steps;   /* combine-and-rescale sequences, per chunk; he355_combine_scalars_rescale: one per call         */
+    uint64_t combinations;  /* k_scalar_combine launches they made, per chunk (constant lows, double angles)                 */
+    uint64_t drops, adds;   /* he355_mod_switch_drop copies / he355_add calls they made, per chunk                           */
+    uint64_t double_angles; /* steps y <- 2 y^2 - 1, per chunk                                                               */
+} he355_cheb_stats_t;       /* 64 bytes */
+int he355_cheb_stats(he355_ctx *ctx, he355_cheb_stats_t *out, int reset);
 /* accumulateCKKS / accumulateBFV: in place log-tree sum of the first `count` slots; d_tmp: scratch slab of the same size.
  * count == 0 is the reference's else-branch (src/engine/seal_context.cpp:312-316, 341-344): every ciphertext is replaced by a
  * FRESH encryption of zero (Encryptor::encrypt_zero; needs the public key; L must be the top level, as SEAL returns a

@@ -56,6 +56,10 @@ class RaiseStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "fused_launches", "streaming_launches", "split_launches")] + [("reserved", C.c_uint64 * 3)]
 
 
+class ChebStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "products", "fused_steps", "combinations", "drops", "adds", "double_angles")]
+
+
 class PolyPlan(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("depth", "L_out", "min_scalar_bits", "degree")]
                 + [(k, C.c_uint64) for k in ("products", "combinations", "rescales", "drops", "adds", "powers", "chunks", "pool_bytes")]
@@ -220,6 +224,12 @@ def lib():
             "he355_ckks_mod_raise": (i32, [vp, i32, i32, i32, u64, vp, vp]),
             "he355_ckks_lift_centred": (i32, [vp, i32, u64, vp, vp]),
             "he355_raise_stats": (i32, [vp, C.POINTER(RaiseStats), i32]),
+            "he355_combine_scalars_rescale": (i32, [vp, i32, i32, u64, C.POINTER(Term), u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "he355_ckks_eval_chebyshev_plan": (i32, [vp, i32, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, u64, C.POINTER(PolyPlan)]),
+            "he355_ckks_eval_chebyshev": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, vp]),
+            "he355_ckks_eval_mod_plan": (i32, [vp, i32, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, i32, u64, C.POINTER(PolyPlan)]),
+            "he355_ckks_eval_mod": (i32, [vp, i32, u64, vp, C.POINTER(C.c_double), u64, i32, C.c_double, C.c_double, i32, vp]),
+            "he355_cheb_stats": (i32, [vp, C.POINTER(ChebStats), i32]),
             "he355_encrypt_zero": (i32, [vp, u64, u64, u64, vp]),
             "he355_set_zero_stream": (i32, [vp, u64, u64]),
             "he355_ntt_forward": (i32, [vp, vp, u64, u8p, u32]),
@@ -257,7 +267,7 @@ C_ABI_SYMBOLS = [
     "he355_relinearize", "he355_relinearize_rescale", "he355_multiply_accumulate", "he355_bfv_multiply_relin_accumulate", "he355_multiply_plain", "he355_add_plain",
     "he355_mod_switch_drop", "he355_bfv_mod_switch", "he355_bfv_add_plain", "he355_bfv_sub_plain", "he355_bfv_multiply_plain", "he355_bfv_noise_budget", "he355_bfv_transform_to_ntt", "he355_bfv_transform_from_ntt", "he355_bfv_plain_to_ntt",
     "he355_bfv_multiply_plain_ntt", "he355_bfv_multiply_plain_accumulate", "he355_bfv_multiply_monomial", "he355_bfv_expand_galois_elts", "he355_bfv_expand", "he355_bfv_merge", "he355_bfv_digit_count", "he355_bfv_decompose", "he355_bfv_decompose_ntt", "he355_bfv_compose", "he355_bfv_gadget_count", "he355_bfv_gadget_decompose", "he355_bfv_gadget_decompose_ntt", "he355_bfv_rgsw_encrypt", "he355_bfv_external_product", "he355_bfv_select", "he355_bfv_selector_encrypt", "he355_bfv_rgsw_encrypt_secret", "he355_bfv_rgsw_from_bfv", "he355_bfv_bytes_per_plain", "he355_bfv_unpack_bytes", "he355_bfv_unpack_bytes_ntt", "he355_bfv_pack_bytes", "he355_bfv_reply_bytes", "he355_bfv_reply_safe_bits", "he355_bfv_reply_compress", "he355_bfv_reply_decrypt", "he355_bfv_seeded_encrypt", "he355_bfv_seeded_selector_encrypt", "he355_bfv_seeded_restore", "he355_keygen_galois_seeded", "he355_set_galois_key_seeded", "he355_sum", "he355_set_public_key", "he355_set_secret_key", "he355_encrypt", "he355_decrypt", "he355_keygen_relin", "he355_keygen_galois", "he355_ckks_encode", "he355_ckks_decode",
-    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_ckks_encode_complex", "he355_ckks_decode_complex", "he355_ckks_decode_complex_slots", "he355_ckks_complex_unit", "he355_ckks_complex_scalar_residues", "he355_combine_scalars_complex", "he355_ckks_eval_poly_complex_plan", "he355_ckks_eval_poly_complex", "he355_ckks_mod_raise", "he355_ckks_lift_centred", "he355_raise_stats", "he355_encrypt_zero", "he355_set_zero_stream",
+    "he355_bfv_encode", "he355_bfv_decode", "he355_ckks_decode_slots", "he355_bfv_decode_slots", "he355_host_alloc", "he355_host_free", "he355_rescale", "he355_apply_galois", "he355_rotate", "he355_rotate_add", "he355_rotate_each", "he355_rotate_sum", "he355_accumulate", "he355_apply_galois_hoisted", "he355_rotate_hoisted", "he355_rotate_hoisted_plain_sum", "he355_rotate_hoisted_plain_sum_lazy", "he355_plain_extend_special", "he355_linear_transform_bsgs", "he355_linear_transform_bsgs_scratch_bytes", "he355_hoist_stats", "he355_hoist_release_keys", "he355_combine_scalars", "he355_ckks_scalar_residues", "he355_ckks_eval_poly_plan", "he355_ckks_eval_poly", "he355_poly_stats", "he355_ckks_encode_complex", "he355_ckks_decode_complex", "he355_ckks_decode_complex_slots", "he355_ckks_complex_unit", "he355_ckks_complex_scalar_residues", "he355_combine_scalars_complex", "he355_ckks_eval_poly_complex_plan", "he355_ckks_eval_poly_complex", "he355_ckks_mod_raise", "he355_ckks_lift_centred", "he355_raise_stats", "he355_combine_scalars_rescale", "he355_ckks_eval_chebyshev_plan", "he355_ckks_eval_chebyshev", "he355_ckks_eval_mod_plan", "he355_ckks_eval_mod", "he355_cheb_stats", "he355_encrypt_zero", "he355_set_zero_stream",
     "he355_ntt_forward", "he355_ntt_inverse", "he355_timer_begin", "he355_timer_end", "he355_probe_dominant_kernel", "he355_clock_probe_begin", "he355_clock_probe_end", "he355_set_chunk", "he355_set_latency_max", "he355_set_level_walk", "he355_set_lds_max", "he355_mem_info", "he355_alloc_stats", "he355_pool_trim", "he355_path_stats", "he355_bfv_route_stats", "he355_bfv_multiply_stats", "he355_bridge_abi", "he355_bridge_group_load_bytes",
 ]
 
@@ -892,6 +902,52 @@ class Context:
         _check(lib().he355_raise_stats(self.h, C.byref(st), int(reset)))
         return {k: int(getattr(st, k)) for k, _ in RaiseStats._fields_ if k != "reserved"}
 
+    # ---- EvalMod: the fused combine-and-rescale step, Chebyshev evaluation, double angles ----
+    def combine_scalars_rescale(self, L, size, n, terms, scalars, out, const=None):
+        """out [n][size][L - 1][N] = rescale(combine_scalars(...)) bit for bit, without the combined slab; arguments as combine_scalars"""
+        tt = (Term * max(1, len(terms)))(*[Term(getattr(b.ptr, "value", b.ptr), int(lv), 0) for b, lv in terms])
+        flat = [int(v) for row in scalars for v in row]
+        sc = (C.c_uint64 * max(1, len(flat)))(*flat)
+        cc = (C.c_uint64 * max(1, L))(*[int(v) for v in const]) if const is not None else None
+        _check(lib().he355_combine_scalars_rescale(self.h, L, size, n, tt, len(terms), sc, cc, out.ptr))
+
+    @staticmethod
+    def _plan_dict(pl):
+        d = {k: getattr(pl, k) for k, _ in PolyPlan._fields_ if k not in ("reserved", "power_mask")}
+        d["powers_computed"] = [k for k in range(1024) if (pl.power_mask[k // 64] >> (k % 64)) & 1]
+        d["double_angles"] = int(pl.reserved[0])
+        return d
+
+    def ckks_eval_chebyshev_plan(self, L, coeffs, log_baby, in_scale, out_scale, n=1) -> dict:
+        """what ckks_eval_chebyshev would do (he355_poly_plan_t; `rescales` counts the fused steps)"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        pl = PolyPlan()
+        _check(lib().he355_ckks_eval_chebyshev_plan(self.h, L, cs, len(coeffs), log_baby, in_scale, out_scale, n, C.byref(pl)))
+        return self._plan_dict(pl)
+
+    def ckks_eval_chebyshev(self, L, n, inp, coeffs, log_baby, in_scale, out_scale, out):
+        """out [n][2][L - depth][N] = sum_k coeffs[k] T_k(in) at the nominal scale out_scale; inp [n][2][L][N] at in_scale, slots in [-1, 1]"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        _check(lib().he355_ckks_eval_chebyshev(self.h, L, n, inp.ptr, cs, len(coeffs), log_baby, in_scale, out_scale, out.ptr))
+
+    def ckks_eval_mod_plan(self, L, coeffs, log_baby, in_scale, out_scale, double_angles, n=1) -> dict:
+        """what ckks_eval_mod would do; out_scale: the scale the output carries (s_r)"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        pl = PolyPlan()
+        _check(lib().he355_ckks_eval_mod_plan(self.h, L, cs, len(coeffs), log_baby, in_scale, out_scale, double_angles, n, C.byref(pl)))
+        return self._plan_dict(pl)
+
+    def ckks_eval_mod(self, L, n, inp, coeffs, log_baby, in_scale, out_scale, double_angles, out):
+        """the Chebyshev polynomial, then double_angles steps y <- 2 y^2 - 1; out [n][2][L - depth - double_angles][N]"""
+        cs = (C.c_double * max(1, len(coeffs)))(*[float(c) for c in coeffs])
+        _check(lib().he355_ckks_eval_mod(self.h, L, n, inp.ptr, cs, len(coeffs), log_baby, in_scale, out_scale, double_angles, out.ptr))
+
+    def cheb_stats(self, reset: bool = False) -> dict:
+        """what combine_scalars_rescale, ckks_eval_chebyshev and ckks_eval_mod ran (he355_cheb_stats)"""
+        st = ChebStats()
+        _check(lib().he355_cheb_stats(self.h, C.byref(st), int(reset)))
+        return {k: int(getattr(st, k)) for k, _ in ChebStats._fields_}
+
     def hoist_release_keys(self):
         _check(lib().he355_hoist_release_keys(self.h))
 
@@ -988,6 +1044,13 @@ class Context:
         ms = C.c_float()
         _check(lib().he355_timer_end(self.h, C.byref(ms)))
         return float(ms.value)
+
+
+def eval_mod_coeffs(K: int, r: int, degree: int) -> list:
+    """The Chebyshev coefficients he355_ckks_eval_mod takes: the interpolant of cos((2 pi / 2^r) (K u - 1/4)) on [-1, 1] at degree + 1
+    Chebyshev points (numpy's chebinterpolate).  With in_scale = q_0 K and r double angles the call computes sin(2 pi t / q_0)."""
+    w = 2.0 * np.pi / float(1 << r)
+    return [float(c) for c in np.polynomial.chebyshev.chebinterpolate(lambda u: np.cos(w * (K * u - 0.25)), degree)]
 
 
 def process_alloc_stats() -> dict:

@@ -5,9 +5,10 @@
 // [n_terms][L], the constant [L] -- takes one region of the table ring (table_ring): calls may follow each other without a sync.
 // halves = 2: he355_combine_scalars_complex -- scalars [n_terms][2][L], the constant [2][L], one launch of k_scalar_combine_cplx.
 struct PolyTerm { const u64 *p; int L; };
-static void combine_scalars(DeviceContext &d, int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out, int halves = 1)
+// upload_combine_table: the table alone (the fused step of ckks_eval_mod.inc reads the same words).  count: he355_poly_stats takes the launch.
+struct CombineTableDev { const u64 *terms, *scalars, *cst; };
+static CombineTableDev upload_combine_table(DeviceContext &d, int L, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, int halves = 1)
 {
-    d.use();
     const size_t Lh = (size_t)L * (size_t)halves;
     const size_t t_words = 2 * (size_t)n_terms, s_words = (size_t)n_terms * Lh, words = t_words + s_words + (h_const ? Lh : 0);
     std::vector<u64> h(words);
@@ -20,20 +21,30 @@ static void combine_scalars(DeviceContext &d, int L, int size, u64 n, const Poly
     const size_t bytes = (words * 8 + 255) & ~(size_t)255;
     u64 *d_tab = reinterpret_cast<u64 *>(d.table_ring(bytes));
     HIPCHECK(hipMemcpy(d_tab, h.data(), words * 8, hipMemcpyHostToDevice));
+    return CombineTableDev{d_tab, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr};
+}
+static void combine_scalars(DeviceContext &d, int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *out, int halves = 1,
+                            bool count = true)
+{
+    d.use();
+    const CombineTableDev t = upload_combine_table(d, L, terms, n_terms, h_scalars, h_const, halves);
     if (halves == 2) {
-        ++d.counters().poly.complex_combinations;
-        launch_scalar_combine_cplx(d.batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+        if (count) ++d.counters().poly.complex_combinations;
+        launch_scalar_combine_cplx(d.batch_env(0, true), L, size, n, t.terms, n_terms, t.scalars, t.cst, out);
     } else {
-        ++d.counters().poly.combinations;
-        launch_scalar_combine(d.batch_env(0, true), L, size, n, d_tab, n_terms, d_tab + t_words, h_const ? d_tab + t_words + s_words : nullptr, out);
+        if (count) ++d.counters().poly.combinations;
+        launch_scalar_combine(d.batch_env(0, true), L, size, n, t.terms, n_terms, t.scalars, t.cst, out);
     }
     HIPCHECK(hipGetLastError());
 }
+static void combine_scalars_rescale(DeviceContext &d, int L, int size, u64 n, const PolyTerm *terms, u64 n_terms, const u64 *h_scalars, const u64 *h_const, u64 *row,
+                                    u64 *out); // (ckks_eval_mod.inc)
 
 // The walk of a polynomial plan (poly_args.h), chunk by chunk in the key-switch chunk: he355_ckks_eval_poly and he355_ckks_eval_poly_complex.
 // The power store and the temporaries are ONE pool block sized for the chunk, taken after the key check and before the first launch; every
-// step is queued on the one stream.
-static void run_poly_plan(he355_ctx *c, const PolyPlan &pl, const char *what, int L, u64 n, const u64 *in, u64 *out)
+// step is queued on the one stream.  cheb: a plan of he355_ckks_eval_chebyshev / he355_ckks_eval_mod -- its steps count in he355_cheb_stats and
+// he355_poly_stats does not move; its fused steps (kPolyFused) share the row block at the plan's row_off.
+static void run_poly_plan(he355_ctx *c, const PolyPlan &pl, const char *what, int L, u64 n, const u64 *in, u64 *out, bool cheb = false)
 {
     DeviceContext &d = dev(c);
     d.use();
@@ -45,10 +56,12 @@ static void run_poly_plan(he355_ctx *c, const PolyPlan &pl, const char *what, in
     const size_t N = P.N;
     Indexer pw{};
     pw.b1 = 1; pw.pairwise = 1;
-    ++d.counters().poly.calls;
+    he355_poly_stats_t &ps = d.counters().poly;
+    he355_cheb_stats_t &cs = d.counters().cheb;
+    ++(cheb ? cs.calls : ps.calls);
     for (u64 off = 0; off < n; off += chunk) {
         const u64 nc = std::min<u64>(chunk, n - off);
-        ++d.counters().poly.chunks;
+        ++(cheb ? cs.chunks : ps.chunks);
         auto at = [&](int b) -> u64 * {
             const PolyBuf &B = pl.bufs[(size_t)b];
             if (B.kind == 0) return const_cast<u64 *>(in) + off * 2 * (size_t)B.L * N;
@@ -58,25 +71,33 @@ static void run_poly_plan(he355_ctx *c, const PolyPlan &pl, const char *what, in
         for (const PolyStep &s : pl.steps) {
             switch (s.op) {
             case kPolyMulRelin:
-                ++d.counters().poly.products;
-                d.multiply_relin(s.L, nc, at(s.a), at(s.b), pw, true, at(s.dst));
+                ++(cheb ? cs.products : ps.products);
+                if (s.angle) ++cs.double_angles;
+                d.multiply_relin(s.L, nc, at(s.a), at(s.b), pw, s.rescale, at(s.dst));
                 break;
             case kPolyDrop:
-                ++d.counters().poly.drops;
+                ++(cheb ? cs.drops : ps.drops);
                 d.mod_switch_drop(pl.bufs[(size_t)s.a].L, s.L, nc * 2, at(s.a), at(s.dst));
                 break;
             case kPolyRescale:
-                ++d.counters().poly.rescales;
+                ++ps.rescales;
                 d.rescale(s.L, 2, nc, at(s.a), at(s.dst));
                 break;
             case kPolyAdd:
-                ++d.counters().poly.adds;
+                ++(cheb ? cs.adds : ps.adds);
                 d.addsub(s.L, 2, nc, at(s.a), at(s.b), pw, at(s.dst), false);
                 break;
             case kPolyCombine: {
                 std::vector<PolyTerm> t;
                 for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
-                combine_scalars(d, s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst), s.cplx ? 2 : 1);
+                if (cheb) ++cs.combinations;
+                combine_scalars(d, s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), at(s.dst), s.cplx ? 2 : 1, !cheb);
+                break;
+            }
+            case kPolyFused: {
+                std::vector<PolyTerm> t;
+                for (int b : s.terms) t.push_back({at(b), pl.bufs[(size_t)b].L});
+                combine_scalars_rescale(d, s.L, 2, nc, t.data(), t.size(), s.scalars.data(), s.cst.empty() ? nullptr : s.cst.data(), blk.get() + pl.row_off * nc, at(s.dst));
                 break;
             }
             }

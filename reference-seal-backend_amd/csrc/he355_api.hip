@@ -29,6 +29,7 @@
 #include "hoist_args.h"
 #include "ntt_core.h"
 #include "poly_args.h"
+#include "cheb_args.h"
 #include "raise_args.h"
 #include "rotation_plan.h"
 #include "client/he_client.h"
@@ -289,6 +290,7 @@ public:
         he355_hoist_stats_t hoist{};
         he355_poly_stats_t poly{};
         he355_raise_stats_t raise{};
+        he355_cheb_stats_t cheb{};
         he355_bfv_route_stats_t routes{};
         he355_bfv_multiply_stats_t mul_routes{};
     };
@@ -305,6 +307,7 @@ public:
     he355_bfv_route_stats_t bfv_route_stats(bool reset) { return take_stats(count_.routes, reset); }
     he355_poly_stats_t poly_stats(bool reset) { return take_stats(count_.poly, reset); }
     he355_raise_stats_t raise_stats(bool reset) { return take_stats(count_.raise, reset); }
+    he355_cheb_stats_t cheb_stats(bool reset) { return take_stats(count_.cheb, reset); }
     size_t pool_trim() { sync(); return pool_.trim(); }
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
@@ -2318,5 +2321,6 @@ int he355_set_chunk(he355_ctx *c, uint64_t ops)
 #include "hoisted_rotations.inc"
 #include "ckks_poly_raise.inc"
 #include "ckks_complex.inc"
+#include "ckks_eval_mod.inc"
 #include "bfv_operands.inc"
 #include "bfv_pir.inc"

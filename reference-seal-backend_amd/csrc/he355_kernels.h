@@ -237,6 +237,8 @@ HE355_FWD(launch_bsgs_ident)
 HE355_FWD(launch_bsgs_inner)
 HE355_FWD(launch_scalar_combine)
 HE355_FWD(launch_scalar_combine_cplx)
+HE355_FWD(launch_scalar_combine_row)
+HE355_FWD(launch_floor_rows_combine)
 HE355_FWD(launch_ckks_encode_cplx)
 HE355_FWD(launch_ckks_gather_cplx)
 HE355_FWD(launch_raise_lift)

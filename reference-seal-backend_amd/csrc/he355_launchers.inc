@@ -105,6 +105,12 @@ void launch_bsgs_inner(const KernelEnv &env, int L, u64 n_ops, const u64 *store,
 // he355_combine_scalars (he355_kernels_poly.hip): out [n][size][L][N] = sum_t scalars[t][i] * term_t + (polynomial 0: cst[i]); d_terms [n_terms]
 // device pairs of words {the term's slab [n][size][L_t][N], L_t >= L}, d_scalars [n_terms][L], d_const [L] or null -- all canonical
 void launch_scalar_combine(const KernelEnv &env, int L, int size, u64 n, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *out);
+// he355_combine_scalars_rescale (he355_kernels_cheb.hip; arithmetic: cheb_core.h): the same tables as launch_scalar_combine, read from ciphertext
+// op_off of the terms' slabs on.  Row L - 1 of the combination alone -> row [n size][N]; then, behind the inverse row pass of `row` and
+// launch_floor_cols(prime L - 1 -> L - 1 targets) into cols [n size][L - 1][N], out [n][size][L - 1][N] = (combination - NTT(cols)) * q_(L-1)^-1
+void launch_scalar_combine_row(const KernelEnv &env, int L, int size, u64 n, u64 op_off, const void *d_terms, u64 n_terms, const u64 *d_scalars, const u64 *d_const, u64 *row);
+void launch_floor_rows_combine(const KernelEnv &env, int L, int size, u64 n, u64 op_off, const u64 *cols, const void *d_terms, u64 n_terms, const u64 *d_scalars,
+                               const u64 *d_const, u64 *out);
 // ---- complex CKKS slots (he355_kernels_cplx.hip; arithmetic: cplx_core.h) --------------------------------------------------------------------
 // he355_combine_scalars_complex: launch_scalar_combine with d_scalars [n_terms][2][L] and d_const [2][L] or null, the half picked by bit
 // (log2 N - 2) of the NTT index

@@ -34,10 +34,10 @@ inline void poly_scalar_residues(const Params &p, const std::string &w, int L, d
 // ---- he355_combine_scalars -----------------------------------------------------------------------------------------------------------
 // True: n == 0, or no term and no constant -- the call touches nothing.  halves = 2: he355_combine_scalars_complex under its own name --
 // scalars [n_terms][2][L], cst [2][L], every other rule the same.
-inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const he355_term *terms, u64 n_terms, const u64 *scalars, const u64 *cst, const u64 *out,
-                                 int halves = 1)
+// out_rows: the rows of a polynomial of `out` (he355_combine_scalars_rescale, cheb_args.h, writes L - 1 of them under its own name `w`).
+inline bool plan_combine_scalars(const Params &p, const std::string &w, int L, int size, u64 n, const he355_term *terms, u64 n_terms, const u64 *scalars, const u64 *cst,
+                                 const u64 *out, int halves, int out_rows)
 {
-    const std::string w(halves == 2 ? "he355_combine_scalars_complex" : "he355_combine_scalars");
     check_level(p, w, L);
     if (size < 2 || size > 3) throw std::invalid_argument(w + ": ciphertext size must be 2 or 3");
     if (n_terms > ((u64)1 << 20)) throw std::invalid_argument(w + ": too many terms for one call (at most 2^20)");
@@ -51,8 +51,8 @@ inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const 
         for (int i = 0; i < halves * L; ++i)
             if (cst[i] >= p.primes[i % L].q) throw std::invalid_argument(w + ": the constant is not a canonical residue");
     // every slab in words, formed in 128 bits: 2^60 words (2^63 bytes) is the most one may span
-    const u128 cap = (u128)1 << 60, out_w = (u128)n * (u128)size * (u128)L * p.N;
-    if (n > cap || out_w > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
+    const u128 cap = (u128)1 << 60, out_w = (u128)n * (u128)size * (u128)out_rows * p.N;
+    if (n > cap || out_w > cap || (u128)n * (u128)size * (u128)L * p.N > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
     for (u64 t = 0; t < n_terms; ++t)
         if ((u128)n * (u128)size * (u128)terms[t].L * p.N > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
     if (n == 0 || (n_terms == 0 && !cst)) return true;
@@ -66,11 +66,17 @@ inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const 
     }
     return false;
 }
+inline bool plan_combine_scalars(const Params &p, int L, int size, u64 n, const he355_term *terms, u64 n_terms, const u64 *scalars, const u64 *cst, const u64 *out,
+                                 int halves = 1)
+{
+    return plan_combine_scalars(p, halves == 2 ? "he355_combine_scalars_complex" : "he355_combine_scalars", L, size, n, terms, n_terms, scalars, cst, out, halves, L);
+}
 
 // ---- he355_ckks_eval_poly --------------------------------------------------------------------------------------------------------------
 // A buffer of the call: [nc][2][L][N] per chunk of nc ciphertexts.  kind 0: d_in, 1: d_out, 2: the pool block at word `off` * nc.
 struct PolyBuf { int kind; u64 off; int L; };
-enum PolyOp { kPolyMulRelin, kPolyDrop, kPolyCombine, kPolyRescale, kPolyAdd };
+enum PolyOp { kPolyMulRelin, kPolyDrop, kPolyCombine, kPolyRescale, kPolyAdd, kPolyFused }; // kPolyFused: he355_combine_scalars_rescale at L, dst at L - 1
+enum PolyBasis { kBasisMonomial = 0, kBasisChebyshev = 1 };
 struct PolyStep {
     PolyStep(PolyOp o, int l) : op(o), L(l) {}
     PolyOp op;
@@ -80,12 +86,15 @@ struct PolyStep {
     std::vector<u64> scalars;  // ... [terms][L] residues ...
     std::vector<u64> cst;      // ... and the constant [L], empty: none
     bool cplx = false;         // he355_ckks_eval_poly_complex: scalars [terms][2][L], cst [2][L] (k_scalar_combine_cplx)
+    bool rescale = true;       // kPolyMulRelin: with the rescale (a Chebyshev power's product goes without: dst at L)
+    bool angle = false;        // kPolyMulRelin: the square of a double-angle step of he355_ckks_eval_mod
 };
 struct PolyPlan {
     he355_poly_plan_t info{};
     std::vector<PolyBuf> bufs;
     std::vector<PolyStep> steps;
     u64 words_per_ct = 0; // pool words per ciphertext of a chunk
+    u64 row_off = 0;      // the Chebyshev basis: word `row_off` * nc of the pool block starts the fused steps' row block [nc][2][N]
     bool empty = false;   // n == 0
 };
 
@@ -98,7 +107,8 @@ inline int poly_clog2(u64 k) // ceil(log2 k), k >= 1
 
 class PolyPlanner {
 public:
-    PolyPlanner(const Params &p, const std::string &w, int L, int log_baby, double in_scale, bool cplx = false) : P(p), w_(w), L_(L), m_((u64)1 << log_baby), cplx_(cplx)
+    PolyPlanner(const Params &p, const std::string &w, int L, int log_baby, double in_scale, bool cplx = false, int basis = kBasisMonomial)
+        : P(p), w_(w), L_(L), m_((u64)1 << log_baby), cplx_(cplx), cheb_(basis == kBasisChebyshev)
     {
         level_[1] = L;
         scale_[1] = in_scale;
@@ -126,6 +136,26 @@ public:
         while (2 * e <= deg) e *= 2;
         return e;
     }
+    // p = lo + (the basis element of e) * hi at e = the largest giant <= deg p; lo trimmed.  Monomials: the two halves of the list.  The
+    // Chebyshev basis (T_k = 2 T_e T_(k-e) - T_(2e-k) for k > e; 2e > deg): hi[0] = c_e, and for k = e + 1 .. deg in increasing order
+    // hi[k - e] = 2.0 * c_k, lo[2e - k] = lo[2e - k] - c_k.  A coefficient that becomes non-finite here is refused.
+    void split(const Poly &p, u64 e, Poly &hi, Poly &lo) const
+    {
+        if (!cheb_) {
+            hi.assign(p.begin() + e, p.end());
+            lo = trimmed(p.data(), e);
+            return;
+        }
+        hi.assign(p.size() - e, Coef{0.0, 0.0});
+        lo.assign(p.begin(), p.begin() + e);
+        hi[0] = p[e];
+        for (u64 k = e + 1; k < p.size(); ++k) {
+            hi[k - e] = {2.0 * p[k].re, 0.0};
+            lo[2 * e - k].re = lo[2 * e - k].re - p[k].re;
+            if (!std::isfinite(hi[k - e].re) || !std::isfinite(lo[2 * e - k].re)) throw std::invalid_argument(w_ + ": a coefficient becomes non-finite in the Chebyshev split");
+        }
+        lo = trimmed(lo.data(), e);
+    }
     int depth(const Poly &p) const // deg p >= 1
     {
         const u64 deg = p.size() - 1;
@@ -136,7 +166,8 @@ public:
             return 1 + d;
         }
         const u64 e = giant_below(deg);
-        const Poly hi(p.begin() + e, p.end()), lo = trimmed(p.data(), e);
+        Poly hi, lo;
+        split(p, e, hi, lo);
         const int dh = hi.size() == 1 ? 1 + poly_clog2(e) : 1 + std::max(depth(hi), poly_clog2(e));
         return lo.size() >= 2 ? std::max(dh, depth(lo)) : dh;
     }
@@ -150,7 +181,8 @@ public:
         }
         const u64 e = giant_below(deg);
         need_[e] = true;
-        const Poly hi(p.begin() + e, p.end()), lo = trimmed(p.data(), e);
+        Poly hi, lo;
+        split(p, e, hi, lo);
         if (hi.size() >= 2) mark(hi);
         if (lo.size() >= 2) mark(lo);
     }
@@ -165,6 +197,10 @@ public:
             const u64 f = k / 2, c = k - f;
             const int l = std::min(level_[f], level_[c]);
             if (l < 2) throw std::invalid_argument(w_ + ": the chain is too short for power " + std::to_string(k));
+            if (cheb_) {
+                cheb_power(pl, k, c, f, l);
+                continue;
+            }
             const int a = dropped(pl, f, l), b = dropped(pl, c, l);
             level_[k] = l - 1;
             scale_[k] = scale_[f] * scale_[c] / (double)P.primes[l - 1].q;
@@ -188,7 +224,8 @@ public:
             return leaf(pl, t, !p[0].zero(), p[0].re * T, p[0].im * T, Lt, dst);
         }
         const u64 e = giant_below(deg);
-        const Poly hi(p.begin() + e, p.end()), lo = trimmed(p.data(), e);
+        Poly hi, lo;
+        split(p, e, hi, lo);
         const bool sum = !lo.empty();
         int prod;
         if (hi.size() == 1) {
@@ -221,8 +258,64 @@ public:
         return out;
     }
     u64 words() const { return words_; }
+    // the fused steps' row block [nc][2][N], behind everything taken so far; returns its word offset per ciphertext
+    u64 take_row_block()
+    {
+        const u64 at = words_;
+        words_ += 2 * (u64)P.N;
+        return at;
+    }
+    // he355_ckks_eval_mod: r steps y <- 2 y^2 - 1 from buffer `y` at level l0 and scale s0; step j squares with the rescale to level
+    // l_j = l0 - j, s_j = (s_(j-1) * s_(j-1)) / q[l_j], then ONE combination 2 z - s_j at l_j (the last one into `dst`).  Returns s_r.
+    double double_angles(PolyPlan &pl, int y, int l0, double s0, int r, int dst)
+    {
+        double s = s0;
+        for (int j = 1; j <= r; ++j) {
+            const int lj = l0 - j;
+            s = (s * s) / (double)P.primes[lj].q;
+            const int z = add_buf(pl, 2, lj);
+            PolyStep m{kPolyMulRelin, lj + 1};
+            m.a = y; m.b = y; m.dst = z; m.angle = true;
+            push(pl, std::move(m));
+            PolyStep c{kPolyCombine, lj};
+            c.terms = {z};
+            c.scalars.assign((size_t)lj, 2);
+            residues(lj, -s, 0.0, c.cst);
+            c.dst = y = j == r ? dst : add_buf(pl, 2, lj);
+            push(pl, std::move(c));
+        }
+        return s;
+    }
 
 private:
+    // T_k = 2 T_a T_b - T_(a-b), a = ceil(k / 2), b = floor(k / 2) at the common level l: the product WITHOUT its rescale, at scale
+    // W = s_a * s_b, then ONE fused step 2 P - W (k even: a - b = 0, T_0 = 1 at scale W) or 2 P - (W / s_1) T_1 (k odd: a - b = 1, the
+    // input read at its own level L).  T_k lies at level l - 1 with scale s_k = W / q[l - 1].
+    void cheb_power(PolyPlan &pl, u64 k, u64 a, u64 b, int l)
+    {
+        const double W = scale_[a] * scale_[b];
+        const int da = dropped(pl, a, l), db = dropped(pl, b, l);
+        const int prod = add_buf(pl, 2, l);
+        PolyStep m{kPolyMulRelin, l};
+        m.a = da; m.b = db; m.dst = prod; m.rescale = false;
+        push(pl, std::move(m));
+        level_[k] = l - 1;
+        scale_[k] = W / (double)P.primes[l - 1].q;
+        buf_[k] = add_buf(pl, 2, l - 1);
+        PolyStep s{kPolyFused, l};
+        s.terms = {prod};
+        s.scalars.assign((size_t)l, 2);
+        if (k & 1) {
+            s.terms.push_back(buf_[1]);
+            residues(l, -(W / scale_[1]), 0.0, s.scalars);
+        } else {
+            residues(l, -W, 0.0, s.cst);
+        }
+        s.dst = buf_[k];
+        push(pl, std::move(s));
+        ++pl.info.powers;
+        pl.info.power_mask[k / 64] |= (u64)1 << (k % 64);
+    }
     int add_buf(PolyPlan &pl, int kind, int L)
     {
         pl.bufs.push_back({kind, kind == 2 ? words_ : 0, L});
@@ -279,6 +372,13 @@ private:
                 }
         }
         if (has_const) residues(Lc, cst_re, cst_im, s.cst);
+        if (cheb_) { // the same leaf as ONE he355_combine_scalars_rescale: no slab at Lt + 1
+            s.op = kPolyFused;
+            const int o = out_buf(pl, dst, Lt);
+            s.dst = o;
+            push(pl, std::move(s));
+            return o;
+        }
         const int tmp = add_buf(pl, 2, Lc);
         s.dst = tmp;
         push(pl, std::move(s));
@@ -296,6 +396,7 @@ private:
         case kPolyCombine: ++pl.info.combinations; break;
         case kPolyRescale: ++pl.info.rescales; break;
         case kPolyAdd: ++pl.info.adds; break;
+        case kPolyFused: ++pl.info.rescales; break; // (the Chebyshev plans: `rescales` counts the fused steps)
         }
         pl.steps.push_back(std::move(s));
     }
@@ -303,7 +404,7 @@ private:
     const std::string w_;
     const int L_;
     const u64 m_;
-    const bool cplx_;
+    const bool cplx_, cheb_;
     bool need_[1024] = {};
     int level_[1024] = {}, buf_[1024] = {};
     double scale_[1024] = {};
@@ -314,8 +415,13 @@ private:
 // `chunk`: the context's batch chunk (info.chunks, and the caller's bound of the pool bytes); in / out may be null for a plan alone
 // (check_ptrs false: he355_ckks_eval_poly_plan)
 // im_coeffs: the imaginary parts of he355_ckks_eval_poly_complex (cplx true; both lists are needed), null for the real call
+// basis: kBasisChebyshev -- he355_ckks_eval_chebyshev (cheb_args.h; real coefficients): the powers are T_k, every power and every leaf ends in
+// ONE he355_combine_scalars_rescale (kPolyFused), a node splits in the Chebyshev basis; the depth formulas, the node rule and every refusal
+// are the monomial call's.  double_angles = r > 0: he355_ckks_eval_mod -- the polynomial at the scale the r steps y <- 2 y^2 - 1 need, then
+// those steps; the depth grows by r and info.out_scale is the scale the steps arrive at.
 inline PolyPlan plan_eval_poly(const Params &p, const char *what, int L, u64 n, const u64 *in, const double *coeffs, u64 n_coeffs, int log_baby, double in_scale,
-                               double out_scale, const u64 *out, bool check_ptrs, u64 chunk, const double *im_coeffs = nullptr, bool cplx = false)
+                               double out_scale, const u64 *out, bool check_ptrs, u64 chunk, const double *im_coeffs = nullptr, bool cplx = false,
+                               int basis = kBasisMonomial, int double_angles = 0)
 {
     const std::string w(what);
     if (p.scheme != kSchemeCKKS) throw std::invalid_argument(w + ": polynomial evaluation is a CKKS operation");
@@ -329,9 +435,10 @@ inline PolyPlan plan_eval_poly(const Params &p, const char *what, int L, u64 n, 
     if (!std::isfinite(in_scale) || !std::isfinite(out_scale) || in_scale <= 0 || out_scale <= 0) throw std::invalid_argument(w + ": a scale must be finite and positive");
     const PolyPlanner::Poly poly = PolyPlanner::trimmed(coeffs, cplx ? im_coeffs : nullptr, n_coeffs);
     if (poly.size() < 2) throw std::invalid_argument(w + ": no non-zero coefficient above c_0 (nothing to evaluate on a ciphertext)");
-    PolyPlanner pp(p, w, L, log_baby, in_scale, cplx);
+    PolyPlanner pp(p, w, L, log_baby, in_scale, cplx, basis);
     PolyPlan pl;
-    pl.info.depth = pp.depth(poly);
+    const int pdepth = pp.depth(poly);
+    pl.info.depth = pdepth + double_angles;
     pl.info.degree = (int32_t)poly.size() - 1;
     if (pl.info.depth >= L) throw std::invalid_argument(w + ": the evaluation takes " + std::to_string(pl.info.depth) + " levels, the input has " + std::to_string(L) + " (depth must be below L)");
     pl.info.L_out = L - pl.info.depth;
@@ -341,7 +448,18 @@ inline PolyPlan plan_eval_poly(const Params &p, const char *what, int L, u64 n, 
     pp.build_powers(pl);
     const int dst = (int)pl.bufs.size();
     pl.bufs.push_back({1, 0, pl.info.L_out});
-    pp.eval(pl, poly, pl.info.L_out, out_scale, dst);
+    if (double_angles > 0) { // S_r = out_scale, S_(j-1) = sqrt(S_j * q[l_j]) backwards; the polynomial runs at the target S_0
+        const int l0 = L - pdepth;
+        double S = out_scale;
+        for (int j = double_angles; j >= 1; --j) S = std::sqrt(S * (double)p.primes[l0 - j].q);
+        if (!std::isfinite(S) || S <= 0) throw std::invalid_argument(w + ": a scale must be finite and positive");
+        const int y = pp.eval(pl, poly, l0, S, -1);
+        pl.info.out_scale = pp.double_angles(pl, y, l0, S, double_angles, dst);
+        pl.info.reserved[0] = (u64)double_angles;
+    } else {
+        pp.eval(pl, poly, pl.info.L_out, out_scale, dst);
+    }
+    if (basis == kBasisChebyshev) pl.row_off = pp.take_row_block();
     pl.words_per_ct = pp.words();
     const u128 cap = (u128)1 << 60, in_w = (u128)n * 2 * (u128)L * p.N, out_w = (u128)n * 2 * (u128)pl.info.L_out * p.N;
     if (n > cap || in_w > cap) throw std::invalid_argument(w + ": the ciphertexts span more than 2^60 words");
